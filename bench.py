@@ -35,16 +35,24 @@ file starts that launcher itself, as a child (``launch_ranks``; the parent touch
       one per path cluster: no data-path collective), value = points of all ranks /
       max-over-ranks time, ``"scaling": "weak"``.
 
+A plain run sets up, warms up, times the K steps and prints the line; on one GPU nothing else runs (sharded runs still
+compare their posterior with the single-GPU path, ``shard_check``, since a disagreement fails the run).
+  --dump-outputs DIR — after the timed steps, the posterior mean and variance of the last timed step (what
+                 ``predict`` hands its caller) go to DIR/mean.npy and DIR/var.npy (float64; float32 for --dtype
+                 float32).  The inputs come from a fixed seed, so two builds can be compared output for output.
+  --full       — after the timed steps also measure fit_predict_one_pass, pcie_inclusive_ms_per_step, profile_flag,
+                 microbench and cpu_baseline (below); without it those keys are null or absent.
+
 Rank 0 prints ONE JSON line.  Besides the contract keys it carries
   roofline     — the dominant kernel (trailing SYRK of the blocked Cholesky, fp64 MFMA):
                  algorithmic flops n(n+1)nb per launch / hipEvent time per launch, both
                  summed over the launches of that kernel in the timed steps (library events
                  on the library's stream, GPX_FLAG_PROFILE; the last few, under-filled
                  updates of a fit run as 64-tiles — another kernel — and are not counted)
-  fit_predict_one_pass — the same step as ONE call (``gp.fit_predict`` -> gpx_fit_predict, ABI v4+: the query rows ride
+  fit_predict_one_pass — (--full) the same step as ONE call (``gp.fit_predict`` -> gpx_fit_predict, ABI v4+: the query rows ride
                  through the factorisation), a few steps after the timed region; reported beside the headline,
                  never ``value``
-  cpu_baseline — the NumPy/SciPy oracle (oracle/gp_oracle.py) on the GPU box's host cores.
+  cpu_baseline — (--full) the NumPy/SciPy oracle (oracle/gp_oracle.py) on the GPU box's host cores.
                  ``value`` is the rate AT THE WORKLOAD (N=65536), measured IN THIS RUN after the GPU timed
                  region (oracle/make_golden_full.py in a child: ~2 min with 16 threads, 35 GB of host memory;
                  ``measured_in_this_run``, ``cores``, ``seconds``).  Hosts with < 40 GB available, or a child that
@@ -79,6 +87,29 @@ def synthetic(N, d, M, seed):
     y = (np.sin(2.0 * np.pi * X[:, 0]) + 0.5 * np.cos(3.0 * X[:, 1:].sum(axis=1))
          + 0.1 * rng.standard_normal(N))
     return X, y, Xs
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, seed=2024):
+    """Write what a caller of the timed path receives as ``out_dir/<name>.npy``: float64 stays float64, anything else
+    is written as float32.  Past DUMP_LIMIT_BYTES in all (only with a very large --mtest) every array keeps the same
+    fixed, seeded sample of its rows, whose row numbers go to ``out_dir/sample_rows.npy``."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    host = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+        host[name] = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+    rows = len(next(iter(host.values())))
+    row_bytes = sum(a.nbytes // max(1, len(a)) for a in host.values()) + 8
+    if rows * row_bytes > DUMP_LIMIT_BYTES:
+        keep = np.sort(np.random.default_rng(seed).choice(rows, DUMP_LIMIT_BYTES // row_bytes, replace=False))
+        host = {name: a[keep] for name, a in host.items()}
+        host["sample_rows"] = keep.astype(np.float64)
+    for name, a in host.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 DEALING = "cyclic" if os.environ.get("GPX_SHARD_DEAL", "snake") in ("cyclic", "0") else "snake"   # gpx_internal.h: Deal
@@ -305,17 +336,25 @@ def main():
     ap.add_argument("--backend", choices=["nccl", "gloo"], default="nccl",
                     help="gloo = rehearsal of the multi-rank code on one GPU (host collectives)")
     ap.add_argument("--device", type=int, default=None, help="HIP device override (rehearsal)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what the headline does not need: the PCIe-inclusive step, the "
+                         "cost of the profile flag, the one-pass step, the microbenchmarks and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the posterior mean and variance of the last timed step to DIR/mean.npy and DIR/var.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-baseline", choices=["auto", "full", "record", "sample"], default="auto",
-                    help="auto (default): the full-size (N=65536) CPU oracle measured live after the GPU timed region (about 2 "
-                         "minutes, 35 GB of host memory) when the host has >= 40 GB available, else the committed record + a "
-                         "bounded live sample; full: live without the memory check; record / sample: see cpu_baseline()")
+                    help="with --full.  auto (default): the full-size (N=65536) CPU oracle measured live after the GPU timed "
+                         "region (about 2 minutes, 35 GB of host memory) when the host has >= 40 GB available, else the "
+                         "committed record + a bounded live sample; full: live without the memory check; record / sample: see "
+                         "cpu_baseline()")
     ap.add_argument("--cpu-baseline-full", action="store_true", help="= --cpu-baseline full (kept from round 3)")
-    ap.add_argument("--no-microbench", action="store_true")
+    ap.add_argument("--no-microbench", action="store_true", help="with --full: skip the microbenchmarks")
     ap.add_argument("--one-pass", action="store_true",
-                    help="process-per-GPU shard, several ranks: also time gp.fit_predict (collective; one rank, groups and the "
-                         "unsharded handle always do)")
+                    help="with --full, process-per-GPU shard, several ranks: also time gp.fit_predict (collective; one rank, "
+                         "groups and the unsharded handle always do under --full)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # Bare launch (`python bench.py --gpus N`, no launcher): start the one-process-per-GPU launcher ourselves,
         # as a CHILD — this process never touches a GPU — and leave with its exit code.
@@ -570,10 +609,12 @@ def run(args):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     ok = True if gp is None else bool(torch.isfinite(mean).all().item() and (var > (0 if dtype == "float64" else -1e-4)).all().item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"mean": mean, "var": var})
     pcie_ms = None
     unprofiled_ms = None
     one_pass = None
-    if world == 1 and not shard:
+    if world == 1 and not shard and args.full:
         # the same step with HOST NumPy arrays in and out (H2D of X, y, Xs and D2H of mean, var inside
         # the clock): never `value`, stated once beside it
         gp.fit(X, y).predict(Xs)
@@ -623,7 +664,7 @@ def run(args):
     # the ONE-PASS form on the sharded schedule (round 4: every rank's slice of the query points rides through its part of
     # the factorisation): beside the headline, never `value`.  One rank and groups (one process makes the calls: an error
     # is an exception here and every rank still reaches the barrier); process-per-GPU shards of several ranks on request.
-    if shard and dtype in ("float64", "float32") and ok and (world == 1 or group or args.one_pass):
+    if args.full and shard and dtype in ("float64", "float32") and ok and (world == 1 or group or args.one_pass):
         err1 = None
         m1p = v1p = None
         try:
@@ -752,7 +793,7 @@ def run(args):
                                    traffic=None, traffic_source=None,
                                    achieved=out["cholesky_tflops"], peak=peak_mfma * world,
                                    frac=out["cholesky_tflops"] / (peak_mfma * world))
-        if world == 1 and not args.no_microbench:
+        if world == 1 and args.full and not args.no_microbench:
             import ctypes as C
             a, b = C.c_double(0), C.c_double(0)
             if _abi.load().gpx_microbench(C.byref(a), C.byref(b)) == 0:
@@ -764,7 +805,7 @@ def run(args):
                                                                  if a.value > 0 and not shard and dtype == "float64" else None)
         if dtype == "mixed":
             out["refinement"] = {k_: acc[k_] / steps for k_ in ("refine", "refine_iters", "refine_resid0", "refine_resid")}
-        if world == 1 and not args.no_cpu_baseline and args.workload == "C3" and N == N_TRAIN:
+        if world == 1 and args.full and not args.no_cpu_baseline and args.workload == "C3" and N == N_TRAIN:
             out["cpu_baseline"] = cpu_baseline("full" if args.cpu_baseline_full else args.cpu_baseline)
         if world > 1:
             sync()

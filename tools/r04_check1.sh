@@ -7,7 +7,7 @@ timeout -k 10 600 python -m pytest tests/test_handover_gpu.py tests/test_fit_pre
 echo "pytest1 rc=$?"; tail -5 $O/pytest1.log
 timeout -k 10 400 bash tools/bench_rehearsal.sh > $O/rehearsal.log 2>&1
 echo "rehearsal rc=$?"; cat $O/rehearsal.log
-timeout -k 10 500 python bench.py > $O/bench.json 2> $O/bench.err
+timeout -k 10 500 python bench.py --full > $O/bench.json 2> $O/bench.err
 echo "bench rc=$?"; python - <<'P'
 import json
 d=json.loads(open('gpurun_out/r04_check1/bench.json').read().strip().splitlines()[-1])

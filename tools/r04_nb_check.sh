@@ -7,10 +7,10 @@ line() { python -c "
 import json,sys
 d=json.loads(open('$1').read().strip().splitlines()[-1]); p=d['phases_ms']
 print('$2', round(d['ms_per_step'],1), 'block', d['config']['block'], 'SYRK', round(d['roofline']['achieved'],2), 'frac', round(d['roofline']['frac'],4), 'launches', d['roofline']['launches'], 'chol', p['chol'], 'predict', p['predict_total'], 'one pass', d['fit_predict_one_pass'] and round(d['fit_predict_one_pass']['ms_per_step'],1))"; }
-python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-microbench > $O/auto.json 2> $O/err.log; line $O/auto.json "auto"
-GPX_NB_WIDE_FROM=0 python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-microbench > $O/nb1024.json 2>> $O/err.log; line $O/nb1024.json "1024"
-GPX_NB_PRED=3072 python bench.py --block 3072 --steps 3 --warmup 1 --no-cpu-baseline --no-microbench > $O/nb3072.json 2>> $O/err.log; line $O/nb3072.json "3072"
-GPX_NB_PRED=4096 python bench.py --block 4096 --steps 3 --warmup 1 --no-cpu-baseline --no-microbench > $O/nb4096.json 2>> $O/err.log; line $O/nb4096.json "4096"
-python bench.py --workload C5 --dtype mixed --steps 3 --warmup 1 --no-cpu-baseline --no-microbench > $O/c5mixed.json 2>> $O/err.log; line $O/c5mixed.json "C5 mixed auto"
-python bench.py --workload C5 --steps 3 --warmup 1 --no-cpu-baseline --no-microbench > $O/c5f32.json 2>> $O/err.log; line $O/c5f32.json "C5 f32 auto"
+python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-microbench > $O/auto.json 2> $O/err.log; line $O/auto.json "auto"
+GPX_NB_WIDE_FROM=0 python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-microbench > $O/nb1024.json 2>> $O/err.log; line $O/nb1024.json "1024"
+GPX_NB_PRED=3072 python bench.py --full --block 3072 --steps 3 --warmup 1 --no-cpu-baseline --no-microbench > $O/nb3072.json 2>> $O/err.log; line $O/nb3072.json "3072"
+GPX_NB_PRED=4096 python bench.py --full --block 4096 --steps 3 --warmup 1 --no-cpu-baseline --no-microbench > $O/nb4096.json 2>> $O/err.log; line $O/nb4096.json "4096"
+python bench.py --full --workload C5 --dtype mixed --steps 3 --warmup 1 --no-cpu-baseline --no-microbench > $O/c5mixed.json 2>> $O/err.log; line $O/c5mixed.json "C5 mixed auto"
+python bench.py --full --workload C5 --steps 3 --warmup 1 --no-cpu-baseline --no-microbench > $O/c5f32.json 2>> $O/err.log; line $O/c5f32.json "C5 f32 auto"
 python tools/alpha_time.py > $O/alpha_time.txt 2>&1; tail -3 $O/alpha_time.txt
