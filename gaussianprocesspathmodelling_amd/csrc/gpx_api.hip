@@ -126,6 +126,8 @@ struct gpx_handle {
   int64_t fq_rows = 0;  // gpx_fit_predict on a shard: padded rows of this rank's slice of the query points (bordered rows of its K buffer)
   int flag_ok = -1;
   int flag_retries = 0;  // fits of this handle that were run again with hipEvents after a parked stream timed out
+  // joint posterior (gpx_predict_cov / gpx_sample_posterior): scratch of their own, never the fit's buffers
+  DevBuf JVT, JTsol, JSig, JSigF, JWinv, JP, JWblk, JUblk, JInfo, JZT, JST, JZin, JOut;
   // event pool
   std::vector<hipEvent_t> ev_pool;
   size_t ev_used = 0;
@@ -1334,6 +1336,237 @@ int fused_predict_tail(gpx_handle* h, int64_t M, void* mean, void* var, int32_t 
   return GPX_OK;
 }
 
+// ---- joint posterior (ABI v6: gpx_predict_cov, gpx_sample_posterior) ----------------------------------------------------
+// Sigma = K(Xs, Xs) - V^T V with V^T = K* L^-T for ALL M query rows in one buffer (Sigma needs every pair of rows), then
+// for samples L_S = chol(Sigma + (diag_add + j) I) and S^T = Z^T L_S^T.  Every buffer is scratch of its own (J*): the
+// fit's factor, block inverses and z^T are only read, so a predict afterwards is bit for bit what it was before.
+constexpr int POST_NB = 1024;         // panel width of the factorisation of Sigma
+constexpr int64_t POST_ROWS = 8192;   // rows of Z^T per transform batch
+
+// device bytes the call needs beyond the fit (the J* buffers and predict's small mean buffers); `have` = what those buffers
+// hold already (ensure() frees and replaces them)
+template <typename T>
+size_t posterior_need(const gpx_handle* h, int64_t M, int64_t S, bool sample, bool z_host, bool out_host, size_t* have) {
+  const size_t E = sizeof(T);
+  const int64_t Mpad = round_up(M, TILE), lds = Mpad + ld_skew<T>(), k = h->k;
+  double b = (double)Mpad * h->ld + (double)Mpad * lds;                                          // V^T, Sigma
+  if (h->nbw == h->nb_pred) b += 2.0 * Mpad * (h->nbw + ld_skew<T>());                            // block-solve buffers
+  b += (double)RHS_ROWS * (Mpad + ld_skew<T>()) * (1 + splitk_splits(h->Npad)) + (double)M * k;   // mean
+  *have = h->JVT.cap + h->JTsol.cap + h->JSig.cap;
+  if (sample) {
+    const int64_t ldp = POST_NB + ld_skew<T>(), nblk = (Mpad + POST_NB - 1) / POST_NB;
+    const int64_t R = std::min<int64_t>(round_up(std::max<int64_t>(POST_ROWS / k, 1) * k, TILE), round_up(S * k, TILE));
+    b += (double)Mpad * lds + (double)(Mpad / KB) * KB * KB + 2.0 * Mpad * ldp + (double)nblk * POST_NB * POST_NB +
+         (double)POST_NB * ldp + 2.0 * R * lds;
+    if (z_host) b += (double)S * M * k;
+    if (out_host) b += (double)S * M * k;
+    *have += h->JSigF.cap + h->JWinv.cap + h->JP.cap + h->JWblk.cap + h->JUblk.cap + h->JZT.cap + h->JST.cap + h->JZin.cap +
+             h->JOut.cap;
+  }
+  return (size_t)(b * E) + 4096;
+}
+
+// refused handles and the memory check: GPX_OK or the error (nothing computed yet)
+template <typename T>
+int posterior_check(gpx_handle* h, const char* fn, int64_t M, int64_t S, bool sample, bool z_host, bool out_host) {
+  char buf[256];
+  size_t have = 0;
+  const size_t need = posterior_need<T>(h, M, S, sample, z_host, out_host, &have);
+  size_t freeb = 0, totalb = 0;
+  HIPCHK(h, hipMemGetInfo(&freeb, &totalb));
+  if ((double)need > (double)freeb + (double)have) {
+    snprintf(buf, sizeof buf, "%s: M = %lld query points need %.3f GB of device memory, %.3f GB are free", fn, (long long)M,
+             need / 1e9, ((double)freeb + (double)have) / 1e9);
+    return fail(h, GPX_E_NOMEM, buf);
+  }
+  return GPX_OK;
+}
+
+// mean (h->meanout, M x k) and the LOWER triangle of Sigma (h->JSig, Mpad x lds; padded rows identity)
+template <typename T>
+int posterior_cov_core(gpx_handle* h, const void* Xq, int64_t M, int32_t mem_kind) {
+  const int64_t N = h->N, Npad = h->Npad, ld = h->ld;
+  const int d = h->d, k = h->k;
+  const int64_t Mpad = round_up(M, TILE), lds = Mpad + ld_skew<T>(), ldm = Mpad + ld_skew<T>();
+  gpx_timings& tm = h->tm;
+  int rc;
+  if ((rc = ensure(h, h->Q, (size_t)M * d * sizeof(T)))) return rc;
+  if ((rc = ensure(h, h->Qs, (size_t)Mpad * d * sizeof(T)))) return rc;
+  if ((rc = ensure(h, h->JVT, (size_t)Mpad * ld * sizeof(T)))) return rc;
+  if ((rc = ensure(h, h->JSig, (size_t)Mpad * lds * sizeof(T)))) return rc;
+  if ((rc = ensure(h, h->MT, (size_t)RHS_ROWS * ldm * sizeof(T)))) return rc;
+  const int ksplit = splitk_splits(Npad);
+  if (ksplit > 1 && (rc = ensure(h, h->MTpart, (size_t)ksplit * RHS_ROWS * ldm * sizeof(T)))) return rc;
+  if ((rc = ensure(h, h->meanout, (size_t)M * k * sizeof(T)))) return rc;
+  SolveWork<T> sw;
+  if (h->nbw == h->nb_pred) {  // the fit's block inverses, same block width: dense block solves (as predict)
+    sw.ldt = h->nbw + ld_skew<T>();
+    if ((rc = ensure(h, h->JTsol, (size_t)2 * Mpad * sw.ldt * sizeof(T)))) return rc;
+    sw.W = (const T*)h->Wblk.p;
+    sw.nbw = h->nbw;
+    sw.T0 = (T*)h->JTsol.p;
+    sw.T1 = sw.T0 + Mpad * sw.ldt;
+  }
+  T* dVT = (T*)h->JVT.p;
+  T* dSig = (T*)h->JSig.p;
+  {
+    PhaseScope ps(h, &tm.kstar);
+    if ((rc = copy_in(h, h->Q.p, Xq, (size_t)M * d * sizeof(T), mem_kind))) return rc;
+    launch_scale_points<T>((const T*)h->Q.p, M, Mpad, d, (const double*)h->ls.p, h->n_ls, (T*)h->Qs.p, h->st);
+    launch_kbuild_cross<T>(h->cfg.kernel, (const T*)h->Qs.p, M, Mpad, (const T*)h->Xs.p, N, Npad, d, h->sf2, dVT, ld, h->st);
+  }
+  {
+    PhaseScope ps(h, &tm.trsm);
+    if ((rc = solve_fwd_enqueue<T>(h, dVT, Mpad, (const T*)h->Lfac, ld, Npad, h->nb_pred, (const T*)h->Winv.p,
+                                   sw.W ? &sw : nullptr)))
+      return rc;
+  }
+  {  // mean^T (64 x Mpad) = z^T V
+    PhaseScope ps(h, &tm.mean);
+    if (ksplit > 1)
+      launch_gemm_nt_splitk<T>((T*)h->MT.p, ldm, (const T*)h->zT, ld, dVT, ld, RHS_ROWS, Mpad, Npad, ksplit,
+                               (T*)h->MTpart.p, ldm, h->st);
+    else
+      launch_gemm_nt<T>(64, (T*)h->MT.p, ldm, (const T*)h->zT, ld, dVT, ld, RHS_ROWS, Mpad, Npad, 0, 1, h->st);
+    launch_unpack_rhs<T>((const T*)h->MT.p, ldm, M, k, 1.0, (T*)h->meanout.p, h->st);
+  }
+  {  // Sigma = K(Xs, Xs) - (V^T)(V^T)^T: lower 64-tiles of the kernel (the block above the diagonal inside a 128-tile is
+     // not built: zero it first), then one SYRK over the lower triangle
+    PhaseScope ps(h, &tm.var);
+    HIPCHK(h, hipMemsetAsync(dSig, 0, (size_t)Mpad * lds * sizeof(T), h->st));
+    launch_kbuild_sym<T>(h->cfg.kernel, (const T*)h->Qs.p, M, Mpad, d, h->sf2, 0.0, dSig, lds, h->st);
+    launch_gemm_nt<T>(128, dSig, lds, dVT, ld, dVT, ld, Mpad, Mpad, Npad, 1, 0, h->st);
+  }
+  return GPX_OK;
+}
+
+template <typename T>
+int predict_cov_impl(gpx_handle* h, const void* Xq, int64_t M, void* mean, void* cov, int32_t mem_kind) {
+  gpx_timings& tm = h->tm;
+  tm.kstar = tm.mean = tm.trsm = tm.var = tm.d2h = tm.predict_total = 0;
+  int rc;
+  if ((rc = posterior_check<T>(h, "gpx_predict_cov", M, 0, false, false, false))) return rc;
+  const int64_t Mpad = round_up(M, TILE), lds = Mpad + ld_skew<T>();
+  {
+    PhaseScope total(h, &tm.predict_total);
+    if ((rc = posterior_cov_core<T>(h, Xq, M, mem_kind))) return rc;
+    {
+      PhaseScope ps(h, &tm.var);
+      launch_mirror_lower<T>((T*)h->JSig.p, lds, Mpad, 0, h->st);  // bit-symmetric copy-out
+    }
+    PhaseScope ps(h, &tm.d2h);
+    if (mean && (rc = copy_out(h, mean, h->meanout.p, (size_t)M * h->k * sizeof(T), mem_kind))) return rc;
+    HIPCHK(h, hipMemcpy2DAsync(cov, (size_t)M * sizeof(T), h->JSig.p, (size_t)lds * sizeof(T), (size_t)M * sizeof(T),
+                               (size_t)M, mem_kind == GPX_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice,
+                               h->st));
+  }
+  HIPCHK(h, hipStreamSynchronize(h->st));
+  HIPCHK(h, hipGetLastError());
+  LAUNCHCHK(h);
+  collect_phases(h);
+  return GPX_OK;
+}
+
+template <typename T>
+int sample_posterior_impl(gpx_handle* h, const void* Xq, int64_t M, int64_t S, uint64_t seed, const void* z,
+                          double diag_add, double jitter, int32_t max_tries, void* out, double* jitter_used, int64_t* info,
+                          int32_t mem_kind) {
+  gpx_timings& tm = h->tm;
+  tm.kstar = tm.mean = tm.trsm = tm.var = tm.d2h = tm.predict_total = 0;
+  const bool host = mem_kind == GPX_MEM_HOST;
+  int rc;
+  if ((rc = posterior_check<T>(h, "gpx_sample_posterior", M, S, true, z && host, host))) return rc;
+  const int k = h->k;
+  const int64_t Mpad = round_up(M, TILE), lds = Mpad + ld_skew<T>(), ldp = POST_NB + ld_skew<T>();
+  const int64_t total = S * k;                                                   // rows of Z^T / S^T
+  const int64_t Rb = std::max<int64_t>(POST_ROWS / k, 1) * k;                    // whole samples per batch
+  const int64_t Rpad = std::min(round_up(Rb, TILE), round_up(total, TILE));      // buffer rows
+  const size_t outn = (size_t)S * M * k;
+  const int64_t nblk = (Mpad + POST_NB - 1) / POST_NB;
+  if ((rc = ensure(h, h->JSigF, (size_t)Mpad * lds * sizeof(T)))) return rc;
+  if ((rc = ensure(h, h->JWinv, (size_t)(Mpad / KB) * KB * KB * sizeof(T)))) return rc;
+  if ((rc = ensure(h, h->JP, (size_t)2 * Mpad * ldp * sizeof(T)))) return rc;
+  if ((rc = ensure(h, h->JWblk, (size_t)nblk * POST_NB * POST_NB * sizeof(T)))) return rc;
+  if ((rc = ensure(h, h->JUblk, (size_t)POST_NB * ldp * sizeof(T)))) return rc;
+  if ((rc = ensure(h, h->JInfo, 64))) return rc;
+  if ((rc = ensure(h, h->JZT, (size_t)Rpad * lds * sizeof(T)))) return rc;
+  if ((rc = ensure(h, h->JST, (size_t)Rpad * lds * sizeof(T)))) return rc;
+  if (z && host && (rc = ensure(h, h->JZin, outn * sizeof(T)))) return rc;
+  if (host && (rc = ensure(h, h->JOut, outn * sizeof(T)))) return rc;
+  T* dF = (T*)h->JSigF.p;
+  int* dInfo = (int*)h->JInfo.p;
+  const T* dz = (const T*)z;
+  T* dout = host ? (T*)h->JOut.p : (T*)out;
+  // the factorisation books its trailing updates into the fit's counters: they stay the fit's, on every way out
+  struct KeepFitClocks {
+    gpx_timings& tm;
+    const gpx_timings saved;
+    ~KeepFitClocks() {
+      tm.syrk_flops = saved.syrk_flops, tm.syrk_launches = saved.syrk_launches;
+      tm.chol_diag = saved.chol_diag, tm.chol_trsm = saved.chol_trsm, tm.chol_strip = saved.chol_strip;
+      tm.chol_syrk = saved.chol_syrk;
+    }
+  } keep_fit_clocks{tm, tm};
+  double j = jitter;
+  int hinfo = INT_MAX;
+  {
+    PhaseScope total_ps(h, &tm.predict_total);
+    if ((rc = posterior_cov_core<T>(h, Xq, M, mem_kind))) return rc;
+    const T* dSig = (const T*)h->JSig.p;  // (allocated by the core)
+    if (z && host) {
+      PhaseScope ps(h, &tm.kstar);
+      if ((rc = copy_in(h, h->JZin.p, z, outn * sizeof(T), GPX_MEM_HOST))) return rc;
+      dz = (const T*)h->JZin.p;
+    }
+    {  // factorisation (jitter escalation) and transform
+      PhaseScope ps(h, &tm.var);
+      for (int t = 0; t < max_tries; ++t) {  // Sigma stays as built: every attempt starts from a fresh copy of it
+        if (t > 0) j = std::max(j, 1e-12 * h->sf2) * 10.0;
+        launch_copy2d<T>(dF, lds, dSig, lds, Mpad, Mpad, h->st);
+        launch_fix_diag<T>(dF, lds, (int)Mpad, (int)M, diag_add + j, h->st);
+        HIPCHK(h, hipMemsetD32Async((hipDeviceptr_t)dInfo, INT_MAX, 1, h->st));
+        InvWork<T> iw;
+        iw.W = (T*)h->JWblk.p;
+        iw.U = (T*)h->JUblk.p;
+        iw.ldu = ldp;
+        iw.nbw = POST_NB;
+        iw.aux = h->st3;
+        if ((rc = chol_enqueue<T>(h, dF, lds, Mpad, POST_NB, (T*)h->JWinv.p, (T*)h->JP.p, (T*)h->JP.p + Mpad * ldp, ldp,
+                                  dInfo, 0, false, 0, &iw)))
+          return rc;
+        HIPCHK(h, hipMemcpyAsync(&hinfo, dInfo, sizeof(int), hipMemcpyDeviceToHost, h->st));
+        HIPCHK(h, hipStreamSynchronize(h->st));
+        LAUNCHCHK(h);
+        if (hinfo < 0)
+          return fail(h, GPX_E_HIP,
+                      "gpx_sample_posterior: a stream parked on a device flag timed out: kernels are being serialised "
+                      "across streams — set GPX_CHAIN_FLAG=0 to hand over by hipEvents instead");
+        if (hinfo == INT_MAX) break;
+      }
+      if (hinfo == INT_MAX) {
+        launch_mirror_lower<T>(dF, lds, Mpad, 1, h->st);  // the product reads B's diagonal tiles whole: zero above L_S
+        for (int64_t r0 = 0; r0 < total; r0 += Rb) {
+          const int64_t rows = std::min(Rb, total - r0), rpad = round_up(rows, TILE);
+          launch_normals<T>((T*)h->JZT.p, lds, r0, rpad, total, M, Mpad, k, seed, dz, h->st);
+          launch_gemm_nt<T>(128, (T*)h->JST.p, lds, (const T*)h->JZT.p, lds, dF, lds, rpad, Mpad, Mpad, 4, 1, h->st);
+          launch_sample_epilogue<T>((const T*)h->JST.p, lds, r0, rows, (const T*)h->meanout.p, M, k, dout, h->st);
+        }
+      }
+    }
+    if (hinfo == INT_MAX && host) {
+      PhaseScope ps2(h, &tm.d2h);
+      if ((rc = copy_out(h, out, dout, outn * sizeof(T), mem_kind))) return rc;
+    }
+  }
+  *jitter_used = j;
+  *info = hinfo == INT_MAX ? 0 : (int64_t)hinfo;
+  HIPCHK(h, hipStreamSynchronize(h->st));
+  HIPCHK(h, hipGetLastError());
+  LAUNCHCHK(h);
+  collect_phases(h);
+  return GPX_OK;
+}
+
 // ZT <- ZT * L^-T = L^-T restricted to the rows this rank owns: the forward substitution of
 // solve_fwd_enqueue on the rows that are not structurally zero.  Row r of L^-T is zero left of
 // column r and the rows are independent (a right-hand multiplication), so the row blocks of
@@ -1787,7 +2020,9 @@ void gpx_destroy(gpx_handle* h) {
                     &h->info, &h->Q, &h->Qs, &h->VT, &h->MT, &h->MTpart, &h->var, &h->meanout, &h->G,
                     &h->Dbuf, &h->Sbuf, &h->YTloc, &h->Cneg, &h->Sv, &h->AT, &h->Lfull, &h->GatherS,
                     &h->GatherR, &h->outM, &h->outV, &h->ZT, &h->ZTloc, &h->ZTpack, &h->gpart, &h->Wblk, &h->Ublk, &h->Tsol, &h->X64, &h->Y64, &h->Xs64,
-                    &h->A64, &h->Aprev, &h->R64, &h->resv_ring, &h->RTloc, &h->P32out, &h->X32, &h->Y32, &h->RT32, &h->Q64, &h->Qs64, &h->Q32, &h->M64, &h->rn, &h->Zfew})
+                    &h->A64, &h->Aprev, &h->R64, &h->resv_ring, &h->RTloc, &h->P32out, &h->X32, &h->Y32, &h->RT32, &h->Q64, &h->Qs64, &h->Q32, &h->M64, &h->rn, &h->Zfew,
+                    &h->JVT, &h->JTsol, &h->JSig, &h->JSigF, &h->JWinv, &h->JP, &h->JWblk, &h->JUblk, &h->JInfo, &h->JZT, &h->JST,
+                    &h->JZin, &h->JOut})
     release(*b);
   destroy_comm(h);
   for (auto e : h->ev_pool) (void)hipEventDestroy(e);
@@ -1935,6 +2170,61 @@ int gpx_predict(gpx_handle* h, const void* Xq, int64_t M, void* mean, void* var,
 }
 GPX_CATCH_ALL
 
+namespace {
+// the joint-posterior calls run on single-device fp64 / fp32 handles; anything else is refused before any work
+int posterior_refused(gpx_handle* h, const char* fn) {
+  char buf[256];
+  const char* why = h->group                                  ? "device groups"
+                    : (h->cfg.world > 1 || h->comm)           ? "sharded handles"
+                    : h->cfg.dtype == GPX_MIXED               ? "GPX_MIXED handles"
+                                                              : nullptr;
+  if (!why) return GPX_OK;
+  snprintf(buf, sizeof buf, "%s: not supported on %s (single-device GPX_F64 / GPX_F32 handles only)", fn, why);
+  return fail(h, GPX_E_UNSUPPORTED, buf);
+}
+}  // namespace
+
+int gpx_predict_cov(gpx_handle* h, const void* Xq, int64_t M, void* mean, void* cov, int32_t mem_kind) try {
+  if (!h) return GPX_E_ARG;
+  if (!Xq || !cov || M <= 0) return fail(h, GPX_E_ARG, "gpx_predict_cov: bad argument");
+  if (mem_kind != GPX_MEM_HOST && mem_kind != GPX_MEM_DEVICE) return fail(h, GPX_E_ARG, "gpx_predict_cov: bad mem_kind");
+  if (!h->fitted) return fail(h, GPX_E_ARG, "gpx_predict_cov: handle has no successful fit");
+  if (M > (int64_t)INT_MAX - 4096) return fail(h, GPX_E_ARG, "gpx_predict_cov: M too large");
+  int rc;
+  if ((rc = posterior_refused(h, "gpx_predict_cov"))) return rc;
+  HIPCHK(h, hipSetDevice(h->cfg.device));
+  h->err.clear();
+  h->phases.clear();
+  h->ev_used = 0;
+  if (h->cfg.dtype == GPX_F32) return predict_cov_impl<float>(h, Xq, M, mean, cov, mem_kind);
+  return predict_cov_impl<double>(h, Xq, M, mean, cov, mem_kind);
+}
+GPX_CATCH_ALL
+
+int gpx_sample_posterior(gpx_handle* h, const void* Xq, int64_t M, int64_t S, uint64_t seed, const void* z,
+                         double diag_add, double jitter, int32_t max_tries, void* out, double* jitter_used, int64_t* info,
+                         int32_t mem_kind) try {
+  if (!h) return GPX_E_ARG;
+  if (!Xq || !out || !info || !jitter_used || M <= 0 || S <= 0)
+    return fail(h, GPX_E_ARG, "gpx_sample_posterior: bad argument");
+  if (mem_kind != GPX_MEM_HOST && mem_kind != GPX_MEM_DEVICE)
+    return fail(h, GPX_E_ARG, "gpx_sample_posterior: bad mem_kind");
+  if (!(diag_add >= 0.0) || !(jitter >= 0.0) || max_tries < 1)
+    return fail(h, GPX_E_ARG, "gpx_sample_posterior: need diag_add >= 0, jitter >= 0, max_tries >= 1");
+  if (!h->fitted) return fail(h, GPX_E_ARG, "gpx_sample_posterior: handle has no successful fit");
+  if (M > (int64_t)INT_MAX - 4096 || S > (int64_t)1 << 40) return fail(h, GPX_E_ARG, "gpx_sample_posterior: M or S too large");
+  int rc;
+  if ((rc = posterior_refused(h, "gpx_sample_posterior"))) return rc;
+  HIPCHK(h, hipSetDevice(h->cfg.device));
+  h->err.clear();
+  h->phases.clear();
+  h->ev_used = 0;
+  if (h->cfg.dtype == GPX_F32)
+    return sample_posterior_impl<float>(h, Xq, M, S, seed, z, diag_add, jitter, max_tries, out, jitter_used, info, mem_kind);
+  return sample_posterior_impl<double>(h, Xq, M, S, seed, z, diag_add, jitter, max_tries, out, jitter_used, info, mem_kind);
+}
+GPX_CATCH_ALL
+
 int gpx_get_alpha(gpx_handle* h, void* out) try {
   if (!h) return GPX_E_ARG;
   if (!h->fitted || !out) return fail(h, GPX_E_ARG, "gpx_get_alpha: no fit or null output");
@@ -1978,7 +2268,8 @@ int gpx_release_scratch(gpx_handle* h) try {
     for (hipStream_t sx : {m->st, m->st2, m->st3, m->st4, m->st5})
       if (sx) HIPCHK(h, hipStreamSynchronize(sx));
     for (DevBuf* b : {&m->ZT, &m->ZTloc, &m->ZTpack, &m->gpart, &m->MTpart, &m->VT, &m->Tsol, &m->Q, &m->Qs, &m->MT, &m->Sv, &m->Q64, &m->Qs64, &m->Q32,
-                      &m->M64, &m->GatherS, &m->GatherR, &m->outM, &m->outV})
+                      &m->M64, &m->GatherS, &m->GatherR, &m->outM, &m->outV, &m->JVT, &m->JTsol, &m->JSig, &m->JSigF,
+                      &m->JWinv, &m->JP, &m->JWblk, &m->JUblk, &m->JInfo, &m->JZT, &m->JST, &m->JZin, &m->JOut})
       release(*b);
   }
   return GPX_OK;

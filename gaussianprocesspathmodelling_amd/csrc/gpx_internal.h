@@ -273,6 +273,21 @@ void launch_few_product(bool cols, bool assign, T* out, int64_t ldo, const T* M,
 void launch_path_distance(const double* paths, int64_t P, const double* cents, int C, int L, double* D,
                           int64_t ldd, hipStream_t st);
 
+// ---- joint posterior (gpx_posterior.hip) -----------------------------------------------------
+// Z^T rows [r0, r0 + rows_pad) (ld) of a call with `total` = S k rows (row r = s k + c) and M columns (mpad, a multiple of
+// 64): element (r, m) = normal number (s M + m) k + c of the Philox stream `seed` (z == null; include/gpx.h specifies it),
+// or z[(s M + m) k + c] of the caller's (S, M, k) array; zero beyond `total` rows and M columns
+template <typename T>
+void launch_normals(T* ZT, int64_t ld, int64_t r0, int64_t rows_pad, int64_t total, int64_t M, int64_t mpad, int k,
+                    uint64_t seed, const T* z, hipStream_t st);
+// A (n x n, lda; n multiple of 64): strict upper triangle <- transpose of the strict lower one (zero_upper: <- 0)
+template <typename T>
+void launch_mirror_lower(T* A, int64_t lda, int64_t n, int zero_upper, hipStream_t st);
+// out[(s M + m) k + c] = mean[m k + c] + ST[r - r0][m] (lds) for the rows r = s k + c in [r0, r0 + rows) (whole samples)
+template <typename T>
+void launch_sample_epilogue(const T* ST, int64_t lds, int64_t r0, int64_t rows, const T* mean, int64_t M, int k, T* out,
+                            hipStream_t st);
+
 // ---- row-block-cyclic shard helpers (gpx_misc.hip; T = double | float) ------------------------
 // A[i][i] = i < nvalid ? A[i][i] + add : 1   for i < n (diagonal of one local row block)
 template <typename T>

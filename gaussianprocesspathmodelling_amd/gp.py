@@ -317,7 +317,12 @@ class GP:
             var += self.noise
         return mean, var
 
-    def predict(self, Xs, return_var=True, include_noise=False):
+    def predict(self, Xs, return_var=True, include_noise=False, return_cov=False):
+        """Posterior at the query points ``Xs`` (M, d): ``mean`` ((M,) for a 1-D ``y``, else (M, k)) and, with
+        ``return_var``, the per-point variance (M,).  ``return_cov=True`` returns ``(mean, cov)`` instead, ``cov`` the
+        joint (M, M) posterior covariance of the latent function (``gpx_predict_cov``: one SYRK more than the variance;
+        the same for every target column), with ``noise`` on its diagonal when ``include_noise``.  NumPy in, NumPy out;
+        a device tensor in, device tensors out."""
         if not self._fitted:
             raise RuntimeError("predict() before a successful fit()")
         pq, kq, keepq, devq, sq = self._as_input(Xs, "Xs")
@@ -325,6 +330,15 @@ class GP:
             raise ValueError(f"Xs must be (M, {self._d})")
         M = sq[0]
         mshape = (M,) if self._y1d else (M, self._k)
+        if return_cov:
+            mean, cov = self._empty(mshape, devq), self._empty((M, M), devq)
+            self._check(self._lib.gpx_predict_cov(self._h, pq, M, self._ptr(mean), self._ptr(cov), kq))
+            if include_noise:
+                if devq is not None:
+                    cov.diagonal().add_(self.noise)
+                else:
+                    cov[np.diag_indices(M)] += self.noise
+            return mean, cov
         if devq is not None:
             import torch
             tdt = torch.float32 if self.dtype == "float32" else torch.float64
@@ -343,6 +357,69 @@ class GP:
         if include_noise:
             var += self.noise
         return mean, var
+
+    def _empty(self, shape, dev):
+        """uninitialised output of the model's element type: on the device `dev` (torch), or NumPy when None"""
+        if dev is not None:
+            import torch
+            return torch.empty(shape, dtype=torch.float32 if self.dtype == "float32" else torch.float64, device=dev)
+        return np.empty(shape, dtype=self._np_dtype)
+
+    @staticmethod
+    def _ptr(a):
+        return C.c_void_p(a.data_ptr() if _is_torch(a) else a.ctypes.data)
+
+    def sample_y(self, Xs, n_samples=1, random_state=0, include_noise=False, z=None, jitter=None, max_tries=8):
+        """Joint samples of the posterior at ``Xs`` (M, d), shaped as scikit-learn's ``sample_y``: (M, S) for a 1-D
+        ``y``, (M, k, S) otherwise, S = ``n_samples``.  Sample s of target c is ``mean[:, c] + L_S z[s, :, c]`` with
+        ``L_S = chol(cov + (diag_add + j) I)`` (``gpx_sample_posterior``), ``diag_add = noise`` when ``include_noise``.
+        ``z`` (S, M, k) are the caller's standard normals; without them the device draws them from the Philox stream
+        ``random_state`` (an int; include/gpx.h specifies it, so a sample depends only on the seed, its index, M and k).
+        ``jitter`` (None: the model's jitter for float64, 1e-6 variance for float32) is multiplied by 10 after a failed
+        factorisation, at most ``max_tries`` attempts; the value that worked is ``sample_jitter_``.  Raises
+        ``numpy.linalg.LinAlgError`` when none did.  NumPy in, NumPy out; a device tensor in, a device tensor out."""
+        if not self._fitted:
+            raise RuntimeError("sample_y() before a successful fit()")
+        pq, kq, keepq, devq, sq = self._as_input(Xs, "Xs")
+        if len(sq) != 2 or sq[1] != self._d:
+            raise ValueError(f"Xs must be (M, {self._d})")
+        M, k, S = sq[0], self._k, int(n_samples)
+        if S < 1:
+            raise ValueError("n_samples must be >= 1")
+        seed = 0 if random_state is None else int(random_state) & 0xFFFFFFFFFFFFFFFF
+        if jitter is None:
+            jitter = 1e-6 * self.variance if self.dtype == "float32" else self.jitter
+        pz, keepz = None, None
+        if z is not None:
+            if devq is not None:            # the normals go where the queries are
+                import torch
+                keepz = torch.as_tensor(z, device=devq).to(torch.float32 if self.dtype == "float32" else torch.float64)
+                keepz = keepz.contiguous()
+                n = keepz.numel()
+                torch.cuda.current_stream(devq).synchronize()
+            else:
+                if _is_torch(z):
+                    z = z.detach().cpu().numpy()
+                keepz = np.ascontiguousarray(z, dtype=self._np_dtype)
+                n = keepz.size
+            if n != S * M * k:
+                raise ValueError(f"z must hold (n_samples, M, k) = ({S}, {M}, {k}) standard normals")
+            pz = self._ptr(keepz)
+        out = self._empty((S, M, k), devq)
+        used, info = C.c_double(0.0), C.c_int64(0)
+        self._check(self._lib.gpx_sample_posterior(self._h, pq, M, S, seed, pz, self.noise if include_noise else 0.0,
+                                                   float(jitter), int(max_tries), self._ptr(out), C.byref(used),
+                                                   C.byref(info), kq))
+        if info.value != 0:
+            raise np.linalg.LinAlgError(
+                f"posterior covariance not positive definite (first bad pivot {info.value}) with jitter up to "
+                f"{used.value:.3g} after {max_tries} attempts")
+        self.sample_jitter_ = float(used.value)
+        if self._y1d:
+            res = out[:, :, 0].T
+        else:
+            res = out.permute(1, 2, 0) if devq is not None else out.transpose(1, 2, 0)
+        return res.contiguous() if devq is not None else np.ascontiguousarray(res)
 
     # -- checkpoint / resume (SURVEY.md §5: optional get_state) ------------------------------
     def get_state(self):

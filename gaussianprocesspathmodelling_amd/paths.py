@@ -247,19 +247,35 @@ class PathModel:
         self.in_lo, self.in_span, self.y_mean, self.y_std = in_lo, in_span, y_mean, y_std
         self.inputs, self.targets = tuple(inputs), tuple(targets)
 
-    def predict(self, q, return_var=True, include_noise=False):
-        """Posterior at raw (un-normalised) inputs ``q`` (M,) or (M, d): mean (M, k) in the
-        targets' own units and, with ``return_var``, the variance (M, k) per target."""
+    def _queries(self, q):
         q = np.asarray(q, dtype=np.float64)
         q = q.reshape(-1, 1) if q.ndim == 1 else q
         if q.ndim != 2 or q.shape[1] != len(self.inputs):
             raise ValueError(f"queries must be (M,) or (M, {len(self.inputs)})")
-        qn = np.ascontiguousarray((q - self.in_lo) / self.in_span)
+        return np.ascontiguousarray((q - self.in_lo) / self.in_span)
+
+    def predict(self, q, return_var=True, include_noise=False, return_cov=False):
+        """Posterior at raw (un-normalised) inputs ``q`` (M,) or (M, d): mean (M, k) in the
+        targets' own units and, with ``return_var``, the variance (M, k) per target.  ``return_cov=True``
+        returns ``(mean (M, k), cov (k, M, M))``: the joint covariance of each target over the queries."""
+        qn = self._queries(q)
+        if return_cov:
+            mean, cov = self.gp.predict(qn, include_noise=include_noise, return_cov=True)
+            mean = mean.reshape(len(qn), -1) * self.y_std + self.y_mean
+            return mean, cov[None, :, :] * (self.y_std ** 2)[:, None, None]
         out = self.gp.predict(qn, return_var=return_var, include_noise=include_noise)
         mean = (out[0] if return_var else out).reshape(len(qn), -1) * self.y_std + self.y_mean
         if not return_var:
             return mean
         return mean, out[1][:, None] * (self.y_std ** 2)[None, :]
+
+    def sample(self, q, n_samples, seed=0, include_noise=False):
+        """``n_samples`` plausible paths of this cluster: joint posterior samples over the raw inputs ``q`` (M,) or
+        (M, d), (n_samples, M, k) in the targets' own units (``GP.sample_y`` on the device, Philox stream ``seed``)."""
+        qn = self._queries(q)
+        s = self.gp.sample_y(qn, n_samples, random_state=seed, include_noise=include_noise)
+        s = s.reshape(len(qn), -1, int(n_samples))                     # (M, k, n)
+        return np.ascontiguousarray(s.transpose(2, 0, 1)) * self.y_std + self.y_mean
 
     def close(self):
         self.gp.close()

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define GPX_ABI_VERSION 5 /* v5: gpx_timings.handover_*, fp32 / mixed shards; v4: + gpx_fit_predict (v3: gpx_set_flags, refine, one-rank groups) */
+#define GPX_ABI_VERSION 6 /* v6: gpx_predict_cov, gpx_sample_posterior; v5: gpx_timings.handover_*, fp32 / mixed shards; v4: + gpx_fit_predict (v3: gpx_set_flags, refine, one-rank groups) */
 
 /* kernel family — SURVEY.md §8 row a1 (nearest reference code: the pairwise
  * distance loop trajectories.calc_distance, GPmap.py:114-121, and the unused
@@ -155,6 +155,37 @@ int gpx_fit_predict(gpx_handle* h, const void* X, const void* y, int64_t N, int3
                     const double* lengthscale, int32_t n_ls, double sf2, double sn2, double jitter, const void* Xs,
                     int64_t M, void* mean, void* var /* may be NULL */, int32_t mem_kind, int64_t* info);
 
+/* ---- joint posterior (ABI v6) ---------------------------------------------------------------------------------------
+ * Both calls: single-device GPX_F64 / GPX_F32 handles after a successful fit, element type the handle's (as gpx_predict).
+ * GPX_MIXED handles, shards and device groups return GPX_E_UNSUPPORTED (nothing computed, the fit stays valid).  A query
+ * set too large for the card returns GPX_E_NOMEM (gpx_last_error names the bytes) before anything is allocated.  Neither
+ * call changes the fit: gpx_predict afterwards is bit-identical to gpx_predict before.  Their device buffers are scratch
+ * (gpx_release_scratch frees them).  Timings: kstar, trsm, mean, d2h, predict_total as for gpx_predict; var = assembling
+ * Sigma (and for sampling its factorisation and the transform).
+ *
+ * mean (M,k) = K* alpha (may be NULL);  cov (M,M) = K(Xs,Xs) - V^T V,  V = L^-1 K*^T: the latent (noise-free) joint
+ * covariance, full and bit-symmetric, row-major, the same for every target column.  Its diagonal is gpx_predict's var up
+ * to rounding (a different summation order). */
+int gpx_predict_cov(gpx_handle* h, const void* Xs, int64_t M, void* mean, void* cov, int32_t mem_kind);
+
+/* S joint posterior samples per target:  out[s,:,c] = mean[:,c] + L_S z[s,:,c],  L_S = chol(cov + (diag_add + j) I),
+ * out (S,M,k) row-major.  z (S,M,k): the caller's standard normals (same memory kind and element type as out), or NULL:
+ * generated on the device from `seed`.  j starts at `jitter`; after a failed factorisation j <- max(j, 1e-12 sf2) * 10,
+ * at most max_tries attempts; *jitter_used = the j of the last attempt (the one that succeeded).  *info > 0: still not
+ * positive definite (first bad pivot, LAPACK convention); the call returns 0 and `out` is undefined.
+ *
+ * The device normals (fixed, so that results can be reproduced anywhere): normal number i = (s M + m) k + c of the call
+ * comes from Philox4x32-10 (Random123 constants) with counter (n & 0xffffffff, n >> 32, 0, 0), n = i >> 1, and key
+ * (seed & 0xffffffff, seed >> 32); its output words w0..w3 give
+ *     u1 = (((w0 << 32 | w1) >> 11) + 1) 2^-53,   u2 = ((w2 << 32 | w3) >> 11) 2^-53,   r = sqrt(-2 ln u1),
+ *     z[2n] = r cos(2 pi u2),   z[2n+1] = r sin(2 pi u2)     (fp64; GPX_F32 handles round these to fp32).
+ * Sample s depends on (seed, s, M, k) only: the first S' samples of a call with S > S' are those of the call with S'.
+ * Known answers: key 0, counter 0 -> 6627e8d5 e169c58d bc57ac4c 9b00dbd8; all-ones key and counter -> 408f276d
+ * 41c83b0e a20bc7c6 6d5451fd. */
+int gpx_sample_posterior(gpx_handle* h, const void* Xs, int64_t M, int64_t S, uint64_t seed, const void* z,
+                         double diag_add, double jitter, int32_t max_tries, void* out /* (S,M,k) */,
+                         double* jitter_used, int64_t* info, int32_t mem_kind);
+
 int gpx_get_alpha(gpx_handle* h, void* out /* (N,k) host */);
 /* Log marginal likelihood of the last fit and its gradient w.r.t. the LOG hyper-parameters —
  * SURVEY.md §8(f) row 1 ("log marginal likelihood + hyper-parameter gradient hooks"; no anchor
@@ -171,7 +202,7 @@ int gpx_get_alpha(gpx_handle* h, void* out /* (N,k) host */);
 int gpx_lml_grad(gpx_handle* h, double* lml, double* grad);
 int gpx_logdet(gpx_handle* h, double* out);
 /* Frees what only the NEXT predict / gradient call would use (the V^T batch, the L^-T buffer of
- * gpx_lml_grad, per-tile partials, compact block buffers); the fit itself (factor, alpha, block
+ * gpx_lml_grad, per-tile partials, compact block buffers, the buffers of the joint-posterior calls); the fit itself (factor, alpha, block
  * inverses) stays valid.  Buffers grow on demand and are otherwise kept for reuse: call this
  * between a gradient and a large predict when N is close to what the card holds (at N = 131072 the
  * factor and L^-T are 137 GB each). */
