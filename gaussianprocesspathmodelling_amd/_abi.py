@@ -70,6 +70,7 @@ SIGNATURES = {
     "gpx_predict_cov": (C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int32]),
     "gpx_sample_posterior": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_uint64, _P, C.c_double, C.c_double, C.c_int32,
                                        _P, _PD, C.POINTER(C.c_int64), C.c_int32]),
+    "gpx_predict_grad": (C.c_int, [_P, _P, C.c_int64, _P, _P, _P, _P, C.c_int32]),
     "gpx_get_alpha": (C.c_int, [_P, _P]),
     "gpx_lml_grad": (C.c_int, [_P, _PD, _PD]),
     "gpx_logdet": (C.c_int, [_P, _PD]),
@@ -82,6 +83,8 @@ SIGNATURES = {
     "gpx_path_distance": (C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int32, _P, C.c_int32]),
     "gpx_kernel_matrix": (C.c_int, [C.c_int32, _PD, C.c_int64, _PD, C.c_int64, C.c_int32, _PD,
                                     C.c_int32, C.c_double, C.c_double, _PD]),
+    "gpx_kernel_grad_matrix": (C.c_int, [C.c_int32, _PD, C.c_int64, _PD, C.c_int64, C.c_int32, _PD, C.c_int32,
+                                         C.c_double, _PD]),
     "gpx_potrf": (C.c_int, [_PD, C.c_int64, C.c_int32, C.POINTER(C.c_int64)]),
     "gpx_trsm": (C.c_int, [_PD, C.c_int64, _PD, C.c_int64]),
     "gpx_gemm_nt": (C.c_int, [_PD, C.c_int64, C.c_int64, _PD, _PD, C.c_int64, C.c_int32]),

@@ -128,6 +128,8 @@ struct gpx_handle {
   int flag_retries = 0;  // fits of this handle that were run again with hipEvents after a parked stream timed out
   // joint posterior (gpx_predict_cov / gpx_sample_posterior): scratch of their own, never the fit's buffers
   DevBuf JVT, JTsol, JSig, JSigF, JWinv, JP, JWblk, JUblk, JInfo, JZT, JST, JZin, JOut;
+  // posterior gradient (gpx_predict_grad): scratch of its own as well
+  DevBuf GV, GTsol, GMT, GMTpart, GVN, GPart, GOut;
   // event pool
   std::vector<hipEvent_t> ev_pool;
   size_t ev_used = 0;
@@ -1567,6 +1569,183 @@ int sample_posterior_impl(gpx_handle* h, const void* Xq, int64_t M, int64_t S, u
   return GPX_OK;
 }
 
+// ---- posterior gradient (gpx_predict_grad) -------------------------------------------------------------------------
+// Mean only (var and dvar NULL): dmean = dK* alpha with the cached alpha, matrix-free (launch_kgrad_matvec); no solve,
+// nothing of size M N is stored; `mean` comes from predict's own mean-only path.
+// Otherwise, per batch of MB query points (GPX_PRED_BATCH, shrunk to what the card holds): V = [K*;] d_1 K*; ...; d_d K*
+// (nblk row blocks of mp rows each) -> ONE forward solve over the nblk mp rows -> ONE split-K z^T V (mean and dmean
+// together) -> row norms against the per-block prior -> unpack.  Every buffer is scratch of its own (G*): the fit is only
+// read, so gpx_predict afterwards is bit-identical.
+
+// prior[b] of the row blocks: sf2 (value rows), then Var[d f / d x_j] = sf2 / l_j^2 (RBF), 5 sf2 / (3 l_j^2) (Matern-5/2)
+int grad_priors(gpx_handle* h, bool with_value, double* prior) {
+  double ls[32];
+  HIPCHK(h, hipMemcpyAsync(ls, h->ls.p, (size_t)h->n_ls * sizeof(double), hipMemcpyDeviceToHost, h->st));
+  HIPCHK(h, hipStreamSynchronize(h->st));
+  int b = 0;
+  if (with_value) prior[b++] = h->sf2;
+  const double c = h->cfg.kernel == GPX_KERNEL_RBF ? 1.0 : 5.0 / 3.0;
+  for (int j = 0; j < h->d; ++j) {
+    const double l = ls[h->n_ls == 1 ? 0 : j];
+    prior[b++] = c * h->sf2 / (l * l);
+  }
+  return GPX_OK;
+}
+
+template <typename T>
+int predict_grad_mean_only(gpx_handle* h, const void* Xq, int64_t M, void* mean, void* dmean, int32_t mem_kind) {
+  const int d = h->d, k = h->k;
+  const int64_t Mpad = round_up(M, TILE);
+  gpx_timings& tm = h->tm;
+  int rc;
+  int KC = 1, S = 1;
+  int64_t chunk = 0;
+  kgrad_matvec_shape(M, h->Npad, d, k, &KC, &S, &chunk);
+  if (mean) {
+    if ((rc = predict_core<T>(h, Xq, M, false, mem_kind))) return rc;  // gpx_predict's mean; leaves Qs scaled
+  } else {
+    if ((rc = ensure_alpha<T>(h))) return rc;
+    if ((rc = ensure(h, h->Q, (size_t)M * d * sizeof(T)))) return rc;
+    if ((rc = ensure(h, h->Qs, (size_t)Mpad * d * sizeof(T)))) return rc;
+    PhaseScope ps(h, &tm.kstar);
+    if ((rc = copy_in(h, h->Q.p, Xq, (size_t)M * d * sizeof(T), mem_kind))) return rc;
+    launch_scale_points<T>((const T*)h->Q.p, M, Mpad, d, (const double*)h->ls.p, h->n_ls, (T*)h->Qs.p, h->st);
+  }
+  if ((rc = ensure(h, h->GPart, (size_t)S * k * d * round_up(M, 64) * sizeof(T)))) return rc;
+  if ((rc = ensure(h, h->GOut, (size_t)M * d * k * sizeof(T)))) return rc;
+  {
+    PhaseScope ps(h, &tm.mean);
+    launch_kgrad_matvec<T>(h->cfg.kernel, (const T*)h->Qs.p, M, (const T*)h->Xs.p, h->Npad, d, h->sf2,
+                           (const T*)h->alphaT, h->ld, k, (const double*)h->ls.p, h->n_ls, (T*)h->GPart.p,
+                           (T*)h->GOut.p, h->st);
+  }
+  PhaseScope ps(h, &tm.d2h);
+  if (mean && (rc = copy_out(h, mean, h->meanout.p, (size_t)M * k * sizeof(T), mem_kind))) return rc;
+  return copy_out(h, dmean, h->GOut.p, (size_t)M * d * k * sizeof(T), mem_kind);
+}
+
+template <typename T>
+int predict_grad_var(gpx_handle* h, const void* Xq, int64_t M, void* mean, void* var, void* dmean, void* dvar,
+                     int32_t mem_kind, const char* fn) {
+  const int64_t N = h->N, Npad = h->Npad, ld = h->ld;
+  const int d = h->d, k = h->k;
+  const size_t E = sizeof(T);
+  const int64_t Mpad = round_up(M, TILE);
+  const bool with_value = mean || var;
+  const int nblk = d + (with_value ? 1 : 0);
+  const int ksplit = splitk_splits(Npad);
+  const bool dense = h->nbw == h->nb_pred;  // the fit's block inverses, same block width: dense block solves
+  const int64_t ldt = h->nbw + ld_skew<T>();
+  // device bytes per padded query point of a batch (V, block-solve buffers, z^T V and its split-K partials, norms),
+  // and the fixed part (queries, outputs, the skew columns of the product buffers)
+  const double per_pt = (double)E * nblk * ((double)ld + (dense ? 2.0 * ldt : 0.0) + RHS_ROWS * (1.0 + ksplit) + 1.0);
+  const double fixed = (double)E * ((double)M * d + (double)Mpad * d + (double)M * (k + 1) * (d + 1) +
+                                    (double)RHS_ROWS * ld_skew<T>() * (1 + ksplit)) + 4096.0;
+  const size_t have = h->GV.cap + h->GTsol.cap + h->GMT.cap + h->GMTpart.cap + h->GVN.cap + h->GOut.cap;
+  size_t freeb = 0, totalb = 0;
+  HIPCHK(h, hipMemGetInfo(&freeb, &totalb));
+  const double avail = (double)freeb + (double)have;
+  if (128.0 * per_pt + fixed > avail) {
+    char buf[256];
+    snprintf(buf, sizeof buf, "%s: one batch of 128 query points needs %.3f GB of device memory, %.3f GB are free", fn,
+             (128.0 * per_pt + fixed) / 1e9, avail / 1e9);
+    return fail(h, GPX_E_NOMEM, buf);
+  }
+  const int64_t fit = (int64_t)((0.8 * avail - fixed) / per_pt) / 128 * 128;
+  const int64_t MB = std::min(pred_batch_rows(h, Mpad, 0, false), std::max<int64_t>(128, fit));
+  const int64_t RB = nblk * MB;                 // rows of the largest batch
+  const int64_t ldm = RB + ld_skew<T>();        // z^T V of one batch
+  double prior[33];
+  int rc;
+  if ((rc = grad_priors(h, with_value, prior))) return rc;
+  if ((rc = ensure(h, h->Q, (size_t)M * d * E))) return rc;
+  if ((rc = ensure(h, h->Qs, (size_t)Mpad * d * E))) return rc;
+  if ((rc = ensure(h, h->GV, (size_t)RB * ld * E))) return rc;
+  if ((rc = ensure(h, h->GMT, (size_t)RHS_ROWS * ldm * E))) return rc;
+  if (ksplit > 1 && (rc = ensure(h, h->GMTpart, (size_t)ksplit * RHS_ROWS * ldm * E))) return rc;
+  if ((rc = ensure(h, h->GVN, (size_t)RB * E))) return rc;
+  const int64_t o_dvar = M * d * k, o_mean = o_dvar + M * d, o_var = o_mean + M * k;
+  if ((rc = ensure(h, h->GOut, (size_t)(o_var + M) * E))) return rc;
+  SolveWork<T> sw;
+  if (dense) {
+    if ((rc = ensure(h, h->GTsol, (size_t)2 * RB * ldt * E))) return rc;
+    sw.ldt = ldt;
+    sw.W = (const T*)h->Wblk.p;
+    sw.nbw = h->nbw;
+    sw.T0 = (T*)h->GTsol.p;
+    sw.T1 = sw.T0 + RB * ldt;
+  }
+  T* dV = (T*)h->GV.p;
+  T* out = (T*)h->GOut.p;
+  gpx_timings& tm = h->tm;
+  {
+    PhaseScope ps(h, &tm.kstar);
+    if ((rc = copy_in(h, h->Q.p, Xq, (size_t)M * d * E, mem_kind))) return rc;
+    launch_scale_points<T>((const T*)h->Q.p, M, Mpad, d, (const double*)h->ls.p, h->n_ls, (T*)h->Qs.p, h->st);
+  }
+  for (int64_t m0 = 0; m0 < Mpad; m0 += MB) {
+    const int64_t mp = std::min(MB, Mpad - m0);        // padded rows of this batch (a multiple of 128)
+    const int64_t mv = std::min<int64_t>(mp, M - m0);  // valid rows
+    const int64_t R = nblk * mp;                       // rows of V in this batch
+    const int64_t ldb = R + ld_skew<T>();
+    {
+      PhaseScope ps(h, &tm.kstar);
+      launch_kgrad_build<T>(h->cfg.kernel, (const T*)h->Qs.p + m0 * d, mv, mp, (const T*)h->Xs.p, N, Npad, d, h->sf2,
+                            (const double*)h->ls.p, h->n_ls, with_value ? 1 : 0, dV, ld, h->st);
+    }
+    {
+      PhaseScope ps(h, &tm.trsm);
+      if ((rc = solve_fwd_enqueue<T>(h, dV, R, (const T*)h->Lfac, ld, Npad, h->nb_pred, (const T*)h->Winv.p,
+                                     dense ? &sw : nullptr)))
+        return rc;
+    }
+    {  // (mean | dmean)^T (64 x R) = z^T V
+      PhaseScope ps(h, &tm.mean);
+      if (ksplit > 1)
+        launch_gemm_nt_splitk<T>((T*)h->GMT.p, ldb, (const T*)h->zT, ld, dV, ld, RHS_ROWS, R, Npad, ksplit,
+                                 (T*)h->GMTpart.p, ldb, h->st);
+      else
+        launch_gemm_nt<T>(64, (T*)h->GMT.p, ldb, (const T*)h->zT, ld, dV, ld, RHS_ROWS, R, Npad, 0, 1, h->st);
+    }
+    {
+      PhaseScope ps(h, &tm.var);
+      launch_grad_norms<T>(dV, ld, mp, mv, nblk, Npad, prior, (T*)h->GVN.p, h->st);
+    }
+    {
+      PhaseScope ps(h, &tm.mean);
+      launch_grad_unpack<T>((const T*)h->GMT.p, ldb, (const T*)h->GVN.p, mp, mv, nblk, d, k, with_value ? 1 : 0,
+                            out + o_mean + m0 * k, out + o_var + m0, out + m0 * d * k, out + o_dvar + m0 * d, h->st);
+    }
+  }
+  PhaseScope ps(h, &tm.d2h);
+  if ((rc = copy_out(h, dmean, out, (size_t)M * d * k * E, mem_kind))) return rc;
+  if (dvar && (rc = copy_out(h, dvar, out + o_dvar, (size_t)M * d * E, mem_kind))) return rc;
+  if (mean && (rc = copy_out(h, mean, out + o_mean, (size_t)M * k * E, mem_kind))) return rc;
+  if (var && (rc = copy_out(h, var, out + o_var, (size_t)M * E, mem_kind))) return rc;
+  return GPX_OK;
+}
+
+template <typename T>
+int predict_grad_impl(gpx_handle* h, const void* Xq, int64_t M, void* mean, void* var, void* dmean, void* dvar,
+                      int32_t mem_kind) {
+  gpx_timings& tm = h->tm;
+  tm.kstar = tm.mean = tm.trsm = tm.var = tm.d2h = tm.predict_total = 0;
+  int rc;
+  {
+    PhaseScope total(h, &tm.predict_total);
+    if (!var && !dvar)
+      rc = predict_grad_mean_only<T>(h, Xq, M, mean, dmean, mem_kind);
+    else
+      rc = predict_grad_var<T>(h, Xq, M, mean, var, dmean, dvar, mem_kind, "gpx_predict_grad");
+    if (rc) return rc;
+  }
+  HIPCHK(h, hipStreamSynchronize(h->st));
+  HIPCHK(h, hipGetLastError());
+  LAUNCHCHK(h);
+  collect_phases(h);
+  return GPX_OK;
+}
+
 // ZT <- ZT * L^-T = L^-T restricted to the rows this rank owns: the forward substitution of
 // solve_fwd_enqueue on the rows that are not structurally zero.  Row r of L^-T is zero left of
 // column r and the rows are independent (a right-hand multiplication), so the row blocks of
@@ -2225,6 +2404,24 @@ int gpx_sample_posterior(gpx_handle* h, const void* Xq, int64_t M, int64_t S, ui
 }
 GPX_CATCH_ALL
 
+int gpx_predict_grad(gpx_handle* h, const void* Xq, int64_t M, void* mean, void* var, void* dmean, void* dvar,
+                     int32_t mem_kind) try {
+  if (!h) return GPX_E_ARG;
+  if (!Xq || !dmean || M <= 0) return fail(h, GPX_E_ARG, "gpx_predict_grad: bad argument");
+  if (mem_kind != GPX_MEM_HOST && mem_kind != GPX_MEM_DEVICE) return fail(h, GPX_E_ARG, "gpx_predict_grad: bad mem_kind");
+  if (!h->fitted) return fail(h, GPX_E_ARG, "gpx_predict_grad: handle has no successful fit");
+  if (M > (int64_t)INT_MAX - 4096) return fail(h, GPX_E_ARG, "gpx_predict_grad: M too large");
+  int rc;
+  if ((rc = posterior_refused(h, "gpx_predict_grad"))) return rc;
+  HIPCHK(h, hipSetDevice(h->cfg.device));
+  h->err.clear();
+  h->phases.clear();
+  h->ev_used = 0;
+  if (h->cfg.dtype == GPX_F32) return predict_grad_impl<float>(h, Xq, M, mean, var, dmean, dvar, mem_kind);
+  return predict_grad_impl<double>(h, Xq, M, mean, var, dmean, dvar, mem_kind);
+}
+GPX_CATCH_ALL
+
 int gpx_get_alpha(gpx_handle* h, void* out) try {
   if (!h) return GPX_E_ARG;
   if (!h->fitted || !out) return fail(h, GPX_E_ARG, "gpx_get_alpha: no fit or null output");
@@ -2269,7 +2466,8 @@ int gpx_release_scratch(gpx_handle* h) try {
       if (sx) HIPCHK(h, hipStreamSynchronize(sx));
     for (DevBuf* b : {&m->ZT, &m->ZTloc, &m->ZTpack, &m->gpart, &m->MTpart, &m->VT, &m->Tsol, &m->Q, &m->Qs, &m->MT, &m->Sv, &m->Q64, &m->Qs64, &m->Q32,
                       &m->M64, &m->GatherS, &m->GatherR, &m->outM, &m->outV, &m->JVT, &m->JTsol, &m->JSig, &m->JSigF,
-                      &m->JWinv, &m->JP, &m->JWblk, &m->JUblk, &m->JInfo, &m->JZT, &m->JST, &m->JZin, &m->JOut})
+                      &m->JWinv, &m->JP, &m->JWblk, &m->JUblk, &m->JInfo, &m->JZT, &m->JST, &m->JZin, &m->JOut,
+                      &m->GV, &m->GTsol, &m->GMT, &m->GMTpart, &m->GVN, &m->GPart, &m->GOut})
       release(*b);
   }
   return GPX_OK;
@@ -2374,6 +2572,44 @@ int gpx_kernel_matrix(int32_t kernel, const double* A, int64_t na, const double*
     memcpy(K + i * nbb, host.data() + i * ld, (size_t)nbb * 8);  // sym: upper part is zero (not built)
 done:
   for (double* p : {dA, dB, dAs, dBs, dls, dK})
+    if (p) (void)hipFree(p);
+  return rc;
+}
+GPX_CATCH_ALL
+
+int gpx_kernel_grad_matrix(int32_t kernel, const double* A, int64_t na, const double* B, int64_t nb_, int32_t d,
+                           const double* lengthscale, int32_t n_ls, double sf2, double* G) try {
+  if (!A || !B || !G || !lengthscale || na <= 0 || nb_ <= 0 || d <= 0 || d > 32 || (n_ls != 1 && n_ls != d))
+    return GPX_E_ARG;
+  if (kernel != GPX_KERNEL_RBF && kernel != GPX_KERNEL_MATERN52) return GPX_E_ARG;
+  Scratch sc;
+  if (!sc.ok) return GPX_E_HIP;
+  hipStream_t st = sc.h.st;
+  const int64_t napad = round_up(na, 64), nbpad = round_up(nb_, 64), ld = nbpad;
+  double *dA = nullptr, *dB = nullptr, *dAs = nullptr, *dBs = nullptr, *dls = nullptr, *dG = nullptr;
+  std::vector<double> host((size_t)d * napad * ld);
+  int rc = GPX_OK;
+  TCHK(hipMalloc(&dA, (size_t)na * d * 8));
+  TCHK(hipMalloc(&dB, (size_t)nb_ * d * 8));
+  TCHK(hipMalloc(&dAs, (size_t)napad * d * 8));
+  TCHK(hipMalloc(&dBs, (size_t)nbpad * d * 8));
+  TCHK(hipMalloc(&dls, 32 * 8));
+  TCHK(hipMalloc(&dG, (size_t)d * napad * ld * 8));
+  TCHK(hipMemcpyAsync(dA, A, (size_t)na * d * 8, hipMemcpyHostToDevice, st));
+  TCHK(hipMemcpyAsync(dB, B, (size_t)nb_ * d * 8, hipMemcpyHostToDevice, st));
+  TCHK(hipMemcpyAsync(dls, lengthscale, (size_t)n_ls * 8, hipMemcpyHostToDevice, st));
+  launch_scale_points(dA, na, napad, d, dls, n_ls, dAs, st);
+  launch_scale_points(dB, nb_, nbpad, d, dls, n_ls, dBs, st);
+  launch_kgrad_build(kernel, (const double*)dAs, na, napad, (const double*)dBs, nb_, nbpad, d, sf2, dls, n_ls, 0, dG, ld,
+                     st);
+  TCHK(hipMemcpyAsync(host.data(), dG, (size_t)d * napad * ld * 8, hipMemcpyDeviceToHost, st));
+  TCHK(hipStreamSynchronize(st));
+  TCHK(hipGetLastError());
+  for (int32_t j = 0; j < d; ++j)
+    for (int64_t i = 0; i < na; ++i)
+      memcpy(G + ((int64_t)j * na + i) * nb_, host.data() + ((int64_t)j * napad + i) * ld, (size_t)nb_ * 8);
+done:
+  for (double* p : {dA, dB, dAs, dBs, dls, dG})
     if (p) (void)hipFree(p);
   return rc;
 }

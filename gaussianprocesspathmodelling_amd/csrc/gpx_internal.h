@@ -288,6 +288,31 @@ template <typename T>
 void launch_sample_epilogue(const T* ST, int64_t lds, int64_t r0, int64_t rows, const T* mean, int64_t M, int k, T* out,
                             hipStream_t st);
 
+// ---- posterior gradient (gpx_deriv.hip) --------------------------------------------------------
+// Row blocks of V (each mpad rows, ld; mpad a multiple of 64): [sf2 k(As, Bs) if with_value — launch_kbuild_cross's
+// numbers] then d k(As, Bs) / d As_j for j < d; zero beyond m rows / n columns.  ls (n_ls = 1 or d) on the device.
+template <typename T>
+void launch_kgrad_build(int kernel, const T* As, int64_t m, int64_t mpad, const T* Bs, int64_t n, int64_t npad, int d,
+                        double sf2, const double* ls, int n_ls, int with_value, T* V, int64_t ld, hipStream_t st);
+// grid of the matrix-free product: KC targets per workgroup, S splits of `chunk` training columns; the partial buffer
+// holds S * k * d * round_up(M, 64) elements
+void kgrad_matvec_shape(int64_t M, int64_t npad, int d, int k, int* KC, int* S, int64_t* chunk);
+// dmean (M, d, k)[m][j][c] = sum_n d k(As_m, Bs_n) / d As_mj alphaT[c][n], matrix-free (neither K* nor its derivative
+// is stored); As readable up to round_up(M, 64) rows, alphaT (k x lda) zero beyond the valid columns
+template <typename T>
+void launch_kgrad_matvec(int kernel, const T* As, int64_t M, const T* Bs, int64_t npad, int d, double sf2,
+                         const T* alphaT, int64_t lda, int k, const double* ls, int n_ls, T* part, T* dmean,
+                         hipStream_t st);
+// out[b mp + i] = prior[b] - sum_{j < ncols} V[b mp + i][j]^2 for i < mv, b < nblk (<= 33; prior on the host)
+template <typename T>
+void launch_grad_norms(const T* V, int64_t ld, int64_t mp, int64_t mv, int nblk, int64_t ncols, const double* prior,
+                       T* out, hipStream_t st);
+// one batch of the variance route: column b mp + i of MT (RHS rows = targets) and entry b mp + i of VN, i < mv, into
+// mean (mv, k) / var (mv) (row block 0 when with_value) and dmean (mv, d, k) / dvar (mv, d); mean, var, dvar may be null
+template <typename T>
+void launch_grad_unpack(const T* MT, int64_t ldm, const T* VN, int64_t mp, int64_t mv, int nblk, int d, int k,
+                        int with_value, T* mean, T* var, T* dmean, T* dvar, hipStream_t st);
+
 // ---- row-block-cyclic shard helpers (gpx_misc.hip; T = double | float) ------------------------
 // A[i][i] = i < nvalid ? A[i][i] + add : 1   for i < n (diagonal of one local row block)
 template <typename T>

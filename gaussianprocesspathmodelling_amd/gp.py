@@ -358,6 +358,29 @@ class GP:
             var += self.noise
         return mean, var
 
+    def predict_gradient(self, Xs, return_var=True, with_value=False):
+        """Gradient of the posterior with respect to the query points ``Xs`` (M, d) (``gpx_predict_grad``): ``dmean``
+        ((M, d) for a 1-D ``y``, else (M, d, k)) and, with ``return_var``, ``dvar`` (M, d), the latent variance of each
+        partial derivative (no noise term: white noise has no derivative).  ``with_value=True`` returns
+        ``(mean, var, dmean, dvar)`` from the same pass (``(mean, dmean)`` without ``return_var``), ``mean`` and ``var``
+        shaped as :meth:`predict`'s.  Without variances the device contracts the kernel derivative with the cached
+        ``alpha`` matrix-free (no solve).  NumPy in, NumPy out; a device tensor in, device tensors out."""
+        if not self._fitted:
+            raise RuntimeError("predict_gradient() before a successful fit()")
+        pq, kq, keepq, devq, sq = self._as_input(Xs, "Xs")
+        if len(sq) != 2 or sq[1] != self._d:
+            raise ValueError(f"Xs must be (M, {self._d})")
+        M, d, k = sq[0], self._d, self._k
+        dmean = self._empty((M, d) if self._y1d else (M, d, k), devq)
+        dvar = self._empty((M, d), devq) if return_var else None
+        mean = self._empty((M,) if self._y1d else (M, k), devq) if with_value else None
+        var = self._empty((M,), devq) if with_value and return_var else None
+        p = lambda a: None if a is None else self._ptr(a)  # noqa: E731
+        self._check(self._lib.gpx_predict_grad(self._h, pq, M, p(mean), p(var), p(dmean), p(dvar), kq))
+        if with_value:
+            return (mean, var, dmean, dvar) if return_var else (mean, dmean)
+        return (dmean, dvar) if return_var else dmean
+
     def _empty(self, shape, dev):
         """uninitialised output of the model's element type: on the device `dev` (torch), or NumPy when None"""
         if dev is not None:

@@ -277,6 +277,31 @@ class PathModel:
         s = s.reshape(len(qn), -1, int(n_samples))                     # (M, k, n)
         return np.ascontiguousarray(s.transpose(2, 0, 1)) * self.y_std + self.y_mean
 
+    def predict_gradient(self, q, return_var=True):
+        """Gradient of the posterior with respect to the raw (un-normalised) inputs ``q`` (M,) or (M, d), in target units
+        per input unit: ``dmean`` (M, d, k) and, with ``return_var``, ``dvar`` (M, d, k), the latent variance of each
+        partial derivative per target (``GP.predict_gradient`` on the device, rescaled by ``y_std[c] / in_span[j]``)."""
+        qn = self._queries(q)
+        M, d = qn.shape
+        out = self.gp.predict_gradient(qn, return_var=return_var)
+        scale = self.y_std[None, None, :] / np.asarray(self.in_span, dtype=np.float64)[None, :, None]   # (1, d, k)
+        dmean = (out[0] if return_var else out).reshape(M, d, -1) * scale
+        if not return_var:
+            return dmean
+        return dmean, out[1][:, :, None] * scale ** 2
+
+    def velocity(self, q, return_var=True):
+        """Velocity of the modelled path at the raw time stamps ``q``: the ``"t"`` column of :meth:`predict_gradient`,
+        (M, k) arrays, e.g. (dx/dt, dy/dt), and with ``return_var`` their latent variances (M, k).  ``q`` is (M,) when
+        ``t`` is the only input, else (M, d) as for :meth:`predict`."""
+        if "t" not in self.inputs:
+            raise ValueError(f"velocity() needs 't' among the model's inputs, have {self.inputs}")
+        jt = self.inputs.index("t")
+        out = self.predict_gradient(q, return_var=return_var)
+        if not return_var:
+            return out[:, jt, :]
+        return out[0][:, jt, :], out[1][:, jt, :]
+
     def close(self):
         self.gp.close()
 

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define GPX_ABI_VERSION 6 /* v6: gpx_predict_cov, gpx_sample_posterior; v5: gpx_timings.handover_*, fp32 / mixed shards; v4: + gpx_fit_predict (v3: gpx_set_flags, refine, one-rank groups) */
+#define GPX_ABI_VERSION 6 /* v6: gpx_predict_cov, gpx_sample_posterior, later gpx_predict_grad and gpx_kernel_grad_matrix (additive: no existing call, struct or layout changed); v5: gpx_timings.handover_*, fp32 / mixed shards; v4: + gpx_fit_predict (v3: gpx_set_flags, refine, one-rank groups) */
 
 /* kernel family — SURVEY.md §8 row a1 (nearest reference code: the pairwise
  * distance loop trajectories.calc_distance, GPmap.py:114-121, and the unused
@@ -186,6 +186,30 @@ int gpx_sample_posterior(gpx_handle* h, const void* Xs, int64_t M, int64_t S, ui
                          double diag_add, double jitter, int32_t max_tries, void* out /* (S,M,k) */,
                          double* jitter_used, int64_t* info, int32_t mem_kind);
 
+/* ---- posterior gradient (ABI v6, additive) ---------------------------------------------------------------------------
+ * The derivative of the posterior with respect to the query point (for a path model: the velocity).  With u = x / l
+ * (per dimension for ARD), r^2 = sum_j (u*_j - u_j)^2:
+ *   RBF         d k(x*, x) / d x*_j = -(sf2 / l_j) (u*_j - u_j) e^(-r^2/2),                        prior Var = sf2 / l_j^2
+ *   Matern-5/2  d k(x*, x) / d x*_j = -(sf2 / l_j) (5/3) (1 + sqrt5 r) e^(-sqrt5 r) (u*_j - u_j),  prior Var = 5 sf2 / (3 l_j^2)
+ * (smooth at r = 0, where it is 0).  With d_j K* the (M, N) matrix of d k(x*_m, x_n) / d x*_mj:
+ *   dmean[m, j, c] = (d_j K* alpha)[m, c] = ((L^-1 d_j K*^T)^T z)[m, c]
+ *   dvar[m, j]     = prior_j - ||L^-1 (d_j K*)_m^T||^2   (latent: no noise term; raw, not clamped; the same for every
+ *                                                         target column, as gpx_predict's var)
+ * Same handles, refusals (GPX_E_UNSUPPORTED for GPX_MIXED, shards, device groups; the fit stays valid), element type and
+ * memory kinds as gpx_predict_cov; the fit is only read (gpx_predict afterwards is bit-identical); its device buffers are
+ * scratch (gpx_release_scratch frees them).  var and dvar both NULL: dmean is computed matrix-free from the cached alpha
+ * (one exponential per query / training pair, no solve, nothing of size M N stored) and mean, if requested, by
+ * gpx_predict's mean-only path.  Otherwise the query points go in batches (GPX_PRED_BATCH, shrunk to the card): the rows
+ * [K*;] d_1 K*; ...; d_d K* of a batch are built by one fused kernel, solved by ONE forward substitution, and one z^T V
+ * product gives mean and dmean together; GPX_E_NOMEM (before any allocation, gpx_last_error names the bytes) when not
+ * even one batch of 128 points fits.  Timings: kstar (builds), trsm, mean, var, d2h, predict_total as for gpx_predict.
+ * Layouts (row-major): dmean (M,d,k), dvar (M,d), mean (M,k), var (M). */
+/* gradient of the posterior at M query points (single-device GPX_F64 / GPX_F32 handles after a successful fit):
+ * dmean (M,d,k) = d mean / d x*,  dvar (M,d) = latent variance of each partial derivative (may be NULL);
+ * mean (M,k) and var (M) (each may be NULL) = gpx_predict's, from the same pass. */
+int gpx_predict_grad(gpx_handle* h, const void* Xs, int64_t M, void* mean, void* var, void* dmean, void* dvar,
+                     int32_t mem_kind);
+
 int gpx_get_alpha(gpx_handle* h, void* out /* (N,k) host */);
 /* Log marginal likelihood of the last fit and its gradient w.r.t. the LOG hyper-parameters —
  * SURVEY.md §8(f) row 1 ("log marginal likelihood + hyper-parameter gradient hooks"; no anchor
@@ -248,6 +272,9 @@ int gpx_path_distance(const double* paths, int64_t P, const double* cents, int64
 int gpx_kernel_matrix(int32_t kernel, const double* A, int64_t na, const double* B, int64_t nb,
                       int32_t d, const double* lengthscale, int32_t n_ls, double sf2,
                       double diag_add, double* K /* (na, nb or na) */);
+/* kernel unit-test entry point (host buffers, fp64): G (d, na, nb)[j][a][b] = d k(A_a, B_b) / d A_aj */
+int gpx_kernel_grad_matrix(int32_t kernel, const double* A, int64_t na, const double* B, int64_t nb, int32_t d,
+                           const double* lengthscale, int32_t n_ls, double sf2, double* G);
 /* in-place lower Cholesky of A (n,n), lda = n; n multiple of 64.  The strictly upper
  * triangle is never read and is scratch on return (diagonal tiles are updated whole).
  * block = panel width (0 = default). */
