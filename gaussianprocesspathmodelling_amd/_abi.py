@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libgpx.so")
 ABI_VERSION = 6
 
-KERNEL_IDS = {"rbf": 0, "matern52": 1}
+KERNEL_IDS = {"rbf": 0, "matern52": 1, "matern32": 2, "matern12": 3}
 DTYPE_IDS = {"float64": 0, "float32": 1, "mixed": 2}
 MEM_HOST, MEM_DEVICE = 0, 1
 E_ARG, E_HIP, E_COMM, E_UNSUPPORTED, E_NOMEM = -1, -2, -3, -4, -5
@@ -85,6 +85,8 @@ SIGNATURES = {
                                     C.c_int32, C.c_double, C.c_double, _PD]),
     "gpx_kernel_grad_matrix": (C.c_int, [C.c_int32, _PD, C.c_int64, _PD, C.c_int64, C.c_int32, _PD, C.c_int32,
                                          C.c_double, _PD]),
+    "gpx_kernel_deriv_matrix": (C.c_int, [C.c_int32, _PD, C.c_int64, _PD, C.c_int64, C.c_int32, _PD, C.c_int32,
+                                          C.c_double, _PD]),
     "gpx_potrf": (C.c_int, [_PD, C.c_int64, C.c_int32, C.POINTER(C.c_int64)]),
     "gpx_trsm": (C.c_int, [_PD, C.c_int64, _PD, C.c_int64]),
     "gpx_gemm_nt": (C.c_int, [_PD, C.c_int64, C.c_int64, _PD, _PD, C.c_int64, C.c_int32]),

@@ -155,6 +155,14 @@ int fail(gpx_handle* h, int code, const char* msg) {
   return code;
 }
 
+bool known_kernel(int32_t kernel) {
+  return kernel == GPX_KERNEL_RBF || kernel == GPX_KERNEL_MATERN52 || kernel == GPX_KERNEL_MATERN32 ||
+         kernel == GPX_KERNEL_MATERN12;
+}
+
+// the refusal of gpx_predict_grad / gpx_kernel_deriv_matrix: k = sf2 e^-r has a kink at r = 0
+#define MATERN12_NO_GRAD "Matern-1/2 is not differentiable (its sample paths have no derivative)"
+
 #define LAUNCHCHK(h)                                                                                  \
   do {                                                                                                \
     if (take_launch_error())                                                                          \
@@ -1577,14 +1585,15 @@ int sample_posterior_impl(gpx_handle* h, const void* Xq, int64_t M, int64_t S, u
 // together) -> row norms against the per-block prior -> unpack.  Every buffer is scratch of its own (G*): the fit is only
 // read, so gpx_predict afterwards is bit-identical.
 
-// prior[b] of the row blocks: sf2 (value rows), then Var[d f / d x_j] = sf2 / l_j^2 (RBF), 5 sf2 / (3 l_j^2) (Matern-5/2)
+// prior[b] of the row blocks: sf2 (value rows), then Var[d f / d x_j] = sf2 / l_j^2 (RBF), 5 sf2 / (3 l_j^2) (Matern-5/2),
+// 3 sf2 / l_j^2 (Matern-3/2)
 int grad_priors(gpx_handle* h, bool with_value, double* prior) {
   double ls[32];
   HIPCHK(h, hipMemcpyAsync(ls, h->ls.p, (size_t)h->n_ls * sizeof(double), hipMemcpyDeviceToHost, h->st));
   HIPCHK(h, hipStreamSynchronize(h->st));
   int b = 0;
   if (with_value) prior[b++] = h->sf2;
-  const double c = h->cfg.kernel == GPX_KERNEL_RBF ? 1.0 : 5.0 / 3.0;
+  const double c = h->cfg.kernel == GPX_KERNEL_RBF ? 1.0 : h->cfg.kernel == GPX_KERNEL_MATERN32 ? 3.0 : 5.0 / 3.0;
   for (int j = 0; j < h->d; ++j) {
     const double l = ls[h->n_ls == 1 ? 0 : j];
     prior[b++] = c * h->sf2 / (l * l);
@@ -2121,8 +2130,7 @@ const char* gpx_last_error(gpx_handle* h) { return h ? h->err.c_str() : g_create
 int gpx_create(gpx_handle** out, const gpx_config* cfg) try {
   if (!out || !cfg) return fail(nullptr, GPX_E_ARG, "gpx_create: null argument");
   *out = nullptr;
-  if (cfg->kernel != GPX_KERNEL_RBF && cfg->kernel != GPX_KERNEL_MATERN52)
-    return fail(nullptr, GPX_E_ARG, "gpx_create: unknown kernel id");
+  if (!known_kernel(cfg->kernel)) return fail(nullptr, GPX_E_ARG, "gpx_create: unknown kernel id");
   if (cfg->dtype != GPX_F64 && cfg->dtype != GPX_F32 && cfg->dtype != GPX_MIXED)
     return fail(nullptr, GPX_E_ARG, "gpx_create: unknown dtype id");
   if (cfg->refine < 0 || cfg->refine > 50) return fail(nullptr, GPX_E_ARG, "gpx_create: need 0 <= refine <= 50");
@@ -2411,6 +2419,7 @@ int gpx_predict_grad(gpx_handle* h, const void* Xq, int64_t M, void* mean, void*
   if (mem_kind != GPX_MEM_HOST && mem_kind != GPX_MEM_DEVICE) return fail(h, GPX_E_ARG, "gpx_predict_grad: bad mem_kind");
   if (!h->fitted) return fail(h, GPX_E_ARG, "gpx_predict_grad: handle has no successful fit");
   if (M > (int64_t)INT_MAX - 4096) return fail(h, GPX_E_ARG, "gpx_predict_grad: M too large");
+  if (h->cfg.kernel == GPX_KERNEL_MATERN12) return fail(h, GPX_E_UNSUPPORTED, "gpx_predict_grad: " MATERN12_NO_GRAD);
   int rc;
   if ((rc = posterior_refused(h, "gpx_predict_grad"))) return rc;
   HIPCHK(h, hipSetDevice(h->cfg.device));
@@ -2537,7 +2546,7 @@ int gpx_kernel_matrix(int32_t kernel, const double* A, int64_t na, const double*
                       double diag_add, double* K) try {
   if (!A || !K || !lengthscale || na <= 0 || d <= 0 || d > 32 || (n_ls != 1 && n_ls != d))
     return GPX_E_ARG;
-  if (kernel != GPX_KERNEL_RBF && kernel != GPX_KERNEL_MATERN52) return GPX_E_ARG;
+  if (!known_kernel(kernel)) return GPX_E_ARG;
   const bool sym = (B == nullptr);
   const int64_t nbb = sym ? na : nb_;
   if (nbb <= 0) return GPX_E_ARG;
@@ -2577,11 +2586,19 @@ done:
 }
 GPX_CATCH_ALL
 
+// the original entry point keeps its original kernel set (RBF, Matern-5/2); every family: gpx_kernel_deriv_matrix
 int gpx_kernel_grad_matrix(int32_t kernel, const double* A, int64_t na, const double* B, int64_t nb_, int32_t d,
-                           const double* lengthscale, int32_t n_ls, double sf2, double* G) try {
+                           const double* lengthscale, int32_t n_ls, double sf2, double* G) {
+  if (kernel != GPX_KERNEL_RBF && kernel != GPX_KERNEL_MATERN52) return GPX_E_ARG;
+  return gpx_kernel_deriv_matrix(kernel, A, na, B, nb_, d, lengthscale, n_ls, sf2, G);
+}
+
+int gpx_kernel_deriv_matrix(int32_t kernel, const double* A, int64_t na, const double* B, int64_t nb_, int32_t d,
+                            const double* lengthscale, int32_t n_ls, double sf2, double* G) try {
   if (!A || !B || !G || !lengthscale || na <= 0 || nb_ <= 0 || d <= 0 || d > 32 || (n_ls != 1 && n_ls != d))
     return GPX_E_ARG;
-  if (kernel != GPX_KERNEL_RBF && kernel != GPX_KERNEL_MATERN52) return GPX_E_ARG;
+  if (!known_kernel(kernel)) return GPX_E_ARG;
+  if (kernel == GPX_KERNEL_MATERN12) return fail(nullptr, GPX_E_UNSUPPORTED, "gpx_kernel_deriv_matrix: " MATERN12_NO_GRAD);
   Scratch sc;
   if (!sc.ok) return GPX_E_HIP;
   hipStream_t st = sc.h.st;

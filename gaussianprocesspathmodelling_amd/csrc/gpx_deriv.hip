@@ -1,9 +1,11 @@
-// gpx_deriv.hip — the kernels of the posterior gradient (gpx_predict_grad / gpx_kernel_grad_matrix, include/gpx.h).
+// gpx_deriv.hip — the kernels of the posterior gradient (gpx_predict_grad / gpx_kernel_grad_matrix / gpx_kernel_deriv_matrix, include/gpx.h).
 //
 // With u = x / l (per dimension), r^2 = sum_j (u*_j - u_j)^2 and one exponential per (query, training) pair:
 //   RBF         k = sf2 e^(-r^2/2)                         d k / d x*_j = -(u*_j - u_j) / l_j * k
 //   Matern-5/2  k = sf2 (1 + s + s^2/3) e^(-s), s = sqrt5 r  d k / d x*_j = -(u*_j - u_j) / l_j * sf2 5/3 (1 + s) e^(-s)
-// (smooth at r = 0, no division by r).  Everything heavy beyond these kernels is the existing engine (gpx_api.hip):
+//   Matern-3/2  k = sf2 (1 + s) e^(-s), s = sqrt3 r          d k / d x*_j = -(u*_j - u_j) / l_j * sf2 3 e^(-s)
+// (smooth at r = 0, no division by r).  Matern-1/2 has no derivative at r = 0: the launchers below do nothing for it
+// (gpx_api.hip refuses the calls before any launch).  Everything heavy beyond these kernels is the existing engine (gpx_api.hip):
 //   mean only:      dmean = dK* alpha, matrix-free (kgrad_matvec_kernel + kgrad_finish_kernel), no solve
 //   with variance:  V = [K*; d_1 K*; ...; d_d K*] (kgrad_build_kernel) -> ONE forward solve over all rows -> ONE split-K
 //                   z^T V (mean and dmean together) -> row norms with a per-row-block prior -> unpack
@@ -18,13 +20,20 @@ namespace {
 constexpr int GT = 64;      // tile edge of the build, query rows per workgroup of the matrix-free product
 constexpr int GMAXD = 32;   // max input dimension (as kbuild_kernel's MAXD)
 constexpr double SQRT5 = 2.23606797749978969640917366873128;
+constexpr double SQRT3 = 1.73205080756887729352744634150587;
 
 // v = sf2 k(r^2) (bit for bit kbuild_kernel's value) and g with d k / d x*_j = -g (u*_j - u_j) / l_j
 template <int KERNEL, typename T>
 __device__ __forceinline__ void kval_grad(T r2, T sf2, T& v, T& g) {
+  static_assert(KERNEL <= 2, "Matern-1/2 is not differentiable");
   if (KERNEL == 0) {
     v = sf2 * exp((T)-0.5 * r2);
     g = v;
+  } else if (KERNEL == 2) {
+    const T s = (T)SQRT3 * sqrt(r2);
+    const T e = exp(-s);
+    v = sf2 * (((T)1 + s) * e);
+    g = sf2 * ((T)3 * e);
   } else {
     const T s = (T)SQRT5 * sqrt(r2);
     const T e = exp(-s);
@@ -290,10 +299,12 @@ void matvec_d(dim3 grid, int KC, const T* As, const T* Bs, int64_t npad, int64_t
 template <typename T>
 void launch_kgrad_build(int kernel, const T* As, int64_t m, int64_t mpad, const T* Bs, int64_t n, int64_t npad, int d,
                         double sf2, const double* ls, int n_ls, int with_value, T* V, int64_t ld, hipStream_t st) {
-  if (kernel == 0)
-    build_d<T, 0>(As, m, mpad, Bs, n, npad, d, sf2, ls, n_ls, with_value, V, ld, st);
-  else
-    build_d<T, 1>(As, m, mpad, Bs, n, npad, d, sf2, ls, n_ls, with_value, V, ld, st);
+  switch (kernel) {
+    case 0: build_d<T, 0>(As, m, mpad, Bs, n, npad, d, sf2, ls, n_ls, with_value, V, ld, st); break;
+    case 1: build_d<T, 1>(As, m, mpad, Bs, n, npad, d, sf2, ls, n_ls, with_value, V, ld, st); break;
+    case 2: build_d<T, 2>(As, m, mpad, Bs, n, npad, d, sf2, ls, n_ls, with_value, V, ld, st); break;
+    default: break;  // Matern-1/2: refused by the API
+  }
 }
 
 void kgrad_matvec_shape(int64_t M, int64_t npad, int d, int k, int* KC, int* S, int64_t* chunk) {
@@ -317,10 +328,12 @@ void launch_kgrad_matvec(int kernel, const T* As, int64_t M, const T* Bs, int64_
   kgrad_matvec_shape(M, npad, d, k, &KC, &S, &chunk);
   const int64_t mpad = round_up(M, GT);
   const dim3 grid((unsigned)(mpad / GT), (unsigned)((k + KC - 1) / KC), (unsigned)S);
-  if (kernel == 0)
-    matvec_d<T, 0>(grid, KC, As, Bs, npad, chunk, d, sf2, alphaT, lda, k, part, mpad, st);
-  else
-    matvec_d<T, 1>(grid, KC, As, Bs, npad, chunk, d, sf2, alphaT, lda, k, part, mpad, st);
+  switch (kernel) {
+    case 0: matvec_d<T, 0>(grid, KC, As, Bs, npad, chunk, d, sf2, alphaT, lda, k, part, mpad, st); break;
+    case 1: matvec_d<T, 1>(grid, KC, As, Bs, npad, chunk, d, sf2, alphaT, lda, k, part, mpad, st); break;
+    case 2: matvec_d<T, 2>(grid, KC, As, Bs, npad, chunk, d, sf2, alphaT, lda, k, part, mpad, st); break;
+    default: return;  // Matern-1/2: refused by the API
+  }
   hipLaunchKernelGGL(kgrad_finish_kernel<T>, dim3(grid_for(M * d * k)), dim3(256), 0, st, part, mpad, S, M, d, k, ls,
                      n_ls, dmean);
 }

@@ -5,7 +5,8 @@
 //
 //     dLML/dlog(theta) = 1/2 sum_ij (sum_c alpha_ic alpha_jc - k K^-1_ij) (dK/dlog theta)_ij
 //
-//   dK/dlog l_c  = kd_ij * ((x_ic - x_jc) / l_c)^2   RBF: kd = Kf;  Matern-5/2: kd = sf2 (5/3)(1+s) e^-s
+//   dK/dlog l_c  = kd_ij * ((x_ic - x_jc) / l_c)^2   RBF: kd = Kf;  Matern-5/2: kd = sf2 (5/3)(1+s) e^-s;
+//                                                    Matern-3/2: kd = 3 sf2 e^-s;  Matern-1/2: kd = sf2 e^-r / r (0 at r = 0)
 //   dK/dlog sf2  = Kf_ij = sf2 k(r_ij)
 //   dK/dlog sn2  = sn2 delta_ij
 //
@@ -24,14 +25,25 @@ namespace gpx {
 namespace {
 
 constexpr double SQRT5 = 2.23606797749978969640917366873128;
+constexpr double SQRT3 = 1.73205080756887729352744634150587;
 constexpr int GMAXD = 32;
 
-// kf = sf2 k(r), kd = the factor of d_c^2 in dK/dlog l_c
+// kf = sf2 k(r), kd = the factor of d_c^2 in dK/dlog l_c; KERNEL = GPX_KERNEL_* (0 RBF, 1 Matern-5/2, 2 Matern-3/2,
+// 3 Matern-1/2).  Matern-1/2: kd = sf2 e^-r / r, set to 0 at r = 0, where kd d_c^2 <= sf2 r e^-r -> 0.
 template <int KERNEL>
 __device__ __forceinline__ void kvals(double r2, double sf2, double& kf, double& kd) {
   if (KERNEL == 0) {
     kf = sf2 * exp(-0.5 * r2);
     kd = kf;
+  } else if (KERNEL == 2) {
+    const double s = SQRT3 * sqrt(r2);
+    const double e = exp(-s);
+    kf = sf2 * ((1.0 + s) * e);
+    kd = 3.0 * (sf2 * e);
+  } else if (KERNEL == 3) {
+    const double r = sqrt(r2);
+    kf = sf2 * exp(-r);
+    kd = r > 0.0 ? kf / r : 0.0;
   } else {
     const double s = SQRT5 * sqrt(r2);
     const double e = sf2 * exp(-s);
@@ -353,28 +365,34 @@ void launch_set_diag_one(double* A, int64_t lda, int64_t n, hipStream_t st) {
 
 void launch_kinv_trace(int kernel, const double* ZT, int64_t ld, int64_t npad, int64_t n, const double* Xs, int d,
                        int ard, double sf2, double sn2, double* part, int ntheta, int P, int rank, hipStream_t st) {
-  if (kernel == 0)
-    launch_kinv_trace_k<0>(ZT, ld, npad, n, Xs, d, ard, sf2, sn2, part, ntheta, P, rank, 0, 0, 0, 0, 0, st);
-  else
-    launch_kinv_trace_k<1>(ZT, ld, npad, n, Xs, d, ard, sf2, sn2, part, ntheta, P, rank, 0, 0, 0, 0, 0, st);
+  switch (kernel) {
+    case 0: launch_kinv_trace_k<0>(ZT, ld, npad, n, Xs, d, ard, sf2, sn2, part, ntheta, P, rank, 0, 0, 0, 0, 0, st); break;
+    case 1: launch_kinv_trace_k<1>(ZT, ld, npad, n, Xs, d, ard, sf2, sn2, part, ntheta, P, rank, 0, 0, 0, 0, 0, st); break;
+    case 2: launch_kinv_trace_k<2>(ZT, ld, npad, n, Xs, d, ard, sf2, sn2, part, ntheta, P, rank, 0, 0, 0, 0, 0, st); break;
+    default: launch_kinv_trace_k<3>(ZT, ld, npad, n, Xs, d, ard, sf2, sn2, part, ntheta, P, rank, 0, 0, 0, 0, 0, st); break;
+  }
 }
 
 void launch_kinv_trace_cols(int kernel, const double* ZTc, int64_t ldc, int64_t npad, int64_t n, const double* Xs,
                             int d, int ard, double sf2, double sn2, double* part, int ntheta, int nb, int P, int rank,
                             int64_t ncols, int snake, hipStream_t st) {
-  if (kernel == 0)
-    launch_kinv_trace_k<0>(ZTc, ldc, npad, n, Xs, d, ard, sf2, sn2, part, ntheta, 1, 0, nb, P, rank, ncols, snake, st);
-  else
-    launch_kinv_trace_k<1>(ZTc, ldc, npad, n, Xs, d, ard, sf2, sn2, part, ntheta, 1, 0, nb, P, rank, ncols, snake, st);
+  switch (kernel) {
+    case 0: launch_kinv_trace_k<0>(ZTc, ldc, npad, n, Xs, d, ard, sf2, sn2, part, ntheta, 1, 0, nb, P, rank, ncols, snake, st); break;
+    case 1: launch_kinv_trace_k<1>(ZTc, ldc, npad, n, Xs, d, ard, sf2, sn2, part, ntheta, 1, 0, nb, P, rank, ncols, snake, st); break;
+    case 2: launch_kinv_trace_k<2>(ZTc, ldc, npad, n, Xs, d, ard, sf2, sn2, part, ntheta, 1, 0, nb, P, rank, ncols, snake, st); break;
+    default: launch_kinv_trace_k<3>(ZTc, ldc, npad, n, Xs, d, ard, sf2, sn2, part, ntheta, 1, 0, nb, P, rank, ncols, snake, st); break;
+  }
 }
 
 void launch_alpha_quad(int kernel, const double* alphaT, int64_t ld, int k, int64_t npad, int64_t n,
                        const double* Xs, int d, int ard, double sf2, double sn2, double* part, int ntheta,
                        hipStream_t st) {
-  if (kernel == 0)
-    launch_alpha_quad_k<0>(alphaT, ld, k, npad, n, Xs, d, ard, sf2, sn2, part, ntheta, st);
-  else
-    launch_alpha_quad_k<1>(alphaT, ld, k, npad, n, Xs, d, ard, sf2, sn2, part, ntheta, st);
+  switch (kernel) {
+    case 0: launch_alpha_quad_k<0>(alphaT, ld, k, npad, n, Xs, d, ard, sf2, sn2, part, ntheta, st); break;
+    case 1: launch_alpha_quad_k<1>(alphaT, ld, k, npad, n, Xs, d, ard, sf2, sn2, part, ntheta, st); break;
+    case 2: launch_alpha_quad_k<2>(alphaT, ld, k, npad, n, Xs, d, ard, sf2, sn2, part, ntheta, st); break;
+    default: launch_alpha_quad_k<3>(alphaT, ld, k, npad, n, Xs, d, ard, sf2, sn2, part, ntheta, st); break;
+  }
 }
 
 void launch_reduce_partials(const double* part, int64_t ntile, int ntheta, double scale, double* out,

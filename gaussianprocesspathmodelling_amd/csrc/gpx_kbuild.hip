@@ -16,14 +16,21 @@ namespace {
 constexpr int KT = 64;      // tile edge
 constexpr int MAXD = 32;    // max input dimension staged in LDS
 constexpr double SQRT5 = 2.23606797749978969640917366873128;
+constexpr double SQRT3 = 1.73205080756887729352744634150587;
 
+// KERNEL = GPX_KERNEL_*: 0 RBF, 1 Matern-5/2, 2 Matern-3/2, 3 Matern-1/2
 template <int KERNEL, typename T>
 __device__ __forceinline__ T kfun(T r2, T sf2) {
   if (KERNEL == 0) {
     return sf2 * exp((T)-0.5 * r2);
-  } else {
+  } else if (KERNEL == 1) {
     const T s = (T)SQRT5 * sqrt(r2);
     return sf2 * (((T)1 + s + s * s / (T)3) * exp(-s));
+  } else if (KERNEL == 2) {
+    const T s = (T)SQRT3 * sqrt(r2);
+    return sf2 * (((T)1 + s) * exp(-s));
+  } else {
+    return sf2 * exp(-sqrt(r2));
   }
 }
 
@@ -153,20 +160,24 @@ void launch_kbuild_sym(int kernel, const T* Xs, int64_t n, int64_t npad, int d, 
                        double diag_add, T* K, int64_t ld, hipStream_t st) {
   const int64_t TT = npad / KT;
   const int64_t nblocks = TT * (TT + 1) / 2;
-  if (kernel == 0)
-    dispatch_d<T, 0, true>(Xs, n, Xs, n, d, nblocks, (int)TT, sf2, diag_add, K, ld, st);
-  else
-    dispatch_d<T, 1, true>(Xs, n, Xs, n, d, nblocks, (int)TT, sf2, diag_add, K, ld, st);
+  switch (kernel) {
+    case 0: dispatch_d<T, 0, true>(Xs, n, Xs, n, d, nblocks, (int)TT, sf2, diag_add, K, ld, st); break;
+    case 1: dispatch_d<T, 1, true>(Xs, n, Xs, n, d, nblocks, (int)TT, sf2, diag_add, K, ld, st); break;
+    case 2: dispatch_d<T, 2, true>(Xs, n, Xs, n, d, nblocks, (int)TT, sf2, diag_add, K, ld, st); break;
+    default: dispatch_d<T, 3, true>(Xs, n, Xs, n, d, nblocks, (int)TT, sf2, diag_add, K, ld, st); break;
+  }
 }
 
 template <typename T>
 void launch_kbuild_cross(int kernel, const T* As, int64_t m, int64_t mpad, const T* Bs, int64_t n,
                          int64_t npad, int d, double sf2, T* K, int64_t ld, hipStream_t st) {
   const int64_t tm = mpad / KT, tn = npad / KT;
-  if (kernel == 0)
-    dispatch_d<T, 0, false>(As, m, Bs, n, d, tm * tn, (int)tn, sf2, 0.0, K, ld, st);
-  else
-    dispatch_d<T, 1, false>(As, m, Bs, n, d, tm * tn, (int)tn, sf2, 0.0, K, ld, st);
+  switch (kernel) {
+    case 0: dispatch_d<T, 0, false>(As, m, Bs, n, d, tm * tn, (int)tn, sf2, 0.0, K, ld, st); break;
+    case 1: dispatch_d<T, 1, false>(As, m, Bs, n, d, tm * tn, (int)tn, sf2, 0.0, K, ld, st); break;
+    case 2: dispatch_d<T, 2, false>(As, m, Bs, n, d, tm * tn, (int)tn, sf2, 0.0, K, ld, st); break;
+    default: dispatch_d<T, 3, false>(As, m, Bs, n, d, tm * tn, (int)tn, sf2, 0.0, K, ld, st); break;
+  }
 }
 
 #define GPX_INSTANTIATE_KBUILD(T)                                                                     \

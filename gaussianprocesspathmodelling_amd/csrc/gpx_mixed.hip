@@ -13,6 +13,7 @@ namespace gpx {
 namespace {
 
 constexpr double SQRT5 = 2.23606797749978969640917366873128;
+constexpr double SQRT3 = 1.73205080756887729352744634150587;
 constexpr int XMAXD = 32;
 constexpr int KMAX = 8;  // target columns of the mixed mode
 
@@ -43,9 +44,15 @@ __device__ __forceinline__ double exp_nonpos(double x) {
   return ldexp(p, (int)n);
 }
 
+// KERNEL = GPX_KERNEL_*: 0 RBF, 1 Matern-5/2, 2 Matern-3/2, 3 Matern-1/2
 template <int KERNEL>
 __device__ __forceinline__ double kval(double r2, double sf2) {
   if (KERNEL == 0) return sf2 * exp_nonpos(-0.5 * r2);
+  if (KERNEL == 3) return sf2 * exp_nonpos(-sqrt(r2));
+  if (KERNEL == 2) {
+    const double s = SQRT3 * sqrt(r2);
+    return sf2 * ((1.0 + s) * exp_nonpos(-s));
+  }
   const double s = SQRT5 * sqrt(r2);
   return sf2 * ((1.0 + s + s * s / 3.0) * exp_nonpos(-s));
 }
@@ -323,10 +330,12 @@ void launch_kmatvec_k(const double* As, int64_t m, int64_t mpad, const double* B
 void launch_kmatvec(int kernel, const double* As, int64_t m, int64_t mpad, const double* Bs, int64_t npad, int d,
                     double sf2, double diag, const double* y, const double* alphaT, int64_t lda, int k,
                     double sign, double* outT, int64_t ldo, hipStream_t st) {
-  if (kernel == 0)
-    launch_kmatvec_k<0>(As, m, mpad, Bs, npad, d, sf2, diag, y, alphaT, lda, k, sign, outT, ldo, st);
-  else
-    launch_kmatvec_k<1>(As, m, mpad, Bs, npad, d, sf2, diag, y, alphaT, lda, k, sign, outT, ldo, st);
+  switch (kernel) {
+    case 0: launch_kmatvec_k<0>(As, m, mpad, Bs, npad, d, sf2, diag, y, alphaT, lda, k, sign, outT, ldo, st); break;
+    case 1: launch_kmatvec_k<1>(As, m, mpad, Bs, npad, d, sf2, diag, y, alphaT, lda, k, sign, outT, ldo, st); break;
+    case 2: launch_kmatvec_k<2>(As, m, mpad, Bs, npad, d, sf2, diag, y, alphaT, lda, k, sign, outT, ldo, st); break;
+    default: launch_kmatvec_k<3>(As, m, mpad, Bs, npad, d, sf2, diag, y, alphaT, lda, k, sign, outT, ldo, st); break;
+  }
 }
 
 // rows (cols = false): out[c][i] (=|-=) sum_j M[i][j] v[c][j];  columns (cols = true): ... sum_j M[j][i] v[c][j]

@@ -29,7 +29,10 @@ class GP:
 
     Parameters
     ----------
-    kernel : "rbf" | "matern52"
+    kernel : "rbf" | "matern52" | "matern32" | "matern12" — scikit-learn's ``RBF`` and ``Matern(nu=2.5 | 1.5 | 0.5)``
+        (include/gpx.h).  Matern-3/2 is the usual prior for trajectories (a velocity, no acceleration);
+        Matern-1/2 (exponential / Ornstein-Uhlenbeck) has no derivative, so :meth:`predict_gradient` raises
+        ``GpxError`` for it.  Every other call runs for all four.
     lengthscale : float or array of d floats (ARD)
     variance : signal variance sf2
     noise : observation-noise variance sn2 (added to the diagonal)

@@ -33,6 +33,12 @@ extern "C" {
  * scipy.spatial.distance import, GPmap.py:10). */
 #define GPX_KERNEL_RBF 0      /* sf2 * exp(-r^2/2)                            */
 #define GPX_KERNEL_MATERN52 1 /* sf2 * (1 + sqrt5 r + 5 r^2/3) exp(-sqrt5 r)  */
+#define GPX_KERNEL_MATERN32 2 /* sf2 * (1 + sqrt3 r) exp(-sqrt3 r)            */
+#define GPX_KERNEL_MATERN12 3 /* sf2 * exp(-r)  (exponential, Ornstein-Uhlenbeck) */
+/* r^2 = sum_j ((x_j - x'_j) / l_j)^2, d_c = (x_c - x'_c) / l_c.  gpx_lml_grad: dK / dlog l_c = kd d_c^2 with
+ *   RBF kd = k,  Matern-5/2 kd = sf2 (5/3) (1 + sqrt5 r) e^(-sqrt5 r),  Matern-3/2 kd = 3 sf2 e^(-sqrt3 r),
+ *   Matern-1/2 kd = sf2 e^(-r) / r, and 0 at r = 0 (kd d_c^2 <= sf2 r -> 0).
+ * Matern-1/2 is not differentiable: gpx_predict_grad and gpx_kernel_deriv_matrix return GPX_E_UNSUPPORTED for it. */
 
 #define GPX_F64 0
 #define GPX_F32 1
@@ -191,7 +197,9 @@ int gpx_sample_posterior(gpx_handle* h, const void* Xs, int64_t M, int64_t S, ui
  * (per dimension for ARD), r^2 = sum_j (u*_j - u_j)^2:
  *   RBF         d k(x*, x) / d x*_j = -(sf2 / l_j) (u*_j - u_j) e^(-r^2/2),                        prior Var = sf2 / l_j^2
  *   Matern-5/2  d k(x*, x) / d x*_j = -(sf2 / l_j) (5/3) (1 + sqrt5 r) e^(-sqrt5 r) (u*_j - u_j),  prior Var = 5 sf2 / (3 l_j^2)
- * (smooth at r = 0, where it is 0).  With d_j K* the (M, N) matrix of d k(x*_m, x_n) / d x*_mj:
+ *   Matern-3/2  d k(x*, x) / d x*_j = -(sf2 / l_j) 3 e^(-sqrt3 r) (u*_j - u_j),                    prior Var = 3 sf2 / l_j^2
+ * (smooth at r = 0, where it is 0).  Matern-1/2 is not differentiable: its handles return GPX_E_UNSUPPORTED
+ * (gpx_last_error says why), nothing is computed and the fit stays valid.  With d_j K* the (M, N) matrix of d k(x*_m, x_n) / d x*_mj:
  *   dmean[m, j, c] = (d_j K* alpha)[m, c] = ((L^-1 d_j K*^T)^T z)[m, c]
  *   dvar[m, j]     = prior_j - ||L^-1 (d_j K*)_m^T||^2   (latent: no noise term; raw, not clamped; the same for every
  *                                                         target column, as gpx_predict's var)
@@ -272,9 +280,14 @@ int gpx_path_distance(const double* paths, int64_t P, const double* cents, int64
 int gpx_kernel_matrix(int32_t kernel, const double* A, int64_t na, const double* B, int64_t nb,
                       int32_t d, const double* lengthscale, int32_t n_ls, double sf2,
                       double diag_add, double* K /* (na, nb or na) */);
-/* kernel unit-test entry point (host buffers, fp64): G (d, na, nb)[j][a][b] = d k(A_a, B_b) / d A_aj */
+/* kernel unit-test entry point (host buffers, fp64): G (d, na, nb)[j][a][b] = d k(A_a, B_b) / d A_aj.
+ * GPX_KERNEL_RBF and GPX_KERNEL_MATERN52 only (its kernel set as first published; any other id is GPX_E_ARG). */
 int gpx_kernel_grad_matrix(int32_t kernel, const double* A, int64_t na, const double* B, int64_t nb, int32_t d,
                            const double* lengthscale, int32_t n_ls, double sf2, double* G);
+/* The same for every kernel family (additive to ABI v6): RBF, Matern-5/2, Matern-3/2; GPX_KERNEL_MATERN12 returns
+ * GPX_E_UNSUPPORTED (gpx_last_error(NULL) says why) and leaves G untouched. */
+int gpx_kernel_deriv_matrix(int32_t kernel, const double* A, int64_t na, const double* B, int64_t nb, int32_t d,
+                            const double* lengthscale, int32_t n_ls, double sf2, double* G);
 /* in-place lower Cholesky of A (n,n), lda = n; n multiple of 64.  The strictly upper
  * triangle is never read and is scratch on return (diagonal tiles are updated whole).
  * block = panel width (0 = default). */
