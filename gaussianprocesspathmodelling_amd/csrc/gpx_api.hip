@@ -38,6 +38,7 @@
 #include <vector>
 
 #include "../../include/gpx.h"
+#include "gpx_cov.h"
 #include "gpx_internal.h"
 
 using namespace gpx;
@@ -153,11 +154,6 @@ namespace {
 int fail(gpx_handle* h, int code, const char* msg) {
   if (h) h->err = msg; else g_create_error = msg;
   return code;
-}
-
-bool known_kernel(int32_t kernel) {
-  return kernel == GPX_KERNEL_RBF || kernel == GPX_KERNEL_MATERN52 || kernel == GPX_KERNEL_MATERN32 ||
-         kernel == GPX_KERNEL_MATERN12;
 }
 
 // the refusal of gpx_predict_grad / gpx_kernel_deriv_matrix: k = sf2 e^-r has a kink at r = 0
@@ -1048,7 +1044,7 @@ int fit_impl(gpx_handle* h, const void* X, const void* y, int64_t N, int32_t d, 
   if ((rc = ensure(h, h->X, (size_t)N * d * sizeof(T)))) return rc;
   if ((rc = ensure(h, h->Y, (size_t)N * k * sizeof(T)))) return rc;
   if ((rc = ensure(h, h->Xs, (size_t)Npad * d * sizeof(T)))) return rc;
-  if ((rc = ensure(h, h->ls, 32 * 8))) return rc;
+  if ((rc = ensure(h, h->ls, MAX_D * 8))) return rc;
   const int64_t NX = RHS_ROWS + Mpad;  // bordered rows: [K* rows of a fused predict] + the right-hand sides
   if (Xq) {
     if ((rc = ensure(h, h->Q, (size_t)M * d * sizeof(T)))) return rc;
@@ -1585,15 +1581,14 @@ int sample_posterior_impl(gpx_handle* h, const void* Xq, int64_t M, int64_t S, u
 // together) -> row norms against the per-block prior -> unpack.  Every buffer is scratch of its own (G*): the fit is only
 // read, so gpx_predict afterwards is bit-identical.
 
-// prior[b] of the row blocks: sf2 (value rows), then Var[d f / d x_j] = sf2 / l_j^2 (RBF), 5 sf2 / (3 l_j^2) (Matern-5/2),
-// 3 sf2 / l_j^2 (Matern-3/2)
+// prior[b] of the row blocks: sf2 (value rows), then Var[d f / d x_j] = cov::grad_prior sf2 / l_j^2
 int grad_priors(gpx_handle* h, bool with_value, double* prior) {
-  double ls[32];
+  double ls[MAX_D];
   HIPCHK(h, hipMemcpyAsync(ls, h->ls.p, (size_t)h->n_ls * sizeof(double), hipMemcpyDeviceToHost, h->st));
   HIPCHK(h, hipStreamSynchronize(h->st));
   int b = 0;
   if (with_value) prior[b++] = h->sf2;
-  const double c = h->cfg.kernel == GPX_KERNEL_RBF ? 1.0 : h->cfg.kernel == GPX_KERNEL_MATERN32 ? 3.0 : 5.0 / 3.0;
+  const double c = cov::grad_prior(h->cfg.kernel);
   for (int j = 0; j < h->d; ++j) {
     const double l = ls[h->n_ls == 1 ? 0 : j];
     prior[b++] = c * h->sf2 / (l * l);
@@ -1664,7 +1659,7 @@ int predict_grad_var(gpx_handle* h, const void* Xq, int64_t M, void* mean, void*
   const int64_t MB = std::min(pred_batch_rows(h, Mpad, 0, false), std::max<int64_t>(128, fit));
   const int64_t RB = nblk * MB;                 // rows of the largest batch
   const int64_t ldm = RB + ld_skew<T>();        // z^T V of one batch
-  double prior[33];
+  double prior[MAX_D + 1];
   int rc;
   if ((rc = grad_priors(h, with_value, prior))) return rc;
   if ((rc = ensure(h, h->Q, (size_t)M * d * E))) return rc;
@@ -1873,7 +1868,7 @@ int lml_grad_impl(gpx_handle* h, double* lml, double* grad) {
     launch_dot_rhs((const double*)h->Y.p, (const double*)h->alphaT, ld, N, k, outv + 2 * ntheta, st);
     if (P > 1 && (rc = cm->allreduce(h, outv, (size_t)ntheta, COMM_SUM))) return rc;
   }
-  double host[2 * 34 + 1];
+  double host[2 * (MAX_D + 2) + 1];
   HIPCHK(h, hipMemcpyAsync(host, outv, (size_t)(2 * ntheta + 1) * 8, hipMemcpyDeviceToHost, st));
   HIPCHK(h, hipStreamSynchronize(st));
   HIPCHK(h, hipGetLastError());
@@ -1906,7 +1901,7 @@ int mixed_fit(gpx_handle* h, const void* X, const void* y, int64_t N, int32_t d,
   if ((rc = ensure(h, h->Y64, (size_t)N * k * 8))) return rc;
   if ((rc = ensure(h, h->X32, (size_t)N * d * 4))) return rc;
   if ((rc = ensure(h, h->Y32, (size_t)N * k * 4))) return rc;
-  if ((rc = ensure(h, h->ls, 32 * 8))) return rc;
+  if ((rc = ensure(h, h->ls, MAX_D * 8))) return rc;
   hipStream_t st = h->st;
   if ((rc = copy_in(h, h->X64.p, X, (size_t)N * d * 8, mem_kind))) return rc;
   if ((rc = copy_in(h, h->Y64.p, y, (size_t)N * k * 8, mem_kind))) return rc;
@@ -2130,7 +2125,7 @@ const char* gpx_last_error(gpx_handle* h) { return h ? h->err.c_str() : g_create
 int gpx_create(gpx_handle** out, const gpx_config* cfg) try {
   if (!out || !cfg) return fail(nullptr, GPX_E_ARG, "gpx_create: null argument");
   *out = nullptr;
-  if (!known_kernel(cfg->kernel)) return fail(nullptr, GPX_E_ARG, "gpx_create: unknown kernel id");
+  if (!cov::known(cfg->kernel)) return fail(nullptr, GPX_E_ARG, "gpx_create: unknown kernel id");
   if (cfg->dtype != GPX_F64 && cfg->dtype != GPX_F32 && cfg->dtype != GPX_MIXED)
     return fail(nullptr, GPX_E_ARG, "gpx_create: unknown dtype id");
   if (cfg->refine < 0 || cfg->refine > 50) return fail(nullptr, GPX_E_ARG, "gpx_create: need 0 <= refine <= 50");
@@ -2226,7 +2221,7 @@ int gpx_fit(gpx_handle* h, const void* X, const void* y, int64_t N, int32_t d, i
             int32_t mem_kind, int64_t* info) try {
   if (!h) return GPX_E_ARG;
   if (!X || !y || !lengthscale || !info) return fail(h, GPX_E_ARG, "gpx_fit: null argument");
-  if (N <= 0 || d <= 0 || d > 32) return fail(h, GPX_E_ARG, "gpx_fit: need N > 0 and 1 <= d <= 32");
+  if (N <= 0 || d <= 0 || d > MAX_D) return fail(h, GPX_E_ARG, "gpx_fit: need N > 0 and 1 <= d <= 32");
   if (k <= 0 || k > RHS_ROWS) return fail(h, GPX_E_ARG, "gpx_fit: need 1 <= k <= 64 target columns");
   if (n_ls != 1 && n_ls != d) return fail(h, GPX_E_ARG, "gpx_fit: n_ls must be 1 or d");
   if (mem_kind != GPX_MEM_HOST && mem_kind != GPX_MEM_DEVICE)
@@ -2261,7 +2256,7 @@ int gpx_fit_predict(gpx_handle* h, const void* X, const void* y, int64_t N, int3
                     int64_t M, void* mean, void* var, int32_t mem_kind, int64_t* info) try {
   if (!h) return GPX_E_ARG;
   if (!X || !y || !lengthscale || !info || !Xq || !mean) return fail(h, GPX_E_ARG, "gpx_fit_predict: null argument");
-  if (N <= 0 || d <= 0 || d > 32 || M <= 0) return fail(h, GPX_E_ARG, "gpx_fit_predict: need N, M > 0 and 1 <= d <= 32");
+  if (N <= 0 || d <= 0 || d > MAX_D || M <= 0) return fail(h, GPX_E_ARG, "gpx_fit_predict: need N, M > 0 and 1 <= d <= 32");
   if (k <= 0 || k > RHS_ROWS) return fail(h, GPX_E_ARG, "gpx_fit_predict: need 1 <= k <= 64 target columns");
   if (n_ls != 1 && n_ls != d) return fail(h, GPX_E_ARG, "gpx_fit_predict: n_ls must be 1 or d");
   if (mem_kind != GPX_MEM_HOST && mem_kind != GPX_MEM_DEVICE) return fail(h, GPX_E_ARG, "gpx_fit_predict: bad mem_kind");
@@ -2419,7 +2414,7 @@ int gpx_predict_grad(gpx_handle* h, const void* Xq, int64_t M, void* mean, void*
   if (mem_kind != GPX_MEM_HOST && mem_kind != GPX_MEM_DEVICE) return fail(h, GPX_E_ARG, "gpx_predict_grad: bad mem_kind");
   if (!h->fitted) return fail(h, GPX_E_ARG, "gpx_predict_grad: handle has no successful fit");
   if (M > (int64_t)INT_MAX - 4096) return fail(h, GPX_E_ARG, "gpx_predict_grad: M too large");
-  if (h->cfg.kernel == GPX_KERNEL_MATERN12) return fail(h, GPX_E_UNSUPPORTED, "gpx_predict_grad: " MATERN12_NO_GRAD);
+  if (!cov::differentiable(h->cfg.kernel)) return fail(h, GPX_E_UNSUPPORTED, "gpx_predict_grad: " MATERN12_NO_GRAD);
   int rc;
   if ((rc = posterior_refused(h, "gpx_predict_grad"))) return rc;
   HIPCHK(h, hipSetDevice(h->cfg.device));
@@ -2544,9 +2539,9 @@ struct Scratch {  // a throw-away handle-like context for the host-buffer entry 
 int gpx_kernel_matrix(int32_t kernel, const double* A, int64_t na, const double* B, int64_t nb_,
                       int32_t d, const double* lengthscale, int32_t n_ls, double sf2,
                       double diag_add, double* K) try {
-  if (!A || !K || !lengthscale || na <= 0 || d <= 0 || d > 32 || (n_ls != 1 && n_ls != d))
+  if (!A || !K || !lengthscale || na <= 0 || d <= 0 || d > MAX_D || (n_ls != 1 && n_ls != d))
     return GPX_E_ARG;
-  if (!known_kernel(kernel)) return GPX_E_ARG;
+  if (!cov::known(kernel)) return GPX_E_ARG;
   const bool sym = (B == nullptr);
   const int64_t nbb = sym ? na : nb_;
   if (nbb <= 0) return GPX_E_ARG;
@@ -2559,7 +2554,7 @@ int gpx_kernel_matrix(int32_t kernel, const double* A, int64_t na, const double*
   int rc = GPX_OK;
   TCHK(hipMalloc(&dA, (size_t)na * d * 8));
   TCHK(hipMalloc(&dAs, (size_t)napad * d * 8));
-  TCHK(hipMalloc(&dls, 32 * 8));
+  TCHK(hipMalloc(&dls, MAX_D * 8));
   TCHK(hipMalloc(&dK, (size_t)napad * ld * 8));
   TCHK(hipMemcpyAsync(dA, A, (size_t)na * d * 8, hipMemcpyHostToDevice, st));
   TCHK(hipMemcpyAsync(dls, lengthscale, (size_t)n_ls * 8, hipMemcpyHostToDevice, st));
@@ -2595,10 +2590,10 @@ int gpx_kernel_grad_matrix(int32_t kernel, const double* A, int64_t na, const do
 
 int gpx_kernel_deriv_matrix(int32_t kernel, const double* A, int64_t na, const double* B, int64_t nb_, int32_t d,
                             const double* lengthscale, int32_t n_ls, double sf2, double* G) try {
-  if (!A || !B || !G || !lengthscale || na <= 0 || nb_ <= 0 || d <= 0 || d > 32 || (n_ls != 1 && n_ls != d))
+  if (!A || !B || !G || !lengthscale || na <= 0 || nb_ <= 0 || d <= 0 || d > MAX_D || (n_ls != 1 && n_ls != d))
     return GPX_E_ARG;
-  if (!known_kernel(kernel)) return GPX_E_ARG;
-  if (kernel == GPX_KERNEL_MATERN12) return fail(nullptr, GPX_E_UNSUPPORTED, "gpx_kernel_deriv_matrix: " MATERN12_NO_GRAD);
+  if (!cov::known(kernel)) return GPX_E_ARG;
+  if (!cov::differentiable(kernel)) return fail(nullptr, GPX_E_UNSUPPORTED, "gpx_kernel_deriv_matrix: " MATERN12_NO_GRAD);
   Scratch sc;
   if (!sc.ok) return GPX_E_HIP;
   hipStream_t st = sc.h.st;
@@ -2610,7 +2605,7 @@ int gpx_kernel_deriv_matrix(int32_t kernel, const double* A, int64_t na, const d
   TCHK(hipMalloc(&dB, (size_t)nb_ * d * 8));
   TCHK(hipMalloc(&dAs, (size_t)napad * d * 8));
   TCHK(hipMalloc(&dBs, (size_t)nbpad * d * 8));
-  TCHK(hipMalloc(&dls, 32 * 8));
+  TCHK(hipMalloc(&dls, MAX_D * 8));
   TCHK(hipMalloc(&dG, (size_t)d * napad * ld * 8));
   TCHK(hipMemcpyAsync(dA, A, (size_t)na * d * 8, hipMemcpyHostToDevice, st));
   TCHK(hipMemcpyAsync(dB, B, (size_t)nb_ * d * 8, hipMemcpyHostToDevice, st));

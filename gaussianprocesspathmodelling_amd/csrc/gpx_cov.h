@@ -1,0 +1,113 @@
+// gpx_cov.h — the covariance families (GPX_KERNEL_*, include/gpx.h), defined once for every HIP kernel that evaluates
+// k(r) and for the host.  With u = x / l (per dimension), r^2 = sum_j (u_j - u'_j)^2 and d_c = (x_c - x'_c) / l_c:
+//
+//   id  family      s        poly(s)          dpoly(s)        e
+//   0   RBF         -        1                1               exp(-r^2 / 2)
+//   1   Matern-5/2  sqrt5 r  1 + s + s^2/3    (5/3)(1 + s)    exp(-s)
+//   2   Matern-3/2  sqrt3 r  1 + s            3               exp(-s)
+//   3   Matern-1/2  r        1                -               exp(-s)
+//
+//   v  = sf2 (poly(s) e)    the value sf2 k(r)
+//   g  = sf2 (dpoly(s) e)   d k / d x*_j = -g (u*_j - u_j) / l_j   (RBF: g = v)
+//   kd = g                  d K / d log l_c = kd d_c^2;  Matern-1/2: kd = v / r, 0 at r = 0 (kd d_c^2 <= sf2 r -> 0)
+//
+// Every kernel evaluates these in this one operation order (value / value_g / value_kd): for one element type and
+// exponential, the value rows of the derivative build and the kf of the LML gradient are bit for bit the kernel build's
+// K.  Matern-1/2 has no derivative at r = 0: it has no g, and no derivative kernel is instantiated for it.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <type_traits>
+
+#include "../../include/gpx.h"
+
+namespace gpx {
+namespace cov {
+
+constexpr bool known(int kernel) { return kernel >= GPX_KERNEL_RBF && kernel <= GPX_KERNEL_MATERN12; }
+constexpr bool differentiable(int kernel) { return known(kernel) && kernel != GPX_KERNEL_MATERN12; }
+// prior Var[d f / d x_j] = grad_prior sf2 / l_j^2, i.e. dpoly(0), of a differentiable family
+constexpr double grad_prior(int kernel) {
+  return kernel == GPX_KERNEL_MATERN52 ? 5.0 / 3.0 : kernel == GPX_KERNEL_MATERN32 ? 3.0 : 1.0;
+}
+
+constexpr double SQRT5 = 2.23606797749978969640917366873128;
+constexpr double SQRT3 = 1.73205080756887729352744634150587;
+
+struct Exp {
+  template <typename T>
+  __device__ __forceinline__ T operator()(T x) const { return exp(x); }
+};
+
+template <int KERNEL, typename T>
+__device__ __forceinline__ T svar(T r2) {  // s (unused by RBF)
+  constexpr double scale = KERNEL == GPX_KERNEL_MATERN52 ? SQRT5 : KERNEL == GPX_KERNEL_MATERN32 ? SQRT3 : 1.0;
+  return KERNEL == GPX_KERNEL_RBF ? (T)0 : (T)scale * sqrt(r2);
+}
+
+template <int KERNEL, typename T>
+__device__ __forceinline__ T earg(T r2, T s) {  // the argument of e
+  return KERNEL == GPX_KERNEL_RBF ? (T)-0.5 * r2 : -s;
+}
+
+template <int KERNEL, typename T>
+__device__ __forceinline__ T poly(T s) {
+  if constexpr (KERNEL == GPX_KERNEL_MATERN52) return (T)1 + s + s * s / (T)3;
+  else if constexpr (KERNEL == GPX_KERNEL_MATERN32) return (T)1 + s;
+  else return (T)1;
+}
+
+template <int KERNEL, typename T>
+__device__ __forceinline__ T dpoly(T s) {
+  static_assert(differentiable(KERNEL), "Matern-1/2 is not differentiable");
+  if constexpr (KERNEL == GPX_KERNEL_MATERN52) return (T)(5.0 / 3.0) * ((T)1 + s);
+  else if constexpr (KERNEL == GPX_KERNEL_MATERN32) return (T)3;
+  else return (T)1;
+}
+
+template <int KERNEL, typename T, typename E = Exp>
+__device__ __forceinline__ T value(T r2, T sf2, E ex = {}) {
+  const T s = svar<KERNEL>(r2);
+  return sf2 * (poly<KERNEL>(s) * ex(earg<KERNEL>(r2, s)));
+}
+
+template <int KERNEL, typename T, typename E = Exp>
+__device__ __forceinline__ void value_g(T r2, T sf2, T& v, T& g, E ex = {}) {
+  const T s = svar<KERNEL>(r2);
+  const T e = ex(earg<KERNEL>(r2, s));
+  v = sf2 * (poly<KERNEL>(s) * e);
+  g = sf2 * (dpoly<KERNEL>(s) * e);
+}
+
+template <int KERNEL, typename T, typename E = Exp>
+__device__ __forceinline__ void value_kd(T r2, T sf2, T& v, T& kd, E ex = {}) {
+  if constexpr (KERNEL == GPX_KERNEL_MATERN12) {
+    const T r = svar<KERNEL>(r2);
+    v = sf2 * (poly<KERNEL>(r) * ex(earg<KERNEL>(r2, r)));
+    kd = r > (T)0 ? v / r : (T)0;
+  } else {
+    value_g<KERNEL>(r2, sf2, v, kd, ex);
+  }
+}
+
+// f(std::integral_constant<int, id>{}) for the family `kernel` (the API refuses unknown ids before any launch)
+template <typename F>
+void dispatch(int kernel, F&& f) {
+  switch (kernel) {
+    case GPX_KERNEL_RBF: f(std::integral_constant<int, GPX_KERNEL_RBF>{}); break;
+    case GPX_KERNEL_MATERN52: f(std::integral_constant<int, GPX_KERNEL_MATERN52>{}); break;
+    case GPX_KERNEL_MATERN32: f(std::integral_constant<int, GPX_KERNEL_MATERN32>{}); break;
+    default: f(std::integral_constant<int, GPX_KERNEL_MATERN12>{}); break;
+  }
+}
+
+// the same over the differentiable families: f is not instantiated for the others, whose ids call nothing
+template <typename F>
+void dispatch_differentiable(int kernel, F&& f) {
+  dispatch(kernel, [&](auto K) {
+    if constexpr (differentiable(K)) f(K);
+  });
+}
+
+}  // namespace cov
+}  // namespace gpx

@@ -1,46 +1,21 @@
 // gpx_deriv.hip — the kernels of the posterior gradient (gpx_predict_grad / gpx_kernel_grad_matrix / gpx_kernel_deriv_matrix, include/gpx.h).
 //
-// With u = x / l (per dimension), r^2 = sum_j (u*_j - u_j)^2 and one exponential per (query, training) pair:
-//   RBF         k = sf2 e^(-r^2/2)                         d k / d x*_j = -(u*_j - u_j) / l_j * k
-//   Matern-5/2  k = sf2 (1 + s + s^2/3) e^(-s), s = sqrt5 r  d k / d x*_j = -(u*_j - u_j) / l_j * sf2 5/3 (1 + s) e^(-s)
-//   Matern-3/2  k = sf2 (1 + s) e^(-s), s = sqrt3 r          d k / d x*_j = -(u*_j - u_j) / l_j * sf2 3 e^(-s)
-// (smooth at r = 0, no division by r).  Matern-1/2 has no derivative at r = 0: the launchers below do nothing for it
-// (gpx_api.hip refuses the calls before any launch).  Everything heavy beyond these kernels is the existing engine (gpx_api.hip):
+// With g of the family (gpx_cov.h), d k / d x*_j = -g (u*_j - u_j) / l_j and u = x / l: one exponential per
+// (query, training) pair.  Matern-1/2 has no derivative at r = 0: the launchers below do nothing for it (gpx_api.hip
+// refuses the calls before any launch).  Everything heavy beyond these kernels is the existing engine (gpx_api.hip):
 //   mean only:      dmean = dK* alpha, matrix-free (kgrad_matvec_kernel + kgrad_finish_kernel), no solve
 //   with variance:  V = [K*; d_1 K*; ...; d_d K*] (kgrad_build_kernel) -> ONE forward solve over all rows -> ONE split-K
 //                   z^T V (mean and dmean together) -> row norms with a per-row-block prior -> unpack
 // All stores are plain vector stores; every reduction runs in a fixed order (bit-reproducible).
 #include <algorithm>
 
+#include "gpx_cov.h"
 #include "gpx_internal.h"
 
 namespace gpx {
 namespace {
 
 constexpr int GT = 64;      // tile edge of the build, query rows per workgroup of the matrix-free product
-constexpr int GMAXD = 32;   // max input dimension (as kbuild_kernel's MAXD)
-constexpr double SQRT5 = 2.23606797749978969640917366873128;
-constexpr double SQRT3 = 1.73205080756887729352744634150587;
-
-// v = sf2 k(r^2) (bit for bit kbuild_kernel's value) and g with d k / d x*_j = -g (u*_j - u_j) / l_j
-template <int KERNEL, typename T>
-__device__ __forceinline__ void kval_grad(T r2, T sf2, T& v, T& g) {
-  static_assert(KERNEL <= 2, "Matern-1/2 is not differentiable");
-  if (KERNEL == 0) {
-    v = sf2 * exp((T)-0.5 * r2);
-    g = v;
-  } else if (KERNEL == 2) {
-    const T s = (T)SQRT3 * sqrt(r2);
-    const T e = exp(-s);
-    v = sf2 * (((T)1 + s) * e);
-    g = sf2 * ((T)3 * e);
-  } else {
-    const T s = (T)SQRT5 * sqrt(r2);
-    const T e = exp(-s);
-    v = sf2 * (((T)1 + s + s * s / (T)3) * e);
-    g = sf2 * ((T)(5.0 / 3.0) * ((T)1 + s) * e);
-  }
-}
 
 // Row blocks of V (each mpad rows, ld): [K* if with_value] then d_1 K* ... d_d K*; tile (ti, tj) of 64 x 64 per
 // workgroup, the same lane map, padding (zero beyond m rows / n columns) and non-temporal 16-byte stores as
@@ -51,9 +26,9 @@ __global__ __launch_bounds__(256) void kgrad_build_kernel(const T* __restrict__ 
                                                          const double* __restrict__ ls, int n_ls, int with_value,
                                                          T* __restrict__ V, int64_t ld, int64_t mpad) {
   const int d = (D > 0) ? D : d_rt;
-  __shared__ T xa[GT * (D > 0 ? D : GMAXD)];
-  __shared__ T xb[GT * (D > 0 ? D : GMAXD)];
-  __shared__ T il[GMAXD];
+  __shared__ T xa[GT * (D > 0 ? D : MAX_D)];
+  __shared__ T xb[GT * (D > 0 ? D : MAX_D)];
+  __shared__ T il[MAX_D];
   const int ti = (int)(blockIdx.x / tiles_n), tj = (int)(blockIdx.x - (int64_t)ti * tiles_n);
   const int64_t i0 = (int64_t)ti * GT, j0 = (int64_t)tj * GT;
   const int tid = threadIdx.x;
@@ -80,8 +55,8 @@ __global__ __launch_bounds__(256) void kgrad_build_kernel(const T* __restrict__ 
       s1 += e1 * e1;
     }
     T v0, g0, v1, g1;
-    kval_grad<KERNEL, T>(s0, sf2, v0, g0);
-    kval_grad<KERNEL, T>(s1, sf2, v1, g1);
+    cov::value_g<KERNEL>(s0, sf2, v0, g0);
+    cov::value_g<KERNEL>(s1, sf2, v1, g1);
     const bool ok0 = row < m && col0 < n, ok1 = row < m && col1 < n;
     T* out = V + row * ld + col0;
     if (with_value) {
@@ -108,7 +83,7 @@ __global__ __launch_bounds__(256) void kgrad_matvec_kernel(const T* __restrict__
                                                           int64_t npad, int64_t chunk, int d_rt, T sf2,
                                                           const T* __restrict__ alphaT, int64_t lda, int k,
                                                           T* __restrict__ part, int64_t ldp) {
-  constexpr int DD = D > 0 ? D : GMAXD;
+  constexpr int DD = D > 0 ? D : MAX_D;
   const int d = (D > 0) ? D : d_rt;
   __shared__ T xb[GT * DD];
   __shared__ T ab[KC * GT];
@@ -144,7 +119,7 @@ __global__ __launch_bounds__(256) void kgrad_matvec_kernel(const T* __restrict__
           r2 += df[c] * df[c];
         }
       T v, gf;
-      kval_grad<KERNEL, T>(r2, sf2, v, gf);
+      cov::value_g<KERNEL>(r2, sf2, v, gf);
 #pragma unroll
       for (int q = 0; q < KC; ++q) {
         const T ga = gf * ab[q * GT + jj];
@@ -187,7 +162,7 @@ __global__ __launch_bounds__(256) void kgrad_finish_kernel(const T* __restrict__
 }
 
 struct Priors {
-  double p[GMAXD + 1];
+  double p[MAX_D + 1];
 };
 
 __device__ __forceinline__ double block_sum(double v, double* red) {
@@ -299,12 +274,7 @@ void matvec_d(dim3 grid, int KC, const T* As, const T* Bs, int64_t npad, int64_t
 template <typename T>
 void launch_kgrad_build(int kernel, const T* As, int64_t m, int64_t mpad, const T* Bs, int64_t n, int64_t npad, int d,
                         double sf2, const double* ls, int n_ls, int with_value, T* V, int64_t ld, hipStream_t st) {
-  switch (kernel) {
-    case 0: build_d<T, 0>(As, m, mpad, Bs, n, npad, d, sf2, ls, n_ls, with_value, V, ld, st); break;
-    case 1: build_d<T, 1>(As, m, mpad, Bs, n, npad, d, sf2, ls, n_ls, with_value, V, ld, st); break;
-    case 2: build_d<T, 2>(As, m, mpad, Bs, n, npad, d, sf2, ls, n_ls, with_value, V, ld, st); break;
-    default: break;  // Matern-1/2: refused by the API
-  }
+  cov::dispatch_differentiable(kernel, [&](auto fam) { build_d<T, fam>(As, m, mpad, Bs, n, npad, d, sf2, ls, n_ls, with_value, V, ld, st); });
 }
 
 void kgrad_matvec_shape(int64_t M, int64_t npad, int d, int k, int* KC, int* S, int64_t* chunk) {
@@ -328,14 +298,11 @@ void launch_kgrad_matvec(int kernel, const T* As, int64_t M, const T* Bs, int64_
   kgrad_matvec_shape(M, npad, d, k, &KC, &S, &chunk);
   const int64_t mpad = round_up(M, GT);
   const dim3 grid((unsigned)(mpad / GT), (unsigned)((k + KC - 1) / KC), (unsigned)S);
-  switch (kernel) {
-    case 0: matvec_d<T, 0>(grid, KC, As, Bs, npad, chunk, d, sf2, alphaT, lda, k, part, mpad, st); break;
-    case 1: matvec_d<T, 1>(grid, KC, As, Bs, npad, chunk, d, sf2, alphaT, lda, k, part, mpad, st); break;
-    case 2: matvec_d<T, 2>(grid, KC, As, Bs, npad, chunk, d, sf2, alphaT, lda, k, part, mpad, st); break;
-    default: return;  // Matern-1/2: refused by the API
-  }
-  hipLaunchKernelGGL(kgrad_finish_kernel<T>, dim3(grid_for(M * d * k)), dim3(256), 0, st, part, mpad, S, M, d, k, ls,
-                     n_ls, dmean);
+  cov::dispatch_differentiable(kernel, [&](auto fam) {
+    matvec_d<T, fam>(grid, KC, As, Bs, npad, chunk, d, sf2, alphaT, lda, k, part, mpad, st);
+    hipLaunchKernelGGL(kgrad_finish_kernel<T>, dim3(grid_for(M * d * k)), dim3(256), 0, st, part, mpad, S, M, d, k, ls,
+                       n_ls, dmean);
+  });
 }
 
 template <typename T>
@@ -343,7 +310,7 @@ void launch_grad_norms(const T* V, int64_t ld, int64_t mp, int64_t mv, int nblk,
                        T* out, hipStream_t st) {
   if (mv <= 0 || nblk <= 0) return;
   Priors pr{};
-  for (int b = 0; b < nblk && b <= GMAXD; ++b) pr.p[b] = prior[b];
+  for (int b = 0; b < nblk && b <= MAX_D; ++b) pr.p[b] = prior[b];
   hipLaunchKernelGGL(grad_norms_kernel<T>, dim3((unsigned)mv, (unsigned)nblk), dim3(256), 0, st, V, ld, mp, ncols, pr,
                      out);
 }

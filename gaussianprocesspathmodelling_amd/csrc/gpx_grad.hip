@@ -5,8 +5,7 @@
 //
 //     dLML/dlog(theta) = 1/2 sum_ij (sum_c alpha_ic alpha_jc - k K^-1_ij) (dK/dlog theta)_ij
 //
-//   dK/dlog l_c  = kd_ij * ((x_ic - x_jc) / l_c)^2   RBF: kd = Kf;  Matern-5/2: kd = sf2 (5/3)(1+s) e^-s;
-//                                                    Matern-3/2: kd = 3 sf2 e^-s;  Matern-1/2: kd = sf2 e^-r / r (0 at r = 0)
+//   dK/dlog l_c  = kd_ij * ((x_ic - x_jc) / l_c)^2   (kd of the family: gpx_cov.h)
 //   dK/dlog sf2  = Kf_ij = sf2 k(r_ij)
 //   dK/dlog sn2  = sn2 delta_ij
 //
@@ -18,39 +17,12 @@
 // (as the kernel build does), multiplied in, reduced over the workgroup and written as one
 // partial sum per (tile, theta).  The alpha alpha^T term is a separate O(N^2 k) pass of the
 // same epilogue over 64x64 tiles.  Partials are summed in a fixed order: deterministic.
+#include "gpx_cov.h"
 #include "gpx_internal.h"
 #include "gpx_tile.h"
 
 namespace gpx {
 namespace {
-
-constexpr double SQRT5 = 2.23606797749978969640917366873128;
-constexpr double SQRT3 = 1.73205080756887729352744634150587;
-constexpr int GMAXD = 32;
-
-// kf = sf2 k(r), kd = the factor of d_c^2 in dK/dlog l_c; KERNEL = GPX_KERNEL_* (0 RBF, 1 Matern-5/2, 2 Matern-3/2,
-// 3 Matern-1/2).  Matern-1/2: kd = sf2 e^-r / r, set to 0 at r = 0, where kd d_c^2 <= sf2 r e^-r -> 0.
-template <int KERNEL>
-__device__ __forceinline__ void kvals(double r2, double sf2, double& kf, double& kd) {
-  if (KERNEL == 0) {
-    kf = sf2 * exp(-0.5 * r2);
-    kd = kf;
-  } else if (KERNEL == 2) {
-    const double s = SQRT3 * sqrt(r2);
-    const double e = exp(-s);
-    kf = sf2 * ((1.0 + s) * e);
-    kd = 3.0 * (sf2 * e);
-  } else if (KERNEL == 3) {
-    const double r = sqrt(r2);
-    kf = sf2 * exp(-r);
-    kd = r > 0.0 ? kf / r : 0.0;
-  } else {
-    const double s = SQRT5 * sqrt(r2);
-    const double e = sf2 * exp(-s);
-    kf = (1.0 + s + s * s / 3.0) * e;
-    kd = (5.0 / 3.0) * (1.0 + s) * e;
-  }
-}
 
 // sum over the 256 threads of a workgroup, every thread gets the result (fixed order)
 __device__ __forceinline__ double wg_sum(double v, double* red) {
@@ -111,7 +83,7 @@ __global__ __launch_bounds__(256, 2) void kinv_trace_kernel(const double* __rest
   // gemm_tile_g ends with a barrier: the staging buffers are free -> scaled points of the
   // tile's rows and columns
   double* xa = smem;
-  double* xb = smem + BT * GMAXD;
+  double* xb = smem + BT * MAX_D;
   const int tid = threadIdx.x;
   for (int e = tid; e < BT * d; e += 256) {
     xa[e] = Xs[(int64_t)ti * BT * d + e];
@@ -147,7 +119,7 @@ __global__ __launch_bounds__(256, 2) void kinv_trace_kernel(const double* __rest
         double v = acc[m][nn][r];
         if (gi >= n || gj >= n) v = 0.0;  // padded rows / columns are not part of K
         double kf, kd;
-        kvals<KERNEL>(r2, sf2, kf, kd);
+        cov::value_kd<KERNEL>(r2, sf2, kf, kd);
         Sf += v * kf;
         if (gi == gj) Sn += v;
         const double t = v * kd;
@@ -208,8 +180,8 @@ __global__ __launch_bounds__(256) void alpha_quad_kernel(const double* __restric
                                                         int ard, double sf2, double sn2,
                                                         double* __restrict__ part, int ntheta) {
   constexpr int KT = 64;
-  __shared__ double xa[KT * GMAXD];
-  __shared__ double xb[KT * GMAXD];
+  __shared__ double xa[KT * MAX_D];
+  __shared__ double xb[KT * MAX_D];
   __shared__ double red[4];
   const int d = (D > 0) ? D : d_rt;
   int ti, tj;
@@ -253,7 +225,7 @@ __global__ __launch_bounds__(256) void alpha_quad_kernel(const double* __restric
       double v = wt[r][q];
       if (gi >= n || gj >= n) v = 0.0;
       double kf, kd;
-      kvals<KERNEL>(r2, sf2, kf, kd);
+      cov::value_kd<KERNEL>(r2, sf2, kf, kd);
       Sf += v * kf;
       if (gi == gj) Sn += v;
       const double t = v * kd;
@@ -365,34 +337,19 @@ void launch_set_diag_one(double* A, int64_t lda, int64_t n, hipStream_t st) {
 
 void launch_kinv_trace(int kernel, const double* ZT, int64_t ld, int64_t npad, int64_t n, const double* Xs, int d,
                        int ard, double sf2, double sn2, double* part, int ntheta, int P, int rank, hipStream_t st) {
-  switch (kernel) {
-    case 0: launch_kinv_trace_k<0>(ZT, ld, npad, n, Xs, d, ard, sf2, sn2, part, ntheta, P, rank, 0, 0, 0, 0, 0, st); break;
-    case 1: launch_kinv_trace_k<1>(ZT, ld, npad, n, Xs, d, ard, sf2, sn2, part, ntheta, P, rank, 0, 0, 0, 0, 0, st); break;
-    case 2: launch_kinv_trace_k<2>(ZT, ld, npad, n, Xs, d, ard, sf2, sn2, part, ntheta, P, rank, 0, 0, 0, 0, 0, st); break;
-    default: launch_kinv_trace_k<3>(ZT, ld, npad, n, Xs, d, ard, sf2, sn2, part, ntheta, P, rank, 0, 0, 0, 0, 0, st); break;
-  }
+  cov::dispatch(kernel, [&](auto fam) { launch_kinv_trace_k<fam>(ZT, ld, npad, n, Xs, d, ard, sf2, sn2, part, ntheta, P, rank, 0, 0, 0, 0, 0, st); });
 }
 
 void launch_kinv_trace_cols(int kernel, const double* ZTc, int64_t ldc, int64_t npad, int64_t n, const double* Xs,
                             int d, int ard, double sf2, double sn2, double* part, int ntheta, int nb, int P, int rank,
                             int64_t ncols, int snake, hipStream_t st) {
-  switch (kernel) {
-    case 0: launch_kinv_trace_k<0>(ZTc, ldc, npad, n, Xs, d, ard, sf2, sn2, part, ntheta, 1, 0, nb, P, rank, ncols, snake, st); break;
-    case 1: launch_kinv_trace_k<1>(ZTc, ldc, npad, n, Xs, d, ard, sf2, sn2, part, ntheta, 1, 0, nb, P, rank, ncols, snake, st); break;
-    case 2: launch_kinv_trace_k<2>(ZTc, ldc, npad, n, Xs, d, ard, sf2, sn2, part, ntheta, 1, 0, nb, P, rank, ncols, snake, st); break;
-    default: launch_kinv_trace_k<3>(ZTc, ldc, npad, n, Xs, d, ard, sf2, sn2, part, ntheta, 1, 0, nb, P, rank, ncols, snake, st); break;
-  }
+  cov::dispatch(kernel, [&](auto fam) { launch_kinv_trace_k<fam>(ZTc, ldc, npad, n, Xs, d, ard, sf2, sn2, part, ntheta, 1, 0, nb, P, rank, ncols, snake, st); });
 }
 
 void launch_alpha_quad(int kernel, const double* alphaT, int64_t ld, int k, int64_t npad, int64_t n,
                        const double* Xs, int d, int ard, double sf2, double sn2, double* part, int ntheta,
                        hipStream_t st) {
-  switch (kernel) {
-    case 0: launch_alpha_quad_k<0>(alphaT, ld, k, npad, n, Xs, d, ard, sf2, sn2, part, ntheta, st); break;
-    case 1: launch_alpha_quad_k<1>(alphaT, ld, k, npad, n, Xs, d, ard, sf2, sn2, part, ntheta, st); break;
-    case 2: launch_alpha_quad_k<2>(alphaT, ld, k, npad, n, Xs, d, ard, sf2, sn2, part, ntheta, st); break;
-    default: launch_alpha_quad_k<3>(alphaT, ld, k, npad, n, Xs, d, ard, sf2, sn2, part, ntheta, st); break;
-  }
+  cov::dispatch(kernel, [&](auto fam) { launch_alpha_quad_k<fam>(alphaT, ld, k, npad, n, Xs, d, ard, sf2, sn2, part, ntheta, st); });
 }
 
 void launch_reduce_partials(const double* part, int64_t ntile, int ntheta, double scale, double* out,

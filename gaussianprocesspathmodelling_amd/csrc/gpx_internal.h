@@ -9,6 +9,7 @@ namespace gpx {
 
 constexpr int KB = 64;      // innermost Cholesky block (one-workgroup POTF2 + inverse)
 constexpr int TILE = 128;   // trailing-update tile; every padded dimension is a multiple
+constexpr int MAX_D = 32;   // max input dimension d (the kernels stage points in LDS arrays of this width)
 // Leading-dimension skew against power-of-two strides: ONE 128-byte line, so that every row of
 // every matrix starts on a 128-byte boundary (hipMalloc bases are 256-byte aligned; all padded
 // dimensions are multiples of 64 elements).  trsm_rlt_kernel DEPENDS on this: it round-trips a

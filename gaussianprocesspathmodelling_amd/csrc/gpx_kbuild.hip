@@ -8,31 +8,13 @@
 // once in LDS, each lane writes 16-byte (2 x f64) pieces so a half-wave covers 512
 // contiguous bytes of one row.  Algorithmic traffic: 8 B per entry written, the
 // points (N*d*8 B) read once per tile row/column from L2.
+#include "gpx_cov.h"
 #include "gpx_internal.h"
 
 namespace gpx {
 namespace {
 
 constexpr int KT = 64;      // tile edge
-constexpr int MAXD = 32;    // max input dimension staged in LDS
-constexpr double SQRT5 = 2.23606797749978969640917366873128;
-constexpr double SQRT3 = 1.73205080756887729352744634150587;
-
-// KERNEL = GPX_KERNEL_*: 0 RBF, 1 Matern-5/2, 2 Matern-3/2, 3 Matern-1/2
-template <int KERNEL, typename T>
-__device__ __forceinline__ T kfun(T r2, T sf2) {
-  if (KERNEL == 0) {
-    return sf2 * exp((T)-0.5 * r2);
-  } else if (KERNEL == 1) {
-    const T s = (T)SQRT5 * sqrt(r2);
-    return sf2 * (((T)1 + s + s * s / (T)3) * exp(-s));
-  } else if (KERNEL == 2) {
-    const T s = (T)SQRT3 * sqrt(r2);
-    return sf2 * (((T)1 + s) * exp(-s));
-  } else {
-    return sf2 * exp(-sqrt(r2));
-  }
-}
 
 template <typename T>
 __global__ __launch_bounds__(256) void scale_points_kernel(const T* __restrict__ X, int64_t n,
@@ -64,8 +46,8 @@ __global__ __launch_bounds__(256) void kbuild_kernel(const T* __restrict__ As, i
                                                     int64_t ld) {
   const int d = (D > 0) ? D : d_rt;
   // LDS sized by the instantiation (d = 3: 2 x 1.5 KB, not 2 x 16 KB): the occupancy is then the waves', not the LDS's
-  __shared__ T xa[KT * (D > 0 ? D : MAXD)];
-  __shared__ T xb[KT * (D > 0 ? D : MAXD)];
+  __shared__ T xa[KT * (D > 0 ? D : MAX_D)];
+  __shared__ T xb[KT * (D > 0 ? D : MAX_D)];
   int ti, tj;
   if (SYM) {
     tri_coords((int64_t)blockIdx.x, ti, tj);
@@ -82,7 +64,7 @@ __global__ __launch_bounds__(256) void kbuild_kernel(const T* __restrict__ As, i
   __syncthreads();
   const int c2 = (tid & 31) * 2;
   const int rg = tid >> 5;
-  T bj0[D > 0 ? D : MAXD], bj1[D > 0 ? D : MAXD];
+  T bj0[D > 0 ? D : MAX_D], bj1[D > 0 ? D : MAX_D];
   if (D > 0) {
 #pragma unroll
     for (int c = 0; c < D; ++c) {
@@ -112,7 +94,7 @@ __global__ __launch_bounds__(256) void kbuild_kernel(const T* __restrict__ As, i
         s1 += e1 * e1;
       }
     }
-    T v0 = kfun<KERNEL, T>(s0, sf2), v1 = kfun<KERNEL, T>(s1, sf2);
+    T v0 = cov::value<KERNEL>(s0, sf2), v1 = cov::value<KERNEL>(s1, sf2);
     if (SYM) {
       if (row == col0) v0 += diag_add;
       if (row == col1) v1 += diag_add;
@@ -160,24 +142,14 @@ void launch_kbuild_sym(int kernel, const T* Xs, int64_t n, int64_t npad, int d, 
                        double diag_add, T* K, int64_t ld, hipStream_t st) {
   const int64_t TT = npad / KT;
   const int64_t nblocks = TT * (TT + 1) / 2;
-  switch (kernel) {
-    case 0: dispatch_d<T, 0, true>(Xs, n, Xs, n, d, nblocks, (int)TT, sf2, diag_add, K, ld, st); break;
-    case 1: dispatch_d<T, 1, true>(Xs, n, Xs, n, d, nblocks, (int)TT, sf2, diag_add, K, ld, st); break;
-    case 2: dispatch_d<T, 2, true>(Xs, n, Xs, n, d, nblocks, (int)TT, sf2, diag_add, K, ld, st); break;
-    default: dispatch_d<T, 3, true>(Xs, n, Xs, n, d, nblocks, (int)TT, sf2, diag_add, K, ld, st); break;
-  }
+  cov::dispatch(kernel, [&](auto fam) { dispatch_d<T, fam, true>(Xs, n, Xs, n, d, nblocks, (int)TT, sf2, diag_add, K, ld, st); });
 }
 
 template <typename T>
 void launch_kbuild_cross(int kernel, const T* As, int64_t m, int64_t mpad, const T* Bs, int64_t n,
                          int64_t npad, int d, double sf2, T* K, int64_t ld, hipStream_t st) {
   const int64_t tm = mpad / KT, tn = npad / KT;
-  switch (kernel) {
-    case 0: dispatch_d<T, 0, false>(As, m, Bs, n, d, tm * tn, (int)tn, sf2, 0.0, K, ld, st); break;
-    case 1: dispatch_d<T, 1, false>(As, m, Bs, n, d, tm * tn, (int)tn, sf2, 0.0, K, ld, st); break;
-    case 2: dispatch_d<T, 2, false>(As, m, Bs, n, d, tm * tn, (int)tn, sf2, 0.0, K, ld, st); break;
-    default: dispatch_d<T, 3, false>(As, m, Bs, n, d, tm * tn, (int)tn, sf2, 0.0, K, ld, st); break;
-  }
+  cov::dispatch(kernel, [&](auto fam) { dispatch_d<T, fam, false>(As, m, Bs, n, d, tm * tn, (int)tn, sf2, 0.0, K, ld, st); });
 }
 
 #define GPX_INSTANTIATE_KBUILD(T)                                                                     \

@@ -7,14 +7,12 @@
 // and the posterior mean is K* alpha in fp64 through the same matrix-free product.  The
 // reference has no counterpart (GPmap.py has no GP code); restated by tests against the fp64
 // oracle (oracle/gp_oracle.py).
+#include "gpx_cov.h"
 #include "gpx_internal.h"
 
 namespace gpx {
 namespace {
 
-constexpr double SQRT5 = 2.23606797749978969640917366873128;
-constexpr double SQRT3 = 1.73205080756887729352744634150587;
-constexpr int XMAXD = 32;
 constexpr int KMAX = 8;  // target columns of the mixed mode
 
 // exp(x) for x <= 0, branch-free: Cody-Waite reduction x = n ln2 + r, |r| <= ln2 / 2, degree-13 Taylor
@@ -23,39 +21,28 @@ constexpr int KMAX = 8;  // target columns of the mixed mode
 // products of the mixed mode regenerate N^2 kernel values per pass.  Measured (round 3, N = 65536, six
 // refinement iterations): 193 -> 178 ms — the pass is a smaller part of an iteration than the two 64-row
 // triangular solves through the fp32 factor.  Relative error 2.2e-16 (checked against numpy over [-630, 0]).
-__device__ __forceinline__ double exp_nonpos(double x) {
-  const double n = rint(x * 1.4426950408889634074);
-  double r = fma(n, -6.93147180369123816490e-01, x);  // ln2 hi
-  r = fma(n, -1.90821492927058770002e-10, r);         // ln2 lo
-  double p = 1.0 / 6227020800.0;                      // 1 / 13!
-  p = fma(p, r, 1.0 / 479001600.0);
-  p = fma(p, r, 1.0 / 39916800.0);
-  p = fma(p, r, 1.0 / 3628800.0);
-  p = fma(p, r, 1.0 / 362880.0);
-  p = fma(p, r, 1.0 / 40320.0);
-  p = fma(p, r, 1.0 / 5040.0);
-  p = fma(p, r, 1.0 / 720.0);
-  p = fma(p, r, 1.0 / 120.0);
-  p = fma(p, r, 1.0 / 24.0);
-  p = fma(p, r, 1.0 / 6.0);
-  p = fma(p, r, 0.5);
-  p = fma(p, r, 1.0);
-  p = fma(p, r, 1.0);
-  return ldexp(p, (int)n);
-}
-
-// KERNEL = GPX_KERNEL_*: 0 RBF, 1 Matern-5/2, 2 Matern-3/2, 3 Matern-1/2
-template <int KERNEL>
-__device__ __forceinline__ double kval(double r2, double sf2) {
-  if (KERNEL == 0) return sf2 * exp_nonpos(-0.5 * r2);
-  if (KERNEL == 3) return sf2 * exp_nonpos(-sqrt(r2));
-  if (KERNEL == 2) {
-    const double s = SQRT3 * sqrt(r2);
-    return sf2 * ((1.0 + s) * exp_nonpos(-s));
+struct ExpNonpos {
+  __device__ __forceinline__ double operator()(double x) const {
+    const double n = rint(x * 1.4426950408889634074);
+    double r = fma(n, -6.93147180369123816490e-01, x);  // ln2 hi
+    r = fma(n, -1.90821492927058770002e-10, r);         // ln2 lo
+    double p = 1.0 / 6227020800.0;                      // 1 / 13!
+    p = fma(p, r, 1.0 / 479001600.0);
+    p = fma(p, r, 1.0 / 39916800.0);
+    p = fma(p, r, 1.0 / 3628800.0);
+    p = fma(p, r, 1.0 / 362880.0);
+    p = fma(p, r, 1.0 / 40320.0);
+    p = fma(p, r, 1.0 / 5040.0);
+    p = fma(p, r, 1.0 / 720.0);
+    p = fma(p, r, 1.0 / 120.0);
+    p = fma(p, r, 1.0 / 24.0);
+    p = fma(p, r, 1.0 / 6.0);
+    p = fma(p, r, 0.5);
+    p = fma(p, r, 1.0);
+    p = fma(p, r, 1.0);
+    return ldexp(p, (int)n);
   }
-  const double s = SQRT5 * sqrt(r2);
-  return sf2 * ((1.0 + s + s * s / 3.0) * exp_nonpos(-s));
-}
+};
 
 // outT[c][i] = (y ? y[i*k + c] : 0) + sign * (sum_j sf2 k(a_i, b_j) alphaT[c][j] + diag * alphaT[c][i])
 // for i < m (0 beyond), c < k <= KMAX.  As (mpad x d), Bs (npad x d) scaled points, zero rows beyond
@@ -70,13 +57,13 @@ __global__ __launch_bounds__(256) void kmatvec_kernel(const double* __restrict__
                                                      double sign, double* __restrict__ outT, int64_t ldo) {
   // sized by the instantiation (round 3): with KMAX-sized buffers (146 KB) ONE workgroup fitted a CU — one wave per
   // SIMD walking a latency chain of global load -> barrier -> 16 kernel values -> barrier; 3.5 KB at k = 1, d = 3
-  __shared__ double xb[64 * (D > 0 ? D : XMAXD)];
+  __shared__ double xb[64 * (D > 0 ? D : MAX_D)];
   __shared__ double ab[KC * 64];
   __shared__ double red[3 * 64 * KC];
   const int d = (D > 0) ? D : d_rt;
   const int tid = threadIdx.x, lane = tid & 63, g = tid >> 6;
   const int64_t i = (int64_t)blockIdx.x * 64 + lane;
-  double xa[D > 0 ? D : XMAXD];
+  double xa[D > 0 ? D : MAX_D];
   for (int c = 0; c < d; ++c) xa[c] = As[i * d + c];  // padded rows are readable
   double acc[KC];
 #pragma unroll
@@ -100,7 +87,7 @@ __global__ __launch_bounds__(256) void kmatvec_kernel(const double* __restrict__
           r2 += e * e;
         }
       }
-      const double kf = kval<KERNEL>(r2, sf2);
+      const double kf = cov::value<KERNEL>(r2, sf2, ExpNonpos{});
 #pragma unroll
       for (int c = 0; c < KC; ++c)
         if (KC <= 2 || c < k) acc[c] += kf * ab[c * 64 + jj];
@@ -330,12 +317,7 @@ void launch_kmatvec_k(const double* As, int64_t m, int64_t mpad, const double* B
 void launch_kmatvec(int kernel, const double* As, int64_t m, int64_t mpad, const double* Bs, int64_t npad, int d,
                     double sf2, double diag, const double* y, const double* alphaT, int64_t lda, int k,
                     double sign, double* outT, int64_t ldo, hipStream_t st) {
-  switch (kernel) {
-    case 0: launch_kmatvec_k<0>(As, m, mpad, Bs, npad, d, sf2, diag, y, alphaT, lda, k, sign, outT, ldo, st); break;
-    case 1: launch_kmatvec_k<1>(As, m, mpad, Bs, npad, d, sf2, diag, y, alphaT, lda, k, sign, outT, ldo, st); break;
-    case 2: launch_kmatvec_k<2>(As, m, mpad, Bs, npad, d, sf2, diag, y, alphaT, lda, k, sign, outT, ldo, st); break;
-    default: launch_kmatvec_k<3>(As, m, mpad, Bs, npad, d, sf2, diag, y, alphaT, lda, k, sign, outT, ldo, st); break;
-  }
+  cov::dispatch(kernel, [&](auto fam) { launch_kmatvec_k<fam>(As, m, mpad, Bs, npad, d, sf2, diag, y, alphaT, lda, k, sign, outT, ldo, st); });
 }
 
 // rows (cols = false): out[c][i] (=|-=) sum_j M[i][j] v[c][j];  columns (cols = true): ... sum_j M[j][i] v[c][j]

@@ -576,7 +576,7 @@ int shard_fit(gpx_handle* h, const void* X, const void* y, int64_t N, int32_t d,
   if ((rc = ensure(h, h->X, (size_t)N * d * sizeof(T)))) return rc;
   if ((rc = ensure(h, h->Y, (size_t)N * k * sizeof(T)))) return rc;
   if ((rc = ensure(h, h->Xs, (size_t)Npad * d * sizeof(T)))) return rc;
-  if ((rc = ensure(h, h->ls, 32 * 8))) return rc;
+  if ((rc = ensure(h, h->ls, MAX_D * 8))) return rc;
   if ((rc = ensure(h, h->K, (size_t)std::max<int64_t>(nloc + Mq, nb) * ld * sizeof(T)))) return rc;
   if (Mq > 0) {
     if ((rc = ensure(h, h->Q, (size_t)Mr * d * sizeof(T)))) return rc;
