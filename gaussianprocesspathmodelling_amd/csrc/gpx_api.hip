@@ -60,9 +60,21 @@ struct Phase {
   double* target;
 };
 
+// One device allocation.  It frees itself: whoever destroys it has selected its device and drained the streams that
+// used it (gpx_destroy, gpx_release_scratch, the unit-test entry points' Scratch).
 struct DevBuf {
   void* p = nullptr;
   size_t cap = 0;
+  DevBuf() = default;
+  DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr, o.cap = 0; }
+  DevBuf& operator=(DevBuf&& o) noexcept {  // the old allocation leaves with `o`
+    std::swap(p, o.p);
+    std::swap(cap, o.cap);
+    return *this;
+  }
+  ~DevBuf() {
+    if (p) (void)hipFree(p);
+  }
 };
 
 struct Comm;   // gpx_shard.inc
@@ -90,8 +102,23 @@ struct gpx_handle {
   double sf2 = 0, sn2 = 0, jitter = 0;
   double logdet = 0;
   DevBuf X, Xs, ls, K, Winv, P, YT, Y, scalars, info;
-  // predict state
-  DevBuf Q, Qs, VT, MT, var, meanout;
+  DevBuf var, meanout;  // predict's results on the device
+  // Scratch: everything gpx_release_scratch frees (`h->scr = {}`) — buffers that any later call allocates again when it
+  // needs them and that no fitted state lives in.  A buffer is scratch by being declared here, and only so.
+  struct ScratchBufs {
+    DevBuf Q, Qs, VT, MT;  // predict: query points (raw, scaled), K* -> V^T of one batch, mean^T
+    DevBuf Tsol;           // predict: compact solved blocks of V^T (2 x batch x (nb + skew))
+    DevBuf MTpart;         // split-K partial tiles of the posterior-mean product
+    DevBuf ZT, gpart;      // gpx_lml_grad: L^-T (Npad x ld) and the per-tile partial sums
+    DevBuf ZTloc, ZTpack;  // sharded gradient: own row blocks of L^-T (stacked), one packed block in flight
+    DevBuf Sv;             // sharded solves: two broadcast buffers of solved blocks
+    DevBuf Q64, Qs64, Q32, M64;             // GPX_MIXED predict
+    DevBuf GatherS, GatherR, outM, outV;    // sharded predict: the all-gather of the ranks' slices
+    // joint posterior (gpx_predict_cov / gpx_sample_posterior): scratch of their own, never the fit's buffers
+    DevBuf JVT, JTsol, JSig, JSigF, JWinv, JP, JWblk, JUblk, JInfo, JZT, JST, JZin, JOut;
+    // posterior gradient (gpx_predict_grad): scratch of its own as well
+    DevBuf GV, GTsol, GMT, GMTpart, GVN, GPart, GOut;
+  } scr;
   // row-block shard (world > 1)
   Comm* comm = nullptr;  // RCCL, in-process or host-callback transport (gpx_shard.inc)
   Group* group = nullptr;    // ndev > 1: this handle only fronts per-device member handles (gpx_group.inc)
@@ -101,25 +128,21 @@ struct gpx_handle {
   void* alphaT = nullptr;  // alpha^T (64 x ld): AT (computed on demand from z^T) or YT (shard)
   bool alpha_ready = false;
   DevBuf AT;
-  DevBuf ZT, gpart;  // gpx_lml_grad: L^-T (Npad x ld) and the per-tile partial sums
   // GPX_MIXED: fp64 side of the mixed-precision mode (the fp32 engine uses the buffers above)
   DevBuf RTloc, P32out;  // GPX_MIXED on a distributed shard: local columns of the refinement's right-hand sides; fp32 predict outputs
-  DevBuf X64, Y64, Xs64, A64, Aprev, R64, X32, Y32, RT32, Q64, Qs64, Q32, M64, rn, Zfew;
+  DevBuf X64, Y64, Xs64, A64, Aprev, R64, X32, Y32, RT32, rn, Zfew;
   int refine = 0;    // GPX_MIXED: 0 = adaptive, > 0 = fixed iteration count
-  DevBuf Tsol;       // predict: compact solved blocks of V^T (2 x batch x (nb + skew))
-  DevBuf MTpart;         // split-K partial tiles of the posterior-mean product
-  DevBuf ZTloc, ZTpack;  // sharded gradient: own row blocks of L^-T (stacked), one packed block in flight
   DevBuf resv_ring;  // device counters of the self-reserving trailing updates ([1024][8] unsigned; GPX_CU_SELF_RESERVE)
   DevBuf Wblk, Ublk; // explicit inverses of the nb x nb diagonal blocks of L ([Npad/nb][nb][nb]) + scratch
   int nbw = 0;       // block width of Wblk (0: not built)
   int nb_shard = 512;  // distribution block = panel width of the sharded factorisation (chosen per fit)
   int nb_shard_env = 0;  // GPX_NB_SHARD override (0: choose from N and the number of ranks)
   int64_t nloc = 0, ldy = 0;
-  DevBuf G, Dbuf, Sbuf, YTloc, Cneg, Sv;
+  DevBuf G, Dbuf, Sbuf, YTloc, Cneg;
   // replicated-factor mode of the shard: every rank keeps the whole L (the panels pass through
   // it anyway), so solves and predictions need no per-panel exchange (gpx_shard.inc)
   bool repl = false;
-  DevBuf Lfull, GatherS, GatherR, outM, outV;
+  DevBuf Lfull;
   const void* Lfac = nullptr;  // the factor the single-GPU solves read: K (unsharded) or Lfull
   // device-flag hand-overs between this handle's streams (diag_enqueue, fused strip): -1 not probed yet, 1 a kernel parked
   // on one stream sees the store of a kernel launched later on another (flag_handover_probe), 0 it does not: hipEvents
@@ -127,14 +150,13 @@ struct gpx_handle {
   int64_t fq_rows = 0;  // gpx_fit_predict on a shard: padded rows of this rank's slice of the query points (bordered rows of its K buffer)
   int flag_ok = -1;
   int flag_retries = 0;  // fits of this handle that were run again with hipEvents after a parked stream timed out
-  // joint posterior (gpx_predict_cov / gpx_sample_posterior): scratch of their own, never the fit's buffers
-  DevBuf JVT, JTsol, JSig, JSigF, JWinv, JP, JWblk, JUblk, JInfo, JZT, JST, JZin, JOut;
-  // posterior gradient (gpx_predict_grad): scratch of its own as well
-  DevBuf GV, GTsol, GMT, GMTpart, GVN, GPart, GOut;
   // event pool
   std::vector<hipEvent_t> ev_pool;
   size_t ev_used = 0;
   std::vector<Phase> phases;
+  // Drains the streams, then destroys the communicator, the events and the streams; the DevBuf members free themselves
+  // after that.  The caller has selected the device (gpx_destroy does).
+  ~gpx_handle();
 };
 
 namespace {
@@ -173,12 +195,6 @@ int ensure(gpx_handle* h, DevBuf& b, size_t bytes) {
   HIPCHK(h, hipMalloc(&b.p, bytes));
   b.cap = bytes;
   return GPX_OK;
-}
-
-void release(DevBuf& b) {
-  if (b.p) (void)hipFree(b.p);
-  b.p = nullptr;
-  b.cap = 0;
 }
 
 hipEvent_t next_event(gpx_handle* h) {
@@ -978,7 +994,7 @@ int64_t pred_batch_rows(gpx_handle* h, int64_t Mpad, size_t row_bytes, bool may_
   if (may_shrink) {
     size_t freeb = 0, totalb = 0;
     if (hipMemGetInfo(&freeb, &totalb) == hipSuccess) {
-      const double avail = 0.8 * ((double)freeb + (double)h->VT.cap);
+      const double avail = 0.8 * ((double)freeb + (double)h->scr.VT.cap);
       const int64_t fit = (int64_t)(avail / (double)row_bytes) / 128 * 128;
       cap = std::max<int64_t>(128, std::min(cap, fit));
     }
@@ -998,6 +1014,115 @@ int auto_panel_width(int64_t Npad) {
     return e ? (int64_t)atoll(e) : (int64_t)40960;
   }();
   return (from > 0 && Npad >= from) ? 2048 : 1024;
+}
+
+// ---- stages every entry point is built from --------------------------------------------------------
+// None of them reads the environment, allocates beyond the ensure() it names or synchronises beyond what it says.
+
+// the start of a call on a single-device handle
+int begin_call(gpx_handle* h) {
+  HIPCHK(h, hipSetDevice(h->cfg.device));
+  h->err.clear();
+  h->phases.clear();  // an earlier call that failed mid-way must not leak its event pairs
+  h->ev_used = 0;
+  return GPX_OK;
+}
+
+int begin_fit(gpx_handle* h) {  // ... of a call that replaces the fit
+  const int rc = begin_call(h);
+  if (rc == GPX_OK) h->fitted = false;
+  return rc;
+}
+
+// the end of a call: the main stream idle, nothing failed on the way, the phase clocks folded into gpx_timings
+int finish_call(gpx_handle* h) {
+  HIPCHK(h, hipStreamSynchronize(h->st));
+  HIPCHK(h, hipGetLastError());
+  LAUNCHCHK(h);
+  collect_phases(h);
+  return GPX_OK;
+}
+
+void reset_predict_clocks(gpx_timings& tm) { tm.kstar = tm.mean = tm.trsm = tm.var = tm.d2h = tm.predict_total = 0; }
+
+// T = float for GPX_F32 handles, double otherwise (GPX_MIXED is dispatched before: its entry points are not templates)
+#define BY_DTYPE(h, fn, ...) ((h)->cfg.dtype == GPX_F32 ? fn<float>(__VA_ARGS__) : fn<double>(__VA_ARGS__))
+
+// room for M query points: Q (M x d, as given) and Qs (padded to whole tiles, scaled by the length scales)
+template <typename T>
+int ensure_queries(gpx_handle* h, int64_t M) {
+  int rc;
+  if ((rc = ensure(h, h->scr.Q, (size_t)M * h->d * sizeof(T)))) return rc;
+  return ensure(h, h->scr.Qs, (size_t)round_up(M, TILE) * h->d * sizeof(T));
+}
+
+// the query points into Q and, scaled, into Qs — inside the caller's phase (predict books it under kstar, a fit that
+// carries query rows under kbuild)
+template <typename T>
+int upload_queries(gpx_handle* h, const void* Xq, int64_t M, int32_t mem_kind) {
+  int rc;
+  if ((rc = copy_in(h, h->scr.Q.p, Xq, (size_t)M * h->d * sizeof(T), mem_kind))) return rc;
+  launch_scale_points<T>((const T*)h->scr.Q.p, M, round_up(M, TILE), h->d, (const double*)h->ls.p, h->n_ls, (T*)h->scr.Qs.p,
+                         h->st);
+  return GPX_OK;
+}
+
+// Dense block solves for solve_fwd_enqueue over `rows` rows: the fit's explicit block inverses and two compact result
+// buffers in `buf`.  *sw stays empty (slab solves) when the solve's block width is not the inverses' or the handle keeps
+// no whole factor.
+template <typename T>
+int dense_solve_work(gpx_handle* h, DevBuf& buf, int64_t rows, SolveWork<T>* sw) {
+  if (h->nbw != h->nb_pred || (h->comm && !h->repl)) return GPX_OK;
+  int rc;
+  sw->ldt = h->nbw + ld_skew<T>();
+  if ((rc = ensure(h, buf, (size_t)2 * rows * sw->ldt * sizeof(T)))) return rc;
+  sw->W = (const T*)h->Wblk.p;
+  sw->nbw = h->nbw;
+  sw->T0 = (T*)buf.p;
+  sw->T1 = sw->T0 + rows * sw->ldt;
+  return GPX_OK;
+}
+
+// mean^T (64 x cols, ldm) = rhs^T (64 x Npad) * V for V^T (cols x Npad), both with the factor's leading dimension: a
+// 64-row product with K = N, so the contraction is split when that fills the chip (part: [splits][64][ldpart])
+template <typename T>
+void mean_product(gpx_handle* h, T* MT, int64_t ldm, const T* rhsT, const T* VT, int64_t cols, T* part, int64_t ldpart) {
+  const int ksplit = splitk_splits(h->Npad);
+  if (ksplit > 1)
+    launch_gemm_nt_splitk<T>(MT, ldm, rhsT, h->ld, VT, h->ld, RHS_ROWS, cols, h->Npad, ksplit, part, ldpart, h->st);
+  else
+    launch_gemm_nt<T>(64, MT, ldm, rhsT, h->ld, VT, h->ld, RHS_ROWS, cols, h->Npad, 0, 1, h->st);
+}
+
+template <typename T>
+int ensure_mean_partials(gpx_handle* h, DevBuf& part, int64_t ldpart) {  // (nothing when mean_product does not split)
+  const int ksplit = splitk_splits(h->Npad);
+  return ksplit > 1 ? ensure(h, part, (size_t)ksplit * RHS_ROWS * ldpart * sizeof(T)) : GPX_OK;
+}
+
+// The predict half of a fit that carried query points as bordered rows: V^T (rows valid of rows_pad, leading dimension
+// h->ld) is in place; what is left is the mean V^T z (h->meanout) and, with want_var, the row norms (h->var).  The caller
+// has ensured MT / MTpart (leading dimension ldm) and the two outputs.
+template <typename T>
+void bordered_mean_var(gpx_handle* h, const T* VT, int64_t rows, int64_t rows_pad, int64_t ldm, bool want_var) {
+  {
+    PhaseScope ps(h, &h->tm.mean);
+    mean_product<T>(h, (T*)h->scr.MT.p, ldm, (const T*)h->zT, VT, rows_pad, (T*)h->scr.MTpart.p, ldm);
+    launch_unpack_rhs<T>((const T*)h->scr.MT.p, ldm, rows, h->k, 1.0, (T*)h->meanout.p, h->st);
+  }
+  if (want_var) {
+    PhaseScope ps(h, &h->tm.var);
+    launch_var_rows<T>(VT, h->ld, rows, h->Npad, h->sf2, (T*)h->var.p, h->st);
+  }
+}
+
+// h->meanout (M x k) and, if asked for, h->var (M) to the caller
+template <typename T>
+int deliver_mean_var(gpx_handle* h, void* mean, void* var, int64_t M, int32_t mem_kind) {
+  PhaseScope ps(h, &h->tm.d2h);
+  int rc;
+  if ((rc = copy_out(h, mean, h->meanout.p, (size_t)M * h->k * sizeof(T), mem_kind))) return rc;
+  return var ? copy_out(h, var, h->var.p, (size_t)M * sizeof(T), mem_kind) : GPX_OK;
 }
 
 template <typename T>
@@ -1046,10 +1171,7 @@ int fit_impl(gpx_handle* h, const void* X, const void* y, int64_t N, int32_t d, 
   if ((rc = ensure(h, h->Xs, (size_t)Npad * d * sizeof(T)))) return rc;
   if ((rc = ensure(h, h->ls, MAX_D * 8))) return rc;
   const int64_t NX = RHS_ROWS + Mpad;  // bordered rows: [K* rows of a fused predict] + the right-hand sides
-  if (Xq) {
-    if ((rc = ensure(h, h->Q, (size_t)M * d * sizeof(T)))) return rc;
-    if ((rc = ensure(h, h->Qs, (size_t)Mpad * d * sizeof(T)))) return rc;
-  }
+  if (Xq && (rc = ensure_queries<T>(h, M))) return rc;
   if ((rc = ensure(h, h->K, (size_t)(Npad + NX) * ld * sizeof(T)))) return rc;
   if ((rc = ensure(h, h->Winv, (size_t)(Npad / KB) * KB * KB * sizeof(T)))) return rc;
   if ((rc = ensure(h, h->P, (size_t)2 * (Npad + NX) * ldp * sizeof(T)))) return rc;
@@ -1092,9 +1214,8 @@ int fit_impl(gpx_handle* h, const void* X, const void* y, int64_t N, int32_t d, 
       launch_kbuild_sym<T>(h->cfg.kernel, (const T*)h->Xs.p, N, Npad, d, sf2, sn2 + jitter, dK, ld,
                         h->st);
       if (Xq) {  // rows [Npad + RHS_ROWS, ... + Mpad): K(Xq, X)
-        if ((rc = copy_in(h, h->Q.p, Xq, (size_t)M * d * sizeof(T), mem_kind))) return rc;
-        launch_scale_points<T>((const T*)h->Q.p, M, Mpad, d, (const double*)h->ls.p, n_ls, (T*)h->Qs.p, h->st);
-        launch_kbuild_cross<T>(h->cfg.kernel, (const T*)h->Qs.p, M, Mpad, (const T*)h->Xs.p, N, Npad, d, sf2,
+        if ((rc = upload_queries<T>(h, Xq, M, mem_kind))) return rc;
+        launch_kbuild_cross<T>(h->cfg.kernel, (const T*)h->scr.Qs.p, M, Mpad, (const T*)h->Xs.p, N, Npad, d, sf2,
                             dK + (Npad + RHS_ROWS) * ld, ld, h->st);
       }
     }
@@ -1117,10 +1238,7 @@ int fit_impl(gpx_handle* h, const void* X, const void* y, int64_t N, int32_t d, 
   int hinfo = 0;
   HIPCHK(h, hipMemcpyAsync(&hinfo, dInfo, sizeof(int), hipMemcpyDeviceToHost, h->st));
   HIPCHK(h, hipMemcpyAsync(&h->logdet, h->scalars.p, sizeof(double), hipMemcpyDeviceToHost, h->st));
-  HIPCHK(h, hipStreamSynchronize(h->st));
-  HIPCHK(h, hipGetLastError());
-  LAUNCHCHK(h);
-  collect_phases(h);
+  if ((rc = finish_call(h))) return rc;
   if (hinfo < 0) {
     // wait_counter_kernel gave up although the self-test passed (a tool attached later, or one that reorders rather than
     // serialises): this handle hands over by hipEvents from now on and the fit runs once more — same kernels, same bits.
@@ -1128,8 +1246,6 @@ int fit_impl(gpx_handle* h, const void* X, const void* y, int64_t N, int32_t d, 
     if (!retried && !getenv("GPX_CHAIN_FLAG") && h->flag_ok != 0) {
       h->flag_ok = 0;
       h->flag_retries += 1;
-      h->phases.clear();
-      h->ev_used = 0;
       return fit_impl<T>(h, X, y, N, d, k, lengthscale, n_ls, sf2, sn2, jitter, mem_kind, info, Xq, M, true);
     }
     return fail(h, GPX_E_HIP,
@@ -1218,56 +1334,40 @@ int predict_core(gpx_handle* h, const void* Xq, int64_t M, bool want_var, int32_
   const int64_t MB = pred_batch_rows(h, Mpad, (size_t)ld * sizeof(T), true);
   gpx_timings& tm = h->tm;
   int rc;
-  if ((rc = ensure(h, h->Q, (size_t)M * d * sizeof(T)))) return rc;
-  if ((rc = ensure(h, h->Qs, (size_t)Mpad * d * sizeof(T)))) return rc;
-  if ((rc = ensure(h, h->VT, (size_t)MB * ld * sizeof(T)))) return rc;
-  if ((rc = ensure(h, h->MT, (size_t)RHS_ROWS * ldm * sizeof(T)))) return rc;
-  // the mean is a 64-row product with K = N: split the contraction so that it fills the chip
-  const int ksplit = splitk_splits(Npad);
-  const int64_t ldpm = std::min(MB, Mpad) + ld_skew<T>();  // partial tiles of ONE batch
-  if (ksplit > 1 && (rc = ensure(h, h->MTpart, (size_t)ksplit * RHS_ROWS * ldpm * sizeof(T)))) return rc;
+  if ((rc = ensure_queries<T>(h, M))) return rc;
+  if ((rc = ensure(h, h->scr.VT, (size_t)MB * ld * sizeof(T)))) return rc;
+  if ((rc = ensure(h, h->scr.MT, (size_t)RHS_ROWS * ldm * sizeof(T)))) return rc;
+  const int64_t ldpm = std::min(MB, Mpad) + ld_skew<T>();  // split-K partial tiles of ONE batch
+  if ((rc = ensure_mean_partials<T>(h, h->scr.MTpart, ldpm))) return rc;
   if ((rc = ensure(h, h->meanout, (size_t)M * k * sizeof(T)))) return rc;
   if ((rc = ensure(h, h->var, (size_t)Mpad * sizeof(T)))) return rc;
-  SolveWork<T> sw;
-  if (want_var && h->nbw == h->nb_pred && (!h->comm || h->repl)) {  // block inverses of this fit (a shard: of the factor it keeps whole), same block width
-    sw.ldt = h->nbw + ld_skew<T>();
-    if ((rc = ensure(h, h->Tsol, (size_t)2 * MB * sw.ldt * sizeof(T)))) return rc;
-    sw.W = (const T*)h->Wblk.p;
-    sw.nbw = h->nbw;
-    sw.T0 = (T*)h->Tsol.p;
-    sw.T1 = sw.T0 + MB * sw.ldt;
-  }
-  T* dVT = (T*)h->VT.p;
+  SolveWork<T> sw;  // block inverses of this fit (a shard: of the factor it keeps whole)
+  if (want_var && (rc = dense_solve_work<T>(h, h->scr.Tsol, MB, &sw))) return rc;
+  T* dVT = (T*)h->scr.VT.p;
   const T* dK = (const T*)h->Lfac;
   const T* dWinv = (const T*)h->Winv.p;
   if (!want_var && (rc = ensure_alpha<T>(h))) return rc;  // mean only: K* alpha with the cached alpha
   const T* rhsT = (const T*)(want_var ? h->zT : h->alphaT);
   {
     PhaseScope ps(h, &tm.kstar);
-    if ((rc = copy_in(h, h->Q.p, Xq, (size_t)M * d * sizeof(T), mem_kind))) return rc;
-    launch_scale_points<T>((const T*)h->Q.p, M, Mpad, d, (const double*)h->ls.p, h->n_ls,
-                        (T*)h->Qs.p, h->st);
+    if ((rc = upload_queries<T>(h, Xq, M, mem_kind))) return rc;
   }
   for (int64_t m0 = 0; m0 < Mpad; m0 += MB) {  // batches of query points through one V^T buffer
     const int64_t mp = std::min(MB, Mpad - m0);       // padded rows of this batch
     const int64_t mv = std::min<int64_t>(mp, M - m0);  // valid rows
     {
       PhaseScope ps(h, &tm.kstar);
-      launch_kbuild_cross<T>(h->cfg.kernel, (const T*)h->Qs.p + m0 * d, mv, mp, (const T*)h->Xs.p, N,
+      launch_kbuild_cross<T>(h->cfg.kernel, (const T*)h->scr.Qs.p + m0 * d, mv, mp, (const T*)h->Xs.p, N,
                           Npad, d, h->sf2, dVT, ld, h->st);
     }
     if (want_var) {
       PhaseScope ps(h, &tm.trsm);
-      if ((rc = solve_fwd_enqueue<T>(h, dVT, mp, dK, ld, Npad, h->nb_pred, dWinv, sw.W ? &sw : nullptr))) return rc;
+      if ((rc = solve_fwd_enqueue<T>(h, dVT, mp, dK, ld, Npad, h->nb_pred, dWinv, &sw))) return rc;
     }
     {  // with the variance: mean^T (64 x mp) = z^T (64 x Npad) * V   (mu = K* K^-1 y = V^T z);
        // mean only: alpha^T * K*^T
       PhaseScope ps(h, &tm.mean);
-      if (ksplit > 1)
-        launch_gemm_nt_splitk<T>((T*)h->MT.p + m0, ldm, rhsT, ld, dVT, ld, RHS_ROWS, mp, Npad, ksplit,
-                                 (T*)h->MTpart.p, ldpm, h->st);
-      else
-        launch_gemm_nt<T>(64, (T*)h->MT.p + m0, ldm, rhsT, ld, dVT, ld, RHS_ROWS, mp, Npad, 0, 1, h->st);
+      mean_product<T>(h, (T*)h->scr.MT.p + m0, ldm, rhsT, dVT, mp, (T*)h->scr.MTpart.p, ldpm);
     }
     if (want_var) {
       PhaseScope ps(h, &tm.var);
@@ -1276,70 +1376,40 @@ int predict_core(gpx_handle* h, const void* Xq, int64_t M, bool want_var, int32_
   }
   {
     PhaseScope ps(h, &tm.mean);
-    launch_unpack_rhs<T>((const T*)h->MT.p, ldm, M, k, 1.0, (T*)h->meanout.p, h->st);
+    launch_unpack_rhs<T>((const T*)h->scr.MT.p, ldm, M, k, 1.0, (T*)h->meanout.p, h->st);
   }
   return GPX_OK;
 }
 
 template <typename T>
 int predict_impl(gpx_handle* h, const void* Xq, int64_t M, void* mean, void* var, int32_t mem_kind) {
-  gpx_timings& tm = h->tm;
-  tm.kstar = tm.mean = tm.trsm = tm.var = tm.d2h = tm.predict_total = 0;
+  reset_predict_clocks(h->tm);
   int rc;
   {
-    PhaseScope total(h, &tm.predict_total);
+    PhaseScope total(h, &h->tm.predict_total);
     if ((rc = predict_core<T>(h, Xq, M, var != nullptr, mem_kind))) return rc;
-    PhaseScope ps(h, &tm.d2h);
-    if ((rc = copy_out(h, mean, h->meanout.p, (size_t)M * h->k * sizeof(T), mem_kind))) return rc;
-    if (var && (rc = copy_out(h, var, h->var.p, (size_t)M * sizeof(T), mem_kind))) return rc;
+    if ((rc = deliver_mean_var<T>(h, mean, var, M, mem_kind))) return rc;
   }
-  HIPCHK(h, hipStreamSynchronize(h->st));
-  HIPCHK(h, hipGetLastError());
-  LAUNCHCHK(h);
-  collect_phases(h);
-  return GPX_OK;
+  return finish_call(h);
 }
 
 // The predict half of gpx_fit_predict: V^T already sits in the Mpad rows below the right-hand sides in the factor's buffer
 // (fit_impl with query points); what is left is the mean V^T z and the row norms.
 template <typename T>
 int fused_predict_tail(gpx_handle* h, int64_t M, void* mean, void* var, int32_t mem_kind) {
-  const int64_t Npad = h->Npad, ld = h->ld;
   const int64_t Mpad = round_up(M, TILE), ldm = Mpad + ld_skew<T>();
-  gpx_timings& tm = h->tm;
-  tm.kstar = tm.mean = tm.trsm = tm.var = tm.d2h = tm.predict_total = 0;
+  reset_predict_clocks(h->tm);
   int rc;
-  if ((rc = ensure(h, h->MT, (size_t)RHS_ROWS * ldm * sizeof(T)))) return rc;
-  const int ksplit = splitk_splits(Npad);
-  const int64_t ldpm = Mpad + ld_skew<T>();
-  if (ksplit > 1 && (rc = ensure(h, h->MTpart, (size_t)ksplit * RHS_ROWS * ldpm * sizeof(T)))) return rc;
+  if ((rc = ensure(h, h->scr.MT, (size_t)RHS_ROWS * ldm * sizeof(T)))) return rc;
+  if ((rc = ensure_mean_partials<T>(h, h->scr.MTpart, ldm))) return rc;
   if ((rc = ensure(h, h->meanout, (size_t)M * h->k * sizeof(T)))) return rc;
   if ((rc = ensure(h, h->var, (size_t)Mpad * sizeof(T)))) return rc;
-  const T* dVT = (const T*)h->Lfac + (Npad + RHS_ROWS) * ld;
   {
-    PhaseScope total(h, &tm.predict_total);
-    {
-      PhaseScope ps(h, &tm.mean);
-      if (ksplit > 1)
-        launch_gemm_nt_splitk<T>((T*)h->MT.p, ldm, (const T*)h->zT, ld, dVT, ld, RHS_ROWS, Mpad, Npad, ksplit,
-                                 (T*)h->MTpart.p, ldpm, h->st);
-      else
-        launch_gemm_nt<T>(64, (T*)h->MT.p, ldm, (const T*)h->zT, ld, dVT, ld, RHS_ROWS, Mpad, Npad, 0, 1, h->st);
-      launch_unpack_rhs<T>((const T*)h->MT.p, ldm, M, h->k, 1.0, (T*)h->meanout.p, h->st);
-    }
-    if (var) {
-      PhaseScope ps(h, &tm.var);
-      launch_var_rows<T>(dVT, ld, M, Npad, h->sf2, (T*)h->var.p, h->st);
-    }
-    PhaseScope ps(h, &tm.d2h);
-    if ((rc = copy_out(h, mean, h->meanout.p, (size_t)M * h->k * sizeof(T), mem_kind))) return rc;
-    if (var && (rc = copy_out(h, var, h->var.p, (size_t)M * sizeof(T), mem_kind))) return rc;
+    PhaseScope total(h, &h->tm.predict_total);
+    bordered_mean_var<T>(h, (const T*)h->Lfac + (h->Npad + RHS_ROWS) * h->ld, M, Mpad, ldm, var != nullptr);
+    if ((rc = deliver_mean_var<T>(h, mean, var, M, mem_kind))) return rc;
   }
-  HIPCHK(h, hipStreamSynchronize(h->st));
-  HIPCHK(h, hipGetLastError());
-  LAUNCHCHK(h);
-  collect_phases(h);
-  return GPX_OK;
+  return finish_call(h);
 }
 
 // ---- joint posterior (ABI v6: gpx_predict_cov, gpx_sample_posterior) ----------------------------------------------------
@@ -1358,7 +1428,7 @@ size_t posterior_need(const gpx_handle* h, int64_t M, int64_t S, bool sample, bo
   double b = (double)Mpad * h->ld + (double)Mpad * lds;                                          // V^T, Sigma
   if (h->nbw == h->nb_pred) b += 2.0 * Mpad * (h->nbw + ld_skew<T>());                            // block-solve buffers
   b += (double)RHS_ROWS * (Mpad + ld_skew<T>()) * (1 + splitk_splits(h->Npad)) + (double)M * k;   // mean
-  *have = h->JVT.cap + h->JTsol.cap + h->JSig.cap;
+  *have = h->scr.JVT.cap + h->scr.JTsol.cap + h->scr.JSig.cap;
   if (sample) {
     const int64_t ldp = POST_NB + ld_skew<T>(), nblk = (Mpad + POST_NB - 1) / POST_NB;
     const int64_t R = std::min<int64_t>(round_up(std::max<int64_t>(POST_ROWS / k, 1) * k, TILE), round_up(S * k, TILE));
@@ -1366,8 +1436,8 @@ size_t posterior_need(const gpx_handle* h, int64_t M, int64_t S, bool sample, bo
          (double)POST_NB * ldp + 2.0 * R * lds;
     if (z_host) b += (double)S * M * k;
     if (out_host) b += (double)S * M * k;
-    *have += h->JSigF.cap + h->JWinv.cap + h->JP.cap + h->JWblk.cap + h->JUblk.cap + h->JZT.cap + h->JST.cap + h->JZin.cap +
-             h->JOut.cap;
+    *have += h->scr.JSigF.cap + h->scr.JWinv.cap + h->scr.JP.cap + h->scr.JWblk.cap + h->scr.JUblk.cap + h->scr.JZT.cap + h->scr.JST.cap + h->scr.JZin.cap +
+             h->scr.JOut.cap;
   }
   return (size_t)(b * E) + 4096;
 }
@@ -1388,7 +1458,7 @@ int posterior_check(gpx_handle* h, const char* fn, int64_t M, int64_t S, bool sa
   return GPX_OK;
 }
 
-// mean (h->meanout, M x k) and the LOWER triangle of Sigma (h->JSig, Mpad x lds; padded rows identity)
+// mean (h->meanout, M x k) and the LOWER triangle of Sigma (h->scr.JSig, Mpad x lds; padded rows identity)
 template <typename T>
 int posterior_cov_core(gpx_handle* h, const void* Xq, int64_t M, int32_t mem_kind) {
   const int64_t N = h->N, Npad = h->Npad, ld = h->ld;
@@ -1396,51 +1466,36 @@ int posterior_cov_core(gpx_handle* h, const void* Xq, int64_t M, int32_t mem_kin
   const int64_t Mpad = round_up(M, TILE), lds = Mpad + ld_skew<T>(), ldm = Mpad + ld_skew<T>();
   gpx_timings& tm = h->tm;
   int rc;
-  if ((rc = ensure(h, h->Q, (size_t)M * d * sizeof(T)))) return rc;
-  if ((rc = ensure(h, h->Qs, (size_t)Mpad * d * sizeof(T)))) return rc;
-  if ((rc = ensure(h, h->JVT, (size_t)Mpad * ld * sizeof(T)))) return rc;
-  if ((rc = ensure(h, h->JSig, (size_t)Mpad * lds * sizeof(T)))) return rc;
-  if ((rc = ensure(h, h->MT, (size_t)RHS_ROWS * ldm * sizeof(T)))) return rc;
-  const int ksplit = splitk_splits(Npad);
-  if (ksplit > 1 && (rc = ensure(h, h->MTpart, (size_t)ksplit * RHS_ROWS * ldm * sizeof(T)))) return rc;
+  if ((rc = ensure_queries<T>(h, M))) return rc;
+  if ((rc = ensure(h, h->scr.JVT, (size_t)Mpad * ld * sizeof(T)))) return rc;
+  if ((rc = ensure(h, h->scr.JSig, (size_t)Mpad * lds * sizeof(T)))) return rc;
+  if ((rc = ensure(h, h->scr.MT, (size_t)RHS_ROWS * ldm * sizeof(T)))) return rc;
+  if ((rc = ensure_mean_partials<T>(h, h->scr.MTpart, ldm))) return rc;
   if ((rc = ensure(h, h->meanout, (size_t)M * k * sizeof(T)))) return rc;
-  SolveWork<T> sw;
-  if (h->nbw == h->nb_pred) {  // the fit's block inverses, same block width: dense block solves (as predict)
-    sw.ldt = h->nbw + ld_skew<T>();
-    if ((rc = ensure(h, h->JTsol, (size_t)2 * Mpad * sw.ldt * sizeof(T)))) return rc;
-    sw.W = (const T*)h->Wblk.p;
-    sw.nbw = h->nbw;
-    sw.T0 = (T*)h->JTsol.p;
-    sw.T1 = sw.T0 + Mpad * sw.ldt;
-  }
-  T* dVT = (T*)h->JVT.p;
-  T* dSig = (T*)h->JSig.p;
+  SolveWork<T> sw;  // dense block solves, as predict
+  if ((rc = dense_solve_work<T>(h, h->scr.JTsol, Mpad, &sw))) return rc;
+  T* dVT = (T*)h->scr.JVT.p;
+  T* dSig = (T*)h->scr.JSig.p;
   {
     PhaseScope ps(h, &tm.kstar);
-    if ((rc = copy_in(h, h->Q.p, Xq, (size_t)M * d * sizeof(T), mem_kind))) return rc;
-    launch_scale_points<T>((const T*)h->Q.p, M, Mpad, d, (const double*)h->ls.p, h->n_ls, (T*)h->Qs.p, h->st);
-    launch_kbuild_cross<T>(h->cfg.kernel, (const T*)h->Qs.p, M, Mpad, (const T*)h->Xs.p, N, Npad, d, h->sf2, dVT, ld, h->st);
+    if ((rc = upload_queries<T>(h, Xq, M, mem_kind))) return rc;
+    launch_kbuild_cross<T>(h->cfg.kernel, (const T*)h->scr.Qs.p, M, Mpad, (const T*)h->Xs.p, N, Npad, d, h->sf2, dVT, ld, h->st);
   }
   {
     PhaseScope ps(h, &tm.trsm);
-    if ((rc = solve_fwd_enqueue<T>(h, dVT, Mpad, (const T*)h->Lfac, ld, Npad, h->nb_pred, (const T*)h->Winv.p,
-                                   sw.W ? &sw : nullptr)))
+    if ((rc = solve_fwd_enqueue<T>(h, dVT, Mpad, (const T*)h->Lfac, ld, Npad, h->nb_pred, (const T*)h->Winv.p, &sw)))
       return rc;
   }
   {  // mean^T (64 x Mpad) = z^T V
     PhaseScope ps(h, &tm.mean);
-    if (ksplit > 1)
-      launch_gemm_nt_splitk<T>((T*)h->MT.p, ldm, (const T*)h->zT, ld, dVT, ld, RHS_ROWS, Mpad, Npad, ksplit,
-                               (T*)h->MTpart.p, ldm, h->st);
-    else
-      launch_gemm_nt<T>(64, (T*)h->MT.p, ldm, (const T*)h->zT, ld, dVT, ld, RHS_ROWS, Mpad, Npad, 0, 1, h->st);
-    launch_unpack_rhs<T>((const T*)h->MT.p, ldm, M, k, 1.0, (T*)h->meanout.p, h->st);
+    mean_product<T>(h, (T*)h->scr.MT.p, ldm, (const T*)h->zT, dVT, Mpad, (T*)h->scr.MTpart.p, ldm);
+    launch_unpack_rhs<T>((const T*)h->scr.MT.p, ldm, M, k, 1.0, (T*)h->meanout.p, h->st);
   }
   {  // Sigma = K(Xs, Xs) - (V^T)(V^T)^T: lower 64-tiles of the kernel (the block above the diagonal inside a 128-tile is
      // not built: zero it first), then one SYRK over the lower triangle
     PhaseScope ps(h, &tm.var);
     HIPCHK(h, hipMemsetAsync(dSig, 0, (size_t)Mpad * lds * sizeof(T), h->st));
-    launch_kbuild_sym<T>(h->cfg.kernel, (const T*)h->Qs.p, M, Mpad, d, h->sf2, 0.0, dSig, lds, h->st);
+    launch_kbuild_sym<T>(h->cfg.kernel, (const T*)h->scr.Qs.p, M, Mpad, d, h->sf2, 0.0, dSig, lds, h->st);
     launch_gemm_nt<T>(128, dSig, lds, dVT, ld, dVT, ld, Mpad, Mpad, Npad, 1, 0, h->st);
   }
   return GPX_OK;
@@ -1449,7 +1504,7 @@ int posterior_cov_core(gpx_handle* h, const void* Xq, int64_t M, int32_t mem_kin
 template <typename T>
 int predict_cov_impl(gpx_handle* h, const void* Xq, int64_t M, void* mean, void* cov, int32_t mem_kind) {
   gpx_timings& tm = h->tm;
-  tm.kstar = tm.mean = tm.trsm = tm.var = tm.d2h = tm.predict_total = 0;
+  reset_predict_clocks(tm);
   int rc;
   if ((rc = posterior_check<T>(h, "gpx_predict_cov", M, 0, false, false, false))) return rc;
   const int64_t Mpad = round_up(M, TILE), lds = Mpad + ld_skew<T>();
@@ -1458,19 +1513,15 @@ int predict_cov_impl(gpx_handle* h, const void* Xq, int64_t M, void* mean, void*
     if ((rc = posterior_cov_core<T>(h, Xq, M, mem_kind))) return rc;
     {
       PhaseScope ps(h, &tm.var);
-      launch_mirror_lower<T>((T*)h->JSig.p, lds, Mpad, 0, h->st);  // bit-symmetric copy-out
+      launch_mirror_lower<T>((T*)h->scr.JSig.p, lds, Mpad, 0, h->st);  // bit-symmetric copy-out
     }
     PhaseScope ps(h, &tm.d2h);
     if (mean && (rc = copy_out(h, mean, h->meanout.p, (size_t)M * h->k * sizeof(T), mem_kind))) return rc;
-    HIPCHK(h, hipMemcpy2DAsync(cov, (size_t)M * sizeof(T), h->JSig.p, (size_t)lds * sizeof(T), (size_t)M * sizeof(T),
+    HIPCHK(h, hipMemcpy2DAsync(cov, (size_t)M * sizeof(T), h->scr.JSig.p, (size_t)lds * sizeof(T), (size_t)M * sizeof(T),
                                (size_t)M, mem_kind == GPX_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice,
                                h->st));
   }
-  HIPCHK(h, hipStreamSynchronize(h->st));
-  HIPCHK(h, hipGetLastError());
-  LAUNCHCHK(h);
-  collect_phases(h);
-  return GPX_OK;
+  return finish_call(h);
 }
 
 template <typename T>
@@ -1478,7 +1529,7 @@ int sample_posterior_impl(gpx_handle* h, const void* Xq, int64_t M, int64_t S, u
                           double diag_add, double jitter, int32_t max_tries, void* out, double* jitter_used, int64_t* info,
                           int32_t mem_kind) {
   gpx_timings& tm = h->tm;
-  tm.kstar = tm.mean = tm.trsm = tm.var = tm.d2h = tm.predict_total = 0;
+  reset_predict_clocks(tm);
   const bool host = mem_kind == GPX_MEM_HOST;
   int rc;
   if ((rc = posterior_check<T>(h, "gpx_sample_posterior", M, S, true, z && host, host))) return rc;
@@ -1489,20 +1540,20 @@ int sample_posterior_impl(gpx_handle* h, const void* Xq, int64_t M, int64_t S, u
   const int64_t Rpad = std::min(round_up(Rb, TILE), round_up(total, TILE));      // buffer rows
   const size_t outn = (size_t)S * M * k;
   const int64_t nblk = (Mpad + POST_NB - 1) / POST_NB;
-  if ((rc = ensure(h, h->JSigF, (size_t)Mpad * lds * sizeof(T)))) return rc;
-  if ((rc = ensure(h, h->JWinv, (size_t)(Mpad / KB) * KB * KB * sizeof(T)))) return rc;
-  if ((rc = ensure(h, h->JP, (size_t)2 * Mpad * ldp * sizeof(T)))) return rc;
-  if ((rc = ensure(h, h->JWblk, (size_t)nblk * POST_NB * POST_NB * sizeof(T)))) return rc;
-  if ((rc = ensure(h, h->JUblk, (size_t)POST_NB * ldp * sizeof(T)))) return rc;
-  if ((rc = ensure(h, h->JInfo, 64))) return rc;
-  if ((rc = ensure(h, h->JZT, (size_t)Rpad * lds * sizeof(T)))) return rc;
-  if ((rc = ensure(h, h->JST, (size_t)Rpad * lds * sizeof(T)))) return rc;
-  if (z && host && (rc = ensure(h, h->JZin, outn * sizeof(T)))) return rc;
-  if (host && (rc = ensure(h, h->JOut, outn * sizeof(T)))) return rc;
-  T* dF = (T*)h->JSigF.p;
-  int* dInfo = (int*)h->JInfo.p;
+  if ((rc = ensure(h, h->scr.JSigF, (size_t)Mpad * lds * sizeof(T)))) return rc;
+  if ((rc = ensure(h, h->scr.JWinv, (size_t)(Mpad / KB) * KB * KB * sizeof(T)))) return rc;
+  if ((rc = ensure(h, h->scr.JP, (size_t)2 * Mpad * ldp * sizeof(T)))) return rc;
+  if ((rc = ensure(h, h->scr.JWblk, (size_t)nblk * POST_NB * POST_NB * sizeof(T)))) return rc;
+  if ((rc = ensure(h, h->scr.JUblk, (size_t)POST_NB * ldp * sizeof(T)))) return rc;
+  if ((rc = ensure(h, h->scr.JInfo, 64))) return rc;
+  if ((rc = ensure(h, h->scr.JZT, (size_t)Rpad * lds * sizeof(T)))) return rc;
+  if ((rc = ensure(h, h->scr.JST, (size_t)Rpad * lds * sizeof(T)))) return rc;
+  if (z && host && (rc = ensure(h, h->scr.JZin, outn * sizeof(T)))) return rc;
+  if (host && (rc = ensure(h, h->scr.JOut, outn * sizeof(T)))) return rc;
+  T* dF = (T*)h->scr.JSigF.p;
+  int* dInfo = (int*)h->scr.JInfo.p;
   const T* dz = (const T*)z;
-  T* dout = host ? (T*)h->JOut.p : (T*)out;
+  T* dout = host ? (T*)h->scr.JOut.p : (T*)out;
   // the factorisation books its trailing updates into the fit's counters: they stay the fit's, on every way out
   struct KeepFitClocks {
     gpx_timings& tm;
@@ -1518,11 +1569,11 @@ int sample_posterior_impl(gpx_handle* h, const void* Xq, int64_t M, int64_t S, u
   {
     PhaseScope total_ps(h, &tm.predict_total);
     if ((rc = posterior_cov_core<T>(h, Xq, M, mem_kind))) return rc;
-    const T* dSig = (const T*)h->JSig.p;  // (allocated by the core)
+    const T* dSig = (const T*)h->scr.JSig.p;  // (allocated by the core)
     if (z && host) {
       PhaseScope ps(h, &tm.kstar);
-      if ((rc = copy_in(h, h->JZin.p, z, outn * sizeof(T), GPX_MEM_HOST))) return rc;
-      dz = (const T*)h->JZin.p;
+      if ((rc = copy_in(h, h->scr.JZin.p, z, outn * sizeof(T), GPX_MEM_HOST))) return rc;
+      dz = (const T*)h->scr.JZin.p;
     }
     {  // factorisation (jitter escalation) and transform
       PhaseScope ps(h, &tm.var);
@@ -1532,12 +1583,12 @@ int sample_posterior_impl(gpx_handle* h, const void* Xq, int64_t M, int64_t S, u
         launch_fix_diag<T>(dF, lds, (int)Mpad, (int)M, diag_add + j, h->st);
         HIPCHK(h, hipMemsetD32Async((hipDeviceptr_t)dInfo, INT_MAX, 1, h->st));
         InvWork<T> iw;
-        iw.W = (T*)h->JWblk.p;
-        iw.U = (T*)h->JUblk.p;
+        iw.W = (T*)h->scr.JWblk.p;
+        iw.U = (T*)h->scr.JUblk.p;
         iw.ldu = ldp;
         iw.nbw = POST_NB;
         iw.aux = h->st3;
-        if ((rc = chol_enqueue<T>(h, dF, lds, Mpad, POST_NB, (T*)h->JWinv.p, (T*)h->JP.p, (T*)h->JP.p + Mpad * ldp, ldp,
+        if ((rc = chol_enqueue<T>(h, dF, lds, Mpad, POST_NB, (T*)h->scr.JWinv.p, (T*)h->scr.JP.p, (T*)h->scr.JP.p + Mpad * ldp, ldp,
                                   dInfo, 0, false, 0, &iw)))
           return rc;
         HIPCHK(h, hipMemcpyAsync(&hinfo, dInfo, sizeof(int), hipMemcpyDeviceToHost, h->st));
@@ -1553,9 +1604,9 @@ int sample_posterior_impl(gpx_handle* h, const void* Xq, int64_t M, int64_t S, u
         launch_mirror_lower<T>(dF, lds, Mpad, 1, h->st);  // the product reads B's diagonal tiles whole: zero above L_S
         for (int64_t r0 = 0; r0 < total; r0 += Rb) {
           const int64_t rows = std::min(Rb, total - r0), rpad = round_up(rows, TILE);
-          launch_normals<T>((T*)h->JZT.p, lds, r0, rpad, total, M, Mpad, k, seed, dz, h->st);
-          launch_gemm_nt<T>(128, (T*)h->JST.p, lds, (const T*)h->JZT.p, lds, dF, lds, rpad, Mpad, Mpad, 4, 1, h->st);
-          launch_sample_epilogue<T>((const T*)h->JST.p, lds, r0, rows, (const T*)h->meanout.p, M, k, dout, h->st);
+          launch_normals<T>((T*)h->scr.JZT.p, lds, r0, rpad, total, M, Mpad, k, seed, dz, h->st);
+          launch_gemm_nt<T>(128, (T*)h->scr.JST.p, lds, (const T*)h->scr.JZT.p, lds, dF, lds, rpad, Mpad, Mpad, 4, 1, h->st);
+          launch_sample_epilogue<T>((const T*)h->scr.JST.p, lds, r0, rows, (const T*)h->meanout.p, M, k, dout, h->st);
         }
       }
     }
@@ -1566,11 +1617,7 @@ int sample_posterior_impl(gpx_handle* h, const void* Xq, int64_t M, int64_t S, u
   }
   *jitter_used = j;
   *info = hinfo == INT_MAX ? 0 : (int64_t)hinfo;
-  HIPCHK(h, hipStreamSynchronize(h->st));
-  HIPCHK(h, hipGetLastError());
-  LAUNCHCHK(h);
-  collect_phases(h);
-  return GPX_OK;
+  return finish_call(h);
 }
 
 // ---- posterior gradient (gpx_predict_grad) -------------------------------------------------------------------------
@@ -1599,7 +1646,6 @@ int grad_priors(gpx_handle* h, bool with_value, double* prior) {
 template <typename T>
 int predict_grad_mean_only(gpx_handle* h, const void* Xq, int64_t M, void* mean, void* dmean, int32_t mem_kind) {
   const int d = h->d, k = h->k;
-  const int64_t Mpad = round_up(M, TILE);
   gpx_timings& tm = h->tm;
   int rc;
   int KC = 1, S = 1;
@@ -1609,23 +1655,21 @@ int predict_grad_mean_only(gpx_handle* h, const void* Xq, int64_t M, void* mean,
     if ((rc = predict_core<T>(h, Xq, M, false, mem_kind))) return rc;  // gpx_predict's mean; leaves Qs scaled
   } else {
     if ((rc = ensure_alpha<T>(h))) return rc;
-    if ((rc = ensure(h, h->Q, (size_t)M * d * sizeof(T)))) return rc;
-    if ((rc = ensure(h, h->Qs, (size_t)Mpad * d * sizeof(T)))) return rc;
+    if ((rc = ensure_queries<T>(h, M))) return rc;
     PhaseScope ps(h, &tm.kstar);
-    if ((rc = copy_in(h, h->Q.p, Xq, (size_t)M * d * sizeof(T), mem_kind))) return rc;
-    launch_scale_points<T>((const T*)h->Q.p, M, Mpad, d, (const double*)h->ls.p, h->n_ls, (T*)h->Qs.p, h->st);
+    if ((rc = upload_queries<T>(h, Xq, M, mem_kind))) return rc;
   }
-  if ((rc = ensure(h, h->GPart, (size_t)S * k * d * round_up(M, 64) * sizeof(T)))) return rc;
-  if ((rc = ensure(h, h->GOut, (size_t)M * d * k * sizeof(T)))) return rc;
+  if ((rc = ensure(h, h->scr.GPart, (size_t)S * k * d * round_up(M, 64) * sizeof(T)))) return rc;
+  if ((rc = ensure(h, h->scr.GOut, (size_t)M * d * k * sizeof(T)))) return rc;
   {
     PhaseScope ps(h, &tm.mean);
-    launch_kgrad_matvec<T>(h->cfg.kernel, (const T*)h->Qs.p, M, (const T*)h->Xs.p, h->Npad, d, h->sf2,
-                           (const T*)h->alphaT, h->ld, k, (const double*)h->ls.p, h->n_ls, (T*)h->GPart.p,
-                           (T*)h->GOut.p, h->st);
+    launch_kgrad_matvec<T>(h->cfg.kernel, (const T*)h->scr.Qs.p, M, (const T*)h->Xs.p, h->Npad, d, h->sf2,
+                           (const T*)h->alphaT, h->ld, k, (const double*)h->ls.p, h->n_ls, (T*)h->scr.GPart.p,
+                           (T*)h->scr.GOut.p, h->st);
   }
   PhaseScope ps(h, &tm.d2h);
   if (mean && (rc = copy_out(h, mean, h->meanout.p, (size_t)M * k * sizeof(T), mem_kind))) return rc;
-  return copy_out(h, dmean, h->GOut.p, (size_t)M * d * k * sizeof(T), mem_kind);
+  return copy_out(h, dmean, h->scr.GOut.p, (size_t)M * d * k * sizeof(T), mem_kind);
 }
 
 template <typename T>
@@ -1645,7 +1689,7 @@ int predict_grad_var(gpx_handle* h, const void* Xq, int64_t M, void* mean, void*
   const double per_pt = (double)E * nblk * ((double)ld + (dense ? 2.0 * ldt : 0.0) + RHS_ROWS * (1.0 + ksplit) + 1.0);
   const double fixed = (double)E * ((double)M * d + (double)Mpad * d + (double)M * (k + 1) * (d + 1) +
                                     (double)RHS_ROWS * ld_skew<T>() * (1 + ksplit)) + 4096.0;
-  const size_t have = h->GV.cap + h->GTsol.cap + h->GMT.cap + h->GMTpart.cap + h->GVN.cap + h->GOut.cap;
+  const size_t have = h->scr.GV.cap + h->scr.GTsol.cap + h->scr.GMT.cap + h->scr.GMTpart.cap + h->scr.GVN.cap + h->scr.GOut.cap;
   size_t freeb = 0, totalb = 0;
   HIPCHK(h, hipMemGetInfo(&freeb, &totalb));
   const double avail = (double)freeb + (double)have;
@@ -1662,30 +1706,21 @@ int predict_grad_var(gpx_handle* h, const void* Xq, int64_t M, void* mean, void*
   double prior[MAX_D + 1];
   int rc;
   if ((rc = grad_priors(h, with_value, prior))) return rc;
-  if ((rc = ensure(h, h->Q, (size_t)M * d * E))) return rc;
-  if ((rc = ensure(h, h->Qs, (size_t)Mpad * d * E))) return rc;
-  if ((rc = ensure(h, h->GV, (size_t)RB * ld * E))) return rc;
-  if ((rc = ensure(h, h->GMT, (size_t)RHS_ROWS * ldm * E))) return rc;
-  if (ksplit > 1 && (rc = ensure(h, h->GMTpart, (size_t)ksplit * RHS_ROWS * ldm * E))) return rc;
-  if ((rc = ensure(h, h->GVN, (size_t)RB * E))) return rc;
+  if ((rc = ensure_queries<T>(h, M))) return rc;
+  if ((rc = ensure(h, h->scr.GV, (size_t)RB * ld * E))) return rc;
+  if ((rc = ensure(h, h->scr.GMT, (size_t)RHS_ROWS * ldm * E))) return rc;
+  if ((rc = ensure_mean_partials<T>(h, h->scr.GMTpart, ldm))) return rc;
+  if ((rc = ensure(h, h->scr.GVN, (size_t)RB * E))) return rc;
   const int64_t o_dvar = M * d * k, o_mean = o_dvar + M * d, o_var = o_mean + M * k;
-  if ((rc = ensure(h, h->GOut, (size_t)(o_var + M) * E))) return rc;
+  if ((rc = ensure(h, h->scr.GOut, (size_t)(o_var + M) * E))) return rc;
   SolveWork<T> sw;
-  if (dense) {
-    if ((rc = ensure(h, h->GTsol, (size_t)2 * RB * ldt * E))) return rc;
-    sw.ldt = ldt;
-    sw.W = (const T*)h->Wblk.p;
-    sw.nbw = h->nbw;
-    sw.T0 = (T*)h->GTsol.p;
-    sw.T1 = sw.T0 + RB * ldt;
-  }
-  T* dV = (T*)h->GV.p;
-  T* out = (T*)h->GOut.p;
+  if ((rc = dense_solve_work<T>(h, h->scr.GTsol, RB, &sw))) return rc;
+  T* dV = (T*)h->scr.GV.p;
+  T* out = (T*)h->scr.GOut.p;
   gpx_timings& tm = h->tm;
   {
     PhaseScope ps(h, &tm.kstar);
-    if ((rc = copy_in(h, h->Q.p, Xq, (size_t)M * d * E, mem_kind))) return rc;
-    launch_scale_points<T>((const T*)h->Q.p, M, Mpad, d, (const double*)h->ls.p, h->n_ls, (T*)h->Qs.p, h->st);
+    if ((rc = upload_queries<T>(h, Xq, M, mem_kind))) return rc;
   }
   for (int64_t m0 = 0; m0 < Mpad; m0 += MB) {
     const int64_t mp = std::min(MB, Mpad - m0);        // padded rows of this batch (a multiple of 128)
@@ -1694,30 +1729,25 @@ int predict_grad_var(gpx_handle* h, const void* Xq, int64_t M, void* mean, void*
     const int64_t ldb = R + ld_skew<T>();
     {
       PhaseScope ps(h, &tm.kstar);
-      launch_kgrad_build<T>(h->cfg.kernel, (const T*)h->Qs.p + m0 * d, mv, mp, (const T*)h->Xs.p, N, Npad, d, h->sf2,
+      launch_kgrad_build<T>(h->cfg.kernel, (const T*)h->scr.Qs.p + m0 * d, mv, mp, (const T*)h->Xs.p, N, Npad, d, h->sf2,
                             (const double*)h->ls.p, h->n_ls, with_value ? 1 : 0, dV, ld, h->st);
     }
     {
       PhaseScope ps(h, &tm.trsm);
-      if ((rc = solve_fwd_enqueue<T>(h, dV, R, (const T*)h->Lfac, ld, Npad, h->nb_pred, (const T*)h->Winv.p,
-                                     dense ? &sw : nullptr)))
+      if ((rc = solve_fwd_enqueue<T>(h, dV, R, (const T*)h->Lfac, ld, Npad, h->nb_pred, (const T*)h->Winv.p, &sw)))
         return rc;
     }
     {  // (mean | dmean)^T (64 x R) = z^T V
       PhaseScope ps(h, &tm.mean);
-      if (ksplit > 1)
-        launch_gemm_nt_splitk<T>((T*)h->GMT.p, ldb, (const T*)h->zT, ld, dV, ld, RHS_ROWS, R, Npad, ksplit,
-                                 (T*)h->GMTpart.p, ldb, h->st);
-      else
-        launch_gemm_nt<T>(64, (T*)h->GMT.p, ldb, (const T*)h->zT, ld, dV, ld, RHS_ROWS, R, Npad, 0, 1, h->st);
+      mean_product<T>(h, (T*)h->scr.GMT.p, ldb, (const T*)h->zT, dV, R, (T*)h->scr.GMTpart.p, ldb);
     }
     {
       PhaseScope ps(h, &tm.var);
-      launch_grad_norms<T>(dV, ld, mp, mv, nblk, Npad, prior, (T*)h->GVN.p, h->st);
+      launch_grad_norms<T>(dV, ld, mp, mv, nblk, Npad, prior, (T*)h->scr.GVN.p, h->st);
     }
     {
       PhaseScope ps(h, &tm.mean);
-      launch_grad_unpack<T>((const T*)h->GMT.p, ldb, (const T*)h->GVN.p, mp, mv, nblk, d, k, with_value ? 1 : 0,
+      launch_grad_unpack<T>((const T*)h->scr.GMT.p, ldb, (const T*)h->scr.GVN.p, mp, mv, nblk, d, k, with_value ? 1 : 0,
                             out + o_mean + m0 * k, out + o_var + m0, out + m0 * d * k, out + o_dvar + m0 * d, h->st);
     }
   }
@@ -1732,22 +1762,17 @@ int predict_grad_var(gpx_handle* h, const void* Xq, int64_t M, void* mean, void*
 template <typename T>
 int predict_grad_impl(gpx_handle* h, const void* Xq, int64_t M, void* mean, void* var, void* dmean, void* dvar,
                       int32_t mem_kind) {
-  gpx_timings& tm = h->tm;
-  tm.kstar = tm.mean = tm.trsm = tm.var = tm.d2h = tm.predict_total = 0;
+  reset_predict_clocks(h->tm);
   int rc;
   {
-    PhaseScope total(h, &tm.predict_total);
+    PhaseScope total(h, &h->tm.predict_total);
     if (!var && !dvar)
       rc = predict_grad_mean_only<T>(h, Xq, M, mean, dmean, mem_kind);
     else
       rc = predict_grad_var<T>(h, Xq, M, mean, var, dmean, dvar, mem_kind, "gpx_predict_grad");
     if (rc) return rc;
   }
-  HIPCHK(h, hipStreamSynchronize(h->st));
-  HIPCHK(h, hipGetLastError());
-  LAUNCHCHK(h);
-  collect_phases(h);
-  return GPX_OK;
+  return finish_call(h);
 }
 
 // ZT <- ZT * L^-T = L^-T restricted to the rows this rank owns: the forward substitution of
@@ -1817,15 +1842,15 @@ int lml_grad_impl(gpx_handle* h, double* lml, double* grad) {
   for (int64_t b = rank; b < nblk; b += P) nloc += std::min<int64_t>(nb, Npad - b * nb);
   int rc;
   if ((rc = ensure_alpha<double>(h))) return rc;
-  if ((rc = ensure(h, h->ZT, (size_t)Npad * ld * 8))) return rc;
+  if ((rc = ensure(h, h->scr.ZT, (size_t)Npad * ld * 8))) return rc;
   if (P > 1) {
-    if ((rc = ensure(h, h->ZTloc, (size_t)std::max<int64_t>(nloc, 1) * ld * 8))) return rc;
-    if ((rc = ensure(h, h->ZTpack, (size_t)nb * Npad * 8))) return rc;
+    if ((rc = ensure(h, h->scr.ZTloc, (size_t)std::max<int64_t>(nloc, 1) * ld * 8))) return rc;
+    if ((rc = ensure(h, h->scr.ZTpack, (size_t)nb * Npad * 8))) return rc;
   }
-  if ((rc = ensure(h, h->gpart, (size_t)((s1n + s2n) * ntheta + 2 * ntheta + 1) * 8))) return rc;
-  double* ZT = (double*)h->ZT.p;
-  double* Zl = P > 1 ? (double*)h->ZTloc.p : ZT;
-  double* part1 = (double*)h->gpart.p;
+  if ((rc = ensure(h, h->scr.gpart, (size_t)((s1n + s2n) * ntheta + 2 * ntheta + 1) * 8))) return rc;
+  double* ZT = (double*)h->scr.ZT.p;
+  double* Zl = P > 1 ? (double*)h->scr.ZTloc.p : ZT;
+  double* part1 = (double*)h->scr.gpart.p;
   double* part2 = part1 + s1n * ntheta;
   double* outv = part2 + s2n * ntheta;  // [ntheta] K^-1 sums, [ntheta] alpha sums, [1] y . alpha
   hipStream_t st = h->st;
@@ -1844,7 +1869,7 @@ int lml_grad_impl(gpx_handle* h, double* lml, double* grad) {
       if ((rc = trtri_enqueue(h, Zl, (const double*)h->Lfac, ld, Npad, nb, (const double*)h->Winv.p, P, rank)))
         return rc;
       if (P > 1) {  // all-gather: block b from rank b % P, only the columns right of its zeros
-        double* pack = (double*)h->ZTpack.p;
+        double* pack = (double*)h->scr.ZTpack.p;
         HIPCHK(h, hipMemsetAsync(ZT, 0, (size_t)Npad * ld * 8, st));
         for (int64_t b = 0; b < nblk; ++b) {
           const int64_t r0 = b * nb, hb = std::min<int64_t>(nb, Npad - r0), w = Npad - r0;
@@ -1870,10 +1895,7 @@ int lml_grad_impl(gpx_handle* h, double* lml, double* grad) {
   }
   double host[2 * (MAX_D + 2) + 1];
   HIPCHK(h, hipMemcpyAsync(host, outv, (size_t)(2 * ntheta + 1) * 8, hipMemcpyDeviceToHost, st));
-  HIPCHK(h, hipStreamSynchronize(st));
-  HIPCHK(h, hipGetLastError());
-  LAUNCHCHK(h);
-  collect_phases(h);
+  if ((rc = finish_call(h))) return rc;
   for (int t = 0; t < ntheta; ++t) grad[t] = 0.5 * (host[ntheta + t] - (double)k * host[t]);
   *lml = -0.5 * host[2 * ntheta] - 0.5 * (double)k * h->logdet -
          0.5 * (double)N * (double)k * 1.8378770664093454835606594728112;  // log(2 pi)
@@ -2000,10 +2022,7 @@ int mixed_fit(gpx_handle* h, const void* X, const void* y, int64_t N, int32_t d,
     launch_rows_add_f32_to_f64((const float*)h->RT32.p, ld32, A64, Npad, k, N, Npad, 1, st);
   }
   HIPCHK(h, hipMemcpyAsync(hn, rn, 24, hipMemcpyDeviceToHost, st));
-  HIPCHK(h, hipStreamSynchronize(st));
-  HIPCHK(h, hipGetLastError());
-  LAUNCHCHK(h);
-  collect_phases(h);
+  if ((rc = finish_call(h))) return rc;
   tm.fit_total += tm.refine;
   tm.refine_iters = iters;
   if (hn[2] > 0) {
@@ -2018,13 +2037,13 @@ int mixed_predict(gpx_handle* h, const void* Xq, int64_t M, void* mean, void* va
   const int d = h->d, k = h->k;
   const int64_t Mpad = round_up(M, TILE);
   gpx_timings& tm = h->tm;
-  tm.kstar = tm.mean = tm.trsm = tm.var = tm.d2h = tm.predict_total = 0;
+  reset_predict_clocks(tm);
   int rc;
-  if ((rc = ensure(h, h->Q64, (size_t)M * d * 8))) return rc;
-  if ((rc = ensure(h, h->Qs64, (size_t)Mpad * d * 8))) return rc;
-  if ((rc = ensure(h, h->Q32, (size_t)M * d * 4))) return rc;
-  if ((rc = ensure(h, h->M64, (size_t)(MIXED_KMAX * Mpad + (size_t)M * k + Mpad) * 8))) return rc;
-  double* MT64 = (double*)h->M64.p;            // [8][Mpad] transposed means
+  if ((rc = ensure(h, h->scr.Q64, (size_t)M * d * 8))) return rc;
+  if ((rc = ensure(h, h->scr.Qs64, (size_t)Mpad * d * 8))) return rc;
+  if ((rc = ensure(h, h->scr.Q32, (size_t)M * d * 4))) return rc;
+  if ((rc = ensure(h, h->scr.M64, (size_t)(MIXED_KMAX * Mpad + (size_t)M * k + Mpad) * 8))) return rc;
+  double* MT64 = (double*)h->scr.M64.p;            // [8][Mpad] transposed means
   double* mout = MT64 + MIXED_KMAX * Mpad;     // (M x k)
   double* vout = mout + (size_t)M * k;         // (M)
   hipStream_t st = h->st;
@@ -2034,33 +2053,33 @@ int mixed_predict(gpx_handle* h, const void* Xq, int64_t M, void* mean, void* va
     // device scratch, before this call's own phases (it synchronises and folds its own clocks).  Its fp32 mean is not
     // used: the mean comes from the refined fp64 alpha below, replicated work on every rank.
     if ((rc = ensure(h, h->P32out, (size_t)M * (k + 1) * 4))) return rc;
-    if ((rc = copy_in(h, h->Q64.p, Xq, (size_t)M * d * 8, mem_kind))) return rc;
-    launch_f64_to_f32((const double*)h->Q64.p, (float*)h->Q32.p, M * d, st);
+    if ((rc = copy_in(h, h->scr.Q64.p, Xq, (size_t)M * d * 8, mem_kind))) return rc;
+    launch_f64_to_f32((const double*)h->scr.Q64.p, (float*)h->scr.Q32.p, M * d, st);
     float* m32 = (float*)h->P32out.p;
     float* v32 = m32 + (size_t)M * k;
     const bool discard = h->discard_out;
     h->discard_out = false;  // the scratch outputs are wanted on every rank
-    rc = shard_predict<float>(h, h->Q32.p, M, m32, v32, GPX_MEM_DEVICE);
+    rc = shard_predict<float>(h, h->scr.Q32.p, M, m32, v32, GPX_MEM_DEVICE);
     h->discard_out = discard;
     if (rc) return rc;
     const double keep[6] = {tm.kstar, tm.trsm, tm.var, tm.mean, tm.predict_total, tm.comm};
     for (int i = 0; i < 6; ++i) shard_ms[i] = keep[i];
-    tm.kstar = tm.mean = tm.trsm = tm.var = tm.d2h = tm.predict_total = 0;
+    reset_predict_clocks(tm);
     launch_f32_to_f64(v32, vout, M, st);
   }
   {
     PhaseScope total(h, &tm.predict_total);
-    if ((rc = copy_in(h, h->Q64.p, Xq, (size_t)M * d * 8, mem_kind))) return rc;
+    if ((rc = copy_in(h, h->scr.Q64.p, Xq, (size_t)M * d * 8, mem_kind))) return rc;
     if (var && !h->comm) {  // variance through the fp32 factor (its own K*, V^T = K* L^-T, row sums)
-      launch_f64_to_f32((const double*)h->Q64.p, (float*)h->Q32.p, M * d, st);
-      if ((rc = predict_core<float>(h, h->Q32.p, M, true, GPX_MEM_DEVICE))) return rc;
+      launch_f64_to_f32((const double*)h->scr.Q64.p, (float*)h->scr.Q32.p, M * d, st);
+      if ((rc = predict_core<float>(h, h->scr.Q32.p, M, true, GPX_MEM_DEVICE))) return rc;
       launch_f32_to_f64((const float*)h->var.p, vout, M, st);
     }
     {
       PhaseScope ps(h, &tm.mean);
-      launch_scale_points<double>((const double*)h->Q64.p, M, Mpad, d, (const double*)h->ls.p, h->n_ls,
-                                  (double*)h->Qs64.p, st);
-      launch_kmatvec(h->cfg.kernel, (const double*)h->Qs64.p, M, Mpad, (const double*)h->Xs64.p, Npad, d, h->sf2,
+      launch_scale_points<double>((const double*)h->scr.Q64.p, M, Mpad, d, (const double*)h->ls.p, h->n_ls,
+                                  (double*)h->scr.Qs64.p, st);
+      launch_kmatvec(h->cfg.kernel, (const double*)h->scr.Qs64.p, M, Mpad, (const double*)h->Xs64.p, Npad, d, h->sf2,
                      0.0, nullptr, (const double*)h->A64.p, Npad, k, 1.0, MT64, Mpad, st);
       launch_unpack_rhs<double>(MT64, Mpad, M, k, 1.0, mout, st);
     }
@@ -2070,10 +2089,7 @@ int mixed_predict(gpx_handle* h, const void* Xq, int64_t M, void* mean, void* va
       if (var && (rc = copy_out(h, var, vout, (size_t)M * 8, mem_kind))) return rc;
     }
   }
-  HIPCHK(h, hipStreamSynchronize(st));
-  HIPCHK(h, hipGetLastError());
-  LAUNCHCHK(h);
-  collect_phases(h);
+  if ((rc = finish_call(h))) return rc;
   tm.kstar += shard_ms[0];
   tm.trsm += shard_ms[1];
   tm.var += shard_ms[2];
@@ -2084,9 +2100,9 @@ int mixed_predict(gpx_handle* h, const void* Xq, int64_t M, void* mean, void* va
 
 int mixed_alpha(gpx_handle* h, void* out) {
   int rc;
-  if ((rc = ensure(h, h->M64, (size_t)h->N * h->k * 8))) return rc;
-  launch_unpack_rhs<double>((const double*)h->A64.p, h->Npad, h->N, h->k, 1.0, (double*)h->M64.p, h->st);
-  HIPCHK(h, hipMemcpyAsync(out, h->M64.p, (size_t)h->N * h->k * 8, hipMemcpyDeviceToHost, h->st));
+  if ((rc = ensure(h, h->scr.M64, (size_t)h->N * h->k * 8))) return rc;
+  launch_unpack_rhs<double>((const double*)h->A64.p, h->Npad, h->N, h->k, 1.0, (double*)h->scr.M64.p, h->st);
+  HIPCHK(h, hipMemcpyAsync(out, h->scr.M64.p, (size_t)h->N * h->k * 8, hipMemcpyDeviceToHost, h->st));
   HIPCHK(h, hipStreamSynchronize(h->st));
   return GPX_OK;
 }
@@ -2103,6 +2119,15 @@ int alpha_impl(gpx_handle* h, void* out) {
 }
 
 }  // namespace
+
+gpx_handle::~gpx_handle() {
+  for (hipStream_t s : {st, st2, st3, st4, st5})
+    if (s) (void)hipStreamSynchronize(s);
+  destroy_comm(this);
+  for (hipEvent_t e : ev_pool) (void)hipEventDestroy(e);
+  for (hipStream_t s : {st, st2, st3, st4, st5})
+    if (s) (void)hipStreamDestroy(s);
+}
 
 extern "C" {
 
@@ -2175,8 +2200,6 @@ int gpx_create(gpx_handle** out, const gpx_config* cfg) try {
       hipStreamCreateWithPriority(&h->st2, hipStreamNonBlocking, prio_hi) != hipSuccess ||
       hipStreamCreateWithPriority(&h->st3, hipStreamNonBlocking, prio_hi) != hipSuccess ||
       hipStreamCreateWithFlags(&h->st4, hipStreamNonBlocking) != hipSuccess) {
-    for (hipStream_t sx : {h->st, h->st2, h->st3})
-      if (sx) (void)hipStreamDestroy(sx);
     delete h;
     return fail(nullptr, GPX_E_HIP, "gpx_create: hipSetDevice/hipStreamCreate failed");
   }
@@ -2187,67 +2210,46 @@ GPX_CATCH_ALL
 
 void gpx_destroy(gpx_handle* h) {
   if (!h) return;
-  if (h->group) {
+  if (h->group)
     destroy_group(h);
-    delete h;
-    return;
-  }
-  (void)hipSetDevice(h->cfg.device);
-  if (h->st) (void)hipStreamSynchronize(h->st);
-  if (h->st2) (void)hipStreamSynchronize(h->st2);
-  if (h->st3) (void)hipStreamSynchronize(h->st3);
-  if (h->st4) (void)hipStreamSynchronize(h->st4);
-  if (h->st5) (void)hipStreamSynchronize(h->st5);
-  for (DevBuf* b : {&h->X, &h->Xs, &h->ls, &h->K, &h->Winv, &h->P, &h->YT, &h->Y, &h->scalars,
-                    &h->info, &h->Q, &h->Qs, &h->VT, &h->MT, &h->MTpart, &h->var, &h->meanout, &h->G,
-                    &h->Dbuf, &h->Sbuf, &h->YTloc, &h->Cneg, &h->Sv, &h->AT, &h->Lfull, &h->GatherS,
-                    &h->GatherR, &h->outM, &h->outV, &h->ZT, &h->ZTloc, &h->ZTpack, &h->gpart, &h->Wblk, &h->Ublk, &h->Tsol, &h->X64, &h->Y64, &h->Xs64,
-                    &h->A64, &h->Aprev, &h->R64, &h->resv_ring, &h->RTloc, &h->P32out, &h->X32, &h->Y32, &h->RT32, &h->Q64, &h->Qs64, &h->Q32, &h->M64, &h->rn, &h->Zfew,
-                    &h->JVT, &h->JTsol, &h->JSig, &h->JSigF, &h->JWinv, &h->JP, &h->JWblk, &h->JUblk, &h->JInfo, &h->JZT, &h->JST,
-                    &h->JZin, &h->JOut})
-    release(*b);
-  destroy_comm(h);
-  for (auto e : h->ev_pool) (void)hipEventDestroy(e);
-  if (h->st) (void)hipStreamDestroy(h->st);
-  if (h->st2) (void)hipStreamDestroy(h->st2);
-  if (h->st3) (void)hipStreamDestroy(h->st3);
-  if (h->st4) (void)hipStreamDestroy(h->st4);
-  if (h->st5) (void)hipStreamDestroy(h->st5);
+  else
+    (void)hipSetDevice(h->cfg.device);
   delete h;
 }
+
+namespace {
+// the argument checks of gpx_fit and gpx_fit_predict (with_queries: Xq, mean and M as well); `fn` heads the messages
+int check_fit_args(gpx_handle* h, const char* fn, bool with_queries, bool any_null, int64_t N, int64_t M, int32_t d, int32_t k,
+                   const double* lengthscale, int32_t n_ls, double sf2, double sn2, double jitter, int32_t mem_kind) {
+  auto bad = [&](const char* what) { return fail(h, GPX_E_ARG, (std::string(fn) + ": " + what).c_str()); };
+  if (any_null) return bad("null argument");
+  if (N <= 0 || d <= 0 || d > MAX_D || (with_queries && M <= 0))
+    return bad(with_queries ? "need N, M > 0 and 1 <= d <= 32" : "need N > 0 and 1 <= d <= 32");
+  if (k <= 0 || k > RHS_ROWS) return bad("need 1 <= k <= 64 target columns");
+  if (n_ls != 1 && n_ls != d) return bad("n_ls must be 1 or d");
+  if (mem_kind != GPX_MEM_HOST && mem_kind != GPX_MEM_DEVICE) return bad("bad mem_kind");
+  if (!(sf2 > 0.0) || sn2 < 0.0 || jitter < 0.0) return bad("need sf2 > 0, sn2 >= 0, jitter >= 0");
+  for (int i = 0; i < n_ls; ++i)
+    if (!(lengthscale[i] > 0.0)) return bad("lengthscale must be > 0");
+  if (N > (int64_t)INT_MAX - 4096) return bad("N too large");
+  return GPX_OK;
+}
+}  // namespace
 
 int gpx_fit(gpx_handle* h, const void* X, const void* y, int64_t N, int32_t d, int32_t k,
             const double* lengthscale, int32_t n_ls, double sf2, double sn2, double jitter,
             int32_t mem_kind, int64_t* info) try {
   if (!h) return GPX_E_ARG;
-  if (!X || !y || !lengthscale || !info) return fail(h, GPX_E_ARG, "gpx_fit: null argument");
-  if (N <= 0 || d <= 0 || d > MAX_D) return fail(h, GPX_E_ARG, "gpx_fit: need N > 0 and 1 <= d <= 32");
-  if (k <= 0 || k > RHS_ROWS) return fail(h, GPX_E_ARG, "gpx_fit: need 1 <= k <= 64 target columns");
-  if (n_ls != 1 && n_ls != d) return fail(h, GPX_E_ARG, "gpx_fit: n_ls must be 1 or d");
-  if (mem_kind != GPX_MEM_HOST && mem_kind != GPX_MEM_DEVICE)
-    return fail(h, GPX_E_ARG, "gpx_fit: bad mem_kind");
-  if (!(sf2 > 0.0) || sn2 < 0.0 || jitter < 0.0)
-    return fail(h, GPX_E_ARG, "gpx_fit: need sf2 > 0, sn2 >= 0, jitter >= 0");
-  for (int i = 0; i < n_ls; ++i)
-    if (!(lengthscale[i] > 0.0)) return fail(h, GPX_E_ARG, "gpx_fit: lengthscale must be > 0");
-  if (N > (int64_t)INT_MAX - 4096) return fail(h, GPX_E_ARG, "gpx_fit: N too large");
+  int rc;
+  if ((rc = check_fit_args(h, "gpx_fit", false, !X || !y || !lengthscale || !info, N, 0, d, k, lengthscale, n_ls, sf2, sn2,
+                           jitter, mem_kind)))
+    return rc;
   if (h->group) return group_fit(h, X, y, N, d, k, lengthscale, n_ls, sf2, sn2, jitter, mem_kind, info);
-  HIPCHK(h, hipSetDevice(h->cfg.device));
-  h->fitted = false;
-  h->err.clear();
-  h->phases.clear();  // an earlier call that failed mid-way must not leak its event pairs
-  h->ev_used = 0;
-  if (h->cfg.world > 1 || h->comm) {  // a 1-rank communicator also takes the sharded schedule
-    if (h->cfg.dtype == GPX_MIXED) return mixed_fit(h, X, y, N, d, k, lengthscale, n_ls, sf2, sn2, jitter, mem_kind, info);
-    if (h->cfg.dtype == GPX_F32) return shard_fit<float>(h, X, y, N, d, k, lengthscale, n_ls, sf2, sn2, jitter, mem_kind, info);
-    return shard_fit<double>(h, X, y, N, d, k, lengthscale, n_ls, sf2, sn2, jitter, mem_kind, info);
-  }
-
-  if (h->cfg.dtype == GPX_MIXED)
-    return mixed_fit(h, X, y, N, d, k, lengthscale, n_ls, sf2, sn2, jitter, mem_kind, info);
-  if (h->cfg.dtype == GPX_F32)
-    return fit_impl<float>(h, X, y, N, d, k, lengthscale, n_ls, sf2, sn2, jitter, mem_kind, info);
-  return fit_impl<double>(h, X, y, N, d, k, lengthscale, n_ls, sf2, sn2, jitter, mem_kind, info);
+  if ((rc = begin_fit(h))) return rc;
+  if (h->cfg.dtype == GPX_MIXED) return mixed_fit(h, X, y, N, d, k, lengthscale, n_ls, sf2, sn2, jitter, mem_kind, info);
+  if (h->cfg.world > 1 || h->comm)  // a 1-rank communicator also takes the sharded schedule
+    return BY_DTYPE(h, shard_fit, h, X, y, N, d, k, lengthscale, n_ls, sf2, sn2, jitter, mem_kind, info);
+  return BY_DTYPE(h, fit_impl, h, X, y, N, d, k, lengthscale, n_ls, sf2, sn2, jitter, mem_kind, info);
 }
 GPX_CATCH_ALL
 
@@ -2255,16 +2257,10 @@ int gpx_fit_predict(gpx_handle* h, const void* X, const void* y, int64_t N, int3
                     const double* lengthscale, int32_t n_ls, double sf2, double sn2, double jitter, const void* Xq,
                     int64_t M, void* mean, void* var, int32_t mem_kind, int64_t* info) try {
   if (!h) return GPX_E_ARG;
-  if (!X || !y || !lengthscale || !info || !Xq || !mean) return fail(h, GPX_E_ARG, "gpx_fit_predict: null argument");
-  if (N <= 0 || d <= 0 || d > MAX_D || M <= 0) return fail(h, GPX_E_ARG, "gpx_fit_predict: need N, M > 0 and 1 <= d <= 32");
-  if (k <= 0 || k > RHS_ROWS) return fail(h, GPX_E_ARG, "gpx_fit_predict: need 1 <= k <= 64 target columns");
-  if (n_ls != 1 && n_ls != d) return fail(h, GPX_E_ARG, "gpx_fit_predict: n_ls must be 1 or d");
-  if (mem_kind != GPX_MEM_HOST && mem_kind != GPX_MEM_DEVICE) return fail(h, GPX_E_ARG, "gpx_fit_predict: bad mem_kind");
-  if (!(sf2 > 0.0) || sn2 < 0.0 || jitter < 0.0)
-    return fail(h, GPX_E_ARG, "gpx_fit_predict: need sf2 > 0, sn2 >= 0, jitter >= 0");
-  for (int i = 0; i < n_ls; ++i)
-    if (!(lengthscale[i] > 0.0)) return fail(h, GPX_E_ARG, "gpx_fit_predict: lengthscale must be > 0");
-  if (N > (int64_t)INT_MAX - 4096) return fail(h, GPX_E_ARG, "gpx_fit_predict: N too large");
+  int rc;
+  if ((rc = check_fit_args(h, "gpx_fit_predict", true, !X || !y || !lengthscale || !info || !Xq || !mean, N, M, d, k,
+                           lengthscale, n_ls, sf2, sn2, jitter, mem_kind)))
+    return rc;
   if (h->group) return group_fit_predict(h, X, y, N, d, k, lengthscale, n_ls, sf2, sn2, jitter, Xq, M, mean, var, mem_kind, info);
   // Shards (round 4): every rank's slice of the query points rides through the sharded factorisation as bordered rows of
   // its local row set (shard_fit with query points + shard_fused_tail) — in the split schedule, up to 8192 rows per rank.
@@ -2277,49 +2273,30 @@ int gpx_fit_predict(gpx_handle* h, const void* X, const void* y, int64_t N, int3
     const bool ride = h->comm && h->cfg.dtype != GPX_MIXED && (!se || atoi(se) != 0) && (!fe || atoi(fe) != 0) &&
                       round_up((M + P - 1) / P, TILE) <= 8192;
     if (!ride) {
-      const int rc2 = gpx_fit(h, X, y, N, d, k, lengthscale, n_ls, sf2, sn2, jitter, mem_kind, info);
-      if (rc2 != GPX_OK || *info != 0) return rc2;
+      rc = gpx_fit(h, X, y, N, d, k, lengthscale, n_ls, sf2, sn2, jitter, mem_kind, info);
+      if (rc != GPX_OK || *info != 0) return rc;
       return gpx_predict(h, Xq, M, mean, var, mem_kind);
     }
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    h->fitted = false;
-    h->err.clear();
-    h->phases.clear();
-    h->ev_used = 0;
-    int rc2 = h->cfg.dtype == GPX_F32
-                  ? shard_fit<float>(h, X, y, N, d, k, lengthscale, n_ls, sf2, sn2, jitter, mem_kind, info, false, Xq, M)
-                  : shard_fit<double>(h, X, y, N, d, k, lengthscale, n_ls, sf2, sn2, jitter, mem_kind, info, false, Xq, M);
-    if (rc2 != GPX_OK || !h->fitted) return rc2;
-    h->phases.clear();
-    h->ev_used = 0;
-    return h->cfg.dtype == GPX_F32 ? shard_fused_tail<float>(h, M, mean, var, mem_kind)
-                                   : shard_fused_tail<double>(h, M, mean, var, mem_kind);
+    if ((rc = begin_fit(h))) return rc;
+    rc = BY_DTYPE(h, shard_fit, h, X, y, N, d, k, lengthscale, n_ls, sf2, sn2, jitter, mem_kind, info, false, Xq, M);
+    if (rc != GPX_OK || !h->fitted) return rc;
+    return BY_DTYPE(h, shard_fused_tail, h, M, mean, var, mem_kind);
   }
   // one batch of query points rides through the factorisation; more than that (ABI v5: it was GPX_E_UNSUPPORTED): the
   // first batch rides, the others go through the ordinary predict against the factor the pass leaves behind — query
   // rows are independent, so the split changes no bit of either part
   const int64_t Mb = std::min<int64_t>(M, pred_batch_rows(h, round_up(M, TILE), 0, false));
-  HIPCHK(h, hipSetDevice(h->cfg.device));
-  h->fitted = false;
-  h->err.clear();
-  h->phases.clear();
-  h->ev_used = 0;
+  if ((rc = begin_fit(h))) return rc;
   const size_t es = h->cfg.dtype == GPX_F32 ? sizeof(float) : sizeof(double);
-  int rc = h->cfg.dtype == GPX_F32
-               ? fit_impl<float>(h, X, y, N, d, k, lengthscale, n_ls, sf2, sn2, jitter, mem_kind, info, Xq, Mb)
-               : fit_impl<double>(h, X, y, N, d, k, lengthscale, n_ls, sf2, sn2, jitter, mem_kind, info, Xq, Mb);
+  rc = BY_DTYPE(h, fit_impl, h, X, y, N, d, k, lengthscale, n_ls, sf2, sn2, jitter, mem_kind, info, Xq, Mb);
   if (rc != GPX_OK || !h->fitted) return rc;  // *info > 0: not positive definite, nothing predicted
-  rc = h->cfg.dtype == GPX_F32 ? fused_predict_tail<float>(h, Mb, mean, var, mem_kind)
-                               : fused_predict_tail<double>(h, Mb, mean, var, mem_kind);
+  rc = BY_DTYPE(h, fused_predict_tail, h, Mb, mean, var, mem_kind);
   if (rc != GPX_OK || Mb == M) return rc;
   const gpx_timings first = h->tm;  // the rest through predict; its clocks are added to the pass's
-  h->phases.clear();
-  h->ev_used = 0;
   const void* Xr = (const char*)Xq + (size_t)Mb * d * es;
   void* mr = (char*)mean + (size_t)Mb * k * es;
   void* vr = var ? (char*)var + (size_t)Mb * es : nullptr;
-  rc = h->cfg.dtype == GPX_F32 ? predict_impl<float>(h, Xr, M - Mb, mr, vr, mem_kind)
-                               : predict_impl<double>(h, Xr, M - Mb, mr, vr, mem_kind);
+  rc = BY_DTYPE(h, predict_impl, h, Xr, M - Mb, mr, vr, mem_kind);
   h->tm.kstar += first.kstar;
   h->tm.mean += first.mean;
   h->tm.trsm += first.trsm;
@@ -2337,18 +2314,11 @@ int gpx_predict(gpx_handle* h, const void* Xq, int64_t M, void* mean, void* var,
   if (mem_kind != GPX_MEM_HOST && mem_kind != GPX_MEM_DEVICE)
     return fail(h, GPX_E_ARG, "gpx_predict: bad mem_kind");
   if (h->group) return group_predict(h, Xq, M, mean, var, mem_kind);
-  HIPCHK(h, hipSetDevice(h->cfg.device));
-  h->err.clear();
-  h->phases.clear();
-  h->ev_used = 0;
-  if (h->cfg.world > 1 || h->comm) {
-    if (h->cfg.dtype == GPX_MIXED) return mixed_predict(h, Xq, M, mean, var, mem_kind);
-    if (h->cfg.dtype == GPX_F32) return shard_predict<float>(h, Xq, M, mean, var, mem_kind);
-    return shard_predict<double>(h, Xq, M, mean, var, mem_kind);
-  }
+  int rc;
+  if ((rc = begin_call(h))) return rc;
   if (h->cfg.dtype == GPX_MIXED) return mixed_predict(h, Xq, M, mean, var, mem_kind);
-  if (h->cfg.dtype == GPX_F32) return predict_impl<float>(h, Xq, M, mean, var, mem_kind);
-  return predict_impl<double>(h, Xq, M, mean, var, mem_kind);
+  if (h->cfg.world > 1 || h->comm) return BY_DTYPE(h, shard_predict, h, Xq, M, mean, var, mem_kind);
+  return BY_DTYPE(h, predict_impl, h, Xq, M, mean, var, mem_kind);
 }
 GPX_CATCH_ALL
 
@@ -2374,12 +2344,8 @@ int gpx_predict_cov(gpx_handle* h, const void* Xq, int64_t M, void* mean, void* 
   if (M > (int64_t)INT_MAX - 4096) return fail(h, GPX_E_ARG, "gpx_predict_cov: M too large");
   int rc;
   if ((rc = posterior_refused(h, "gpx_predict_cov"))) return rc;
-  HIPCHK(h, hipSetDevice(h->cfg.device));
-  h->err.clear();
-  h->phases.clear();
-  h->ev_used = 0;
-  if (h->cfg.dtype == GPX_F32) return predict_cov_impl<float>(h, Xq, M, mean, cov, mem_kind);
-  return predict_cov_impl<double>(h, Xq, M, mean, cov, mem_kind);
+  if ((rc = begin_call(h))) return rc;
+  return BY_DTYPE(h, predict_cov_impl, h, Xq, M, mean, cov, mem_kind);
 }
 GPX_CATCH_ALL
 
@@ -2397,13 +2363,8 @@ int gpx_sample_posterior(gpx_handle* h, const void* Xq, int64_t M, int64_t S, ui
   if (M > (int64_t)INT_MAX - 4096 || S > (int64_t)1 << 40) return fail(h, GPX_E_ARG, "gpx_sample_posterior: M or S too large");
   int rc;
   if ((rc = posterior_refused(h, "gpx_sample_posterior"))) return rc;
-  HIPCHK(h, hipSetDevice(h->cfg.device));
-  h->err.clear();
-  h->phases.clear();
-  h->ev_used = 0;
-  if (h->cfg.dtype == GPX_F32)
-    return sample_posterior_impl<float>(h, Xq, M, S, seed, z, diag_add, jitter, max_tries, out, jitter_used, info, mem_kind);
-  return sample_posterior_impl<double>(h, Xq, M, S, seed, z, diag_add, jitter, max_tries, out, jitter_used, info, mem_kind);
+  if ((rc = begin_call(h))) return rc;
+  return BY_DTYPE(h, sample_posterior_impl, h, Xq, M, S, seed, z, diag_add, jitter, max_tries, out, jitter_used, info, mem_kind);
 }
 GPX_CATCH_ALL
 
@@ -2417,12 +2378,8 @@ int gpx_predict_grad(gpx_handle* h, const void* Xq, int64_t M, void* mean, void*
   if (!cov::differentiable(h->cfg.kernel)) return fail(h, GPX_E_UNSUPPORTED, "gpx_predict_grad: " MATERN12_NO_GRAD);
   int rc;
   if ((rc = posterior_refused(h, "gpx_predict_grad"))) return rc;
-  HIPCHK(h, hipSetDevice(h->cfg.device));
-  h->err.clear();
-  h->phases.clear();
-  h->ev_used = 0;
-  if (h->cfg.dtype == GPX_F32) return predict_grad_impl<float>(h, Xq, M, mean, var, dmean, dvar, mem_kind);
-  return predict_grad_impl<double>(h, Xq, M, mean, var, dmean, dvar, mem_kind);
+  if ((rc = begin_call(h))) return rc;
+  return BY_DTYPE(h, predict_grad_impl, h, Xq, M, mean, var, dmean, dvar, mem_kind);
 }
 GPX_CATCH_ALL
 
@@ -2437,8 +2394,7 @@ int gpx_get_alpha(gpx_handle* h, void* out) try {
   }
   HIPCHK(h, hipSetDevice(h->cfg.device));
   if (h->cfg.dtype == GPX_MIXED) return mixed_alpha(h, out);
-  if (h->cfg.dtype == GPX_F32) return alpha_impl<float>(h, out);
-  return alpha_impl<double>(h, out);
+  return BY_DTYPE(h, alpha_impl, h, out);
 }
 GPX_CATCH_ALL
 
@@ -2448,10 +2404,8 @@ int gpx_lml_grad(gpx_handle* h, double* lml, double* grad) try {
   if (h->cfg.dtype != GPX_F64) return fail(h, GPX_E_UNSUPPORTED, "gpx_lml_grad: fp64 handles only");
   if (h->group) return group_lml_grad(h, lml, grad);
   if (h->cfg.world > 1 && !h->comm) return fail(h, GPX_E_ARG, "gpx_lml_grad: sharded handle without a communicator");
-  HIPCHK(h, hipSetDevice(h->cfg.device));
-  h->err.clear();
-  h->phases.clear();
-  h->ev_used = 0;
+  int rc;
+  if ((rc = begin_call(h))) return rc;
   if (h->comm && !h->repl) return shard_lml_grad_dist(h, lml, grad);  // factor only held distributed
   return lml_grad_impl(h, lml, grad);
 }
@@ -2468,11 +2422,7 @@ int gpx_release_scratch(gpx_handle* h) try {
     HIPCHK(h, hipSetDevice(m->cfg.device));
     for (hipStream_t sx : {m->st, m->st2, m->st3, m->st4, m->st5})
       if (sx) HIPCHK(h, hipStreamSynchronize(sx));
-    for (DevBuf* b : {&m->ZT, &m->ZTloc, &m->ZTpack, &m->gpart, &m->MTpart, &m->VT, &m->Tsol, &m->Q, &m->Qs, &m->MT, &m->Sv, &m->Q64, &m->Qs64, &m->Q32,
-                      &m->M64, &m->GatherS, &m->GatherR, &m->outM, &m->outV, &m->JVT, &m->JTsol, &m->JSig, &m->JSigF,
-                      &m->JWinv, &m->JP, &m->JWblk, &m->JUblk, &m->JInfo, &m->JZT, &m->JST, &m->JZin, &m->JOut,
-                      &m->GV, &m->GTsol, &m->GMT, &m->GMTpart, &m->GVN, &m->GPart, &m->GOut})
-      release(*b);
+    m->scr = {};  // every scratch buffer moves into a temporary that frees it
   }
   return GPX_OK;
 }
@@ -2516,16 +2466,7 @@ struct Scratch {  // a throw-away handle-like context for the host-buffer entry 
          hipStreamCreateWithFlags(&h.st3, hipStreamNonBlocking) == hipSuccess &&
          hipStreamCreateWithFlags(&h.st4, hipStreamNonBlocking) == hipSuccess;
   }
-  ~Scratch() {
-    for (hipStream_t s : {h.st, h.st2, h.st3, h.st4})
-      if (s) {
-        (void)hipStreamSynchronize(s);
-        (void)hipStreamDestroy(s);
-      }
-    for (auto e : h.ev_pool) (void)hipEventDestroy(e);
-    release(h.resv_ring);
-  }
-};
+};  // (~gpx_handle tears down streams, events and whatever buffer a scheduler function allocated)
 #define TCHK(call)                                   \
   do {                                               \
     if ((call) != hipSuccess) {                      \

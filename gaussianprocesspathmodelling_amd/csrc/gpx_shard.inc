@@ -304,7 +304,6 @@ struct LocalHub {
 struct LocalComm : Comm {
   LocalHub* hub = nullptr;
   DevBuf scratch;  // world x count staging of the reductions (element type of the call)
-  ~LocalComm() override { release(scratch); }
   int lost(gpx_handle* h) {
     if (h->err.empty()) h->err = "device group aborted: another rank failed";
     return GPX_E_COMM;
@@ -578,10 +577,7 @@ int shard_fit(gpx_handle* h, const void* X, const void* y, int64_t N, int32_t d,
   if ((rc = ensure(h, h->Xs, (size_t)Npad * d * sizeof(T)))) return rc;
   if ((rc = ensure(h, h->ls, MAX_D * 8))) return rc;
   if ((rc = ensure(h, h->K, (size_t)std::max<int64_t>(nloc + Mq, nb) * ld * sizeof(T)))) return rc;
-  if (Mq > 0) {
-    if ((rc = ensure(h, h->Q, (size_t)Mr * d * sizeof(T)))) return rc;
-    if ((rc = ensure(h, h->Qs, (size_t)Mq * d * sizeof(T)))) return rc;
-  }
+  if (Mq > 0 && (rc = ensure_queries<T>(h, Mr))) return rc;
   if ((rc = ensure(h, h->Winv, (size_t)(Npad / KB) * KB * KB * sizeof(T)))) return rc;
   // two of each panel buffer: the look-ahead stream fills one set while the main stream
   // still reads the other
@@ -683,9 +679,8 @@ int shard_fit(gpx_handle* h, const void* X, const void* y, int64_t N, int32_t d,
         launch_fix_diag(A + lb * nb * ld + g * nb, ld, nb, (int)mvalid, sn2 + jitter, st);
       }
       if (Mq > 0) {  // bordered rows [nloc, nloc + Mq): K(Xq_r, X), every column
-        if ((rc = copy_in(h, h->Q.p, (const char*)Xq + (size_t)mq0 * d * sizeof(T), (size_t)Mr * d * sizeof(T), mem_kind))) return rc;
-        launch_scale_points((const T*)h->Q.p, Mr, Mq, d, (const double*)h->ls.p, n_ls, (T*)h->Qs.p, st);
-        launch_kbuild_cross(h->cfg.kernel, (const T*)h->Qs.p, Mr, Mq, Xs, N, Npad, d, sf2, A + nloc * ld, ld, st);
+        if ((rc = upload_queries<T>(h, (const char*)Xq + (size_t)mq0 * d * sizeof(T), Mr, mem_kind))) return rc;
+        launch_kbuild_cross(h->cfg.kernel, (const T*)h->scr.Qs.p, Mr, Mq, Xs, N, Npad, d, sf2, A + nloc * ld, ld, st);
       }
     }
     {
@@ -1006,16 +1001,11 @@ int shard_fit(gpx_handle* h, const void* X, const void* y, int64_t N, int32_t d,
   HIPCHK(h, hipMemcpyAsync(scal + 1, &dinfo, sizeof(double), hipMemcpyHostToDevice, st));
   COMMCHK(cm->allreduce(h, scal + 1, 1, COMM_MIN));
   HIPCHK(h, hipMemcpyAsync(&dinfo, scal + 1, sizeof(double), hipMemcpyDeviceToHost, st));
-  HIPCHK(h, hipStreamSynchronize(st));
-  HIPCHK(h, hipGetLastError());
-  LAUNCHCHK(h);
-  collect_phases(h);
+  if ((rc = finish_call(h))) return rc;
   if (dinfo < 0) {  // same decision on every rank: dinfo is all-reduced, the environment is the launch's
     if (!retried && !getenv("GPX_CHAIN_FLAG")) {
       h->flag_ok = 0;  // this handle hands over by hipEvents from now on; the fit runs once more (same kernels, same bits)
       h->flag_retries += 1;
-      h->phases.clear();
-      h->ev_used = 0;
       return shard_fit<T>(h, X, y, N, d, k, lengthscale, n_ls, sf2, sn2, jitter, mem_kind, info, true, Xq, Mquery);
     }
     return fail(h, GPX_E_HIP, "a stream parked on a device flag timed out on some rank (kernels serialised across streams? set GPX_CHAIN_FLAG=0)");
@@ -1038,12 +1028,12 @@ int shard_gather_slices(gpx_handle* h, int64_t M, int64_t Mc, int64_t Mr, bool w
   const size_t slot = (size_t)Mc * (k + 1);  // elements per rank: mean (Mc x k) then var (Mc)
   gpx_timings& tm = h->tm;
   int rc;
-  if ((rc = ensure(h, h->GatherS, slot * sizeof(T)))) return rc;
-  if ((rc = ensure(h, h->GatherR, slot * 8 * P))) return rc;
-  if ((rc = ensure(h, h->outM, (size_t)M * k * sizeof(T)))) return rc;
-  if ((rc = ensure(h, h->outV, (size_t)M * sizeof(T)))) return rc;
-  T* S = (T*)h->GatherS.p;
-  T* R = (T*)h->GatherR.p;
+  if ((rc = ensure(h, h->scr.GatherS, slot * sizeof(T)))) return rc;
+  if ((rc = ensure(h, h->scr.GatherR, slot * 8 * P))) return rc;
+  if ((rc = ensure(h, h->scr.outM, (size_t)M * k * sizeof(T)))) return rc;
+  if ((rc = ensure(h, h->scr.outV, (size_t)M * sizeof(T)))) return rc;
+  T* S = (T*)h->scr.GatherS.p;
+  T* R = (T*)h->scr.GatherR.p;
   hipStream_t st = h->st;
   HIPCHK(h, hipMemsetAsync(S, 0, slot * sizeof(T), st));
   if (Mr > 0) {
@@ -1058,16 +1048,16 @@ int shard_gather_slices(gpx_handle* h, int64_t M, int64_t Mc, int64_t Mr, bool w
   for (int q = 0; q < P; ++q) {
     const int64_t q0 = std::min<int64_t>(M, (int64_t)q * Mc), q1 = std::min<int64_t>(M, (int64_t)(q + 1) * Mc);
     if (q1 <= q0) continue;
-    HIPCHK(h, hipMemcpyAsync((T*)h->outM.p + q0 * k, R + (size_t)q * slot, (size_t)(q1 - q0) * k * sizeof(T),
+    HIPCHK(h, hipMemcpyAsync((T*)h->scr.outM.p + q0 * k, R + (size_t)q * slot, (size_t)(q1 - q0) * k * sizeof(T),
                              hipMemcpyDeviceToDevice, st));
     if (want_var)
-      HIPCHK(h, hipMemcpyAsync((T*)h->outV.p + q0, R + (size_t)q * slot + (size_t)Mc * k,
+      HIPCHK(h, hipMemcpyAsync((T*)h->scr.outV.p + q0, R + (size_t)q * slot + (size_t)Mc * k,
                                (size_t)(q1 - q0) * sizeof(T), hipMemcpyDeviceToDevice, st));
   }
   PhaseScope ps(h, &tm.d2h);
   if (!h->discard_out) {  // a group's ranks > 0 hold the same result; rank 0 delivers it
-    if ((rc = copy_out(h, mean, h->outM.p, (size_t)M * k * sizeof(T), mem_kind))) return rc;
-    if (want_var && (rc = copy_out(h, var, h->outV.p, (size_t)M * sizeof(T), mem_kind))) return rc;
+    if ((rc = copy_out(h, mean, h->scr.outM.p, (size_t)M * k * sizeof(T), mem_kind))) return rc;
+    if (want_var && (rc = copy_out(h, var, h->scr.outV.p, (size_t)M * sizeof(T), mem_kind))) return rc;
   }
   return GPX_OK;
 }
@@ -1079,45 +1069,24 @@ template <typename T>
 int shard_fused_tail(gpx_handle* h, int64_t M, void* mean, void* var, int32_t mem_kind) {
   Comm* cm = h->comm;
   const int P = cm->world, r = cm->rank;
-  const int64_t Npad = h->Npad, ld = h->ld;
   const int64_t Mc = round_up((M + P - 1) / P, TILE);
   const int64_t m0 = std::min<int64_t>(M, (int64_t)r * Mc), m1 = std::min<int64_t>(M, (int64_t)(r + 1) * Mc);
   const int64_t Mr = m1 - m0, Mq = round_up(Mr, TILE), ldm = Mq + ld_skew<T>();
   if (Mq != h->fq_rows) return fail(h, GPX_E_ARG, "gpx_fit_predict: the factorisation carried other query rows");
-  gpx_timings& tm = h->tm;
-  tm.kstar = tm.mean = tm.trsm = tm.var = tm.d2h = tm.predict_total = 0;
-  hipStream_t st = h->st;
+  reset_predict_clocks(h->tm);
   int rc;
   if ((rc = ensure(h, h->meanout, (size_t)std::max<int64_t>(Mr, 1) * h->k * sizeof(T)))) return rc;
   if ((rc = ensure(h, h->var, (size_t)std::max<int64_t>(Mq, TILE) * sizeof(T)))) return rc;
   {
-    PhaseScope total(h, &tm.predict_total);
+    PhaseScope total(h, &h->tm.predict_total);
     if (Mr > 0) {
-      const int ksplit = splitk_splits(Npad);
-      if ((rc = ensure(h, h->MT, (size_t)RHS_ROWS * ldm * sizeof(T)))) return rc;
-      if (ksplit > 1 && (rc = ensure(h, h->MTpart, (size_t)ksplit * RHS_ROWS * ldm * sizeof(T)))) return rc;
-      const T* dVT = (const T*)h->K.p + h->nloc * ld;
-      {
-        PhaseScope ps(h, &tm.mean);
-        if (ksplit > 1)
-          launch_gemm_nt_splitk<T>((T*)h->MT.p, ldm, (const T*)h->zT, ld, dVT, ld, RHS_ROWS, Mq, Npad, ksplit,
-                                   (T*)h->MTpart.p, ldm, st);
-        else
-          launch_gemm_nt<T>(64, (T*)h->MT.p, ldm, (const T*)h->zT, ld, dVT, ld, RHS_ROWS, Mq, Npad, 0, 1, st);
-        launch_unpack_rhs<T>((const T*)h->MT.p, ldm, Mr, h->k, 1.0, (T*)h->meanout.p, st);
-      }
-      if (var) {
-        PhaseScope ps(h, &tm.var);
-        launch_var_rows<T>(dVT, ld, Mr, Npad, h->sf2, (T*)h->var.p, st);
-      }
+      if ((rc = ensure(h, h->scr.MT, (size_t)RHS_ROWS * ldm * sizeof(T)))) return rc;
+      if ((rc = ensure_mean_partials<T>(h, h->scr.MTpart, ldm))) return rc;
+      bordered_mean_var<T>(h, (const T*)h->K.p + h->nloc * h->ld, Mr, Mq, ldm, var != nullptr);
     }
     if ((rc = shard_gather_slices<T>(h, M, Mc, Mr, var != nullptr, mean, var, mem_kind))) return rc;
   }
-  HIPCHK(h, hipStreamSynchronize(st));
-  HIPCHK(h, hipGetLastError());
-  LAUNCHCHK(h);
-  collect_phases(h);
-  return GPX_OK;
+  return finish_call(h);
 }
 
 // Replicated-factor predict: rank r takes query points [r*Mc, (r+1)*Mc) through the
@@ -1130,21 +1099,15 @@ int shard_predict_repl(gpx_handle* h, const void* Xq, int64_t M, void* mean, voi
   const int64_t Mc = round_up((M + P - 1) / P, TILE);
   const int64_t m0 = std::min<int64_t>(M, (int64_t)r * Mc), m1 = std::min<int64_t>(M, (int64_t)(r + 1) * Mc);
   const int64_t Mr = m1 - m0;
-  gpx_timings& tm = h->tm;
-  tm.kstar = tm.mean = tm.trsm = tm.var = tm.d2h = tm.predict_total = 0;
+  reset_predict_clocks(h->tm);
   int rc;
-  hipStream_t st = h->st;
   {
-    PhaseScope total(h, &tm.predict_total);
+    PhaseScope total(h, &h->tm.predict_total);
     if ((rc = predict_core<T>(h, (const char*)Xq + (size_t)m0 * d * sizeof(T), Mr, var != nullptr, mem_kind)))
       return rc;
     if ((rc = shard_gather_slices<T>(h, M, Mc, Mr, var != nullptr, mean, var, mem_kind))) return rc;
   }
-  HIPCHK(h, hipStreamSynchronize(st));
-  HIPCHK(h, hipGetLastError());
-  LAUNCHCHK(h);
-  collect_phases(h);
-  return GPX_OK;
+  return finish_call(h);
 }
 
 // XT (mp rows x own columns, ldv) <- XT L^-T over the block-cyclic column layout (local column block lb =
@@ -1227,12 +1190,12 @@ int shard_lml_grad_dist(gpx_handle* h, double* lml, double* grad) {
   tm.grad_trtri = tm.grad_trace = tm.grad_total = 0;
   const int64_t s1n = kinv_trace_slots(Npad), s2n = alpha_quad_slots(Npad);
   int rc;
-  if ((rc = ensure(h, h->ZTloc, (size_t)Npad * ldv * 8))) return rc;
-  if ((rc = ensure(h, h->Sv, (size_t)2 * MB * nb * 8))) return rc;
-  if ((rc = ensure(h, h->gpart, (size_t)((s1n + s2n) * ntheta + 2 * ntheta + 1) * 8))) return rc;
-  double* Z = (double*)h->ZTloc.p;
-  double* SvB[2] = {(double*)h->Sv.p, (double*)h->Sv.p + (size_t)MB * nb};
-  double* part1 = (double*)h->gpart.p;
+  if ((rc = ensure(h, h->scr.ZTloc, (size_t)Npad * ldv * 8))) return rc;
+  if ((rc = ensure(h, h->scr.Sv, (size_t)2 * MB * nb * 8))) return rc;
+  if ((rc = ensure(h, h->scr.gpart, (size_t)((s1n + s2n) * ntheta + 2 * ntheta + 1) * 8))) return rc;
+  double* Z = (double*)h->scr.ZTloc.p;
+  double* SvB[2] = {(double*)h->scr.Sv.p, (double*)h->scr.Sv.p + (size_t)MB * nb};
+  double* part1 = (double*)h->scr.gpart.p;
   double* part2 = part1 + s1n * ntheta;
   double* outv = part2 + s2n * ntheta;
   hipStream_t st = h->st;
@@ -1266,10 +1229,7 @@ int shard_lml_grad_dist(gpx_handle* h, double* lml, double* grad) {
   }
   double host[2 * 34 + 1];
   HIPCHK(h, hipMemcpyAsync(host, outv, (size_t)(2 * ntheta + 1) * 8, hipMemcpyDeviceToHost, st));
-  HIPCHK(h, hipStreamSynchronize(st));
-  HIPCHK(h, hipGetLastError());
-  LAUNCHCHK(h);
-  collect_phases(h);
+  if ((rc = finish_call(h))) return rc;
   for (int t = 0; t < ntheta; ++t) grad[t] = 0.5 * (host[ntheta + t] - (double)k * host[t]);
   *lml = -0.5 * host[2 * ntheta] - 0.5 * (double)k * h->logdet -
          0.5 * (double)N * (double)k * 1.8378770664093454835606594728112;  // log(2 pi)
@@ -1292,26 +1252,23 @@ int shard_predict(gpx_handle* h, const void* Xq, int64_t M, void* mean, void* va
   // loop — so the batch size depends on nothing but M and GPX_PRED_BATCH.
   const int64_t MB = pred_batch_rows(h, Mpad, (size_t)ldv * sizeof(T), false);
   gpx_timings& tm = h->tm;
-  tm.kstar = tm.mean = tm.trsm = tm.var = tm.d2h = tm.predict_total = 0;
+  reset_predict_clocks(tm);
   int rc;
-  if ((rc = ensure(h, h->Q, (size_t)M * d * sizeof(T)))) return rc;
-  if ((rc = ensure(h, h->Qs, (size_t)Mpad * d * sizeof(T)))) return rc;
-  if ((rc = ensure(h, h->VT, (size_t)MB * ldv * sizeof(T)))) return rc;
-  if ((rc = ensure(h, h->MT, (size_t)RHS_ROWS * ldm * sizeof(T)))) return rc;
+  if ((rc = ensure_queries<T>(h, M))) return rc;
+  if ((rc = ensure(h, h->scr.VT, (size_t)MB * ldv * sizeof(T)))) return rc;
+  if ((rc = ensure(h, h->scr.MT, (size_t)RHS_ROWS * ldm * sizeof(T)))) return rc;
   if ((rc = ensure(h, h->meanout, (size_t)M * k * sizeof(T)))) return rc;
   if ((rc = ensure(h, h->var, (size_t)Mpad * sizeof(T)))) return rc;
-  if ((rc = ensure(h, h->Sv, (size_t)2 * MB * nb * sizeof(T)))) return rc;
-  T* VT = (T*)h->VT.p;
-  T* SvB[2] = {(T*)h->Sv.p, (T*)h->Sv.p + (size_t)MB * nb};
+  if ((rc = ensure(h, h->scr.Sv, (size_t)2 * MB * nb * sizeof(T)))) return rc;
+  T* VT = (T*)h->scr.VT.p;
+  T* SvB[2] = {(T*)h->scr.Sv.p, (T*)h->scr.Sv.p + (size_t)MB * nb};
   const T* Xs = (const T*)h->Xs.p;
   hipStream_t st = h->st;
   {
     PhaseScope total(h, &tm.predict_total);
     {
       PhaseScope ps(h, &tm.kstar);
-      if ((rc = copy_in(h, h->Q.p, Xq, (size_t)M * d * sizeof(T), mem_kind))) return rc;
-      launch_scale_points((const T*)h->Q.p, M, Mpad, d, (const double*)h->ls.p, h->n_ls,
-                          (T*)h->Qs.p, st);
+      if ((rc = upload_queries<T>(h, Xq, M, mem_kind))) return rc;
     }
     for (int64_t m0 = 0; m0 < Mpad; m0 += MB) {
       const int64_t mp = std::min(MB, Mpad - m0), mv = std::min<int64_t>(mp, M - m0);
@@ -1320,17 +1277,17 @@ int shard_predict(gpx_handle* h, const void* Xq, int64_t M, void* mean, void* va
         for (int64_t lb = 0; lb < nlb; ++lb) {
           const int64_t g = sh.global(sh.r, lb);
           const int64_t nvalid = std::max<int64_t>(0, std::min<int64_t>(nb, N - g * nb));
-          launch_kbuild_cross(h->cfg.kernel, (const T*)h->Qs.p + m0 * d, mv, mp, Xs + g * nb * d, nvalid,
+          launch_kbuild_cross(h->cfg.kernel, (const T*)h->scr.Qs.p + m0 * d, mv, mp, Xs + g * nb * d, nvalid,
                               nb, d, h->sf2, VT + lb * nb, ldv, st);
         }
       }
       {  // partial means of this batch: alpha^T (own columns) * K*^T (own columns)
         PhaseScope ps(h, &tm.mean);
         if (nloc > 0)
-          launch_gemm_nt(64, (T*)h->MT.p + m0, ldm, (const T*)h->YTloc.p, ldy, VT, ldv, RHS_ROWS, mp,
+          launch_gemm_nt(64, (T*)h->scr.MT.p + m0, ldm, (const T*)h->YTloc.p, ldy, VT, ldv, RHS_ROWS, mp,
                          nloc, 0, 1, st);
         else
-          HIPCHK(h, hipMemset2DAsync((T*)h->MT.p + m0, (size_t)ldm * sizeof(T), 0, (size_t)mp * sizeof(T), RHS_ROWS, st));
+          HIPCHK(h, hipMemset2DAsync((T*)h->scr.MT.p + m0, (size_t)ldm * sizeof(T), 0, (size_t)mp * sizeof(T), RHS_ROWS, st));
       }
       if (var) {
         // Forward substitution V^T <- V^T L^-T over the block-cyclic columns with one-block
@@ -1350,9 +1307,9 @@ int shard_predict(gpx_handle* h, const void* Xq, int64_t M, void* mean, void* va
       PhaseScope ps(h, &tm.mean);
       {
         PhaseScope pc(h, &tm.comm);
-        COMMCHK(cm->allreduce(h, (T*)h->MT.p, (size_t)RHS_ROWS * ldm, COMM_SUM));
+        COMMCHK(cm->allreduce(h, (T*)h->scr.MT.p, (size_t)RHS_ROWS * ldm, COMM_SUM));
       }
-      launch_unpack_rhs((const T*)h->MT.p, ldm, M, k, 1.0, (T*)h->meanout.p, st);
+      launch_unpack_rhs((const T*)h->scr.MT.p, ldm, M, k, 1.0, (T*)h->meanout.p, st);
     }
     if (var) {
       PhaseScope ps(h, &tm.var);
@@ -1362,17 +1319,9 @@ int shard_predict(gpx_handle* h, const void* Xq, int64_t M, void* mean, void* va
       }
       launch_add_scalar((T*)h->var.p, M, h->sf2, st);
     }
-    if (!h->discard_out) {
-      PhaseScope ps(h, &tm.d2h);
-      if ((rc = copy_out(h, mean, h->meanout.p, (size_t)M * k * sizeof(T), mem_kind))) return rc;
-      if (var && (rc = copy_out(h, var, h->var.p, (size_t)M * sizeof(T), mem_kind))) return rc;
-    }
+    if (!h->discard_out && (rc = deliver_mean_var<T>(h, mean, var, M, mem_kind))) return rc;
   }
-  HIPCHK(h, hipStreamSynchronize(st));
-  HIPCHK(h, hipGetLastError());
-  LAUNCHCHK(h);
-  collect_phases(h);
-  return GPX_OK;
+  return finish_call(h);
 }
 
 void destroy_comm(gpx_handle* h) {

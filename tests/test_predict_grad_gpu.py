@@ -285,3 +285,32 @@ def test_path_velocity_matches_finite_differences_of_predict():
     finally:
         for mm in models.values():
             mm.close()
+
+
+def test_close_frees_the_gradient_buffers():
+    """``close()`` returns the scratch of ``predict_gradient`` to the device.  The V buffer of this call holds three row
+    blocks (value and two partials) of M = 2048 rows of N + skew fp64 columns: 3 * 2048 * (4096 + 16) * 8 bytes, about
+    200 MB.  Free device memory after the close must be within half of that (100 MB) of what it was before the model
+    existed: the bound comes from the buffer's size, it is not a measurement.
+
+    One model is fitted and closed before the first reading: the first use of the library in a process costs device
+    memory that no handle owns (code objects, queues, kernel scratch: 172 MB measured, the same with and without the
+    leak, constant over any number of models), and a test that runs alone would count it."""
+    import torch
+
+    N, d, M = 4096, 2, 2048
+    X, y, Xs = synthetic_problem(N, d, M, seed=11)
+    with GP("matern52", 0.3, 1.5, 1e-2, jitter=0.0, device=0) as warm:
+        warm.fit(X, y).predict(Xs)
+    torch.cuda.synchronize()
+    free_before = torch.cuda.mem_get_info(0)[0]
+    gp = GP("matern52", 0.3, 1.5, 1e-2, jitter=0.0, device=0)
+    try:
+        gp.fit(X, y).predict_gradient(Xs, return_var=True, with_value=True)
+    finally:
+        gp.close()
+    torch.cuda.synchronize()
+    free_after = torch.cuda.mem_get_info(0)[0]
+    gv_bytes = 3 * M * (N + 16) * 8
+    print(f"free before {free_before}  after close {free_after}  not returned {free_before - free_after}  GV {gv_bytes}")
+    assert free_before - free_after <= gv_bytes // 2
