@@ -11,7 +11,9 @@
 // Data layout in HBM (element type T = double, or float for the fp32 / mixed handles; row-major):
 //   K / L   [Npad+64][ld]  ld = Npad + one 128-byte line (skew against power-of-two strides; rows
 //                          128-byte aligned); only the lower triangle is referenced; rows/cols >= N
-//                          are identity; rows [Npad, Npad+64) carry the right-hand sides ("bordered")
+//                          are identity; rows [Npad, Npad+64) carry the right-hand sides ("bordered").
+//                          After gpx_reserve / a gpx_append that outgrew the buffer: ld = capacity rows + that line,
+//                          and Npad grows inside the buffer (append_room, append_restart)
 //   Winv    [Npad/64][64][64]   inverses of the 64x64 diagonal blocks of L
 //   Wblk    [Npad/nb][nb][nb]   explicit inverses of the nb x nb diagonal blocks (panel / block solves
 //                               are dense products with them), built beside the factorisation
@@ -150,6 +152,7 @@ struct gpx_handle {
   int64_t fq_rows = 0;  // gpx_fit_predict on a shard: padded rows of this rank's slice of the query points (bordered rows of its K buffer)
   int flag_ok = -1;
   int flag_retries = 0;  // fits of this handle that were run again with hipEvents after a parked stream timed out
+  int64_t reserve = 0;   // gpx_reserve: points the layout of the next fit / append leaves room for (0: what the fit needs)
   // event pool
   std::vector<hipEvent_t> ev_pool;
   size_t ev_used = 0;
@@ -1149,7 +1152,10 @@ int fit_impl(gpx_handle* h, const void* X, const void* y, int64_t N, int32_t d, 
              int32_t mem_kind, int64_t* info, const void* Xq = nullptr, int64_t M = 0, bool retried = false) {
   const int64_t Npad = round_up(N, TILE);
   const int64_t Mpad = Xq ? round_up(M, TILE) : 0;
-  const int64_t ld = Npad + ld_skew<T>();
+  // rows the buffers are laid out for: the fit's own, or what gpx_reserve asked for (appends then happen in place)
+  const int64_t cap = h->reserve > 0 ? std::max(Npad, round_up(h->reserve, TILE)) : Npad;
+  const int64_t capN = h->reserve > 0 ? cap : N;
+  const int64_t ld = cap + ld_skew<T>();
   if (h->cfg.block == 0) {  // the library's choice; predict's block solves use the fit's block inverses: same width
     h->nb = auto_panel_width(Npad);
     if (!h->nb_pred_env) h->nb_pred = h->nb;
@@ -1166,18 +1172,18 @@ int fit_impl(gpx_handle* h, const void* X, const void* y, int64_t N, int32_t d, 
 
   int rc;
   if ((rc = flag_handover_probe(h))) return rc;  // once per handle: device flags or hipEvents between the streams
-  if ((rc = ensure(h, h->X, (size_t)N * d * sizeof(T)))) return rc;
-  if ((rc = ensure(h, h->Y, (size_t)N * k * sizeof(T)))) return rc;
-  if ((rc = ensure(h, h->Xs, (size_t)Npad * d * sizeof(T)))) return rc;
+  if ((rc = ensure(h, h->X, (size_t)capN * d * sizeof(T)))) return rc;
+  if ((rc = ensure(h, h->Y, (size_t)capN * k * sizeof(T)))) return rc;
+  if ((rc = ensure(h, h->Xs, (size_t)cap * d * sizeof(T)))) return rc;
   if ((rc = ensure(h, h->ls, MAX_D * 8))) return rc;
   const int64_t NX = RHS_ROWS + Mpad;  // bordered rows: [K* rows of a fused predict] + the right-hand sides
   if (Xq && (rc = ensure_queries<T>(h, M))) return rc;
-  if ((rc = ensure(h, h->K, (size_t)(Npad + NX) * ld * sizeof(T)))) return rc;
-  if ((rc = ensure(h, h->Winv, (size_t)(Npad / KB) * KB * KB * sizeof(T)))) return rc;
-  if ((rc = ensure(h, h->P, (size_t)2 * (Npad + NX) * ldp * sizeof(T)))) return rc;
+  if ((rc = ensure(h, h->K, (size_t)(cap + NX) * ld * sizeof(T)))) return rc;
+  if ((rc = ensure(h, h->Winv, (size_t)(cap / KB) * KB * KB * sizeof(T)))) return rc;
+  if ((rc = ensure(h, h->P, (size_t)2 * (cap + NX) * ldp * sizeof(T)))) return rc;
   if ((rc = ensure(h, h->scalars, 64))) return rc;
   if ((rc = ensure(h, h->info, 64))) return rc;
-  const int64_t nblk = (Npad + h->nb - 1) / h->nb;
+  const int64_t nblk = (cap + h->nb - 1) / h->nb;
   const int64_t ldu = h->nb + ld_skew<T>();
   if ((rc = ensure(h, h->Wblk, (size_t)nblk * h->nb * h->nb * sizeof(T)))) return rc;
   if ((rc = ensure(h, h->Ublk, (size_t)h->nb * ldu * sizeof(T)))) return rc;
@@ -1257,6 +1263,209 @@ int fit_impl(gpx_handle* h, const void* X, const void* y, int64_t N, int32_t d, 
   *info = (hinfo == INT_MAX) ? 0 : (int64_t)hinfo;
   h->fitted = (*info == 0);
   if (h->fitted) h->nbw = h->nb;
+  return GPX_OK;
+}
+
+// ---- gpx_append: more observations without a new factorisation of the old ones -------------------------
+// Rows [0, R0) of L, R0 = the last panel boundary inside the old data, do not change when rows are added below them, and
+// neither do columns [0, R0) of z^T.  An append is the right-looking factorisation restarted at R0: the left part of the
+// new rows (one forward solve against the R0 columns), the trailing square [R0, Npad')^2 rebuilt and reduced by the Schur
+// term of those columns in one product, then chol_enqueue on it with the right-hand sides as bordered rows.
+
+// Room for `Nnew` points.  Within the layout's capacity nothing of the factor moves; beyond it the factor's lower triangle
+// and columns [0, R0) of z^T move into a buffer with room for one more panel width of points (or what gpx_reserve asked
+// for), and the point, block-inverse and panel buffers grow with it.  Every allocation happens before anything is touched:
+// on GPX_E_NOMEM the fit is as it was.
+template <typename T>
+int append_room(gpx_handle* h, int64_t Nnew) {
+  const int64_t skew = ld_skew<T>(), cap0 = h->ld - skew, NpadNew = round_up(Nnew, TILE), want = round_up(h->reserve, TILE);
+  const int64_t N = h->N, Npad = h->Npad, nb = h->nb, d = h->d, k = h->k;
+  const bool relayout = NpadNew > cap0 || want > cap0;
+  const int64_t cap = !relayout ? cap0 : NpadNew <= want ? want : round_up(Nnew + nb, TILE);
+  const int64_t ld = cap + skew, R0 = N / nb * nb;
+  struct Grow {
+    DevBuf* buf;
+    size_t need, keep;
+    DevBuf fresh;
+  } g[] = {{&h->X, (size_t)cap * d * sizeof(T), (size_t)N * d * sizeof(T), {}},
+           {&h->Y, (size_t)cap * k * sizeof(T), (size_t)N * k * sizeof(T), {}},
+           {&h->Xs, (size_t)cap * d * sizeof(T), (size_t)Npad * d * sizeof(T), {}},
+           {&h->Winv, (size_t)(cap / KB) * KB * KB * sizeof(T), (size_t)(Npad / KB) * KB * KB * sizeof(T), {}},
+           {&h->Wblk, (size_t)((cap + nb - 1) / nb) * nb * nb * sizeof(T), (size_t)(R0 / nb) * nb * nb * sizeof(T), {}}};
+  const size_t kbytes = (size_t)(cap + RHS_ROWS) * ld * sizeof(T);
+  const size_t pbytes = (size_t)2 * (cap + RHS_ROWS) * h->ldp * sizeof(T);
+  const bool newK = relayout || h->K.cap < kbytes, newP = h->P.cap < pbytes;
+  double need = (newK ? (double)kbytes : 0.0) + (newP ? (double)pbytes : 0.0);
+  for (Grow& x : g)
+    if (x.buf->cap < x.need) need += (double)x.need;
+  if (need == 0.0) return GPX_OK;
+  size_t freeb = 0, totalb = 0;
+  HIPCHK(h, hipMemGetInfo(&freeb, &totalb));
+  const double avail = (double)freeb + (newP ? (double)h->P.cap : 0.0);  // the panel buffers are scratch: freed first
+  char msg[256];
+  snprintf(msg, sizeof msg, "gpx_append: %.0f bytes of device memory needed for %lld points (beside the fit), %.0f available",
+           need, (long long)Nnew, avail);
+  if (need > avail) return fail(h, GPX_E_NOMEM, msg);
+  DevBuf Knew;
+  if (newP) h->P = DevBuf();
+  bool ok = !newK || hipMalloc(&Knew.p, kbytes) == hipSuccess;
+  if (ok && newK) Knew.cap = kbytes;
+  for (Grow& x : g)
+    if (ok && x.buf->cap < x.need) {
+      ok = hipMalloc(&x.fresh.p, x.need) == hipSuccess;
+      if (ok) x.fresh.cap = x.need;
+    }
+  if (ok && newP) {
+    ok = hipMalloc(&h->P.p, pbytes) == hipSuccess;
+    if (ok) h->P.cap = pbytes;
+  }
+  if (!ok) {
+    (void)hipGetLastError();
+    return fail(h, GPX_E_NOMEM, msg);  // (the fresh buffers free themselves; the fit is untouched)
+  }
+  for (Grow& x : g)
+    if (x.fresh.p && x.keep) HIPCHK(h, hipMemcpyAsync(x.fresh.p, x.buf->p, x.keep, hipMemcpyDeviceToDevice, h->st));
+  T* zT = (T*)h->zT;
+  if (newK) {  // the factor's lower triangle; z^T keeps its row (append_restart moves it when Npad changes)
+    T* dst = (T*)Knew.p;
+    launch_copy_lower<T>(dst, ld, (const T*)h->K.p, h->ld, Npad, h->st);
+    zT = dst + Npad * ld;
+    HIPCHK(h, hipMemsetAsync(zT, 0, (size_t)RHS_ROWS * ld * sizeof(T), h->st));
+    launch_copy2d<T>(zT, ld, (const T*)h->zT, h->ld, RHS_ROWS, R0, h->st);
+  }
+  HIPCHK(h, hipStreamSynchronize(h->st));
+  for (Grow& x : g)
+    if (x.fresh.p) *x.buf = std::move(x.fresh);  // the old allocation leaves with x.fresh
+  if (newK) {
+    h->K = std::move(Knew);
+    h->ld = ld;
+    h->Lfac = h->K.p;
+    h->zT = zT;
+  }
+  return GPX_OK;
+}
+
+// The restart itself, from what is resident: points [0, Nnew) in h->X / h->Y (Xnew != null: the last m of them are copied
+// in first), the factor of the first Nold.  Nnew == Nold rebuilds the fit of Nold points from its first R0 columns — what
+// a failed append runs to hand the previous model back.  *hinfo: the device's pivot word (INT_MAX: positive definite).
+template <typename T>
+int append_restart(gpx_handle* h, int64_t Nold, int64_t Nnew, const void* Xnew, const void* ynew, int32_t mem_kind,
+                   int* hinfo) {
+  const int64_t ld = h->ld, ldp = h->ldp, nb = h->nb;
+  const int d = h->d, k = h->k;
+  const int64_t R0 = Nold / nb * nb, R1 = Nold / TILE * TILE;  // first column / first row that is computed again
+  const int64_t Npad = round_up(Nnew, TILE), np = Npad - R0, rows = Npad - R1, m = Nnew - Nold;
+  const bool profile = (h->cfg.flags & GPX_FLAG_PROFILE) != 0;
+  gpx_timings& tm = h->tm;
+  T* dK = (T*)h->K.p;
+  T* Xs = (T*)h->Xs.p;
+  T* Winv = (T*)h->Winv.p;
+  T* dYT = dK + Npad * ld;
+  int* dInfo = (int*)h->info.p;
+  int rc;
+  SolveWork<T> sw;
+  if (R0 > 0 && (rc = dense_solve_work<T>(h, h->scr.Tsol, rows, &sw))) return rc;
+  InvWork<T> iw;
+  iw.W = (T*)h->Wblk.p + (R0 / nb) * nb * nb;
+  iw.U = (T*)h->Ublk.p;
+  iw.ldu = nb + ld_skew<T>();
+  iw.nbw = (int)nb;
+  iw.aux = h->st3;
+  {
+    PhaseScope total(h, &tm.fit_total);
+    {
+      PhaseScope ps(h, &tm.h2d);
+      if (m > 0 && Xnew) {
+        if ((rc = copy_in(h, (T*)h->X.p + Nold * d, Xnew, (size_t)m * d * sizeof(T), mem_kind))) return rc;
+        if ((rc = copy_in(h, (T*)h->Y.p + Nold * k, ynew, (size_t)m * k * sizeof(T), mem_kind))) return rc;
+      }
+      const int init = INT_MAX;
+      HIPCHK(h, hipMemcpyAsync(dInfo, &init, sizeof(int), hipMemcpyHostToDevice, h->st));
+    }
+    {
+      PhaseScope ps(h, &tm.kbuild);
+      if (dYT != (T*)h->zT) {  // Npad changes: columns [0, R0) of z^T to their new rows before those rows are built
+        HIPCHK(h, hipMemsetAsync(dYT, 0, (size_t)RHS_ROWS * ld * sizeof(T), h->st));
+        launch_copy2d<T>(dYT, ld, (const T*)h->zT, ld, RHS_ROWS, R0, h->st);
+        h->zT = dYT;
+      }
+      launch_scale_points<T>((const T*)h->X.p + R1 * d, Nnew - R1, rows, d, (const double*)h->ls.p, h->n_ls, Xs + R1 * d,
+                             h->st);
+      if (R0 > 0)  // left part of the 128-row tiles that hold a new point: K(x_i, x_j), j < R0
+        launch_kbuild_cross<T>(h->cfg.kernel, Xs + R1 * d, Nnew - R1, rows, Xs, R0, R0, d, h->sf2, dK + R1 * ld, ld, h->st);
+      launch_kbuild_sym<T>(h->cfg.kernel, Xs + R0 * d, Nnew - R0, np, d, h->sf2, h->sn2 + h->jitter, dK + R0 * ld + R0, ld,
+                           h->st);
+    }
+    {
+      PhaseScope ps(h, &tm.chol);
+      if (R0 > 0 && (rc = solve_fwd_enqueue<T>(h, dK + R1 * ld, rows, dK, ld, R0, h->nb_pred, Winv, &sw))) return rc;
+      launch_pack_rhs<T>((const T*)h->Y.p + R0 * k, Nnew - R0, k, dYT + R0, ld, np, RHS_ROWS, h->st);
+      if (R0 > 0) {  // Schur term of the R0 columns already factorised: the square, then the bordered rows
+        launch_gemm_nt<T>(128, dK + R0 * ld + R0, ld, dK + R0 * ld, ld, dK + R0 * ld, ld, np, np, R0, 1, 0, h->st);
+        launch_gemm_nt<T>(64, dYT + R0, ld, dYT, ld, dK + R0 * ld, ld, RHS_ROWS, np, R0, 0, 0, h->st);
+      }
+      if ((rc = chol_enqueue<T>(h, dK + R0 * ld + R0, ld, np, (int)nb, Winv + (R0 / KB) * (KB * KB), (T*)h->P.p,
+                                (T*)h->P.p + (np + RHS_ROWS) * ldp, ldp, dInfo, R0, profile, RHS_ROWS, &iw, 0)))
+        return rc;
+    }
+    {
+      PhaseScope ps(h, &tm.logdet);
+      launch_logdet<T>(dK, ld, Npad, (double*)h->scalars.p, h->st);
+    }
+  }
+  HIPCHK(h, hipMemcpyAsync(hinfo, dInfo, sizeof(int), hipMemcpyDeviceToHost, h->st));
+  HIPCHK(h, hipMemcpyAsync(&h->logdet, h->scalars.p, sizeof(double), hipMemcpyDeviceToHost, h->st));
+  return finish_call(h);
+}
+
+template <typename T>
+int append_impl(gpx_handle* h, const void* Xnew, const void* ynew, int64_t m, int32_t mem_kind, int64_t* info) {
+  const int64_t Nold = h->N, Nnew = Nold + m;
+  gpx_timings& tm = h->tm;
+  tm.h2d = tm.kbuild = tm.chol = tm.solve = tm.logdet = tm.fit_total = 0;
+  tm.chol_diag = tm.chol_trsm = tm.chol_strip = tm.chol_syrk = tm.syrk_flops = tm.comm = 0;
+  tm.syrk_launches = 0;
+  tm.kbuild_bytes = (double)sizeof(T) * ((double)m * (double)(Nold + Nnew + 1) / 2.0 + (double)m * h->d);
+  int rc;
+  if ((rc = flag_handover_probe(h))) return rc;
+  if ((rc = append_room<T>(h, Nnew))) return rc;  // nothing of the fit has been touched yet
+  {  // ... nor by the block-solve buffers of the new rows' forward solve
+    SolveWork<T> sw;
+    if ((rc = dense_solve_work<T>(h, h->scr.Tsol, round_up(Nnew, TILE) - Nold / TILE * TILE, &sw))) return rc;
+  }
+  h->fitted = false;  // until the restart (or the restart back) has gone through
+  h->alphaT = nullptr;
+  h->alpha_ready = false;
+  // the restart; a parked stream that timed out: once more with hipEvents, as fit_impl does (same kernels, same bits)
+  auto restart = [&](int64_t n1, const void* Xa, const void* ya, int* hinfo) -> int {
+    for (int attempt = 0;; ++attempt) {
+      int r = append_restart<T>(h, Nold, n1, Xa, ya, mem_kind, hinfo);
+      if (r != GPX_OK || *hinfo >= 0) return r;
+      if (attempt > 0 || getenv("GPX_CHAIN_FLAG") || h->flag_ok == 0)
+        return fail(h, GPX_E_HIP,
+                    "a stream parked on a device flag timed out: kernels are being serialised across streams — "
+                    "set GPX_CHAIN_FLAG=0 (and leave GPX_FUSED_STRIP unset) to hand over by hipEvents instead");
+      h->flag_ok = 0;
+      h->flag_retries += 1;
+      if ((r = begin_call(h))) return r;
+    }
+  };
+  int hinfo = 0;
+  if ((rc = restart(Nnew, Xnew, ynew, &hinfo))) return rc;
+  *info = (hinfo == INT_MAX) ? 0 : (int64_t)hinfo;
+  int64_t Nfit = Nnew;
+  if (*info > 0) {  // not positive definite with the new points: the same restart with none of them is the previous fit
+    int back = 0;
+    if ((rc = begin_call(h))) return rc;
+    if ((rc = restart(Nold, nullptr, nullptr, &back))) return rc;
+    if (back != INT_MAX) return fail(h, GPX_E_HIP, "gpx_append: the previous fit could not be restored");
+    Nfit = Nold;
+  }
+  h->N = Nfit;
+  h->Npad = round_up(Nfit, TILE);
+  tm.handover_flags = chain_flag_enabled(h) ? 1.0 : 0.0;
+  tm.handover_retries = (double)h->flag_retries;
+  h->fitted = true;
   return GPX_OK;
 }
 
@@ -2380,6 +2589,43 @@ int gpx_predict_grad(gpx_handle* h, const void* Xq, int64_t M, void* mean, void*
   if ((rc = posterior_refused(h, "gpx_predict_grad"))) return rc;
   if ((rc = begin_call(h))) return rc;
   return BY_DTYPE(h, predict_grad_impl, h, Xq, M, mean, var, dmean, dvar, mem_kind);
+}
+GPX_CATCH_ALL
+
+int gpx_append(gpx_handle* h, const void* Xnew, const void* ynew, int64_t m, int32_t mem_kind, int64_t* info) try {
+  if (!h) return GPX_E_ARG;
+  if (!Xnew || !ynew || !info || m <= 0) return fail(h, GPX_E_ARG, "gpx_append: bad argument");
+  if (mem_kind != GPX_MEM_HOST && mem_kind != GPX_MEM_DEVICE) return fail(h, GPX_E_ARG, "gpx_append: bad mem_kind");
+  int rc;
+  if ((rc = posterior_refused(h, "gpx_append"))) return rc;
+  if (!h->fitted) return fail(h, GPX_E_ARG, "gpx_append: handle has no successful fit");
+  if (m > (int64_t)INT_MAX - 4096 - h->N) return fail(h, GPX_E_ARG, "gpx_append: N + m too large");
+  if ((rc = begin_call(h))) return rc;
+  return BY_DTYPE(h, append_impl, h, Xnew, ynew, m, mem_kind, info);
+}
+GPX_CATCH_ALL
+
+int gpx_reserve(gpx_handle* h, int64_t capacity) try {
+  if (!h) return GPX_E_ARG;
+  if (capacity < 0 || capacity > (int64_t)INT_MAX - 4096) return fail(h, GPX_E_ARG, "gpx_reserve: bad capacity");
+  int rc;
+  if ((rc = posterior_refused(h, "gpx_reserve"))) return rc;
+  if (h->fitted && capacity < h->N) return fail(h, GPX_E_ARG, "gpx_reserve: the handle already holds more points");
+  h->reserve = capacity;  // laid out by the next gpx_fit / gpx_append
+  return GPX_OK;
+}
+GPX_CATCH_ALL
+
+int gpx_factor_info(gpx_handle* h, const void** factor, int64_t* ld, int64_t* capacity) try {
+  if (!h) return GPX_E_ARG;
+  if (!h->fitted) return fail(h, GPX_E_ARG, "gpx_factor_info: handle has no successful fit");
+  int rc;
+  if ((rc = posterior_refused(h, "gpx_factor_info"))) return rc;
+  const int64_t skew = h->cfg.dtype == GPX_F32 ? ld_skew<float>() : ld_skew<double>();
+  if (factor) *factor = h->K.p;
+  if (ld) *ld = h->ld;
+  if (capacity) *capacity = h->ld - skew;
+  return GPX_OK;
 }
 GPX_CATCH_ALL
 

@@ -209,6 +209,10 @@ void launch_var_rows(const T* VT, int64_t ld, int64_t m, int64_t ncols, double s
 // dst (rows x cols, ldd) = src (rows x cols, lds), streaming; cols * sizeof(T) multiple of 16, 16-byte aligned rows
 template <typename T>
 void launch_copy2d(T* dst, int64_t ldd, const T* src, int64_t lds, int64_t rows, int64_t cols, hipStream_t st);
+// lower triangle of dst (n x n, ldd) = that of src (lds), whole 128-tiles (the diagonal tiles included); n a multiple of
+// 128, rows 16-byte aligned.  Half the traffic of launch_copy2d on the square: moving a factor into a larger buffer.
+template <typename T>
+void launch_copy_lower(T* dst, int64_t ldd, const T* src, int64_t lds, int64_t n, hipStream_t st);
 // A[i][i] = 1 for i < n
 template <typename T>
 void launch_set_diag_one_t(T* A, int64_t lda, int64_t n, hipStream_t st);

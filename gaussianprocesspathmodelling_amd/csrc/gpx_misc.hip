@@ -75,6 +75,23 @@ __global__ __launch_bounds__(256) void copy2d_kernel(T* __restrict__ dst, int64_
   }
 }
 
+// The same for the lower triangle of a square matrix, by rows of 128-tiles: tile row blockIdx.y (rows [128 y, 128 y + 128))
+// carries columns [0, 128 (y + 1)) — half the traffic of the square.  n a multiple of 128.
+template <typename T>
+__global__ __launch_bounds__(256) void copy_lower_kernel(T* __restrict__ dst, int64_t ldd, const T* __restrict__ src,
+                                                        int64_t lds, int64_t n) {
+  typedef float v4 __attribute__((ext_vector_type(4)));
+  const int64_t r0 = (int64_t)blockIdx.y * 128;
+  if (r0 >= n) return;
+  const int64_t pieces = (r0 + 128) * (int64_t)sizeof(T) / 16;  // 16-byte pieces per row of this tile row
+  const int64_t total = 128 * pieces;
+  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
+    const int64_t r = r0 + e / pieces, c = e % pieces;
+    const v4 v = __builtin_nontemporal_load(reinterpret_cast<const v4*>(src + r * lds) + c);
+    __builtin_nontemporal_store(v, reinterpret_cast<v4*>(dst + r * ldd) + c);
+  }
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void set_diag_one_kernel_t(T* A, int64_t lda, int64_t n) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -396,6 +413,13 @@ void launch_copy2d(T* dst, int64_t ldd, const T* src, int64_t lds, int64_t rows,
   hipLaunchKernelGGL(copy2d_kernel<T>, dim3((unsigned)(bx > 8192 ? 8192 : bx)), dim3(256), 0, st, dst, ldd, src, lds, rows, cols);
 }
 
+template <typename T>
+void launch_copy_lower(T* dst, int64_t ldd, const T* src, int64_t lds, int64_t n, hipStream_t st) {
+  if (n <= 0) return;
+  debug_delay(st);
+  hipLaunchKernelGGL(copy_lower_kernel<T>, dim3(16, (unsigned)(n / 128)), dim3(256), 0, st, dst, ldd, src, lds, n);
+}
+
 void launch_flag_probe_wait(const unsigned* flag, unsigned* seen, unsigned max_polls, hipStream_t st) {
   hipLaunchKernelGGL(flag_probe_wait_kernel, dim3(1), dim3(64), 0, st, flag, seen, max_polls);
 }
@@ -424,6 +448,7 @@ void launch_logdet(const T* A, int64_t lda, int64_t n, double* out, hipStream_t 
   template void launch_logdet<T>(const T*, int64_t, int64_t, double*, hipStream_t);                 \
   template void launch_set_diag_one_t<T>(T*, int64_t, int64_t, hipStream_t);                        \
   template void launch_copy2d<T>(T*, int64_t, const T*, int64_t, int64_t, int64_t, hipStream_t);           \
+  template void launch_copy_lower<T>(T*, int64_t, const T*, int64_t, int64_t, hipStream_t);                \
   template void launch_fix_diag<T>(T*, int64_t, int, int, double, hipStream_t);                           \
   template void launch_unpermute_panel<T>(const T*, int64_t, T*, int64_t, int, Deal, int, int, int64_t, hipStream_t); \
   template void launch_pack_rhs_local<T>(const T*, int64_t, int, T*, int64_t, int, int, Deal, int, int, hipStream_t); \

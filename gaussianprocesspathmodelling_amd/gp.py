@@ -252,6 +252,50 @@ class GP:
         self.log_det_ = float(ld.value)
         return self
 
+    def update(self, X_new, y_new):
+        """Append observations to the fitted model without factorising the old ones again (``gpx_append``): afterwards
+        the model is, to rounding, what ``fit`` of the concatenated data with the same hyper-parameters and the jitter
+        the fit needed would be.  Inputs as for :meth:`fit`: NumPy arrays or device tensors, both of the same kind,
+        ``y_new`` 1-D or (m, k) as fitted.  Only the rows of the new points and the last, partly filled panel of the
+        Cholesky factor are computed (include/gpx.h); :meth:`reserve` keeps the factor from being moved.  Raises
+        ``numpy.linalg.LinAlgError`` when the kernel matrix with the new points is not positive definite: the model is
+        then unchanged (the previous fit, every call valid).  float64 / float32 models on one device.  Returns ``self``."""
+        if not self._fitted:
+            raise RuntimeError("update() before a successful fit()")
+        px, kx, keepx, devx, sx = self._as_input(X_new, "X_new")
+        py, ky, keepy, devy, sy = self._as_input(y_new, "y_new")
+        if len(sx) != 2 or sx[1] != self._d:
+            raise ValueError(f"X_new must be (m, {self._d})")
+        m = sx[0]
+        if self._y1d:
+            ok = len(sy) == 1 or (len(sy) == 2 and sy[1] == 1)
+        else:
+            ok = len(sy) == 2 and sy[1] == self._k
+        if not ok or sy[0] != m:
+            raise ValueError("y_new must be (m,)" if self._y1d else f"y_new must be (m, {self._k})")
+        if kx != ky:
+            raise ValueError("X_new and y_new must both be host arrays or both be device tensors")
+        if m == 0:
+            return self
+        info = C.c_int64(0)
+        self._check(self._lib.gpx_append(self._h, px, py, m, kx, C.byref(info)))
+        if info.value != 0:
+            raise np.linalg.LinAlgError(
+                f"kernel matrix with the new points not positive definite (first bad pivot {info.value}): the model "
+                f"is unchanged (N = {self._N}); refit the concatenated data with a larger jitter")
+        self._N += m
+        self._alpha = None
+        ld = C.c_double(0.0)
+        self._check(self._lib.gpx_logdet(self._h, C.byref(ld)))
+        self.log_det_ = float(ld.value)
+        return self
+
+    def reserve(self, n):
+        """Lay the factor out for up to ``n`` points (``gpx_reserve``) at the next :meth:`fit` or :meth:`update`:
+        updates within it happen in place, nothing is reallocated or copied.  0 = what the fit itself needs."""
+        self._check(self._lib.gpx_reserve(self._h, int(n)))
+        return self
+
     def fit_predict(self, X, y, Xs, include_noise=False):
         """``fit(X, y)`` and ``predict(Xs)`` (mean and variance) as ONE factorisation pass: the cross-kernel rows
         of the query points ride through the blocked Cholesky as bordered rows (``gpx_fit_predict``), so the

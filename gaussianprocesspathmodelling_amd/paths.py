@@ -302,6 +302,21 @@ class PathModel:
             return out[:, jt, :]
         return out[0][:, jt, :], out[1][:, jt, :]
 
+    def add_paths(self, trajs, keys):
+        """Append the paths ``keys`` of ``trajs`` to this cluster's model (``GP.update``: the factor of the paths already
+        modelled is kept).  Inputs and targets go through the normalisation fixed at the first fit (``in_lo``,
+        ``in_span``, ``y_mean``, ``y_std``), so the result is the GP of all the cluster's paths under that normalisation.
+        Extends ``keys``; returns ``self``."""
+        keys = list(keys)
+        if not keys:
+            return self
+        X, Y, _ = to_gp_inputs(trajs, keys, inputs=self.inputs, targets=self.targets, normalise=False)
+        Xn = np.ascontiguousarray((X - self.in_lo) / self.in_span)
+        Yn = np.ascontiguousarray((Y - self.y_mean) / self.y_std)
+        self.gp.update(Xn, Yn)
+        self.keys.extend(keys)
+        return self
+
     def close(self):
         self.gp.close()
 

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define GPX_ABI_VERSION 6 /* v6: gpx_predict_cov, gpx_sample_posterior, later gpx_predict_grad and gpx_kernel_grad_matrix (additive: no existing call, struct or layout changed); v5: gpx_timings.handover_*, fp32 / mixed shards; v4: + gpx_fit_predict (v3: gpx_set_flags, refine, one-rank groups) */
+#define GPX_ABI_VERSION 6 /* v6: gpx_predict_cov, gpx_sample_posterior, later gpx_predict_grad, gpx_kernel_grad_matrix, gpx_append, gpx_reserve and gpx_factor_info (additive: no existing call, struct or layout changed); v5: gpx_timings.handover_*, fp32 / mixed shards; v4: + gpx_fit_predict (v3: gpx_set_flags, refine, one-rank groups) */
 
 /* kernel family — SURVEY.md §8 row a1 (nearest reference code: the pairwise
  * distance loop trajectories.calc_distance, GPmap.py:114-121, and the unused
@@ -217,6 +217,36 @@ int gpx_sample_posterior(gpx_handle* h, const void* Xs, int64_t M, int64_t S, ui
  * mean (M,k) and var (M) (each may be NULL) = gpx_predict's, from the same pass. */
 int gpx_predict_grad(gpx_handle* h, const void* Xs, int64_t M, void* mean, void* var, void* dmean, void* dvar,
                      int32_t mem_kind);
+
+/* ---- appending observations (additive to ABI v6) ------------------------------------------------------------------------
+ * gpx_append: m more observations into a fitted handle without factorising the old ones again.  Xnew (m,d), ynew (m,k)
+ * row-major in the handle's element type, d and k as fitted.  Afterwards the handle is, to rounding, what gpx_fit of the
+ * concatenated N + m points with the same hyper-parameters and the fit's jitter would have left: every other call
+ * (gpx_predict, _cov, _grad, gpx_sample_posterior, gpx_get_alpha, gpx_logdet, gpx_lml_grad, a further gpx_append) works on
+ * N + m points.  With nb the fit's panel width (kept for the life of the fit) and R0 = floor(N / nb) nb, rows [0, R0) of L
+ * and columns [0, R0) of z^T = (L^-1 y)^T stay as they are; the call solves the left part of the 128-row tiles that hold a
+ * new point against those R0 columns, rebuilds K on [R0, N + m)^2, subtracts the Schur term of the R0 columns in one product
+ * and restarts the blocked factorisation there (the right-hand sides ride as bordered rows, as in gpx_fit):
+ * m' R0^2 + n'^2 R0 + n'^3 / 3 flops, m' the rows solved again and n' the padded trailing size, against N^3 / 3.
+ * *info > 0: 1-based index, in the concatenated data, of the first non-positive pivot; the call returns 0 and the handle
+ * holds the previous fit again (N points, every call valid): the same restart with no new point rebuilds it.
+ * Timings: the fit fields (h2d, kbuild, chol, logdet, fit_total), zeroed at the start of the call.
+ * Single-device GPX_F64 / GPX_F32 handles after a successful fit (else GPX_E_ARG); GPX_MIXED handles, shards and device
+ * groups return GPX_E_UNSUPPORTED (nothing computed, the fit stays valid).
+ * Memory: within the capacity of the layout (gpx_reserve; without it the padding up to the next multiple of 128) nothing
+ * is reallocated or copied.  Beyond it the factor's lower triangle moves into a buffer with room for one more panel
+ * width of points, so a stream of small appends reallocates at most once per nb points; old and new buffer exist side by
+ * side for that moment.  GPX_E_NOMEM (gpx_last_error names the bytes) comes before anything is touched: the fit stays valid. */
+int gpx_append(gpx_handle* h, const void* Xnew, const void* ynew, int64_t m, int32_t mem_kind, int64_t* info);
+/* The next gpx_fit and later gpx_append lay the factor buffer out for up to `capacity` points (leading dimension from
+ * round_up(capacity, 128)); appends within it happen in place.  0 (the default): what the fit itself needs — a handle
+ * that never calls this fits exactly as before.  On a fitted handle a capacity below its N is GPX_E_ARG; a larger one
+ * takes effect with the next append (one move of the factor).  Refusals as for gpx_append. */
+int gpx_reserve(gpx_handle* h, int64_t capacity);
+/* Where the factor lives (single-device GPX_F64 / GPX_F32 handles after a successful fit): its device pointer (row-major,
+ * lower triangle), leading dimension in elements and the points the layout has room for.  Any output may be NULL.  The
+ * pointer changes only when a fit or an append has to reallocate. */
+int gpx_factor_info(gpx_handle* h, const void** factor, int64_t* ld, int64_t* capacity);
 
 int gpx_get_alpha(gpx_handle* h, void* out /* (N,k) host */);
 /* Log marginal likelihood of the last fit and its gradient w.r.t. the LOG hyper-parameters —
