@@ -71,6 +71,8 @@ SIGNATURES = {
     "gpx_sample_posterior": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_uint64, _P, C.c_double, C.c_double, C.c_int32,
                                        _P, _PD, C.POINTER(C.c_int64), C.c_int32]),
     "gpx_predict_grad": (C.c_int, [_P, _P, C.c_int64, _P, _P, _P, _P, C.c_int32]),
+    "gpx_score_blocks": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, C.c_double, _P, _P, _P, C.c_int32,
+                                   C.POINTER(C.c_int64)]),
     "gpx_append": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, C.POINTER(C.c_int64)]),
     "gpx_reserve": (C.c_int, [_P, C.c_int64]),
     "gpx_factor_info": (C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),

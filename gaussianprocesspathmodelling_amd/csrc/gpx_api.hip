@@ -120,6 +120,8 @@ struct gpx_handle {
     DevBuf JVT, JTsol, JSig, JSigF, JWinv, JP, JWblk, JUblk, JInfo, JZT, JST, JZin, JOut;
     // posterior gradient (gpx_predict_grad): scratch of its own as well
     DevBuf GV, GTsol, GMT, GMTpart, GVN, GPart, GOut;
+    // block scoring (gpx_score_blocks): targets, per-slice Gram partials, batch mean^T, results + the bad-block word
+    DevBuf SY, SPart, SMT, SOut;
   } scr;
   // row-block shard (world > 1)
   Comm* comm = nullptr;  // RCCL, in-process or host-callback transport (gpx_shard.inc)
@@ -1829,6 +1831,118 @@ int sample_posterior_impl(gpx_handle* h, const void* Xq, int64_t M, int64_t S, u
   return finish_call(h);
 }
 
+// ---- joint density of blocks of query points (gpx_score_blocks) -------------------------------------------
+// predict_core's batch loop with whole blocks per batch: floor(MB / Lg) blocks, their rows padded to 128 for the solve, so
+// no block straddles two V^T buffers; the row norms of predict give way to the per-block Gram of V^T and the block
+// factorisation (gpx_score.hip).  V^T, its solve buffers and the mean product's buffers are predict's own scratch; the fit
+// is only read.
+
+// device bytes per row of a batch beyond the fit: V^T, the two compact solve buffers, the Gram partials of its share of a block
+template <typename T>
+size_t score_row_bytes(const gpx_handle* h, int Lg) {
+  const int LP = score_lp(Lg);
+  size_t b = (size_t)h->ld * sizeof(T);
+  if (h->nbw == h->nb_pred) b += (size_t)2 * (h->nbw + ld_skew<T>()) * sizeof(T);
+  return b + ((size_t)score_slices(h->Npad) * LP * LP * sizeof(double) + Lg - 1) / Lg;
+}
+
+template <typename T>
+int score_impl(gpx_handle* h, const void* Xq, const void* yq, int64_t G, int32_t Lg, double diag_add, void* logp, void* maha,
+               void* logdet, int32_t mem_kind, int64_t* info) {
+  const int64_t N = h->N, Npad = h->Npad, ld = h->ld, M = G * Lg;
+  const int d = h->d, k = h->k;
+  const int64_t Mpad = round_up(M, TILE);
+  gpx_timings& tm = h->tm;
+  reset_predict_clocks(tm);
+  int rc;
+  {  // not one 128-row batch beside what the call keeps per query point: refused before anything is allocated
+    const size_t row_bytes = score_row_bytes<T>(h, Lg);
+    const size_t E = sizeof(T);
+    const double small = (double)(M + 2 * TILE) * d * 2 * E + (double)M * k * 2 * E + (double)G * (2 * k + 1) * E +
+                         (double)RHS_ROWS * (TILE + ld_skew<T>()) * (1 + splitk_splits(Npad)) * E + 4096;
+    const double need = (double)TILE * row_bytes + small;
+    const double have = (double)h->scr.VT.cap + h->scr.Tsol.cap + h->scr.SPart.cap + h->scr.Q.cap + h->scr.Qs.cap + h->scr.SY.cap +
+                        h->scr.SOut.cap + h->scr.SMT.cap + h->scr.MTpart.cap + h->meanout.cap;
+    size_t freeb = 0, totalb = 0;
+    HIPCHK(h, hipMemGetInfo(&freeb, &totalb));
+    if (need > (double)freeb + have) {
+      char buf[256];
+      snprintf(buf, sizeof buf, "gpx_score_blocks: one batch of 128 rows needs %.3f GB of device memory, %.3f GB are free",
+               need / 1e9, ((double)freeb + have) / 1e9);
+      return fail(h, GPX_E_NOMEM, buf);
+    }
+  }
+  const int64_t MB = pred_batch_rows(h, Mpad, score_row_bytes<T>(h, Lg), true);
+  const int64_t bpb = std::min<int64_t>(G, MB / Lg);  // whole blocks per batch (MB >= 128 >= 2 Lg)
+  const int64_t rows_b = round_up(bpb * Lg, TILE);     // <= MB
+  const int64_t ldmb = rows_b + ld_skew<T>();
+  const int S = score_slices(Npad), LP = score_lp(Lg);
+  // a batch reads rows_b rows of Qs from its first block on: up to 127 rows beyond M
+  if ((rc = ensure_queries<T>(h, M + TILE))) return rc;
+  if ((rc = ensure(h, h->scr.SY, (size_t)M * k * sizeof(T)))) return rc;
+  if ((rc = ensure(h, h->scr.VT, (size_t)rows_b * ld * sizeof(T)))) return rc;
+  if ((rc = ensure(h, h->scr.SMT, (size_t)RHS_ROWS * ldmb * sizeof(T)))) return rc;
+  if ((rc = ensure_mean_partials<T>(h, h->scr.MTpart, ldmb))) return rc;
+  if ((rc = ensure(h, h->meanout, (size_t)M * k * sizeof(T)))) return rc;
+  if ((rc = ensure(h, h->scr.SPart, (size_t)bpb * S * LP * LP * sizeof(double)))) return rc;
+  const size_t out_elems = (size_t)G * (2 * k + 1);
+  const size_t bad_off = round_up((int64_t)(out_elems * sizeof(T)), 16);
+  if ((rc = ensure(h, h->scr.SOut, bad_off + 16))) return rc;
+  SolveWork<T> sw;
+  if ((rc = dense_solve_work<T>(h, h->scr.Tsol, rows_b, &sw))) return rc;
+  T* dVT = (T*)h->scr.VT.p;
+  T* dMT = (T*)h->scr.SMT.p;
+  T* dLogp = (T*)h->scr.SOut.p;
+  T* dMaha = dLogp + G * k;
+  T* dLogdet = dMaha + G * k;
+  int* dBad = (int*)((char*)h->scr.SOut.p + bad_off);
+  const T* dQs = (const T*)h->scr.Qs.p;
+  int hbad = INT_MAX;
+  {
+    PhaseScope total(h, &tm.predict_total);
+    {
+      PhaseScope ps(h, &tm.kstar);
+      if ((rc = upload_queries<T>(h, Xq, M, mem_kind))) return rc;
+      HIPCHK(h, hipMemsetAsync((T*)h->scr.Qs.p + Mpad * d, 0, (size_t)TILE * d * sizeof(T), h->st));
+      if ((rc = copy_in(h, h->scr.SY.p, yq, (size_t)M * k * sizeof(T), mem_kind))) return rc;
+      const int init = INT_MAX;
+      HIPCHK(h, hipMemcpyAsync(dBad, &init, sizeof(int), hipMemcpyHostToDevice, h->st));
+    }
+    for (int64_t g0 = 0; g0 < G; g0 += bpb) {  // batches of whole blocks through one V^T buffer
+      const int64_t nb = std::min(bpb, G - g0), m0 = g0 * Lg;
+      const int64_t mv = nb * Lg, mp = round_up(mv, TILE);
+      {
+        PhaseScope ps(h, &tm.kstar);
+        launch_kbuild_cross<T>(h->cfg.kernel, dQs + m0 * d, mv, mp, (const T*)h->Xs.p, N, Npad, d, h->sf2, dVT, ld, h->st);
+      }
+      {
+        PhaseScope ps(h, &tm.trsm);
+        if ((rc = solve_fwd_enqueue<T>(h, dVT, mp, (const T*)h->Lfac, ld, Npad, h->nb_pred, (const T*)h->Winv.p, &sw))) return rc;
+      }
+      {  // mean^T (64 x mp) = z^T V, then the batch's rows of the mean (M, k)
+        PhaseScope ps(h, &tm.mean);
+        mean_product<T>(h, dMT, ldmb, (const T*)h->zT, dVT, mp, (T*)h->scr.MTpart.p, ldmb);
+        launch_unpack_rhs<T>(dMT, ldmb, mv, k, 1.0, (T*)h->meanout.p + m0 * k, h->st);
+      }
+      {
+        PhaseScope ps(h, &tm.var);
+        launch_block_gram<T>(dVT, ld, nb, Lg, Npad, (double*)h->scr.SPart.p, h->st);
+        launch_block_score<T>(h->cfg.kernel, (const double*)h->scr.SPart.p, nb, Lg, Npad, dQs + m0 * d, d,
+                              (const T*)h->scr.SY.p + m0 * k, (const T*)h->meanout.p + m0 * k, k, h->sf2, diag_add, dLogp,
+                              dMaha, dLogdet, g0, dBad, h->st);
+      }
+    }
+    PhaseScope ps(h, &tm.d2h);
+    if ((rc = copy_out(h, logp, dLogp, (size_t)G * k * sizeof(T), mem_kind))) return rc;
+    if (maha && (rc = copy_out(h, maha, dMaha, (size_t)G * k * sizeof(T), mem_kind))) return rc;
+    if (logdet && (rc = copy_out(h, logdet, dLogdet, (size_t)G * sizeof(T), mem_kind))) return rc;
+    HIPCHK(h, hipMemcpyAsync(&hbad, dBad, sizeof(int), hipMemcpyDeviceToHost, h->st));
+  }
+  if ((rc = finish_call(h))) return rc;
+  *info = hbad == INT_MAX ? 0 : (int64_t)hbad;
+  return GPX_OK;
+}
+
 // ---- posterior gradient (gpx_predict_grad) -------------------------------------------------------------------------
 // Mean only (var and dvar NULL): dmean = dK* alpha with the cached alpha, matrix-free (launch_kgrad_matvec); no solve,
 // nothing of size M N is stored; `mean` comes from predict's own mean-only path.
@@ -2589,6 +2703,22 @@ int gpx_predict_grad(gpx_handle* h, const void* Xq, int64_t M, void* mean, void*
   if ((rc = posterior_refused(h, "gpx_predict_grad"))) return rc;
   if ((rc = begin_call(h))) return rc;
   return BY_DTYPE(h, predict_grad_impl, h, Xq, M, mean, var, dmean, dvar, mem_kind);
+}
+GPX_CATCH_ALL
+
+int gpx_score_blocks(gpx_handle* h, const void* Xs, const void* ys, int64_t G, int32_t Lg, double diag_add, void* logp,
+                     void* maha, void* logdet, int32_t mem_kind, int64_t* info) try {
+  if (!h) return GPX_E_ARG;
+  if (!Xs || !ys || !logp || !info || G <= 0) return fail(h, GPX_E_ARG, "gpx_score_blocks: bad argument");
+  if (Lg < 1 || Lg > 64) return fail(h, GPX_E_ARG, "gpx_score_blocks: need 1 <= Lg <= 64");
+  if (!(diag_add >= 0.0)) return fail(h, GPX_E_ARG, "gpx_score_blocks: need diag_add >= 0");
+  if (mem_kind != GPX_MEM_HOST && mem_kind != GPX_MEM_DEVICE) return fail(h, GPX_E_ARG, "gpx_score_blocks: bad mem_kind");
+  if (!h->fitted) return fail(h, GPX_E_ARG, "gpx_score_blocks: handle has no successful fit");
+  if (G > ((int64_t)INT_MAX - 4096) / Lg) return fail(h, GPX_E_ARG, "gpx_score_blocks: G * Lg too large");
+  int rc;
+  if ((rc = posterior_refused(h, "gpx_score_blocks"))) return rc;
+  if ((rc = begin_call(h))) return rc;
+  return BY_DTYPE(h, score_impl, h, Xs, ys, G, Lg, diag_add, logp, maha, logdet, mem_kind, info);
 }
 GPX_CATCH_ALL
 

@@ -318,6 +318,23 @@ template <typename T>
 void launch_grad_unpack(const T* MT, int64_t ldm, const T* VN, int64_t mp, int64_t mv, int nblk, int d, int k,
                         int with_value, T* mean, T* var, T* dmean, T* dvar, hipStream_t st);
 
+// ---- joint density of blocks of query points (gpx_score.hip) -----------------------------------
+// Column slices of V^T per block in launch_block_gram: a function of npad ONLY (a block's partial sums, and with them its
+// results, may not depend on how many blocks a call or a batch holds).
+int score_slices(int64_t npad);
+inline int score_lp(int Lg) { return 16 * ((Lg + 15) / 16); }  // Gram edge: Lg rounded up to whole 16 x 16 MFMA tiles
+// part [nblk][score_slices(npad)][LP][LP] (fp64; only the lower 16 x 16 tiles are written): per-slice Gram of the rows
+// [b Lg, (b + 1) Lg) of VT (ld) over the columns [0, npad), block b < nblk, 1 <= Lg <= 64
+template <typename T>
+void launch_block_gram(const T* VT, int64_t ld, int64_t nblk, int Lg, int64_t npad, double* part, hipStream_t st);
+// Block b < nblk of a batch (global number g0 + b): S = sf2 k(Qs_b, Qs_b) + diag_add I - sum of its partials, Cholesky,
+// r = ys_b - mean_b (each (Lg, k)), then maha[g][c] = |L^-1 r_c|^2, logdet[g] = log|S|, logp[g][c]; Qs, ys, mean start at
+// the batch's first row, the outputs at block 0 of the call.  A pivot that is not > 0: NaN outputs, *bad = min(*bad, g + 1).
+template <typename T>
+void launch_block_score(int kernel, const double* part, int64_t nblk, int Lg, int64_t npad, const T* Qs, int d,
+                        const T* ys, const T* mean, int k, double sf2, double diag_add, T* logp, T* maha, T* logdet,
+                        int64_t g0, int* bad, hipStream_t st);
+
 // ---- row-block-cyclic shard helpers (gpx_misc.hip; T = double | float) ------------------------
 // A[i][i] = i < nvalid ? A[i][i] + add : 1   for i < n (diagonal of one local row block)
 template <typename T>

@@ -428,6 +428,56 @@ class GP:
             return (mean, var, dmean, dvar) if return_var else (mean, dmean)
         return (dmean, dvar) if return_var else dmean
 
+    def score_blocks(self, Xs, ys, block, include_noise=True, return_parts=False, on_bad="raise"):
+        """Joint log predictive density of whole blocks of query points (``gpx_score_blocks``): ``Xs`` (G * block, d)
+        holds G blocks of ``block`` consecutive points (a path = a block, 1 <= block <= 64), ``ys`` their observed
+        targets ((G * block,) for a 1-D ``y``, else (G * block, k)).  Returns ``logp`` ((G,) for a 1-D fit, else
+        (G, k)): the log-density of each block's targets under the joint posterior of its points — of noisy
+        observations with ``include_noise`` (``noise`` on the diagonal), else of the latent function.  With
+        ``return_parts``: ``(logp, maha, logdet)``, ``maha`` shaped as ``logp`` and ``logdet`` (G,), so that
+        ``logp = -maha / 2 - logdet / 2 - block / 2 log 2 pi``.  Only the block-diagonal of the joint covariance is
+        ever formed, and a block's numbers do not depend on the other blocks of the call.  A block whose covariance
+        is not positive definite (possible without the noise term) raises ``numpy.linalg.LinAlgError`` naming the
+        first such block; ``on_bad="nan"`` returns the arrays instead, that block's entries NaN and
+        ``score_info_`` its 1-based index.  NumPy in, NumPy out; device tensors in, device tensors out."""
+        if not self._fitted:
+            raise RuntimeError("score_blocks() before a successful fit()")
+        if on_bad not in ("raise", "nan"):
+            raise ValueError("on_bad must be 'raise' or 'nan'")
+        Lg = int(block)
+        if not 1 <= Lg <= 64:
+            raise ValueError("block must be between 1 and 64")
+        pq, kq, keepq, devq, sq = self._as_input(Xs, "Xs")
+        py, ky, keepy, devy, sy = self._as_input(ys, "ys")
+        if len(sq) != 2 or sq[1] != self._d:
+            raise ValueError(f"Xs must be (G * block, {self._d})")
+        M = sq[0]
+        if M == 0 or M % Lg:
+            raise ValueError(f"Xs must hold whole blocks of {Lg} points, has {M} rows")
+        if self._y1d:
+            ok = len(sy) == 1 or (len(sy) == 2 and sy[1] == 1)
+        else:
+            ok = len(sy) == 2 and sy[1] == self._k
+        if not ok or sy[0] != M:
+            raise ValueError("ys must be (G * block,)" if self._y1d else f"ys must be (G * block, {self._k})")
+        if kq != ky:
+            raise ValueError("Xs and ys must both be host arrays or both be device tensors")
+        G = M // Lg
+        oshape = (G,) if self._y1d else (G, self._k)
+        logp = self._empty(oshape, devq)
+        maha = self._empty(oshape, devq) if return_parts else None
+        logdet = self._empty((G,), devq) if return_parts else None
+        p = lambda a: None if a is None else self._ptr(a)  # noqa: E731
+        info = C.c_int64(0)
+        self._check(self._lib.gpx_score_blocks(self._h, pq, py, G, Lg, self.noise if include_noise else 0.0,
+                                               p(logp), p(maha), p(logdet), kq, C.byref(info)))
+        self.score_info_ = int(info.value)
+        if self.score_info_ and on_bad == "raise":
+            raise np.linalg.LinAlgError(
+                f"block {self.score_info_ - 1} (the first of its kind) has a joint posterior covariance that is not "
+                f"positive definite; score with include_noise=True or on_bad='nan'")
+        return (logp, maha, logdet) if return_parts else logp
+
     def _empty(self, shape, dev):
         """uninitialised output of the model's element type: on the device `dev` (torch), or NumPy when None"""
         if dev is not None:

@@ -317,6 +317,24 @@ class PathModel:
         self.keys.extend(keys)
         return self
 
+    def log_likelihood(self, paths_txy, include_noise=True):
+        """How likely whole paths are under this cluster's model: ``paths_txy`` (P, L, 3) raw (t, x, y) paths of one
+        length L <= 64 -> (P, k) log-densities of each path's targets, in the targets' own units, under the joint
+        posterior of its L points (``GP.score_blocks`` on the device: the points of a path are strongly correlated, so
+        this is not the sum of the per-point densities).  Inputs and targets go through the model's normalisation; the
+        Jacobian of the standardisation, ``-L log y_std[c]``, is included, so models with different standardisations
+        are comparable."""
+        arr = np.asarray(paths_txy, dtype=np.float64)
+        if arr.ndim != 3 or arr.shape[2] != 3 or arr.shape[0] == 0:
+            raise ValueError("paths must be a non-empty (P, L, 3) array of (t, x, y)")
+        P, L = arr.shape[:2]
+        col = {"t": 0, "x": 1, "y": 2}
+        flat = arr.reshape(-1, 3)
+        Xn = np.ascontiguousarray((flat[:, [col[c] for c in self.inputs]] - self.in_lo) / self.in_span)
+        Yn = np.ascontiguousarray((flat[:, [col[c] for c in self.targets]] - self.y_mean) / self.y_std)
+        logp = self.gp.score_blocks(Xn, Yn, L, include_noise=include_noise)
+        return np.asarray(logp, dtype=np.float64).reshape(P, -1) - L * np.log(self.y_std)[None, :]
+
     def close(self):
         self.gp.close()
 
@@ -402,3 +420,28 @@ def fit_path_models(trajs, clusters, inputs=("t",), targets=("x", "y"), devices=
                 m.close()
             raise err
     return {cid: models[cid] for cid, _ in jobs}
+
+
+# ---- which cluster does a path belong to: whole-path likelihood under every cluster's GP ----------
+def path_log_likelihood_matrix(trajs, models, keys=None):
+    """``(keys, LL)``: LL[p, c] = log-density of path ``keys[p]`` of ``trajs`` under model c of ``models`` =
+    {cluster id: :class:`PathModel`} (column order = ``models``' order), summed over the targets
+    (:meth:`PathModel.log_likelihood`).  The GP counterpart of :func:`path_distance_matrix`: it weighs a deviation
+    by what the cluster's own paths do at that point of the path, and it is a density, so an anomalous path shows
+    as a low maximum over the clusters."""
+    keys = trajs.keys() if keys is None else list(keys)
+    arr = trajs.as_array(keys)
+    LL = np.empty((len(keys), len(models)), dtype=np.float64)
+    if keys:
+        for c, m in enumerate(models.values()):
+            LL[:, c] = m.log_likelihood(arr).sum(axis=1)
+    return keys, LL
+
+
+def assign_paths(trajs, models, keys=None):
+    """{cluster id: [path ids]} by the largest whole-path log-likelihood (first maximum on ties) — the shape
+    :func:`kmeans` returns, so each list can go straight to that cluster's :meth:`PathModel.add_paths`."""
+    keys, LL = path_log_likelihood_matrix(trajs, models, keys)
+    cids = list(models.keys())
+    best = np.argmax(LL, axis=1) if keys else np.zeros(0, dtype=int)
+    return {cid: [keys[p] for p in np.nonzero(best == c)[0]] for c, cid in enumerate(cids)}

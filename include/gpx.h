@@ -218,6 +218,33 @@ int gpx_sample_posterior(gpx_handle* h, const void* Xs, int64_t M, int64_t S, ui
 int gpx_predict_grad(gpx_handle* h, const void* Xs, int64_t M, void* mean, void* var, void* dmean, void* dvar,
                      int32_t mem_kind);
 
+/* ---- joint density of blocks of query points (additive to ABI v6) --------------------------------------------------------
+ * How likely is a whole path under the fitted model: the query points come in G blocks of Lg consecutive points (a path =
+ * a block), and each block is scored under its JOINT posterior — the Lg x Lg diagonal block of gpx_predict_cov's matrix,
+ * never the (G Lg)^2 matrix itself.  Per batch of query points the call runs gpx_predict's K* build, variance solve and
+ * mean product, then ONE more pass over V^T = K* L^-T (the traffic of gpx_predict's variance pass): the lower 16 x 16 tiles
+ * of each block's Gram through the fp64 MFMA (fp32 rows are widened on the way in), one fp64 partial per column slice — the
+ * slice count depends on N only, nothing is accumulated atomically — and per block, in fp64 whatever the element type,
+ * S_g = sf2 k(X_g, X_g) + diag_add I - Gram, its Cholesky, and the forward solve of the k residual columns.  A block's
+ * results therefore do not depend on G, on its position in the call or on the batch size (GPX_PRED_BATCH; batches hold whole
+ * blocks).  Same handles, refusals (GPX_E_UNSUPPORTED for GPX_MIXED, shards, device groups: nothing computed, the fit stays
+ * valid), element type and memory kinds as gpx_predict_cov; every family, Matern-1/2 included (no derivative is involved).
+ * The fit is only read (gpx_predict afterwards is bit-identical); the device buffers are scratch (gpx_release_scratch frees
+ * them).  GPX_E_NOMEM (before any allocation, gpx_last_error names the bytes) when not even one batch of 128 rows fits.
+ * Bad arguments: GPX_E_ARG; *info is written only when the call returns 0.  Timings: kstar, trsm, mean, d2h, predict_total as
+ * for gpx_predict; var = the Gram pass plus the block factorisations. */
+/* Joint log predictive density of G blocks of Lg consecutive query points each (a path = a block).
+ * Xs (G*Lg, d), ys (G*Lg, k) row-major in the handle's element type, d and k as fitted.  For block g with
+ * m_g = K*_g alpha (Lg,k), S_g = K(X_g,X_g) - V_g^T V_g + diag_add I (the same for every target), r_c = ys_g[:,c] - m_g[:,c]:
+ *   maha[g,c] = r_c^T S_g^-1 r_c,  logdet[g] = log|S_g|,
+ *   logp[g,c] = -1/2 maha[g,c] - 1/2 logdet[g] - Lg/2 log 2 pi.
+ * diag_add >= 0: sn2 for the density of noisy observations, 0 for the latent function.  1 <= Lg <= 64, G >= 1.
+ * maha, logdet may be NULL.  *info > 0: 1-based index of the FIRST block whose S_g has a non-positive pivot; that
+ * block's outputs are NaN, every other block is valid; the call returns 0.  The fit is only read. */
+int gpx_score_blocks(gpx_handle* h, const void* Xs, const void* ys, int64_t G, int32_t Lg, double diag_add,
+                     void* logp /* (G,k) */, void* maha /* (G,k) */, void* logdet /* (G) */,
+                     int32_t mem_kind, int64_t* info);
+
 /* ---- appending observations (additive to ABI v6) ------------------------------------------------------------------------
  * gpx_append: m more observations into a fitted handle without factorising the old ones again.  Xnew (m,d), ynew (m,k)
  * row-major in the handle's element type, d and k as fitted.  Afterwards the handle is, to rounding, what gpx_fit of the

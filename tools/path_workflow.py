@@ -2,7 +2,8 @@
 """The reference's workflow end to end on the GPU, at a size where it matters: a synthetic CSV in
 the reference's wire format (header row with the id, `t,_,x,y` rows, `###`; GPmap.py:178-204) ->
 read_csv (validity rules) -> k-means over whole paths (distances on the GPU) -> one two-target GP
-per cluster (x(t), y(t) on one factor) -> posterior path + band per cluster.  Prints one JSON line
+per cluster (x(t), y(t) on one factor) -> posterior path + band per cluster -> every path scored under every
+cluster's model (whole-path log-likelihood, GP.score_blocks) and assigned to the likeliest.  Prints one JSON line
 with the stage times.   python tools/path_workflow.py [--paths 3000] [--clusters 6] [--optimize]"""
 import argparse, io, json, os, random, sys, time
 import numpy as np
@@ -52,7 +53,13 @@ for cid, m in models.items():
     out[str(cid)] = {"paths": len(clusters[cid]), "n_train": 33 * len(clusters[cid]), "end_point": mean[-1].round(0).tolist(),
                      "band_3sigma_coverage": float(inside), "lengthscale": m.gp.lengthscale.round(4).tolist(), "noise": round(m.gp.noise, 5)}
 times["predict_s"] = time.perf_counter() - t0
+t0 = time.perf_counter()
+_, LL = gpaths.path_log_likelihood_matrix(trajs, models, keys)
+times["score_s"] = time.perf_counter() - t0
+cids = list(models)
+by_gp = {cids[c]: {keys[p] for p in np.nonzero(np.argmax(LL, axis=1) == c)[0]} for c in range(len(cids))}
+agree = sum(len(by_gp[cid] & set(clusters[cid])) for cid in cids) / max(1, len(keys))
 for m in models.values():
     m.close()
 print(json.dumps({"config": f"{a.paths} synthetic paths of 33 points in the reference CSV format, k = {a.clusters}, devices = {a.devices}",
-                  "kept_paths": len(keys), **{k: round(v, 3) for k, v in times.items()}, "clusters": out}))
+                  "kept_paths": len(keys), "likelihood_agrees_with_kmeans": round(agree, 4), **{k: round(v, 3) for k, v in times.items()}, "clusters": out}))
