@@ -105,6 +105,7 @@ SIGNATURES = {
     "gpx_debug_set_delay": (C.c_int, [C.c_uint64]),
     "gpx_debug_gemm_bench": (C.c_int, [C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
                                        C.POINTER(C.c_double)]),
+    "gpx_debug_env": (C.c_int, [C.c_char_p, C.c_int32]),
     "gpx_mfma_probe": (C.c_int, [_PD, _PD, _PD]),
     "gpx_mfma_probe_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "gpx_microbench": (C.c_int, [_PD, _PD]),

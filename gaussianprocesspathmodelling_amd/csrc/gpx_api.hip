@@ -41,6 +41,7 @@
 
 #include "../../include/gpx.h"
 #include "gpx_cov.h"
+#include "gpx_env.h"
 #include "gpx_internal.h"
 
 using namespace gpx;
@@ -88,8 +89,8 @@ struct gpx_handle {
   gpx_config cfg{};
   int nb = 1024;       // Cholesky panel width
   int nb_solve = 256;  // block width of the alpha solves (one 64-row slab: latency-bound)
-  int nb_pred = 1024;  // block width of the variance TRSM (follows the panel width when the library chooses that: auto_panel_width)
-  bool nb_pred_env = false;  // GPX_NB_PRED given: never overridden
+  int nb_pred = 1024;  // block width of the variance TRSM (follows the panel width when the library chooses that — auto_panel_width — unless GPX_NB_PRED is given: env.nb_pred >= 0)
+  EnvKnobs env;        // the environment switches (gpx_env.h): create entries from gpx_create, call entries as of the start of this call (begin_call)
   hipStream_t st = nullptr;   // main stream
   hipStream_t st2 = nullptr;  // look-ahead (panel) stream, high priority
   hipStream_t st3 = nullptr;  // side stream of the diagonal chain: in-block SYRKs, block inverses
@@ -140,7 +141,6 @@ struct gpx_handle {
   DevBuf Wblk, Ublk; // explicit inverses of the nb x nb diagonal blocks of L ([Npad/nb][nb][nb]) + scratch
   int nbw = 0;       // block width of Wblk (0: not built)
   int nb_shard = 512;  // distribution block = panel width of the sharded factorisation (chosen per fit)
-  int nb_shard_env = 0;  // GPX_NB_SHARD override (0: choose from N and the number of ranks)
   int64_t nloc = 0, ldy = 0;
   DevBuf G, Dbuf, Sbuf, YTloc, Cneg;
   // replicated-factor mode of the shard: every rank keeps the whole L (the panels pass through
@@ -211,6 +211,26 @@ hipEvent_t next_event(gpx_handle* h) {
   return h->ev_pool[h->ev_used++];
 }
 
+// "what stream a has been given so far": a pooled event recorded on a, in *e — for a wait that comes later.  `site`
+// names the caller in the message of a call that fails here.
+int record_event(gpx_handle* h, hipStream_t a, const char* site, hipEvent_t* e) {
+  if (!(*e = next_event(h))) {
+    char msg[64];
+    snprintf(msg, sizeof msg, "hipEventCreate failed (%s)", site);
+    return fail(h, GPX_E_HIP, msg);
+  }
+  HIPCHK(h, hipEventRecord(*e, a));
+  return GPX_OK;
+}
+
+// stream b waits for what stream a has been given so far
+int stream_waits(gpx_handle* h, hipStream_t b, hipStream_t a, const char* site) {
+  hipEvent_t e;
+  if (int rc = record_event(h, a, site, &e)) return rc;
+  HIPCHK(h, hipStreamWaitEvent(b, e, 0));
+  return GPX_OK;
+}
+
 // roctx ranges around the phases (SURVEY.md §5 "tracing"): `rocprofv3 --marker-trace --kernel-trace` then shows which
 // phase of a fit / predict enqueued which kernels.  librocprofiler-sdk-roctx.so is resolved at run time — the copy a
 // profiler already mapped if there is one — and everything is a no-op when it is absent or GPX_ROCTX=0.  The ranges
@@ -222,8 +242,9 @@ struct Roctx {
 const Roctx& roctx() {
   static const Roctx r = [] {
     Roctx x;
-    const char* e = getenv("GPX_ROCTX");
-    if (e && atoi(e) == 0) return x;
+    EnvKnobs env;
+    env_read(env, EnvAt::process);
+    if (!env.roctx) return x;
     void* lib = nullptr;
     for (const char* n : {"librocprofiler-sdk-roctx.so.1", "librocprofiler-sdk-roctx.so", "libroctx64.so.4", "libroctx64.so"})
       if ((lib = dlopen(n, RTLD_NOW | RTLD_NOLOAD))) break;
@@ -285,14 +306,10 @@ void collect_phases(gpx_handle* h) {
   h->ev_used = 0;
 }
 
-// rocprofv3 --pmc (or a counter input file) exports ROCPROF_COUNTER_COLLECTION=1 into the profiled process.
-// Counter collection serialises kernels across streams in an order of its own, which a stream parked on a
+// EnvKnobs::counters_collected: rocprofv3 --pmc (or a counter input file) exports ROCPROF_COUNTER_COLLECTION=1 into the
+// profiled process.  Counter collection serialises kernels across streams in an order of its own, which a stream parked on a
 // device flag (wait_counter_kernel) does not survive — it would spin until its time-out — so the device-side
 // hand-overs switch themselves off there and the schedule falls back to hipEvents (same kernels otherwise).
-bool counters_are_being_collected() {
-  const char* e = getenv("ROCPROF_COUNTER_COLLECTION");
-  return e && atoi(e) != 0;
-}
 
 // Self-test of the device-flag hand-over, once per handle: a wait kernel on the side stream, then a
 // one-thread store on the main stream.  With concurrent queues the waiter sees the flag within microseconds; where
@@ -302,8 +319,8 @@ bool counters_are_being_collected() {
 // wait_counter_kernel's 15 s time-out inside a fit.  GPX_CHAIN_FLAG=0|1 overrides (and skips the probe).
 int flag_handover_probe(gpx_handle* h) {
   if (h->flag_ok >= 0) return GPX_OK;
-  if (getenv("GPX_CHAIN_FLAG")) return GPX_OK;  // explicit override (chain_flag_enabled reads it per call): nothing cached
-  if (counters_are_being_collected() || !h->st3) {
+  if (h->env.chain_flag >= 0) return GPX_OK;  // explicit override (chain_flag_enabled looks at it per call): nothing cached
+  if (h->env.counters_collected || !h->st3) {
     h->flag_ok = 0;
     return GPX_OK;
   }
@@ -325,10 +342,28 @@ int flag_handover_probe(gpx_handle* h) {
   return GPX_OK;
 }
 
-// device-flag hand-overs for this handle's schedule?  (read per call: tests switch the environment)
+// device-flag hand-overs for this handle's schedule?  (per call: tests switch GPX_CHAIN_FLAG between fits)
 bool chain_flag_enabled(const gpx_handle* h) {
-  if (const char* e = getenv("GPX_CHAIN_FLAG")) return atoi(e) != 0;
-  return !counters_are_being_collected() && h->flag_ok == 1;
+  if (h->env.chain_flag >= 0) return h->env.chain_flag != 0;
+  return !h->env.counters_collected && h->flag_ok == 1;
+}
+
+// the trailing update of chol_enqueue: one fused launch (GPX_FUSED_STRIP, device-flag hand-overs only), else the split
+// schedule (the default), else the round-2 look-ahead
+bool fused_strip_in_force(const gpx_handle* h) { return h->env.fused_strip && chain_flag_enabled(h); }
+bool split_strip_in_force(const gpx_handle* h) { return h->env.split_strip && !fused_strip_in_force(h); }
+
+// A stream parked on a device flag timed out (a negative info word) although the handle's self-test passed — a tool
+// attached later, or one that reorders rather than serialises.  True: the handle hands over by hipEvents from now on and
+// the caller runs its work once more (same kernels, same bits).  False — a second failure, or the user forced the flag
+// with GPX_CHAIN_FLAG — is the caller's error.  The decision uses nothing that differs between the ranks of a shard (not
+// the rank-local h->flag_ok: with it at 0 and the flag not forced no stream of THIS handle parks, but a peer's may have
+// timed out, and the ranks must retry — or leave — together).
+bool retry_with_events(gpx_handle* h, bool retried) {
+  if (retried || h->env.chain_flag >= 0) return false;
+  h->flag_ok = 0;
+  h->flag_retries += 1;
+  return true;
 }
 
 struct LatencyGuard {  // set_latency_mode(0) on every exit path of a scheduler function
@@ -390,7 +425,7 @@ int diag_enqueue(gpx_handle* h, T* A, int64_t ld, int64_t o, int nbp, T* Winv, i
     Wp = iw->W + (o / iw->nbw) * (int64_t)iw->nbw * iw->nbw;
     // the side stream starts behind everything already queued on s: the W block may live in a
     // buffer that earlier work on s (or, through its waits, on other ranks) is still reading
-    hipEvent_t e0 = next_event(h);
+    hipEvent_t e0 = next_event(h);  // (taken in front of the memset: not record_event)
     if (!e0) return fail(h, GPX_E_HIP, "hipEventCreate failed (block inverse)");
     // the step flag (info[9]) is reset in front of the FIRST block only; later blocks count on (one memset and
     // the gaps around it less on the chain per block; every stream that polls the flag starts behind e0)
@@ -412,10 +447,7 @@ int diag_enqueue(gpx_handle* h, T* A, int64_t ld, int64_t o, int nbp, T* Winv, i
   // (POTF2 of 64, the 64 x 64 block below it, its update, POTF2 of the second 64: potf2_128_kernel),
   // then one solve of the rows below, one update inside the block and one inverse-extension event
   // per 128 columns instead of per 64 (GPX_DIAG_STEP=64 selects the old stepping: A/B measurement).
-  const int diag_step = [] {  // read per call (tests switch it)
-    const char* e = getenv("GPX_DIAG_STEP");
-    return (e && atoi(e) == 64) ? 64 : 128;
-  }();
+  const int diag_step = h->env.diag_step;
   const int nq = nbp / KB;
   for (int q = 0; q < nq;) {
     const int w = (diag_step == 128 && q + 1 < nq) ? 2 : 1;  // 64-blocks factored by this step
@@ -444,10 +476,7 @@ int diag_enqueue(gpx_handle* h, T* A, int64_t ld, int64_t o, int nbp, T* Winv, i
         }
         launch_wait_counter(dflag, seq, info, iw->aux);
       } else {  // the same two launches (the same arithmetic, bit for bit), both behind the step's event
-        hipEvent_t e = next_event(h);
-        if (!e) return fail(h, GPX_E_HIP, "hipEventCreate failed (block inverse)");
-        HIPCHK(h, hipEventRecord(e, s));
-        HIPCHK(h, hipStreamWaitEvent(iw->aux, e, 0));
+        if (int rc = stream_waits(h, iw->aux, s, "block inverse")) return rc;
         launch_inv_extend<T>(iw->U, iw->ldu, A + o * ld + o, ld, Winv + (o / KB) * (KB * KB), q, q + w, Wp, iw->nbw,
                              iw->aux, 1);
       }
@@ -458,9 +487,7 @@ int diag_enqueue(gpx_handle* h, T* A, int64_t ld, int64_t o, int nbp, T* Winv, i
   }
   if (iw) {
     iw->seq = seq;
-    iw->ready = next_event(h);
-    if (!iw->ready) return fail(h, GPX_E_HIP, "hipEventCreate failed (block inverse)");
-    HIPCHK(h, hipEventRecord(iw->ready, iw->aux));
+    if (int rc = record_event(h, iw->aux, "block inverse", &iw->ready)) return rc;
   }
   return GPX_OK;
 }
@@ -482,9 +509,7 @@ int panel_solve_enqueue(gpx_handle* h, T* A, int64_t ld, int64_t o, int nbp, int
   const int64_t rows = rows_main + nx;
   if (rows <= 0) {
     if (iw && last && row0 > 0) {  // nothing in this part: the first part's copy is the panel's
-      iw->copied[set] = next_event(h);
-      if (!iw->copied[set]) return fail(h, GPX_E_HIP, "hipEventCreate failed (panel copy)");
-      HIPCHK(h, hipEventRecord(iw->copied[set], h->st4));
+      if (int rc = record_event(h, h->st4, "panel copy", &iw->copied[set])) return rc;
     }
     return GPX_OK;
   }
@@ -507,16 +532,9 @@ int panel_solve_enqueue(gpx_handle* h, T* A, int64_t ld, int64_t o, int nbp, int
       launch_gemm_nt<T>(64, P + rows_main * ldp, ldp, Apanel + rows_main * ld, ld, Wp, iw->nbw, nx, nbp, nbp, 4, 1,
                         s);
   }
-  hipEvent_t e = next_event(h);
-  if (!e) return fail(h, GPX_E_HIP, "hipEventCreate failed (panel copy)");
-  HIPCHK(h, hipEventRecord(e, s));
-  HIPCHK(h, hipStreamWaitEvent(h->st4, e, 0));
+  if (int rc = stream_waits(h, h->st4, s, "panel copy")) return rc;
   launch_copy2d<T>(Apanel, ld, P, ldp, rows, nbp, h->st4);
-  if (last) {
-    iw->copied[set] = next_event(h);
-    if (!iw->copied[set]) return fail(h, GPX_E_HIP, "hipEventCreate failed (panel copy)");
-    HIPCHK(h, hipEventRecord(iw->copied[set], h->st4));
-  }
+  if (last) return record_event(h, h->st4, "panel copy", &iw->copied[set]);
   return GPX_OK;
 }
 
@@ -540,10 +558,10 @@ int chol_enqueue(gpx_handle* h, T* A, int64_t ld, int64_t n, int nb, T* Winv, T*
   hipStream_t s0 = h->st, s1 = h->st2;
   T* Pbuf[2] = {P0, P1};
   int rc;
-  const bool fuse_env = [] {  // read per call (tests switch it); default OFF: measured equal, see DESIGN.md §5.2
-    const char* e = getenv("GPX_FUSED_STRIP");
-    return e && atoi(e) != 0;
-  }() && chain_flag_enabled(h);
+  // The schedule is a function of the arguments and the handle: its switches are h->env, the snapshot the call took
+  // when it began (gpx_env.h), and nothing below reads the environment.
+  const EnvKnobs& env = h->env;
+  const bool fuse_env = fused_strip_in_force(h);  // default OFF: measured equal, see DESIGN.md §5.2
   unsigned* ctr = reinterpret_cast<unsigned*>(info + 8);  // the info buffer is 64 bytes: [0] pivot, [8] strip counter
   unsigned target = 0;
   // is the trailing update of the panel at offset o one fused launch?  (128-tiles for strip and rest)
@@ -584,18 +602,9 @@ int chol_enqueue(gpx_handle* h, T* A, int64_t ld, int64_t n, int nb, T* Winv, T*
     const int64_t nrest = ntrail - nbn;
     return nrest > 0 && ntrail % 128 == 0 && nbn % 128 == 0 && gemm_nt_tile(128, nrest, nrest, 1) == 128;
   };
-  const bool split_env = [] {  // read per call (tests switch it)
-    const char* e = getenv("GPX_SPLIT_STRIP");
-    return !e || atoi(e) != 0;
-  }() && !fuse_env;  // (the fused update keeps its own hand-over)
-  const bool top_env = [] {  // GPX_SOLVE_TOP=0: the whole panel solve on the chain (A/B)
-    const char* e = getenv("GPX_SOLVE_TOP");
-    return !e || atoi(e) != 0;
-  }();
-  const int rest_split = [] {  // trailing rows (in panels) up to which the REST hands its first column block over early
-    const char* e = getenv("GPX_REST_SPLIT");
-    return e ? atoi(e) : 16;
-  }();
+  const bool split_env = split_strip_in_force(h);  // (the fused update keeps its own hand-over)
+  const bool top_env = env.solve_top;              // GPX_SOLVE_TOP=0: the whole panel solve on the chain (A/B)
+  const int rest_split = env.rest_split;  // trailing rows (in panels) up to which the REST hands its first column block over early
   // The LAST nx_side bordered rows (the query points of gpx_fit_predict: a multiple of 128) are the main stream's
   // business alone in the split schedule: their panel solves, like their updates, are throughput work no step of the
   // chain waits for (tried: a stream of their own that trails the factorisation panel by panel, reading L from A —
@@ -621,16 +630,15 @@ int chol_enqueue(gpx_handle* h, T* A, int64_t ld, int64_t n, int nb, T* Winv, T*
   set_latency_mode(1);  // panel 0: nothing runs beside it
   // GPX_CU_SELF_RESERVE = k (round 4): where the chain sets the pace, the main stream's products leave k CUs per XCD to it
   // by themselves (gemm_nt_resv_kernel: persistent grids that exit on the reserved CUs).  Split schedule only.
-  const int resv_k = [] {
-    const char* e = getenv("GPX_CU_SELF_RESERVE");
-    const int v = e ? atoi(e) : 0;
-    return v > 0 && v <= 4 ? v : 0;
-  }();
+  // GPX_RESV_ALL=1 (experiment): every panel's main-stream products, not only the chain-bound ones.  GPX_RESV_CHAIN: 0
+  // chain untouched, 1 (default) POTF2 padded to 130 KB of LDS, 2 also its slab launches.  GPX_RESV_FORM: the grid of the
+  // self-reserving launches (launch_gemm_nt).
+  const int resv_k = env.cu_self_reserve;
   ReserveGuard reserve_guard;
   if (resv_k > 0 && split_env) {
     if ((rc = ensure(h, h->resv_ring, (size_t)RESV_RING * 8 * sizeof(unsigned)))) return rc;
     HIPCHK(h, hipMemsetAsync(h->resv_ring.p, 0, (size_t)RESV_RING * 8 * sizeof(unsigned), s0));
-    reserve_ring((unsigned*)h->resv_ring.p, RESV_RING);
+    reserve_ring((unsigned*)h->resv_ring.p, RESV_RING, env.resv_form);
   }
   const bool any_fused = is_fused(0);
   if (any_fused) HIPCHK(h, hipMemsetAsync(ctr, 0, sizeof(unsigned), s0));
@@ -647,18 +655,11 @@ int chol_enqueue(gpx_handle* h, T* A, int64_t ld, int64_t n, int nb, T* Winv, T*
     }
     if (any_fused) {
       bordered_update(0, Pbuf[0], s0);
-      hipEvent_t e_init = next_event(h);
-      if (!e_init) return fail(h, GPX_E_HIP, "hipEventCreate failed (look-ahead)");
-      HIPCHK(h, hipEventRecord(e_init, s0));
-      HIPCHK(h, hipStreamWaitEvent(s1, e_init, 0));  // counter reset + panel 0 before the parked stream's first poll
+      if ((rc = stream_waits(h, s1, s0, "look-ahead"))) return rc;  // counter reset + panel 0 before the parked stream's first poll
     }
   }
   hipEvent_t e_main = nullptr;  // split strip: "the main stream's work on the trailing matrix so far is complete"
-  if (split_env && n > nb) {
-    e_main = next_event(h);
-    if (!e_main) return fail(h, GPX_E_HIP, "hipEventCreate failed (look-ahead)");
-    HIPCHK(h, hipEventRecord(e_main, s0));  // panel 0 ran on the main stream
-  }
+  if (split_env && n > nb && (rc = record_event(h, s0, "look-ahead", &e_main))) return rc;  // panel 0 ran on the main stream
   int step = 0;
   for (int64_t o = 0; o < n; o += nb, ++step) {
     const int nbp = (int)std::min<int64_t>(nb, n - o);
@@ -701,11 +702,7 @@ int chol_enqueue(gpx_handle* h, T* A, int64_t ld, int64_t n, int nb, T* Winv, T*
     if (split_env) {
       hipStream_t sm = s0;
       // self-reserving main-stream products where the chain sets the pace (the criterion of the REST's early hand-over)
-      static const bool resv_all = [] {  // GPX_RESV_ALL=1 (experiment): every panel's main-stream products, not only the chain-bound ones
-        const char* e = getenv("GPX_RESV_ALL");
-        return e && atoi(e) != 0;
-      }();
-      const int resv_it = (resv_k > 0 && (resv_all || ntrail <= (int64_t)(rest_split + 1) * nb)) ? resv_k : 0;
+      const int resv_it = (resv_k > 0 && (env.resv_all || ntrail <= (int64_t)(rest_split + 1) * nb)) ? resv_k : 0;
       // SPLIT STRIP (round 3, the default): of the strip only the next DIAGONAL block is on the chain.  It is
       // updated on the look-ahead stream itself, right behind the panel solve that produced its operand (no
       // hand-over between streams on the chain; 64-tiles in latency mode: a K = nb walk of a 64-tile is a
@@ -728,9 +725,8 @@ int chol_enqueue(gpx_handle* h, T* A, int64_t ld, int64_t n, int nb, T* Winv, T*
                             0, sm);
         bordered_block(o, Pc, sm, t0, nbn, 0, nxc);
       }
-      hipEvent_t e_below = next_event(h);
-      if (!e_below) return fail(h, GPX_E_HIP, "hipEventCreate failed (look-ahead)");
-      HIPCHK(h, hipEventRecord(e_below, sm));
+      hipEvent_t e_below;
+      if ((rc = record_event(h, sm, "look-ahead", &e_below))) return rc;
       // REST.  Where the chain, not the update, sets the pace (the last `rest_split` panels' worth of trailing
       // rows: all of N = 8192, the tail of N = 65536), the column block of the panel AFTER next goes first, as a
       // launch of its own, and the look-ahead stream's next diagonal-block update waits for that launch only:
@@ -746,9 +742,7 @@ int chol_enqueue(gpx_handle* h, T* A, int64_t ld, int64_t n, int nb, T* Winv, T*
           PhaseScope ps(h, &h->tm.chol_strip, profile, sm);
           launch_gemm_nt<T>(tile, Cr, ld, Pr, ldp, Pr, ldp, nrest, nbn2, nbp, 2, 0, sm);
         }
-        e_main = next_event(h);
-        if (!e_main) return fail(h, GPX_E_HIP, "hipEventCreate failed (look-ahead)");
-        HIPCHK(h, hipEventRecord(e_main, sm));
+        if ((rc = record_event(h, sm, "look-ahead", &e_main))) return rc;
       }
       const int64_t nr = ahead ? nrest - nbn2 : nrest, off = ahead ? nbn2 : 0;
       if (nr > 0) {
@@ -760,11 +754,7 @@ int chol_enqueue(gpx_handle* h, T* A, int64_t ld, int64_t n, int nb, T* Winv, T*
           h->tm.syrk_launches += 1;
         }
       }
-      if (!ahead) {
-        e_main = next_event(h);
-        if (!e_main) return fail(h, GPX_E_HIP, "hipEventCreate failed (look-ahead)");
-        HIPCHK(h, hipEventRecord(e_main, sm));
-      }
+      if (!ahead && (rc = record_event(h, sm, "look-ahead", &e_main))) return rc;
       {  // the bordered rows' share of the REST (columns beyond the next panel); the side rows' whole step — their
          // panel solve and the update of every column to the right — behind everything the chain waits for
         PhaseScope ps(h, &h->tm.chol_strip, profile, sm);
@@ -775,11 +765,7 @@ int chol_enqueue(gpx_handle* h, T* A, int64_t ld, int64_t n, int nb, T* Winv, T*
       set_reserve_mode(0);
       {
         PhaseScope ps(h, &h->tm.chol_diag, profile, s1);
-        static const int chain_env = [] {  // GPX_RESV_CHAIN: 0 chain untouched, 1 (default) POTF2 padded to 130 KB of LDS, 2 also its slab launches
-          const char* e = getenv("GPX_RESV_CHAIN");
-          return e ? atoi(e) : 1;
-        }();
-        set_reserve_chain(resv_it > 0 ? chain_env : 0);
+        set_reserve_chain(resv_it > 0 ? env.resv_chain : 0);
         rc = diag_enqueue(h, A, ld, t0, nbn, Winv, info, gidx0, s1, iw);
         set_reserve_chain(0);
         if (rc) return rc;
@@ -823,10 +809,7 @@ int chol_enqueue(gpx_handle* h, T* A, int64_t ld, int64_t n, int nb, T* Winv, T*
     }
     // the two streams touch the same matrix: an event that cannot be created / recorded /
     // waited on must fail the call, never let the streams run unordered
-    hipEvent_t e_strip = next_event(h);
-    if (!e_strip) return fail(h, GPX_E_HIP, "hipEventCreate failed (look-ahead)");
-    HIPCHK(h, hipEventRecord(e_strip, s0));
-    HIPCHK(h, hipStreamWaitEvent(s1, e_strip, 0));
+    if ((rc = stream_waits(h, s1, s0, "look-ahead"))) return rc;
     {  // look-ahead stream: factor diagonal block p+1, solve panel p+1
       {
         PhaseScope ps(h, &h->tm.chol_diag, profile, s1);
@@ -853,12 +836,8 @@ int chol_enqueue(gpx_handle* h, T* A, int64_t ld, int64_t n, int nb, T* Winv, T*
     HIPCHK(h, hipStreamWaitEvent(s0, e_panel, 0));
   }
   if (iw) {  // join the side and copy streams: the last inverse and every panel copy-back are in W / A
-    for (hipStream_t sj : {iw->aux, h->st4}) {
-      hipEvent_t e = next_event(h);
-      if (!e) return fail(h, GPX_E_HIP, "hipEventCreate failed (join)");
-      HIPCHK(h, hipEventRecord(e, sj));
-      HIPCHK(h, hipStreamWaitEvent(s0, e, 0));
-    }
+    for (hipStream_t sj : {iw->aux, h->st4})
+      if ((rc = stream_waits(h, s0, sj, "join"))) return rc;
   }
   return GPX_OK;
 }
@@ -991,11 +970,7 @@ int copy_out(gpx_handle* h, void* dst, const void* src, size_t bytes, int mem_ki
 // GPX_PRED_BATCH rows (default 8192, a multiple of 128), and — where every rank decides for
 // itself (no collective inside the batch loop) — shrunk to what the card has left.
 int64_t pred_batch_rows(gpx_handle* h, int64_t Mpad, size_t row_bytes, bool may_shrink) {
-  int64_t cap = 8192;
-  if (const char* e = getenv("GPX_PRED_BATCH")) {
-    const long v = atol(e);
-    if (v >= 128 && v <= (1L << 22)) cap = v / 128 * 128;
-  }
+  int64_t cap = h->env.pred_batch;
   if (may_shrink) {
     size_t freeb = 0, totalb = 0;
     if (hipMemGetInfo(&freeb, &totalb) == hipSuccess) {
@@ -1013,19 +988,23 @@ int64_t pred_batch_rows(gpx_handle* h, int64_t Mpad, size_t row_bytes, bool may_
 // weigh half as much, 72.4 against 71.7 TF) and of block steps of the variance solve: C3 1602-1605 -> 1579-1584 ms, C5 fp32
 // 881 -> 859 ms; equal at N = 16384 ... 32768, slower at N = 8192 where the chain sets the pace (12.5 vs 13.2 ms):
 // tools/r04_nb_sweep.sh, profiles/r04_panel_width.txt.  GPX_NB_WIDE_FROM = rows from which 2048 is used (0: never).
-int auto_panel_width(int64_t Npad) {
-  static const int64_t from = [] {
-    const char* e = getenv("GPX_NB_WIDE_FROM");
-    return e ? (int64_t)atoll(e) : (int64_t)40960;
-  }();
+int auto_panel_width(const gpx_handle* h, int64_t Npad) {
+  const int64_t from = h->env.nb_wide_from;
   return (from > 0 && Npad >= from) ? 2048 : 1024;
 }
 
 // ---- stages every entry point is built from --------------------------------------------------------
-// None of them reads the environment, allocates beyond the ensure() it names or synchronises beyond what it says.
+// None of them reads the environment — begin_call has taken the call's snapshot of it, h->env, and that is what they and
+// everything below them consult — allocates beyond the ensure() it names or synchronises beyond what it says.
 
-// the start of a call on a single-device handle
+// The call entries of the environment (gpx_env.h) into the handle: by begin_call — the rank handles of a device group
+// and handles with a communicator come through it as well (their entry points are the single-device ones) — and by
+// the three places that enqueue without it: gpx_get_alpha, the unit-test entry points' Scratch, create_group.
+void refresh_env(gpx_handle* h) { env_read(h->env, EnvAt::call); }
+
+// the start of a call on one handle (a single-device one, a rank of a device group, one with a communicator)
 int begin_call(gpx_handle* h) {
+  refresh_env(h);
   HIPCHK(h, hipSetDevice(h->cfg.device));
   h->err.clear();
   h->phases.clear();  // an earlier call that failed mid-way must not leak its event pairs
@@ -1159,8 +1138,8 @@ int fit_impl(gpx_handle* h, const void* X, const void* y, int64_t N, int32_t d, 
   const int64_t capN = h->reserve > 0 ? cap : N;
   const int64_t ld = cap + ld_skew<T>();
   if (h->cfg.block == 0) {  // the library's choice; predict's block solves use the fit's block inverses: same width
-    h->nb = auto_panel_width(Npad);
-    if (!h->nb_pred_env) h->nb_pred = h->nb;
+    h->nb = auto_panel_width(h, Npad);
+    if (h->env.nb_pred < 0) h->nb_pred = h->nb;
   }
   const int64_t ldp = h->nb + ld_skew<T>();
   h->N = N; h->Npad = Npad; h->ld = ld; h->ldp = ldp; h->d = d; h->k = k; h->n_ls = n_ls;
@@ -1251,11 +1230,8 @@ int fit_impl(gpx_handle* h, const void* X, const void* y, int64_t N, int32_t d, 
     // wait_counter_kernel gave up although the self-test passed (a tool attached later, or one that reorders rather than
     // serialises): this handle hands over by hipEvents from now on and the fit runs once more — same kernels, same bits.
     // Only a forced GPX_CHAIN_FLAG=1, or a second failure, is an error.
-    if (!retried && !getenv("GPX_CHAIN_FLAG") && h->flag_ok != 0) {
-      h->flag_ok = 0;
-      h->flag_retries += 1;
+    if (retry_with_events(h, retried))
       return fit_impl<T>(h, X, y, N, d, k, lengthscale, n_ls, sf2, sn2, jitter, mem_kind, info, Xq, M, true);
-    }
     return fail(h, GPX_E_HIP,
                 "a stream parked on a device flag timed out: kernels are being serialised across streams — "
                 "set GPX_CHAIN_FLAG=0 (and leave GPX_FUSED_STRIP unset) to hand over by hipEvents instead");
@@ -1443,12 +1419,10 @@ int append_impl(gpx_handle* h, const void* Xnew, const void* ynew, int64_t m, in
     for (int attempt = 0;; ++attempt) {
       int r = append_restart<T>(h, Nold, n1, Xa, ya, mem_kind, hinfo);
       if (r != GPX_OK || *hinfo >= 0) return r;
-      if (attempt > 0 || getenv("GPX_CHAIN_FLAG") || h->flag_ok == 0)
+      if (!retry_with_events(h, attempt > 0))
         return fail(h, GPX_E_HIP,
                     "a stream parked on a device flag timed out: kernels are being serialised across streams — "
                     "set GPX_CHAIN_FLAG=0 (and leave GPX_FUSED_STRIP unset) to hand over by hipEvents instead");
-      h->flag_ok = 0;
-      h->flag_retries += 1;
       if ((r = begin_call(h))) return r;
     }
   };
@@ -1508,8 +1482,7 @@ int solve_few(gpx_handle* h, T* RT, int k, const T* L, int64_t ld, int64_t n, co
 // an unsharded fit, or of a shard that keeps the whole factor), at most 8 right-hand sides (GPX_FEW_SOLVE=0: always the
 // slab path)
 bool few_solver_applies(const gpx_handle* h) {
-  const char* e = getenv("GPX_FEW_SOLVE");
-  return (!e || atoi(e) != 0) && h->nbw > 0 && (h->nbw <= 1024 ? h->nbw % 128 == 0 : h->nbw % 1024 == 0) && h->k <= 8 &&
+  return h->env.few_solve && h->nbw > 0 && (h->nbw <= 1024 ? h->nbw % 128 == 0 : h->nbw % 1024 == 0) && h->k <= 8 &&
          (!h->comm || h->repl) && h->Wblk.p;
 }
 
@@ -2152,11 +2125,7 @@ int lml_grad_impl(gpx_handle* h, double* lml, double* grad) {
   Comm* cm = h->comm;
   const int P = cm ? cm->world : 1, rank = cm ? cm->rank : 0;
   // the gradient's sweeps keep their measured 1024-blocks whatever the fit's panel width (GPX_NB_GRAD overrides: A/B)
-  const int nb = [&] {
-    const char* e = getenv("GPX_NB_GRAD");
-    const int v = e ? atoi(e) : 0;
-    return (v >= 128 && v <= 4096 && v % 128 == 0) ? v : std::min(h->nb_pred, 1024);
-  }();
+  const int nb = h->env.nb_grad ? h->env.nb_grad : std::min(h->nb_pred, 1024);
   gpx_timings& tm = h->tm;
   tm.grad_trtri = tm.grad_trace = tm.grad_total = 0;
   const int64_t s1n = kinv_trace_slots(Npad), s2n = alpha_quad_slots(Npad);
@@ -2505,17 +2474,9 @@ int gpx_create(gpx_handle** out, const gpx_config* cfg) try {
   h->cfg.device = device;
   h->nb = nb;
   h->refine = cfg->refine;  // 0: adaptive
-  if (const char* e = getenv("GPX_NB_SHARD")) h->nb_shard_env = atoi(e);
-  if (h->nb_shard_env < 128 || h->nb_shard_env > 2048 || h->nb_shard_env % 128 != 0) h->nb_shard_env = 0;
-  // tuning overrides; anything that is not a multiple of 128 in [128, 2048] is ignored
-  auto block_env = [](const char* name, int dflt) {
-    const char* e = getenv(name);
-    const int v = e ? atoi(e) : dflt;
-    return (v >= 128 && v <= 4096 && v % 128 == 0) ? v : dflt;
-  };
-  h->nb_solve = block_env("GPX_NB_SOLVE", h->nb_solve);
-  h->nb_pred = block_env("GPX_NB_PRED", h->nb_pred);
-  h->nb_pred_env = getenv("GPX_NB_PRED") != nullptr;
+  env_read(h->env, EnvAt::create);  // tuning overrides: GPX_NB_SHARD, GPX_NB_SOLVE, GPX_NB_PRED (gpx_env.h)
+  h->nb_solve = h->env.nb_solve;
+  if (h->env.nb_pred >= 0) h->nb_pred = h->env.nb_pred;
   int prio_lo = 0, prio_hi = 0;
   if (hipSetDevice(device) != hipSuccess ||
       hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi) != hipSuccess ||
@@ -2557,6 +2518,25 @@ int check_fit_args(gpx_handle* h, const char* fn, bool with_queries, bool any_nu
   if (N > (int64_t)INT_MAX - 4096) return bad("N too large");
   return GPX_OK;
 }
+
+// gpx_fit on one handle, behind its argument checks and begin_fit
+int fit_begun(gpx_handle* h, const void* X, const void* y, int64_t N, int32_t d, int32_t k, const double* lengthscale,
+              int32_t n_ls, double sf2, double sn2, double jitter, int32_t mem_kind, int64_t* info) {
+  if (h->cfg.dtype == GPX_MIXED) return mixed_fit(h, X, y, N, d, k, lengthscale, n_ls, sf2, sn2, jitter, mem_kind, info);
+  if (h->cfg.world > 1 || h->comm)  // a 1-rank communicator also takes the sharded schedule
+    return BY_DTYPE(h, shard_fit, h, X, y, N, d, k, lengthscale, n_ls, sf2, sn2, jitter, mem_kind, info);
+  return BY_DTYPE(h, fit_impl, h, X, y, N, d, k, lengthscale, n_ls, sf2, sn2, jitter, mem_kind, info);
+}
+
+// gpx_fit_predict on a handle with a communicator: do the query rows ride through the sharded factorisation, as bordered
+// rows of every rank's local row set?  In the split schedule only (GPX_SPLIT_STRIP), up to 8192 rows per rank, unless
+// GPX_SHARD_FUSED=0.  Decided here, once per call, from the call's snapshot; shard_fit relies on it (query rows that reach
+// it outside the split schedule are GPX_E_UNSUPPORTED).
+bool queries_ride_through_shard(const gpx_handle* h, int64_t M) {
+  if (!h->comm || h->cfg.dtype == GPX_MIXED || !h->env.split_strip || !h->env.shard_fused) return false;
+  const int P = h->comm->world;
+  return round_up((M + P - 1) / P, TILE) <= 8192;
+}
 }  // namespace
 
 int gpx_fit(gpx_handle* h, const void* X, const void* y, int64_t N, int32_t d, int32_t k,
@@ -2569,10 +2549,7 @@ int gpx_fit(gpx_handle* h, const void* X, const void* y, int64_t N, int32_t d, i
     return rc;
   if (h->group) return group_fit(h, X, y, N, d, k, lengthscale, n_ls, sf2, sn2, jitter, mem_kind, info);
   if ((rc = begin_fit(h))) return rc;
-  if (h->cfg.dtype == GPX_MIXED) return mixed_fit(h, X, y, N, d, k, lengthscale, n_ls, sf2, sn2, jitter, mem_kind, info);
-  if (h->cfg.world > 1 || h->comm)  // a 1-rank communicator also takes the sharded schedule
-    return BY_DTYPE(h, shard_fit, h, X, y, N, d, k, lengthscale, n_ls, sf2, sn2, jitter, mem_kind, info);
-  return BY_DTYPE(h, fit_impl, h, X, y, N, d, k, lengthscale, n_ls, sf2, sn2, jitter, mem_kind, info);
+  return fit_begun(h, X, y, N, d, k, lengthscale, n_ls, sf2, sn2, jitter, mem_kind, info);
 }
 GPX_CATCH_ALL
 
@@ -2589,18 +2566,13 @@ int gpx_fit_predict(gpx_handle* h, const void* X, const void* y, int64_t N, int3
   // its local row set (shard_fit with query points + shard_fused_tail) — in the split schedule, up to 8192 rows per rank.
   // Otherwise, and in the mixed mode (its refinement needs the factor first), the call IS the two calls (same results;
   // ABI v5 — it was GPX_E_UNSUPPORTED).  *info > 0: not positive definite, nothing predicted.
+  if ((rc = begin_fit(h))) return rc;  // (the call's snapshot of the environment: what is decided below reads it)
   if (h->cfg.world > 1 || h->comm || h->cfg.dtype == GPX_MIXED) {
-    const char* se = getenv("GPX_SPLIT_STRIP");
-    const char* fe = getenv("GPX_SHARD_FUSED");
-    const int P = h->comm ? h->comm->world : 1;
-    const bool ride = h->comm && h->cfg.dtype != GPX_MIXED && (!se || atoi(se) != 0) && (!fe || atoi(fe) != 0) &&
-                      round_up((M + P - 1) / P, TILE) <= 8192;
-    if (!ride) {
-      rc = gpx_fit(h, X, y, N, d, k, lengthscale, n_ls, sf2, sn2, jitter, mem_kind, info);
+    if (!queries_ride_through_shard(h, M)) {
+      rc = fit_begun(h, X, y, N, d, k, lengthscale, n_ls, sf2, sn2, jitter, mem_kind, info);
       if (rc != GPX_OK || *info != 0) return rc;
       return gpx_predict(h, Xq, M, mean, var, mem_kind);
     }
-    if ((rc = begin_fit(h))) return rc;
     rc = BY_DTYPE(h, shard_fit, h, X, y, N, d, k, lengthscale, n_ls, sf2, sn2, jitter, mem_kind, info, false, Xq, M);
     if (rc != GPX_OK || !h->fitted) return rc;
     return BY_DTYPE(h, shard_fused_tail, h, M, mean, var, mem_kind);
@@ -2609,7 +2581,6 @@ int gpx_fit_predict(gpx_handle* h, const void* X, const void* y, int64_t N, int3
   // first batch rides, the others go through the ordinary predict against the factor the pass leaves behind — query
   // rows are independent, so the split changes no bit of either part
   const int64_t Mb = std::min<int64_t>(M, pred_batch_rows(h, round_up(M, TILE), 0, false));
-  if ((rc = begin_fit(h))) return rc;
   const size_t es = h->cfg.dtype == GPX_F32 ? sizeof(float) : sizeof(double);
   rc = BY_DTYPE(h, fit_impl, h, X, y, N, d, k, lengthscale, n_ls, sf2, sn2, jitter, mem_kind, info, Xq, Mb);
   if (rc != GPX_OK || !h->fitted) return rc;  // *info > 0: not positive definite, nothing predicted
@@ -2768,6 +2739,7 @@ int gpx_get_alpha(gpx_handle* h, void* out) try {
     if (rc != GPX_OK) h->err = m0->err;
     return rc;
   }
+  refresh_env(h);  // (not begin_call: the clocks and the message of the call before stay)
   HIPCHK(h, hipSetDevice(h->cfg.device));
   if (h->cfg.dtype == GPX_MIXED) return mixed_alpha(h, out);
   return BY_DTYPE(h, alpha_impl, h, out);
@@ -2835,6 +2807,7 @@ struct Scratch {  // a throw-away handle-like context for the host-buffer entry 
   bool ok = false;
   Scratch() {
     int dev = 0;
+    refresh_env(&h);  // the schedulers a unit-test entry point runs read h.env like any call
     if (hipGetDevice(&dev) != hipSuccess) return;
     h.cfg.device = dev;
     ok = hipStreamCreateWithFlags(&h.st, hipStreamNonBlocking) == hipSuccess &&
@@ -3236,6 +3209,13 @@ int gpx_debug_deal(int32_t P, int32_t snake, int64_t nblk, int32_t* owner, int64
 }
 GPX_CATCH_ALL
 
+int gpx_debug_env(char* buf, int32_t n) try {
+  EnvKnobs env;  // a fresh snapshot of every moment; the create entries as gpx_create resolves them
+  for (EnvAt at : {EnvAt::create, EnvAt::call, EnvAt::process}) env_read(env, at);
+  return env_print(env, buf, n);
+}
+GPX_CATCH_ALL
+
 int gpx_microbench(double* mfma_tflops, double* copy_gbs) try {
   if (!mfma_tflops || !copy_gbs) return GPX_E_ARG;
   Scratch sc;
@@ -3245,12 +3225,9 @@ int gpx_microbench(double* mfma_tflops, double* copy_gbs) try {
   hipEvent_t e0 = nullptr, e1 = nullptr;
   const int64_t count = (int64_t)1 << 28;  // 2 GiB per buffer
   const int64_t skew = 0;  // (round 3: a skewed destination measured slower than an aligned one: tools/copy_bw.hip)
-  int iters = 65536;  // ~0.23 s: long enough to be past the clock ramp (a 14 ms loop read 75 TF,
-                      // the sustained rate is 77.8); GPX_MICROBENCH_ITERS overrides
-  if (const char* e = getenv("GPX_MICROBENCH_ITERS")) {
-    const long v = atol(e);
-    if (v >= 64 && v <= (1L << 20)) iters = (int)v;
-  }
+  // 65536 iterations, ~0.23 s: long enough to be past the clock ramp (a 14 ms loop read 75 TF, the sustained rate is
+  // 77.8); GPX_MICROBENCH_ITERS overrides
+  const int iters = sc.h.env.microbench_iters;
   const int blocks = 256 * 8;
   float ms = 0.f;
   int rc = GPX_OK;

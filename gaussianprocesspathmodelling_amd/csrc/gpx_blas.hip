@@ -1037,6 +1037,7 @@ struct ReserveState {
   int k = 0;
   unsigned* ring = nullptr;  // [cap][8] counters, zeroed by the caller before the first launch of a fit
   int cap = 0, used = 0;
+  int form = 1;              // grid of the self-reserving launches: 1 turnover, 0 persistent (GPX_RESV_FORM; launch_gemm_nt_t)
   int chain = 0;             // narrow slab launches of the chain ask for a whole CU's worth of LDS (see launch_trsm_rlt)
 };
 thread_local ReserveState g_resv;
@@ -1087,10 +1088,7 @@ void launch_gemm_nt_t(T* C, int64_t ldc, const T* A, int64_t lda, const T* B, in
   // once there) and a tail of persistent "sweepers" that finish whatever the burnt ones left.  0, "persistent": about
   // as many workgroups as the chip has slots, all looping (measured: the chain's wide launches then only get the
   // reserved CUs until the update retires — C2 13.3 against 12.5 ms).
-  static const int form = [] {
-    const char* e = getenv("GPX_RESV_FORM");
-    return e ? atoi(e) : 1;
-  }();
+  const int form = g_resv.form;
   unsigned sweep0 = 0;
   auto resv_grid = [&](int64_t total) {
     const int per_cu = BT == 128 ? 2 : (ks == 4 ? 1 : ks == 2 ? 2 : 4);
@@ -1170,8 +1168,9 @@ void launch_gemm_nt_t(T* C, int64_t ldc, const T* A, int64_t lda, const T* B, in
 // A launcher that refuses its operands (the 128-byte row alignment trsm_rlt_kernel depends on)
 // launches nothing and raises this flag; every API entry point turns it into an error return.
 void set_latency_mode(int on) { g_latency_mode = on; }
-void reserve_ring(unsigned* ring, int cap) {
+void reserve_ring(unsigned* ring, int cap, int form) {
   g_resv.ring = ring;
+  g_resv.form = form;
   g_resv.cap = ring ? cap : 0;
   g_resv.used = 0;
   g_resv.k = 0;

@@ -95,6 +95,7 @@ int create_group(gpx_handle** out, const gpx_config* cfg) {
   }
   g->cfg = *cfg;
   g->group = G;
+  refresh_env(g);  // (GPX_GROUP_INITALL below)
   G->transport = transport;
   int rc = GPX_OK;
   try {
@@ -150,10 +151,9 @@ int create_group(gpx_handle** out, const gpx_config* cfg) {
       // One communicator per device, created from this thread: ncclCommInitAll (default), or P grouped
       // ncclCommInitRank calls on one unique id (GPX_GROUP_INITALL=0) — the creation style of the
       // one-process-per-GPU shard (gpx_comm_init).  Both are exercised by the one-rank group tests.
-      const char* e = getenv("GPX_GROUP_INITALL");
       int nrc = 0;
       const char* what = "ncclCommInitAll";
-      if (!e || atoi(e) != 0) {
+      if (g->env.group_initall) {
         nrc = api->CommInitAll(comms, P, devs);
       } else {
         what = "grouped ncclCommInitRank";

@@ -90,7 +90,9 @@ RcclApi* rccl_api(std::string* err) {
   // BEFORE importing torch aborts at exit (static destructors: "double free or corruption", round 3,
   // tools/rccl_exit_probe.py), so the Python host imports torch and points GPX_RCCL_PATH at its copy
   // before the first RCCL use (_abi.prefer_torch_rccl).
-  const char* names[] = {getenv("GPX_RCCL_PATH"), "librccl.so.1", "librccl.so"};
+  EnvKnobs env;
+  env_read(env, EnvAt::process);
+  const char* names[] = {env.rccl_path, "librccl.so.1", "librccl.so"};
   for (const char* n : names) {
     if (!n || !*n) continue;
     api.lib = dlopen(n, RTLD_NOW | RTLD_GLOBAL | RTLD_NOLOAD);
@@ -334,11 +336,7 @@ struct LocalComm : Comm {
     LCHK(hipStreamWaitEvent(st, hub->pub[q].ev, 0));
     // (GPX_LOCAL_FORCE_PEER=1, test hook: the peer-copy call also between ranks that share a device — the only way a
     //  one-GPU box executes that line at all; with equal ordinals it is an ordinary copy)
-    static const bool force_peer = [] {
-      const char* e = getenv("GPX_LOCAL_FORCE_PEER");
-      return e && atoi(e) != 0;
-    }();
-    if (hub->dev[q] == hub->dev[rank] && !force_peer)
+    if (hub->dev[q] == hub->dev[rank] && !h->env.local_force_peer)
       LCHK(hipMemcpyAsync(dst, hub->pub[q].ptr, bytes, hipMemcpyDeviceToDevice, st));
     else
       LCHK(hipMemcpyPeerAsync(dst, hub->dev[rank], hub->pub[q].ptr, hub->dev[q], bytes, st));
@@ -449,12 +447,6 @@ struct Shard {
     return bc;
   }
 };
-// which dealing a fit uses: read per fit (tests switch it), kept in the handle for everything that follows the fit
-inline int shard_deal_env() {
-  const char* e = getenv("GPX_SHARD_DEAL");
-  return (e && (strcmp(e, "cyclic") == 0 || strcmp(e, "0") == 0)) ? 0 : 1;
-}
-
 #define COMMCHK(expr)                 \
   do {                                \
     int rc_ = (expr);                 \
@@ -542,10 +534,11 @@ int shard_fit(gpx_handle* h, const void* X, const void* y, int64_t N, int32_t d,
   // 16 blocks per rank, 17 % at 8); snake dealing (round 4): 0.65 % / 2.6 % in the same cases, so 8 blocks per rank
   // are enough — 1024 up to N / (8 P), down to 256 (tools/scaling_model.py: P = 8, N = 65536: fit 235 -> 223 -> 212 ms
   // for cyclic 512 / snake 512 / snake 1024).
-  const int snake = shard_deal_env();
+  const EnvKnobs& env = h->env;  // the call's snapshot (gpx_env.h): nothing below reads the environment
+  const int snake = env.shard_snake;  // the dealing: per fit (tests switch it), kept in the handle for everything that follows the fit
   int nb = 1024;
   while (nb > 256 && (int64_t)nb * (snake ? 8 : 16) * cm->world > N) nb >>= 1;
-  if (h->nb_shard_env) nb = h->nb_shard_env;
+  if (env.nb_shard) nb = env.nb_shard;
   h->nb_shard = nb;
   Shard sh{cm->world, cm->rank, nb, 0};
   sh.snake = h->shard_snake = snake;
@@ -603,16 +596,14 @@ int shard_fit(gpx_handle* h, const void* X, const void* y, int64_t N, int32_t d,
     size_t freeb = 0, totalb = 0;
     HIPCHK(h, hipMemGetInfo(&freeb, &totalb));
     h->repl = (double)(Npad + RHS_ROWS) * (double)ld * (double)sizeof(T) <= 0.35 * (double)totalb;
-    if (const char* e = getenv("GPX_SHARD_REPLICATE")) h->repl = atoi(e) != 0;
+    if (env.shard_replicate >= 0) h->repl = env.shard_replicate != 0;
   }
   const bool repl = h->repl;
   // replicated factor + dense panel solves: every rank also keeps the explicit block inverses W_p that pass through it
   // with the diagonal blocks (N nb doubles: 0.5 GB at N = 65536, nb = 1024), for the streaming few-right-hand-side solver
   // and predict's dense block solves — what the unsharded handle has in Wblk
-  const bool keep_w = repl && [] {
-    const char* e = getenv("GPX_SHARD_DENSE_PANEL");
-    return !e || atoi(e) != 0;
-  }();
+  const bool dense_panel = env.shard_dense_panel;
+  const bool keep_w = repl && dense_panel;
   h->nbw = 0;  // valid again once this fit has finished
   if (keep_w && (rc = ensure(h, h->Wblk, (size_t)sh.nblk * nb * nb * sizeof(T)))) return rc;
   if (repl) {
@@ -697,20 +688,12 @@ int shard_fit(gpx_handle* h, const void* X, const void* y, int64_t N, int32_t d,
       // the exchange path that bounds the factorisation at P = 8 (at the price of nb^2 more doubles
       // per broadcast); which one wins on real xGMI hardware is unmeasured (one-GPU rehearsals, where
       // the ranks hide each other's latency chains, favour the slab form by 5-25 %).
-      const char* dp_env = getenv("GPX_SHARD_DENSE_PANEL");
-      const bool dense_panel = !dp_env || atoi(dp_env) != 0;
-      const bool split_env_early = [] {  // (the split schedule's switch, read again below; the two pipelines belong to it)
-        const char* e = getenv("GPX_SPLIT_STRIP");
-        return !e || atoi(e) != 0;
-      }();
+      // (GPX_SHARD_DENSE_PANEL: dense_panel above)
       hipEvent_t e_copied[2] = {nullptr, nullptr};  // copy-back of the panel last written into Ploc[set]
       hipEvent_t e_lcopy[2] = {nullptr, nullptr};   // replicated factor: the copy of the panel last gathered into GB[set]
       // Replicated factor: the gathered panel goes into the full copy on the COPY stream, beside the REST (HBM work beside
       // MFMA work) instead of in front of it on the main stream (GPX_REPL_COPY_SIDE=0: A/B)
-      const bool side_copy = [] {
-        const char* e = getenv("GPX_REPL_COPY_SIDE");
-        return !e || atoi(e) != 0;
-      }();
+      const bool side_copy = env.repl_copy_side;
       // TWO PIPELINES (round 4): the owner of the next diagonal block runs its update (STRIP_D) and the block's chain on a
       // stream of their own (sd), right behind ITS solve of the panel — beside the all-gather of that panel on s1 instead
       // of behind it.  Per panel the cycle solve -> all-gather -> STRIP_D -> diagonal chain -> broadcast -> solve becomes
@@ -719,10 +702,8 @@ int shard_fit(gpx_handle* h, const void* X, const void* y, int64_t N, int32_t d,
       // Default: from 4 ranks on.  On ONE card it cannot pay (the "all-gather" of one rank is a local copy that then runs
       // beside the chain: fit 1393 -> 1400 ms; four ranks sharing the card: equal within noise — profiles/r04_two_pipelines.txt);
       // what it is worth over xGMI is the model's (tools/scaling_model.py), unmeasured.  GPX_SHARD_TWO_PIPE=0 / 1 forces it.
-      const bool two_pipe = [&] {
-        const char* e = getenv("GPX_SHARD_TWO_PIPE");
-        return e ? atoi(e) != 0 : sh.P >= 4;
-      }() && split_env_early;
+      const bool split_env = env.split_strip;  // (on a shard there is no fused strip; the two pipelines belong to the split schedule)
+      const bool two_pipe = (env.shard_two_pipe >= 0 ? env.shard_two_pipe != 0 : sh.P >= 4) && split_env;
       if (two_pipe && !h->st5) {
         int lo = 0, hi = 0;
         HIPCHK(h, hipDeviceGetStreamPriorityRange(&lo, &hi));
@@ -766,10 +747,7 @@ int shard_fit(gpx_handle* h, const void* X, const void* y, int64_t N, int32_t d,
                                    (size_t)nb * KB * sizeof(T), hipMemcpyDeviceToDevice, sdx));
           if (below) HIPCHK(h, hipStreamWaitEvent(sdx, iw.ready, 0));
           if (sdx != sx) {  // the block joins the exchange stream in front of its broadcast
-            hipEvent_t e_diag = next_event(h);
-            if (!e_diag) return fail(h, GPX_E_HIP, "hipEventCreate failed (diagonal chain)");
-            HIPCHK(h, hipEventRecord(e_diag, sdx));
-            HIPCHK(h, hipStreamWaitEvent(sx, e_diag, 0));
+            COMMCHK(stream_waits(h, sx, sdx, "diagonal chain"));
           }
         }
         if (last && !repl && !ride) return GPX_OK;  // last block: nothing below it
@@ -800,20 +778,12 @@ int shard_fit(gpx_handle* h, const void* X, const void* y, int64_t N, int32_t d,
           T* Arows = A + lb0 * nb * ld + o;
           if (e_copied[set]) HIPCHK(h, hipStreamWaitEvent(sx, e_copied[set], 0));  // Ploc[set] is free again
           launch_gemm_nt<T>(128, PlocB[set], ldp, Arows, ld, Wp, nb, rows, nb, nb, 4, 1, sx);
-          hipEvent_t e = next_event(h);
-          if (!e) return fail(h, GPX_E_HIP, "hipEventCreate failed (panel copy)");
-          HIPCHK(h, hipEventRecord(e, sx));
-          HIPCHK(h, hipStreamWaitEvent(h->st4, e, 0));
+          COMMCHK(stream_waits(h, h->st4, sx, "panel copy"));
           launch_copy2d<T>(Arows, ld, PlocB[set], ldp, rows, nb, h->st4);
-          e_copied[set] = next_event(h);
-          if (!e_copied[set]) return fail(h, GPX_E_HIP, "hipEventCreate failed (panel copy)");
-          HIPCHK(h, hipEventRecord(e_copied[set], h->st4));
+          COMMCHK(record_event(h, h->st4, "panel copy", &e_copied[set]));
         }
-        if (two_pipe) {  // "this rank's rows of panel p are solved" — what the next diagonal block's update waits for
-          e_solved[set] = next_event(h);
-          if (!e_solved[set]) return fail(h, GPX_E_HIP, "hipEventCreate failed (panel solve)");
-          HIPCHK(h, hipEventRecord(e_solved[set], sx));
-        }
+        // "this rank's rows of panel p are solved" — what the next diagonal block's update waits for
+        if (two_pipe) COMMCHK(record_event(h, sx, "panel solve", &e_solved[set]));
         if (last) return GPX_OK;  // (only bordered rows below the last block: nobody's operand)
         const int64_t mc = sh.maxcnt(p);
         if (e_lcopy[set]) HIPCHK(h, hipStreamWaitEvent(sx, e_lcopy[set], 0));  // GB[set] is free again
@@ -836,14 +806,7 @@ int shard_fit(gpx_handle* h, const void* X, const void* y, int64_t N, int32_t d,
       //     over as a launch of its own: REST_A -> e_main(p) -> REST_B, so that the next STRIP_D never waits for the bulk.
       // Round 3 ran the whole STRIP on the main stream first and started the chain behind it (GPX_SPLIT_STRIP=0 keeps that
       // form: A/B and bit-identity tests): a step was STRIP + max(REST, chain); now it is max(STRIP_B + REST, chain).
-      const bool split_env = [] {  // read per call (tests switch it)
-        const char* e = getenv("GPX_SPLIT_STRIP");
-        return !e || atoi(e) != 0;
-      }();
-      const int rest_split = [] {  // as chol_enqueue: trailing rows (in panels, per sqrt(P)) up to which the REST is split
-        const char* e = getenv("GPX_REST_SPLIT");
-        return e ? atoi(e) : 16;
-      }();
+      const int rest_split = env.rest_split;  // as chol_enqueue: trailing rows (in panels, per sqrt(P)) up to which the REST is split
       // first row of block g (> q) in the gathered panel q: rank-major pieces of maxcnt(q) rows, each rank's own blocks
       // beyond q in order (what bc_brow computes per tile column inside the staircase kernel)
       auto grow = [&](int64_t q, int64_t g) -> int64_t {
@@ -852,11 +815,7 @@ int shard_fit(gpx_handle* h, const void* X, const void* y, int64_t N, int32_t d,
       };
       COMMCHK(panel(0, 0, s0, nullptr));
       hipEvent_t e_main = nullptr;  // "this rank's updates of the trailing matrix that touch the next diagonal block are complete"
-      if (split_env && sh.nblk > 1) {
-        e_main = next_event(h);
-        if (!e_main) return fail(h, GPX_E_HIP, "hipEventCreate failed (look-ahead)");
-        HIPCHK(h, hipEventRecord(e_main, s0));
-      }
+      if (split_env && sh.nblk > 1) COMMCHK(record_event(h, s0, "look-ahead", &e_main));
       for (int64_t p = 0; p + 1 < sh.nblk; ++p) {
         const int cur = (int)(p & 1), nxt = cur ^ 1;
         const int64_t lb0 = sh.lb0(p, sh.r), rows = nloc - lb0 * nb;
@@ -881,18 +840,13 @@ int shard_fit(gpx_handle* h, const void* X, const void* y, int64_t N, int32_t d,
             launch_gemm_nt<T>(128, A + lb1 * nb * ld + (p + 1) * nb, ld, PlocB[cur] + (lb1 - lb0) * nb * ldp, ldp,
                                    GB[cur] + grow(p, p + 1) * ldp, ldp, rows1 + Mq, (int64_t)nb, nb, 0, 0, s0);
           }
-          hipEvent_t e_below = next_event(h);
-          if (!e_below) return fail(h, GPX_E_HIP, "hipEventCreate failed (look-ahead)");
-          HIPCHK(h, hipEventRecord(e_below, s0));
+          hipEvent_t e_below;
+          COMMCHK(record_event(h, s0, "look-ahead", &e_below));
           if (repl) {  // panel p into the full factor (un-permuted on the way): off the panel chain
             hipStream_t sc = side_copy ? h->st4 : s0;
             if (side_copy) HIPCHK(h, hipStreamWaitEvent(sc, e_below, 0));  // (s0 waited for the gathered panel p before)
             launch_unpermute_panel(GB[cur], ldp, Lfull + (p + 1) * nb * ld + p * nb, ld, nb, sh.deal(), (int)p, (int)sh.nblk, mcp, sc);
-            if (side_copy) {
-              e_lcopy[cur] = next_event(h);
-              if (!e_lcopy[cur]) return fail(h, GPX_E_HIP, "hipEventCreate failed (panel copy)");
-              HIPCHK(h, hipEventRecord(e_lcopy[cur], sc));
-            }
+            if (side_copy) COMMCHK(record_event(h, sc, "panel copy", &e_lcopy[cur]));
           }
           // REST: own rows beyond block p+1 x columns beyond it (block-cyclic staircase).  The panel buffers it reads are
           // rewritten two panel solves later, behind e_below(p+1) of this stream, i.e. behind all of this update.
@@ -904,11 +858,7 @@ int shard_fit(gpx_handle* h, const void* X, const void* y, int64_t N, int32_t d,
             launch_gemm_nt_bc(A + lb1 * nb * ld + (p + 2) * nb, ld, PlocB[cur] + (lb1 - lb0) * nb * ldp, ldp,
                               GB[cur], ldp, rows1 + Mq, (int64_t)nb, nb, sh.mask(tpb, lb1, p + 2, p, mcp), s0);
           }
-          if (ahead) {
-            e_main = next_event(h);
-            if (!e_main) return fail(h, GPX_E_HIP, "hipEventCreate failed (look-ahead)");
-            HIPCHK(h, hipEventRecord(e_main, s0));
-          }
+          if (ahead) COMMCHK(record_event(h, s0, "look-ahead", &e_main));
           if (ahead) {  // REST_B: own rows beyond block p+2 x columns beyond it
             const int64_t lb2 = sh.lb0(p + 2, sh.r), rows2 = nloc - lb2 * nb;
             if (rows2 + Mq > 0 && nrest - nb > 0) {
@@ -924,9 +874,7 @@ int shard_fit(gpx_handle* h, const void* X, const void* y, int64_t N, int32_t d,
                                 GB[cur], ldp, rows1 + Mq, nrest, nb, sh.mask(tpb, lb1, p + 2, p, mcp), s0);
               tm.syrk_launches += 1;
             }
-            e_main = next_event(h);
-            if (!e_main) return fail(h, GPX_E_HIP, "hipEventCreate failed (look-ahead)");
-            HIPCHK(h, hipEventRecord(e_main, s0));
+            COMMCHK(record_event(h, s0, "look-ahead", &e_main));
           }
           COMMCHK(panel(p + 1, nxt, s1, e_below));
           HIPCHK(h, hipEventRecord(e_panel, s1));
@@ -939,10 +887,7 @@ int shard_fit(gpx_handle* h, const void* X, const void* y, int64_t N, int32_t d,
           launch_gemm_nt_bc(A + lb0 * nb * ld + (p + 1) * nb, ld, PlocB[cur], ldp, GB[cur], ldp, rows,
                             (int64_t)nb, nb, sh.mask(tpb, lb0, p + 1, p, mcp), s0);
         }
-        hipEvent_t e_strip = next_event(h);
-        if (!e_strip) return fail(h, GPX_E_HIP, "hipEventCreate failed (look-ahead)");
-        HIPCHK(h, hipEventRecord(e_strip, s0));
-        HIPCHK(h, hipStreamWaitEvent(s1, e_strip, 0));
+        COMMCHK(stream_waits(h, s1, s0, "look-ahead"));
         if (repl)  // panel p into the full factor: behind the strip, i.e. off the panel chain
           launch_unpermute_panel(GB[cur], ldp, Lfull + (p + 1) * nb * ld + p * nb, ld, nb, sh.deal(), (int)p, (int)sh.nblk, mcp, s0);
         // the host enqueues the REST before the look-ahead chain's dozens of small launches (round 3, as on one
@@ -959,11 +904,7 @@ int shard_fit(gpx_handle* h, const void* X, const void* y, int64_t N, int32_t d,
       }
     }
     for (hipStream_t sj : {h->st3, h->st4, h->st5}) {  // every panel copy-back is in A before anything reads L from it
-      if (!sj) continue;
-      hipEvent_t e = next_event(h);
-      if (!e) return fail(h, GPX_E_HIP, "hipEventCreate failed (join)");
-      HIPCHK(h, hipEventRecord(e, sj));
-      HIPCHK(h, hipStreamWaitEvent(st, e, 0));
+      if (sj) COMMCHK(stream_waits(h, st, sj, "join"));
     }
     if (!repl) {  // alpha = L^-T L^-1 y on the local column layout YTloc (64 x nloc), then replicated in the global layout
       PhaseScope ps(h, &tm.solve);
@@ -977,7 +918,7 @@ int shard_fit(gpx_handle* h, const void* X, const void* y, int64_t N, int32_t d,
       h->nbw = keep_w ? nb : 0;  // the block inverses of this fit are complete on this rank (joined above: st3, and s1 through e_panel)
       // predict's block solves are dense products with them when its block width is theirs: follow the shard's block
       // (512 query rows per rank at nb = 512, P = 8: 46.5 ms dense against 52.8 ms with 1024-wide slab solves — profiles/r04_predict_block_ab.txt)
-      if (keep_w && !h->nb_pred_env) h->nb_pred = nb;
+      if (keep_w && env.nb_pred < 0) h->nb_pred = nb;
       if (few_solver_applies(h)) {  // k <= 8: one stream over the factor with the block inverses (round 4; 18 ms -> ~2 at N = 65536)
         if ((rc = solve_few<T>(h, zT, k, Lfull, ld, Npad, (const T*)h->Wblk.p, nb, true, false))) return rc;
       } else if ((rc = solve_fwd_enqueue<T>(h, zT, RHS_ROWS, Lfull, ld, Npad, h->nb_solve, Winv))) {
@@ -1002,12 +943,9 @@ int shard_fit(gpx_handle* h, const void* X, const void* y, int64_t N, int32_t d,
   COMMCHK(cm->allreduce(h, scal + 1, 1, COMM_MIN));
   HIPCHK(h, hipMemcpyAsync(&dinfo, scal + 1, sizeof(double), hipMemcpyDeviceToHost, st));
   if ((rc = finish_call(h))) return rc;
-  if (dinfo < 0) {  // same decision on every rank: dinfo is all-reduced, the environment is the launch's
-    if (!retried && !getenv("GPX_CHAIN_FLAG")) {
-      h->flag_ok = 0;  // this handle hands over by hipEvents from now on; the fit runs once more (same kernels, same bits)
-      h->flag_retries += 1;
+  if (dinfo < 0) {  // same decision on every rank: dinfo is all-reduced, the environment is the launch's (retry_with_events uses nothing rank-local)
+    if (retry_with_events(h, retried))  // this handle hands over by hipEvents from now on; the fit runs once more (same kernels, same bits)
       return shard_fit<T>(h, X, y, N, d, k, lengthscale, n_ls, sf2, sn2, jitter, mem_kind, info, true, Xq, Mquery);
-    }
     return fail(h, GPX_E_HIP, "a stream parked on a device flag timed out on some rank (kernels serialised across streams? set GPX_CHAIN_FLAG=0)");
   }
   tm.handover_flags = chain_flag_enabled(h) ? 1.0 : 0.0;

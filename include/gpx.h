@@ -399,6 +399,12 @@ int gpx_debug_set_delay(uint64_t seed);
  * k of 32.  One warm-up launch, then the mean of `iters` back-to-back launches in ms. */
 int gpx_debug_gemm_bench(int32_t dtype, int64_t n, int64_t k, int32_t lower, int32_t mode, int32_t iters,
                          double* ms_per_launch);
+/* The environment switches as the library resolves them right now (additive to ABI v6; no device needed, none touched):
+ * a fresh snapshot of every switch of INTEGRATION.md §7 — the ones a handle reads when it is created as gpx_create
+ * would resolve them — as one "NAME=value\n" line each; an unset switch whose default is a rule of its own (tri-states,
+ * GPX_NB_PRED, GPX_RCCL_PATH) prints as "unset".  Writes at most n - 1 characters and a terminating 0 into buf (nothing
+ * when buf is NULL or n <= 0) and returns the length of the whole text, as snprintf does. */
+int gpx_debug_env(char* buf, int32_t n);
 
 #ifdef __cplusplus
 }

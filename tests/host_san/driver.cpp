@@ -11,6 +11,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <string>
 #include <vector>
 
 #include "../../include/gpx.h"
@@ -142,12 +143,40 @@ static void argument_validation() {
   EXPECT(gpx_debug_gemm_bench(GPX_F64, 100, 64, 1, 0, 1, &x) == GPX_E_ARG);
 }
 
+// gpx_debug_env: the one parser of the environment (csrc/gpx_env.h) and its bounded printer
+static void env_snapshot() {
+  const int n = gpx_debug_env(nullptr, 0);
+  EXPECT(n > 0);
+  EXPECT(gpx_debug_env(nullptr, 64) == n);
+  std::vector<char> buf((size_t)n + 1, 'x');
+  EXPECT(gpx_debug_env(buf.data(), 0) == n && buf[0] == 'x');
+  EXPECT(gpx_debug_env(buf.data(), 8) == n && std::strlen(buf.data()) == 7 && buf[8] == 'x');  // too small: cut, terminated
+  EXPECT(gpx_debug_env(buf.data(), n + 1) == n && (int)std::strlen(buf.data()) == n);
+  // an empty and a 4 KiB value for an integer and a boolean switch
+  const std::string digits(4096, '7'), letters(4096, 'y');
+  auto line = [&](const char* want) {
+    std::vector<char> b(8192);
+    const int m = gpx_debug_env(b.data(), (int32_t)b.size());
+    return m > 0 && m < (int)b.size() && std::strstr(b.data(), want) != nullptr;
+  };
+  for (const std::string& v : {std::string(), digits, letters}) {
+    setenv("GPX_PRED_BATCH", v.c_str(), 1);
+    setenv("GPX_SPLIT_STRIP", v.c_str(), 1);
+    EXPECT(line("GPX_PRED_BATCH=8192\n"));  // empty, out of range, not a number: the default
+    EXPECT(line(v == digits ? "GPX_SPLIT_STRIP=1\n" : "GPX_SPLIT_STRIP=0\n"));
+  }
+  unsetenv("GPX_PRED_BATCH");
+  unsetenv("GPX_SPLIT_STRIP");
+  EXPECT(line("GPX_SPLIT_STRIP=1\n"));
+}
+
 int main(int argc, char** argv) {
   const bool tsan = argc > 1 && std::strcmp(argv[1], "tsan") == 0;
   hub_rounds();
   if (!tsan) {
     tile_maps();
     argument_validation();
+    env_snapshot();
   }
   std::printf("host sanitizer driver (%s): %d failed expectation(s)\n", tsan ? "tsan" : "asan+ubsan", fails);
   return fails ? 1 : 0;

@@ -100,3 +100,18 @@ def test_in_process_default_reports_its_handover():
         gp.fit(X, y)
         flags = gp.timings_["handover_flags"]
         assert flags == (0.0 if os.environ.get("GPX_CHAIN_FLAG") == "0" or os.environ.get("ROCPROF_COUNTER_COLLECTION") else 1.0)
+
+
+def test_chain_flag_switched_between_fits_of_one_handle(monkeypatch):
+    """GPX_CHAIN_FLAG is read at the start of every call: the same handle hands over by hipEvents in the fit after it was
+    set to 0 and by device flags again after 1, and the three factorisations (six 256-wide panels) agree bit for bit."""
+    monkeypatch.delenv("GPX_CHAIN_FLAG", raising=False)
+    X, y, _ = synthetic_problem(1536, 2, 8, seed=5)
+    with GP("rbf", 0.25, 1.5, 1e-2, jitter=0.0, block=256) as gp:
+        gp.fit(X, y)
+        first = (gp.alpha_.copy(), gp.log_det_)
+        for value in ("0", "1"):
+            monkeypatch.setenv("GPX_CHAIN_FLAG", value)
+            gp.fit(X, y)
+            assert gp.timings_["handover_flags"] == float(value)
+            assert np.array_equal(gp.alpha_, first[0]) and gp.log_det_ == first[1]
