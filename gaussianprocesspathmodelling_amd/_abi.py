@@ -75,6 +75,11 @@ SIGNATURES = {
                                    C.POINTER(C.c_int64)]),
     "gpx_append": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, C.POINTER(C.c_int64)]),
     "gpx_reserve": (C.c_int, [_P, C.c_int64]),
+    "gpx_set_noise_weights": (C.c_int, [_P, _P, C.c_int64, C.c_int32]),
+    "gpx_get_noise_weights": (C.c_int, [_P, _P]),
+    "gpx_append_weighted": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int32, C.POINTER(C.c_int64)]),
+    "gpx_score_blocks_weighted": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int32, C.c_double, _P, _P, _P, C.c_int32,
+                                            C.POINTER(C.c_int64)]),
     "gpx_factor_info": (C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "gpx_get_alpha": (C.c_int, [_P, _P]),
     "gpx_lml_grad": (C.c_int, [_P, _PD, _PD]),

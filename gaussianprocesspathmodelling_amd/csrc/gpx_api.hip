@@ -2,6 +2,7 @@
 //
 // Implements the fit()/predict() hot path of SURVEY.md §8 (rows a1-a6) on one MI355X:
 //   fit:     K = sf2 k(X,X) + (sn2+jitter) I  ->  blocked Cholesky (in place, lower)
+//            (with gpx_set_noise_weights: + diag(sn2 w_i + jitter) — DESIGN.md §3.4f)
 //            ->  alpha = L^-T L^-1 y  ->  logdet
 //   predict: K* = sf2 k(Xs,X) -> mean = K* alpha -> V^T = K* L^-T -> var = sf2 - rowsumsq(V^T)
 // The reference has no such path (GPmap.py has no fit/predict/linalg beyond
@@ -123,6 +124,7 @@ struct gpx_handle {
     DevBuf GV, GTsol, GMT, GMTpart, GVN, GPart, GOut;
     // block scoring (gpx_score_blocks): targets, per-slice Gram partials, batch mean^T, results + the bad-block word
     DevBuf SY, SPart, SMT, SOut;
+    DevBuf SW;  // gpx_score_blocks_weighted: the query points' weights
   } scr;
   // row-block shard (world > 1)
   Comm* comm = nullptr;  // RCCL, in-process or host-callback transport (gpx_shard.inc)
@@ -155,6 +157,13 @@ struct gpx_handle {
   int flag_ok = -1;
   int flag_retries = 0;  // fits of this handle that were run again with hipEvents after a parked stream timed out
   int64_t reserve = 0;   // gpx_reserve: points the layout of the next fit / append leaves room for (0: what the fit needs)
+  // per-observation noise weights (gpx_set_noise_weights).  Nothing here is allocated, and no kernel
+  // reads any of it, while no weights are set.
+  DevBuf Wset;           // the weights of the next fits, in the handle's element type (double for GPX_MIXED)
+  int64_t nw_set = 0;    // how many (0: none set)
+  DevBuf Wfit, Wfit64;   // the weights of the CURRENT fit: in the fit engine's element type, with room for the layout's
+                         // capacity (appends); GPX_MIXED: and in fp64 (refinement, gpx_get_noise_weights)
+  bool weighted = false; // the current fit was built with Wfit
   // event pool
   std::vector<hipEvent_t> ev_pool;
   size_t ev_used = 0;
@@ -1123,6 +1132,25 @@ int solve_few(gpx_handle* h, T* RT, int k, const T* L, int64_t ld, int64_t n, co
 
 namespace {
 
+// The weights of the fit that begins: a copy of what gpx_set_noise_weights stored (the fit keeps its own: a later
+// gpx_set_noise_weights does not touch it), in the engine's element type T; none set: nothing happens here.
+template <typename T>
+int stage_fit_weights(gpx_handle* h, int64_t N, int64_t cap) {
+  h->weighted = false;
+  if (h->nw_set == 0) return GPX_OK;
+  int rc;
+  if ((rc = ensure(h, h->Wfit, (size_t)cap * sizeof(T)))) return rc;
+  if (h->cfg.dtype == GPX_MIXED) {  // T = float: the fp32 factorisation; the fp64 copy serves the refinement
+    if ((rc = ensure(h, h->Wfit64, (size_t)cap * 8))) return rc;
+    HIPCHK(h, hipMemcpyAsync(h->Wfit64.p, h->Wset.p, (size_t)N * 8, hipMemcpyDeviceToDevice, h->st));
+    launch_f64_to_f32((const double*)h->Wfit64.p, (float*)h->Wfit.p, N, h->st);
+  } else {
+    HIPCHK(h, hipMemcpyAsync(h->Wfit.p, h->Wset.p, (size_t)N * sizeof(T), hipMemcpyDeviceToDevice, h->st));
+  }
+  h->weighted = true;
+  return GPX_OK;
+}
+
 // Xq != null (gpx_fit_predict): the M query points' cross-kernel rows K* ride through the factorisation as
 // bordered rows too — below the right-hand sides — and leave it as
 // V^T = (L^-1 K*^T)^T: the variance solve of predict costs no pass of its own (its M N^2 flops are rows of
@@ -1168,6 +1196,7 @@ int fit_impl(gpx_handle* h, const void* X, const void* y, int64_t N, int32_t d, 
   const int64_t ldu = h->nb + ld_skew<T>();
   if ((rc = ensure(h, h->Wblk, (size_t)nblk * h->nb * h->nb * sizeof(T)))) return rc;
   if ((rc = ensure(h, h->Ublk, (size_t)h->nb * ldu * sizeof(T)))) return rc;
+  if ((rc = stage_fit_weights<T>(h, N, cap))) return rc;
   InvWork<T> iw;
   iw.W = (T*)h->Wblk.p;
   iw.U = (T*)h->Ublk.p;
@@ -1198,8 +1227,11 @@ int fit_impl(gpx_handle* h, const void* X, const void* y, int64_t N, int32_t d, 
       PhaseScope ps(h, &tm.kbuild);
       launch_scale_points<T>((const T*)h->X.p, N, Npad, d, (const double*)h->ls.p, n_ls,
                           (T*)h->Xs.p, h->st);
-      launch_kbuild_sym<T>(h->cfg.kernel, (const T*)h->Xs.p, N, Npad, d, sf2, sn2 + jitter, dK, ld,
-                        h->st);
+      if (h->weighted)
+        launch_kbuild_sym_w<T>(h->cfg.kernel, (const T*)h->Xs.p, N, Npad, d, sf2, (const T*)h->Wfit.p, sn2, jitter, dK, ld,
+                               h->st);
+      else
+        launch_kbuild_sym<T>(h->cfg.kernel, (const T*)h->Xs.p, N, Npad, d, sf2, sn2 + jitter, dK, ld, h->st);
       if (Xq) {  // rows [Npad + RHS_ROWS, ... + Mpad): K(Xq, X)
         if ((rc = upload_queries<T>(h, Xq, M, mem_kind))) return rc;
         launch_kbuild_cross<T>(h->cfg.kernel, (const T*)h->scr.Qs.p, M, Mpad, (const T*)h->Xs.p, N, Npad, d, sf2,
@@ -1254,8 +1286,9 @@ int fit_impl(gpx_handle* h, const void* X, const void* y, int64_t N, int32_t d, 
 // and columns [0, R0) of z^T move into a buffer with room for one more panel width of points (or what gpx_reserve asked
 // for), and the point, block-inverse and panel buffers grow with it.  Every allocation happens before anything is touched:
 // on GPX_E_NOMEM the fit is as it was.
+// with_weights: the fit has noise weights, or the new points bring some — the weight vector follows the same capacity.
 template <typename T>
-int append_room(gpx_handle* h, int64_t Nnew) {
+int append_room(gpx_handle* h, int64_t Nnew, bool with_weights) {
   const int64_t skew = ld_skew<T>(), cap0 = h->ld - skew, NpadNew = round_up(Nnew, TILE), want = round_up(h->reserve, TILE);
   const int64_t N = h->N, Npad = h->Npad, nb = h->nb, d = h->d, k = h->k;
   const bool relayout = NpadNew > cap0 || want > cap0;
@@ -1269,7 +1302,8 @@ int append_room(gpx_handle* h, int64_t Nnew) {
            {&h->Y, (size_t)cap * k * sizeof(T), (size_t)N * k * sizeof(T), {}},
            {&h->Xs, (size_t)cap * d * sizeof(T), (size_t)Npad * d * sizeof(T), {}},
            {&h->Winv, (size_t)(cap / KB) * KB * KB * sizeof(T), (size_t)(Npad / KB) * KB * KB * sizeof(T), {}},
-           {&h->Wblk, (size_t)((cap + nb - 1) / nb) * nb * nb * sizeof(T), (size_t)(R0 / nb) * nb * nb * sizeof(T), {}}};
+           {&h->Wblk, (size_t)((cap + nb - 1) / nb) * nb * nb * sizeof(T), (size_t)(R0 / nb) * nb * nb * sizeof(T), {}},
+           {&h->Wfit, with_weights ? (size_t)cap * sizeof(T) : 0, h->weighted ? (size_t)N * sizeof(T) : 0, {}}};
   const size_t kbytes = (size_t)(cap + RHS_ROWS) * ld * sizeof(T);
   const size_t pbytes = (size_t)2 * (cap + RHS_ROWS) * h->ldp * sizeof(T);
   const bool newK = relayout || h->K.cap < kbytes, newP = h->P.cap < pbytes;
@@ -1371,8 +1405,12 @@ int append_restart(gpx_handle* h, int64_t Nold, int64_t Nnew, const void* Xnew, 
                              h->st);
       if (R0 > 0)  // left part of the 128-row tiles that hold a new point: K(x_i, x_j), j < R0
         launch_kbuild_cross<T>(h->cfg.kernel, Xs + R1 * d, Nnew - R1, rows, Xs, R0, R0, d, h->sf2, dK + R1 * ld, ld, h->st);
-      launch_kbuild_sym<T>(h->cfg.kernel, Xs + R0 * d, Nnew - R0, np, d, h->sf2, h->sn2 + h->jitter, dK + R0 * ld + R0, ld,
-                           h->st);
+      if (h->weighted)  // the rebuilt square needs the stored weights of rows [R0, Nold) beside the new points'
+        launch_kbuild_sym_w<T>(h->cfg.kernel, Xs + R0 * d, Nnew - R0, np, d, h->sf2, (const T*)h->Wfit.p + R0, h->sn2, h->jitter,
+                               dK + R0 * ld + R0, ld, h->st);
+      else
+        launch_kbuild_sym<T>(h->cfg.kernel, Xs + R0 * d, Nnew - R0, np, d, h->sf2, h->sn2 + h->jitter, dK + R0 * ld + R0, ld,
+                             h->st);
     }
     {
       PhaseScope ps(h, &tm.chol);
@@ -1397,7 +1435,8 @@ int append_restart(gpx_handle* h, int64_t Nold, int64_t Nnew, const void* Xnew, 
 }
 
 template <typename T>
-int append_impl(gpx_handle* h, const void* Xnew, const void* ynew, int64_t m, int32_t mem_kind, int64_t* info) {
+int append_impl(gpx_handle* h, const void* Xnew, const void* ynew, const void* wnew, int64_t m, int32_t mem_kind,
+                int64_t* info) {
   const int64_t Nold = h->N, Nnew = Nold + m;
   gpx_timings& tm = h->tm;
   tm.h2d = tm.kbuild = tm.chol = tm.solve = tm.logdet = tm.fit_total = 0;
@@ -1406,10 +1445,22 @@ int append_impl(gpx_handle* h, const void* Xnew, const void* ynew, int64_t m, in
   tm.kbuild_bytes = (double)sizeof(T) * ((double)m * (double)(Nold + Nnew + 1) / 2.0 + (double)m * h->d);
   int rc;
   if ((rc = flag_handover_probe(h))) return rc;
-  if ((rc = append_room<T>(h, Nnew))) return rc;  // nothing of the fit has been touched yet
+  const bool was_weighted = h->weighted;
+  if ((rc = append_room<T>(h, Nnew, was_weighted || wnew))) return rc;  // nothing of the fit has been touched yet
   {  // ... nor by the block-solve buffers of the new rows' forward solve
     SolveWork<T> sw;
     if ((rc = dense_solve_work<T>(h, h->scr.Tsol, round_up(Nnew, TILE) - Nold / TILE * TILE, &sw))) return rc;
+  }
+  // The weight vector has the factor's capacity (append_room grew it with the layout, keeping the N weights of the fit).
+  // A fit without weights that is given some gets ones for its own points first.
+  if (was_weighted || wnew) {
+    if (!was_weighted) launch_fill<T>((T*)h->Wfit.p, Nold, 1.0, h->st);
+    if (wnew) {
+      if ((rc = copy_in(h, (T*)h->Wfit.p + Nold, wnew, (size_t)m * sizeof(T), mem_kind))) return rc;
+    } else {
+      launch_fill<T>((T*)h->Wfit.p + Nold, m, 1.0, h->st);
+    }
+    h->weighted = true;
   }
   h->fitted = false;  // until the restart (or the restart back) has gone through
   h->alphaT = nullptr;
@@ -1436,6 +1487,7 @@ int append_impl(gpx_handle* h, const void* Xnew, const void* ynew, int64_t m, in
     if ((rc = restart(Nold, nullptr, nullptr, &back))) return rc;
     if (back != INT_MAX) return fail(h, GPX_E_HIP, "gpx_append: the previous fit could not be restored");
     Nfit = Nold;
+    h->weighted = was_weighted;  // (the weights of the first Nold points were never touched)
   }
   h->N = Nfit;
   h->Npad = round_up(Nfit, TILE);
@@ -1820,8 +1872,8 @@ size_t score_row_bytes(const gpx_handle* h, int Lg) {
 }
 
 template <typename T>
-int score_impl(gpx_handle* h, const void* Xq, const void* yq, int64_t G, int32_t Lg, double diag_add, void* logp, void* maha,
-               void* logdet, int32_t mem_kind, int64_t* info) {
+int score_impl(gpx_handle* h, const void* Xq, const void* yq, const void* wq, int64_t G, int32_t Lg, double diag_add,
+               void* logp, void* maha, void* logdet, int32_t mem_kind, int64_t* info) {
   const int64_t N = h->N, Npad = h->Npad, ld = h->ld, M = G * Lg;
   const int d = h->d, k = h->k;
   const int64_t Mpad = round_up(M, TILE);
@@ -1831,11 +1883,11 @@ int score_impl(gpx_handle* h, const void* Xq, const void* yq, int64_t G, int32_t
   {  // not one 128-row batch beside what the call keeps per query point: refused before anything is allocated
     const size_t row_bytes = score_row_bytes<T>(h, Lg);
     const size_t E = sizeof(T);
-    const double small = (double)(M + 2 * TILE) * d * 2 * E + (double)M * k * 2 * E + (double)G * (2 * k + 1) * E +
+    const double small = (double)(M + 2 * TILE) * d * 2 * E + (double)M * (2 * k + (wq ? 1 : 0)) * E + (double)G * (2 * k + 1) * E +
                          (double)RHS_ROWS * (TILE + ld_skew<T>()) * (1 + splitk_splits(Npad)) * E + 4096;
     const double need = (double)TILE * row_bytes + small;
     const double have = (double)h->scr.VT.cap + h->scr.Tsol.cap + h->scr.SPart.cap + h->scr.Q.cap + h->scr.Qs.cap + h->scr.SY.cap +
-                        h->scr.SOut.cap + h->scr.SMT.cap + h->scr.MTpart.cap + h->meanout.cap;
+                        h->scr.SOut.cap + h->scr.SMT.cap + h->scr.MTpart.cap + h->meanout.cap + (wq ? h->scr.SW.cap : 0);
     size_t freeb = 0, totalb = 0;
     HIPCHK(h, hipMemGetInfo(&freeb, &totalb));
     if (need > (double)freeb + have) {
@@ -1853,6 +1905,7 @@ int score_impl(gpx_handle* h, const void* Xq, const void* yq, int64_t G, int32_t
   // a batch reads rows_b rows of Qs from its first block on: up to 127 rows beyond M
   if ((rc = ensure_queries<T>(h, M + TILE))) return rc;
   if ((rc = ensure(h, h->scr.SY, (size_t)M * k * sizeof(T)))) return rc;
+  if (wq && (rc = ensure(h, h->scr.SW, (size_t)M * sizeof(T)))) return rc;
   if ((rc = ensure(h, h->scr.VT, (size_t)rows_b * ld * sizeof(T)))) return rc;
   if ((rc = ensure(h, h->scr.SMT, (size_t)RHS_ROWS * ldmb * sizeof(T)))) return rc;
   if ((rc = ensure_mean_partials<T>(h, h->scr.MTpart, ldmb))) return rc;
@@ -1878,6 +1931,7 @@ int score_impl(gpx_handle* h, const void* Xq, const void* yq, int64_t G, int32_t
       if ((rc = upload_queries<T>(h, Xq, M, mem_kind))) return rc;
       HIPCHK(h, hipMemsetAsync((T*)h->scr.Qs.p + Mpad * d, 0, (size_t)TILE * d * sizeof(T), h->st));
       if ((rc = copy_in(h, h->scr.SY.p, yq, (size_t)M * k * sizeof(T), mem_kind))) return rc;
+      if (wq && (rc = copy_in(h, h->scr.SW.p, wq, (size_t)M * sizeof(T), mem_kind))) return rc;
       const int init = INT_MAX;
       HIPCHK(h, hipMemcpyAsync(dBad, &init, sizeof(int), hipMemcpyHostToDevice, h->st));
     }
@@ -1902,7 +1956,7 @@ int score_impl(gpx_handle* h, const void* Xq, const void* yq, int64_t G, int32_t
         launch_block_gram<T>(dVT, ld, nb, Lg, Npad, (double*)h->scr.SPart.p, h->st);
         launch_block_score<T>(h->cfg.kernel, (const double*)h->scr.SPart.p, nb, Lg, Npad, dQs + m0 * d, d,
                               (const T*)h->scr.SY.p + m0 * k, (const T*)h->meanout.p + m0 * k, k, h->sf2, diag_add, dLogp,
-                              dMaha, dLogdet, g0, dBad, h->st);
+                              dMaha, dLogdet, g0, dBad, h->st, wq ? (const T*)h->scr.SW.p + m0 : nullptr);
       }
     }
     PhaseScope ps(h, &tm.d2h);
@@ -2145,6 +2199,8 @@ int lml_grad_impl(gpx_handle* h, double* lml, double* grad) {
   double* part1 = (double*)h->scr.gpart.p;
   double* part2 = part1 + s1n * ntheta;
   double* outv = part2 + s2n * ntheta;  // [ntheta] K^-1 sums, [ntheta] alpha sums, [1] y . alpha
+  // per-observation noise: dK / dlog sn2 = sn2 diag(w), so the noise entry of both passes takes w_i per row
+  const double* wv = h->weighted ? (const double*)h->Wfit.p : nullptr;
   hipStream_t st = h->st;
   {
     PhaseScope total(h, &tm.grad_total);
@@ -2176,10 +2232,10 @@ int lml_grad_impl(gpx_handle* h, double* lml, double* grad) {
       PhaseScope ps(h, &tm.grad_trace);
       HIPCHK(h, hipMemsetAsync(part1, 0, (size_t)(s1n + s2n) * ntheta * 8, st));  // ragged-edge / other ranks' slots write nothing
       launch_kinv_trace(h->cfg.kernel, ZT, ld, Npad, N, (const double*)h->Xs.p, d, ard, h->sf2, h->sn2, part1,
-                        ntheta, P, rank, st);
+                        ntheta, P, rank, st, wv);
     }
     launch_alpha_quad(h->cfg.kernel, (const double*)h->alphaT, ld, k, Npad, N, (const double*)h->Xs.p, d, ard,
-                      h->sf2, h->sn2, part2, ntheta, st);
+                      h->sf2, h->sn2, part2, ntheta, st, wv);
     launch_reduce_partials(part1, s1n, ntheta, 1.0, outv, st);
     launch_reduce_partials(part2, s2n, ntheta, 1.0, outv + ntheta, st);
     launch_dot_rhs((const double*)h->Y.p, (const double*)h->alphaT, ld, N, k, outv + 2 * ntheta, st);
@@ -2267,9 +2323,9 @@ int mixed_fit(gpx_handle* h, const void* X, const void* y, int64_t N, int32_t d,
   int iters = 0;
   for (int it = 0;; ++it) {
     PhaseScope ps(h, &tm.refine);
-    // r = y - (K + diag I) alpha  (fp64, matrix-free)
+    // r = y - (K + diag I) alpha  (fp64, matrix-free; per-observation noise: diag(sn2 w_i + jitter))
     launch_kmatvec(h->cfg.kernel, Xs64, N, Npad, Xs64, Npad, d, sf2, sn2 + jitter, (const double*)h->Y64.p, A64,
-                   Npad, k, -1.0, R64, Npad, st);
+                   Npad, k, -1.0, R64, Npad, st, h->weighted ? (const double*)h->Wfit64.p : nullptr, sn2, jitter);
     bool last = it == max_it;
     if (it == 0 || last || adaptive) launch_rows_sumsq(R64, Npad, k, N, rn + (it == 0 ? 0 : 1), st);
     if (adaptive) {
@@ -2519,12 +2575,63 @@ int check_fit_args(gpx_handle* h, const char* fn, bool with_queries, bool any_nu
   return GPX_OK;
 }
 
+// Per-observation noise weights (or query weights) must be finite and >= 0.  Host arrays are read here; device arrays by
+// one small reduction kernel whose verdict (a word of h->scalars) is the only thing copied back.  es = element size (4 / 8).  `stream` null (the
+// front handle of a device group owns none): the device array is read back and checked on the host.
+int check_weights(gpx_handle* h, const char* fn, const void* w, int64_t n, int32_t mem_kind, size_t es, hipStream_t stream) {
+  auto bad = [&]() { return fail(h, GPX_E_ARG, (std::string(fn) + ": weights must be finite and >= 0").c_str()); };
+  auto host_ok = [&](const void* p) {
+    for (int64_t i = 0; i < n; ++i) {
+      const double v = es == 4 ? (double)((const float*)p)[i] : ((const double*)p)[i];
+      if (!(v >= 0.0) || !std::isfinite(v)) return false;
+    }
+    return true;
+  };
+  if (mem_kind == GPX_MEM_HOST) return host_ok(w) ? GPX_OK : bad();
+  if (!stream) {
+    std::vector<char> tmp((size_t)n * es);
+    HIPCHK(h, hipMemcpy(tmp.data(), w, tmp.size(), hipMemcpyDefault));
+    return host_ok(tmp.data()) ? GPX_OK : bad();
+  }
+  int rc, hbad = 0;
+  if ((rc = ensure(h, h->scalars, 64))) return rc;  // the fit's own 64 bytes ([0, 16): logdet, info): the verdict at byte 32
+  int* flag = (int*)((char*)h->scalars.p + 32);
+  if (es == 4)
+    launch_check_weights<float>((const float*)w, n, flag, stream);
+  else
+    launch_check_weights<double>((const double*)w, n, flag, stream);
+  HIPCHK(h, hipMemcpyAsync(&hbad, flag, sizeof(int), hipMemcpyDeviceToHost, stream));
+  HIPCHK(h, hipStreamSynchronize(stream));
+  HIPCHK(h, hipGetLastError());
+  return hbad ? bad() : GPX_OK;
+}
+
+// a fit on a handle with weights set: refused on device groups, shards and handles that own a communicator, and when the
+// weights are not one per observation — before anything is computed or exchanged
+int check_fit_weights(gpx_handle* h, const char* fn, int64_t N) {
+  if (h->nw_set == 0) return GPX_OK;
+  char buf[256];
+  if (h->group || h->cfg.world > 1 || h->comm) {
+    snprintf(buf, sizeof buf, "%s: per-observation noise weights are not supported on %s (single-device handles only; "
+             "clear them with gpx_set_noise_weights(h, NULL, 0, ...))", fn, h->group ? "device groups" : "sharded handles");
+    return fail(h, GPX_E_UNSUPPORTED, buf);
+  }
+  if (N != h->nw_set) {
+    snprintf(buf, sizeof buf, "%s: %lld noise weights are set for a fit of %lld observations", fn, (long long)h->nw_set,
+             (long long)N);
+    return fail(h, GPX_E_ARG, buf);
+  }
+  return GPX_OK;
+}
+
 // gpx_fit on one handle, behind its argument checks and begin_fit
 int fit_begun(gpx_handle* h, const void* X, const void* y, int64_t N, int32_t d, int32_t k, const double* lengthscale,
               int32_t n_ls, double sf2, double sn2, double jitter, int32_t mem_kind, int64_t* info) {
   if (h->cfg.dtype == GPX_MIXED) return mixed_fit(h, X, y, N, d, k, lengthscale, n_ls, sf2, sn2, jitter, mem_kind, info);
-  if (h->cfg.world > 1 || h->comm)  // a 1-rank communicator also takes the sharded schedule
+  if (h->cfg.world > 1 || h->comm) {  // a 1-rank communicator also takes the sharded schedule
+    h->weighted = false;
     return BY_DTYPE(h, shard_fit, h, X, y, N, d, k, lengthscale, n_ls, sf2, sn2, jitter, mem_kind, info);
+  }
   return BY_DTYPE(h, fit_impl, h, X, y, N, d, k, lengthscale, n_ls, sf2, sn2, jitter, mem_kind, info);
 }
 
@@ -2547,6 +2654,7 @@ int gpx_fit(gpx_handle* h, const void* X, const void* y, int64_t N, int32_t d, i
   if ((rc = check_fit_args(h, "gpx_fit", false, !X || !y || !lengthscale || !info, N, 0, d, k, lengthscale, n_ls, sf2, sn2,
                            jitter, mem_kind)))
     return rc;
+  if ((rc = check_fit_weights(h, "gpx_fit", N))) return rc;
   if (h->group) return group_fit(h, X, y, N, d, k, lengthscale, n_ls, sf2, sn2, jitter, mem_kind, info);
   if ((rc = begin_fit(h))) return rc;
   return fit_begun(h, X, y, N, d, k, lengthscale, n_ls, sf2, sn2, jitter, mem_kind, info);
@@ -2561,6 +2669,7 @@ int gpx_fit_predict(gpx_handle* h, const void* X, const void* y, int64_t N, int3
   if ((rc = check_fit_args(h, "gpx_fit_predict", true, !X || !y || !lengthscale || !info || !Xq || !mean, N, M, d, k,
                            lengthscale, n_ls, sf2, sn2, jitter, mem_kind)))
     return rc;
+  if ((rc = check_fit_weights(h, "gpx_fit_predict", N))) return rc;
   if (h->group) return group_fit_predict(h, X, y, N, d, k, lengthscale, n_ls, sf2, sn2, jitter, Xq, M, mean, var, mem_kind, info);
   // Shards (round 4): every rank's slice of the query points rides through the sharded factorisation as bordered rows of
   // its local row set (shard_fit with query points + shard_fused_tail) — in the split schedule, up to 8192 rows per rank.
@@ -2677,8 +2786,10 @@ int gpx_predict_grad(gpx_handle* h, const void* Xq, int64_t M, void* mean, void*
 }
 GPX_CATCH_ALL
 
-int gpx_score_blocks(gpx_handle* h, const void* Xs, const void* ys, int64_t G, int32_t Lg, double diag_add, void* logp,
-                     void* maha, void* logdet, int32_t mem_kind, int64_t* info) try {
+namespace {
+// gpx_score_blocks (wq null) and gpx_score_blocks_weighted: one body, so the refusals are the same
+int score_blocks_entry(gpx_handle* h, const void* Xs, const void* ys, const void* wq, int64_t G, int32_t Lg, double diag_add,
+                       void* logp, void* maha, void* logdet, int32_t mem_kind, int64_t* info) {
   if (!h) return GPX_E_ARG;
   if (!Xs || !ys || !logp || !info || G <= 0) return fail(h, GPX_E_ARG, "gpx_score_blocks: bad argument");
   if (Lg < 1 || Lg > 64) return fail(h, GPX_E_ARG, "gpx_score_blocks: need 1 <= Lg <= 64");
@@ -2689,11 +2800,13 @@ int gpx_score_blocks(gpx_handle* h, const void* Xs, const void* ys, int64_t G, i
   int rc;
   if ((rc = posterior_refused(h, "gpx_score_blocks"))) return rc;
   if ((rc = begin_call(h))) return rc;
-  return BY_DTYPE(h, score_impl, h, Xs, ys, G, Lg, diag_add, logp, maha, logdet, mem_kind, info);
+  if (wq && (rc = check_weights(h, "gpx_score_blocks_weighted", wq, G * Lg, mem_kind, h->cfg.dtype == GPX_F32 ? 4 : 8, h->st)))
+    return rc;
+  return BY_DTYPE(h, score_impl, h, Xs, ys, wq, G, Lg, diag_add, logp, maha, logdet, mem_kind, info);
 }
-GPX_CATCH_ALL
 
-int gpx_append(gpx_handle* h, const void* Xnew, const void* ynew, int64_t m, int32_t mem_kind, int64_t* info) try {
+int append_entry(gpx_handle* h, const void* Xnew, const void* ynew, const void* wnew, int64_t m, int32_t mem_kind,
+                 int64_t* info) {
   if (!h) return GPX_E_ARG;
   if (!Xnew || !ynew || !info || m <= 0) return fail(h, GPX_E_ARG, "gpx_append: bad argument");
   if (mem_kind != GPX_MEM_HOST && mem_kind != GPX_MEM_DEVICE) return fail(h, GPX_E_ARG, "gpx_append: bad mem_kind");
@@ -2702,7 +2815,90 @@ int gpx_append(gpx_handle* h, const void* Xnew, const void* ynew, int64_t m, int
   if (!h->fitted) return fail(h, GPX_E_ARG, "gpx_append: handle has no successful fit");
   if (m > (int64_t)INT_MAX - 4096 - h->N) return fail(h, GPX_E_ARG, "gpx_append: N + m too large");
   if ((rc = begin_call(h))) return rc;
-  return BY_DTYPE(h, append_impl, h, Xnew, ynew, m, mem_kind, info);
+  if (wnew && (rc = check_weights(h, "gpx_append_weighted", wnew, m, mem_kind, h->cfg.dtype == GPX_F32 ? 4 : 8, h->st)))
+    return rc;
+  return BY_DTYPE(h, append_impl, h, Xnew, ynew, wnew, m, mem_kind, info);
+}
+}  // namespace
+
+int gpx_score_blocks(gpx_handle* h, const void* Xs, const void* ys, int64_t G, int32_t Lg, double diag_add, void* logp,
+                     void* maha, void* logdet, int32_t mem_kind, int64_t* info) try {
+  return score_blocks_entry(h, Xs, ys, nullptr, G, Lg, diag_add, logp, maha, logdet, mem_kind, info);
+}
+GPX_CATCH_ALL
+
+int gpx_score_blocks_weighted(gpx_handle* h, const void* Xs, const void* ys, const void* wq, int64_t G, int32_t Lg,
+                              double diag_add, void* logp, void* maha, void* logdet, int32_t mem_kind, int64_t* info) try {
+  return score_blocks_entry(h, Xs, ys, wq, G, Lg, diag_add, logp, maha, logdet, mem_kind, info);
+}
+GPX_CATCH_ALL
+
+int gpx_append(gpx_handle* h, const void* Xnew, const void* ynew, int64_t m, int32_t mem_kind, int64_t* info) try {
+  return append_entry(h, Xnew, ynew, nullptr, m, mem_kind, info);
+}
+GPX_CATCH_ALL
+
+int gpx_append_weighted(gpx_handle* h, const void* Xnew, const void* ynew, const void* wnew, int64_t m, int32_t mem_kind,
+                        int64_t* info) try {
+  return append_entry(h, Xnew, ynew, wnew, m, mem_kind, info);
+}
+GPX_CATCH_ALL
+
+int gpx_set_noise_weights(gpx_handle* h, const void* w, int64_t n, int32_t mem_kind) try {
+  if (!h) return GPX_E_ARG;
+  if (mem_kind != GPX_MEM_HOST && mem_kind != GPX_MEM_DEVICE) return fail(h, GPX_E_ARG, "gpx_set_noise_weights: bad mem_kind");
+  if (n < 0 || (n == 0) != (w == nullptr) || n > (int64_t)INT_MAX - 4096)
+    return fail(h, GPX_E_ARG, "gpx_set_noise_weights: need n weights, or NULL and 0 to clear them");
+  const size_t es = h->cfg.dtype == GPX_F32 ? 4 : 8;
+  int rc;
+  if (h->group) {  // a group's fit with weights is refused (check_fit_weights): only their count is kept
+    if (n > 0 && (rc = check_weights(h, "gpx_set_noise_weights", w, n, mem_kind, es, nullptr))) return rc;
+    h->nw_set = n;
+    return GPX_OK;
+  }
+  if (n == 0 && h->nw_set == 0) return GPX_OK;
+  HIPCHK(h, hipSetDevice(h->cfg.device));
+  if (n == 0) {
+    HIPCHK(h, hipStreamSynchronize(h->st));
+    h->Wset = DevBuf();
+    h->nw_set = 0;
+    return GPX_OK;
+  }
+  // validated where the caller holds them, before the handle's copy is overwritten: a refused call leaves the weights of
+  // the call before in place.  The buffer is kept from call to call (an optimiser sets the same n before every fit).
+  if ((rc = check_weights(h, "gpx_set_noise_weights", w, n, mem_kind, es, h->st))) return rc;
+  if (h->Wset.cap < (size_t)n * es) {
+    DevBuf fresh;  // (allocated before the old one is let go: GPX_E_NOMEM leaves the previous weights too)
+    if (hipMalloc(&fresh.p, (size_t)n * es) != hipSuccess) {
+      (void)hipGetLastError();
+      return fail(h, GPX_E_NOMEM, "gpx_set_noise_weights: out of device memory");
+    }
+    fresh.cap = (size_t)n * es;
+    HIPCHK(h, hipStreamSynchronize(h->st));
+    h->Wset = std::move(fresh);
+  }
+  if ((rc = copy_in(h, h->Wset.p, w, (size_t)n * es, mem_kind))) return rc;
+  HIPCHK(h, hipStreamSynchronize(h->st));
+  h->nw_set = n;
+  return GPX_OK;
+}
+GPX_CATCH_ALL
+
+int gpx_get_noise_weights(gpx_handle* h, void* out) try {
+  if (!h) return GPX_E_ARG;
+  if (!h->fitted || !out) return fail(h, GPX_E_ARG, "gpx_get_noise_weights: no fit or null output");
+  const bool f32 = h->cfg.dtype == GPX_F32;
+  const int64_t N = h->group ? h->group->members[0]->N : h->N;
+  if (!h->weighted) {
+    for (int64_t i = 0; i < N; ++i)
+      if (f32) ((float*)out)[i] = 1.0f; else ((double*)out)[i] = 1.0;
+    return GPX_OK;
+  }
+  HIPCHK(h, hipSetDevice(h->cfg.device));
+  const void* src = h->cfg.dtype == GPX_MIXED ? h->Wfit64.p : h->Wfit.p;
+  HIPCHK(h, hipMemcpyAsync(out, src, (size_t)N * (f32 ? 4 : 8), hipMemcpyDeviceToHost, h->st));
+  HIPCHK(h, hipStreamSynchronize(h->st));
+  return GPX_OK;
 }
 GPX_CATCH_ALL
 

@@ -39,13 +39,17 @@ __device__ __forceinline__ double wg_sum(double v, double* red) {
 // grid: the hole-free triangular super-tile map of the SYRK (tile_coords<true>), 128x128 tiles.
 // part[lin * ntheta + t], t = (lengthscales..., sf2, sn2): sum over the tile of
 // K^-1_ij (dK/dlog theta_t)_ij, off-diagonal tiles counted twice (symmetry).
-template <int KERNEL, int D>
+// WEIGHTED: per-observation noise, dK/dlog sn2 = sn2 diag(wv) — the noise entry sums wv[i] K^-1_ii.  An instantiation of
+// its own: the epilogue sits at the edge of the register file (see the scheduling barrier below), and one more load in it
+// changes what the unweighted kernel spills.
+template <int KERNEL, int D, bool WEIGHTED>
 __global__ __launch_bounds__(256, 2) void kinv_trace_kernel(const double* __restrict__ ZT, int64_t ld,
                                                             int tiles, int64_t npad, int64_t n,
                                                             const double* __restrict__ Xs, int d_rt, int ard,
                                                             double sf2, double sn2, double* __restrict__ part,
                                                             int ntheta, int64_t nslots, int P, int rank,
-                                                            int dc_nb, int dc_P, int dc_r, int64_t dc_cols, int dc_snake) {
+                                                            int dc_nb, int dc_P, int dc_r, int64_t dc_cols, int dc_snake,
+                                                            const double* __restrict__ wv) {
   constexpr int BT = 128;
   __shared__ __attribute__((aligned(16))) double smem[TileShapeG<double, BT, BT>::SMEM_ELEMS];
   __shared__ double red[4];
@@ -121,7 +125,11 @@ __global__ __launch_bounds__(256, 2) void kinv_trace_kernel(const double* __rest
         double kf, kd;
         cov::value_kd<KERNEL>(r2, sf2, kf, kd);
         Sf += v * kf;
-        if (gi == gj) Sn += v;
+        if (WEIGHTED) {
+          if (gi == gj && gi < n) Sn += v * wv[gi];
+        } else {
+          if (gi == gj) Sn += v;
+        }
         const double t = v * kd;
         Sl += t * r2;
         acc[m][nn][r] = t;  // kept for the per-dimension pass (ARD)
@@ -178,7 +186,8 @@ template <int KERNEL, int D>
 __global__ __launch_bounds__(256) void alpha_quad_kernel(const double* __restrict__ alphaT, int64_t ld, int k,
                                                         int64_t n, const double* __restrict__ Xs, int d_rt,
                                                         int ard, double sf2, double sn2,
-                                                        double* __restrict__ part, int ntheta) {
+                                                        double* __restrict__ part, int ntheta,
+                                                        const double* __restrict__ wv) {
   constexpr int KT = 64;
   __shared__ double xa[KT * MAX_D];
   __shared__ double xb[KT * MAX_D];
@@ -227,7 +236,7 @@ __global__ __launch_bounds__(256) void alpha_quad_kernel(const double* __restric
       double kf, kd;
       cov::value_kd<KERNEL>(r2, sf2, kf, kd);
       Sf += v * kf;
-      if (gi == gj) Sn += v;
+      if (gi == gj) Sn += (wv && gi < n) ? v * wv[gi] : v;
       const double t = v * kd;
       Sl += t * r2;
       wt[r][q] = t;
@@ -293,30 +302,39 @@ __global__ __launch_bounds__(256) void set_diag_one_kernel(double* A, int64_t ld
 template <int KERNEL>
 void launch_kinv_trace_k(const double* ZT, int64_t ld, int64_t npad, int64_t n, const double* Xs, int d, int ard,
                          double sf2, double sn2, double* part, int ntheta, int P, int rank, int dc_nb, int dc_P,
-                         int dc_r, int64_t dc_cols, int dc_snake, hipStream_t st) {
+                         int dc_r, int64_t dc_cols, int dc_snake, const double* wv, hipStream_t st) {
   const int tiles = (int)(npad / 128);
   const int64_t ts = (tiles + 7) / 8;
   const int64_t nslots = ts * (ts - 1) / 2 * 64 + ts * 36;
   const int64_t octets = (nslots + 511) / 512, mine = octets > rank ? (octets - rank + P - 1) / P : 0;
   if (mine == 0) return;
   dim3 grid((unsigned)(mine * 512)), block(256);  // whole octets of 8 x 64 slots
+  if (wv) {
+    switch (d) {
+      case 1: hipLaunchKernelGGL((kinv_trace_kernel<KERNEL, 1, true>), grid, block, 0, st, ZT, ld, tiles, npad, n, Xs, d, ard, sf2, sn2, part, ntheta, nslots, P, rank, dc_nb, dc_P, dc_r, dc_cols, dc_snake, wv); break;
+      case 2: hipLaunchKernelGGL((kinv_trace_kernel<KERNEL, 2, true>), grid, block, 0, st, ZT, ld, tiles, npad, n, Xs, d, ard, sf2, sn2, part, ntheta, nslots, P, rank, dc_nb, dc_P, dc_r, dc_cols, dc_snake, wv); break;
+      case 3: hipLaunchKernelGGL((kinv_trace_kernel<KERNEL, 3, true>), grid, block, 0, st, ZT, ld, tiles, npad, n, Xs, d, ard, sf2, sn2, part, ntheta, nslots, P, rank, dc_nb, dc_P, dc_r, dc_cols, dc_snake, wv); break;
+      default: hipLaunchKernelGGL((kinv_trace_kernel<KERNEL, 0, true>), grid, block, 0, st, ZT, ld, tiles, npad, n, Xs, d, ard, sf2, sn2, part, ntheta, nslots, P, rank, dc_nb, dc_P, dc_r, dc_cols, dc_snake, wv); break;
+    }
+    return;
+  }
   switch (d) {
-    case 1: hipLaunchKernelGGL((kinv_trace_kernel<KERNEL, 1>), grid, block, 0, st, ZT, ld, tiles, npad, n, Xs, d, ard, sf2, sn2, part, ntheta, nslots, P, rank, dc_nb, dc_P, dc_r, dc_cols, dc_snake); break;
-    case 2: hipLaunchKernelGGL((kinv_trace_kernel<KERNEL, 2>), grid, block, 0, st, ZT, ld, tiles, npad, n, Xs, d, ard, sf2, sn2, part, ntheta, nslots, P, rank, dc_nb, dc_P, dc_r, dc_cols, dc_snake); break;
-    case 3: hipLaunchKernelGGL((kinv_trace_kernel<KERNEL, 3>), grid, block, 0, st, ZT, ld, tiles, npad, n, Xs, d, ard, sf2, sn2, part, ntheta, nslots, P, rank, dc_nb, dc_P, dc_r, dc_cols, dc_snake); break;
-    default: hipLaunchKernelGGL((kinv_trace_kernel<KERNEL, 0>), grid, block, 0, st, ZT, ld, tiles, npad, n, Xs, d, ard, sf2, sn2, part, ntheta, nslots, P, rank, dc_nb, dc_P, dc_r, dc_cols, dc_snake); break;
+    case 1: hipLaunchKernelGGL((kinv_trace_kernel<KERNEL, 1, false>), grid, block, 0, st, ZT, ld, tiles, npad, n, Xs, d, ard, sf2, sn2, part, ntheta, nslots, P, rank, dc_nb, dc_P, dc_r, dc_cols, dc_snake, wv); break;
+    case 2: hipLaunchKernelGGL((kinv_trace_kernel<KERNEL, 2, false>), grid, block, 0, st, ZT, ld, tiles, npad, n, Xs, d, ard, sf2, sn2, part, ntheta, nslots, P, rank, dc_nb, dc_P, dc_r, dc_cols, dc_snake, wv); break;
+    case 3: hipLaunchKernelGGL((kinv_trace_kernel<KERNEL, 3, false>), grid, block, 0, st, ZT, ld, tiles, npad, n, Xs, d, ard, sf2, sn2, part, ntheta, nslots, P, rank, dc_nb, dc_P, dc_r, dc_cols, dc_snake, wv); break;
+    default: hipLaunchKernelGGL((kinv_trace_kernel<KERNEL, 0, false>), grid, block, 0, st, ZT, ld, tiles, npad, n, Xs, d, ard, sf2, sn2, part, ntheta, nslots, P, rank, dc_nb, dc_P, dc_r, dc_cols, dc_snake, wv); break;
   }
 }
 
 template <int KERNEL>
 void launch_alpha_quad_k(const double* alphaT, int64_t ld, int k, int64_t npad, int64_t n, const double* Xs, int d,
-                         int ard, double sf2, double sn2, double* part, int ntheta, hipStream_t st) {
+                         int ard, double sf2, double sn2, double* part, int ntheta, const double* wv, hipStream_t st) {
   const int64_t T = npad / 64;
   dim3 grid((unsigned)(T * (T + 1) / 2)), block(256);
   if (d == 3)
-    hipLaunchKernelGGL((alpha_quad_kernel<KERNEL, 3>), grid, block, 0, st, alphaT, ld, k, n, Xs, d, ard, sf2, sn2, part, ntheta);
+    hipLaunchKernelGGL((alpha_quad_kernel<KERNEL, 3>), grid, block, 0, st, alphaT, ld, k, n, Xs, d, ard, sf2, sn2, part, ntheta, wv);
   else
-    hipLaunchKernelGGL((alpha_quad_kernel<KERNEL, 0>), grid, block, 0, st, alphaT, ld, k, n, Xs, d, ard, sf2, sn2, part, ntheta);
+    hipLaunchKernelGGL((alpha_quad_kernel<KERNEL, 0>), grid, block, 0, st, alphaT, ld, k, n, Xs, d, ard, sf2, sn2, part, ntheta, wv);
 }
 
 }  // namespace
@@ -336,20 +354,21 @@ void launch_set_diag_one(double* A, int64_t lda, int64_t n, hipStream_t st) {
 }
 
 void launch_kinv_trace(int kernel, const double* ZT, int64_t ld, int64_t npad, int64_t n, const double* Xs, int d,
-                       int ard, double sf2, double sn2, double* part, int ntheta, int P, int rank, hipStream_t st) {
-  cov::dispatch(kernel, [&](auto fam) { launch_kinv_trace_k<fam>(ZT, ld, npad, n, Xs, d, ard, sf2, sn2, part, ntheta, P, rank, 0, 0, 0, 0, 0, st); });
+                       int ard, double sf2, double sn2, double* part, int ntheta, int P, int rank, hipStream_t st,
+                       const double* wv) {
+  cov::dispatch(kernel, [&](auto fam) { launch_kinv_trace_k<fam>(ZT, ld, npad, n, Xs, d, ard, sf2, sn2, part, ntheta, P, rank, 0, 0, 0, 0, 0, wv, st); });
 }
 
 void launch_kinv_trace_cols(int kernel, const double* ZTc, int64_t ldc, int64_t npad, int64_t n, const double* Xs,
                             int d, int ard, double sf2, double sn2, double* part, int ntheta, int nb, int P, int rank,
                             int64_t ncols, int snake, hipStream_t st) {
-  cov::dispatch(kernel, [&](auto fam) { launch_kinv_trace_k<fam>(ZTc, ldc, npad, n, Xs, d, ard, sf2, sn2, part, ntheta, 1, 0, nb, P, rank, ncols, snake, st); });
+  cov::dispatch(kernel, [&](auto fam) { launch_kinv_trace_k<fam>(ZTc, ldc, npad, n, Xs, d, ard, sf2, sn2, part, ntheta, 1, 0, nb, P, rank, ncols, snake, nullptr, st); });
 }
 
 void launch_alpha_quad(int kernel, const double* alphaT, int64_t ld, int k, int64_t npad, int64_t n,
                        const double* Xs, int d, int ard, double sf2, double sn2, double* part, int ntheta,
-                       hipStream_t st) {
-  cov::dispatch(kernel, [&](auto fam) { launch_alpha_quad_k<fam>(alphaT, ld, k, npad, n, Xs, d, ard, sf2, sn2, part, ntheta, st); });
+                       hipStream_t st, const double* wv) {
+  cov::dispatch(kernel, [&](auto fam) { launch_alpha_quad_k<fam>(alphaT, ld, k, npad, n, Xs, d, ard, sf2, sn2, part, ntheta, wv, st); });
 }
 
 void launch_reduce_partials(const double* part, int64_t ntile, int ntheta, double scale, double* out,

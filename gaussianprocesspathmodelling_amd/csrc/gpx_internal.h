@@ -92,6 +92,11 @@ void launch_scale_points(const T* X, int64_t n, int64_t npad, int d, const doubl
 template <typename T>
 void launch_kbuild_sym(int kernel, const T* Xs, int64_t n, int64_t npad, int d, double sf2,
                        double diag_add, T* K, int64_t ld, hipStream_t st);
+// The same with per-observation noise: + (sn2 w[i] + jitter) on the diagonal of row i < n, w (n) on the device
+// (w = 1 everywhere: the bits of launch_kbuild_sym with diag_add = sn2 + jitter).
+template <typename T>
+void launch_kbuild_sym_w(int kernel, const T* Xs, int64_t n, int64_t npad, int d, double sf2, const T* w, double sn2,
+                         double jitter, T* K, int64_t ld, hipStream_t st);
 // Rectangular K*[mpad, npad] (ld) = sf2*k(As_i, Bs_j); rows >= m or cols >= n are zero.
 template <typename T>
 void launch_kbuild_cross(int kernel, const T* As, int64_t m, int64_t mpad, const T* Bs, int64_t n,
@@ -236,7 +241,8 @@ void launch_set_diag_one(double* A, int64_t lda, int64_t n, hipStream_t st);
 // part[slot][t] = sum over the tile of (ZT ZT^T)_ij (dK/dlog theta_t)_ij, ZT = L^-T (npad x npad, ld);
 // rank `rank` of P covers every P-th octet of 64-slot groups (P = 1: all of them)
 void launch_kinv_trace(int kernel, const double* ZT, int64_t ld, int64_t npad, int64_t n, const double* Xs, int d,
-                       int ard, double sf2, double sn2, double* part, int ntheta, int P, int rank, hipStream_t st);
+                       int ard, double sf2, double sn2, double* part, int ntheta, int P, int rank, hipStream_t st,
+                       const double* wv = nullptr);  // wv (n): the noise entry sums w_i (K^-1)_ii (null: w = 1)
 // the same for a factor that is only held distributed: ZTc (npad rows x ncols, ldc) = the columns of L^-T
 // that belong to this rank's row blocks of L (height nb, block-cyclic over P ranks, local order); every
 // rank visits every tile and contracts over its own columns: the ranks' partial sums add up
@@ -246,7 +252,7 @@ void launch_kinv_trace_cols(int kernel, const double* ZTc, int64_t ldc, int64_t 
 // part[slot][t] = sum over the tile of (sum_c alpha_ic alpha_jc) (dK/dlog theta_t)_ij, alphaT (k x npad, ld)
 void launch_alpha_quad(int kernel, const double* alphaT, int64_t ld, int k, int64_t npad, int64_t n,
                        const double* Xs, int d, int ard, double sf2, double sn2, double* part, int ntheta,
-                       hipStream_t st);
+                       hipStream_t st, const double* wv = nullptr);  // wv (n): the noise entry sums w_i sum_c alpha_ic^2
 void launch_reduce_partials(const double* part, int64_t ntile, int ntheta, double scale, double* out,
                             hipStream_t st);
 // out[0] = sum_i sum_c y[i*k + c] * alphaT[c*ld + i]
@@ -259,7 +265,8 @@ void launch_dot_rhs(const double* y, const double* alphaT, int64_t ld, int64_t n
 // alphaT (k x lda) zero beyond the valid columns.
 void launch_kmatvec(int kernel, const double* As, int64_t m, int64_t mpad, const double* Bs, int64_t npad, int d,
                     double sf2, double diag, const double* y, const double* alphaT, int64_t lda, int k,
-                    double sign, double* outT, int64_t ldo, hipStream_t st);
+                    double sign, double* outT, int64_t ldo, hipStream_t st, const double* wv = nullptr, double wsn2 = 0.0,
+                    double wjit = 0.0);  // wv (m) != null: row i's diagonal term is (wsn2 wv[i] + wjit) alphaT[c][i], not diag
 void launch_f64_to_f32(const double* in, float* out, int64_t count, hipStream_t st);
 void launch_f32_to_f64(const float* in, double* out, int64_t count, hipStream_t st);
 // dst (R x ldd, float) = rows [0, rows) x [0, n) of src (double), zero elsewhere up to npad
@@ -334,7 +341,8 @@ void launch_block_gram(const T* VT, int64_t ld, int64_t nblk, int Lg, int64_t np
 template <typename T>
 void launch_block_score(int kernel, const double* part, int64_t nblk, int Lg, int64_t npad, const T* Qs, int d,
                         const T* ys, const T* mean, int k, double sf2, double diag_add, T* logp, T* maha, T* logdet,
-                        int64_t g0, int* bad, hipStream_t st);
+                        int64_t g0, int* bad, hipStream_t st, const T* wq = nullptr);  // wq (nblk Lg), from the batch's first
+                                                                                       // row: + diag_add wq[i] per point
 
 // ---- row-block-cyclic shard helpers (gpx_misc.hip; T = double | float) ------------------------
 // A[i][i] = i < nvalid ? A[i][i] + add : 1   for i < n (diagonal of one local row block)
@@ -359,6 +367,13 @@ template <typename T>
 void launch_add_block(T* dst, int64_t ldd, const T* src, int64_t lds, int rows, int cols, double sign, hipStream_t st);
 template <typename T>
 void launch_add_scalar(T* p, int64_t count, double v, hipStream_t st);
+// p[i] = v, i < count
+template <typename T>
+void launch_fill(T* p, int64_t count, double v, hipStream_t st);
+// *bad = 1 if any of w[0..n) is negative or not finite, else 0 (one workgroup; per-observation noise weights that
+// arrive as device pointers)
+template <typename T>
+void launch_check_weights(const T* w, int64_t n, int* bad, hipStream_t st);
 // dst[i] = op over q < P of src[q*count + i] in rank order (op 0 sum, 1 min); dst may not alias src
 template <typename T>
 void launch_reduce_ranks(const T* src, T* dst, int P, int64_t count, int op, hipStream_t st);

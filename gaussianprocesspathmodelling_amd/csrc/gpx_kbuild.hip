@@ -39,11 +39,14 @@ __device__ __forceinline__ void tri_coords(int64_t t, int& ti, int& tj) {
 
 // SYM: lower tiles of a square matrix built from one point set (As == Bs), diagonal
 // gets + diag_add, padding becomes identity.  !SYM: all tiles, padding is zero.
-template <typename T, int KERNEL, bool SYM, int D>
+// WEIGHTED (SYM only): row i < m of the diagonal gets + (wsn2 w[i] + wjit) instead of diag_add — per-observation noise;
+// the sum is formed in fp64 and rounded once, as the host forms sn2 + jitter for the scalar form (w = 1: the same bits).
+template <typename T, int KERNEL, bool SYM, int D, bool WEIGHTED = false>
 __global__ __launch_bounds__(256) void kbuild_kernel(const T* __restrict__ As, int64_t m,
                                                     const T* __restrict__ Bs, int64_t n, int d_rt,
                                                     int tiles_n, T sf2, T diag_add, T* __restrict__ K,
-                                                    int64_t ld) {
+                                                    int64_t ld, const T* __restrict__ w = nullptr,
+                                                    double wsn2 = 0.0, double wjit = 0.0) {
   const int d = (D > 0) ? D : d_rt;
   // LDS sized by the instantiation (d = 3: 2 x 1.5 KB, not 2 x 16 KB): the occupancy is then the waves', not the LDS's
   __shared__ T xa[KT * (D > 0 ? D : MAX_D)];
@@ -96,8 +99,16 @@ __global__ __launch_bounds__(256) void kbuild_kernel(const T* __restrict__ As, i
     }
     T v0 = cov::value<KERNEL>(s0, sf2), v1 = cov::value<KERNEL>(s1, sf2);
     if (SYM) {
-      if (row == col0) v0 += diag_add;
-      if (row == col1) v1 += diag_add;
+      if (WEIGHTED) {  // (only diagonal tiles read w: one load per row there)
+        if (ti == tj && row < m) {
+          const T da = (T)(wsn2 * (double)w[row] + wjit);
+          if (row == col0) v0 += da;
+          if (row == col1) v1 += da;
+        }
+      } else {
+        if (row == col0) v0 += diag_add;
+        if (row == col1) v1 += diag_add;
+      }
       if (row >= m || col0 >= n) v0 = (row == col0) ? (T)1 : (T)0;
       if (row >= m || col1 >= n) v1 = (row == col1) ? (T)1 : (T)0;
     } else {
@@ -111,6 +122,20 @@ __global__ __launch_bounds__(256) void kbuild_kernel(const T* __restrict__ As, i
     // this kernel 3.36 ms = 5.1 TB/s against 3.52 with plain stores and 3.58 with the 2 x 16 KB static LDS of rounds 1-3;
     // unrolling (1 / 2 / 4 / 8 rows), persistent tile walks, row strips and an occupancy hint all land within 3.4-3.9 ms.
     __builtin_nontemporal_store(out, reinterpret_cast<pair_t*>(K + row * ld + col0));
+  }
+}
+
+// the weighted symmetric build (launch_kbuild_sym_w)
+template <typename T, int KERNEL>
+void dispatch_d_w(const T* Xs, int64_t n, int d, int64_t nblocks, int tiles_n, double sf2, const T* w, double sn2,
+                  double jitter, T* K, int64_t ld, hipStream_t st) {
+  dim3 grid((unsigned)nblocks), block(256);
+  const T s = (T)sf2, z = (T)0;
+  switch (d) {
+    case 1: hipLaunchKernelGGL((kbuild_kernel<T, KERNEL, true, 1, true>), grid, block, 0, st, Xs, n, Xs, n, d, tiles_n, s, z, K, ld, w, sn2, jitter); break;
+    case 2: hipLaunchKernelGGL((kbuild_kernel<T, KERNEL, true, 2, true>), grid, block, 0, st, Xs, n, Xs, n, d, tiles_n, s, z, K, ld, w, sn2, jitter); break;
+    case 3: hipLaunchKernelGGL((kbuild_kernel<T, KERNEL, true, 3, true>), grid, block, 0, st, Xs, n, Xs, n, d, tiles_n, s, z, K, ld, w, sn2, jitter); break;
+    default: hipLaunchKernelGGL((kbuild_kernel<T, KERNEL, true, 0, true>), grid, block, 0, st, Xs, n, Xs, n, d, tiles_n, s, z, K, ld, w, sn2, jitter); break;
   }
 }
 
@@ -146,6 +171,14 @@ void launch_kbuild_sym(int kernel, const T* Xs, int64_t n, int64_t npad, int d, 
 }
 
 template <typename T>
+void launch_kbuild_sym_w(int kernel, const T* Xs, int64_t n, int64_t npad, int d, double sf2, const T* w, double sn2,
+                         double jitter, T* K, int64_t ld, hipStream_t st) {
+  const int64_t TT = npad / KT;
+  const int64_t nblocks = TT * (TT + 1) / 2;
+  cov::dispatch(kernel, [&](auto fam) { dispatch_d_w<T, fam>(Xs, n, d, nblocks, (int)TT, sf2, w, sn2, jitter, K, ld, st); });
+}
+
+template <typename T>
 void launch_kbuild_cross(int kernel, const T* As, int64_t m, int64_t mpad, const T* Bs, int64_t n,
                          int64_t npad, int d, double sf2, T* K, int64_t ld, hipStream_t st) {
   const int64_t tm = mpad / KT, tn = npad / KT;
@@ -157,6 +190,8 @@ void launch_kbuild_cross(int kernel, const T* As, int64_t m, int64_t mpad, const
                                        hipStream_t);                                                  \
   template void launch_kbuild_sym<T>(int, const T*, int64_t, int64_t, int, double, double, T*,        \
                                      int64_t, hipStream_t);                                           \
+  template void launch_kbuild_sym_w<T>(int, const T*, int64_t, int64_t, int, double, const T*, double, double, T*, \
+                                       int64_t, hipStream_t);                                         \
   template void launch_kbuild_cross<T>(int, const T*, int64_t, int64_t, const T*, int64_t, int64_t,   \
                                        int, double, T*, int64_t, hipStream_t);
 GPX_INSTANTIATE_KBUILD(double)

@@ -230,6 +230,25 @@ __global__ __launch_bounds__(256) void add_scalar_kernel(T* p, int64_t count, do
     p[i] += (T)v;
 }
 
+template <typename T>
+__global__ __launch_bounds__(256) void fill_kernel(T* p, int64_t count, double v) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < count; i += (int64_t)gridDim.x * 256)
+    p[i] = (T)v;
+}
+
+// per-observation noise weights must be finite and >= 0: *bad = 1 if one of w[0..n) is not (a NaN fails the first
+// comparison), else 0.  One workgroup: a few thousand to a few hundred thousand numbers, read once per gpx_set_noise_weights.
+template <typename T>
+__global__ __launch_bounds__(256) void check_weights_kernel(const T* __restrict__ w, int64_t n, int* __restrict__ bad) {
+  int b = 0;
+  for (int64_t i = threadIdx.x; i < n; i += 256) {
+    const T v = w[i];
+    if (!(v >= (T)0) || !(v - v == (T)0)) b = 1;  // (inf - inf is NaN)
+  }
+  b = __syncthreads_or(b);
+  if (threadIdx.x == 0) *bad = b ? 1 : 0;
+}
+
 // dst[i] = op over q < P of src[q * count + i], in rank order (in-process transport: every rank
 // that reduces gets bit-identical results); op 0 = sum, 1 = min
 template <typename T>
@@ -299,6 +318,18 @@ void launch_add_scalar(T* p, int64_t count, double v, hipStream_t st) {
   if (count <= 0) return;
   const int64_t bx = (count + 255) / 256;
   hipLaunchKernelGGL(add_scalar_kernel<T>, dim3((unsigned)(bx > 1024 ? 1024 : bx)), dim3(256), 0, st, p, count, v);
+}
+
+template <typename T>
+void launch_fill(T* p, int64_t count, double v, hipStream_t st) {
+  if (count <= 0) return;
+  const int64_t bx = (count + 255) / 256;
+  hipLaunchKernelGGL(fill_kernel<T>, dim3((unsigned)(bx > 1024 ? 1024 : bx)), dim3(256), 0, st, p, count, v);
+}
+
+template <typename T>
+void launch_check_weights(const T* w, int64_t n, int* bad, hipStream_t st) {
+  hipLaunchKernelGGL(check_weights_kernel<T>, dim3(1), dim3(256), 0, st, w, n, bad);
 }
 
 template <typename T>
@@ -455,6 +486,8 @@ void launch_logdet(const T* A, int64_t lda, int64_t n, double* out, hipStream_t 
   template void launch_scatter_local<T>(const T*, int64_t, T*, int64_t, int, int, Deal, int, int, hipStream_t); \
   template void launch_add_block<T>(T*, int64_t, const T*, int64_t, int, int, double, hipStream_t);        \
   template void launch_add_scalar<T>(T*, int64_t, double, hipStream_t);                                    \
+  template void launch_fill<T>(T*, int64_t, double, hipStream_t);                                          \
+  template void launch_check_weights<T>(const T*, int64_t, int*, hipStream_t);                             \
   template void launch_reduce_ranks<T>(const T*, T*, int, int64_t, int, hipStream_t);                      \
   template void launch_logdet_acc<T>(const T*, int64_t, int, double*, hipStream_t);
 GPX_INSTANTIATE_MISC(double)

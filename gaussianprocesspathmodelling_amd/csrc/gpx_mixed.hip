@@ -54,7 +54,8 @@ __global__ __launch_bounds__(256) void kmatvec_kernel(const double* __restrict__
                                                      const double* __restrict__ Bs, int64_t npad, int d_rt,
                                                      double sf2, double diag, const double* __restrict__ y,
                                                      const double* __restrict__ alphaT, int64_t lda, int k,
-                                                     double sign, double* __restrict__ outT, int64_t ldo) {
+                                                     double sign, double* __restrict__ outT, int64_t ldo,
+                                                     const double* __restrict__ wv, double wsn2, double wjit) {
   // sized by the instantiation (round 3): with KMAX-sized buffers (146 KB) ONE workgroup fitted a CU — one wave per
   // SIMD walking a latency chain of global load -> barrier -> 16 kernel values -> barrier; 3.5 KB at k = 1, d = 3
   __shared__ double xb[64 * (D > 0 ? D : MAX_D)];
@@ -106,7 +107,10 @@ __global__ __launch_bounds__(256) void kmatvec_kernel(const double* __restrict__
         double v = acc[c];
         for (int q = 0; q < 3; ++q) v += red[(q * 64 + lane) * KC + c];
         double out = 0.0;
-        if (i < m) out = (y ? y[i * k + c] : 0.0) + sign * (v + diag * alphaT[(int64_t)c * lda + i]);
+        if (i < m) {  // wv: per-observation noise, the diagonal the weighted kernel build put there
+          const double dg = wv ? wsn2 * wv[i] + wjit : diag;
+          out = (y ? y[i * k + c] : 0.0) + sign * (v + dg * alphaT[(int64_t)c * lda + i]);
+        }
         outT[(int64_t)c * ldo + i] = out;
       }
   }
@@ -292,32 +296,32 @@ void launch_few_kc(bool cols, bool assign, T* out, int64_t ldo, const T* M, int6
 template <int KERNEL, int KC>
 void launch_kmatvec_kc(const double* As, int64_t m, int64_t mpad, const double* Bs, int64_t npad, int d, double sf2,
                        double diag, const double* y, const double* alphaT, int64_t lda, int k, double sign,
-                       double* outT, int64_t ldo, hipStream_t st) {
+                       double* outT, int64_t ldo, const double* wv, double wsn2, double wjit, hipStream_t st) {
   dim3 grid((unsigned)(mpad / 64)), block(256);
   if (d == 3)
-    hipLaunchKernelGGL((kmatvec_kernel<KERNEL, 3, KC>), grid, block, 0, st, As, m, Bs, npad, d, sf2, diag, y, alphaT, lda, k, sign, outT, ldo);
+    hipLaunchKernelGGL((kmatvec_kernel<KERNEL, 3, KC>), grid, block, 0, st, As, m, Bs, npad, d, sf2, diag, y, alphaT, lda, k, sign, outT, ldo, wv, wsn2, wjit);
   else
-    hipLaunchKernelGGL((kmatvec_kernel<KERNEL, 0, KC>), grid, block, 0, st, As, m, Bs, npad, d, sf2, diag, y, alphaT, lda, k, sign, outT, ldo);
+    hipLaunchKernelGGL((kmatvec_kernel<KERNEL, 0, KC>), grid, block, 0, st, As, m, Bs, npad, d, sf2, diag, y, alphaT, lda, k, sign, outT, ldo, wv, wsn2, wjit);
 }
 
 template <int KERNEL>
 void launch_kmatvec_k(const double* As, int64_t m, int64_t mpad, const double* Bs, int64_t npad, int d, double sf2,
                       double diag, const double* y, const double* alphaT, int64_t lda, int k, double sign,
-                      double* outT, int64_t ldo, hipStream_t st) {
+                      double* outT, int64_t ldo, const double* wv, double wsn2, double wjit, hipStream_t st) {
   if (k == 1)
-    launch_kmatvec_kc<KERNEL, 1>(As, m, mpad, Bs, npad, d, sf2, diag, y, alphaT, lda, k, sign, outT, ldo, st);
+    launch_kmatvec_kc<KERNEL, 1>(As, m, mpad, Bs, npad, d, sf2, diag, y, alphaT, lda, k, sign, outT, ldo, wv, wsn2, wjit, st);
   else if (k == 2)
-    launch_kmatvec_kc<KERNEL, 2>(As, m, mpad, Bs, npad, d, sf2, diag, y, alphaT, lda, k, sign, outT, ldo, st);
+    launch_kmatvec_kc<KERNEL, 2>(As, m, mpad, Bs, npad, d, sf2, diag, y, alphaT, lda, k, sign, outT, ldo, wv, wsn2, wjit, st);
   else
-    launch_kmatvec_kc<KERNEL, KMAX>(As, m, mpad, Bs, npad, d, sf2, diag, y, alphaT, lda, k, sign, outT, ldo, st);
+    launch_kmatvec_kc<KERNEL, KMAX>(As, m, mpad, Bs, npad, d, sf2, diag, y, alphaT, lda, k, sign, outT, ldo, wv, wsn2, wjit, st);
 }
 
 }  // namespace
 
 void launch_kmatvec(int kernel, const double* As, int64_t m, int64_t mpad, const double* Bs, int64_t npad, int d,
                     double sf2, double diag, const double* y, const double* alphaT, int64_t lda, int k,
-                    double sign, double* outT, int64_t ldo, hipStream_t st) {
-  cov::dispatch(kernel, [&](auto fam) { launch_kmatvec_k<fam>(As, m, mpad, Bs, npad, d, sf2, diag, y, alphaT, lda, k, sign, outT, ldo, st); });
+                    double sign, double* outT, int64_t ldo, hipStream_t st, const double* wv, double wsn2, double wjit) {
+  cov::dispatch(kernel, [&](auto fam) { launch_kmatvec_k<fam>(As, m, mpad, Bs, npad, d, sf2, diag, y, alphaT, lda, k, sign, outT, ldo, wv, wsn2, wjit, st); });
 }
 
 // rows (cols = false): out[c][i] (=|-=) sum_j M[i][j] v[c][j];  columns (cols = true): ... sum_j M[j][i] v[c][j]

@@ -137,7 +137,8 @@ __global__ __launch_bounds__(256) void block_score_kernel(const double* __restri
                                                          const T* __restrict__ Qs, int d, const T* __restrict__ ys,
                                                          const T* __restrict__ mean, int k, int Lg, double sf2,
                                                          double diag_add, T* __restrict__ logp, T* __restrict__ maha,
-                                                         T* __restrict__ logdet, int64_t g0, int* __restrict__ bad) {
+                                                         T* __restrict__ logdet, int64_t g0, int* __restrict__ bad,
+                                                         const T* __restrict__ wq) {
   __shared__ double Sm[64 * SLD];  // S, then its Cholesky factor (lower)
   __shared__ double Wm[64 * SLD];  // residuals r (Lg x k), then L^-1 r
   __shared__ double piv;
@@ -155,7 +156,7 @@ __global__ __launch_bounds__(256) void block_score_kernel(const double* __restri
       r2 += df * df;
     }
     double v = cov::value<KERNEL, double>(r2, sf2);
-    if (i == j) v += diag_add;
+    if (i == j) v += wq ? diag_add * (double)wq[row0 + i] : diag_add;  // per-point weight of the added diagonal
     Sm[i * SLD + j] = v - gram;
   }
   for (int e = tid; e < Lg * k; e += 256) {
@@ -240,19 +241,19 @@ void launch_block_gram(const T* VT, int64_t ld, int64_t nblk, int Lg, int64_t np
 template <typename T>
 void launch_block_score(int kernel, const double* part, int64_t nblk, int Lg, int64_t npad, const T* Qs, int d,
                         const T* ys, const T* mean, int k, double sf2, double diag_add, T* logp, T* maha, T* logdet,
-                        int64_t g0, int* bad, hipStream_t st) {
+                        int64_t g0, int* bad, hipStream_t st, const T* wq) {
   debug_delay(st);
   const int S = score_slices(npad), LP = score_lp(Lg);
   cov::dispatch(kernel, [&](auto fam) {
     hipLaunchKernelGGL((block_score_kernel<T, fam>), dim3((unsigned)nblk), dim3(256), 0, st, part, S, LP, Qs, d, ys, mean,
-                       k, Lg, sf2, diag_add, logp, maha, logdet, g0, bad);
+                       k, Lg, sf2, diag_add, logp, maha, logdet, g0, bad, wq);
   });
 }
 
 #define GPX_INSTANTIATE_SCORE(T)                                                                                       \
   template void launch_block_gram<T>(const T*, int64_t, int64_t, int, int64_t, double*, hipStream_t);                 \
   template void launch_block_score<T>(int, const double*, int64_t, int, int64_t, const T*, int, const T*, const T*,  \
-                                      int, double, double, T*, T*, T*, int64_t, int*, hipStream_t);
+                                      int, double, double, T*, T*, T*, int64_t, int*, hipStream_t, const T*);
 GPX_INSTANTIATE_SCORE(double)
 GPX_INSTANTIATE_SCORE(float)
 

@@ -4,7 +4,7 @@ This is the Python host side of the hot path.  The upstream ref
 (``GPmap.py``) has no such class — its public names are ``trajectory``,
 ``trajectories``, ``readcsvfile`` (``GPmap.py:12,28,178``) — so the surface is the one
 BASELINE.json's north_star names: hyper-parameters are fixed inputs, ``fit(X, y)``
-factorises ``K = sf2 k(X,X) + (sn2 + jitter) I`` and solves for ``alpha``,
+factorises ``K = sf2 k(X,X) + (sn2 + jitter) I`` (``noise_weights``: ``+ diag(sn2 w_i + jitter)``) and solves for ``alpha``,
 ``predict(Xs)`` returns the posterior mean and (latent) variance.
 
 All arithmetic runs in ``csrc/libgpx.so`` (hand-written HIP for gfx950) through the
@@ -35,7 +35,10 @@ class GP:
         ``GpxError`` for it.  Every other call runs for all four.
     lengthscale : float or array of d floats (ARD)
     variance : signal variance sf2
-    noise : observation-noise variance sn2 (added to the diagonal)
+    noise : observation-noise variance sn2 (added to the diagonal).  ``fit(..., noise_weights=w)`` makes it the LEVEL of a
+        per-observation noise ``sn2 * w_i`` (``w_i >= 0``, one per observation, shared by the targets; ``w_i = 0`` is an
+        exact observation); absolute variances are ``noise=1.0, noise_weights=variances``.  ``lml_gradient`` and
+        ``optimize`` learn the level, the weights are fixed data.  One device only (not ``devices=`` / ``world=``).
     jitter : extra diagonal term; default 1e-10 * variance
     dtype : "float64" | "float32" (everything, including the factorisation, in fp32:
         the precision study of BASELINE.json configs[4]; not a 1e-6 path) | "mixed" (float64 in and
@@ -124,6 +127,7 @@ class GP:
             raise _abi.GpxError(rc, self._lib.gpx_last_error(None).decode())
         self._h = h
         self._fitted = False
+        self._weights_set = False  # gpx_set_noise_weights holds a vector for the next fits
         self._alpha = None
         self.info_ = 0
         self.jitter_used_ = self.jitter
@@ -212,8 +216,40 @@ class GP:
         arr = np.ascontiguousarray(a, dtype=self._np_dtype)
         return C.c_void_p(arr.ctypes.data), _abi.MEM_HOST, arr, None, arr.shape
 
+    def _weights_input(self, w, n, kind, name, like):
+        """per-point weights ``w`` (n,) -> pointer (None for ``w is None``) and keepalive; same kind as ``like``"""
+        if w is None:
+            return None, None
+        pw, kw, keepw, devw, sw = self._as_input(w, name)
+        if tuple(sw) != (n,):
+            raise ValueError(f"{name} must be ({n},), one weight per point")
+        if kw != kind:
+            raise ValueError(f"{name} must be of the same kind as {like}: both host arrays or both device tensors")
+        return pw, keepw
+
+    def _set_noise_weights(self, w, n, kind):
+        """the weights of the fits that follow (``gpx_set_noise_weights``); None clears them.  A refused vector
+        (wrong length or kind: ValueError; negative or non-finite: GpxError) leaves the handle as it was."""
+        pw, keepw = self._weights_input(w, n, kind, "noise_weights", "X")
+        if pw is None and not self._weights_set:
+            return  # (a model that never had weights makes no call at all)
+        self._check(self._lib.gpx_set_noise_weights(self._h, pw, n if pw is not None else 0, kind))
+        self._weights_set = pw is not None
+
+    @property
+    def noise_weights_(self):
+        """Per-observation noise weights of the fitted model (N,), appended points included; ones without any."""
+        if not self._fitted:
+            raise RuntimeError("no fit")
+        out = np.empty((self._N,), dtype=self._np_dtype)
+        self._check(self._lib.gpx_get_noise_weights(self._h, C.c_void_p(out.ctypes.data)))
+        return out
+
     # -- API ----------------------------------------------------------------------------
-    def fit(self, X, y):
+    def fit(self, X, y, noise_weights=None):
+        """Factorise and solve.  ``noise_weights`` (N,), of the same kind as ``X`` (NumPy array or device tensor): the
+        diagonal of K gets ``noise * w_i + jitter`` instead of ``noise + jitter``; None (the default) means none — also
+        after a weighted fit."""
         px, kx, keepx, devx, sx = self._as_input(X, "X")
         py, ky, keepy, devy, sy = self._as_input(y, "y")
         if len(sx) != 2:
@@ -226,6 +262,7 @@ class GP:
         k = 1 if len(sy) == 1 else sy[1]
         if self.lengthscale.size not in (1, d):
             raise ValueError("lengthscale must be scalar or have d entries")
+        self._set_noise_weights(noise_weights, N, kx)  # (refused: the model is as it was)
         self._y1d = len(sy) == 1
         self._N, self._d, self._k = N, d, k
         self._alpha = None
@@ -252,14 +289,16 @@ class GP:
         self.log_det_ = float(ld.value)
         return self
 
-    def update(self, X_new, y_new):
+    def update(self, X_new, y_new, noise_weights=None):
         """Append observations to the fitted model without factorising the old ones again (``gpx_append``): afterwards
         the model is, to rounding, what ``fit`` of the concatenated data with the same hyper-parameters and the jitter
         the fit needed would be.  Inputs as for :meth:`fit`: NumPy arrays or device tensors, both of the same kind,
         ``y_new`` 1-D or (m, k) as fitted.  Only the rows of the new points and the last, partly filled panel of the
         Cholesky factor are computed (include/gpx.h); :meth:`reserve` keeps the factor from being moved.  Raises
         ``numpy.linalg.LinAlgError`` when the kernel matrix with the new points is not positive definite: the model is
-        then unchanged (the previous fit, every call valid).  float64 / float32 models on one device.  Returns ``self``."""
+        then unchanged (the previous fit, every call valid).  float64 / float32 models on one device.
+        ``noise_weights`` (m,): the new points' noise weights (``gpx_append_weighted``), of the same kind as ``X_new``;
+        None appends with weight 1, on a weighted model too.  Returns ``self``."""
         if not self._fitted:
             raise RuntimeError("update() before a successful fit()")
         px, kx, keepx, devx, sx = self._as_input(X_new, "X_new")
@@ -275,10 +314,14 @@ class GP:
             raise ValueError("y_new must be (m,)" if self._y1d else f"y_new must be (m, {self._k})")
         if kx != ky:
             raise ValueError("X_new and y_new must both be host arrays or both be device tensors")
+        pw, keepw = self._weights_input(noise_weights, m, kx, "noise_weights", "X_new")
         if m == 0:
             return self
         info = C.c_int64(0)
-        self._check(self._lib.gpx_append(self._h, px, py, m, kx, C.byref(info)))
+        if pw is None:
+            self._check(self._lib.gpx_append(self._h, px, py, m, kx, C.byref(info)))
+        else:
+            self._check(self._lib.gpx_append_weighted(self._h, px, py, pw, m, kx, C.byref(info)))
         if info.value != 0:
             raise np.linalg.LinAlgError(
                 f"kernel matrix with the new points not positive definite (first bad pivot {info.value}): the model "
@@ -296,19 +339,20 @@ class GP:
         self._check(self._lib.gpx_reserve(self._h, int(n)))
         return self
 
-    def fit_predict(self, X, y, Xs, include_noise=False):
+    def fit_predict(self, X, y, Xs, include_noise=False, noise_weights=None):
         """``fit(X, y)`` and ``predict(Xs)`` (mean and variance) as ONE factorisation pass: the cross-kernel rows
         of the query points ride through the blocked Cholesky as bordered rows (``gpx_fit_predict``), so the
         variance solve is part of the trailing updates instead of a pass of its own — the small-N schedule
         (N = 8192: the updates' idle CUs take the work).  The model is fitted afterwards as after ``fit``.
         On a shard or a device group every rank's slice of the query points rides through ITS part of the sharded
-        factorisation (collective: every rank of a shard makes the call).  ``dtype="mixed"`` takes the two calls."""
+        factorisation (collective: every rank of a shard makes the call).  ``dtype="mixed"`` takes the two calls.
+        ``noise_weights`` as for :meth:`fit`; ``include_noise`` as for :meth:`predict`."""
         fused = self.dtype in ("float64", "float32")
         pq, kq, keepq, devq, sq = self._as_input(Xs, "Xs")
         px, kx, keepx, devx, sx = self._as_input(X, "X")
         py, ky, keepy, devy, sy = self._as_input(y, "y")
         if not fused or len(sq) != 2 or not (kx == ky == kq):
-            mean, var = self.fit(X, y).predict(Xs, include_noise=include_noise)
+            mean, var = self.fit(X, y, noise_weights=noise_weights).predict(Xs, include_noise=include_noise)
             return mean, var
         if len(sx) != 2:
             raise ValueError("X must be (N, d)")
@@ -321,6 +365,7 @@ class GP:
         if self.lengthscale.size not in (1, d):
             raise ValueError("lengthscale must be scalar or have d entries")
         M = sq[0]
+        self._set_noise_weights(noise_weights, N, kx)
         self._y1d = len(sy) == 1
         self._N, self._d, self._k = N, d, k
         self._alpha = None
@@ -345,7 +390,7 @@ class GP:
             if rc in (_abi.E_UNSUPPORTED, _abi.E_NOMEM):
                 # the library's own limits decide (its batch cap honours GPX_PRED_BATCH; M more bordered rows of K and
                 # of the panel buffers may not fit beside the factor): the documented fallback is the two calls
-                return self.fit(X, y).predict(Xs, include_noise=include_noise)
+                return self.fit(X, y, noise_weights=noise_weights).predict(Xs, include_noise=include_noise)
             self._check(rc)
             self.info_ = int(info.value)
             if self.info_ == 0:
@@ -368,8 +413,10 @@ class GP:
         """Posterior at the query points ``Xs`` (M, d): ``mean`` ((M,) for a 1-D ``y``, else (M, k)) and, with
         ``return_var``, the per-point variance (M,).  ``return_cov=True`` returns ``(mean, cov)`` instead, ``cov`` the
         joint (M, M) posterior covariance of the latent function (``gpx_predict_cov``: one SYRK more than the variance;
-        the same for every target column), with ``noise`` on its diagonal when ``include_noise``.  NumPy in, NumPy out;
-        a device tensor in, device tensors out."""
+        the same for every target column), with ``noise`` on its diagonal when ``include_noise``.  ``include_noise``
+        adds ``noise`` times 1 also on a model fitted with ``noise_weights``: a query point has no weight of its own
+        (scale the latent variance yourself for another one).  NumPy in, NumPy out; a device tensor in, device tensors
+        out."""
         if not self._fitted:
             raise RuntimeError("predict() before a successful fit()")
         pq, kq, keepq, devq, sq = self._as_input(Xs, "Xs")
@@ -428,7 +475,7 @@ class GP:
             return (mean, var, dmean, dvar) if return_var else (mean, dmean)
         return (dmean, dvar) if return_var else dmean
 
-    def score_blocks(self, Xs, ys, block, include_noise=True, return_parts=False, on_bad="raise"):
+    def score_blocks(self, Xs, ys, block, include_noise=True, return_parts=False, on_bad="raise", noise_weights=None):
         """Joint log predictive density of whole blocks of query points (``gpx_score_blocks``): ``Xs`` (G * block, d)
         holds G blocks of ``block`` consecutive points (a path = a block, 1 <= block <= 64), ``ys`` their observed
         targets ((G * block,) for a 1-D ``y``, else (G * block, k)).  Returns ``logp`` ((G,) for a 1-D fit, else
@@ -439,7 +486,9 @@ class GP:
         ever formed, and a block's numbers do not depend on the other blocks of the call.  A block whose covariance
         is not positive definite (possible without the noise term) raises ``numpy.linalg.LinAlgError`` naming the
         first such block; ``on_bad="nan"`` returns the arrays instead, that block's entries NaN and
-        ``score_info_`` its 1-based index.  NumPy in, NumPy out; device tensors in, device tensors out."""
+        ``score_info_`` its 1-based index.  ``noise_weights`` (G * block,), of the same kind as ``Xs``: query point i
+        gets ``noise * w_i`` on the diagonal instead of ``noise`` (``gpx_score_blocks_weighted``; nothing without
+        ``include_noise``).  NumPy in, NumPy out; device tensors in, device tensors out."""
         if not self._fitted:
             raise RuntimeError("score_blocks() before a successful fit()")
         if on_bad not in ("raise", "nan"):
@@ -468,9 +517,15 @@ class GP:
         maha = self._empty(oshape, devq) if return_parts else None
         logdet = self._empty((G,), devq) if return_parts else None
         p = lambda a: None if a is None else self._ptr(a)  # noqa: E731
+        pw, keepw = self._weights_input(noise_weights, M, kq, "noise_weights", "Xs")
         info = C.c_int64(0)
-        self._check(self._lib.gpx_score_blocks(self._h, pq, py, G, Lg, self.noise if include_noise else 0.0,
-                                               p(logp), p(maha), p(logdet), kq, C.byref(info)))
+        diag_add = self.noise if include_noise else 0.0
+        if pw is None:
+            self._check(self._lib.gpx_score_blocks(self._h, pq, py, G, Lg, diag_add, p(logp), p(maha), p(logdet), kq,
+                                                   C.byref(info)))
+        else:
+            self._check(self._lib.gpx_score_blocks_weighted(self._h, pq, py, pw, G, Lg, diag_add, p(logp), p(maha),
+                                                            p(logdet), kq, C.byref(info)))
         self.score_info_ = int(info.value)
         if self.score_info_ and on_bad == "raise":
             raise np.linalg.LinAlgError(
@@ -608,7 +663,8 @@ class GP:
     def lml_gradient(self):
         """``(lml, grad)`` of the last ``fit``: the log marginal likelihood and its analytic
         gradient w.r.t. the LOG hyper-parameters, ordered (lengthscale[0..n_ls), variance, noise)
-        — R&W eq. 5.9, 1/2 tr((alpha alpha^T - K^-1) dK/dtheta), computed on the GPU by
+        — R&W eq. 5.9, 1/2 tr((alpha alpha^T - K^-1) dK/dtheta) (with ``noise_weights``: dK/dlog noise =
+        noise diag(w)), computed on the GPU by
         ``gpx_lml_grad`` (about two more factorisations' worth of MFMA work: L^-T, then K^-1
         formed and consumed tile by tile, never stored).  fp64 models.  Sharded ones (``devices=`` or
         ``world=``): with the replicated factor L^-T is built in row blocks dealt over the GPUs,
@@ -624,7 +680,7 @@ class GP:
         return float(lml.value), grad
 
     def optimize(self, X, y, params=("lengthscale", "variance", "noise"), bounds=(1e-4, 1e4), maxiter=40,
-                 rel_step=1e-4, jac="analytic"):
+                 rel_step=1e-4, jac="analytic", noise_weights=None):
         """Fit the hyper-parameters by maximising the log marginal likelihood (SURVEY.md §8f
         rank 1: the natural step after ``fit``; the reference has no counterpart).
 
@@ -635,7 +691,8 @@ class GP:
         to ``jac="3-point"`` central differences: 2 p extra fits per gradient.
         Non-positive-definite trial points count as very bad, they do not raise.  Leaves the
         model fitted at the best point found and returns scipy's result (``.fun`` = minus the
-        log marginal likelihood there)."""
+        log marginal likelihood there).  ``noise_weights`` as for :meth:`fit`: every fit of the search, the final one
+        included, is made with them; ``noise`` is then the level that is learnt."""
         from scipy.optimize import minimize
         names = [p for p in ("lengthscale", "variance", "noise") if p in params]
         if not names or len(names) != len(tuple(params)):
@@ -665,7 +722,7 @@ class GP:
             # sharded: the gradient needs the replicated-factor mode, which the library picks from N
             # and the card's memory at fit time — ask it once (every rank gets the same answer)
             try:
-                self.fit(X, y)
+                self.fit(X, y, noise_weights=noise_weights)
                 self.lml_gradient()
             except _abi.GpxError:
                 analytic = False
@@ -683,7 +740,7 @@ class GP:
             unpack(v)
             g = np.zeros(len(cols))
             try:
-                self.fit(X, y)
+                self.fit(X, y, noise_weights=noise_weights)
                 if analytic:
                     try:
                         lml, full = self.lml_gradient()
@@ -719,6 +776,6 @@ class GP:
         except _NoAnalyticGradient:
             res = search(best["v"], False)   # from the best point the analytic steps reached
         unpack(best["v"])
-        self.fit(X, y)
+        self.fit(X, y, noise_weights=noise_weights)
         res.x, res.fun = best["v"], best["f"]
         return res

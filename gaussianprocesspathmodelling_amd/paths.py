@@ -240,12 +240,23 @@ class PathModel:
     """GP model of one cluster of paths: inputs (by default the time stamp, mapped to [0, 1]) ->
     (x, y) as two targets sharing ONE Cholesky factor.  Targets are
     standardised per column before the fit (the GP prior has zero mean) and mapped back by
-    :meth:`predict`."""
+    :meth:`predict`.  ``step_weights`` (L,), or None: the per-step noise weights the model was fitted with
+    (``fit_path_models(step_noise=True)``); :meth:`add_paths` and :meth:`log_likelihood` then use them too."""
 
-    def __init__(self, gp, keys, in_lo, in_span, y_mean, y_std, inputs, targets):
+    def __init__(self, gp, keys, in_lo, in_span, y_mean, y_std, inputs, targets, step_weights=None):
         self.gp, self.keys = gp, list(keys)
         self.in_lo, self.in_span, self.y_mean, self.y_std = in_lo, in_span, y_mean, y_std
         self.inputs, self.targets = tuple(inputs), tuple(targets)
+        self.step_weights = None if step_weights is None else np.asarray(step_weights, dtype=np.float64)
+
+    def _tiled_weights(self, n_rows, what):
+        """the step weights repeated for n_rows / L whole paths (None without step weights)"""
+        if self.step_weights is None:
+            return None
+        L = len(self.step_weights)
+        if n_rows % L:
+            raise ValueError(f"{what}: the model has per-step noise weights for paths of {L} points")
+        return np.tile(self.step_weights, n_rows // L)
 
     def _queries(self, q):
         q = np.asarray(q, dtype=np.float64)
@@ -306,14 +317,17 @@ class PathModel:
         """Append the paths ``keys`` of ``trajs`` to this cluster's model (``GP.update``: the factor of the paths already
         modelled is kept).  Inputs and targets go through the normalisation fixed at the first fit (``in_lo``,
         ``in_span``, ``y_mean``, ``y_std``), so the result is the GP of all the cluster's paths under that normalisation.
+        A model with ``step_weights`` appends with them, tiled over the new paths (which must have its path length).
         Extends ``keys``; returns ``self``."""
         keys = list(keys)
         if not keys:
             return self
+        if self.step_weights is not None and any(len(trajs.pathdict[q]) != len(self.step_weights) for q in keys):
+            raise ValueError(f"add_paths: the model has per-step noise weights for paths of {len(self.step_weights)} points")
         X, Y, _ = to_gp_inputs(trajs, keys, inputs=self.inputs, targets=self.targets, normalise=False)
         Xn = np.ascontiguousarray((X - self.in_lo) / self.in_span)
         Yn = np.ascontiguousarray((Y - self.y_mean) / self.y_std)
-        self.gp.update(Xn, Yn)
+        self.gp.update(Xn, Yn, noise_weights=self._tiled_weights(len(Xn), "add_paths"))
         self.keys.extend(keys)
         return self
 
@@ -323,24 +337,44 @@ class PathModel:
         posterior of its L points (``GP.score_blocks`` on the device: the points of a path are strongly correlated, so
         this is not the sum of the per-point densities).  Inputs and targets go through the model's normalisation; the
         Jacobian of the standardisation, ``-L log y_std[c]``, is included, so models with different standardisations
-        are comparable."""
+        are comparable.  A model with ``step_weights`` scores with them (point s of a path gets ``noise * w_s``); paths
+        of another length than its own then raise ``ValueError``."""
         arr = np.asarray(paths_txy, dtype=np.float64)
         if arr.ndim != 3 or arr.shape[2] != 3 or arr.shape[0] == 0:
             raise ValueError("paths must be a non-empty (P, L, 3) array of (t, x, y)")
         P, L = arr.shape[:2]
+        if self.step_weights is not None and L != len(self.step_weights):
+            raise ValueError(f"log_likelihood: the model has per-step noise weights for paths of {len(self.step_weights)} "
+                             f"points, these have {L}")
         col = {"t": 0, "x": 1, "y": 2}
         flat = arr.reshape(-1, 3)
         Xn = np.ascontiguousarray((flat[:, [col[c] for c in self.inputs]] - self.in_lo) / self.in_span)
         Yn = np.ascontiguousarray((flat[:, [col[c] for c in self.targets]] - self.y_mean) / self.y_std)
-        logp = self.gp.score_blocks(Xn, Yn, L, include_noise=include_noise)
+        logp = self.gp.score_blocks(Xn, Yn, L, include_noise=include_noise,
+                                    noise_weights=self._tiled_weights(P * L, "log_likelihood"))
         return np.asarray(logp, dtype=np.float64).reshape(P, -1) - L * np.log(self.y_std)[None, :]
 
     def close(self):
         self.gp.close()
 
 
+STEP_WEIGHT_FLOOR = 1e-3
+
+
+def step_noise_weights(Yn, n_paths):
+    """Per-step noise weights of one cluster: ``Yn`` (n_paths * L, k) standardised targets, path after path.  The
+    weight of step s is the variance over the paths of the targets at step s (about their mean path), averaged over
+    the targets, divided by its mean over the steps and floored at 1e-3 — the spread of the cluster along the path,
+    relative to its average.  (L,); all ones for a single path (or paths without any spread)."""
+    Y3 = np.asarray(Yn, dtype=np.float64).reshape(n_paths, -1, Yn.shape[-1] if np.ndim(Yn) > 1 else 1)
+    v = Y3.var(axis=0).mean(axis=1)
+    if n_paths < 2 or not v.mean() > 0:
+        return np.ones(Y3.shape[1])
+    return np.maximum(v / v.mean(), STEP_WEIGHT_FLOOR)
+
+
 def fit_path_models(trajs, clusters, inputs=("t",), targets=("x", "y"), devices=None, optimize=False,
-                    lengthscale=0.25, variance=1.0, noise=0.05, **gp_kwargs):
+                    lengthscale=0.25, variance=1.0, noise=0.05, step_noise=False, **gp_kwargs):
     """One exact GP per cluster of ``clusters`` = {cluster id: [path ids]} — what
     :func:`kmeans` (``kmeansclustering``, GPmap.py:36-93) returns — modelling the cluster's paths
     as (x(t), y(t)); the modelling step the reference's title names and its clustering prepares
@@ -350,7 +384,10 @@ def fit_path_models(trajs, clusters, inputs=("t",), targets=("x", "y"), devices=
     parts"): cluster i is fitted on ``devices[i % len(devices)]`` (an int n = devices 0..n-1;
     default: the current device), one host thread per device, no data-path collective.  With
     ``optimize`` the hyper-parameters of each model are fitted by :meth:`GP.optimize` (analytic
-    gradient) first.  Returns {cluster id: :class:`PathModel`}; empty clusters are skipped."""
+    gradient) first.  ``step_noise``: the paths of a cluster are tight in some places and spread out in others, so each
+    cluster's observations get per-step noise weights (:func:`step_noise_weights`, tiled over its paths; the paths
+    of a cluster have one length); ``noise`` stays the level, and the model keeps them as ``step_weights``.
+    Returns {cluster id: :class:`PathModel`}; empty clusters are skipped."""
     import threading
     from concurrent.futures import ThreadPoolExecutor
     from .gp import GP
@@ -383,15 +420,17 @@ def fit_path_models(trajs, clusters, inputs=("t",), targets=("x", "y"), devices=
         Yn = np.ascontiguousarray((Y - mu) / sd)
         gp = GP(lengthscale=lengthscale, variance=variance, noise=noise, device=devs[slot % len(devs)],
                 **gp_kwargs)
+        sw = step_noise_weights(Yn, len(keys)) if step_noise else None
+        w = None if sw is None else np.tile(sw, len(keys))
         try:
             if optimize:
-                gp.optimize(X, Yn)                 # leaves the model fitted at the best point
+                gp.optimize(X, Yn, noise_weights=w)  # leaves the model fitted at the best point
             else:
-                gp.fit(X, Yn)
+                gp.fit(X, Yn, noise_weights=w)
         except Exception:
             gp.close()
             raise
-        return cid, PathModel(gp, keys, lo, span, mu, sd, inputs, targets)
+        return cid, PathModel(gp, keys, lo, span, mu, sd, inputs, targets, step_weights=sw)
 
     by_dev = [[] for _ in devs]                    # one worker per device, its clusters in order
     for i, (cid, keys) in enumerate(jobs):

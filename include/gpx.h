@@ -275,6 +275,39 @@ int gpx_reserve(gpx_handle* h, int64_t capacity);
  * pointer changes only when a fit or an append has to reallocate. */
 int gpx_factor_info(gpx_handle* h, const void** factor, int64_t* ld, int64_t* capacity);
 
+/* ---- per-observation noise weights (additive to ABI v6) ---------------------------------------------------------------
+ * Model: K = sf2 k(X,X) + diag(sn2 w_i + jitter), one weight w_i >= 0 per observation, shared by the k targets.  w = 1
+ * everywhere is the model of a handle that never calls this, bit for bit; w_i = 0 is an exact observation (only the jitter
+ * on its diagonal entry).  sn2 stays the level gpx_lml_grad differentiates: dK / dlog sn2 = sn2 diag(w), so its noise entry
+ * is 1/2 sn2 sum_i w_i (sum_c alpha_ic^2 - k (K^-1)_ii); the weights are fixed data.  Absolute variances: sn2 = 1, w = them.
+ *
+ * gpx_set_noise_weights copies n weights (the handle's element type: double for GPX_F64 / GPX_MIXED, float for GPX_F32;
+ * host or device memory as mem_kind says) into the handle.  They apply to every later gpx_fit / gpx_fit_predict — a
+ * jitter-escalation loop, the repeated fits of an optimiser — until they are replaced or cleared (w == NULL with n == 0).
+ * A negative or non-finite weight: GPX_E_ARG, nothing is stored and the weights of the call before stay.  A fit with
+ * N != n returns GPX_E_ARG before anything is computed.  An existing fit is not touched: it keeps the weights it was made
+ * with, for every call, until the next fit.
+ * Single-device GPX_F64, GPX_F32 and GPX_MIXED handles (GPX_MIXED: the fp64 refinement runs against the weighted
+ * matrix-free kernel; gpx_lml_grad stays GPX_F64 only).  On device groups, shards and handles that own a communicator
+ * the call itself succeeds, and a fit with weights set returns GPX_E_UNSUPPORTED before anything is computed or
+ * exchanged (gpx_last_error says why); once they are cleared the handle fits as before.
+ * With no weights set a handle launches no additional kernel and allocates nothing more. */
+int gpx_set_noise_weights(gpx_handle* h, const void* w, int64_t n, int32_t mem_kind);
+/* The weights of the current fit (appended points included), all ones when it had none.  GPX_E_ARG without a fit. */
+int gpx_get_noise_weights(gpx_handle* h, void* out /* (N) host, the handle's element type */);
+/* gpx_append with weights wnew (m) for the new points (NULL: ones — what plain gpx_append does on a weighted fit too).
+ * Validated like gpx_set_noise_weights, before the fit is touched.  The weight vector follows the factor's capacity rules
+ * (gpx_reserve): nothing is reallocated within capacity.  A failed append (*info > 0) hands back the previous weights with
+ * the previous fit.  Refusals as for gpx_append. */
+int gpx_append_weighted(gpx_handle* h, const void* Xnew, const void* ynew, const void* wnew, int64_t m, int32_t mem_kind,
+                        int64_t* info);
+/* gpx_score_blocks with S_g = K(X_g,X_g) - V_g^T V_g + diag_add diag(wq_g): wq (G*Lg) weights of the query points in the
+ * handle's element type, validated like gpx_set_noise_weights; wq == NULL is gpx_score_blocks exactly.  The weights of
+ * the FIT play no part here beyond the factor they went into.  Refusals as for gpx_score_blocks. */
+int gpx_score_blocks_weighted(gpx_handle* h, const void* Xs, const void* ys, const void* wq, int64_t G, int32_t Lg,
+                              double diag_add, void* logp /* (G,k) */, void* maha /* (G,k) */, void* logdet /* (G) */,
+                              int32_t mem_kind, int64_t* info);
+
 int gpx_get_alpha(gpx_handle* h, void* out /* (N,k) host */);
 /* Log marginal likelihood of the last fit and its gradient w.r.t. the LOG hyper-parameters —
  * SURVEY.md §8(f) row 1 ("log marginal likelihood + hyper-parameter gradient hooks"; no anchor
