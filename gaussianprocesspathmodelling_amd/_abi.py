@@ -77,6 +77,8 @@ SIGNATURES = {
     "gpx_reserve": (C.c_int, [_P, C.c_int64]),
     "gpx_set_noise_weights": (C.c_int, [_P, _P, C.c_int64, C.c_int32]),
     "gpx_get_noise_weights": (C.c_int, [_P, _P]),
+    "gpx_set_observation_kinds": (C.c_int, [_P, _P, C.c_int64, C.c_double, C.c_int32]),
+    "gpx_get_observation_kinds": (C.c_int, [_P, _P]),
     "gpx_append_weighted": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int32, C.POINTER(C.c_int64)]),
     "gpx_score_blocks_weighted": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int32, C.c_double, _P, _P, _P, C.c_int32,
                                             C.POINTER(C.c_int64)]),

@@ -164,6 +164,15 @@ struct gpx_handle {
   DevBuf Wfit, Wfit64;   // the weights of the CURRENT fit: in the fit engine's element type, with room for the layout's
                          // capacity (appends); GPX_MIXED: and in fp64 (refinement, gpx_get_noise_weights)
   bool weighted = false; // the current fit was built with Wfit
+  // observation kinds (gpx_set_observation_kinds): -1 a value of f, j a value of d f / d x_j.  Nothing here
+  // is allocated, and no kernel reads any of it, while no kinds are set.
+  std::vector<int32_t> kinds_set;  // the kinds of the next fits (empty: none set)
+  double sn2_deriv_set = 0.0;      // ... and the noise variance of their derivative rows
+  std::vector<int32_t> kinds_fit;  // the kinds of the CURRENT fit (kinded only)
+  DevBuf Kfit, Dfit;               // the same on the device, -1 up to the layout's capacity; the finished diagonal terms
+  double sn2_deriv = 0.0;
+  bool kinded = false;             // the current fit was built by the KINDS builders: every K* against it is, too
+  bool has_deriv = false;          // ... and has at least one derivative row
   // event pool
   std::vector<hipEvent_t> ev_pool;
   size_t ev_used = 0;
@@ -1151,6 +1160,38 @@ int stage_fit_weights(gpx_handle* h, int64_t N, int64_t cap) {
   return GPX_OK;
 }
 
+// The kinds of the fit that begins, as stage_fit_weights: the fit keeps its own copy (host and device, -1 beyond N up to the
+// capacity) and the finished diagonal terms (kind_i < 0 ? sn2 : sn2_deriv) w_i + jitter; none set: nothing happens here.
+// Matern-1/2 (all kinds are -1 then: check_fit_kinds) has no KINDS builders and needs none: it is the plain model.
+template <typename T>
+int stage_fit_kinds(gpx_handle* h, int64_t N, int64_t cap, double sn2, double jitter) {
+  h->kinded = h->has_deriv = false;
+  if (h->kinds_set.empty() || !cov::differentiable(h->cfg.kernel)) return GPX_OK;
+  int rc;
+  if ((rc = ensure(h, h->Kfit, (size_t)cap * sizeof(int32_t)))) return rc;
+  if ((rc = ensure(h, h->Dfit, (size_t)cap * sizeof(T)))) return rc;
+  HIPCHK(h, hipStreamSynchronize(h->st));  // (kinds_fit is the source of an asynchronous copy of the fit before)
+  h->kinds_fit = h->kinds_set;
+  h->sn2_deriv = h->sn2_deriv_set;
+  HIPCHK(h, hipMemsetAsync(h->Kfit.p, 0xFF, (size_t)cap * sizeof(int32_t), h->st));  // -1
+  HIPCHK(h, hipMemcpyAsync(h->Kfit.p, h->kinds_fit.data(), (size_t)N * sizeof(int32_t), hipMemcpyHostToDevice, h->st));
+  launch_kinds_diag<T>((const int32_t*)h->Kfit.p, h->weighted ? (const T*)h->Wfit.p : nullptr, N, sn2, h->sn2_deriv, jitter,
+                       (T*)h->Dfit.p, h->st);
+  h->kinded = true;
+  for (int32_t kk : h->kinds_fit) h->has_deriv |= kk >= 0;
+  return GPX_OK;
+}
+
+// K* of value rows As (m valid of mpad) against the training set of the current fit: the KINDS builder on a fit with kinds
+template <typename T>
+void kbuild_cross_fit(gpx_handle* h, const T* As, int64_t m, int64_t mpad, T* K, int64_t ld) {
+  if (h->kinded)
+    launch_kbuild_cross_k<T>(h->cfg.kernel, As, m, mpad, (const T*)h->Xs.p, h->N, h->Npad, h->d, h->sf2,
+                             (const int32_t*)h->Kfit.p, (const double*)h->ls.p, h->n_ls, K, ld, h->st);
+  else
+    launch_kbuild_cross<T>(h->cfg.kernel, As, m, mpad, (const T*)h->Xs.p, h->N, h->Npad, h->d, h->sf2, K, ld, h->st);
+}
+
 // Xq != null (gpx_fit_predict): the M query points' cross-kernel rows K* ride through the factorisation as
 // bordered rows too — below the right-hand sides — and leave it as
 // V^T = (L^-1 K*^T)^T: the variance solve of predict costs no pass of its own (its M N^2 flops are rows of
@@ -1197,6 +1238,7 @@ int fit_impl(gpx_handle* h, const void* X, const void* y, int64_t N, int32_t d, 
   if ((rc = ensure(h, h->Wblk, (size_t)nblk * h->nb * h->nb * sizeof(T)))) return rc;
   if ((rc = ensure(h, h->Ublk, (size_t)h->nb * ldu * sizeof(T)))) return rc;
   if ((rc = stage_fit_weights<T>(h, N, cap))) return rc;
+  if ((rc = stage_fit_kinds<T>(h, N, cap, sn2, jitter))) return rc;
   InvWork<T> iw;
   iw.W = (T*)h->Wblk.p;
   iw.U = (T*)h->Ublk.p;
@@ -1227,15 +1269,17 @@ int fit_impl(gpx_handle* h, const void* X, const void* y, int64_t N, int32_t d, 
       PhaseScope ps(h, &tm.kbuild);
       launch_scale_points<T>((const T*)h->X.p, N, Npad, d, (const double*)h->ls.p, n_ls,
                           (T*)h->Xs.p, h->st);
-      if (h->weighted)
+      if (h->kinded)
+        launch_kbuild_sym_k<T>(h->cfg.kernel, (const T*)h->Xs.p, N, Npad, d, sf2, (const int32_t*)h->Kfit.p,
+                               (const double*)h->ls.p, n_ls, (const T*)h->Dfit.p, dK, ld, h->st);
+      else if (h->weighted)
         launch_kbuild_sym_w<T>(h->cfg.kernel, (const T*)h->Xs.p, N, Npad, d, sf2, (const T*)h->Wfit.p, sn2, jitter, dK, ld,
                                h->st);
       else
         launch_kbuild_sym<T>(h->cfg.kernel, (const T*)h->Xs.p, N, Npad, d, sf2, sn2 + jitter, dK, ld, h->st);
       if (Xq) {  // rows [Npad + RHS_ROWS, ... + Mpad): K(Xq, X)
         if ((rc = upload_queries<T>(h, Xq, M, mem_kind))) return rc;
-        launch_kbuild_cross<T>(h->cfg.kernel, (const T*)h->scr.Qs.p, M, Mpad, (const T*)h->Xs.p, N, Npad, d, sf2,
-                            dK + (Npad + RHS_ROWS) * ld, ld, h->st);
+        kbuild_cross_fit<T>(h, (const T*)h->scr.Qs.p, M, Mpad, dK + (Npad + RHS_ROWS) * ld, ld);
       }
     }
     {
@@ -1593,8 +1637,7 @@ int predict_core(gpx_handle* h, const void* Xq, int64_t M, bool want_var, int32_
     const int64_t mv = std::min<int64_t>(mp, M - m0);  // valid rows
     {
       PhaseScope ps(h, &tm.kstar);
-      launch_kbuild_cross<T>(h->cfg.kernel, (const T*)h->scr.Qs.p + m0 * d, mv, mp, (const T*)h->Xs.p, N,
-                          Npad, d, h->sf2, dVT, ld, h->st);
+      kbuild_cross_fit<T>(h, (const T*)h->scr.Qs.p + m0 * d, mv, mp, dVT, ld);
     }
     if (want_var) {
       PhaseScope ps(h, &tm.trsm);
@@ -1715,7 +1758,7 @@ int posterior_cov_core(gpx_handle* h, const void* Xq, int64_t M, int32_t mem_kin
   {
     PhaseScope ps(h, &tm.kstar);
     if ((rc = upload_queries<T>(h, Xq, M, mem_kind))) return rc;
-    launch_kbuild_cross<T>(h->cfg.kernel, (const T*)h->scr.Qs.p, M, Mpad, (const T*)h->Xs.p, N, Npad, d, h->sf2, dVT, ld, h->st);
+    kbuild_cross_fit<T>(h, (const T*)h->scr.Qs.p, M, Mpad, dVT, ld);
   }
   {
     PhaseScope ps(h, &tm.trsm);
@@ -1940,7 +1983,7 @@ int score_impl(gpx_handle* h, const void* Xq, const void* yq, const void* wq, in
       const int64_t mv = nb * Lg, mp = round_up(mv, TILE);
       {
         PhaseScope ps(h, &tm.kstar);
-        launch_kbuild_cross<T>(h->cfg.kernel, dQs + m0 * d, mv, mp, (const T*)h->Xs.p, N, Npad, d, h->sf2, dVT, ld, h->st);
+        kbuild_cross_fit<T>(h, dQs + m0 * d, mv, mp, dVT, ld);
       }
       {
         PhaseScope ps(h, &tm.trsm);
@@ -2080,7 +2123,8 @@ int predict_grad_var(gpx_handle* h, const void* Xq, int64_t M, void* mean, void*
     {
       PhaseScope ps(h, &tm.kstar);
       launch_kgrad_build<T>(h->cfg.kernel, (const T*)h->scr.Qs.p + m0 * d, mv, mp, (const T*)h->Xs.p, N, Npad, d, h->sf2,
-                            (const double*)h->ls.p, h->n_ls, with_value ? 1 : 0, dV, ld, h->st);
+                            (const double*)h->ls.p, h->n_ls, with_value ? 1 : 0, dV, ld, h->st,
+                            h->kinded ? (const int32_t*)h->Kfit.p : nullptr);
     }
     {
       PhaseScope ps(h, &tm.trsm);
@@ -2116,7 +2160,7 @@ int predict_grad_impl(gpx_handle* h, const void* Xq, int64_t M, void* mean, void
   int rc;
   {
     PhaseScope total(h, &h->tm.predict_total);
-    if (!var && !dvar)
+    if (!var && !dvar && !h->has_deriv)  // (the matrix-free product knows no derivative columns: the batch route then)
       rc = predict_grad_mean_only<T>(h, Xq, M, mean, dmean, mem_kind);
     else
       rc = predict_grad_var<T>(h, Xq, M, mean, var, dmean, dvar, mem_kind, "gpx_predict_grad");
@@ -2624,6 +2668,39 @@ int check_fit_weights(gpx_handle* h, const char* fn, int64_t N) {
   return GPX_OK;
 }
 
+// a fit on a handle with observation kinds set, before anything is computed or exchanged: GPX_E_ARG for kinds that do not
+// fit the call (not one per observation, a dimension >= d), GPX_E_UNSUPPORTED where no KINDS builder runs
+int check_fit_kinds(gpx_handle* h, const char* fn, int64_t N, int32_t d) {
+  if (h->kinds_set.empty()) return GPX_OK;
+  char buf[320];
+  const char* where = h->group ? "device groups" : (h->cfg.world > 1 || h->comm) ? "sharded handles"
+                      : h->cfg.dtype == GPX_MIXED ? "GPX_MIXED handles" : nullptr;
+  if (where) {
+    snprintf(buf, sizeof buf, "%s: observation kinds are not supported on %s (single-device GPX_F64 / GPX_F32 handles "
+             "only; clear them with gpx_set_observation_kinds(h, NULL, 0, ...))", fn, where);
+    return fail(h, GPX_E_UNSUPPORTED, buf);
+  }
+  if (N != (int64_t)h->kinds_set.size()) {
+    snprintf(buf, sizeof buf, "%s: %lld observation kinds are set for a fit of %lld observations", fn,
+             (long long)h->kinds_set.size(), (long long)N);
+    return fail(h, GPX_E_ARG, buf);
+  }
+  bool deriv = false;
+  for (int64_t i = 0; i < N; ++i) {
+    if (h->kinds_set[i] >= d) {
+      snprintf(buf, sizeof buf, "%s: observation %lld has kind %d, the inputs have %d dimensions", fn, (long long)i,
+               (int)h->kinds_set[i], (int)d);
+      return fail(h, GPX_E_ARG, buf);
+    }
+    deriv |= h->kinds_set[i] >= 0;
+  }
+  if (deriv && !cov::differentiable(h->cfg.kernel)) {
+    snprintf(buf, sizeof buf, "%s: derivative observations: " MATERN12_NO_GRAD, fn);
+    return fail(h, GPX_E_UNSUPPORTED, buf);
+  }
+  return GPX_OK;
+}
+
 // gpx_fit on one handle, behind its argument checks and begin_fit
 int fit_begun(gpx_handle* h, const void* X, const void* y, int64_t N, int32_t d, int32_t k, const double* lengthscale,
               int32_t n_ls, double sf2, double sn2, double jitter, int32_t mem_kind, int64_t* info) {
@@ -2655,6 +2732,7 @@ int gpx_fit(gpx_handle* h, const void* X, const void* y, int64_t N, int32_t d, i
                            jitter, mem_kind)))
     return rc;
   if ((rc = check_fit_weights(h, "gpx_fit", N))) return rc;
+  if ((rc = check_fit_kinds(h, "gpx_fit", N, d))) return rc;
   if (h->group) return group_fit(h, X, y, N, d, k, lengthscale, n_ls, sf2, sn2, jitter, mem_kind, info);
   if ((rc = begin_fit(h))) return rc;
   return fit_begun(h, X, y, N, d, k, lengthscale, n_ls, sf2, sn2, jitter, mem_kind, info);
@@ -2670,6 +2748,7 @@ int gpx_fit_predict(gpx_handle* h, const void* X, const void* y, int64_t N, int3
                            lengthscale, n_ls, sf2, sn2, jitter, mem_kind)))
     return rc;
   if ((rc = check_fit_weights(h, "gpx_fit_predict", N))) return rc;
+  if ((rc = check_fit_kinds(h, "gpx_fit_predict", N, d))) return rc;
   if (h->group) return group_fit_predict(h, X, y, N, d, k, lengthscale, n_ls, sf2, sn2, jitter, Xq, M, mean, var, mem_kind, info);
   // Shards (round 4): every rank's slice of the query points rides through the sharded factorisation as bordered rows of
   // its local row set (shard_fit with query points + shard_fused_tail) — in the split schedule, up to 8192 rows per rank.
@@ -2814,6 +2893,10 @@ int append_entry(gpx_handle* h, const void* Xnew, const void* ynew, const void* 
   if ((rc = posterior_refused(h, "gpx_append"))) return rc;
   if (!h->fitted) return fail(h, GPX_E_ARG, "gpx_append: handle has no successful fit");
   if (m > (int64_t)INT_MAX - 4096 - h->N) return fail(h, GPX_E_ARG, "gpx_append: N + m too large");
+  if (h->has_deriv)
+    return fail(h, GPX_E_UNSUPPORTED, "gpx_append: the fit has derivative observations (gpx_set_observation_kinds): fit the "
+                                      "concatenated data instead");
+  h->kinded = false;  // (kinds all -1: the plain model, and from here on the plain builders' — the same numbers)
   if ((rc = begin_call(h))) return rc;
   if (wnew && (rc = check_weights(h, "gpx_append_weighted", wnew, m, mem_kind, h->cfg.dtype == GPX_F32 ? 4 : 8, h->st)))
     return rc;
@@ -2902,6 +2985,48 @@ int gpx_get_noise_weights(gpx_handle* h, void* out) try {
 }
 GPX_CATCH_ALL
 
+int gpx_set_observation_kinds(gpx_handle* h, const int32_t* kind, int64_t n, double sn2_deriv, int32_t mem_kind) try {
+  if (!h) return GPX_E_ARG;
+  if (mem_kind != GPX_MEM_HOST && mem_kind != GPX_MEM_DEVICE)
+    return fail(h, GPX_E_ARG, "gpx_set_observation_kinds: bad mem_kind");
+  if (n < 0 || (n == 0) != (kind == nullptr) || n > (int64_t)INT_MAX - 4096)
+    return fail(h, GPX_E_ARG, "gpx_set_observation_kinds: need n kinds, or NULL and 0 to clear them");
+  if (n == 0) {
+    h->kinds_set.clear();
+    h->sn2_deriv_set = 0.0;
+    return GPX_OK;
+  }
+  if (!(sn2_deriv >= 0.0) || !std::isfinite(sn2_deriv))
+    return fail(h, GPX_E_ARG, "gpx_set_observation_kinds: sn2_deriv must be finite and >= 0");
+  // validated in a copy of the caller's array, before the handle's is replaced: a refused call leaves the kinds of the
+  // call before in place
+  std::vector<int32_t> fresh((size_t)n);
+  if (mem_kind == GPX_MEM_HOST) {
+    std::copy(kind, kind + n, fresh.begin());
+  } else {
+    if (!h->group) HIPCHK(h, hipSetDevice(h->cfg.device));
+    HIPCHK(h, hipMemcpy(fresh.data(), kind, (size_t)n * sizeof(int32_t), hipMemcpyDefault));
+  }
+  for (int64_t i = 0; i < n; ++i)
+    if (fresh[i] < -1) return fail(h, GPX_E_ARG, "gpx_set_observation_kinds: a kind is -1 (a value) or a dimension >= 0");
+  h->kinds_set = std::move(fresh);
+  h->sn2_deriv_set = sn2_deriv;
+  return GPX_OK;
+}
+GPX_CATCH_ALL
+
+int gpx_get_observation_kinds(gpx_handle* h, int32_t* out) try {
+  if (!h) return GPX_E_ARG;
+  if (!h->fitted || !out) return fail(h, GPX_E_ARG, "gpx_get_observation_kinds: no fit or null output");
+  const int64_t N = h->group ? h->group->members[0]->N : h->N;
+  if (h->kinded && (int64_t)h->kinds_fit.size() == N)
+    std::copy(h->kinds_fit.begin(), h->kinds_fit.end(), out);
+  else
+    std::fill(out, out + N, (int32_t)-1);
+  return GPX_OK;
+}
+GPX_CATCH_ALL
+
 int gpx_reserve(gpx_handle* h, int64_t capacity) try {
   if (!h) return GPX_E_ARG;
   if (capacity < 0 || capacity > (int64_t)INT_MAX - 4096) return fail(h, GPX_E_ARG, "gpx_reserve: bad capacity");
@@ -2946,6 +3071,9 @@ int gpx_lml_grad(gpx_handle* h, double* lml, double* grad) try {
   if (!h) return GPX_E_ARG;
   if (!h->fitted || !lml || !grad) return fail(h, GPX_E_ARG, "gpx_lml_grad: no fit or null output");
   if (h->cfg.dtype != GPX_F64) return fail(h, GPX_E_UNSUPPORTED, "gpx_lml_grad: fp64 handles only");
+  if (h->has_deriv)  // (dK / dlog l of the derivative blocks is not implemented)
+    return fail(h, GPX_E_UNSUPPORTED, "gpx_lml_grad: the fit has derivative observations (gpx_set_observation_kinds): no "
+                                      "analytic gradient, use differences of the log marginal likelihood");
   if (h->group) return group_lml_grad(h, lml, grad);
   if (h->cfg.world > 1 && !h->comm) return fail(h, GPX_E_ARG, "gpx_lml_grad: sharded handle without a communicator");
   int rc;

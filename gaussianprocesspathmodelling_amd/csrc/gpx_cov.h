@@ -10,8 +10,17 @@
 //   v  = sf2 (poly(s) e)    the value sf2 k(r)
 //   g  = sf2 (dpoly(s) e)   d k / d x*_j = -g (u*_j - u_j) / l_j   (RBF: g = v)
 //   kd = g                  d K / d log l_c = kd d_c^2;  Matern-1/2: kd = v / r, 0 at r = 0 (kd d_c^2 <= sf2 r -> 0)
+//   h                       d g / d x'_j = h (u_j - u'_j) / l_j: the second-derivative block (derivative observations)
+//        RBF         v
+//        Matern-5/2  sf2 (25/3) e
+//        Matern-3/2  9 sf2 e / s, taken as 0 at r = 0 (h only ever multiplies u_i u_j, and h u_i u_j <= 9 sf2 r / sqrt3 -> 0)
+//        Matern-1/2  -
 //
-// Every kernel evaluates these in this one operation order (value / value_g / value_kd): for one element type and
+// Observation kinds (element): a row of a fit is a value of f (kind -1) or of d f / d x_j (kind j); with u = (x_a - x_b) / l
+//   (-1, -1)  v                 ( i, -1)  -g u_i / l_i
+//   (-1,  j)  +g u_j / l_j      ( i,  j)  (g delta_ij - h u_i u_j) / (l_i l_j)      at r = 0: (j, j) = grad_prior sf2 / l_j^2
+//
+// Every kernel evaluates these in this one operation order (value / value_g / value_gh / value_kd): for one element type and
 // exponential, the value rows of the derivative build and the kf of the LML gradient are bit for bit the kernel build's
 // K.  Matern-1/2 has no derivative at r = 0: it has no g, and no derivative kernel is instantiated for it.
 #pragma once
@@ -77,6 +86,29 @@ __device__ __forceinline__ void value_g(T r2, T sf2, T& v, T& g, E ex = {}) {
   const T e = ex(earg<KERNEL>(r2, s));
   v = sf2 * (poly<KERNEL>(s) * e);
   g = sf2 * (dpoly<KERNEL>(s) * e);
+}
+
+// v and g as value_g forms them (the same bits), and h
+template <int KERNEL, typename T, typename E = Exp>
+__device__ __forceinline__ void value_gh(T r2, T sf2, T& v, T& g, T& h, E ex = {}) {
+  static_assert(differentiable(KERNEL), "Matern-1/2 is not differentiable");
+  const T s = svar<KERNEL>(r2);
+  const T e = ex(earg<KERNEL>(r2, s));
+  v = sf2 * (poly<KERNEL>(s) * e);
+  g = sf2 * (dpoly<KERNEL>(s) * e);
+  if constexpr (KERNEL == GPX_KERNEL_MATERN52) h = sf2 * ((T)(25.0 / 3.0) * e);
+  else if constexpr (KERNEL == GPX_KERNEL_MATERN32) h = s > (T)0 ? sf2 * ((T)9 * e) / s : (T)0;
+  else h = v;
+}
+
+// The covariance of an observation of kind ka at x_a with one of kind kb at x_b (the table above) — the one place the
+// mixed formula exists.  ua = u_ka and ila = 1 / l_ka (anything when ka < 0), ub and ilb the same for kb; u = (x_a - x_b) / l.
+// Products of the two sides are formed side by side, so that swapping a and b (u -> -u) gives the same bits.
+template <typename T>
+__host__ __device__ __forceinline__ T element(int ka, int kb, T v, T g, T h, T ua, T ub, T ila, T ilb) {
+  if (ka < 0) return kb < 0 ? v : g * ub * ilb;
+  if (kb < 0) return -g * ua * ila;
+  return ((ka == kb ? g : (T)0) - h * (ua * ub)) * (ila * ilb);
 }
 
 template <int KERNEL, typename T, typename E = Exp>

@@ -20,11 +20,15 @@ constexpr int GT = 64;      // tile edge of the build, query rows per workgroup 
 // Row blocks of V (each mpad rows, ld): [K* if with_value] then d_1 K* ... d_d K*; tile (ti, tj) of 64 x 64 per
 // workgroup, the same lane map, padding (zero beyond m rows / n columns) and non-temporal 16-byte stores as
 // kbuild_kernel; r^2 and the exponential once per pair, 1 + d stores of it.  HBM-write-bound.
-template <typename T, int KERNEL, int D>
+// KINDS: the columns are observations with a kind (gpx_cov.h; kcol readable up to the padded size, -1 there): against a
+// derivative column the value rows hold the (-1, j) element and the d_i K* rows the (i, j) element (cov::element).  A tile
+// whose 64 column kinds are all -1 — decided once per workgroup — takes the path, and gives the numbers, of the plain build.
+template <typename T, int KERNEL, int D, bool KINDS = false>
 __global__ __launch_bounds__(256) void kgrad_build_kernel(const T* __restrict__ As, int64_t m, const T* __restrict__ Bs,
                                                          int64_t n, int d_rt, int tiles_n, T sf2,
                                                          const double* __restrict__ ls, int n_ls, int with_value,
-                                                         T* __restrict__ V, int64_t ld, int64_t mpad) {
+                                                         T* __restrict__ V, int64_t ld, int64_t mpad,
+                                                         const int32_t* __restrict__ kcol = nullptr) {
   const int d = (D > 0) ? D : d_rt;
   __shared__ T xa[GT * (D > 0 ? D : MAX_D)];
   __shared__ T xb[GT * (D > 0 ? D : MAX_D)];
@@ -37,7 +41,21 @@ __global__ __launch_bounds__(256) void kgrad_build_kernel(const T* __restrict__ 
     xb[e] = Bs[j0 * d + e];
   }
   if (tid < d) il[tid] = (T)(1.0 / ls[n_ls == 1 ? 0 : tid]);
-  __syncthreads();
+  bool mixed = false;
+  const int* skb = nullptr;
+  if constexpr (KINDS) {
+    __shared__ int kbs[GT];
+    int deriv = 0;
+    if (tid >= 256 - GT) {  // (the last wave: the first ones stage 1 / l)
+      const int kk = kcol[j0 + tid - (256 - GT)];
+      kbs[tid - (256 - GT)] = kk;
+      deriv = kk >= 0;
+    }
+    mixed = __syncthreads_or(deriv) != 0;
+    skb = kbs;
+  } else {
+    __syncthreads();
+  }
   const int c2 = (tid & 31) * 2;
   const int rg = tid >> 5;
   const int64_t col0 = j0 + c2, col1 = col0 + 1;
@@ -53,6 +71,32 @@ __global__ __launch_bounds__(256) void kgrad_build_kernel(const T* __restrict__ 
       const T e0 = a - xb[c2 * d + c], e1 = a - xb[(c2 + 1) * d + c];
       s0 += e0 * e0;
       s1 += e1 * e1;
+    }
+    if constexpr (KINDS) {
+      if (mixed) {
+        const bool ok0 = row < m && col0 < n, ok1 = row < m && col1 < n;
+        T* out = V + row * ld + col0;
+        T v0, g0, h0, v1, g1, h1;
+        cov::value_gh<KERNEL>(s0, sf2, v0, g0, h0);
+        cov::value_gh<KERNEL>(s1, sf2, v1, g1, h1);
+        const int kb0 = skb[c2], kb1 = skb[c2 + 1];
+        const int cb0 = kb0 < 0 ? 0 : kb0, cb1 = kb1 < 0 ? 0 : kb1;  // (kinds < d: the API checks)
+        const T* pa = xa + ir * d;
+        const T *pb0 = xb + c2 * d, *pb1 = pb0 + d;
+        const T ub0 = pa[cb0] - pb0[cb0], ub1 = pa[cb1] - pb1[cb1], ilb0 = il[cb0], ilb1 = il[cb1];
+        if (with_value) {
+          pair_t w = {ok0 ? cov::element<T>(-1, kb0, v0, g0, h0, (T)0, ub0, (T)0, ilb0) : (T)0,
+                      ok1 ? cov::element<T>(-1, kb1, v1, g1, h1, (T)0, ub1, (T)0, ilb1) : (T)0};
+          __builtin_nontemporal_store(w, reinterpret_cast<pair_t*>(out));
+          out += blk;
+        }
+        for (int c = 0; c < d; ++c) {
+          pair_t w = {ok0 ? cov::element<T>(c, kb0, v0, g0, h0, pa[c] - pb0[c], ub0, il[c], ilb0) : (T)0,
+                      ok1 ? cov::element<T>(c, kb1, v1, g1, h1, pa[c] - pb1[c], ub1, il[c], ilb1) : (T)0};
+          __builtin_nontemporal_store(w, reinterpret_cast<pair_t*>(out + c * blk));
+        }
+        continue;
+      }
     }
     T v0, g0, v1, g1;
     cov::value_g<KERNEL>(s0, sf2, v0, g0);
@@ -227,11 +271,20 @@ unsigned grid_for(int64_t work) {
 
 template <typename T, int KERNEL>
 void build_d(const T* As, int64_t m, int64_t mpad, const T* Bs, int64_t n, int64_t npad, int d, double sf2,
-             const double* ls, int n_ls, int with_value, T* V, int64_t ld, hipStream_t st) {
+             const double* ls, int n_ls, int with_value, T* V, int64_t ld, hipStream_t st, const int32_t* kcol) {
   const int64_t tm = mpad / GT, tn = npad / GT;
   dim3 grid((unsigned)(tm * tn)), block(256);
   const T s = (T)sf2;
   const int tnn = (int)tn;
+  if (kcol) {  // observations with kinds
+    switch (d) {
+      case 1: hipLaunchKernelGGL((kgrad_build_kernel<T, KERNEL, 1, true>), grid, block, 0, st, As, m, Bs, n, d, tnn, s, ls, n_ls, with_value, V, ld, mpad, kcol); break;
+      case 2: hipLaunchKernelGGL((kgrad_build_kernel<T, KERNEL, 2, true>), grid, block, 0, st, As, m, Bs, n, d, tnn, s, ls, n_ls, with_value, V, ld, mpad, kcol); break;
+      case 3: hipLaunchKernelGGL((kgrad_build_kernel<T, KERNEL, 3, true>), grid, block, 0, st, As, m, Bs, n, d, tnn, s, ls, n_ls, with_value, V, ld, mpad, kcol); break;
+      default: hipLaunchKernelGGL((kgrad_build_kernel<T, KERNEL, 0, true>), grid, block, 0, st, As, m, Bs, n, d, tnn, s, ls, n_ls, with_value, V, ld, mpad, kcol); break;
+    }
+    return;
+  }
   switch (d) {
     case 1: hipLaunchKernelGGL((kgrad_build_kernel<T, KERNEL, 1>), grid, block, 0, st, As, m, Bs, n, d, tnn, s, ls, n_ls, with_value, V, ld, mpad); break;
     case 2: hipLaunchKernelGGL((kgrad_build_kernel<T, KERNEL, 2>), grid, block, 0, st, As, m, Bs, n, d, tnn, s, ls, n_ls, with_value, V, ld, mpad); break;
@@ -273,8 +326,9 @@ void matvec_d(dim3 grid, int KC, const T* As, const T* Bs, int64_t npad, int64_t
 
 template <typename T>
 void launch_kgrad_build(int kernel, const T* As, int64_t m, int64_t mpad, const T* Bs, int64_t n, int64_t npad, int d,
-                        double sf2, const double* ls, int n_ls, int with_value, T* V, int64_t ld, hipStream_t st) {
-  cov::dispatch_differentiable(kernel, [&](auto fam) { build_d<T, fam>(As, m, mpad, Bs, n, npad, d, sf2, ls, n_ls, with_value, V, ld, st); });
+                        double sf2, const double* ls, int n_ls, int with_value, T* V, int64_t ld, hipStream_t st,
+                        const int32_t* kind_b) {
+  cov::dispatch_differentiable(kernel, [&](auto fam) { build_d<T, fam>(As, m, mpad, Bs, n, npad, d, sf2, ls, n_ls, with_value, V, ld, st, kind_b); });
 }
 
 void kgrad_matvec_shape(int64_t M, int64_t npad, int d, int k, int* KC, int* S, int64_t* chunk) {
@@ -325,7 +379,7 @@ void launch_grad_unpack(const T* MT, int64_t ldm, const T* VN, int64_t mp, int64
 
 #define GPX_INSTANTIATE_DERIV(T)                                                                                       \
   template void launch_kgrad_build<T>(int, const T*, int64_t, int64_t, const T*, int64_t, int64_t, int, double,       \
-                                      const double*, int, int, T*, int64_t, hipStream_t);                             \
+                                      const double*, int, int, T*, int64_t, hipStream_t, const int32_t*);             \
   template void launch_kgrad_matvec<T>(int, const T*, int64_t, const T*, int64_t, int, double, const T*, int64_t, int, \
                                        const double*, int, T*, T*, hipStream_t);                                      \
   template void launch_grad_norms<T>(const T*, int64_t, int64_t, int64_t, int, int64_t, const double*, T*,            \

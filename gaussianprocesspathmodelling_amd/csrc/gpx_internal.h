@@ -101,6 +101,20 @@ void launch_kbuild_sym_w(int kernel, const T* Xs, int64_t n, int64_t npad, int d
 template <typename T>
 void launch_kbuild_cross(int kernel, const T* As, int64_t m, int64_t mpad, const T* Bs, int64_t n,
                          int64_t npad, int d, double sf2, T* K, int64_t ld, hipStream_t st);
+// Observations with kinds (gpx_cov.h: kind -1 a value of f, j a value of d f / d x_j; the arrays are readable up to the
+// padded sizes and hold -1 there; ls (n_ls = 1 or d) on the device; differentiable families only).
+// diag[i] = (kind[i] < 0 ? sn2 : sn2_deriv) (w ? w[i] : 1) + jitter for i < n, formed in fp64 and rounded once
+template <typename T>
+void launch_kinds_diag(const int32_t* kind, const T* w, int64_t n, double sn2, double sn2_deriv, double jitter, T* diag,
+                       hipStream_t st);
+// launch_kbuild_sym over such observations: cov::element per pair, + diag[i] on the diagonal of row i < n
+template <typename T>
+void launch_kbuild_sym_k(int kernel, const T* Xs, int64_t n, int64_t npad, int d, double sf2, const int32_t* kind,
+                         const double* ls, int n_ls, const T* diag, T* K, int64_t ld, hipStream_t st);
+// launch_kbuild_cross with value rows (As) against such observations as columns (Bs, kind_b)
+template <typename T>
+void launch_kbuild_cross_k(int kernel, const T* As, int64_t m, int64_t mpad, const T* Bs, int64_t n, int64_t npad, int d,
+                           double sf2, const int32_t* kind_b, const double* ls, int n_ls, T* K, int64_t ld, hipStream_t st);
 
 // ---- dense blocks (gpx_blas.hip) ---------------------------------------------------
 // In-place Cholesky of one 64x64 diagonal block (lower) + its inverse Winv (64x64,
@@ -304,9 +318,11 @@ void launch_sample_epilogue(const T* ST, int64_t lds, int64_t r0, int64_t rows, 
 // ---- posterior gradient (gpx_deriv.hip) --------------------------------------------------------
 // Row blocks of V (each mpad rows, ld; mpad a multiple of 64): [sf2 k(As, Bs) if with_value — launch_kbuild_cross's
 // numbers] then d k(As, Bs) / d As_j for j < d; zero beyond m rows / n columns.  ls (n_ls = 1 or d) on the device.
+// kind_b != null: the columns are observations with kinds (as launch_kbuild_cross_k's).
 template <typename T>
 void launch_kgrad_build(int kernel, const T* As, int64_t m, int64_t mpad, const T* Bs, int64_t n, int64_t npad, int d,
-                        double sf2, const double* ls, int n_ls, int with_value, T* V, int64_t ld, hipStream_t st);
+                        double sf2, const double* ls, int n_ls, int with_value, T* V, int64_t ld, hipStream_t st,
+                        const int32_t* kind_b = nullptr);
 // grid of the matrix-free product: KC targets per workgroup, S splits of `chunk` training columns; the partial buffer
 // holds S * k * d * round_up(M, 64) elements
 void kgrad_matvec_shape(int64_t M, int64_t npad, int d, int k, int* KC, int* S, int64_t* chunk);

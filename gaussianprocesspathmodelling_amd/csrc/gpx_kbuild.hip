@@ -41,12 +41,20 @@ __device__ __forceinline__ void tri_coords(int64_t t, int& ti, int& tj) {
 // gets + diag_add, padding becomes identity.  !SYM: all tiles, padding is zero.
 // WEIGHTED (SYM only): row i < m of the diagonal gets + (wsn2 w[i] + wjit) instead of diag_add — per-observation noise;
 // the sum is formed in fp64 and rounded once, as the host forms sn2 + jitter for the scalar form (w = 1: the same bits).
-template <typename T, int KERNEL, bool SYM, int D, bool WEIGHTED = false>
+// KINDS: the columns (SYM: and the rows) are observations with a kind (gpx_cov.h: -1 a value, j a derivative along x_j);
+// krow (null: all values) / kcol are readable up to the padded sizes and hold -1 there, ls (n_ls) are the lengthscales.
+// The 64 + 64 kinds and 1 / l are staged beside the points.  A tile whose kinds are all -1 — decided once per workgroup,
+// wave-uniform — takes the value-only path, whose numbers are those of the plain build; a mixed tile evaluates cov::element,
+// still one exponential per pair.  SYM: w is the finished per-row diagonal term (launch_kinds_diag), read on diagonal tiles.
+template <typename T, int KERNEL, bool SYM, int D, bool WEIGHTED = false, bool KINDS = false>
 __global__ __launch_bounds__(256) void kbuild_kernel(const T* __restrict__ As, int64_t m,
                                                     const T* __restrict__ Bs, int64_t n, int d_rt,
                                                     int tiles_n, T sf2, T diag_add, T* __restrict__ K,
                                                     int64_t ld, const T* __restrict__ w = nullptr,
-                                                    double wsn2 = 0.0, double wjit = 0.0) {
+                                                    double wsn2 = 0.0, double wjit = 0.0,
+                                                    const int32_t* __restrict__ krow = nullptr,
+                                                    const int32_t* __restrict__ kcol = nullptr,
+                                                    const double* __restrict__ ls = nullptr, int n_ls = 0) {
   const int d = (D > 0) ? D : d_rt;
   // LDS sized by the instantiation (d = 3: 2 x 1.5 KB, not 2 x 16 KB): the occupancy is then the waves', not the LDS's
   __shared__ T xa[KT * (D > 0 ? D : MAX_D)];
@@ -64,7 +72,26 @@ __global__ __launch_bounds__(256) void kbuild_kernel(const T* __restrict__ As, i
     xa[e] = As[i0 * d + e];  // rows of the padded point array are always readable
     xb[e] = Bs[j0 * d + e];
   }
-  __syncthreads();
+  bool mixed = false;
+  const int* ska = nullptr;
+  const int* skb = nullptr;
+  const T* sil = nullptr;
+  if constexpr (KINDS) {
+    __shared__ int kab[2 * KT];
+    __shared__ T ilv[D > 0 ? D : MAX_D];
+    int deriv = 0;
+    if (tid < 2 * KT) {
+      const int kk = tid < KT ? (krow ? krow[i0 + tid] : -1) : kcol[j0 + tid - KT];
+      kab[tid] = kk;
+      deriv = kk >= 0;
+    } else if (tid - 2 * KT < d) {
+      ilv[tid - 2 * KT] = (T)(1.0 / ls[n_ls == 1 ? 0 : tid - 2 * KT]);
+    }
+    mixed = __syncthreads_or(deriv) != 0;
+    ska = kab, skb = kab + KT, sil = ilv;
+  } else {
+    __syncthreads();
+  }
   const int c2 = (tid & 31) * 2;
   const int rg = tid >> 5;
   T bj0[D > 0 ? D : MAX_D], bj1[D > 0 ? D : MAX_D];
@@ -97,9 +124,32 @@ __global__ __launch_bounds__(256) void kbuild_kernel(const T* __restrict__ As, i
         s1 += e1 * e1;
       }
     }
-    T v0 = cov::value<KERNEL>(s0, sf2), v1 = cov::value<KERNEL>(s1, sf2);
+    T v0, v1;
+    if constexpr (KINDS) {
+      if (mixed) {
+        T g0, h0, g1, h1;
+        cov::value_gh<KERNEL>(s0, sf2, v0, g0, h0);
+        cov::value_gh<KERNEL>(s1, sf2, v1, g1, h1);
+        const int ka = ska[il], kb0 = skb[c2], kb1 = skb[c2 + 1];
+        const int ca = ka < 0 ? 0 : ka, cb0 = kb0 < 0 ? 0 : kb0, cb1 = kb1 < 0 ? 0 : kb1;  // (kinds < d: the API checks)
+        const T* pa = xa + il * d;
+        const T *pb0 = xb + c2 * d, *pb1 = pb0 + d;
+        v0 = cov::element<T>(ka, kb0, v0, g0, h0, pa[ca] - pb0[ca], pa[cb0] - pb0[cb0], sil[ca], sil[cb0]);
+        v1 = cov::element<T>(ka, kb1, v1, g1, h1, pa[ca] - pb1[ca], pa[cb1] - pb1[cb1], sil[ca], sil[cb1]);
+      } else {
+        v0 = cov::value<KERNEL>(s0, sf2), v1 = cov::value<KERNEL>(s1, sf2);
+      }
+    } else {
+      v0 = cov::value<KERNEL>(s0, sf2), v1 = cov::value<KERNEL>(s1, sf2);
+    }
     if (SYM) {
-      if (WEIGHTED) {  // (only diagonal tiles read w: one load per row there)
+      if (KINDS) {  // the finished diagonal term of row `row` (only diagonal tiles read it)
+        if (ti == tj && row < m) {
+          const T da = w[row];
+          if (row == col0) v0 += da;
+          if (row == col1) v1 += da;
+        }
+      } else if (WEIGHTED) {  // (only diagonal tiles read w: one load per row there)
         if (ti == tj && row < m) {
           const T da = (T)(wsn2 * (double)w[row] + wjit);
           if (row == col0) v0 += da;
@@ -137,6 +187,31 @@ void dispatch_d_w(const T* Xs, int64_t n, int d, int64_t nblocks, int tiles_n, d
     case 3: hipLaunchKernelGGL((kbuild_kernel<T, KERNEL, true, 3, true>), grid, block, 0, st, Xs, n, Xs, n, d, tiles_n, s, z, K, ld, w, sn2, jitter); break;
     default: hipLaunchKernelGGL((kbuild_kernel<T, KERNEL, true, 0, true>), grid, block, 0, st, Xs, n, Xs, n, d, tiles_n, s, z, K, ld, w, sn2, jitter); break;
   }
+}
+
+// the builds over observations with kinds (launch_kbuild_sym_k / launch_kbuild_cross_k)
+template <typename T, int KERNEL, bool SYM>
+void dispatch_d_k(const T* As, int64_t m, const T* Bs, int64_t n, int d, int64_t nblocks, int tiles_n, double sf2,
+                  const int32_t* krow, const int32_t* kcol, const double* ls, int n_ls, const T* diag, T* K, int64_t ld,
+                  hipStream_t st) {
+  dim3 grid((unsigned)nblocks), block(256);
+  const T s = (T)sf2, z = (T)0;
+  switch (d) {
+    case 1: hipLaunchKernelGGL((kbuild_kernel<T, KERNEL, SYM, 1, false, true>), grid, block, 0, st, As, m, Bs, n, d, tiles_n, s, z, K, ld, diag, 0.0, 0.0, krow, kcol, ls, n_ls); break;
+    case 2: hipLaunchKernelGGL((kbuild_kernel<T, KERNEL, SYM, 2, false, true>), grid, block, 0, st, As, m, Bs, n, d, tiles_n, s, z, K, ld, diag, 0.0, 0.0, krow, kcol, ls, n_ls); break;
+    case 3: hipLaunchKernelGGL((kbuild_kernel<T, KERNEL, SYM, 3, false, true>), grid, block, 0, st, As, m, Bs, n, d, tiles_n, s, z, K, ld, diag, 0.0, 0.0, krow, kcol, ls, n_ls); break;
+    default: hipLaunchKernelGGL((kbuild_kernel<T, KERNEL, SYM, 0, false, true>), grid, block, 0, st, As, m, Bs, n, d, tiles_n, s, z, K, ld, diag, 0.0, 0.0, krow, kcol, ls, n_ls); break;
+  }
+}
+
+// diag[i] = (kind[i] < 0 ? sn2 : sn2_deriv) (w ? w[i] : 1) + jitter, i < n: formed in fp64 and rounded once
+template <typename T>
+__global__ __launch_bounds__(256) void kinds_diag_kernel(const int32_t* __restrict__ kind, const T* __restrict__ w,
+                                                        int64_t n, double sn2, double sn2_deriv, double jitter,
+                                                        T* __restrict__ diag) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  diag[i] = (T)((kind[i] < 0 ? sn2 : sn2_deriv) * (w ? (double)w[i] : 1.0) + jitter);
 }
 
 template <typename T, int KERNEL, bool SYM>
@@ -185,6 +260,32 @@ void launch_kbuild_cross(int kernel, const T* As, int64_t m, int64_t mpad, const
   cov::dispatch(kernel, [&](auto fam) { dispatch_d<T, fam, false>(As, m, Bs, n, d, tm * tn, (int)tn, sf2, 0.0, K, ld, st); });
 }
 
+template <typename T>
+void launch_kinds_diag(const int32_t* kind, const T* w, int64_t n, double sn2, double sn2_deriv, double jitter, T* diag,
+                       hipStream_t st) {
+  hipLaunchKernelGGL(kinds_diag_kernel<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, kind, w, n, sn2, sn2_deriv,
+                     jitter, diag);
+}
+
+template <typename T>
+void launch_kbuild_sym_k(int kernel, const T* Xs, int64_t n, int64_t npad, int d, double sf2, const int32_t* kind,
+                         const double* ls, int n_ls, const T* diag, T* K, int64_t ld, hipStream_t st) {
+  const int64_t TT = npad / KT;
+  const int64_t nblocks = TT * (TT + 1) / 2;
+  cov::dispatch_differentiable(kernel, [&](auto fam) {
+    dispatch_d_k<T, fam, true>(Xs, n, Xs, n, d, nblocks, (int)TT, sf2, kind, kind, ls, n_ls, diag, K, ld, st);
+  });
+}
+
+template <typename T>
+void launch_kbuild_cross_k(int kernel, const T* As, int64_t m, int64_t mpad, const T* Bs, int64_t n, int64_t npad, int d,
+                           double sf2, const int32_t* kind_b, const double* ls, int n_ls, T* K, int64_t ld, hipStream_t st) {
+  const int64_t tm = mpad / KT, tn = npad / KT;
+  cov::dispatch_differentiable(kernel, [&](auto fam) {
+    dispatch_d_k<T, fam, false>(As, m, Bs, n, d, tm * tn, (int)tn, sf2, nullptr, kind_b, ls, n_ls, nullptr, K, ld, st);
+  });
+}
+
 #define GPX_INSTANTIATE_KBUILD(T)                                                                     \
   template void launch_scale_points<T>(const T*, int64_t, int64_t, int, const double*, int, T*,       \
                                        hipStream_t);                                                  \
@@ -193,7 +294,12 @@ void launch_kbuild_cross(int kernel, const T* As, int64_t m, int64_t mpad, const
   template void launch_kbuild_sym_w<T>(int, const T*, int64_t, int64_t, int, double, const T*, double, double, T*, \
                                        int64_t, hipStream_t);                                         \
   template void launch_kbuild_cross<T>(int, const T*, int64_t, int64_t, const T*, int64_t, int64_t,   \
-                                       int, double, T*, int64_t, hipStream_t);
+                                       int, double, T*, int64_t, hipStream_t);                        \
+  template void launch_kinds_diag<T>(const int32_t*, const T*, int64_t, double, double, double, T*, hipStream_t); \
+  template void launch_kbuild_sym_k<T>(int, const T*, int64_t, int64_t, int, double, const int32_t*, const double*, int, \
+                                       const T*, T*, int64_t, hipStream_t);                           \
+  template void launch_kbuild_cross_k<T>(int, const T*, int64_t, int64_t, const T*, int64_t, int64_t, int, double, \
+                                         const int32_t*, const double*, int, T*, int64_t, hipStream_t);
 GPX_INSTANTIATE_KBUILD(double)
 GPX_INSTANTIATE_KBUILD(float)
 

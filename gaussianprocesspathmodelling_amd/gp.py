@@ -128,6 +128,7 @@ class GP:
         self._h = h
         self._fitted = False
         self._weights_set = False  # gpx_set_noise_weights holds a vector for the next fits
+        self._kinds_set = False    # gpx_set_observation_kinds holds kinds for the next fits
         self._alpha = None
         self.info_ = 0
         self.jitter_used_ = self.jitter
@@ -245,11 +246,87 @@ class GP:
         self._check(self._lib.gpx_get_noise_weights(self._h, C.c_void_p(out.ctypes.data)))
         return out
 
+    def _set_observation_kinds(self, kinds, derivative_noise):
+        """the kinds of the fits that follow (``gpx_set_observation_kinds``); None clears them"""
+        if kinds is None:
+            if self._kinds_set:
+                self._check(self._lib.gpx_set_observation_kinds(self._h, None, 0, 0.0, _abi.MEM_HOST))
+                self._kinds_set = False
+            return  # (a model that never had kinds makes no call at all)
+        self._check(self._lib.gpx_set_observation_kinds(self._h, C.c_void_p(kinds.ctypes.data), kinds.size,
+                                                        float(derivative_noise), _abi.MEM_HOST))
+        self._kinds_set = True
+
+    def _with_derivatives(self, X, y, derivatives, noise_weights=None):
+        """``(X, y, noise_weights, kinds)`` of a fit: without ``derivatives`` the arguments as they are and no kinds;
+        with ``derivatives = (Xd, dims, yd)`` the value rows first and the derivative rows last, ``kinds`` (N + Nd,)
+        int32 (-1: a value, j: a value of d f / d x_j), and weights of length N extended by ones."""
+        if derivatives is None:
+            return X, y, noise_weights, None
+        try:
+            Xd, dims, yd = derivatives
+        except (TypeError, ValueError):
+            raise ValueError("derivatives must be (Xd, dims, yd)") from None
+        if not (_is_torch(X) == _is_torch(Xd) == _is_torch(yd) == _is_torch(y)):
+            raise ValueError("Xd and yd must be of the same kind as X and y: all NumPy arrays or all tensors")
+        if not _is_torch(X):
+            X, y, Xd, yd = (np.asarray(v) for v in (X, y, Xd, yd))
+            if noise_weights is not None:
+                noise_weights = np.asarray(noise_weights)
+        if len(X.shape) != 2 or len(Xd.shape) != 2 or Xd.shape[1] != X.shape[1]:
+            raise ValueError("X must be (N, d) and Xd (Nd, d)")
+        N, d = int(X.shape[0]), int(X.shape[1])
+        Nd = int(Xd.shape[0])
+        if len(y.shape) not in (1, 2) or y.shape[0] != N:
+            raise ValueError("y must be (N,) or (N, k) with the same N as X")
+        if tuple(yd.shape) != (Nd,) + tuple(y.shape[1:]):
+            raise ValueError("yd must be (Nd,) or (Nd, k), shaped as y")
+        dims = np.asarray(dims)
+        if dims.ndim == 0:
+            dims = np.full((Nd,), int(dims))
+        if dims.shape != (Nd,) or not np.issubdtype(dims.dtype, np.integer) or np.any(dims < 0) or np.any(dims >= d):
+            raise ValueError(f"dims must be an int or (Nd,) ints in [0, {d})")
+        kinds = np.concatenate([np.full((N,), -1, dtype=np.int32), dims.astype(np.int32)])
+        if _is_torch(X):
+            import torch
+            cat, ones = torch.cat, lambda like: torch.ones((Nd,), dtype=like.dtype, device=like.device)
+            Xd, yd = Xd.to(X.device, X.dtype), yd.to(y.device, y.dtype)
+        else:
+            cat, ones = np.concatenate, lambda like: np.ones((Nd,), dtype=np.asarray(like).dtype)
+        w = noise_weights
+        if w is not None and tuple(w.shape) == (N,) and Nd > 0:
+            w = cat([w, ones(w)])
+        return cat([X, Xd]), cat([y, yd]), w, kinds
+
+    @property
+    def observation_kinds_(self):
+        """Kind of every observation row of the fitted model (N,) int32: -1 a value of f, j a value of d f / d x_j
+        (``fit(..., derivatives=)`` puts the value rows first); all -1 for a fit without derivative observations."""
+        if not self._fitted:
+            raise RuntimeError("no fit")
+        out = np.empty((self._N,), dtype=np.int32)
+        self._check(self._lib.gpx_get_observation_kinds(self._h, C.c_void_p(out.ctypes.data)))
+        return out
+
     # -- API ----------------------------------------------------------------------------
-    def fit(self, X, y, noise_weights=None):
+    def fit(self, X, y, noise_weights=None, derivatives=None, derivative_noise=0.0):
         """Factorise and solve.  ``noise_weights`` (N,), of the same kind as ``X`` (NumPy array or device tensor): the
         diagonal of K gets ``noise * w_i + jitter`` instead of ``noise + jitter``; None (the default) means none — also
-        after a weighted fit."""
+        after a weighted fit.
+
+        ``derivatives = (Xd, dims, yd)`` conditions the model on derivative observations as well
+        (``gpx_set_observation_kinds``): ``yd[i]`` ((Nd,) or (Nd, k), as ``y``) is a value of d f / d x_dims[i] at
+        ``Xd[i]`` — a velocity when that input is time; ``dims`` an int or (Nd,) ints; ``Xd`` and ``yd`` of the same
+        kind as ``X``.  Their noise variance is ``derivative_noise`` (>= 0, fixed; 0 with a waypoint ``w_i = 0`` at the
+        same point: "pass through here with this velocity").  The model then holds the N value rows followed by the Nd
+        derivative rows (``alpha_``, ``observation_kinds_``, ``noise_weights_``); ``noise_weights`` may have length N
+        (derivative rows get 1) or N + Nd.  RBF, Matern-5/2 and Matern-3/2 on one device, float64 / float32; None (the
+        default) means none — also after such a fit."""
+        X, y, noise_weights, kinds = self._with_derivatives(X, y, derivatives, noise_weights)
+        return self._fit_rows(X, y, noise_weights, kinds, derivative_noise)
+
+    def _fit_rows(self, X, y, noise_weights, kinds, derivative_noise):
+        """:meth:`fit` of observation rows that are concatenated already, ``kinds`` (None: all values) theirs"""
         px, kx, keepx, devx, sx = self._as_input(X, "X")
         py, ky, keepy, devy, sy = self._as_input(y, "y")
         if len(sx) != 2:
@@ -263,6 +340,7 @@ class GP:
         if self.lengthscale.size not in (1, d):
             raise ValueError("lengthscale must be scalar or have d entries")
         self._set_noise_weights(noise_weights, N, kx)  # (refused: the model is as it was)
+        self._set_observation_kinds(kinds, derivative_noise)
         self._y1d = len(sy) == 1
         self._N, self._d, self._k = N, d, k
         self._alpha = None
@@ -339,21 +417,26 @@ class GP:
         self._check(self._lib.gpx_reserve(self._h, int(n)))
         return self
 
-    def fit_predict(self, X, y, Xs, include_noise=False, noise_weights=None):
+    def fit_predict(self, X, y, Xs, include_noise=False, noise_weights=None, derivatives=None, derivative_noise=0.0):
         """``fit(X, y)`` and ``predict(Xs)`` (mean and variance) as ONE factorisation pass: the cross-kernel rows
         of the query points ride through the blocked Cholesky as bordered rows (``gpx_fit_predict``), so the
         variance solve is part of the trailing updates instead of a pass of its own — the small-N schedule
         (N = 8192: the updates' idle CUs take the work).  The model is fitted afterwards as after ``fit``.
         On a shard or a device group every rank's slice of the query points rides through ITS part of the sharded
         factorisation (collective: every rank of a shard makes the call).  ``dtype="mixed"`` takes the two calls.
-        ``noise_weights`` as for :meth:`fit`; ``include_noise`` as for :meth:`predict`."""
+        ``noise_weights``, ``derivatives`` and ``derivative_noise`` as for :meth:`fit`; ``include_noise`` as for
+        :meth:`predict`."""
+        X, y, noise_weights, kinds = self._with_derivatives(X, y, derivatives, noise_weights)
+
+        def two_calls():
+            return self._fit_rows(X, y, noise_weights, kinds, derivative_noise).predict(Xs, include_noise=include_noise)
+
         fused = self.dtype in ("float64", "float32")
         pq, kq, keepq, devq, sq = self._as_input(Xs, "Xs")
         px, kx, keepx, devx, sx = self._as_input(X, "X")
         py, ky, keepy, devy, sy = self._as_input(y, "y")
         if not fused or len(sq) != 2 or not (kx == ky == kq):
-            mean, var = self.fit(X, y, noise_weights=noise_weights).predict(Xs, include_noise=include_noise)
-            return mean, var
+            return two_calls()
         if len(sx) != 2:
             raise ValueError("X must be (N, d)")
         N, d = sx
@@ -366,6 +449,7 @@ class GP:
             raise ValueError("lengthscale must be scalar or have d entries")
         M = sq[0]
         self._set_noise_weights(noise_weights, N, kx)
+        self._set_observation_kinds(kinds, derivative_noise)
         self._y1d = len(sy) == 1
         self._N, self._d, self._k = N, d, k
         self._alpha = None
@@ -387,10 +471,11 @@ class GP:
         for _ in range(max(1, self.max_tries)):
             rc = self._lib.gpx_fit_predict(self._h, px, py, N, d, k, _abi.dptr(ls), ls.size, self.variance, self.noise,
                                            jitter, pq, M, pm, pv, kx, C.byref(info))
-            if rc in (_abi.E_UNSUPPORTED, _abi.E_NOMEM):
+            if rc == _abi.E_NOMEM or (rc == _abi.E_UNSUPPORTED and kinds is None):
                 # the library's own limits decide (its batch cap honours GPX_PRED_BATCH; M more bordered rows of K and
                 # of the panel buffers may not fit beside the factor): the documented fallback is the two calls
-                return self.fit(X, y, noise_weights=noise_weights).predict(Xs, include_noise=include_noise)
+                # (with kinds set, GPX_E_UNSUPPORTED is the refusal of the model itself: raised below)
+                return two_calls()
             self._check(rc)
             self.info_ = int(info.value)
             if self.info_ == 0:
@@ -650,10 +735,16 @@ class GP:
         self._check(self._lib.gpx_get_timings(self._h, C.byref(t)))
         return t.as_dict()
 
-    def log_marginal_likelihood(self, y):
-        """-1/2 y^T alpha - 1/2 logdet - N/2 log(2 pi), summed over target columns."""
+    def log_marginal_likelihood(self, y, derivatives=None, derivative_noise=0.0):
+        """-1/2 y^T alpha - 1/2 logdet - N/2 log(2 pi), summed over target columns.  ``derivatives`` as passed to
+        :meth:`fit` (their targets follow ``y``; N counts both; ``derivative_noise`` is part of the fit already)."""
         if _is_torch(y):
             y = y.detach().cpu().numpy()
+        if derivatives is not None:
+            yd = derivatives[2]
+            yd = yd.detach().cpu().numpy() if _is_torch(yd) else np.asarray(yd)
+            y = np.concatenate([np.asarray(y, dtype=np.float64).reshape(len(y), -1),
+                                np.asarray(yd, dtype=np.float64).reshape(len(yd), -1)])
         Y = np.asarray(y, dtype=np.float64).reshape(self._N, -1)
         A = self.alpha_.reshape(self._N, -1).astype(np.float64)
         n, k = Y.shape
@@ -680,7 +771,7 @@ class GP:
         return float(lml.value), grad
 
     def optimize(self, X, y, params=("lengthscale", "variance", "noise"), bounds=(1e-4, 1e4), maxiter=40,
-                 rel_step=1e-4, jac="analytic", noise_weights=None):
+                 rel_step=1e-4, jac="analytic", noise_weights=None, derivatives=None, derivative_noise=0.0):
         """Fit the hyper-parameters by maximising the log marginal likelihood (SURVEY.md §8f
         rank 1: the natural step after ``fit``; the reference has no counterpart).
 
@@ -692,7 +783,10 @@ class GP:
         Non-positive-definite trial points count as very bad, they do not raise.  Leaves the
         model fitted at the best point found and returns scipy's result (``.fun`` = minus the
         log marginal likelihood there).  ``noise_weights`` as for :meth:`fit`: every fit of the search, the final one
-        included, is made with them; ``noise`` is then the level that is learnt."""
+        included, is made with them; ``noise`` is then the level that is learnt.  ``derivatives`` and
+        ``derivative_noise`` as for :meth:`fit` as well: such a model has no analytic gradient, the search runs on
+        central differences of the log marginal likelihood; ``derivative_noise`` is fixed, not learnt."""
+        fit_kw = dict(noise_weights=noise_weights, derivatives=derivatives, derivative_noise=derivative_noise)
         from scipy.optimize import minimize
         names = [p for p in ("lengthscale", "variance", "noise") if p in params]
         if not names or len(names) != len(tuple(params)):
@@ -722,7 +816,7 @@ class GP:
             # sharded: the gradient needs the replicated-factor mode, which the library picks from N
             # and the card's memory at fit time — ask it once (every rank gets the same answer)
             try:
-                self.fit(X, y, noise_weights=noise_weights)
+                self.fit(X, y, **fit_kw)
                 self.lml_gradient()
             except _abi.GpxError:
                 analytic = False
@@ -740,7 +834,7 @@ class GP:
             unpack(v)
             g = np.zeros(len(cols))
             try:
-                self.fit(X, y, noise_weights=noise_weights)
+                self.fit(X, y, **fit_kw)
                 if analytic:
                     try:
                         lml, full = self.lml_gradient()
@@ -754,7 +848,7 @@ class GP:
                         raise _NoAnalyticGradient() from e
                     f, g = -lml, -full[cols]
                 else:
-                    f = -self.log_marginal_likelihood(y)
+                    f = -self.log_marginal_likelihood(y, derivatives=derivatives)
             except np.linalg.LinAlgError:
                 f = 1e300
             if not np.isfinite(f) or not np.all(np.isfinite(g)):
@@ -776,6 +870,6 @@ class GP:
         except _NoAnalyticGradient:
             res = search(best["v"], False)   # from the best point the analytic steps reached
         unpack(best["v"])
-        self.fit(X, y, noise_weights=noise_weights)
+        self.fit(X, y, **fit_kw)
         res.x, res.fun = best["v"], best["f"]
         return res

@@ -241,13 +241,17 @@ class PathModel:
     (x, y) as two targets sharing ONE Cholesky factor.  Targets are
     standardised per column before the fit (the GP prior has zero mean) and mapped back by
     :meth:`predict`.  ``step_weights`` (L,), or None: the per-step noise weights the model was fitted with
-    (``fit_path_models(step_noise=True)``); :meth:`add_paths` and :meth:`log_likelihood` then use them too."""
+    (``fit_path_models(step_noise=True)``); :meth:`add_paths` and :meth:`log_likelihood` then use them too.
+    ``has_velocities``: the model was also conditioned on observed velocities (``fit_path_models(velocities=)``: derivative
+    observations along ``"t"``); every prediction works unchanged, :meth:`add_paths` does not (``GP.update`` cannot append
+    to such a fit)."""
 
-    def __init__(self, gp, keys, in_lo, in_span, y_mean, y_std, inputs, targets, step_weights=None):
+    def __init__(self, gp, keys, in_lo, in_span, y_mean, y_std, inputs, targets, step_weights=None, has_velocities=False):
         self.gp, self.keys = gp, list(keys)
         self.in_lo, self.in_span, self.y_mean, self.y_std = in_lo, in_span, y_mean, y_std
         self.inputs, self.targets = tuple(inputs), tuple(targets)
         self.step_weights = None if step_weights is None else np.asarray(step_weights, dtype=np.float64)
+        self.has_velocities = bool(has_velocities)
 
     def _tiled_weights(self, n_rows, what):
         """the step weights repeated for n_rows / L whole paths (None without step weights)"""
@@ -320,6 +324,9 @@ class PathModel:
         A model with ``step_weights`` appends with them, tiled over the new paths (which must have its path length).
         Extends ``keys``; returns ``self``."""
         keys = list(keys)
+        if self.has_velocities:
+            raise ValueError("add_paths: the model is conditioned on velocities (derivative observations), and a fit with "
+                             "derivative observations cannot be appended to: fit the cluster again with fit_path_models")
         if not keys:
             return self
         if self.step_weights is not None and any(len(trajs.pathdict[q]) != len(self.step_weights) for q in keys):
@@ -374,7 +381,8 @@ def step_noise_weights(Yn, n_paths):
 
 
 def fit_path_models(trajs, clusters, inputs=("t",), targets=("x", "y"), devices=None, optimize=False,
-                    lengthscale=0.25, variance=1.0, noise=0.05, step_noise=False, **gp_kwargs):
+                    lengthscale=0.25, variance=1.0, noise=0.05, step_noise=False, velocities=None, velocity_noise=0.05,
+                    **gp_kwargs):
     """One exact GP per cluster of ``clusters`` = {cluster id: [path ids]} — what
     :func:`kmeans` (``kmeansclustering``, GPmap.py:36-93) returns — modelling the cluster's paths
     as (x(t), y(t)); the modelling step the reference's title names and its clustering prepares
@@ -387,6 +395,11 @@ def fit_path_models(trajs, clusters, inputs=("t",), targets=("x", "y"), devices=
     gradient) first.  ``step_noise``: the paths of a cluster are tight in some places and spread out in others, so each
     cluster's observations get per-step noise weights (:func:`step_noise_weights`, tiled over its paths; the paths
     of a cluster have one length); ``noise`` stays the level, and the model keeps them as ``step_weights``.
+    ``velocities`` = {path id: (L, k)}: observed velocities of (some of) the paths — tracker or odometry output — one row
+    per path point and one column per target, in raw target units per raw time unit.  Needs ``"t"`` among the inputs.
+    They condition the cluster's GP as derivative observations along ``"t"`` at the path's own points
+    (``GP.fit(derivatives=)``), normalised by the chain rule ``v * in_span[t] / y_std[c]``; ``velocity_noise`` is their
+    noise variance in those normalised units (as ``noise`` is for the positions; fixed, not learnt by ``optimize``).
     Returns {cluster id: :class:`PathModel`}; empty clusters are skipped."""
     import threading
     from concurrent.futures import ThreadPoolExecutor
@@ -402,6 +415,9 @@ def fit_path_models(trajs, clusters, inputs=("t",), targets=("x", "y"), devices=
         if not devs:
             raise ValueError("devices must not be empty")
     known = set(trajs.keys())
+    velocities = dict(velocities) if velocities else {}
+    if velocities and "t" not in inputs:
+        raise ValueError(f"velocities need 't' among the inputs, have {tuple(inputs)}")
     jobs = []
     for cid, keys in clusters.items():
         keys = list(keys)
@@ -412,25 +428,46 @@ def fit_path_models(trajs, clusters, inputs=("t",), targets=("x", "y"), devices=
             raise KeyError(f"cluster {cid!r} names unknown paths {missing[:3]}")
         jobs.append((cid, keys))
 
+    def cluster_velocities(keys, X, span, sd):
+        """(Xd, dims, yd) of the cluster's paths that have velocities (None: none has): derivative observations along "t"
+        at the normalised inputs of those paths' own points, d target / d t_normalised = v * span[t] / y_std"""
+        jt = tuple(inputs).index("t") if velocities else 0
+        rows, vals, at = [], [], 0
+        for q in keys:
+            L = len(trajs.pathdict[q])
+            if q in velocities:
+                v = np.asarray(velocities[q], dtype=np.float64)
+                if v.shape != (L, len(targets)):
+                    raise ValueError(f"velocities[{q!r}] must be ({L}, {len(targets)}): one row per path point, one column "
+                                     f"per target")
+                rows.append(np.arange(at, at + L))
+                vals.append(v * span[jt] / sd[None, :])
+            at += L
+        if not rows:
+            return None
+        return np.ascontiguousarray(X[np.concatenate(rows)]), jt, np.ascontiguousarray(np.concatenate(vals))
+
     def fit_one(slot, cid, keys):
         X, Y, (lo, span) = to_gp_inputs(trajs, keys, inputs=inputs, targets=targets, normalise=True)
         mu = Y.mean(axis=0)
         sd = Y.std(axis=0)
         sd = np.where(sd > 0, sd, 1.0)
         Yn = np.ascontiguousarray((Y - mu) / sd)
+        der = cluster_velocities(keys, X, span, sd)
         gp = GP(lengthscale=lengthscale, variance=variance, noise=noise, device=devs[slot % len(devs)],
                 **gp_kwargs)
         sw = step_noise_weights(Yn, len(keys)) if step_noise else None
         w = None if sw is None else np.tile(sw, len(keys))
+        kw = {} if der is None else dict(derivatives=der, derivative_noise=velocity_noise)
         try:
             if optimize:
-                gp.optimize(X, Yn, noise_weights=w)  # leaves the model fitted at the best point
+                gp.optimize(X, Yn, noise_weights=w, **kw)  # leaves the model fitted at the best point
             else:
-                gp.fit(X, Yn, noise_weights=w)
+                gp.fit(X, Yn, noise_weights=w, **kw)
         except Exception:
             gp.close()
             raise
-        return cid, PathModel(gp, keys, lo, span, mu, sd, inputs, targets, step_weights=sw)
+        return cid, PathModel(gp, keys, lo, span, mu, sd, inputs, targets, step_weights=sw, has_velocities=der is not None)
 
     by_dev = [[] for _ in devs]                    # one worker per device, its clusters in order
     for i, (cid, keys) in enumerate(jobs):

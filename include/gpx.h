@@ -308,6 +308,35 @@ int gpx_score_blocks_weighted(gpx_handle* h, const void* Xs, const void* ys, con
                               double diag_add, void* logp /* (G,k) */, void* maha /* (G,k) */, void* logdet /* (G) */,
                               int32_t mem_kind, int64_t* info);
 
+/* ---- derivative observations (additive to ABI v6) ----------------------------------------------------------------------
+ * Model: row i of a fit is an observation at x_i with a kind: -1 a value of f, j (0 <= j < d) a value of d f / d x_j — a
+ * velocity along input j.  A derivative of a GP is jointly Gaussian with it, so both enter one Gram matrix, one Cholesky
+ * factor and the same prediction stages.  With u = (x_a - x_b) / l per dimension and v, g, h of the family (csrc/gpx_cov.h;
+ * RBF: g = h = v) the entry for kinds (a, b) is
+ *   (-1, -1)  v               ( i, -1)  -g u_i / l_i
+ *   (-1,  j)  g u_j / l_j     ( i,  j)  (g delta_ij - h u_i u_j) / (l_i l_j)
+ * and the diagonal term is (kind_i < 0 ? sn2 : sn2_deriv) w_i + jitter: sn2_deriv >= 0 is the noise variance of the
+ * derivative rows (a level of its own: its unit is target / input), w the noise weights (ones when none are set).  A value
+ * with w_i = 0 and a derivative with sn2_deriv = 0 at the same point say "pass through here with this velocity".
+ * Query points stay values (gpx_predict, gpx_predict_cov, gpx_sample_posterior, gpx_score_blocks) or values and
+ * derivatives (gpx_predict_grad); their prior variances do not change.
+ *
+ * gpx_set_observation_kinds copies n kinds (host or device memory as mem_kind says) and sn2_deriv into the handle.  They
+ * apply to every later gpx_fit / gpx_fit_predict until they are replaced or cleared (kind == NULL with n == 0).  A kind
+ * below -1, or a negative or non-finite sn2_deriv: GPX_E_ARG, nothing is stored and the kinds of the call before stay.  A
+ * fit with N != n, or with a kind >= d, returns GPX_E_ARG before anything is computed.  An existing fit is not touched: it
+ * keeps the kinds it was made with, for every call, until the next fit.
+ * Single-device GPX_F64 / GPX_F32 handles, RBF, Matern-5/2 and Matern-3/2.  GPX_E_UNSUPPORTED before anything is computed
+ * or exchanged, with the previous fit still valid and gpx_last_error saying why: a fit with a derivative kind on a
+ * Matern-1/2 handle (not differentiable; kinds that are all -1 fit as the plain model there); a fit with kinds set on
+ * GPX_MIXED handles, device groups, shards and handles that own a communicator (the set call itself succeeds, and once
+ * the kinds are cleared the handle fits as before); gpx_lml_grad, gpx_append and gpx_append_weighted on a fit that has a
+ * derivative row.  gpx_predict_grad without variances takes the batch route on such a fit (its matrix-free product knows
+ * value columns only).  With no kinds set a handle launches the kernels it launched before and allocates nothing more. */
+int gpx_set_observation_kinds(gpx_handle* h, const int32_t* kind, int64_t n, double sn2_deriv, int32_t mem_kind);
+/* The kinds of the current fit, all -1 when it was made without any.  GPX_E_ARG without a fit. */
+int gpx_get_observation_kinds(gpx_handle* h, int32_t* out /* (N) host */);
+
 int gpx_get_alpha(gpx_handle* h, void* out /* (N,k) host */);
 /* Log marginal likelihood of the last fit and its gradient w.r.t. the LOG hyper-parameters —
  * SURVEY.md §8(f) row 1 ("log marginal likelihood + hyper-parameter gradient hooks"; no anchor
