@@ -1574,8 +1574,9 @@ int solve_few(gpx_handle* h, T* RT, int k, const T* L, int64_t ld, int64_t n, co
   return GPX_OK;
 }
 
-// the streaming solver needs the fit's explicit block inverses (h->Wblk, blocks of width h->nbw <= 1024: every block of
-// an unsharded fit, or of a shard that keeps the whole factor), at most 8 right-hand sides (GPX_FEW_SOLVE=0: always the
+// the streaming solver needs the fit's explicit block inverses (h->Wblk, blocks of width h->nbw up to 1024 or a multiple
+// of 1024, which solve_few serves in 1024-sub-blocks; other widths above 1024 take the slab path: every block of an
+// unsharded fit, or of a shard that keeps the whole factor), at most 8 right-hand sides (GPX_FEW_SOLVE=0: always the
 // slab path)
 bool few_solver_applies(const gpx_handle* h) {
   return h->env.few_solve && h->nbw > 0 && (h->nbw <= 1024 ? h->nbw % 128 == 0 : h->nbw % 1024 == 0) && h->k <= 8 &&

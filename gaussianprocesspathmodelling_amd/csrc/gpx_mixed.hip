@@ -158,7 +158,7 @@ __global__ __launch_bounds__(256) void rows_sumsq_kernel(const double* __restric
 // row) or with the row block (backward: columns to the left, one lane per column pair, sixteen waves over the
 // block's rows) — bandwidth-bound launches of the whole GPU instead of slab solves and 64-row MFMA updates that are
 // 20-30 us of launch and latency each.  Fixed summation order everywhere (no atomics).
-constexpr int FEW_NJ = 1024;  // widest block (the panel width's maximum is 2048: wider falls back to the slab path)
+constexpr int FEW_NJ = 1024;  // widest block of a sweep (panels of 2048, 3072, 4096 are served in 1024-sub-blocks; other widths above 1024 take the slab path)
 
 // 16-byte row loads (4 floats / 2 doubles per lane), 8-byte column loads (2 floats / 1 double per lane)
 template <typename T>

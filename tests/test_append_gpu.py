@@ -123,6 +123,8 @@ def check(o, ref, fresh, tag):
     (2048, 100, 3, 1, "rbf", False, 1024),        # N an exact multiple of nb: R0 = N, only new rows are factorised
     (1500, 2500, 3, 1, "rbf", False, 1024),       # m > nb: several panels of the restart, the look-ahead schedule
     (8192 + 512, 200, 3, 1, "rbf", False, 0),     # the library's width, R0 = 8192
+    (4000, 450, 3, 1, "rbf", False, 2048),        # a wide factor: R0 = 2048, the new points cross 4096 and open a third panel
+    (4300, 200, 3, 1, "rbf", False, 2048),        # R0 = 4096: only the ragged third panel is redone
 ])
 def test_single_append(N, m, d, k, kernel, ard, block):
     X, y, Xs = problem(N + m, d, 90, k, seed=N + m)
@@ -193,6 +195,29 @@ def test_chain_of_appends_with_and_without_reserve():
     assert len(set(ptrs)) == 1 and cap == 4096 and ld == 4096 + 16     # in place: the factor never moved
     check(res, ref, fresh, "reserved chain:")
     check(res, ref, plain, "reserved against unreserved chain:")
+
+
+def test_append_in_place_on_the_wide_panel_width(monkeypatch):
+    """the first wide row of test_single_append under the library's own choice of 2048-wide panels (GPX_NB_WIDE_FROM=2048:
+    nb_pred = 2048, so the forward solve of the new rows takes the dense block solves) on a reserved factor: it does not move"""
+    N, m = 4000, 450
+    X, y, Xs = problem(N + m, 3, 90, 1, seed=N + m)
+    ref = reference("rbf", 0.25, X, y, Xs, False, False)
+    monkeypatch.setenv("GPX_NB_WIDE_FROM", "2048")
+    monkeypatch.delenv("GPX_NB_PRED", raising=False)
+    with GP("rbf", 0.25, SF2, SN2, jitter=0.0) as gp:
+        fresh = outputs(gp.fit(X, y), Xs, False, False)
+    with GP("rbf", 0.25, SF2, SN2, jitter=0.0) as gp:
+        gp.reserve(6144)
+        gp.fit(X[:N], y[:N])
+        before = factor_ptr(gp)
+        gp.update(X[N:], y[N:])
+        assert factor_ptr(gp) == before and before[1:] == (6144 + 16, 6144)       # in place: the factor never moved
+        assert gp.get_state()["fitted"]["N"] == N + m
+        check(outputs(gp, Xs, False, False), ref, fresh, "wide-auto, reserved, N=4000 m=450:")
+    monkeypatch.delenv("GPX_NB_WIDE_FROM")
+    with GP("rbf", 0.25, SF2, SN2, jitter=0.0) as gp:                          # the 1024 fit: other bits, so the width took
+        assert not np.array_equal(gp.fit(X, y).alpha_, fresh["alpha"])
 
 
 def test_untouched_handles_keep_their_bits_and_appends_do_not_depend_on_stream_timing():

@@ -390,3 +390,66 @@ def test_schedule_variants_give_the_same_factorisation(monkeypatch, env):
             assert np.max(np.abs(mean - m0)) <= 1e-9 * np.abs(m0).max() and abs(gp.log_det_ - ld0) <= 1e-12 * abs(ld0)
         m2, v2 = gp.fit(X, y).predict(Xs)                  # refit: the strip counter is reset per fit
         assert np.array_equal(m2, mean) and np.array_equal(v2, var)
+
+
+_WIDE_BASE = []
+
+
+def wide_schedule_baseline():
+    """the default schedule at N = 12288 in 2048-wide panels (GPX_NB_WIDE_FROM=2048 is set by the caller): mean / var /
+    alpha / logdet and the trailing-update counters — computed by the first wide variant that runs, before its own
+    switches are set.  The counters are host arithmetic over nr (nr + 1) nbp per large update, so they are exact: they must
+    be those of an explicit block=2048 handle and not those of the 1024 fit — that is what shows that the width took."""
+    if not _WIDE_BASE:
+        X, y, Xs, mr, vr, m0, v0, a0, ld0 = schedule_variants_baseline()
+        with GP("rbf", 0.25, 1.5, 1e-2, jitter=0.0) as gp:
+            mean, var = gp.fit(X, y).predict(Xs)
+            wide = (gp.timings_["syrk_flops"], gp.timings_["syrk_launches"])
+            _WIDE_BASE.append((mean, var, gp.alpha_.copy(), gp.log_det_))
+        counters = {}
+        with pytest.MonkeyPatch.context() as mp:
+            mp.delenv("GPX_NB_WIDE_FROM")
+            for name, block, nb_pred in (("default", 0, None), ("explicit", 2048, "2048")):
+                if nb_pred:
+                    mp.setenv("GPX_NB_PRED", nb_pred)          # read when the handle is created
+                with GP("rbf", 0.25, 1.5, 1e-2, jitter=0.0, block=block) as gp:
+                    me, ve = gp.fit(X, y).predict(Xs)
+                    counters[name] = (gp.timings_["syrk_flops"], gp.timings_["syrk_launches"])
+                    if name == "explicit":
+                        assert np.array_equal(me, mean) and np.array_equal(ve, var) and np.array_equal(gp.alpha_, _WIDE_BASE[0][2])
+        print(f"trailing updates (flops, launches): wide-auto {wide} block=2048 {counters['explicit']} default {counters['default']}")
+        assert wide == counters["explicit"] and wide[0] != counters["default"][0] and wide[1] != counters["default"][1]
+        assert not np.array_equal(_WIDE_BASE[0][2], a0)
+    return _WIDE_BASE[0]
+
+
+@pytest.mark.parametrize("env", [{"GPX_FUSED_STRIP": "1"}, {"GPX_DIAG_STEP": "64"},
+                                 {"GPX_FUSED_STRIP": "1", "GPX_DIAG_STEP": "64"}, {"GPX_CU_SELF_RESERVE": "1"}, {"GPX_CU_SELF_RESERVE": "4"},
+                                 {"GPX_CHAIN_FLAG": "0"},
+                                 {"GPX_SPLIT_STRIP": "0"}, {"GPX_SPLIT_STRIP": "0", "GPX_CHAIN_FLAG": "0"},
+                                 {"GPX_REST_SPLIT": "0"}, {"GPX_REST_SPLIT": "4"}, {"GPX_SOLVE_TOP": "0"}])
+def test_schedule_variants_at_the_wide_panel_width(monkeypatch, env):
+    """The schedule switches of the test above on 2048-wide panels (GPX_NB_WIDE_FROM=2048: what the library picks from
+    N = 40960 on, and what the benchmark runs).  N = 12288 is 6 panels: the first three trailing updates are large enough to
+    fuse, the "ahead" launch of the REST runs (8192, 6144, 4096 rows beyond the strip), and the REST runs on 128-tiles with
+    K = 2048 (6144 and 4096 rows: more than 448 live tiles) — below N = 65536 the only place where the hot kernel of the
+    benchmark runs with its real K.  Same bars: the oracle at 1e-6, the wide default schedule bit for bit (the diagonal
+    stepping: 1e-9 on the mean, 1e-12 on logdet), a refit on the handle bit for bit."""
+    X, y, Xs, mr, vr = schedule_variants_baseline()[:5]
+    monkeypatch.setenv("GPX_NB_WIDE_FROM", "2048")
+    monkeypatch.delenv("GPX_NB_PRED", raising=False)
+    m0, v0, a0, ld0 = wide_schedule_baseline()
+    for k_, v_ in env.items():
+        monkeypatch.setenv(k_, v_)
+    with GP("rbf", 0.25, 1.5, 1e-2, jitter=0.0) as gp:
+        mean, var = gp.fit(X, y).predict(Xs)
+        assert gp.info_ == 0
+        em, ev = assert_parity(mean, var, mr, vr, 1.5)
+        dm, dl = np.max(np.abs(mean - m0)) / np.abs(m0).max(), abs(gp.log_det_ - ld0) / abs(ld0)
+        print(f"wide {env}: mean {em:.2e} var {ev:.2e} against the oracle; mean {dm:.2e} logdet {dl:.2e} against the wide default")
+        if "GPX_DIAG_STEP" not in env:
+            assert np.array_equal(mean, m0) and np.array_equal(var, v0) and np.array_equal(gp.alpha_, a0)
+        else:
+            assert dm <= 1e-9 and dl <= 1e-12
+        m2, v2 = gp.fit(X, y).predict(Xs)
+        assert np.array_equal(m2, mean) and np.array_equal(v2, var)

@@ -57,7 +57,11 @@ def test_kernel_matrix_cross(gpx, kernel):
 
 @pytest.mark.parametrize("m,n,k,lower", [(128, 128, 16, 0), (128, 256, 64, 0), (256, 384, 512, 0),
                                          (64, 192, 32, 0), (192, 64, 528, 0), (384, 384, 512, 1),
-                                         (320, 320, 64, 1)])
+                                         (320, 320, 64, 1),
+                                         # the library's own walks: K = 1024 and 2048 (the panel widths), 128- and 64-tiles,
+                                         # and a K that is a multiple of 16 but not of 32
+                                         (256, 256, 1024, 0), (256, 384, 2048, 0), (384, 384, 2048, 1), (192, 192, 2048, 1),
+                                         (128, 256, 2064, 0)])
 def test_gemm_nt(gpx, m, n, k, lower):
     rng = np.random.default_rng(m * 7 + n * 3 + k)
     A = rng.standard_normal((m, k))
@@ -101,7 +105,8 @@ def test_trsm_right_lower_trans(gpx, m, nb):
     assert np.max(np.abs(X - ref)) <= 1e-10 * np.max(np.abs(ref))
 
 
-@pytest.mark.parametrize("n,block", [(64, 0), (128, 128), (512, 0), (1024, 0), (1152, 256), (2048, 512)])
+@pytest.mark.parametrize("n,block", [(64, 0), (128, 128), (512, 0), (1024, 0), (1152, 256), (2048, 512),
+                                     (4608, 2048), (2560, 1536)])   # several panels wider than 512, one no power of two
 def test_potrf_backward_error(gpx, n, block):
     rng = np.random.default_rng(n)
     Xp = rng.uniform(size=(n, 3))

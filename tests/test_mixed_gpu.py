@@ -83,7 +83,7 @@ def test_mixed_limits():
                                          (1024, 10, 128, 8), (4096, 200, 1024, 1)])
 def test_refinement_across_panel_widths(N, M, block, k):
     """The refinement's streaming few-right-hand-side solves work with the fit's block inverses: every panel width up to
-    1024 (wider: the slab path), a single panel, a ragged last panel, 1 .. 8 targets — adaptive default, 1e-6 on the mean."""
+    1024 and its multiples (2048: 1024-sub-blocks of the wide inverses; other widths above 1024: the slab path), a single panel, a ragged last panel, 1 .. 8 targets — adaptive default, 1e-6 on the mean."""
     X, y, Xs = synthetic_problem(N, 3, M, seed=N + block)
     Y = y if k == 1 else np.stack([np.cos((c + 1) * y) if c else y for c in range(k)], axis=1)
     ref = OracleGP("rbf", 0.25, 1.5, 1e-2, jitter=0.0).fit(X, Y)
