@@ -10,6 +10,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "gpx_internal.h"
 
 namespace gpx {
@@ -76,6 +78,14 @@ struct TileShapeG {
   __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gptr),  \
                                    (__attribute__((address_space(3))) void*)(lptr), 16, 0, 0)
 
+// a pointer the compiler can keep in SGPRs whatever it was computed from (a tile index read from LDS, say)
+template <typename P>
+__device__ __forceinline__ const P* uniform_ptr(const P* p) {
+  const uint64_t v = (uint64_t)p;
+  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v), hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
+  return (const P*)(((uint64_t)hi << 32) | lo);
+}
+
 // WVM = waves along M (2: 256-thread workgroup, 2 x 2 waves; 4: 512 threads, 4 x 2 waves).
 template <typename T, int BM, int BN, int WVM = 2, int KSUB = 1>
 __device__ __forceinline__ void gemm_tile_g(const T* A, int64_t lda, const T* B, int64_t ldb, int K,
@@ -94,20 +104,24 @@ __device__ __forceinline__ void gemm_tile_g(const T* A, int64_t lda, const T* B,
   T* As = smem;
   T* Bs = smem + 2 * S::A_STAGE;
 
-  // DMA: instruction q of this wave covers rows 8*(wave*I + q) .. +7; lane -> (row, slot)
+  // DMA: instruction q of this wave covers rows 8*(wave*I + q) .. +7; lane -> (row, slot).  The source is a
+  // wave-uniform base (the wave's first row; advanced per k-step in scalar registers) plus a 32-bit per-lane
+  // byte offset that is fixed for the tile: the wave's 8*I rows span (8*I - 1) * ld + BK elements, which fits 32
+  // bits of bytes for every ld < 2^24 elements — far beyond any matrix that fits the device.
   const int drow = lane >> 3, dslot = lane & 7;
-  const T* ga[IA];
-  const T* gb[IB];
+  uint32_t oa[IA], ob[IB];
 #pragma unroll
   for (int q = 0; q < IA; ++q) {
     const int row = (wave * IA + q) * 8 + drow;
-    ga[q] = A + (int64_t)row * lda + (dslot ^ swz(row)) * SL;
+    oa[q] = ((uint32_t)(q * 8 + drow) * (uint32_t)lda + (uint32_t)((dslot ^ swz(row)) * SL)) * (uint32_t)sizeof(T);
   }
 #pragma unroll
   for (int q = 0; q < IB; ++q) {
     const int row = (wave * IB + q) * 8 + drow;
-    gb[q] = B + (int64_t)row * ldb + (dslot ^ swz(row)) * SL;
+    ob[q] = ((uint32_t)(q * 8 + drow) * (uint32_t)ldb + (uint32_t)((dslot ^ swz(row)) * SL)) * (uint32_t)sizeof(T);
   }
+  const char* const gA = (const char*)uniform_ptr(A + (int64_t)(wave * IA * 8) * lda);
+  const char* const gB = (const char*)uniform_ptr(B + (int64_t)(wave * IB * 8) * ldb);
   T* const la = As + wave * IA * RQ;  // wave-uniform LDS destinations
   T* const lb = Bs + wave * IB * RQ;
 
@@ -118,48 +132,94 @@ __device__ __forceinline__ void gemm_tile_g(const T* A, int64_t lda, const T* B,
   const int b_off0 = (wc * WN + l15) * BK + ((2 * l4) ^ sw) * SL;
   const int b_off1 = (wc * WN + l15) * BK + ((2 * l4 + 1) ^ sw) * SL;
 
-#pragma unroll
-  for (int u = 0; u < KSUB; ++u) {
-#pragma unroll
-    for (int q = 0; q < IA; ++q) GPX_GLDS16(ga[q] + u * BK, la + u * BM * BK + q * RQ);
-#pragma unroll
-    for (int q = 0; q < IB; ++q) GPX_GLDS16(gb[q] + u * BK, lb + u * BN * BK + q * RQ);
-  }
-  __syncthreads();
-
-  // Per k-step: 8 first-half fragment reads, then the MFMAs with everything else issued in
-  // their shadow: the second-half fragment reads inside the first quarter of the burst, the
-  // DMA of step t+1 inside the second (sched_group_barrier: 0x8 MFMA, 0x100 DS read, 0x20
-  // VMEM read).  Measured on the SYRK: 65.1 TF with DMA + all 16 reads clumped before the
-  // burst -> 67.9 TF interleaved.  (A 4-stage, one-workgroup-per-CU variant with counted
-  // vmcnt and a second fragment set reached only 59.6 TF: per-wave wait time fell from 8.7 %
-  // to 3.7 %, but nothing covers the tile epilogue and the launch tail any more.)  The DMA is unconditional (clamped to the last step, landing in
-  // the buffer nobody reads again) so that the loop body stays one basic block.
-  constexpr int HALF = SL * MT * NT;  // MFMAs per half step
-  const int KT = K / (BK * KSUB);
-  for (int kt = 0; kt < KT; ++kt) {
-    const int buf = kt & 1;
-    const int64_t ko = (int64_t)(kt + 1 < KT ? kt + 1 : kt) * (BK * KSUB);
+  // stage `buf` <- the KSUB lines of k-step kt
+  auto dma = [&](int buf, int kt) __attribute__((always_inline)) {
+    const int64_t kb = (int64_t)kt * (BK * KSUB) * (int64_t)sizeof(T);
 #pragma unroll
     for (int u = 0; u < KSUB; ++u) {
-      const T* Ab = As + buf * S::A_STAGE + u * BM * BK;
-      const T* Bb = Bs + buf * S::B_STAGE + u * BN * BK;
-      slot_t a0[MT], b0[NT], a1[MT], b1[NT];
+#pragma unroll
+      for (int q = 0; q < IA; ++q)
+        GPX_GLDS16(gA + kb + u * BK * (int)sizeof(T) + oa[q], la + buf * S::A_STAGE + u * BM * BK + q * RQ);
+#pragma unroll
+      for (int q = 0; q < IB; ++q)
+        GPX_GLDS16(gB + kb + u * BK * (int)sizeof(T) + ob[q], lb + buf * S::B_STAGE + u * BN * BK + q * RQ);
+    }
+  };
+  // the last MT*NT MFMAs of a k-step (second half, s = SL-1): they run AFTER the step's barrier, see below
+  slot_t a0[MT], b0[NT], a1[MT], b1[NT];
+  auto carried = [&]() __attribute__((always_inline)) {
+#pragma unroll
+    for (int m = 0; m < MT; ++m)
+#pragma unroll
+      for (int n = 0; n < NT; ++n) acc[m][n] = Num<T>::mfma(a1[m][SL - 1], b1[n][SL - 1], acc[m][n]);
+  };
+
+  // The k-step is ROTATED across its barrier.  The barrier releases the four waves at once and all of them
+  // need fragments before their next MFMA, so the first-half fragment reads used to be exposed on every step;
+  // now the last MT*NT MFMAs of step t (registers only) are carried over the barrier and cover the reads of
+  // step t+1:
+  //   barrier | first-half reads of t+1 | carried MFMAs of t | first quarter of the burst: one second-half read and
+  //   one DMA of step t+2 per G_RD MFMAs | the rest of the step's MFMAs minus the carried ones (pure MFMA: covers
+  //   the DMA latency with the co-resident workgroup's burst) | vmcnt(0), barrier
+  // (The DMA in the SECOND quarter, where it was before the rotation, measured 0.17 % slower on the step: the
+  //  carried MFMAs take 1024 cycles out of the cover between DMA issue and vmcnt(0).)
+  // (sched_group_barrier: 0x8 MFMA, 0x100 DS read, 0x20 VMEM read).  Every accumulator still receives the
+  // same MFMAs in the same order — k-steps in order, a0 s = 0..SL-1, then a1 — so results are bit-identical to
+  // the unrotated loop.  The carried MFMAs read a1/b1 and the reads they cover write a0/b0: no second
+  // fragment set.  Every LDS read of a stage has returned before the MFMA that uses it, hence before the barrier
+  // that precedes the DMA overwriting that stage.  The first step is peeled (nothing carried in), the carried
+  // MFMAs of the last one are drained after the loop; with KSUB > 1 the carry is the tail of the last
+  // sub-step.  BUF is a template argument (the loop below is unrolled by two): every LDS offset is an
+  // immediate, no address arithmetic in front of the reads.  The DMA is unconditional (clamped to the last
+  // step, landing in the buffer nobody reads again) so that the body stays one basic block.
+  constexpr int HALF = SL * MT * NT;  // MFMAs per half step
+  constexpr int G_RD = HALF / (2 * (MT + NT));  // MFMAs per second-half read + DMA
+  constexpr int REST = 2 * HALF - (MT + NT) * G_RD;  // MFMAs of a sub-step behind its interleaved quarter
+  const int KT = K / (BK * KSUB);
+  auto kstep = [&](auto carry_c, auto buf_c, int kt) __attribute__((always_inline)) {
+    constexpr bool CARRY = decltype(carry_c)::value;
+    constexpr int BUF = decltype(buf_c)::value;
+    const int kn = kt + 1 < KT ? kt + 1 : kt;
+#pragma unroll
+    for (int u = 0; u < KSUB; ++u) {
+      const T* Ab = As + BUF * S::A_STAGE + u * BM * BK;
+      const T* Bb = Bs + BUF * S::B_STAGE + u * BN * BK;
+      const bool carry_in = CARRY && u == 0, carry_out = u == KSUB - 1;
 #pragma unroll
       for (int m = 0; m < MT; ++m) a0[m] = *reinterpret_cast<const slot_t*>(Ab + a_off0 + m * 16 * BK);
 #pragma unroll
       for (int n = 0; n < NT; ++n) b0[n] = *reinterpret_cast<const slot_t*>(Bb + b_off0 + n * 16 * BK);
+      if (carry_in) carried();
+      // Base and lane offset are made opaque per step so that their sum is formed HERE, where the instruction
+      // selector can fold it into the scalar-base + 32-bit-VGPR-offset form of the load: otherwise hipcc hoists
+      // the sums out of the loop as 64-bit VGPR pairs and advances each with a 64-bit VALU add per DMA.  (The
+      // offsets pass THROUGH the empty asm, loop-carried, so no register copy is made for them either.)
+      const int64_t kb = ((int64_t)kn * (BK * KSUB) + u * BK) * (int64_t)sizeof(T);
+      const char* pa = gA + kb;
+      const char* pb = gB + kb;
+      asm("" : "+s"(pa), "+s"(pb));
+      auto read2 = [&](int i) __attribute__((always_inline)) {  // second-half fragment i
+        if (i < MT)
+          a1[i] = *reinterpret_cast<const slot_t*>(Ab + a_off1 + i * 16 * BK);
+        else
+          b1[i - MT] = *reinterpret_cast<const slot_t*>(Bb + b_off1 + (i - MT) * 16 * BK);
+      };
+      auto dma1 = [&](int i) __attribute__((always_inline)) {  // DMA i of the next step
+        if (i < IA) {
+          asm("" : "+v"(oa[i]) : "s"(pa));
+          GPX_GLDS16(pa + oa[i], la + (BUF ^ 1) * S::A_STAGE + u * BM * BK + i * RQ);
+        } else {
+          const int q = i - IA;
+          asm("" : "+v"(ob[q]) : "s"(pb));
+          GPX_GLDS16(pb + ob[q], lb + (BUF ^ 1) * S::B_STAGE + u * BN * BK + q * RQ);
+        }
+      };
+      // in program order too: a DMA writes LDS, so the scheduler never moves it above an earlier LDS read
+      static_assert(MT + NT == IA + IB, "one DMA per second-half fragment read");
 #pragma unroll
-      for (int m = 0; m < MT; ++m) a1[m] = *reinterpret_cast<const slot_t*>(Ab + a_off1 + m * 16 * BK);
-#pragma unroll
-      for (int n = 0; n < NT; ++n) b1[n] = *reinterpret_cast<const slot_t*>(Bb + b_off1 + n * 16 * BK);
-      {
-#pragma unroll
-        for (int q = 0; q < IA; ++q)
-          GPX_GLDS16(ga[q] + ko + u * BK, la + (buf ^ 1) * S::A_STAGE + u * BM * BK + q * RQ);
-#pragma unroll
-        for (int q = 0; q < IB; ++q)
-          GPX_GLDS16(gb[q] + ko + u * BK, lb + (buf ^ 1) * S::B_STAGE + u * BN * BK + q * RQ);
+      for (int i = 0; i < MT + NT; ++i) {
+        read2(i);
+        dma1(i);
       }
 #pragma unroll
       for (int s = 0; s < SL; ++s)
@@ -168,32 +228,44 @@ __device__ __forceinline__ void gemm_tile_g(const T* A, int64_t lda, const T* B,
 #pragma unroll
           for (int n = 0; n < NT; ++n) acc[m][n] = Num<T>::mfma(a0[m][s], b0[n][s], acc[m][n]);
 #pragma unroll
-      for (int s = 0; s < SL; ++s)
+      for (int s = 0; s < (carry_out ? SL - 1 : SL); ++s)
 #pragma unroll
         for (int m = 0; m < MT; ++m)
 #pragma unroll
           for (int n = 0; n < NT; ++n) acc[m][n] = Num<T>::mfma(a1[m][s], b1[n][s], acc[m][n]);
-      __builtin_amdgcn_sched_group_barrier(0x100, MT + NT, 0);  // first-half fragments first
-      // first quarter of the burst: one second-half fragment read per 2 MFMAs; second
-      // quarter: the DMA of step t+1, one per 2 MFMAs; the second half is pure MFMA (covers
-      // the DMA latency together with the co-resident workgroup's burst)
+      __builtin_amdgcn_sched_group_barrier(0x100, MT + NT, 0);               // first-half fragments first
+      if (carry_in) __builtin_amdgcn_sched_group_barrier(0x8, MT * NT, 0);  // the carried MFMAs cover them
 #pragma unroll
       for (int i = 0; i < MT + NT; ++i) {
-        __builtin_amdgcn_sched_group_barrier(0x8, HALF / (2 * (MT + NT)), 0);
+        __builtin_amdgcn_sched_group_barrier(0x8, G_RD, 0);
         __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-      }
-#pragma unroll
-      for (int i = 0; i < IA + IB; ++i) {
-        __builtin_amdgcn_sched_group_barrier(0x8, HALF / (2 * (IA + IB)), 0);
         __builtin_amdgcn_sched_group_barrier(0x20, 1, 0);
       }
-      if (KSUB > 1) __builtin_amdgcn_sched_group_barrier(0x8, HALF, 0);  // the rest of this sub-step's MFMAs stay here
+      // the rest of this sub-step's MFMAs stay in it
+      if (KSUB > 1) {
+        if (carry_out)
+          __builtin_amdgcn_sched_group_barrier(0x8, REST - MT * NT, 0);
+        else
+          __builtin_amdgcn_sched_group_barrier(0x8, REST, 0);
+      }
     }
     // keep the MFMAs ABOVE the barrier: hipcc otherwise sinks them below the vmcnt(0)
     // drain of __syncthreads() and the DMA latency is exposed on every k-step
     __builtin_amdgcn_sched_barrier(0);
     __syncthreads();
+  };
+  using std::integral_constant;
+  dma(0, 0);
+  __syncthreads();
+  if (KT < 1) return;  // (no caller asks for it)
+  kstep(integral_constant<bool, false>{}, integral_constant<int, 0>{}, 0);
+  int kt = 1;
+  for (; kt + 1 < KT; kt += 2) {
+    kstep(integral_constant<bool, true>{}, integral_constant<int, 1>{}, kt);
+    kstep(integral_constant<bool, true>{}, integral_constant<int, 0>{}, kt + 1);
   }
+  if (kt < KT) kstep(integral_constant<bool, true>{}, integral_constant<int, 1>{}, kt);
+  carried();
 }
 
 template <typename V4, int MT, int NT>
