@@ -2218,9 +2218,11 @@ int trtri_enqueue(gpx_handle* h, double* ZT, const double* L, int64_t ld, int64_
 // non-zero part (block b: rows x columns >= b nb, packed), the fused K^-1 trace pass with the
 // tile groups dealt over the ranks, one all-reduce of ntheta sums.  alpha and its quadratic
 // form are replicated work (O(N^2)), identical on every rank.
-int lml_grad_impl(gpx_handle* h, double* lml, double* grad) {
+// kinds (gpx_lml_grad_full on a fit with derivative observations; one device): the KINDS instantiations of both passes,
+// theta = (lengthscales..., sf2, sn2, sn2_deriv).
+int lml_grad_impl(gpx_handle* h, double* lml, double* grad, bool kinds = false) {
   const int64_t N = h->N, Npad = h->Npad, ld = h->ld;
-  const int d = h->d, k = h->k, ntheta = h->n_ls + 2, ard = h->n_ls > 1;
+  const int d = h->d, k = h->k, ntheta = h->n_ls + (kinds ? 3 : 2), ard = h->n_ls > 1;
   Comm* cm = h->comm;
   const int P = cm ? cm->world : 1, rank = cm ? cm->rank : 0;
   // the gradient's sweeps keep their measured 1024-blocks whatever the fit's panel width (GPX_NB_GRAD overrides: A/B)
@@ -2276,20 +2278,31 @@ int lml_grad_impl(gpx_handle* h, double* lml, double* grad) {
     {
       PhaseScope ps(h, &tm.grad_trace);
       HIPCHK(h, hipMemsetAsync(part1, 0, (size_t)(s1n + s2n) * ntheta * 8, st));  // ragged-edge / other ranks' slots write nothing
-      launch_kinv_trace(h->cfg.kernel, ZT, ld, Npad, N, (const double*)h->Xs.p, d, ard, h->sf2, h->sn2, part1,
-                        ntheta, P, rank, st, wv);
+      if (kinds)
+        launch_kinv_trace_kinds(h->cfg.kernel, ZT, ld, Npad, N, (const double*)h->Xs.p, d, ard, h->sf2, h->sn2,
+                                h->sn2_deriv, (const int32_t*)h->Kfit.p, (const double*)h->ls.p, h->n_ls, part1, ntheta,
+                                st, wv);
+      else
+        launch_kinv_trace(h->cfg.kernel, ZT, ld, Npad, N, (const double*)h->Xs.p, d, ard, h->sf2, h->sn2, part1,
+                          ntheta, P, rank, st, wv);
     }
-    launch_alpha_quad(h->cfg.kernel, (const double*)h->alphaT, ld, k, Npad, N, (const double*)h->Xs.p, d, ard,
-                      h->sf2, h->sn2, part2, ntheta, st, wv);
+    if (kinds)
+      launch_alpha_quad_kinds(h->cfg.kernel, (const double*)h->alphaT, ld, k, Npad, N, (const double*)h->Xs.p, d, ard,
+                              h->sf2, h->sn2, h->sn2_deriv, (const int32_t*)h->Kfit.p, (const double*)h->ls.p, h->n_ls,
+                              part2, ntheta, st, wv);
+    else
+      launch_alpha_quad(h->cfg.kernel, (const double*)h->alphaT, ld, k, Npad, N, (const double*)h->Xs.p, d, ard,
+                        h->sf2, h->sn2, part2, ntheta, st, wv);
     launch_reduce_partials(part1, s1n, ntheta, 1.0, outv, st);
     launch_reduce_partials(part2, s2n, ntheta, 1.0, outv + ntheta, st);
     launch_dot_rhs((const double*)h->Y.p, (const double*)h->alphaT, ld, N, k, outv + 2 * ntheta, st);
     if (P > 1 && (rc = cm->allreduce(h, outv, (size_t)ntheta, COMM_SUM))) return rc;
   }
-  double host[2 * (MAX_D + 2) + 1];
+  double host[2 * (MAX_D + 3) + 1];
   HIPCHK(h, hipMemcpyAsync(host, outv, (size_t)(2 * ntheta + 1) * 8, hipMemcpyDeviceToHost, st));
   if ((rc = finish_call(h))) return rc;
   for (int t = 0; t < ntheta; ++t) grad[t] = 0.5 * (host[ntheta + t] - (double)k * host[t]);
+  if (kinds && h->sn2_deriv == 0.0) grad[ntheta - 1] = 0.0;  // (exactly: not -0, and no 0 x inf)
   *lml = -0.5 * host[2 * ntheta] - 0.5 * (double)k * h->logdet -
          0.5 * (double)N * (double)k * 1.8378770664093454835606594728112;  // log(2 pi)
   return GPX_OK;
@@ -3072,15 +3085,30 @@ int gpx_lml_grad(gpx_handle* h, double* lml, double* grad) try {
   if (!h) return GPX_E_ARG;
   if (!h->fitted || !lml || !grad) return fail(h, GPX_E_ARG, "gpx_lml_grad: no fit or null output");
   if (h->cfg.dtype != GPX_F64) return fail(h, GPX_E_UNSUPPORTED, "gpx_lml_grad: fp64 handles only");
-  if (h->has_deriv)  // (dK / dlog l of the derivative blocks is not implemented)
-    return fail(h, GPX_E_UNSUPPORTED, "gpx_lml_grad: the fit has derivative observations (gpx_set_observation_kinds): no "
-                                      "analytic gradient, use differences of the log marginal likelihood");
+  if (h->has_deriv)  // (n_ls + 2 entries have no room for d / dlog sn2_deriv)
+    return fail(h, GPX_E_UNSUPPORTED, "gpx_lml_grad: the fit has derivative observations (gpx_set_observation_kinds): "
+                                      "call gpx_lml_grad_full, whose gradient has the n_ls + 3 entries of such a fit");
   if (h->group) return group_lml_grad(h, lml, grad);
   if (h->cfg.world > 1 && !h->comm) return fail(h, GPX_E_ARG, "gpx_lml_grad: sharded handle without a communicator");
   int rc;
   if ((rc = begin_call(h))) return rc;
   if (h->comm && !h->repl) return shard_lml_grad_dist(h, lml, grad);  // factor only held distributed
   return lml_grad_impl(h, lml, grad);
+}
+GPX_CATCH_ALL
+
+int gpx_lml_grad_full(gpx_handle* h, double* lml, double* grad) try {
+  if (!h) return GPX_E_ARG;
+  if (!h->fitted || !lml || !grad) return fail(h, GPX_E_ARG, "gpx_lml_grad_full: no fit or null output");
+  if (h->cfg.dtype != GPX_F64) return fail(h, GPX_E_UNSUPPORTED, "gpx_lml_grad_full: fp64 handles only");
+  if (h->group || h->comm || h->cfg.world > 1)
+    return fail(h, GPX_E_UNSUPPORTED, "gpx_lml_grad_full: single-device handles only (gpx_lml_grad on shards and groups)");
+  int rc;
+  if ((rc = begin_call(h))) return rc;
+  if (h->has_deriv) return lml_grad_impl(h, lml, grad, true);
+  if ((rc = lml_grad_impl(h, lml, grad))) return rc;  // no derivative row: gpx_lml_grad's numbers
+  grad[h->n_ls + 2] = 0.0;
+  return GPX_OK;
 }
 GPX_CATCH_ALL
 
@@ -3237,6 +3265,65 @@ int gpx_kernel_deriv_matrix(int32_t kernel, const double* A, int64_t na, const d
       memcpy(G + ((int64_t)j * na + i) * nb_, host.data() + ((int64_t)j * napad + i) * ld, (size_t)nb_ * 8);
 done:
   for (double* p : {dA, dB, dAs, dBs, dls, dG})
+    if (p) (void)hipFree(p);
+  return rc;
+}
+GPX_CATCH_ALL
+
+int gpx_kernel_dl_matrix(int32_t kernel, const double* A, const int32_t* ka, int64_t na, const double* B,
+                         const int32_t* kb, int64_t nb_, int32_t d, const double* lengthscale, int32_t n_ls, double sf2,
+                         double* G) try {
+  if (!A || !B || !G || !lengthscale || na <= 0 || nb_ <= 0 || d <= 0 || d > MAX_D || (n_ls != 1 && n_ls != d))
+    return GPX_E_ARG;
+  if (!cov::known(kernel)) return GPX_E_ARG;
+  bool deriv = false;
+  for (int64_t i = 0; ka && i < na; ++i) {
+    if (ka[i] < -1 || ka[i] >= d) return GPX_E_ARG;
+    deriv |= ka[i] >= 0;
+  }
+  for (int64_t j = 0; kb && j < nb_; ++j) {
+    if (kb[j] < -1 || kb[j] >= d) return GPX_E_ARG;
+    deriv |= kb[j] >= 0;
+  }
+  if (deriv && !cov::differentiable(kernel))
+    return fail(nullptr, GPX_E_UNSUPPORTED, "gpx_kernel_dl_matrix: " MATERN12_NO_GRAD);
+  Scratch sc;
+  if (!sc.ok) return GPX_E_HIP;
+  hipStream_t st = sc.h.st;
+  const int64_t napad = round_up(na, 64), nbpad = round_up(nb_, 64), ld = nbpad;
+  double *dA = nullptr, *dB = nullptr, *dAs = nullptr, *dBs = nullptr, *dls = nullptr, *dG = nullptr;
+  int32_t *dka = nullptr, *dkb = nullptr;
+  std::vector<double> host((size_t)n_ls * napad * ld);
+  int rc = GPX_OK;
+  TCHK(hipMalloc(&dA, (size_t)na * d * 8));
+  TCHK(hipMalloc(&dB, (size_t)nb_ * d * 8));
+  TCHK(hipMalloc(&dAs, (size_t)napad * d * 8));
+  TCHK(hipMalloc(&dBs, (size_t)nbpad * d * 8));
+  TCHK(hipMalloc(&dls, MAX_D * 8));
+  TCHK(hipMalloc(&dG, (size_t)n_ls * napad * ld * 8));
+  TCHK(hipMemcpyAsync(dA, A, (size_t)na * d * 8, hipMemcpyHostToDevice, st));
+  TCHK(hipMemcpyAsync(dB, B, (size_t)nb_ * d * 8, hipMemcpyHostToDevice, st));
+  TCHK(hipMemcpyAsync(dls, lengthscale, (size_t)n_ls * 8, hipMemcpyHostToDevice, st));
+  if (ka) {
+    TCHK(hipMalloc(&dka, (size_t)na * sizeof(int32_t)));
+    TCHK(hipMemcpyAsync(dka, ka, (size_t)na * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  }
+  if (kb) {
+    TCHK(hipMalloc(&dkb, (size_t)nb_ * sizeof(int32_t)));
+    TCHK(hipMemcpyAsync(dkb, kb, (size_t)nb_ * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  }
+  TCHK(hipMemsetAsync(dG, 0, (size_t)n_ls * napad * ld * 8, st));
+  launch_scale_points(dA, na, napad, d, dls, n_ls, dAs, st);
+  launch_scale_points(dB, nb_, nbpad, d, dls, n_ls, dBs, st);
+  launch_dl_matrix(kernel, dAs, dka, na, napad, dBs, dkb, nb_, d, dls, n_ls, sf2, dG, ld, st);
+  TCHK(hipMemcpyAsync(host.data(), dG, (size_t)n_ls * napad * ld * 8, hipMemcpyDeviceToHost, st));
+  TCHK(hipStreamSynchronize(st));
+  TCHK(hipGetLastError());
+  for (int32_t c = 0; c < n_ls; ++c)
+    for (int64_t i = 0; i < na; ++i)
+      memcpy(G + ((int64_t)c * na + i) * nb_, host.data() + ((int64_t)c * napad + i) * ld, (size_t)nb_ * 8);
+done:
+  for (void* p : {(void*)dA, (void*)dB, (void*)dAs, (void*)dBs, (void*)dls, (void*)dG, (void*)dka, (void*)dkb})
     if (p) (void)hipFree(p);
   return rc;
 }

@@ -20,7 +20,18 @@
 //   (-1, -1)  v                 ( i, -1)  -g u_i / l_i
 //   (-1,  j)  +g u_j / l_j      ( i,  j)  (g delta_ij - h u_i u_j) / (l_i l_j)      at r = 0: (j, j) = grad_prior sf2 / l_j^2
 //
-// Every kernel evaluates these in this one operation order (value / value_g / value_gh / value_kd): for one element type and
+// Derivative of an element E of kinds (ka, kb) by a log lengthscale (element_dl; the LML gradient of a fit with derivative
+// observations): d E / d log l_c = A u_c^2 + (delta(ka, c) + delta(kb, c)) B, with p = -2 d h / d (r^2):
+//        RBF         v
+//        Matern-5/2  sf2 (125/3) e / s, taken as 0 at r = 0          (p only ever multiplies u_i u_j u_c^2 -> 0)
+//        Matern-3/2  27 sf2 e (1 + s) / s^3, taken as 0 at r = 0
+//   (-1, -1)  A = g                B = 0
+//   (-1,  j)  A = +h u_j / l_j     B = -2 g u_j / l_j
+//   ( i, -1)  A = -h u_i / l_i     B = +2 g u_i / l_i
+//   ( i,  j)  A = (h delta_ij - p u_i u_j) / (l_i l_j)      B = (2 h u_i u_j - g delta_ij) / (l_i l_j)
+// One lengthscale for all dimensions sums over c: A r^2 + ((ka >= 0) + (kb >= 0)) B.
+//
+// Every kernel evaluates these in this one operation order (value / value_g / value_gh / value_ghp / value_kd): for one element type and
 // exponential, the value rows of the derivative build and the kf of the LML gradient are bit for bit the kernel build's
 // K.  Matern-1/2 has no derivative at r = 0: it has no g, and no derivative kernel is instantiated for it.
 #pragma once
@@ -109,6 +120,45 @@ __host__ __device__ __forceinline__ T element(int ka, int kb, T v, T g, T h, T u
   if (ka < 0) return kb < 0 ? v : g * ub * ilb;
   if (kb < 0) return -g * ua * ila;
   return ((ka == kb ? g : (T)0) - h * (ua * ub)) * (ila * ilb);
+}
+
+// v, g and h as value_gh forms them (the same bits), and p
+template <int KERNEL, typename T, typename E = Exp>
+__device__ __forceinline__ void value_ghp(T r2, T sf2, T& v, T& g, T& h, T& p, E ex = {}) {
+  static_assert(differentiable(KERNEL), "Matern-1/2 is not differentiable");
+  const T s = svar<KERNEL>(r2);
+  const T e = ex(earg<KERNEL>(r2, s));
+  v = sf2 * (poly<KERNEL>(s) * e);
+  g = sf2 * (dpoly<KERNEL>(s) * e);
+  if constexpr (KERNEL == GPX_KERNEL_MATERN52) {
+    h = sf2 * ((T)(25.0 / 3.0) * e);
+    p = s > (T)0 ? sf2 * ((T)(125.0 / 3.0) * e) / s : (T)0;
+  } else if constexpr (KERNEL == GPX_KERNEL_MATERN32) {
+    h = s > (T)0 ? sf2 * ((T)9 * e) / s : (T)0;
+    p = s > (T)0 ? sf2 * ((T)27 * e * ((T)1 + s)) / (s * s * s) : (T)0;
+  } else {
+    h = v;
+    p = v;
+  }
+}
+
+// d element / d log l_c = A u_c^2 + (delta(ka, c) + delta(kb, c)) B (the table above), arguments as element's.  The same
+// discipline: products of the two sides side by side, so that swapping a and b (u -> -u) gives the same bits.
+template <typename T>
+__host__ __device__ __forceinline__ void element_dl(int ka, int kb, T g, T h, T p, T ua, T ub, T ila, T ilb, T& A, T& B) {
+  if (ka < 0) {
+    if (kb < 0) {
+      A = g, B = (T)0;
+    } else {
+      A = h * ub * ilb, B = (T)-2 * g * ub * ilb;
+    }
+  } else if (kb < 0) {
+    A = -h * ua * ila, B = (T)2 * g * ua * ila;
+  } else {
+    const T uu = ua * ub, ll = ila * ilb;
+    A = ((ka == kb ? h : (T)0) - p * uu) * ll;
+    B = ((T)2 * h * uu - (ka == kb ? g : (T)0)) * ll;
+  }
 }
 
 template <int KERNEL, typename T, typename E = Exp>

@@ -17,6 +17,12 @@
 // (as the kernel build does), multiplied in, reduced over the workgroup and written as one
 // partial sum per (tile, theta).  The alpha alpha^T term is a separate O(N^2 k) pass of the
 // same epilogue over 64x64 tiles.  Partials are summed in a fixed order: deterministic.
+//
+// Fits with derivative observations (KINDS instantiations of both kernels; gpx_lml_grad_full): an element of K of kinds
+// (ka, kb) is cov::element and its d / dlog l_c is A u_c^2 + (delta(ka, c) + delta(kb, c)) B (cov::element_dl, the table in
+// gpx_cov.h).  W A stays in the accumulators for the per-dimension pass exactly as W kd does; W B is summed per row (the
+// rows of kind >= 0) and per column of the thread's elements and goes to the dimension that row's / column's kind names.
+// theta = (lengthscales..., sf2, sn2, sn2_deriv): the diagonal sum is split by the row's kind.
 #include "gpx_cov.h"
 #include "gpx_internal.h"
 #include "gpx_tile.h"
@@ -42,14 +48,19 @@ __device__ __forceinline__ double wg_sum(double v, double* red) {
 // WEIGHTED: per-observation noise, dK/dlog sn2 = sn2 diag(wv) — the noise entry sums wv[i] K^-1_ii.  An instantiation of
 // its own: the epilogue sits at the edge of the register file (see the scheduling barrier below), and one more load in it
 // changes what the unweighted kernel spills.
-template <int KERNEL, int D, bool WEIGHTED>
+// KINDS: the fit has derivative observations — kind (readable up to npad, -1 there), ls (n_ls) and sn2_deriv are read, wv
+// may be null (WEIGHTED is not used), ntheta = n_ls + 3.  Instantiations of their own for the same reason.
+template <int KERNEL, int D, bool WEIGHTED, bool KINDS = false>
 __global__ __launch_bounds__(256, 2) void kinv_trace_kernel(const double* __restrict__ ZT, int64_t ld,
                                                             int tiles, int64_t npad, int64_t n,
                                                             const double* __restrict__ Xs, int d_rt, int ard,
                                                             double sf2, double sn2, double* __restrict__ part,
                                                             int ntheta, int64_t nslots, int P, int rank,
                                                             int dc_nb, int dc_P, int dc_r, int64_t dc_cols, int dc_snake,
-                                                            const double* __restrict__ wv) {
+                                                            const double* __restrict__ wv,
+                                                            const int32_t* __restrict__ kind = nullptr,
+                                                            const double* __restrict__ ls = nullptr, int n_ls = 0,
+                                                            double sn2_deriv = 0.0) {
   constexpr int BT = 128;
   __shared__ __attribute__((aligned(16))) double smem[TileShapeG<double, BT, BT>::SMEM_ELEMS];
   __shared__ double red[4];
@@ -93,10 +104,22 @@ __global__ __launch_bounds__(256, 2) void kinv_trace_kernel(const double* __rest
     xa[e] = Xs[(int64_t)ti * BT * d + e];
     xb[e] = Xs[(int64_t)tj * BT * d + e];
   }
+  const int* ska = nullptr;
+  const int* skb = nullptr;
+  const double* sil = nullptr;
+  if constexpr (KINDS) {  // the tile's row and column kinds and 1 / l, beside the points
+    __shared__ int kab[2 * BT];
+    __shared__ double ilv[MAX_D];
+    kab[tid] = kind[(tid < BT ? (int64_t)ti * BT : (int64_t)tj * BT - BT) + tid];
+    if (tid < d) ilv[tid] = 1.0 / ls[n_ls == 1 ? 0 : tid];
+    ska = kab, skb = kab + BT, sil = ilv;
+  }
   __syncthreads();
   const int lane = tid & 63, wave = tid >> 6;
   const int wr = wave >> 1, wc = wave & 1, l15 = lane & 15, l4 = lane >> 4;
   double Sf = 0.0, Sn = 0.0, Sl = 0.0;
+  // KINDS: the diagonal sum of the derivative rows, and W B summed over the thread's elements of a row / of a column
+  [[maybe_unused]] double Sd = 0.0, RB[4][4] = {}, CB[4] = {};
 #pragma unroll
   for (int m = 0; m < 4; ++m)
 #pragma unroll
@@ -122,17 +145,39 @@ __global__ __launch_bounds__(256, 2) void kinv_trace_kernel(const double* __rest
         }
         double v = acc[m][nn][r];
         if (gi >= n || gj >= n) v = 0.0;  // padded rows / columns are not part of K
-        double kf, kd;
-        cov::value_kd<KERNEL>(r2, sf2, kf, kd);
-        Sf += v * kf;
-        if (WEIGHTED) {
-          if (gi == gj && gi < n) Sn += v * wv[gi];
+        if constexpr (KINDS) {
+          if constexpr (cov::differentiable(KERNEL)) {
+            double kf, g, h, p, A, B;
+            cov::value_ghp<KERNEL>(r2, sf2, kf, g, h, p);
+            const int ka = ska[il], kb = skb[jl];
+            const int ca = ka < 0 ? 0 : ka, cb = kb < 0 ? 0 : kb;  // (kinds < d: the fit checked)
+            const double ua = xa[il * d + ca] - xb[jl * d + ca], ub = xa[il * d + cb] - xb[jl * d + cb];
+            Sf += v * cov::element<double>(ka, kb, kf, g, h, ua, ub, sil[ca], sil[cb]);
+            if (gi == gj && gi < n) {
+              const double vw = wv ? v * wv[gi] : v;
+              if (ka < 0) Sn += vw;
+              else Sd += vw;
+            }
+            cov::element_dl<double>(ka, kb, g, h, p, ua, ub, sil[ca], sil[cb], A, B);
+            const double t = v * A, tb = v * B;
+            Sl += t * r2;
+            if (ka >= 0) RB[m][r] += tb;
+            if (kb >= 0) CB[nn] += tb;
+            acc[m][nn][r] = t;  // kept for the per-dimension pass (ARD)
+          }
         } else {
-          if (gi == gj) Sn += v;
+          double kf, kd;
+          cov::value_kd<KERNEL>(r2, sf2, kf, kd);
+          Sf += v * kf;
+          if (WEIGHTED) {
+            if (gi == gj && gi < n) Sn += v * wv[gi];
+          } else {
+            if (gi == gj) Sn += v;
+          }
+          const double t = v * kd;
+          Sl += t * r2;
+          acc[m][nn][r] = t;  // kept for the per-dimension pass (ARD)
         }
-        const double t = v * kd;
-        Sl += t * r2;
-        acc[m][nn][r] = t;  // kept for the per-dimension pass (ARD)
         // one element at a time: left alone, the scheduler interleaves all 64 evaluations of
         // this fully unrolled nest (the accumulators must stay in registers) and spills hundreds
         // of VGPRs; the epilogue is < 1 % of the tile's time either way
@@ -141,8 +186,16 @@ __global__ __launch_bounds__(256, 2) void kinv_trace_kernel(const double* __rest
     }
   const double w = (ti == tj) ? 1.0 : 2.0;
   double* out = part + lin * ntheta;
-  const int nls = ntheta - 2;
+  const int nls = ntheta - (KINDS ? 3 : 2);
   if (!ard) {
+    if constexpr (KINDS) {  // one lengthscale: every dimension a kind names is that one
+#pragma unroll
+      for (int m = 0; m < 4; ++m)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) Sl += RB[m][r];
+#pragma unroll
+      for (int nn = 0; nn < 4; ++nn) Sl += CB[nn];
+    }
     const double s = wg_sum(Sl, red);
     if (tid == 0) out[0] = w * s;
   } else {
@@ -159,7 +212,15 @@ __global__ __launch_bounds__(256, 2) void kinv_trace_kernel(const double* __rest
             const double e = xa[il * d + c] - xb[jl * d + c];
             s += acc[m][nn][r] * e * e;
           }
+          if constexpr (KINDS) {
+            if (ska[il] == c) s += RB[m][r];
+          }
         }
+      if constexpr (KINDS) {
+#pragma unroll
+        for (int nn = 0; nn < 4; ++nn)
+          if (skb[wc * 64 + nn * 16 + l15] == c) s += CB[nn];
+      }
       s = wg_sum(s, red);
       if (tid == 0) out[c] = w * s;
     }
@@ -168,6 +229,10 @@ __global__ __launch_bounds__(256, 2) void kinv_trace_kernel(const double* __rest
   if (tid == 0) {
     out[nls] = w * sf;
     out[nls + 1] = sn * sn2;  // only diagonal tiles hold diagonal elements (w = 1 there)
+  }
+  if constexpr (KINDS) {
+    const double sd = wg_sum(Sd, red);
+    if (tid == 0) out[nls + 2] = sd * sn2_deriv;
   }
 }
 
@@ -182,12 +247,16 @@ __device__ __forceinline__ void tri_coords64(int64_t t, int& ti, int& tj) {
   tj = (int)(t - i * (i + 1) / 2);
 }
 
-template <int KERNEL, int D>
+// KINDS: as kinv_trace_kernel's.
+template <int KERNEL, int D, bool KINDS = false>
 __global__ __launch_bounds__(256) void alpha_quad_kernel(const double* __restrict__ alphaT, int64_t ld, int k,
                                                         int64_t n, const double* __restrict__ Xs, int d_rt,
                                                         int ard, double sf2, double sn2,
                                                         double* __restrict__ part, int ntheta,
-                                                        const double* __restrict__ wv) {
+                                                        const double* __restrict__ wv,
+                                                        const int32_t* __restrict__ kind = nullptr,
+                                                        const double* __restrict__ ls = nullptr, int n_ls = 0,
+                                                        double sn2_deriv = 0.0) {
   constexpr int KT = 64;
   __shared__ double xa[KT * MAX_D];
   __shared__ double xb[KT * MAX_D];
@@ -200,6 +269,16 @@ __global__ __launch_bounds__(256) void alpha_quad_kernel(const double* __restric
   for (int e = tid; e < KT * d; e += 256) {
     xa[e] = Xs[i0 * d + e];
     xb[e] = Xs[j0 * d + e];
+  }
+  const int* ska = nullptr;
+  const int* skb = nullptr;
+  const double* sil = nullptr;
+  if constexpr (KINDS) {
+    __shared__ int kab[2 * KT];
+    __shared__ double ilv[MAX_D];
+    if (tid < 2 * KT) kab[tid] = kind[(tid < KT ? i0 : j0 - KT) + tid];
+    else if (tid - 2 * KT < d) ilv[tid - 2 * KT] = 1.0 / ls[n_ls == 1 ? 0 : tid - 2 * KT];
+    ska = kab, skb = kab + KT, sil = ilv;
   }
   __syncthreads();
   const int jl0 = (tid & 31) * 2, rg = tid >> 5;
@@ -218,6 +297,7 @@ __global__ __launch_bounds__(256) void alpha_quad_kernel(const double* __restric
     }
   }
   double Sf = 0.0, Sn = 0.0, Sl = 0.0;
+  [[maybe_unused]] double Sd = 0.0, RB[8] = {}, CB[2] = {};
 #pragma unroll
   for (int r = 0; r < 8; ++r) {
     const int il = rg + 8 * r;
@@ -233,31 +313,67 @@ __global__ __launch_bounds__(256) void alpha_quad_kernel(const double* __restric
       }
       double v = wt[r][q];
       if (gi >= n || gj >= n) v = 0.0;
-      double kf, kd;
-      cov::value_kd<KERNEL>(r2, sf2, kf, kd);
-      Sf += v * kf;
-      if (gi == gj) Sn += (wv && gi < n) ? v * wv[gi] : v;
-      const double t = v * kd;
-      Sl += t * r2;
-      wt[r][q] = t;
+      if constexpr (KINDS) {
+        if constexpr (cov::differentiable(KERNEL)) {
+          double kf, g, h, p, A, B;
+          cov::value_ghp<KERNEL>(r2, sf2, kf, g, h, p);
+          const int ka = ska[il], kb = skb[jl];
+          const int ca = ka < 0 ? 0 : ka, cb = kb < 0 ? 0 : kb;
+          const double ua = xa[il * d + ca] - xb[jl * d + ca], ub = xa[il * d + cb] - xb[jl * d + cb];
+          Sf += v * cov::element<double>(ka, kb, kf, g, h, ua, ub, sil[ca], sil[cb]);
+          if (gi == gj && gi < n) {
+            const double vw = wv ? v * wv[gi] : v;
+            if (ka < 0) Sn += vw;
+            else Sd += vw;
+          }
+          cov::element_dl<double>(ka, kb, g, h, p, ua, ub, sil[ca], sil[cb], A, B);
+          const double t = v * A, tb = v * B;
+          Sl += t * r2;
+          if (ka >= 0) RB[r] += tb;
+          if (kb >= 0) CB[q] += tb;
+          wt[r][q] = t;
+        }
+      } else {
+        double kf, kd;
+        cov::value_kd<KERNEL>(r2, sf2, kf, kd);
+        Sf += v * kf;
+        if (gi == gj) Sn += (wv && gi < n) ? v * wv[gi] : v;
+        const double t = v * kd;
+        Sl += t * r2;
+        wt[r][q] = t;
+      }
     }
   }
   const double w = (ti == tj) ? 1.0 : 2.0;
   double* out = part + (int64_t)blockIdx.x * ntheta;
-  const int nls = ntheta - 2;
+  const int nls = ntheta - (KINDS ? 3 : 2);
   if (!ard) {
+    if constexpr (KINDS) {
+#pragma unroll
+      for (int r = 0; r < 8; ++r) Sl += RB[r];
+      Sl += CB[0];
+      Sl += CB[1];
+    }
     const double s = wg_sum(Sl, red);
     if (tid == 0) out[0] = w * s;
   } else {
     for (int c = 0; c < d; ++c) {
       double s = 0.0;
 #pragma unroll
-      for (int r = 0; r < 8; ++r)
+      for (int r = 0; r < 8; ++r) {
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
           const double e = xa[(rg + 8 * r) * d + c] - xb[(jl0 + q) * d + c];
           s += wt[r][q] * e * e;
         }
+        if constexpr (KINDS) {
+          if (ska[rg + 8 * r] == c) s += RB[r];
+        }
+      }
+      if constexpr (KINDS) {
+        if (skb[jl0] == c) s += CB[0];
+        if (skb[jl0 + 1] == c) s += CB[1];
+      }
       s = wg_sum(s, red);
       if (tid == 0) out[c] = w * s;
     }
@@ -266,6 +382,10 @@ __global__ __launch_bounds__(256) void alpha_quad_kernel(const double* __restric
   if (tid == 0) {
     out[nls] = w * sf;
     out[nls + 1] = sn * sn2;
+  }
+  if constexpr (KINDS) {
+    const double sd = wg_sum(Sd, red);
+    if (tid == 0) out[nls + 2] = sd * sn2_deriv;
   }
 }
 
@@ -299,16 +419,69 @@ __global__ __launch_bounds__(256) void set_diag_one_kernel(double* A, int64_t ld
   if (i < n) A[i * lda + i] = 1.0;
 }
 
+// ---- d K / d log l_c as a matrix (gpx_kernel_dl_matrix: the unit test of cov::element_dl) --------------------------------
+// G[c][i][j] (n_ls blocks of napad x ld) for observations of kinds ka (null: values) at As against kinds kb at Bs; scaled
+// points.  Matern-1/2 (values only: the API checks) has A = kd.
+template <int KERNEL>
+__global__ __launch_bounds__(256) void dl_matrix_kernel(const double* __restrict__ As, const int32_t* __restrict__ ka,
+                                                       int64_t na, int64_t napad, const double* __restrict__ Bs,
+                                                       const int32_t* __restrict__ kb, int64_t nb, int d,
+                                                       const double* __restrict__ ls, int n_ls, double sf2,
+                                                       double* __restrict__ G, int64_t ld) {
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= na * nb) return;
+  const int64_t i = e / nb, j = e - i * nb;
+  const double* pa = As + i * d;
+  const double* pb = Bs + j * d;
+  double r2 = 0.0;
+  for (int c = 0; c < d; ++c) {
+    const double u = pa[c] - pb[c];
+    r2 += u * u;
+  }
+  const int kia = ka ? ka[i] : -1, kib = kb ? kb[j] : -1;
+  double A, B = 0.0;
+  if constexpr (cov::differentiable(KERNEL)) {
+    double v, g, h, p;
+    cov::value_ghp<KERNEL>(r2, sf2, v, g, h, p);
+    const int ca = kia < 0 ? 0 : kia, cb = kib < 0 ? 0 : kib;
+    cov::element_dl<double>(kia, kib, g, h, p, pa[ca] - pb[ca], pa[cb] - pb[cb], 1.0 / ls[n_ls == 1 ? 0 : ca],
+                            1.0 / ls[n_ls == 1 ? 0 : cb], A, B);
+  } else {
+    double v;
+    cov::value_kd<KERNEL>(r2, sf2, v, A);
+  }
+  if (n_ls == 1) {
+    G[i * ld + j] = A * r2 + (double)((kia >= 0) + (kib >= 0)) * B;
+  } else {
+    for (int c = 0; c < d; ++c) {
+      const double u = pa[c] - pb[c];
+      G[((int64_t)c * napad + i) * ld + j] = A * (u * u) + (double)((kia == c) + (kib == c)) * B;
+    }
+  }
+}
+
 template <int KERNEL>
 void launch_kinv_trace_k(const double* ZT, int64_t ld, int64_t npad, int64_t n, const double* Xs, int d, int ard,
                          double sf2, double sn2, double* part, int ntheta, int P, int rank, int dc_nb, int dc_P,
-                         int dc_r, int64_t dc_cols, int dc_snake, const double* wv, hipStream_t st) {
+                         int dc_r, int64_t dc_cols, int dc_snake, const double* wv, hipStream_t st,
+                         const int32_t* kind = nullptr, const double* ls = nullptr, int n_ls = 0, double sn2_deriv = 0.0) {
   const int tiles = (int)(npad / 128);
   const int64_t ts = (tiles + 7) / 8;
   const int64_t nslots = ts * (ts - 1) / 2 * 64 + ts * 36;
   const int64_t octets = (nslots + 511) / 512, mine = octets > rank ? (octets - rank + P - 1) / P : 0;
   if (mine == 0) return;
   dim3 grid((unsigned)(mine * 512)), block(256);  // whole octets of 8 x 64 slots
+  if (kind) {
+    if constexpr (cov::differentiable(KERNEL)) {
+      switch (d) {
+        case 1: hipLaunchKernelGGL((kinv_trace_kernel<KERNEL, 1, false, true>), grid, block, 0, st, ZT, ld, tiles, npad, n, Xs, d, ard, sf2, sn2, part, ntheta, nslots, P, rank, dc_nb, dc_P, dc_r, dc_cols, dc_snake, wv, kind, ls, n_ls, sn2_deriv); break;
+        case 2: hipLaunchKernelGGL((kinv_trace_kernel<KERNEL, 2, false, true>), grid, block, 0, st, ZT, ld, tiles, npad, n, Xs, d, ard, sf2, sn2, part, ntheta, nslots, P, rank, dc_nb, dc_P, dc_r, dc_cols, dc_snake, wv, kind, ls, n_ls, sn2_deriv); break;
+        case 3: hipLaunchKernelGGL((kinv_trace_kernel<KERNEL, 3, false, true>), grid, block, 0, st, ZT, ld, tiles, npad, n, Xs, d, ard, sf2, sn2, part, ntheta, nslots, P, rank, dc_nb, dc_P, dc_r, dc_cols, dc_snake, wv, kind, ls, n_ls, sn2_deriv); break;
+        default: hipLaunchKernelGGL((kinv_trace_kernel<KERNEL, 0, false, true>), grid, block, 0, st, ZT, ld, tiles, npad, n, Xs, d, ard, sf2, sn2, part, ntheta, nslots, P, rank, dc_nb, dc_P, dc_r, dc_cols, dc_snake, wv, kind, ls, n_ls, sn2_deriv); break;
+      }
+    }
+    return;
+  }
   if (wv) {
     switch (d) {
       case 1: hipLaunchKernelGGL((kinv_trace_kernel<KERNEL, 1, true>), grid, block, 0, st, ZT, ld, tiles, npad, n, Xs, d, ard, sf2, sn2, part, ntheta, nslots, P, rank, dc_nb, dc_P, dc_r, dc_cols, dc_snake, wv); break;
@@ -328,9 +501,19 @@ void launch_kinv_trace_k(const double* ZT, int64_t ld, int64_t npad, int64_t n, 
 
 template <int KERNEL>
 void launch_alpha_quad_k(const double* alphaT, int64_t ld, int k, int64_t npad, int64_t n, const double* Xs, int d,
-                         int ard, double sf2, double sn2, double* part, int ntheta, const double* wv, hipStream_t st) {
+                         int ard, double sf2, double sn2, double* part, int ntheta, const double* wv, hipStream_t st,
+                         const int32_t* kind = nullptr, const double* ls = nullptr, int n_ls = 0, double sn2_deriv = 0.0) {
   const int64_t T = npad / 64;
   dim3 grid((unsigned)(T * (T + 1) / 2)), block(256);
+  if (kind) {
+    if constexpr (cov::differentiable(KERNEL)) {
+      if (d == 3)
+        hipLaunchKernelGGL((alpha_quad_kernel<KERNEL, 3, true>), grid, block, 0, st, alphaT, ld, k, n, Xs, d, ard, sf2, sn2, part, ntheta, wv, kind, ls, n_ls, sn2_deriv);
+      else
+        hipLaunchKernelGGL((alpha_quad_kernel<KERNEL, 0, true>), grid, block, 0, st, alphaT, ld, k, n, Xs, d, ard, sf2, sn2, part, ntheta, wv, kind, ls, n_ls, sn2_deriv);
+    }
+    return;
+  }
   if (d == 3)
     hipLaunchKernelGGL((alpha_quad_kernel<KERNEL, 3>), grid, block, 0, st, alphaT, ld, k, n, Xs, d, ard, sf2, sn2, part, ntheta, wv);
   else
@@ -357,6 +540,28 @@ void launch_kinv_trace(int kernel, const double* ZT, int64_t ld, int64_t npad, i
                        int ard, double sf2, double sn2, double* part, int ntheta, int P, int rank, hipStream_t st,
                        const double* wv) {
   cov::dispatch(kernel, [&](auto fam) { launch_kinv_trace_k<fam>(ZT, ld, npad, n, Xs, d, ard, sf2, sn2, part, ntheta, P, rank, 0, 0, 0, 0, 0, wv, st); });
+}
+
+void launch_kinv_trace_kinds(int kernel, const double* ZT, int64_t ld, int64_t npad, int64_t n, const double* Xs, int d,
+                             int ard, double sf2, double sn2, double sn2_deriv, const int32_t* kind, const double* ls,
+                             int n_ls, double* part, int ntheta, hipStream_t st, const double* wv) {
+  cov::dispatch_differentiable(kernel, [&](auto fam) { launch_kinv_trace_k<fam>(ZT, ld, npad, n, Xs, d, ard, sf2, sn2, part, ntheta, 1, 0, 0, 0, 0, 0, 0, wv, st, kind, ls, n_ls, sn2_deriv); });
+}
+
+void launch_alpha_quad_kinds(int kernel, const double* alphaT, int64_t ld, int k, int64_t npad, int64_t n,
+                             const double* Xs, int d, int ard, double sf2, double sn2, double sn2_deriv,
+                             const int32_t* kind, const double* ls, int n_ls, double* part, int ntheta, hipStream_t st,
+                             const double* wv) {
+  cov::dispatch_differentiable(kernel, [&](auto fam) { launch_alpha_quad_k<fam>(alphaT, ld, k, npad, n, Xs, d, ard, sf2, sn2, part, ntheta, wv, st, kind, ls, n_ls, sn2_deriv); });
+}
+
+void launch_dl_matrix(int kernel, const double* As, const int32_t* ka, int64_t na, int64_t napad, const double* Bs,
+                      const int32_t* kb, int64_t nb, int d, const double* ls, int n_ls, double sf2, double* G, int64_t ld,
+                      hipStream_t st) {
+  cov::dispatch(kernel, [&](auto fam) {
+    hipLaunchKernelGGL(dl_matrix_kernel<fam>, dim3((unsigned)((na * nb + 255) / 256)), dim3(256), 0, st, As, ka, na, napad, Bs,
+                       kb, nb, d, ls, n_ls, sf2, G, ld);
+  });
 }
 
 void launch_kinv_trace_cols(int kernel, const double* ZTc, int64_t ldc, int64_t npad, int64_t n, const double* Xs,

@@ -267,6 +267,20 @@ void launch_kinv_trace_cols(int kernel, const double* ZTc, int64_t ldc, int64_t 
 void launch_alpha_quad(int kernel, const double* alphaT, int64_t ld, int k, int64_t npad, int64_t n,
                        const double* Xs, int d, int ard, double sf2, double sn2, double* part, int ntheta,
                        hipStream_t st, const double* wv = nullptr);  // wv (n): the noise entry sums w_i sum_c alpha_ic^2
+// Both passes for a fit with derivative observations (differentiable families; kind readable up to npad, -1 there; ls
+// (n_ls) on the device): theta = (lengthscale[0..n_ls), sf2, sn2, sn2_deriv), ntheta = n_ls + 3; one device
+void launch_kinv_trace_kinds(int kernel, const double* ZT, int64_t ld, int64_t npad, int64_t n, const double* Xs, int d,
+                             int ard, double sf2, double sn2, double sn2_deriv, const int32_t* kind, const double* ls,
+                             int n_ls, double* part, int ntheta, hipStream_t st, const double* wv = nullptr);
+void launch_alpha_quad_kinds(int kernel, const double* alphaT, int64_t ld, int k, int64_t npad, int64_t n,
+                             const double* Xs, int d, int ard, double sf2, double sn2, double sn2_deriv,
+                             const int32_t* kind, const double* ls, int n_ls, double* part, int ntheta, hipStream_t st,
+                             const double* wv = nullptr);
+// G (n_ls blocks of napad x ld)[c][i][j] = d cov(obs of kind ka[i] at As_i, obs of kind kb[j] at Bs_j) / d log l_c, i < na,
+// j < nb (cov::element_dl); scaled points, ka / kb null: values; a kind >= 0 needs a differentiable family
+void launch_dl_matrix(int kernel, const double* As, const int32_t* ka, int64_t na, int64_t napad, const double* Bs,
+                      const int32_t* kb, int64_t nb, int d, const double* ls, int n_ls, double sf2, double* G, int64_t ld,
+                      hipStream_t st);
 void launch_reduce_partials(const double* part, int64_t ntile, int ntheta, double scale, double* out,
                             hipStream_t st);
 // out[0] = sum_i sum_c y[i*k + c] * alphaT[c*ld + i]

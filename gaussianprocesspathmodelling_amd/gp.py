@@ -129,6 +129,7 @@ class GP:
         self._fitted = False
         self._weights_set = False  # gpx_set_noise_weights holds a vector for the next fits
         self._kinds_set = False    # gpx_set_observation_kinds holds kinds for the next fits
+        self.derivative_noise = 0.0  # noise variance of the derivative rows of the last fit(derivatives=) (0 without any)
         self._alpha = None
         self.info_ = 0
         self.jitter_used_ = self.jitter
@@ -317,8 +318,9 @@ class GP:
         ``derivatives = (Xd, dims, yd)`` conditions the model on derivative observations as well
         (``gpx_set_observation_kinds``): ``yd[i]`` ((Nd,) or (Nd, k), as ``y``) is a value of d f / d x_dims[i] at
         ``Xd[i]`` — a velocity when that input is time; ``dims`` an int or (Nd,) ints; ``Xd`` and ``yd`` of the same
-        kind as ``X``.  Their noise variance is ``derivative_noise`` (>= 0, fixed; 0 with a waypoint ``w_i = 0`` at the
-        same point: "pass through here with this velocity").  The model then holds the N value rows followed by the Nd
+        kind as ``X``.  Their noise variance is ``derivative_noise`` (>= 0; the attribute of that name keeps it, and
+        :meth:`optimize` learns it on request; 0 with a waypoint ``w_i = 0`` at the same point: "pass through here with
+        this velocity").  The model then holds the N value rows followed by the Nd
         derivative rows (``alpha_``, ``observation_kinds_``, ``noise_weights_``); ``noise_weights`` may have length N
         (derivative rows get 1) or N + Nd.  RBF, Matern-5/2 and Matern-3/2 on one device, float64 / float32; None (the
         default) means none — also after such a fit."""
@@ -341,6 +343,7 @@ class GP:
             raise ValueError("lengthscale must be scalar or have d entries")
         self._set_noise_weights(noise_weights, N, kx)  # (refused: the model is as it was)
         self._set_observation_kinds(kinds, derivative_noise)
+        self.derivative_noise = 0.0 if kinds is None else float(derivative_noise)
         self._y1d = len(sy) == 1
         self._N, self._d, self._k = N, d, k
         self._alpha = None
@@ -751,7 +754,7 @@ class GP:
         return float(-0.5 * np.sum(Y * A) - 0.5 * k * self.log_det_
                      - 0.5 * n * k * np.log(2.0 * np.pi))
 
-    def lml_gradient(self):
+    def lml_gradient(self, derivative_noise=False):
         """``(lml, grad)`` of the last ``fit``: the log marginal likelihood and its analytic
         gradient w.r.t. the LOG hyper-parameters, ordered (lengthscale[0..n_ls), variance, noise)
         — R&W eq. 5.9, 1/2 tr((alpha alpha^T - K^-1) dK/dtheta) (with ``noise_weights``: dK/dlog noise =
@@ -762,12 +765,18 @@ class GP:
         all-gathered once, and the trace pass is split over the GPUs; when the factor is only held
         distributed (C4-sized problems) L^-T is built distributed, every GPU keeps the columns of its
         own row blocks and contracts the trace over them — either way every rank returns the same
-        numbers."""
+        numbers.
+
+        ``derivative_noise=True`` (``gpx_lml_grad_full``; one device, float64): one more entry at the end, the derivative
+        by log ``derivative_noise`` — 0 for a fit without derivative observations or with ``derivative_noise == 0``.
+        This is the call for a fit with ``derivatives=``, which the default call refuses (its gradient has no room for
+        that entry); on any other fit the leading entries and ``lml`` are the default call's bit for bit."""
         if not self._fitted:
             raise RuntimeError("lml_gradient() before a successful fit()")
         lml = C.c_double(0.0)
-        grad = np.empty(self.lengthscale.size + 2, dtype=np.float64)
-        self._check(self._lib.gpx_lml_grad(self._h, C.byref(lml), _abi.dptr(grad)))
+        grad = np.empty(self.lengthscale.size + (3 if derivative_noise else 2), dtype=np.float64)
+        call = self._lib.gpx_lml_grad_full if derivative_noise else self._lib.gpx_lml_grad
+        self._check(call(self._h, C.byref(lml), _abi.dptr(grad)))
         return float(lml.value), grad
 
     def optimize(self, X, y, params=("lengthscale", "variance", "noise"), bounds=(1e-4, 1e4), maxiter=40,
@@ -784,14 +793,28 @@ class GP:
         model fitted at the best point found and returns scipy's result (``.fun`` = minus the
         log marginal likelihood there).  ``noise_weights`` as for :meth:`fit`: every fit of the search, the final one
         included, is made with them; ``noise`` is then the level that is learnt.  ``derivatives`` and
-        ``derivative_noise`` as for :meth:`fit` as well: such a model has no analytic gradient, the search runs on
-        central differences of the log marginal likelihood; ``derivative_noise`` is fixed, not learnt."""
-        fit_kw = dict(noise_weights=noise_weights, derivatives=derivatives, derivative_noise=derivative_noise)
+        ``derivative_noise`` as for :meth:`fit` as well: the analytic gradient of such a model is
+        ``lml_gradient(derivative_noise=True)``, at the same cost.  ``params`` may then also name ``"derivative_noise"``:
+        the noise variance of the derivative observations is learnt with the others, starting from the value passed,
+        and the attribute ``derivative_noise`` holds the result (``ValueError`` without ``derivatives`` or when it starts
+        at 0: log-space cannot leave 0).  Left out of ``params`` it stays fixed."""
         from scipy.optimize import minimize
-        names = [p for p in ("lengthscale", "variance", "noise") if p in params]
+        names = [p for p in ("lengthscale", "variance", "noise", "derivative_noise") if p in params]
         if not names or len(names) != len(tuple(params)):
-            raise ValueError("params must be a non-empty subset of lengthscale / variance / noise")
+            raise ValueError("params must be a non-empty subset of lengthscale / variance / noise / derivative_noise")
+        if "derivative_noise" in names:
+            if derivatives is None:
+                raise ValueError("params names derivative_noise, but there are no derivatives")
+            if not float(derivative_noise) > 0:
+                raise ValueError("derivative_noise must start above 0 to be learnt (the search runs in log-space)")
         n_ls = self.lengthscale.size
+        full_grad = derivatives is not None   # a fit with derivative rows: the gradient with the derivative_noise entry
+        if full_grad:
+            self.derivative_noise = float(derivative_noise)   # where the search starts; unpack() moves it when it is learnt
+
+        def fit_kw():   # every fit of the search, the final one included, with the current derivative_noise
+            return dict(noise_weights=noise_weights, derivatives=derivatives,
+                        derivative_noise=self.derivative_noise if full_grad else derivative_noise)
 
         def pack():
             v = []
@@ -816,16 +839,17 @@ class GP:
             # sharded: the gradient needs the replicated-factor mode, which the library picks from N
             # and the card's memory at fit time — ask it once (every rank gets the same answer)
             try:
-                self.fit(X, y, **fit_kw)
+                self.fit(X, y, **fit_kw())
                 self.lml_gradient()
             except _abi.GpxError:
                 analytic = False
             except np.linalg.LinAlgError:
                 pass
-        # columns of the full gradient (lengthscale.., variance, noise) that move
+        # columns of the full gradient (lengthscale.., variance, noise, derivative_noise) that move
         cols = []
         for p in names:
-            cols.extend(range(n_ls) if p == "lengthscale" else [n_ls + (0 if p == "variance" else 1)])
+            cols.extend(range(n_ls) if p == "lengthscale" else
+                        [n_ls + ("variance", "noise", "derivative_noise").index(p)])
 
         class _NoAnalyticGradient(Exception):
             pass
@@ -834,10 +858,10 @@ class GP:
             unpack(v)
             g = np.zeros(len(cols))
             try:
-                self.fit(X, y, **fit_kw)
+                self.fit(X, y, **fit_kw())
                 if analytic:
                     try:
-                        lml, full = self.lml_gradient()
+                        lml, full = self.lml_gradient(derivative_noise=full_grad)
                     except _abi.GpxError as e:
                         # no gradient for this model after all (factor only held distributed, or no
                         # room for the N x N L^-T buffer): free what the attempt allocated and let the
@@ -870,6 +894,6 @@ class GP:
         except _NoAnalyticGradient:
             res = search(best["v"], False)   # from the best point the analytic steps reached
         unpack(best["v"])
-        self.fit(X, y, **fit_kw)
+        self.fit(X, y, **fit_kw())
         res.x, res.fun = best["v"], best["f"]
         return res

@@ -244,7 +244,8 @@ class PathModel:
     (``fit_path_models(step_noise=True)``); :meth:`add_paths` and :meth:`log_likelihood` then use them too.
     ``has_velocities``: the model was also conditioned on observed velocities (``fit_path_models(velocities=)``: derivative
     observations along ``"t"``); every prediction works unchanged, :meth:`add_paths` does not (``GP.update`` cannot append
-    to such a fit)."""
+    to such a fit).  ``velocity_noise``: the noise variance of those velocities in the model's normalised units, as given
+    or as learnt (``fit_path_models(learn_velocity_noise=True)``); None without velocities."""
 
     def __init__(self, gp, keys, in_lo, in_span, y_mean, y_std, inputs, targets, step_weights=None, has_velocities=False):
         self.gp, self.keys = gp, list(keys)
@@ -252,6 +253,10 @@ class PathModel:
         self.inputs, self.targets = tuple(inputs), tuple(targets)
         self.step_weights = None if step_weights is None else np.asarray(step_weights, dtype=np.float64)
         self.has_velocities = bool(has_velocities)
+
+    @property
+    def velocity_noise(self):
+        return float(self.gp.derivative_noise) if self.has_velocities else None
 
     def _tiled_weights(self, n_rows, what):
         """the step weights repeated for n_rows / L whole paths (None without step weights)"""
@@ -382,7 +387,7 @@ def step_noise_weights(Yn, n_paths):
 
 def fit_path_models(trajs, clusters, inputs=("t",), targets=("x", "y"), devices=None, optimize=False,
                     lengthscale=0.25, variance=1.0, noise=0.05, step_noise=False, velocities=None, velocity_noise=0.05,
-                    **gp_kwargs):
+                    learn_velocity_noise=False, **gp_kwargs):
     """One exact GP per cluster of ``clusters`` = {cluster id: [path ids]} — what
     :func:`kmeans` (``kmeansclustering``, GPmap.py:36-93) returns — modelling the cluster's paths
     as (x(t), y(t)); the modelling step the reference's title names and its clustering prepares
@@ -392,14 +397,16 @@ def fit_path_models(trajs, clusters, inputs=("t",), targets=("x", "y"), devices=
     parts"): cluster i is fitted on ``devices[i % len(devices)]`` (an int n = devices 0..n-1;
     default: the current device), one host thread per device, no data-path collective.  With
     ``optimize`` the hyper-parameters of each model are fitted by :meth:`GP.optimize` (analytic
-    gradient) first.  ``step_noise``: the paths of a cluster are tight in some places and spread out in others, so each
+    gradient, with ``velocities`` as well) first.  ``step_noise``: the paths of a cluster are tight in some places and spread out in others, so each
     cluster's observations get per-step noise weights (:func:`step_noise_weights`, tiled over its paths; the paths
     of a cluster have one length); ``noise`` stays the level, and the model keeps them as ``step_weights``.
     ``velocities`` = {path id: (L, k)}: observed velocities of (some of) the paths — tracker or odometry output — one row
     per path point and one column per target, in raw target units per raw time unit.  Needs ``"t"`` among the inputs.
     They condition the cluster's GP as derivative observations along ``"t"`` at the path's own points
     (``GP.fit(derivatives=)``), normalised by the chain rule ``v * in_span[t] / y_std[c]``; ``velocity_noise`` is their
-    noise variance in those normalised units (as ``noise`` is for the positions; fixed, not learnt by ``optimize``).
+    noise variance in those normalised units (as ``noise`` is for the positions).  ``optimize`` keeps it fixed unless
+    ``learn_velocity_noise`` is set: then each cluster that has velocities learns its own, starting from ``velocity_noise``
+    (which must be > 0), and :attr:`PathModel.velocity_noise` reports it.
     Returns {cluster id: :class:`PathModel`}; empty clusters are skipped."""
     import threading
     from concurrent.futures import ThreadPoolExecutor
@@ -461,6 +468,8 @@ def fit_path_models(trajs, clusters, inputs=("t",), targets=("x", "y"), devices=
         kw = {} if der is None else dict(derivatives=der, derivative_noise=velocity_noise)
         try:
             if optimize:
+                if learn_velocity_noise and der is not None:
+                    kw["params"] = ("lengthscale", "variance", "noise", "derivative_noise")
                 gp.optimize(X, Yn, noise_weights=w, **kw)  # leaves the model fitted at the best point
             else:
                 gp.fit(X, Yn, noise_weights=w, **kw)

@@ -330,8 +330,8 @@ int gpx_score_blocks_weighted(gpx_handle* h, const void* Xs, const void* ys, con
  * or exchanged, with the previous fit still valid and gpx_last_error saying why: a fit with a derivative kind on a
  * Matern-1/2 handle (not differentiable; kinds that are all -1 fit as the plain model there); a fit with kinds set on
  * GPX_MIXED handles, device groups, shards and handles that own a communicator (the set call itself succeeds, and once
- * the kinds are cleared the handle fits as before); gpx_lml_grad, gpx_append and gpx_append_weighted on a fit that has a
- * derivative row.  gpx_predict_grad without variances takes the batch route on such a fit (its matrix-free product knows
+ * the kinds are cleared the handle fits as before); gpx_lml_grad (gpx_lml_grad_full is the gradient of such a fit),
+ * gpx_append and gpx_append_weighted on a fit that has a derivative row.  gpx_predict_grad without variances takes the batch route on such a fit (its matrix-free product knows
  * value columns only).  With no kinds set a handle launches the kernels it launched before and allocates nothing more. */
 int gpx_set_observation_kinds(gpx_handle* h, const int32_t* kind, int64_t n, double sn2_deriv, int32_t mem_kind);
 /* The kinds of the current fit, all -1 when it was made without any.  GPX_E_ARG without a fit. */
@@ -351,6 +351,16 @@ int gpx_get_alpha(gpx_handle* h, void* out /* (N,k) host */);
  * each rank keeps the columns that belong to its own row blocks (N^2 / P numbers), contracts the
  * trace over them, and ntheta numbers are all-reduced (round 3; was GPX_E_UNSUPPORTED). */
 int gpx_lml_grad(gpx_handle* h, double* lml, double* grad);
+/* The same with one more entry (additive to ABI v6), for fits with derivative observations (gpx_set_observation_kinds) as
+ * well: grad[n_ls + 2] = d lml / d log sn2_deriv, with dK / dlog sn2_deriv = sn2_deriv w_i on the derivative rows and
+ * dK / dlog sn2 = sn2 w_i on the value rows.  The entry is exactly 0 when the fit has no derivative row or sn2_deriv = 0.
+ * The derivative of a Gram entry of kinds (ka, kb) by a log lengthscale is the table of csrc/gpx_cov.h (element_dl),
+ * evaluated in the epilogue of the same fused K^-1 trace pass: the cost is gpx_lml_grad's.  Single-device GPX_F64 handles,
+ * with or without kinds or noise weights; on a fit without a derivative row *lml and grad[0 .. n_ls + 2) are gpx_lml_grad's
+ * bit for bit.  GPX_E_UNSUPPORTED on other element types and on shards, device groups and handles that own a communicator
+ * (no fit with a derivative row exists there: gpx_lml_grad is their call).  A failed call writes nothing and leaves the
+ * fit valid. */
+int gpx_lml_grad_full(gpx_handle* h, double* lml, double* grad /* n_ls + 3 */);
 int gpx_logdet(gpx_handle* h, double* out);
 /* Frees what only the NEXT predict / gradient call would use (the V^T batch, the L^-T buffer of
  * gpx_lml_grad, per-tile partials, compact block buffers, the buffers of the joint-posterior calls); the fit itself (factor, alpha, block
@@ -407,6 +417,14 @@ int gpx_kernel_grad_matrix(int32_t kernel, const double* A, int64_t na, const do
  * GPX_E_UNSUPPORTED (gpx_last_error(NULL) says why) and leaves G untouched. */
 int gpx_kernel_deriv_matrix(int32_t kernel, const double* A, int64_t na, const double* B, int64_t nb, int32_t d,
                             const double* lengthscale, int32_t n_ls, double sf2, double* G);
+/* kernel unit-test entry point (host buffers, fp64; additive to ABI v6): G (n_ls, na, nb)[c][a][b] = the derivative by
+ * log lengthscale[c] of the covariance between an observation of kind ka[a] at A_a and one of kind kb[b] at B_b (kinds as
+ * in gpx_set_observation_kinds; ka / kb == NULL: all values) — what gpx_lml_grad_full contracts with K^-1.  n_ls == 1: the
+ * one lengthscale of every dimension.  A kind outside [-1, d): GPX_E_ARG.  GPX_KERNEL_MATERN12 with any kind >= 0 returns
+ * GPX_E_UNSUPPORTED (gpx_last_error(NULL) says why) and leaves G untouched. */
+int gpx_kernel_dl_matrix(int32_t kernel, const double* A, const int32_t* ka, int64_t na, const double* B,
+                         const int32_t* kb, int64_t nb, int32_t d, const double* lengthscale, int32_t n_ls, double sf2,
+                         double* G /* (n_ls, na, nb) */);
 /* in-place lower Cholesky of A (n,n), lda = n; n multiple of 64.  The strictly upper
  * triangle is never read and is scratch on return (diagonal tiles are updated whole).
  * block = panel width (0 = default). */

@@ -3,7 +3,10 @@
 (L^-T by structured forward substitution + fused K^-1 trace pass), against central differences of
 the GPU's own LML for two parameters.   python tools/grad_bench.py [--ntrain 65536]
 With --devices n: the same gradient on a device group of n ranks (one GPU box: the ranks share the
-card, so this checks the sharded gradient at scale against the single-GPU one, it is not a speed-up)."""
+card, so this checks the sharded gradient at scale against the single-GPU one, it is not a speed-up).
+With --derivatives: a quarter of the ntrain rows are derivative observations (gpx_lml_grad_full, the KINDS instantiations
+of the trace kernels), beside the value-only gradient at the same N in the same run, and the wall time of
+GP.optimize(maxiter=3) on the same data with the analytic gradient and with central differences."""
 import argparse, json, os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -13,8 +16,48 @@ from gaussianprocesspathmodelling_amd import GP
 ap = argparse.ArgumentParser()
 ap.add_argument("--ntrain", type=int, default=65536)
 ap.add_argument("--devices", type=int, default=0)
+ap.add_argument("--derivatives", action="store_true")
 a = ap.parse_args()
 N = a.ntrain
+if a.derivatives:
+    rng = np.random.default_rng(12345)
+    Nd = N // 4
+    Nv, d = N - Nd, 3
+    w = rng.uniform(2.0, 5.0, d)
+    f = lambda A: np.sin(A @ w) + 0.3 * np.cos(2.0 * A.sum(axis=1))  # noqa: E731
+    df = lambda A, j: np.cos(A @ w) * w[j] - 0.6 * np.sin(2.0 * A.sum(axis=1))  # noqa: E731
+    X, Xd, dims = rng.uniform(0, 1, (Nv, d)), rng.uniform(0, 1, (Nd, d)), rng.integers(0, d, Nd)
+    y, yd = f(X) + 0.1 * rng.standard_normal(Nv), df(Xd, dims) + 0.2 * rng.standard_normal(Nd)
+    der = (Xd, dims, yd)
+    ls, sf2, sn2, snd = np.array([0.3, 0.25, 0.4]), 1.5, 1e-2, 5e-2
+    keys = ("fit_total", "grad_total", "grad_trtri", "grad_trace")
+    out = {"config": f"N={N} ({Nv} values + {Nd} derivative rows) d=3 Matern-5/2 ARD fp64"}
+    with GP("matern52", ls, sf2, sn2) as gp:
+        Xall = np.concatenate([X, Xd])
+        yall = f(Xall) + 0.1 * rng.standard_normal(N)
+        gp.fit(Xall, yall); gp.lml_gradient()                 # warm-up (allocations)
+        gp.fit(Xall, yall)
+        t0 = time.perf_counter(); gp.lml_gradient(); dt = time.perf_counter() - t0
+        tm = gp.timings_
+        out["values_only_same_N"] = dict({k + "_ms": tm[k] for k in keys}, grad_wall_ms=dt * 1e3)
+        gp.fit(X, y, derivatives=der, derivative_noise=snd); gp.lml_gradient(derivative_noise=True)
+        gp.fit(X, y, derivatives=der, derivative_noise=snd)
+        t0 = time.perf_counter(); lml, grad = gp.lml_gradient(derivative_noise=True); dt = time.perf_counter() - t0
+        tm = gp.timings_
+        out["with_derivatives"] = dict({k + "_ms": tm[k] for k in keys}, grad_wall_ms=dt * 1e3, lml=lml, grad=grad.tolist())
+        out["grad_total_ratio"] = out["with_derivatives"]["grad_total_ms"] / out["values_only_same_N"]["grad_total_ms"]
+        out["trace_ratio"] = out["with_derivatives"]["grad_trace_ms"] / out["values_only_same_N"]["grad_trace_ms"]
+        for jac in ("analytic", "3-point"):
+            walls = []
+            for rep in range(2):                               # (the first run imports the optimiser)
+                gp.lengthscale, gp.variance, gp.noise = ls.copy(), sf2, sn2
+                t0 = time.perf_counter()
+                res = gp.optimize(X, y, maxiter=3, jac=jac, derivatives=der, derivative_noise=snd)
+                walls.append(time.perf_counter() - t0)
+            out[f"optimize_maxiter3_{jac}"] = {"wall_s": walls[1], "first_wall_s": walls[0], "nfev": int(res.nfev),
+                                               "lml": -float(res.fun)}
+    print(json.dumps(out))
+    sys.exit(0)
 X, y, _ = synthetic(N, 3, 16, 12345)
 ls, sf2, sn2 = np.array([0.3, 0.2, 0.25]), 1.5, 1e-2
 if a.devices > 1:
