@@ -79,6 +79,13 @@ SIGNATURES = {
     "gpx_get_noise_weights": (C.c_int, [_P, _P]),
     "gpx_set_observation_kinds": (C.c_int, [_P, _P, C.c_int64, C.c_double, C.c_int32]),
     "gpx_get_observation_kinds": (C.c_int, [_P, _P]),
+    "gpx_set_path_groups": (C.c_int, [_P, _P, C.c_int64, C.c_double, _PD, C.c_int32, C.c_int32]),
+    "gpx_get_path_groups": (C.c_int, [_P, _P]),
+    "gpx_forecast_blocks": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_double, _P, _P, _P, _P, C.c_int32,
+                                      C.POINTER(C.c_int64)]),
+    "gpx_kernel_path_matrix": (C.c_int, [C.c_int32, C.c_int32, _PD, C.POINTER(C.c_int32), C.c_int64, _PD,
+                                         C.POINTER(C.c_int32), C.c_int64, C.c_int32, _PD, C.c_int32, C.c_double, _PD,
+                                         C.c_int32, C.c_double, _PD]),
     "gpx_append_weighted": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int32, C.POINTER(C.c_int64)]),
     "gpx_score_blocks_weighted": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int32, C.c_double, _P, _P, _P, C.c_int32,
                                             C.POINTER(C.c_int64)]),

@@ -122,7 +122,7 @@ struct gpx_handle {
     DevBuf JVT, JTsol, JSig, JSigF, JWinv, JP, JWblk, JUblk, JInfo, JZT, JST, JZin, JOut;
     // posterior gradient (gpx_predict_grad): scratch of its own as well
     DevBuf GV, GTsol, GMT, GMTpart, GVN, GPart, GOut;
-    // block scoring (gpx_score_blocks): targets, per-slice Gram partials, batch mean^T, results + the bad-block word
+    // block scoring (gpx_score_blocks, gpx_forecast_blocks): targets, per-slice Gram partials, batch mean^T, results + the bad-block word
     DevBuf SY, SPart, SMT, SOut;
     DevBuf SW;  // gpx_score_blocks_weighted: the query points' weights
   } scr;
@@ -173,6 +173,16 @@ struct gpx_handle {
   double sn2_deriv = 0.0;
   bool kinded = false;             // the current fit was built by the KINDS builders: every K* against it is, too
   bool has_deriv = false;          // ... and has at least one derivative row
+  // path ids (gpx_set_path_groups): id >= 0 the path of an observation, -1 none; a same-path pair gets
+  // + sg2 k(., .; ls_path).  Nothing here is allocated, and no kernel reads any of it, while no ids are set.
+  std::vector<int32_t> groups_set;  // the ids of the next fits (empty: none set)
+  double sg2_set = 0.0;             // ... their within-path variance
+  std::vector<double> lsp_set;      // ... and lengthscales (1 or d)
+  std::vector<int32_t> groups_fit;  // the ids of the CURRENT fit (grouped only)
+  std::vector<double> q_fit;        // q_c = (l_c / l_path,c)^2 of the current fit (d entries; the source of Gq)
+  DevBuf Gfit, Gdiag, Gq;           // the ids on the device, -1 up to the layout's capacity; the finished diagonal terms; q
+  double sg2 = 0.0;
+  bool grouped = false;             // the current fit was built by the GROUPS builder (ids set, one >= 0, sg2 > 0)
   // event pool
   std::vector<hipEvent_t> ev_pool;
   size_t ev_used = 0;
@@ -1182,7 +1192,44 @@ int stage_fit_kinds(gpx_handle* h, int64_t N, int64_t cap, double sn2, double ji
   return GPX_OK;
 }
 
+// does the next fit take the GROUPS builder?  Path ids set, one of them >= 0, and sg2 > 0: anything else is the plain model
+bool groups_effective(const gpx_handle* h) {
+  if (h->groups_set.empty() || !(h->sg2_set > 0.0)) return false;
+  for (int32_t g : h->groups_set)
+    if (g >= 0) return true;
+  return false;
+}
+
+// The path ids of the fit that begins, as stage_fit_kinds: the fit keeps its own copy (host and device, -1 beyond N up to
+// the capacity), q_c = (l_c / l_path,c)^2 and the finished diagonal terms sn2 w_i + jitter; not effective: nothing happens here.
+template <typename T>
+int stage_fit_groups(gpx_handle* h, int64_t N, int64_t cap, int d, const double* lengthscale, int n_ls, double sn2,
+                     double jitter) {
+  h->grouped = false;
+  if (!groups_effective(h)) return GPX_OK;
+  int rc;
+  if ((rc = ensure(h, h->Gfit, (size_t)cap * sizeof(int32_t)))) return rc;
+  if ((rc = ensure(h, h->Gdiag, (size_t)cap * sizeof(T)))) return rc;
+  if ((rc = ensure(h, h->Gq, MAX_D * 8))) return rc;
+  HIPCHK(h, hipStreamSynchronize(h->st));  // (groups_fit and q_fit are the sources of asynchronous copies of the fit before)
+  h->groups_fit = h->groups_set;
+  h->sg2 = h->sg2_set;
+  h->q_fit.assign((size_t)d, 0.0);
+  for (int c = 0; c < d; ++c) {
+    const double r = lengthscale[n_ls == 1 ? 0 : c] / h->lsp_set[h->lsp_set.size() == 1 ? 0 : c];
+    h->q_fit[c] = r * r;
+  }
+  HIPCHK(h, hipMemsetAsync(h->Gfit.p, 0xFF, (size_t)cap * sizeof(int32_t), h->st));  // -1
+  HIPCHK(h, hipMemcpyAsync(h->Gfit.p, h->groups_fit.data(), (size_t)N * sizeof(int32_t), hipMemcpyHostToDevice, h->st));
+  HIPCHK(h, hipMemcpyAsync(h->Gq.p, h->q_fit.data(), (size_t)d * 8, hipMemcpyHostToDevice, h->st));
+  launch_kinds_diag<T>((const int32_t*)h->Gfit.p, h->weighted ? (const T*)h->Wfit.p : nullptr, N, sn2, sn2, jitter,
+                       (T*)h->Gdiag.p, h->st);
+  h->grouped = true;
+  return GPX_OK;
+}
+
 // K* of value rows As (m valid of mpad) against the training set of the current fit: the KINDS builder on a fit with kinds
+// (a fit with path ids takes the plain builder: query rows are values of f, and Cov[f(x*), y_i] = sf2 k(x*, x_i))
 template <typename T>
 void kbuild_cross_fit(gpx_handle* h, const T* As, int64_t m, int64_t mpad, T* K, int64_t ld) {
   if (h->kinded)
@@ -1239,6 +1286,7 @@ int fit_impl(gpx_handle* h, const void* X, const void* y, int64_t N, int32_t d, 
   if ((rc = ensure(h, h->Ublk, (size_t)h->nb * ldu * sizeof(T)))) return rc;
   if ((rc = stage_fit_weights<T>(h, N, cap))) return rc;
   if ((rc = stage_fit_kinds<T>(h, N, cap, sn2, jitter))) return rc;
+  if ((rc = stage_fit_groups<T>(h, N, cap, d, lengthscale, n_ls, sn2, jitter))) return rc;
   InvWork<T> iw;
   iw.W = (T*)h->Wblk.p;
   iw.U = (T*)h->Ublk.p;
@@ -1269,7 +1317,10 @@ int fit_impl(gpx_handle* h, const void* X, const void* y, int64_t N, int32_t d, 
       PhaseScope ps(h, &tm.kbuild);
       launch_scale_points<T>((const T*)h->X.p, N, Npad, d, (const double*)h->ls.p, n_ls,
                           (T*)h->Xs.p, h->st);
-      if (h->kinded)
+      if (h->grouped)  // (never with kinds set: check_fit_groups)
+        launch_kbuild_sym_g<T>(h->cfg.kernel, (const T*)h->Xs.p, N, Npad, d, sf2, (const int32_t*)h->Gfit.p,
+                               (const double*)h->Gq.p, h->sg2, (const T*)h->Gdiag.p, dK, ld, h->st);
+      else if (h->kinded)
         launch_kbuild_sym_k<T>(h->cfg.kernel, (const T*)h->Xs.p, N, Npad, d, sf2, (const int32_t*)h->Kfit.p,
                                (const double*)h->ls.p, n_ls, (const T*)h->Dfit.p, dK, ld, h->st);
       else if (h->weighted)
@@ -1915,11 +1966,22 @@ size_t score_row_bytes(const gpx_handle* h, int Lg) {
   return b + ((size_t)score_slices(h->Npad) * LP * LP * sizeof(double) + Lg - 1) / Lg;
 }
 
+// gpx_forecast_blocks is the same batch loop with Lg = Lo + Lp rows per block, of which the first Lo carry targets, and
+// block_forecast_kernel in place of block_score_kernel: `fc` says so (null: scoring).
+struct ForecastOut {
+  int Lp;                          // rows to forecast per block (Lo = Lg - Lp observed ones before them)
+  void *mean, *cov, *var, *logp;   // the caller's outputs (cov, var, logp may be null)
+};
+
 template <typename T>
 int score_impl(gpx_handle* h, const void* Xq, const void* yq, const void* wq, int64_t G, int32_t Lg, double diag_add,
-               void* logp, void* maha, void* logdet, int32_t mem_kind, int64_t* info) {
+               void* logp, void* maha, void* logdet, int32_t mem_kind, int64_t* info, const ForecastOut* fc = nullptr) {
   const int64_t N = h->N, Npad = h->Npad, ld = h->ld, M = G * Lg;
   const int d = h->d, k = h->k;
+  const int Lp = fc ? fc->Lp : 0, Lo = Lg - Lp;  // rows of a block that carry targets: Lo (scoring: all Lg)
+  const int64_t My = G * Lo;
+  const double sg2 = h->grouped ? h->sg2 : 0.0;  // a fit with path ids: every block is a new path
+  const double* dq = h->grouped ? (const double*)h->Gq.p : nullptr;
   const int64_t Mpad = round_up(M, TILE);
   gpx_timings& tm = h->tm;
   reset_predict_clocks(tm);
@@ -1928,16 +1990,17 @@ int score_impl(gpx_handle* h, const void* Xq, const void* yq, const void* wq, in
     const size_t row_bytes = score_row_bytes<T>(h, Lg);
     const size_t E = sizeof(T);
     const double small = (double)(M + 2 * TILE) * d * 2 * E + (double)M * (2 * k + (wq ? 1 : 0)) * E + (double)G * (2 * k + 1) * E +
-                         (double)RHS_ROWS * (TILE + ld_skew<T>()) * (1 + splitk_splits(Npad)) * E + 4096;
+                         (double)G * Lp * (k + Lp + 1) * E + (double)RHS_ROWS * (TILE + ld_skew<T>()) * (1 + splitk_splits(Npad)) * E + 4096;
     const double need = (double)TILE * row_bytes + small;
     const double have = (double)h->scr.VT.cap + h->scr.Tsol.cap + h->scr.SPart.cap + h->scr.Q.cap + h->scr.Qs.cap + h->scr.SY.cap +
-                        h->scr.SOut.cap + h->scr.SMT.cap + h->scr.MTpart.cap + h->meanout.cap + (wq ? h->scr.SW.cap : 0);
+                        h->scr.SOut.cap + h->scr.SMT.cap + h->scr.MTpart.cap + h->meanout.cap +
+                        (wq ? h->scr.SW.cap : 0);
     size_t freeb = 0, totalb = 0;
     HIPCHK(h, hipMemGetInfo(&freeb, &totalb));
     if (need > (double)freeb + have) {
       char buf[256];
-      snprintf(buf, sizeof buf, "gpx_score_blocks: one batch of 128 rows needs %.3f GB of device memory, %.3f GB are free",
-               need / 1e9, ((double)freeb + have) / 1e9);
+      snprintf(buf, sizeof buf, "%s: one batch of 128 rows needs %.3f GB of device memory, %.3f GB are free",
+               fc ? "gpx_forecast_blocks" : "gpx_score_blocks", need / 1e9, ((double)freeb + have) / 1e9);
       return fail(h, GPX_E_NOMEM, buf);
     }
   }
@@ -1948,24 +2011,31 @@ int score_impl(gpx_handle* h, const void* Xq, const void* yq, const void* wq, in
   const int S = score_slices(Npad), LP = score_lp(Lg);
   // a batch reads rows_b rows of Qs from its first block on: up to 127 rows beyond M
   if ((rc = ensure_queries<T>(h, M + TILE))) return rc;
-  if ((rc = ensure(h, h->scr.SY, (size_t)M * k * sizeof(T)))) return rc;
+  if ((rc = ensure(h, h->scr.SY, (size_t)My * k * sizeof(T)))) return rc;
   if (wq && (rc = ensure(h, h->scr.SW, (size_t)M * sizeof(T)))) return rc;
   if ((rc = ensure(h, h->scr.VT, (size_t)rows_b * ld * sizeof(T)))) return rc;
   if ((rc = ensure(h, h->scr.SMT, (size_t)RHS_ROWS * ldmb * sizeof(T)))) return rc;
   if ((rc = ensure_mean_partials<T>(h, h->scr.MTpart, ldmb))) return rc;
   if ((rc = ensure(h, h->meanout, (size_t)M * k * sizeof(T)))) return rc;
   if ((rc = ensure(h, h->scr.SPart, (size_t)bpb * S * LP * LP * sizeof(double)))) return rc;
-  const size_t out_elems = (size_t)G * (2 * k + 1);
+  const size_t out_elems = fc ? (size_t)G * Lp * (k + Lp + 1) + (size_t)G * k : (size_t)G * (2 * k + 1);
   const size_t bad_off = round_up((int64_t)(out_elems * sizeof(T)), 16);
-  if ((rc = ensure(h, h->scr.SOut, bad_off + 16))) return rc;
+  DevBuf& outbuf = h->scr.SOut;
+  if ((rc = ensure(h, outbuf, bad_off + 16))) return rc;
   SolveWork<T> sw;
   if ((rc = dense_solve_work<T>(h, h->scr.Tsol, rows_b, &sw))) return rc;
   T* dVT = (T*)h->scr.VT.p;
   T* dMT = (T*)h->scr.SMT.p;
-  T* dLogp = (T*)h->scr.SOut.p;
+  // the results of a call, one layout per kind of call (out_elems above), the bad-block word behind either:
+  //   scoring   logp (G, k) | maha (G, k) | logdet (G)
+  //   forecast  logp (G, k) | mean (G Lp, k) | cov (G, Lp, Lp) | var (G Lp)
+  T* dLogp = (T*)outbuf.p;
   T* dMaha = dLogp + G * k;
   T* dLogdet = dMaha + G * k;
-  int* dBad = (int*)((char*)h->scr.SOut.p + bad_off);
+  T* dFmean = dLogp + G * k;
+  T* dFcov = dFmean + G * Lp * k;
+  T* dFvar = dFcov + G * Lp * Lp;
+  int* dBad = (int*)((char*)outbuf.p + bad_off);
   const T* dQs = (const T*)h->scr.Qs.p;
   int hbad = INT_MAX;
   {
@@ -1974,7 +2044,7 @@ int score_impl(gpx_handle* h, const void* Xq, const void* yq, const void* wq, in
       PhaseScope ps(h, &tm.kstar);
       if ((rc = upload_queries<T>(h, Xq, M, mem_kind))) return rc;
       HIPCHK(h, hipMemsetAsync((T*)h->scr.Qs.p + Mpad * d, 0, (size_t)TILE * d * sizeof(T), h->st));
-      if ((rc = copy_in(h, h->scr.SY.p, yq, (size_t)M * k * sizeof(T), mem_kind))) return rc;
+      if ((rc = copy_in(h, h->scr.SY.p, yq, (size_t)My * k * sizeof(T), mem_kind))) return rc;
       if (wq && (rc = copy_in(h, h->scr.SW.p, wq, (size_t)M * sizeof(T), mem_kind))) return rc;
       const int init = INT_MAX;
       HIPCHK(h, hipMemcpyAsync(dBad, &init, sizeof(int), hipMemcpyHostToDevice, h->st));
@@ -1998,13 +2068,25 @@ int score_impl(gpx_handle* h, const void* Xq, const void* yq, const void* wq, in
       {
         PhaseScope ps(h, &tm.var);
         launch_block_gram<T>(dVT, ld, nb, Lg, Npad, (double*)h->scr.SPart.p, h->st);
-        launch_block_score<T>(h->cfg.kernel, (const double*)h->scr.SPart.p, nb, Lg, Npad, dQs + m0 * d, d,
-                              (const T*)h->scr.SY.p + m0 * k, (const T*)h->meanout.p + m0 * k, k, h->sf2, diag_add, dLogp,
-                              dMaha, dLogdet, g0, dBad, h->st, wq ? (const T*)h->scr.SW.p + m0 : nullptr);
+        if (fc)
+          launch_block_forecast<T>(h->cfg.kernel, (const double*)h->scr.SPart.p, nb, Lo, Lp, Npad, dQs + m0 * d, d,
+                                   (const T*)h->scr.SY.p + g0 * Lo * k, (const T*)h->meanout.p + m0 * k, k, h->sf2, sg2, dq,
+                                   diag_add, dFmean, dFcov, dFvar, dLogp, g0, dBad, h->st);
+        else
+          launch_block_score<T>(h->cfg.kernel, (const double*)h->scr.SPart.p, nb, Lg, Npad, dQs + m0 * d, d,
+                                (const T*)h->scr.SY.p + m0 * k, (const T*)h->meanout.p + m0 * k, k, h->sf2, diag_add, dLogp,
+                                dMaha, dLogdet, g0, dBad, h->st, wq ? (const T*)h->scr.SW.p + m0 : nullptr, sg2, dq);
       }
     }
     PhaseScope ps(h, &tm.d2h);
-    if ((rc = copy_out(h, logp, dLogp, (size_t)G * k * sizeof(T), mem_kind))) return rc;
+    if (fc) {
+      if ((rc = copy_out(h, fc->mean, dFmean, (size_t)G * Lp * k * sizeof(T), mem_kind))) return rc;
+      if (fc->cov && (rc = copy_out(h, fc->cov, dFcov, (size_t)G * Lp * Lp * sizeof(T), mem_kind))) return rc;
+      if (fc->var && (rc = copy_out(h, fc->var, dFvar, (size_t)G * Lp * sizeof(T), mem_kind))) return rc;
+      if (fc->logp && (rc = copy_out(h, fc->logp, dLogp, (size_t)G * k * sizeof(T), mem_kind))) return rc;
+    } else if ((rc = copy_out(h, logp, dLogp, (size_t)G * k * sizeof(T), mem_kind))) {
+      return rc;
+    }
     if (maha && (rc = copy_out(h, maha, dMaha, (size_t)G * k * sizeof(T), mem_kind))) return rc;
     if (logdet && (rc = copy_out(h, logdet, dLogdet, (size_t)G * sizeof(T), mem_kind))) return rc;
     HIPCHK(h, hipMemcpyAsync(&hbad, dBad, sizeof(int), hipMemcpyDeviceToHost, h->st));
@@ -2715,9 +2797,37 @@ int check_fit_kinds(gpx_handle* h, const char* fn, int64_t N, int32_t d) {
   return GPX_OK;
 }
 
+// a fit on a handle with path ids set, before anything is computed or exchanged: GPX_E_ARG for ids or lengthscales that do
+// not fit the call, GPX_E_UNSUPPORTED where no GROUPS builder runs (only when the ids take effect: groups_effective)
+int check_fit_groups(gpx_handle* h, const char* fn, int64_t N, int32_t d) {
+  if (h->groups_set.empty()) return GPX_OK;
+  char buf[320];
+  if (N != (int64_t)h->groups_set.size()) {
+    snprintf(buf, sizeof buf, "%s: %lld path ids are set for a fit of %lld observations", fn,
+             (long long)h->groups_set.size(), (long long)N);
+    return fail(h, GPX_E_ARG, buf);
+  }
+  if (h->lsp_set.size() != 1 && (int64_t)h->lsp_set.size() != d) {
+    snprintf(buf, sizeof buf, "%s: %d path lengthscales are set, the inputs have %d dimensions (need 1 or d)", fn,
+             (int)h->lsp_set.size(), (int)d);
+    return fail(h, GPX_E_ARG, buf);
+  }
+  if (!groups_effective(h)) return GPX_OK;
+  const char* where = h->group ? "device groups" : (h->cfg.world > 1 || h->comm) ? "sharded handles"
+                      : h->cfg.dtype == GPX_MIXED ? "GPX_MIXED handles"
+                      : !h->kinds_set.empty() ? "handles that also have observation kinds set" : nullptr;
+  if (where) {
+    snprintf(buf, sizeof buf, "%s: path ids are not supported on %s (no builder of the within-path covariance runs there; "
+             "single-device GPX_F64 / GPX_F32 handles only; clear them with gpx_set_path_groups(h, NULL, 0, ...))", fn, where);
+    return fail(h, GPX_E_UNSUPPORTED, buf);
+  }
+  return GPX_OK;
+}
+
 // gpx_fit on one handle, behind its argument checks and begin_fit
 int fit_begun(gpx_handle* h, const void* X, const void* y, int64_t N, int32_t d, int32_t k, const double* lengthscale,
               int32_t n_ls, double sf2, double sn2, double jitter, int32_t mem_kind, int64_t* info) {
+  h->grouped = false;  // (fit_impl decides; the other engines never build with path ids: check_fit_groups)
   if (h->cfg.dtype == GPX_MIXED) return mixed_fit(h, X, y, N, d, k, lengthscale, n_ls, sf2, sn2, jitter, mem_kind, info);
   if (h->cfg.world > 1 || h->comm) {  // a 1-rank communicator also takes the sharded schedule
     h->weighted = false;
@@ -2747,6 +2857,7 @@ int gpx_fit(gpx_handle* h, const void* X, const void* y, int64_t N, int32_t d, i
     return rc;
   if ((rc = check_fit_weights(h, "gpx_fit", N))) return rc;
   if ((rc = check_fit_kinds(h, "gpx_fit", N, d))) return rc;
+  if ((rc = check_fit_groups(h, "gpx_fit", N, d))) return rc;
   if (h->group) return group_fit(h, X, y, N, d, k, lengthscale, n_ls, sf2, sn2, jitter, mem_kind, info);
   if ((rc = begin_fit(h))) return rc;
   return fit_begun(h, X, y, N, d, k, lengthscale, n_ls, sf2, sn2, jitter, mem_kind, info);
@@ -2763,6 +2874,7 @@ int gpx_fit_predict(gpx_handle* h, const void* X, const void* y, int64_t N, int3
     return rc;
   if ((rc = check_fit_weights(h, "gpx_fit_predict", N))) return rc;
   if ((rc = check_fit_kinds(h, "gpx_fit_predict", N, d))) return rc;
+  if ((rc = check_fit_groups(h, "gpx_fit_predict", N, d))) return rc;
   if (h->group) return group_fit_predict(h, X, y, N, d, k, lengthscale, n_ls, sf2, sn2, jitter, Xq, M, mean, var, mem_kind, info);
   // Shards (round 4): every rank's slice of the query points rides through the sharded factorisation as bordered rows of
   // its local row set (shard_fit with query points + shard_fused_tail) — in the split schedule, up to 8192 rows per rank.
@@ -2775,6 +2887,7 @@ int gpx_fit_predict(gpx_handle* h, const void* X, const void* y, int64_t N, int3
       if (rc != GPX_OK || *info != 0) return rc;
       return gpx_predict(h, Xq, M, mean, var, mem_kind);
     }
+    h->grouped = false;
     rc = BY_DTYPE(h, shard_fit, h, X, y, N, d, k, lengthscale, n_ls, sf2, sn2, jitter, mem_kind, info, false, Xq, M);
     if (rc != GPX_OK || !h->fitted) return rc;
     return BY_DTYPE(h, shard_fused_tail, h, M, mean, var, mem_kind);
@@ -2910,6 +3023,9 @@ int append_entry(gpx_handle* h, const void* Xnew, const void* ynew, const void* 
   if (h->has_deriv)
     return fail(h, GPX_E_UNSUPPORTED, "gpx_append: the fit has derivative observations (gpx_set_observation_kinds): fit the "
                                       "concatenated data instead");
+  if (h->grouped)
+    return fail(h, GPX_E_UNSUPPORTED, "gpx_append: the fit has path ids (gpx_set_path_groups) and the appended rows would be "
+                                      "built without the within-path covariance: fit the concatenated data instead");
   h->kinded = false;  // (kinds all -1: the plain model, and from here on the plain builders' — the same numbers)
   if ((rc = begin_call(h))) return rc;
   if (wnew && (rc = check_weights(h, "gpx_append_weighted", wnew, m, mem_kind, h->cfg.dtype == GPX_F32 ? 4 : 8, h->st)))
@@ -3041,6 +3157,73 @@ int gpx_get_observation_kinds(gpx_handle* h, int32_t* out) try {
 }
 GPX_CATCH_ALL
 
+int gpx_set_path_groups(gpx_handle* h, const int32_t* group, int64_t n, double sg2, const double* ls_path,
+                        int32_t n_ls_path, int32_t mem_kind) try {
+  if (!h) return GPX_E_ARG;
+  if (mem_kind != GPX_MEM_HOST && mem_kind != GPX_MEM_DEVICE) return fail(h, GPX_E_ARG, "gpx_set_path_groups: bad mem_kind");
+  if (n < 0 || (n == 0) != (group == nullptr) || n > (int64_t)INT_MAX - 4096)
+    return fail(h, GPX_E_ARG, "gpx_set_path_groups: need n path ids, or NULL and 0 to clear them");
+  if (n == 0) {
+    h->groups_set.clear();
+    h->lsp_set.clear();
+    h->sg2_set = 0.0;
+    return GPX_OK;
+  }
+  if (!(sg2 >= 0.0) || !std::isfinite(sg2)) return fail(h, GPX_E_ARG, "gpx_set_path_groups: sg2 must be finite and >= 0");
+  if (!ls_path || n_ls_path < 1 || n_ls_path > MAX_D)
+    return fail(h, GPX_E_ARG, "gpx_set_path_groups: need 1 or d path lengthscales");
+  for (int32_t c = 0; c < n_ls_path; ++c)
+    if (!(ls_path[c] > 0.0) || !std::isfinite(ls_path[c]))
+      return fail(h, GPX_E_ARG, "gpx_set_path_groups: path lengthscales must be finite and > 0");
+  // validated in a copy of the caller's array, before the handle's is replaced: a refused call leaves the setting of the
+  // call before in place
+  std::vector<int32_t> fresh((size_t)n);
+  if (mem_kind == GPX_MEM_HOST) {
+    std::copy(group, group + n, fresh.begin());
+  } else {
+    if (!h->group) HIPCHK(h, hipSetDevice(h->cfg.device));
+    HIPCHK(h, hipMemcpy(fresh.data(), group, (size_t)n * sizeof(int32_t), hipMemcpyDefault));
+  }
+  for (int64_t i = 0; i < n; ++i)
+    if (fresh[i] < -1) return fail(h, GPX_E_ARG, "gpx_set_path_groups: a path id is -1 (no path) or >= 0");
+  h->groups_set = std::move(fresh);
+  h->lsp_set.assign(ls_path, ls_path + n_ls_path);
+  h->sg2_set = sg2;
+  return GPX_OK;
+}
+GPX_CATCH_ALL
+
+int gpx_get_path_groups(gpx_handle* h, int32_t* out) try {
+  if (!h) return GPX_E_ARG;
+  if (!h->fitted || !out) return fail(h, GPX_E_ARG, "gpx_get_path_groups: no fit or null output");
+  const int64_t N = h->group ? h->group->members[0]->N : h->N;
+  if (h->grouped && (int64_t)h->groups_fit.size() == N)
+    std::copy(h->groups_fit.begin(), h->groups_fit.end(), out);
+  else
+    std::fill(out, out + N, (int32_t)-1);
+  return GPX_OK;
+}
+GPX_CATCH_ALL
+
+int gpx_forecast_blocks(gpx_handle* h, const void* Xb, const void* yo, int64_t G, int32_t Lo, int32_t Lp, double diag_add,
+                        void* mean, void* cov, void* var, void* logp, int32_t mem_kind, int64_t* info) try {
+  if (!h) return GPX_E_ARG;
+  if (!Xb || !yo || !mean || !info || G <= 0) return fail(h, GPX_E_ARG, "gpx_forecast_blocks: bad argument");
+  if (Lo < 1 || Lp < 1 || (int64_t)Lo + Lp > 64)
+    return fail(h, GPX_E_ARG, "gpx_forecast_blocks: need 1 <= Lo, 1 <= Lp and Lo + Lp <= 64");
+  if (!(diag_add >= 0.0)) return fail(h, GPX_E_ARG, "gpx_forecast_blocks: need diag_add >= 0");
+  if (mem_kind != GPX_MEM_HOST && mem_kind != GPX_MEM_DEVICE) return fail(h, GPX_E_ARG, "gpx_forecast_blocks: bad mem_kind");
+  if (!h->fitted) return fail(h, GPX_E_ARG, "gpx_forecast_blocks: handle has no successful fit");
+  const int32_t Lg = Lo + Lp;
+  if (G > ((int64_t)INT_MAX - 4096) / (Lg * (int64_t)Lp)) return fail(h, GPX_E_ARG, "gpx_forecast_blocks: G too large");
+  int rc;
+  if ((rc = posterior_refused(h, "gpx_forecast_blocks"))) return rc;
+  if ((rc = begin_call(h))) return rc;
+  const ForecastOut fc{Lp, mean, cov, var, logp};
+  return BY_DTYPE(h, score_impl, h, Xb, yo, nullptr, G, Lg, diag_add, nullptr, nullptr, nullptr, mem_kind, info, &fc);
+}
+GPX_CATCH_ALL
+
 int gpx_reserve(gpx_handle* h, int64_t capacity) try {
   if (!h) return GPX_E_ARG;
   if (capacity < 0 || capacity > (int64_t)INT_MAX - 4096) return fail(h, GPX_E_ARG, "gpx_reserve: bad capacity");
@@ -3085,6 +3268,9 @@ int gpx_lml_grad(gpx_handle* h, double* lml, double* grad) try {
   if (!h) return GPX_E_ARG;
   if (!h->fitted || !lml || !grad) return fail(h, GPX_E_ARG, "gpx_lml_grad: no fit or null output");
   if (h->cfg.dtype != GPX_F64) return fail(h, GPX_E_UNSUPPORTED, "gpx_lml_grad: fp64 handles only");
+  if (h->grouped)
+    return fail(h, GPX_E_UNSUPPORTED, "gpx_lml_grad: the fit has path ids (gpx_set_path_groups); the gradient passes evaluate "
+                                      "dK / dtheta matrix-free without the within-path covariance (difference the LML instead)");
   if (h->has_deriv)  // (n_ls + 2 entries have no room for d / dlog sn2_deriv)
     return fail(h, GPX_E_UNSUPPORTED, "gpx_lml_grad: the fit has derivative observations (gpx_set_observation_kinds): "
                                       "call gpx_lml_grad_full, whose gradient has the n_ls + 3 entries of such a fit");
@@ -3103,6 +3289,10 @@ int gpx_lml_grad_full(gpx_handle* h, double* lml, double* grad) try {
   if (h->cfg.dtype != GPX_F64) return fail(h, GPX_E_UNSUPPORTED, "gpx_lml_grad_full: fp64 handles only");
   if (h->group || h->comm || h->cfg.world > 1)
     return fail(h, GPX_E_UNSUPPORTED, "gpx_lml_grad_full: single-device handles only (gpx_lml_grad on shards and groups)");
+  if (h->grouped)
+    return fail(h, GPX_E_UNSUPPORTED, "gpx_lml_grad_full: the fit has path ids (gpx_set_path_groups); the gradient passes "
+                                      "evaluate dK / dtheta matrix-free without the within-path covariance (difference the "
+                                      "LML instead)");
   int rc;
   if ((rc = begin_call(h))) return rc;
   if (h->has_deriv) return lml_grad_impl(h, lml, grad, true);
@@ -3267,6 +3457,79 @@ done:
   for (double* p : {dA, dB, dAs, dBs, dls, dG})
     if (p) (void)hipFree(p);
   return rc;
+}
+GPX_CATCH_ALL
+
+extern "C++" {
+namespace {
+template <typename T>
+int kernel_path_matrix_t(int32_t kernel, const double* A, const int32_t* ga, int64_t na, const double* B, const int32_t* gb,
+                         int64_t nb_, int32_t d, const double* lengthscale, int32_t n_ls, double sf2, const double* ls_path,
+                         int32_t n_ls_path, double sg2, double* K) {
+  Scratch sc;
+  if (!sc.ok) return GPX_E_HIP;
+  hipStream_t st = sc.h.st;
+  const int64_t napad = round_up(na, 64), nbpad = round_up(nb_, 64), ld = nbpad;
+  T *dA = nullptr, *dB = nullptr, *dAs = nullptr, *dBs = nullptr, *dK = nullptr;
+  double *dls = nullptr, *dq = nullptr;
+  int32_t *dga = nullptr, *dgb = nullptr;
+  std::vector<T> hA(A, A + na * d), hB(B, B + nb_ * d), host((size_t)napad * ld);  // (rounded to T on the host)
+  std::vector<double> q((size_t)d);
+  for (int c = 0; c < d; ++c) {
+    const double r = lengthscale[n_ls == 1 ? 0 : c] / ls_path[n_ls_path == 1 ? 0 : c];
+    q[c] = r * r;
+  }
+  int rc = GPX_OK;
+  TCHK(hipMalloc(&dA, (size_t)na * d * sizeof(T)));
+  TCHK(hipMalloc(&dB, (size_t)nb_ * d * sizeof(T)));
+  TCHK(hipMalloc(&dAs, (size_t)napad * d * sizeof(T)));
+  TCHK(hipMalloc(&dBs, (size_t)nbpad * d * sizeof(T)));
+  TCHK(hipMalloc(&dls, MAX_D * 8));
+  TCHK(hipMalloc(&dq, MAX_D * 8));
+  TCHK(hipMalloc(&dga, (size_t)napad * 4));
+  TCHK(hipMalloc(&dgb, (size_t)nbpad * 4));
+  TCHK(hipMalloc(&dK, (size_t)napad * ld * sizeof(T)));
+  TCHK(hipMemcpyAsync(dA, hA.data(), (size_t)na * d * sizeof(T), hipMemcpyHostToDevice, st));
+  TCHK(hipMemcpyAsync(dB, hB.data(), (size_t)nb_ * d * sizeof(T), hipMemcpyHostToDevice, st));
+  TCHK(hipMemcpyAsync(dls, lengthscale, (size_t)n_ls * 8, hipMemcpyHostToDevice, st));
+  TCHK(hipMemcpyAsync(dq, q.data(), (size_t)d * 8, hipMemcpyHostToDevice, st));
+  TCHK(hipMemsetAsync(dga, 0xFF, (size_t)napad * 4, st));  // -1 beyond the valid ids
+  TCHK(hipMemsetAsync(dgb, 0xFF, (size_t)nbpad * 4, st));
+  TCHK(hipMemcpyAsync(dga, ga, (size_t)na * 4, hipMemcpyHostToDevice, st));
+  TCHK(hipMemcpyAsync(dgb, gb, (size_t)nb_ * 4, hipMemcpyHostToDevice, st));
+  launch_scale_points<T>(dA, na, napad, d, dls, n_ls, dAs, st);
+  launch_scale_points<T>(dB, nb_, nbpad, d, dls, n_ls, dBs, st);
+  launch_kbuild_cross_g<T>(kernel, dAs, dga, na, napad, dBs, dgb, nb_, nbpad, d, sf2, dq, sg2, dK, ld, st);
+  TCHK(hipMemcpyAsync(host.data(), dK, (size_t)napad * ld * sizeof(T), hipMemcpyDeviceToHost, st));
+  TCHK(hipStreamSynchronize(st));
+  TCHK(hipGetLastError());
+  for (int64_t i = 0; i < na; ++i)
+    for (int64_t j = 0; j < nb_; ++j) K[i * nb_ + j] = (double)host[(size_t)i * ld + j];
+done:
+  for (void* p : {(void*)dA, (void*)dB, (void*)dAs, (void*)dBs, (void*)dK, (void*)dls, (void*)dq, (void*)dga, (void*)dgb})
+    if (p) (void)hipFree(p);
+  return rc;
+}
+}  // namespace
+}  // extern "C++"
+
+int gpx_kernel_path_matrix(int32_t kernel, int32_t dtype, const double* A, const int32_t* ga, int64_t na, const double* B,
+                           const int32_t* gb, int64_t nb_, int32_t d, const double* lengthscale, int32_t n_ls, double sf2,
+                           const double* ls_path, int32_t n_ls_path, double sg2, double* K) try {
+  if (!A || !B || !ga || !gb || !K || !lengthscale || !ls_path || na <= 0 || nb_ <= 0 || d <= 0 || d > MAX_D ||
+      (n_ls != 1 && n_ls != d) || (n_ls_path != 1 && n_ls_path != d))
+    return GPX_E_ARG;
+  if (!cov::known(kernel) || (dtype != GPX_F64 && dtype != GPX_F32)) return GPX_E_ARG;
+  if (!(sg2 >= 0.0) || !std::isfinite(sg2)) return GPX_E_ARG;
+  for (int32_t c = 0; c < n_ls_path; ++c)
+    if (!(ls_path[c] > 0.0) || !std::isfinite(ls_path[c])) return GPX_E_ARG;
+  for (int64_t i = 0; i < na; ++i)
+    if (ga[i] < -1) return GPX_E_ARG;
+  for (int64_t i = 0; i < nb_; ++i)
+    if (gb[i] < -1) return GPX_E_ARG;
+  if (dtype == GPX_F32)
+    return kernel_path_matrix_t<float>(kernel, A, ga, na, B, gb, nb_, d, lengthscale, n_ls, sf2, ls_path, n_ls_path, sg2, K);
+  return kernel_path_matrix_t<double>(kernel, A, ga, na, B, gb, nb_, d, lengthscale, n_ls, sf2, ls_path, n_ls_path, sg2, K);
 }
 GPX_CATCH_ALL
 

@@ -116,6 +116,18 @@ template <typename T>
 void launch_kbuild_cross_k(int kernel, const T* As, int64_t m, int64_t mpad, const T* Bs, int64_t n, int64_t npad, int d,
                            double sf2, const int32_t* kind_b, const double* ls, int n_ls, T* K, int64_t ld, hipStream_t st);
 
+// Observations with path ids (id >= 0 names the path of an observation, -1 none; the arrays are readable up
+// to the padded sizes and hold -1 there): + sg2 k(x, x'; l_path) where the ids of a pair match.  q (d entries, device) =
+// (l_c / l_path,c)^2: the scaled points' differences times sqrt(q_c) are the path kernel's.  diag as launch_kinds_diag's.
+template <typename T>
+void launch_kbuild_sym_g(int kernel, const T* Xs, int64_t n, int64_t npad, int d, double sf2, const int32_t* group,
+                         const double* q, double sg2, const T* diag, T* K, int64_t ld, hipStream_t st);
+// the rectangular build over two sets of such observations (gpx_kernel_path_matrix)
+template <typename T>
+void launch_kbuild_cross_g(int kernel, const T* As, const int32_t* group_a, int64_t m, int64_t mpad, const T* Bs,
+                           const int32_t* group_b, int64_t n, int64_t npad, int d, double sf2, const double* q, double sg2,
+                           T* K, int64_t ld, hipStream_t st);
+
 // ---- dense blocks (gpx_blas.hip) ---------------------------------------------------
 // In-place Cholesky of one 64x64 diagonal block (lower) + its inverse Winv (64x64,
 // row-major, upper part zero).  gidx0 = global index of the block's first row (info).
@@ -371,8 +383,17 @@ void launch_block_gram(const T* VT, int64_t ld, int64_t nblk, int Lg, int64_t np
 template <typename T>
 void launch_block_score(int kernel, const double* part, int64_t nblk, int Lg, int64_t npad, const T* Qs, int d,
                         const T* ys, const T* mean, int k, double sf2, double diag_add, T* logp, T* maha, T* logdet,
-                        int64_t g0, int* bad, hipStream_t st, const T* wq = nullptr);  // wq (nblk Lg), from the batch's first
-                                                                                       // row: + diag_add wq[i] per point
+                        int64_t g0, int* bad, hipStream_t st, const T* wq = nullptr,  // wq (nblk Lg), from the batch's first
+                        double sg2 = 0.0, const double* q = nullptr);                 // row: + diag_add wq[i] per point
+// sg2 > 0 (a fit with path ids): every block is a new path, S gains sg2 k(Qs_b, Qs_b; l_path); q (d, device) = (l_c / l_path,c)^2
+// Block b < nblk of a batch of gpx_forecast_blocks: Lo observed rows, then Lp rows to forecast (Lo + Lp <= 64); part as
+// above with Lg = Lo + Lp; Qs and mean ((Lo + Lp) rows per block) and yo (Lo rows per block) start at the batch's first
+// block, the outputs at block 0 of the call: fmean (G Lp, k), fcov (G, Lp, Lp) | null, fvar (G Lp) | null, flogp (G, k) | null.
+// diag_add goes on the observed rows only.  A pivot that is not > 0: NaN outputs, *bad = min(*bad, g + 1).
+template <typename T>
+void launch_block_forecast(int kernel, const double* part, int64_t nblk, int Lo, int Lp, int64_t npad, const T* Qs, int d,
+                           const T* yo, const T* mean, int k, double sf2, double sg2, const double* q, double diag_add,
+                           T* fmean, T* fcov, T* fvar, T* flogp, int64_t g0, int* bad, hipStream_t st);
 
 // ---- row-block-cyclic shard helpers (gpx_misc.hip; T = double | float) ------------------------
 // A[i][i] = i < nvalid ? A[i][i] + add : 1   for i < n (diagonal of one local row block)

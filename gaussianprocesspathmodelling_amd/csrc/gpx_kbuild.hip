@@ -8,6 +8,8 @@
 // once in LDS, each lane writes 16-byte (2 x f64) pieces so a half-wave covers 512
 // contiguous bytes of one row.  Algorithmic traffic: 8 B per entry written, the
 // points (N*d*8 B) read once per tile row/column from L2.
+#include <climits>
+
 #include "gpx_cov.h"
 #include "gpx_internal.h"
 
@@ -46,7 +48,15 @@ __device__ __forceinline__ void tri_coords(int64_t t, int& ti, int& tj) {
 // The 64 + 64 kinds and 1 / l are staged beside the points.  A tile whose kinds are all -1 — decided once per workgroup,
 // wave-uniform — takes the value-only path, whose numbers are those of the plain build; a mixed tile evaluates cov::element,
 // still one exponential per pair.  SYM: w is the finished per-row diagonal term (launch_kinds_diag), read on diagonal tiles.
-template <typename T, int KERNEL, bool SYM, int D, bool WEIGHTED = false, bool KINDS = false>
+// GROUPS (never with KINDS): the observations carry path ids (-1: no path) and a same-path pair gets + sg2 k(., .; l_path),
+// the within-path deviation of the hierarchical model.  The side channels are reused: krow / kcol are
+// the row / column ids (readable up to the padded sizes, -1 there), ls (n_ls == d) holds q_c = (l_c / l_path,c)^2 and wsn2
+// is sg2; SYM: w is the finished per-row diagonal term, as for KINDS.  The 64 + 64 ids and q are staged beside the points.
+// Whether the tile can hold a same-path pair — the ranges of the non-negative row and column ids overlap — is decided once
+// per workgroup, wave-uniform; a tile that cannot takes the value-only path, whose numbers are those of the plain build.
+// Otherwise r_path^2 = sum_c q_c e_c^2 from the scaled differences e_c the loop forms anyway, and cov::value(r_path^2, sg2)
+// is added where the ids match (SYM: the diagonal gets sg2 this way).
+template <typename T, int KERNEL, bool SYM, int D, bool WEIGHTED = false, bool KINDS = false, bool GROUPS = false>
 __global__ __launch_bounds__(256) void kbuild_kernel(const T* __restrict__ As, int64_t m,
                                                     const T* __restrict__ Bs, int64_t n, int d_rt,
                                                     int tiles_n, T sf2, T diag_add, T* __restrict__ K,
@@ -89,6 +99,27 @@ __global__ __launch_bounds__(256) void kbuild_kernel(const T* __restrict__ As, i
     }
     mixed = __syncthreads_or(deriv) != 0;
     ska = kab, skb = kab + KT, sil = ilv;
+  } else if constexpr (GROUPS) {
+    static_assert(!WEIGHTED, "the GROUPS build takes its diagonal from the finished per-row vector");
+    __shared__ int gab[2 * KT];
+    __shared__ int rng[4];  // lowest / highest non-negative id of the rows, of the columns
+    __shared__ T qv[D > 0 ? D : MAX_D];
+    if (tid < 2 * KT) {  // wave 0: the rows, wave 1: the columns
+      const int id = tid < KT ? krow[i0 + tid] : kcol[j0 + tid - KT];
+      gab[tid] = id;
+      int lo = id >= 0 ? id : INT_MAX, hi = id;
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) {
+        lo = min(lo, __shfl_xor(lo, o));
+        hi = max(hi, __shfl_xor(hi, o));
+      }
+      if ((tid & 63) == 0) rng[2 * (tid >> 6)] = lo, rng[2 * (tid >> 6) + 1] = hi;
+    } else if (tid - 2 * KT < d) {
+      qv[tid - 2 * KT] = (T)ls[tid - 2 * KT];
+    }
+    __syncthreads();
+    mixed = rng[0] <= rng[3] && rng[2] <= rng[1];  // (no id >= 0 on a side: lo = INT_MAX, hi < 0)
+    ska = gab, skb = gab + KT, sil = qv;
   } else {
     __syncthreads();
   }
@@ -108,6 +139,7 @@ __global__ __launch_bounds__(256) void kbuild_kernel(const T* __restrict__ As, i
     const int il = rg + 8 * r;
     const int64_t row = i0 + il;
     T s0 = (T)0, s1 = (T)0;
+    [[maybe_unused]] T p0 = (T)0, p1 = (T)0;  // GROUPS, on a tile that can hold a same-path pair: r_path^2
     if (D > 0) {
 #pragma unroll
       for (int c = 0; c < D; ++c) {
@@ -115,6 +147,9 @@ __global__ __launch_bounds__(256) void kbuild_kernel(const T* __restrict__ As, i
         const T e0 = a - bj0[c], e1 = a - bj1[c];
         s0 += e0 * e0;
         s1 += e1 * e1;
+        if constexpr (GROUPS) {
+          if (mixed) p0 += sil[c] * (e0 * e0), p1 += sil[c] * (e1 * e1);
+        }
       }
     } else {
       for (int c = 0; c < d; ++c) {
@@ -122,6 +157,9 @@ __global__ __launch_bounds__(256) void kbuild_kernel(const T* __restrict__ As, i
         const T e0 = a - xb[c2 * d + c], e1 = a - xb[(c2 + 1) * d + c];
         s0 += e0 * e0;
         s1 += e1 * e1;
+        if constexpr (GROUPS) {
+          if (mixed) p0 += sil[c] * (e0 * e0), p1 += sil[c] * (e1 * e1);
+        }
       }
     }
     T v0, v1;
@@ -141,9 +179,16 @@ __global__ __launch_bounds__(256) void kbuild_kernel(const T* __restrict__ As, i
       }
     } else {
       v0 = cov::value<KERNEL>(s0, sf2), v1 = cov::value<KERNEL>(s1, sf2);
+      if constexpr (GROUPS) {
+        if (mixed) {
+          const int ga = ska[il];
+          if (ga >= 0 && ga == skb[c2]) v0 += cov::value<KERNEL>(p0, (T)wsn2);
+          if (ga >= 0 && ga == skb[c2 + 1]) v1 += cov::value<KERNEL>(p1, (T)wsn2);
+        }
+      }
     }
     if (SYM) {
-      if (KINDS) {  // the finished diagonal term of row `row` (only diagonal tiles read it)
+      if (KINDS || GROUPS) {  // the finished diagonal term of row `row` (only diagonal tiles read it)
         if (ti == tj && row < m) {
           const T da = w[row];
           if (row == col0) v0 += da;
@@ -201,6 +246,21 @@ void dispatch_d_k(const T* As, int64_t m, const T* Bs, int64_t n, int d, int64_t
     case 2: hipLaunchKernelGGL((kbuild_kernel<T, KERNEL, SYM, 2, false, true>), grid, block, 0, st, As, m, Bs, n, d, tiles_n, s, z, K, ld, diag, 0.0, 0.0, krow, kcol, ls, n_ls); break;
     case 3: hipLaunchKernelGGL((kbuild_kernel<T, KERNEL, SYM, 3, false, true>), grid, block, 0, st, As, m, Bs, n, d, tiles_n, s, z, K, ld, diag, 0.0, 0.0, krow, kcol, ls, n_ls); break;
     default: hipLaunchKernelGGL((kbuild_kernel<T, KERNEL, SYM, 0, false, true>), grid, block, 0, st, As, m, Bs, n, d, tiles_n, s, z, K, ld, diag, 0.0, 0.0, krow, kcol, ls, n_ls); break;
+  }
+}
+
+// the builds over observations with path ids (launch_kbuild_sym_g / launch_kbuild_cross_g)
+template <typename T, int KERNEL, bool SYM>
+void dispatch_d_g(const T* As, int64_t m, const T* Bs, int64_t n, int d, int64_t nblocks, int tiles_n, double sf2,
+                  const int32_t* grow, const int32_t* gcol, const double* q, double sg2, const T* diag, T* K, int64_t ld,
+                  hipStream_t st) {
+  dim3 grid((unsigned)nblocks), block(256);
+  const T s = (T)sf2, z = (T)0;
+  switch (d) {
+    case 1: hipLaunchKernelGGL((kbuild_kernel<T, KERNEL, SYM, 1, false, false, true>), grid, block, 0, st, As, m, Bs, n, d, tiles_n, s, z, K, ld, diag, sg2, 0.0, grow, gcol, q, d); break;
+    case 2: hipLaunchKernelGGL((kbuild_kernel<T, KERNEL, SYM, 2, false, false, true>), grid, block, 0, st, As, m, Bs, n, d, tiles_n, s, z, K, ld, diag, sg2, 0.0, grow, gcol, q, d); break;
+    case 3: hipLaunchKernelGGL((kbuild_kernel<T, KERNEL, SYM, 3, false, false, true>), grid, block, 0, st, As, m, Bs, n, d, tiles_n, s, z, K, ld, diag, sg2, 0.0, grow, gcol, q, d); break;
+    default: hipLaunchKernelGGL((kbuild_kernel<T, KERNEL, SYM, 0, false, false, true>), grid, block, 0, st, As, m, Bs, n, d, tiles_n, s, z, K, ld, diag, sg2, 0.0, grow, gcol, q, d); break;
   }
 }
 
@@ -286,6 +346,26 @@ void launch_kbuild_cross_k(int kernel, const T* As, int64_t m, int64_t mpad, con
   });
 }
 
+template <typename T>
+void launch_kbuild_sym_g(int kernel, const T* Xs, int64_t n, int64_t npad, int d, double sf2, const int32_t* group,
+                         const double* q, double sg2, const T* diag, T* K, int64_t ld, hipStream_t st) {
+  const int64_t TT = npad / KT;
+  const int64_t nblocks = TT * (TT + 1) / 2;
+  cov::dispatch(kernel, [&](auto fam) {
+    dispatch_d_g<T, fam, true>(Xs, n, Xs, n, d, nblocks, (int)TT, sf2, group, group, q, sg2, diag, K, ld, st);
+  });
+}
+
+template <typename T>
+void launch_kbuild_cross_g(int kernel, const T* As, const int32_t* group_a, int64_t m, int64_t mpad, const T* Bs,
+                           const int32_t* group_b, int64_t n, int64_t npad, int d, double sf2, const double* q, double sg2,
+                           T* K, int64_t ld, hipStream_t st) {
+  const int64_t tm = mpad / KT, tn = npad / KT;
+  cov::dispatch(kernel, [&](auto fam) {
+    dispatch_d_g<T, fam, false>(As, m, Bs, n, d, tm * tn, (int)tn, sf2, group_a, group_b, q, sg2, nullptr, K, ld, st);
+  });
+}
+
 #define GPX_INSTANTIATE_KBUILD(T)                                                                     \
   template void launch_scale_points<T>(const T*, int64_t, int64_t, int, const double*, int, T*,       \
                                        hipStream_t);                                                  \
@@ -298,6 +378,10 @@ void launch_kbuild_cross_k(int kernel, const T* As, int64_t m, int64_t mpad, con
   template void launch_kinds_diag<T>(const int32_t*, const T*, int64_t, double, double, double, T*, hipStream_t); \
   template void launch_kbuild_sym_k<T>(int, const T*, int64_t, int64_t, int, double, const int32_t*, const double*, int, \
                                        const T*, T*, int64_t, hipStream_t);                           \
+  template void launch_kbuild_sym_g<T>(int, const T*, int64_t, int64_t, int, double, const int32_t*, const double*, double, \
+                                       const T*, T*, int64_t, hipStream_t);                           \
+  template void launch_kbuild_cross_g<T>(int, const T*, const int32_t*, int64_t, int64_t, const T*, const int32_t*, int64_t, \
+                                         int64_t, int, double, const double*, double, T*, int64_t, hipStream_t); \
   template void launch_kbuild_cross_k<T>(int, const T*, int64_t, int64_t, const T*, int64_t, int64_t, int, double, \
                                          const int32_t*, const double*, int, T*, int64_t, hipStream_t);
 GPX_INSTANTIATE_KBUILD(double)

@@ -15,7 +15,10 @@
 //   block_score_kernel  one workgroup per block, fp64 whatever the element type: partials summed in slice order,
 //                       S = sf2 k(X_g, X_g) + diag_add I - Gram from the scaled queries (gpx_cov.h), Cholesky of S in
 //                       LDS, r = ys - mean, forward solve of the k columns, maha / logdet / logp.  A pivot that is not
-//                       > 0 makes the block's outputs NaN and lowers *bad to its 1-based index.
+//                       > 0 makes the block's outputs NaN and lowers *bad to its 1-based index.  On a fit with path ids
+//                       the block is a new path: S gains sg2 k(X_g, X_g; l_path).
+//   block_forecast_kernel  gpx_forecast_blocks: the same S for Lo observed + Lp forecast rows, the same Cholesky stopped
+//                       after Lo columns, one Schur update (built from the same device functions).
 //
 // LDS row slab: row stride 66 doubles (= 2 mod 32), so the 16 rows x 2 columns a half-wave reads for one MFMA operand
 // (ds_read_b64, 64 four-byte banks) fall on 32 distinct bank pairs.
@@ -132,20 +135,16 @@ __device__ __forceinline__ double quad_sum(double v) {
   return v;
 }
 
+// ---- the device code block_score_kernel and block_forecast_kernel share ----------------------------------------------------
+
+// Lower triangle of S (Lg x Lg, stride SLD) of the block whose first row is row0: sf2 k + [sg2 k(., .; l_path)] - Gram, the
+// partials summed in slice order; + diag_add (times wq[i] if given) on the diagonal of the rows i < nd.  sg2 > 0 (a fit with
+// path ids: the block is a new path) adds the within-path term from the scaled queries with q_c = (l_c / l_path,c)^2.
 template <typename T, int KERNEL>
-__global__ __launch_bounds__(256) void block_score_kernel(const double* __restrict__ part, int S, int LP,
-                                                         const T* __restrict__ Qs, int d, const T* __restrict__ ys,
-                                                         const T* __restrict__ mean, int k, int Lg, double sf2,
-                                                         double diag_add, T* __restrict__ logp, T* __restrict__ maha,
-                                                         T* __restrict__ logdet, int64_t g0, int* __restrict__ bad,
-                                                         const T* __restrict__ wq) {
-  __shared__ double Sm[64 * SLD];  // S, then its Cholesky factor (lower)
-  __shared__ double Wm[64 * SLD];  // residuals r (Lg x k), then L^-1 r
-  __shared__ double piv;
-  const int tid = threadIdx.x;
-  const int64_t b = blockIdx.x, row0 = b * Lg;
-  const double* pb = part + b * S * (int64_t)(LP * LP);
-  for (int e = tid; e < Lg * Lg; e += 256) {
+__device__ __forceinline__ void block_build_s(double* Sm, const double* pb, int S, int LP, const T* __restrict__ Qs,
+                                              int64_t row0, int d, int Lg, int nd, double sf2, double sg2,
+                                              const double* __restrict__ q, double diag_add, const T* __restrict__ wq) {
+  for (int e = threadIdx.x; e < Lg * Lg; e += 256) {
     const int i = e / Lg, j = e - i * Lg;
     if (j > i) continue;
     double gram = 0.0;
@@ -156,66 +155,158 @@ __global__ __launch_bounds__(256) void block_score_kernel(const double* __restri
       r2 += df * df;
     }
     double v = cov::value<KERNEL, double>(r2, sf2);
-    if (i == j) v += wq ? diag_add * (double)wq[row0 + i] : diag_add;  // per-point weight of the added diagonal
+    if (sg2 > 0.0) {  // (the same for every thread)
+      double rp2 = 0.0;
+      for (int c = 0; c < d; ++c) {
+        const double df = (double)Qs[(row0 + i) * d + c] - (double)Qs[(row0 + j) * d + c];
+        rp2 += q[c] * (df * df);
+      }
+      v += cov::value<KERNEL, double>(rp2, sg2);
+    }
+    if (i == j && i < nd) v += wq ? diag_add * (double)wq[row0 + i] : diag_add;  // per-point weight of the added diagonal
     Sm[i * SLD + j] = v - gram;
   }
-  for (int e = tid; e < Lg * k; e += 256) {
-    const int i = e / k, c = e - i * k;
-    Wm[i * SLD + c] = (double)ys[row0 * k + e] - (double)mean[row0 * k + e];
-  }
-  __syncthreads();
+}
 
-  // left-looking Cholesky: row ci of column j by the four lanes of a quad (the contraction index dealt mod 4)
-  const int ci = tid >> 2, q = tid & 3;
-  bool ok = true;
-  double half_logdet = 0.0;
-  for (int j = 0; j < Lg; ++j) {
+// Left-looking Cholesky of the columns j < nc over ALL Lg rows: row ci of column j by the four lanes of a quad (the
+// contraction index dealt mod 4).  nc == Lg: the factor of S.  nc < Lg: L_oo in the leading nc x nc block,
+// B = S_po L_oo^-T in the rows below it, the trailing block untouched.  false: a pivot was not > 0 (the same for every thread).
+__device__ __forceinline__ bool block_chol_cols(double* Sm, int Lg, int nc, double* piv, double& half_logdet) {
+  const int tid = threadIdx.x, ci = tid >> 2, q = tid & 3;
+  for (int j = 0; j < nc; ++j) {
     const bool mine = ci >= j && ci < Lg;
     double acc = 0.0;
     if (mine)
       for (int p = q; p < j; p += 4) acc += Sm[ci * SLD + p] * Sm[j * SLD + p];
     acc = quad_sum(acc);
     const double v = mine ? Sm[ci * SLD + j] - acc : 0.0;
-    if (ci == j && q == 0) piv = v;
+    if (ci == j && q == 0) *piv = v;
     __syncthreads();
-    const double dj = piv;
-    if (!(dj > 0.0)) {  // the same for every thread
-      ok = false;
-      break;
-    }
+    const double dj = *piv;
+    if (!(dj > 0.0)) return false;
     const double lj = sqrt(dj);
     if (mine && q == 0) Sm[ci * SLD + j] = ci == j ? lj : v / lj;
     half_logdet += log(lj);
     __syncthreads();
   }
+  return true;
+}
 
-  // w = L^-1 r: column ci by the lanes of quad ci (all in one wave)
+// w = L^-1 r for the leading n x n block of the factor: column ci by the lanes of quad ci (all in one wave); returns this
+// thread's |w_ci|^2 (ci < k)
+__device__ __forceinline__ double block_forward(const double* Sm, double* Wm, int n, int k) {
+  const int tid = threadIdx.x, ci = tid >> 2, q = tid & 3;
   double mh = 0.0;
-  if (ok) {
-    for (int i = 0; i < Lg; ++i) {
-      double acc = 0.0;
-      if (ci < k)
-        for (int p = q; p < i; p += 4) acc += Sm[i * SLD + p] * Wm[p * SLD + ci];
-      acc = quad_sum(acc);
-      double w = 0.0;
-      if (ci < k) {
-        w = (Wm[i * SLD + ci] - acc) / Sm[i * SLD + i];
-        mh += w * w;
-      }
-      if (ci < k && q == 0) Wm[i * SLD + ci] = w;
-      __syncthreads();
+  for (int i = 0; i < n; ++i) {
+    double acc = 0.0;
+    if (ci < k)
+      for (int p = q; p < i; p += 4) acc += Sm[i * SLD + p] * Wm[p * SLD + ci];
+    acc = quad_sum(acc);
+    double w = 0.0;
+    if (ci < k) {
+      w = (Wm[i * SLD + ci] - acc) / Sm[i * SLD + i];
+      mh += w * w;
     }
+    if (ci < k && q == 0) Wm[i * SLD + ci] = w;
+    __syncthreads();
   }
+  return mh;
+}
+
+constexpr double LOG_2PI = 1.83787706640934548356065947281;
+
+template <typename T, int KERNEL>
+__global__ __launch_bounds__(256) void block_score_kernel(const double* __restrict__ part, int S, int LP,
+                                                         const T* __restrict__ Qs, int d, const T* __restrict__ ys,
+                                                         const T* __restrict__ mean, int k, int Lg, double sf2,
+                                                         double diag_add, T* __restrict__ logp, T* __restrict__ maha,
+                                                         T* __restrict__ logdet, int64_t g0, int* __restrict__ bad,
+                                                         const T* __restrict__ wq, double sg2,
+                                                         const double* __restrict__ q) {
+  __shared__ double Sm[64 * SLD];  // S, then its Cholesky factor (lower)
+  __shared__ double Wm[64 * SLD];  // residuals r (Lg x k), then L^-1 r
+  __shared__ double piv;
+  const int tid = threadIdx.x;
+  const int64_t b = blockIdx.x, row0 = b * Lg;
+  block_build_s<T, KERNEL>(Sm, part + b * S * (int64_t)(LP * LP), S, LP, Qs, row0, d, Lg, Lg, sf2, sg2, q, diag_add, wq);
+  for (int e = tid; e < Lg * k; e += 256) {
+    const int i = e / k, c = e - i * k;
+    Wm[i * SLD + c] = (double)ys[row0 * k + e] - (double)mean[row0 * k + e];
+  }
+  __syncthreads();
+
+  const int ci = tid >> 2, qd = tid & 3;
+  double half_logdet = 0.0;
+  const bool ok = block_chol_cols(Sm, Lg, Lg, &piv, half_logdet);
+  double mh = 0.0;
+  if (ok) mh = block_forward(Sm, Wm, Lg, k);
   const double nan = __builtin_nan("");
   const int64_t g = g0 + b;
-  if (ci < k && q == 0) {
+  if (ci < k && qd == 0) {
     maha[g * k + ci] = (T)(ok ? mh : nan);
-    logp[g * k + ci] = (T)(ok ? -0.5 * mh - half_logdet - 0.5 * Lg * 1.83787706640934548356065947281 : nan);
+    logp[g * k + ci] = (T)(ok ? -0.5 * mh - half_logdet - 0.5 * Lg * LOG_2PI : nan);
   }
   if (tid == 0) {
     logdet[g] = (T)(ok ? 2.0 * half_logdet : nan);
     if (!ok) atomicMin(bad, (int)(g + 1));
   }
+}
+
+// gpx_forecast_blocks: one workgroup per block of Lo observed rows, then Lp rows to forecast (Lg = Lo + Lp <= 64).  The score
+// kernel stopped after Lo columns plus one Schur update: the joint S with diag_add on the observed rows only, the Cholesky
+// of its first Lo columns over all rows (L_oo and B = S_po L_oo^-T in place), w = L_oo^-1 (yo - mean_o), then
+//   fmean = mean_p + B w,   fcov = S_pp - B B^T (the lower triangle computed, both halves written),   fvar = diag(fcov),
+//   flogp = the joint log-density of the observed rows (what block_score_kernel gives for them alone).
+// Every sum runs in index order inside one thread (or one quad): nothing depends on G, the position or the batch.
+template <typename T, int KERNEL>
+__global__ __launch_bounds__(256) void block_forecast_kernel(const double* __restrict__ part, int S, int LP,
+                                                            const T* __restrict__ Qs, int d, const T* __restrict__ yo,
+                                                            const T* __restrict__ mean, int k, int Lo, int Lp, double sf2,
+                                                            double sg2, const double* __restrict__ q, double diag_add,
+                                                            T* __restrict__ fmean, T* __restrict__ fcov,
+                                                            T* __restrict__ fvar, T* __restrict__ flogp, int64_t g0,
+                                                            int* __restrict__ bad) {
+  __shared__ double Sm[64 * SLD];  // S; then L_oo, B below it, S_pp
+  __shared__ double Wm[64 * SLD];  // rows < Lo: yo - mean_o, then w; rows >= Lo: mean_p
+  __shared__ double piv;
+  const int tid = threadIdx.x, Lg = Lo + Lp;
+  const int64_t b = blockIdx.x, row0 = b * Lg;
+  block_build_s<T, KERNEL>(Sm, part + b * S * (int64_t)(LP * LP), S, LP, Qs, row0, d, Lg, Lo, sf2, sg2, q, diag_add,
+                           (const T*)nullptr);
+  for (int e = tid; e < Lg * k; e += 256) {
+    const int i = e / k, c = e - i * k;
+    const double m = (double)mean[row0 * k + e];
+    Wm[i * SLD + c] = i < Lo ? (double)yo[b * Lo * k + e] - m : m;
+  }
+  __syncthreads();
+
+  const int ci = tid >> 2, qd = tid & 3;
+  double half_logdet = 0.0;
+  const bool ok = block_chol_cols(Sm, Lg, Lo, &piv, half_logdet);
+  double mh = 0.0;
+  if (ok) mh = block_forward(Sm, Wm, Lo, k);
+  const double nan = __builtin_nan("");
+  const int64_t g = g0 + b;
+  for (int e = tid; e < Lp * k; e += 256) {
+    const int i = e / k, c = e - i * k;
+    double acc = Wm[(Lo + i) * SLD + c];
+    for (int p = 0; p < Lo; ++p) acc += Sm[(Lo + i) * SLD + p] * Wm[p * SLD + c];
+    fmean[(g * Lp + i) * k + c] = (T)(ok ? acc : nan);
+  }
+  for (int e = tid; e < Lp * Lp; e += 256) {
+    const int i = e / Lp, j = e - i * Lp;
+    if (j > i) continue;
+    double acc = Sm[(Lo + i) * SLD + Lo + j];
+    for (int p = 0; p < Lo; ++p) acc -= Sm[(Lo + i) * SLD + p] * Sm[(Lo + j) * SLD + p];
+    const T v = (T)(ok ? acc : nan);
+    if (fcov) {
+      fcov[(g * Lp + i) * Lp + j] = v;
+      fcov[(g * Lp + j) * Lp + i] = v;
+    }
+    if (fvar && i == j) fvar[g * Lp + i] = v;
+  }
+  if (flogp && ci < k && qd == 0) flogp[g * k + ci] = (T)(ok ? -0.5 * mh - half_logdet - 0.5 * Lo * LOG_2PI : nan);
+  if (tid == 0 && !ok) atomicMin(bad, (int)(g + 1));
 }
 
 }  // namespace
@@ -241,19 +332,35 @@ void launch_block_gram(const T* VT, int64_t ld, int64_t nblk, int Lg, int64_t np
 template <typename T>
 void launch_block_score(int kernel, const double* part, int64_t nblk, int Lg, int64_t npad, const T* Qs, int d,
                         const T* ys, const T* mean, int k, double sf2, double diag_add, T* logp, T* maha, T* logdet,
-                        int64_t g0, int* bad, hipStream_t st, const T* wq) {
+                        int64_t g0, int* bad, hipStream_t st, const T* wq, double sg2, const double* q) {
   debug_delay(st);
   const int S = score_slices(npad), LP = score_lp(Lg);
   cov::dispatch(kernel, [&](auto fam) {
     hipLaunchKernelGGL((block_score_kernel<T, fam>), dim3((unsigned)nblk), dim3(256), 0, st, part, S, LP, Qs, d, ys, mean,
-                       k, Lg, sf2, diag_add, logp, maha, logdet, g0, bad, wq);
+                       k, Lg, sf2, diag_add, logp, maha, logdet, g0, bad, wq, sg2, q);
+  });
+}
+
+template <typename T>
+void launch_block_forecast(int kernel, const double* part, int64_t nblk, int Lo, int Lp, int64_t npad, const T* Qs, int d,
+                           const T* yo, const T* mean, int k, double sf2, double sg2, const double* q, double diag_add,
+                           T* fmean, T* fcov, T* fvar, T* flogp, int64_t g0, int* bad, hipStream_t st) {
+  debug_delay(st);
+  const int S = score_slices(npad), LP = score_lp(Lo + Lp);
+  cov::dispatch(kernel, [&](auto fam) {
+    hipLaunchKernelGGL((block_forecast_kernel<T, fam>), dim3((unsigned)nblk), dim3(256), 0, st, part, S, LP, Qs, d, yo,
+                       mean, k, Lo, Lp, sf2, sg2, q, diag_add, fmean, fcov, fvar, flogp, g0, bad);
   });
 }
 
 #define GPX_INSTANTIATE_SCORE(T)                                                                                       \
   template void launch_block_gram<T>(const T*, int64_t, int64_t, int, int64_t, double*, hipStream_t);                 \
   template void launch_block_score<T>(int, const double*, int64_t, int, int64_t, const T*, int, const T*, const T*,  \
-                                      int, double, double, T*, T*, T*, int64_t, int*, hipStream_t, const T*);
+                                      int, double, double, T*, T*, T*, int64_t, int*, hipStream_t, const T*, double,  \
+                                      const double*);                                                                  \
+  template void launch_block_forecast<T>(int, const double*, int64_t, int, int, int64_t, const T*, int, const T*,      \
+                                         const T*, int, double, double, const double*, double, T*, T*, T*, T*, int64_t, \
+                                         int*, hipStream_t);
 GPX_INSTANTIATE_SCORE(double)
 GPX_INSTANTIATE_SCORE(float)
 

@@ -24,6 +24,37 @@ def _is_torch(x) -> bool:
     return type(x).__module__.split(".")[0] == "torch"
 
 
+def check_path_args(path_ids, path_variance, path_lengthscale, n=None, d=None, derivatives=None):
+    """Validation of ``fit(..., path_ids=, path_variance=, path_lengthscale=)`` -> ``(ids, variance, lengthscale)``: ``ids``
+    None or a contiguous (N,) int32 array, ``lengthscale`` None (the model's own) or a 1-D float64 array.  Raises
+    ``ValueError`` for ids that are not one integer >= -1 per observation, a negative or non-finite variance, a
+    lengthscale that is not positive (or has neither 1 nor d entries), and for path ids together with ``derivatives``."""
+    var = float(path_variance)
+    if not np.isfinite(var) or var < 0:
+        raise ValueError("path_variance must be finite and >= 0")
+    lsp = None
+    if path_lengthscale is not None:
+        lsp = np.atleast_1d(np.asarray(path_lengthscale, dtype=np.float64)).copy()
+        if lsp.ndim != 1 or lsp.size == 0 or not np.all(np.isfinite(lsp)) or not np.all(lsp > 0):
+            raise ValueError("path_lengthscale must be a positive scalar or 1-D array")
+        if d is not None and lsp.size not in (1, d):
+            raise ValueError("path_lengthscale must be scalar or have d entries")
+    if path_ids is None:
+        return None, var, lsp
+    if derivatives is not None:
+        raise ValueError("path_ids cannot be combined with derivatives=: no builder evaluates both")
+    if _is_torch(path_ids):
+        path_ids = path_ids.detach().cpu().numpy()
+    ids = np.asarray(path_ids)
+    if ids.ndim != 1 or (n is not None and ids.shape[0] != n):
+        raise ValueError("path_ids must be (N,), one id per observation")
+    if not np.issubdtype(ids.dtype, np.integer):
+        raise ValueError("path_ids must be integers")
+    if ids.size and (ids.min() < -1 or ids.max() > np.iinfo(np.int32).max):
+        raise ValueError("path_ids must be >= 0, or -1 for an observation that belongs to no path")
+    return np.ascontiguousarray(ids, dtype=np.int32), var, lsp
+
+
 class GP:
     """Exact GP regressor on one MI355X (or a row-block shard of several).
 
@@ -130,6 +161,9 @@ class GP:
         self._weights_set = False  # gpx_set_noise_weights holds a vector for the next fits
         self._kinds_set = False    # gpx_set_observation_kinds holds kinds for the next fits
         self.derivative_noise = 0.0  # noise variance of the derivative rows of the last fit(derivatives=) (0 without any)
+        self._groups_set = False   # gpx_set_path_groups holds path ids for the next fits
+        self.path_variance = 0.0   # within-path variance sg2 of the last fit(path_ids=) (0 without any)
+        self.path_lengthscale = None  # ... and its lengthscale(s) (None without path ids)
         self._alpha = None
         self.info_ = 0
         self.jitter_used_ = self.jitter
@@ -258,6 +292,31 @@ class GP:
                                                         float(derivative_noise), _abi.MEM_HOST))
         self._kinds_set = True
 
+    def _set_path_groups(self, ids, variance, lengthscale):
+        """the path ids of the fits that follow (``gpx_set_path_groups``); None clears them"""
+        if ids is None:
+            if self._groups_set:
+                self._check(self._lib.gpx_set_path_groups(self._h, None, 0, 0.0, None, 0, _abi.MEM_HOST))
+                self._groups_set = False
+            self.path_variance, self.path_lengthscale = 0.0, None
+            return  # (a model that never had path ids makes no call at all)
+        lsp = self.lengthscale if lengthscale is None else lengthscale
+        lsp = np.ascontiguousarray(lsp, dtype=np.float64)
+        self._check(self._lib.gpx_set_path_groups(self._h, C.c_void_p(ids.ctypes.data), ids.size, float(variance),
+                                                  _abi.dptr(lsp), lsp.size, _abi.MEM_HOST))
+        self._groups_set = True
+        self.path_variance, self.path_lengthscale = float(variance), lsp.copy()
+
+    @property
+    def path_ids_(self):
+        """Path id of every observation of the fitted model (N,) int32; all -1 for a fit without path ids (or with
+        ``path_variance == 0``, which is the plain model)."""
+        if not self._fitted:
+            raise RuntimeError("no fit")
+        out = np.empty((self._N,), dtype=np.int32)
+        self._check(self._lib.gpx_get_path_groups(self._h, C.c_void_p(out.ctypes.data)))
+        return out
+
     def _with_derivatives(self, X, y, derivatives, noise_weights=None):
         """``(X, y, noise_weights, kinds)`` of a fit: without ``derivatives`` the arguments as they are and no kinds;
         with ``derivatives = (Xd, dims, yd)`` the value rows first and the derivative rows last, ``kinds`` (N + Nd,)
@@ -310,7 +369,8 @@ class GP:
         return out
 
     # -- API ----------------------------------------------------------------------------
-    def fit(self, X, y, noise_weights=None, derivatives=None, derivative_noise=0.0):
+    def fit(self, X, y, noise_weights=None, derivatives=None, derivative_noise=0.0, path_ids=None, path_variance=0.0,
+            path_lengthscale=None):
         """Factorise and solve.  ``noise_weights`` (N,), of the same kind as ``X`` (NumPy array or device tensor): the
         diagonal of K gets ``noise * w_i + jitter`` instead of ``noise + jitter``; None (the default) means none — also
         after a weighted fit.
@@ -323,11 +383,23 @@ class GP:
         this velocity").  The model then holds the N value rows followed by the Nd
         derivative rows (``alpha_``, ``observation_kinds_``, ``noise_weights_``); ``noise_weights`` may have length N
         (derivative rows get 1) or N + Nd.  RBF, Matern-5/2 and Matern-3/2 on one device, float64 / float32; None (the
-        default) means none — also after such a fit."""
-        X, y, noise_weights, kinds = self._with_derivatives(X, y, derivatives, noise_weights)
-        return self._fit_rows(X, y, noise_weights, kinds, derivative_noise)
+        default) means none — also after such a fit.
 
-    def _fit_rows(self, X, y, noise_weights, kinds, derivative_noise):
+        ``path_ids`` (N,) ints (NumPy array or tensor) fit the hierarchical model ``y_p(t) = f(t) + g_p(t) + noise``
+        (``gpx_set_path_groups``): observations with the same id >= 0 belong to one path and share a deviation ``g_p``,
+        a GP of the model's covariance family with variance ``path_variance`` and lengthscale ``path_lengthscale`` (None:
+        the model's ``lengthscale``), independent between paths; id -1 is an observation of ``f`` alone.  EVERY
+        PREDICTION (:meth:`predict`, ``return_cov``, :meth:`predict_gradient`, :meth:`sample_y`) IS THEN THE POSTERIOR OF
+        THE CLUSTER MEAN ``f``; :meth:`score_blocks` scores each block as a new path (``+ path_variance k(., .;
+        path_lengthscale)``) and :meth:`forecast_blocks` forecasts one from its first points.  The attributes
+        ``path_variance``, ``path_lengthscale`` and ``path_ids_`` keep what the fit used.  ``path_variance=0`` or ids that
+        are all -1 are the plain fit bit for bit; None (the default) means none — also after such a fit.  float64 /
+        float32 on one device, not with ``derivatives``; :meth:`update` and :meth:`lml_gradient` refuse such a fit."""
+        ids, pvar, plsp = check_path_args(path_ids, path_variance, path_lengthscale, derivatives=derivatives)
+        X, y, noise_weights, kinds = self._with_derivatives(X, y, derivatives, noise_weights)
+        return self._fit_rows(X, y, noise_weights, kinds, derivative_noise, (ids, pvar, plsp))
+
+    def _fit_rows(self, X, y, noise_weights, kinds, derivative_noise, paths=(None, 0.0, None)):
         """:meth:`fit` of observation rows that are concatenated already, ``kinds`` (None: all values) theirs"""
         px, kx, keepx, devx, sx = self._as_input(X, "X")
         py, ky, keepy, devy, sy = self._as_input(y, "y")
@@ -341,8 +413,13 @@ class GP:
         k = 1 if len(sy) == 1 else sy[1]
         if self.lengthscale.size not in (1, d):
             raise ValueError("lengthscale must be scalar or have d entries")
+        if paths[0] is not None and paths[0].shape[0] != N:
+            raise ValueError(f"path_ids must be ({N},), one id per observation")
+        if paths[2] is not None and paths[2].size not in (1, d):
+            raise ValueError("path_lengthscale must be scalar or have d entries")
         self._set_noise_weights(noise_weights, N, kx)  # (refused: the model is as it was)
         self._set_observation_kinds(kinds, derivative_noise)
+        self._set_path_groups(*paths)
         self.derivative_noise = 0.0 if kinds is None else float(derivative_noise)
         self._y1d = len(sy) == 1
         self._N, self._d, self._k = N, d, k
@@ -420,19 +497,22 @@ class GP:
         self._check(self._lib.gpx_reserve(self._h, int(n)))
         return self
 
-    def fit_predict(self, X, y, Xs, include_noise=False, noise_weights=None, derivatives=None, derivative_noise=0.0):
+    def fit_predict(self, X, y, Xs, include_noise=False, noise_weights=None, derivatives=None, derivative_noise=0.0,
+                    path_ids=None, path_variance=0.0, path_lengthscale=None):
         """``fit(X, y)`` and ``predict(Xs)`` (mean and variance) as ONE factorisation pass: the cross-kernel rows
         of the query points ride through the blocked Cholesky as bordered rows (``gpx_fit_predict``), so the
         variance solve is part of the trailing updates instead of a pass of its own — the small-N schedule
         (N = 8192: the updates' idle CUs take the work).  The model is fitted afterwards as after ``fit``.
         On a shard or a device group every rank's slice of the query points rides through ITS part of the sharded
         factorisation (collective: every rank of a shard makes the call).  ``dtype="mixed"`` takes the two calls.
-        ``noise_weights``, ``derivatives`` and ``derivative_noise`` as for :meth:`fit`; ``include_noise`` as for
-        :meth:`predict`."""
+        ``noise_weights``, ``derivatives``, ``derivative_noise`` and the ``path_*`` keywords as for :meth:`fit` (with
+        path ids the prediction is the posterior of the cluster mean ``f``); ``include_noise`` as for :meth:`predict`."""
+        paths = check_path_args(path_ids, path_variance, path_lengthscale, derivatives=derivatives)
         X, y, noise_weights, kinds = self._with_derivatives(X, y, derivatives, noise_weights)
 
         def two_calls():
-            return self._fit_rows(X, y, noise_weights, kinds, derivative_noise).predict(Xs, include_noise=include_noise)
+            return self._fit_rows(X, y, noise_weights, kinds, derivative_noise, paths).predict(
+                Xs, include_noise=include_noise)
 
         fused = self.dtype in ("float64", "float32")
         pq, kq, keepq, devq, sq = self._as_input(Xs, "Xs")
@@ -451,8 +531,13 @@ class GP:
         if self.lengthscale.size not in (1, d):
             raise ValueError("lengthscale must be scalar or have d entries")
         M = sq[0]
+        if paths[0] is not None and paths[0].shape[0] != N:
+            raise ValueError(f"path_ids must be ({N},), one id per observation")
+        if paths[2] is not None and paths[2].size not in (1, d):
+            raise ValueError("path_lengthscale must be scalar or have d entries")
         self._set_noise_weights(noise_weights, N, kx)
         self._set_observation_kinds(kinds, derivative_noise)
+        self._set_path_groups(*paths)
         self._y1d = len(sy) == 1
         self._N, self._d, self._k = N, d, k
         self._alpha = None
@@ -474,7 +559,7 @@ class GP:
         for _ in range(max(1, self.max_tries)):
             rc = self._lib.gpx_fit_predict(self._h, px, py, N, d, k, _abi.dptr(ls), ls.size, self.variance, self.noise,
                                            jitter, pq, M, pm, pv, kx, C.byref(info))
-            if rc == _abi.E_NOMEM or (rc == _abi.E_UNSUPPORTED and kinds is None):
+            if rc == _abi.E_NOMEM or (rc == _abi.E_UNSUPPORTED and kinds is None and paths[0] is None):
                 # the library's own limits decide (its batch cap honours GPX_PRED_BATCH; M more bordered rows of K and
                 # of the panel buffers may not fit beside the factor): the documented fallback is the two calls
                 # (with kinds set, GPX_E_UNSUPPORTED is the refusal of the model itself: raised below)
@@ -576,7 +661,10 @@ class GP:
         first such block; ``on_bad="nan"`` returns the arrays instead, that block's entries NaN and
         ``score_info_`` its 1-based index.  ``noise_weights`` (G * block,), of the same kind as ``Xs``: query point i
         gets ``noise * w_i`` on the diagonal instead of ``noise`` (``gpx_score_blocks_weighted``; nothing without
-        ``include_noise``).  NumPy in, NumPy out; device tensors in, device tensors out."""
+        ``include_noise``).  On a model fitted with ``path_ids`` every block is a NEW path of the hierarchical model: its
+        covariance is the posterior of ``f`` plus ``path_variance k(., .; path_lengthscale)``, so a path that runs beside
+        the cluster mean is one deviation, not ``block`` independent surprises.  NumPy in, NumPy out; device tensors in,
+        device tensors out."""
         if not self._fitted:
             raise RuntimeError("score_blocks() before a successful fit()")
         if on_bad not in ("raise", "nan"):
@@ -620,6 +708,68 @@ class GP:
                 f"block {self.score_info_ - 1} (the first of its kind) has a joint posterior covariance that is not "
                 f"positive definite; score with include_noise=True or on_bad='nan'")
         return (logp, maha, logdet) if return_parts else logp
+
+    def forecast_blocks(self, Xo, yo, Xp, blocks=None, include_noise=True, return_cov=True, return_logp=False,
+                        on_bad="raise"):
+        """Forecast of partly observed new paths (``gpx_forecast_blocks``): ``Xo`` (G * Lo, d) holds the Lo observed
+        points of each of G paths, ``yo`` their targets ((G * Lo,) for a 1-D ``y``, else (G * Lo, k)), ``Xp`` (G * Lp, d)
+        the Lp points to forecast per path; ``blocks`` = G (None: one path), Lo + Lp <= 64.  Each path is a new draw of
+        the model — the posterior of ``f`` plus, on a fit with ``path_ids``, its own deviation ``g`` — conditioned on
+        its observed points (``noise`` on their diagonal with ``include_noise``).  Returns ``(mean, cov)``: the forecast
+        mean ((G * Lp,) or (G * Lp, k)) and the latent joint covariance (G, Lp, Lp), shared by the targets; with
+        ``return_cov=False`` ``(mean, var)``, ``var`` (G * Lp,) its diagonal; with ``return_logp`` a third entry, the
+        joint log-density of each observed prefix ((G,) or (G, k): :meth:`score_blocks` of those points).  A path whose
+        conditioning matrix is not positive definite raises ``numpy.linalg.LinAlgError``; ``on_bad="nan"`` returns NaN
+        for it instead and ``forecast_info_`` its 1-based index.  NumPy in, NumPy out; device tensors in, device tensors
+        out."""
+        if not self._fitted:
+            raise RuntimeError("forecast_blocks() before a successful fit()")
+        if on_bad not in ("raise", "nan"):
+            raise ValueError("on_bad must be 'raise' or 'nan'")
+        G = 1 if blocks is None else int(blocks)
+        if G < 1:
+            raise ValueError("blocks must be >= 1")
+        po, ko, keepo, devo, so = self._as_input(Xo, "Xo")
+        py, ky, keepy, devy, sy = self._as_input(yo, "yo")
+        pp, kp, keepp, devp, sp = self._as_input(Xp, "Xp")
+        if len(so) != 2 or so[1] != self._d or len(sp) != 2 or sp[1] != self._d:
+            raise ValueError(f"Xo must be (G * Lo, {self._d}) and Xp (G * Lp, {self._d})")
+        if so[0] == 0 or sp[0] == 0 or so[0] % G or sp[0] % G:
+            raise ValueError(f"Xo and Xp must hold {G} whole blocks each, have {so[0]} and {sp[0]} rows")
+        Lo, Lp = so[0] // G, sp[0] // G
+        if Lo + Lp > 64:
+            raise ValueError(f"a block has Lo + Lp = {Lo} + {Lp} points, at most 64")
+        if self._y1d:
+            ok = len(sy) == 1 or (len(sy) == 2 and sy[1] == 1)
+        else:
+            ok = len(sy) == 2 and sy[1] == self._k
+        if not ok or sy[0] != G * Lo:
+            raise ValueError("yo must be (G * Lo,)" if self._y1d else f"yo must be (G * Lo, {self._k})")
+        if not (ko == ky == kp):
+            raise ValueError("Xo, yo and Xp must all be host arrays or all be device tensors")
+        d = self._d
+        if devo is not None:  # each block: its observed points, then its points to forecast
+            import torch
+            Xb = torch.cat([keepo.reshape(G, Lo, d), keepp.reshape(G, Lp, d)], dim=1).reshape(G * (Lo + Lp), d).contiguous()
+            torch.cuda.current_stream(devo).synchronize()
+        else:
+            Xb = np.ascontiguousarray(np.concatenate([keepo.reshape(G, Lo, d), keepp.reshape(G, Lp, d)], axis=1)
+                                      .reshape(G * (Lo + Lp), d))
+        mean = self._empty((G * Lp,) if self._y1d else (G * Lp, self._k), devo)
+        cov = self._empty((G, Lp, Lp), devo) if return_cov else None
+        var = None if return_cov else self._empty((G * Lp,), devo)
+        logp = self._empty((G,) if self._y1d else (G, self._k), devo) if return_logp else None
+        p = lambda a: None if a is None else self._ptr(a)  # noqa: E731
+        info = C.c_int64(0)
+        self._check(self._lib.gpx_forecast_blocks(self._h, self._ptr(Xb), py, G, Lo, Lp, self.noise if include_noise else 0.0,
+                                                  p(mean), p(cov), p(var), p(logp), ko, C.byref(info)))
+        self.forecast_info_ = int(info.value)
+        if self.forecast_info_ and on_bad == "raise":
+            raise np.linalg.LinAlgError(
+                f"block {self.forecast_info_ - 1} (the first of its kind) has a conditioning matrix that is not positive "
+                f"definite; forecast with include_noise=True or on_bad='nan'")
+        out = (mean, cov if return_cov else var)
+        return out + (logp,) if return_logp else out
 
     def _empty(self, shape, dev):
         """uninitialised output of the model's element type: on the device `dev` (torch), or NumPy when None"""
@@ -691,13 +841,20 @@ class GP:
         The training data and the factor are NOT included — the factor is N^2 numbers the GPU
         rebuilds faster than storage returns them, and the path is deterministic:
         ``GP.from_state(s).fit(X, y)`` reproduces alpha, mean and variance bit for bit (tested),
-        so a hyper-parameter search is resumed by saving this after every ``optimize`` step."""
+        so a hyper-parameter search is resumed by saving this after every ``optimize`` step.  ``path_variance`` and
+        ``path_lengthscale`` of a model fitted with ``path_ids`` are recorded under ``"fitted"``, but they are arguments of
+        :meth:`fit`, as the ids are: resume such a model with ``GP.from_state(s).fit(X, y, path_ids=ids,
+        path_variance=s["fitted"]["path_variance"], path_lengthscale=s["fitted"]["path_lengthscale"])`` — without them
+        the fit is the plain model."""
         st = {"format": 1, "kernel": self.kernel, "lengthscale": [float(v) for v in self.lengthscale],
               "variance": self.variance, "noise": self.noise, "jitter": self.jitter, "dtype": self.dtype,
               "block": self.block, "max_tries": self.max_tries, "refine": self.refine}
         if self._fitted:
             st["fitted"] = {"N": int(self._N), "d": int(self._d), "k": int(self._k),
                             "jitter_used": float(self.jitter_used_), "log_det": float(self.log_det_)}
+            if self.path_lengthscale is not None:
+                st["fitted"].update(path_variance=float(self.path_variance),
+                                    path_lengthscale=[float(v) for v in self.path_lengthscale])
         return st
 
     @classmethod
@@ -780,7 +937,8 @@ class GP:
         return float(lml.value), grad
 
     def optimize(self, X, y, params=("lengthscale", "variance", "noise"), bounds=(1e-4, 1e4), maxiter=40,
-                 rel_step=1e-4, jac="analytic", noise_weights=None, derivatives=None, derivative_noise=0.0):
+                 rel_step=1e-4, jac="analytic", noise_weights=None, derivatives=None, derivative_noise=0.0,
+                 path_ids=None, path_variance=0.0, path_lengthscale=None):
         """Fit the hyper-parameters by maximising the log marginal likelihood (SURVEY.md §8f
         rank 1: the natural step after ``fit``; the reference has no counterpart).
 
@@ -797,11 +955,25 @@ class GP:
         ``lml_gradient(derivative_noise=True)``, at the same cost.  ``params`` may then also name ``"derivative_noise"``:
         the noise variance of the derivative observations is learnt with the others, starting from the value passed,
         and the attribute ``derivative_noise`` holds the result (``ValueError`` without ``derivatives`` or when it starts
-        at 0: log-space cannot leave 0).  Left out of ``params`` it stays fixed."""
+        at 0: log-space cannot leave 0).  Left out of ``params`` it stays fixed.
+
+        ``path_ids``, ``path_variance`` and ``path_lengthscale`` as for :meth:`fit`.  A model with path ids has no
+        analytic gradient yet, so the search then runs on central differences; ``params`` may name ``"path_variance"``
+        (which must start above 0) and ``"path_lengthscale"`` (every entry moves), and the attributes of those names
+        hold the result."""
         from scipy.optimize import minimize
-        names = [p for p in ("lengthscale", "variance", "noise", "derivative_noise") if p in params]
+        known = ("lengthscale", "variance", "noise", "derivative_noise", "path_variance", "path_lengthscale")
+        names = [p for p in known if p in params]
         if not names or len(names) != len(tuple(params)):
-            raise ValueError("params must be a non-empty subset of lengthscale / variance / noise / derivative_noise")
+            raise ValueError("params must be a non-empty subset of " + " / ".join(known))
+        ids, pvar, plsp = check_path_args(path_ids, path_variance, path_lengthscale, derivatives=derivatives)
+        if ids is None and ("path_variance" in names or "path_lengthscale" in names):
+            raise ValueError("params names path_variance / path_lengthscale, but there are no path_ids")
+        if "path_variance" in names and not pvar > 0:
+            raise ValueError("path_variance must start above 0 to be learnt (the search runs in log-space)")
+        if ids is not None:   # where the search starts; unpack() moves them when they are learnt
+            self.path_variance = pvar
+            self.path_lengthscale = self.lengthscale.copy() if plsp is None else plsp
         if "derivative_noise" in names:
             if derivatives is None:
                 raise ValueError("params names derivative_noise, but there are no derivatives")
@@ -813,13 +985,16 @@ class GP:
             self.derivative_noise = float(derivative_noise)   # where the search starts; unpack() moves it when it is learnt
 
         def fit_kw():   # every fit of the search, the final one included, with the current derivative_noise
-            return dict(noise_weights=noise_weights, derivatives=derivatives,
-                        derivative_noise=self.derivative_noise if full_grad else derivative_noise)
+            kw = dict(noise_weights=noise_weights, derivatives=derivatives,
+                      derivative_noise=self.derivative_noise if full_grad else derivative_noise)
+            if ids is not None:
+                kw.update(path_ids=ids, path_variance=self.path_variance, path_lengthscale=self.path_lengthscale)
+            return kw
 
         def pack():
             v = []
             for p in names:
-                v.extend(np.log(self.lengthscale) if p == "lengthscale" else
+                v.extend(np.log(getattr(self, p)) if p in ("lengthscale", "path_lengthscale") else
                          [np.log(max(getattr(self, p), bounds[0]))])
             return np.asarray(v, dtype=np.float64)
 
@@ -829,12 +1004,16 @@ class GP:
                 if p == "lengthscale":
                     self.lengthscale = np.exp(v[i:i + n_ls])
                     i += n_ls
+                elif p == "path_lengthscale":
+                    n = self.path_lengthscale.size
+                    self.path_lengthscale = np.exp(v[i:i + n])
+                    i += n
                 else:
                     setattr(self, p, float(np.exp(v[i])))
                     i += 1
 
         best = {"f": np.inf, "v": pack()}
-        analytic = jac == "analytic" and self.dtype == "float64"
+        analytic = jac == "analytic" and self.dtype == "float64" and ids is None  # (no analytic gradient with path ids)
         if analytic and (self.world > 1 or self._is_group or self._host_comm is not None):
             # sharded: the gradient needs the replicated-factor mode, which the library picks from N
             # and the card's memory at fit time — ask it once (every rank gets the same answer)
@@ -848,6 +1027,8 @@ class GP:
         # columns of the full gradient (lengthscale.., variance, noise, derivative_noise) that move
         cols = []
         for p in names:
+            if p in ("path_variance", "path_lengthscale"):
+                continue  # (central differences only: `cols` is not read then)
             cols.extend(range(n_ls) if p == "lengthscale" else
                         [n_ls + ("variance", "noise", "derivative_noise").index(p)])
 

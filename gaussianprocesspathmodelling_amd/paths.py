@@ -245,14 +245,20 @@ class PathModel:
     ``has_velocities``: the model was also conditioned on observed velocities (``fit_path_models(velocities=)``: derivative
     observations along ``"t"``); every prediction works unchanged, :meth:`add_paths` does not (``GP.update`` cannot append
     to such a fit).  ``velocity_noise``: the noise variance of those velocities in the model's normalised units, as given
-    or as learnt (``fit_path_models(learn_velocity_noise=True)``); None without velocities."""
+    or as learnt (``fit_path_models(learn_velocity_noise=True)``); None without velocities.
+    ``within_path``: the model is the hierarchical one (``fit_path_models(within_path=True)``): every path is the cluster
+    mean plus a deviation of its own.  :meth:`predict`, :meth:`sample` and :meth:`velocity` are then about the cluster
+    mean, :meth:`log_likelihood` scores a path as a new member of the cluster, :meth:`forecast` continues one from its
+    first points; :meth:`add_paths` does not work (``GP.update`` cannot append to such a fit)."""
 
-    def __init__(self, gp, keys, in_lo, in_span, y_mean, y_std, inputs, targets, step_weights=None, has_velocities=False):
+    def __init__(self, gp, keys, in_lo, in_span, y_mean, y_std, inputs, targets, step_weights=None, has_velocities=False,
+                 within_path=False):
         self.gp, self.keys = gp, list(keys)
         self.in_lo, self.in_span, self.y_mean, self.y_std = in_lo, in_span, y_mean, y_std
         self.inputs, self.targets = tuple(inputs), tuple(targets)
         self.step_weights = None if step_weights is None else np.asarray(step_weights, dtype=np.float64)
         self.has_velocities = bool(has_velocities)
+        self.within_path = bool(within_path)
 
     @property
     def velocity_noise(self):
@@ -332,6 +338,9 @@ class PathModel:
         if self.has_velocities:
             raise ValueError("add_paths: the model is conditioned on velocities (derivative observations), and a fit with "
                              "derivative observations cannot be appended to: fit the cluster again with fit_path_models")
+        if self.within_path:
+            raise ValueError("add_paths: the model has within-path deviations (path ids), and a fit with path ids cannot be "
+                             "appended to: fit the cluster again with fit_path_models")
         if not keys:
             return self
         if self.step_weights is not None and any(len(trajs.pathdict[q]) != len(self.step_weights) for q in keys):
@@ -366,6 +375,39 @@ class PathModel:
                                     noise_weights=self._tiled_weights(P * L, "log_likelihood"))
         return np.asarray(logp, dtype=np.float64).reshape(P, -1) - L * np.log(self.y_std)[None, :]
 
+    def forecast(self, prefix_txy, t_future, include_noise=True, return_logp=False):
+        """Where partly observed paths of this cluster go: ``prefix_txy`` (P, Lo, 3) raw (t, x, y), the first Lo points
+        of P new paths, ``t_future`` (Lp,) raw time stamps shared by the paths or (P, Lp) (``t`` must be the model's only
+        input; Lo + Lp <= 64) -> ``(mean (P, Lp, k), cov (P, k, Lp, Lp))`` in the targets' own units: each path is a new
+        member of the cluster conditioned on its prefix (``GP.forecast_blocks``).  On a ``within_path`` model the prefix
+        pins the path's own deviation down; on any other model it barely moves the cluster mean.  ``return_logp``: a
+        third entry (P, k), the joint log-density of each prefix in the targets' own units (``-Lo log y_std`` included,
+        as :meth:`log_likelihood`), from the same call.  The observed points get the model's ``noise`` as it is, also on
+        a model with ``step_weights``."""
+        arr = np.asarray(prefix_txy, dtype=np.float64)
+        if arr.ndim != 3 or arr.shape[2] != 3 or arr.shape[0] == 0 or arr.shape[1] == 0:
+            raise ValueError("prefixes must be a non-empty (P, Lo, 3) array of (t, x, y)")
+        if self.inputs != ("t",):
+            raise ValueError(f"forecast() needs 't' as the model's only input, have {self.inputs}")
+        P, Lo = arr.shape[:2]
+        tf = np.asarray(t_future, dtype=np.float64)
+        if tf.ndim == 1:
+            tf = np.broadcast_to(tf, (P, tf.shape[0]))
+        if tf.ndim != 2 or tf.shape[0] != P or tf.shape[1] == 0:
+            raise ValueError(f"t_future must be (Lp,) or ({P}, Lp)")
+        Lp = tf.shape[1]
+        col = {"t": 0, "x": 1, "y": 2}
+        flat = arr.reshape(-1, 3)
+        Xo = np.ascontiguousarray((flat[:, [0]] - self.in_lo) / self.in_span)
+        Yo = np.ascontiguousarray((flat[:, [col[c] for c in self.targets]] - self.y_mean) / self.y_std)
+        Xp = np.ascontiguousarray((tf.reshape(-1, 1) - self.in_lo) / self.in_span)
+        mean, cov, logp = self.gp.forecast_blocks(Xo, Yo, Xp, blocks=P, include_noise=include_noise, return_logp=True)
+        mean = np.asarray(mean, dtype=np.float64).reshape(P, Lp, -1) * self.y_std + self.y_mean
+        cov = np.asarray(cov, dtype=np.float64)[:, None, :, :] * (self.y_std ** 2)[None, :, None, None]
+        if not return_logp:
+            return mean, cov
+        return mean, cov, np.asarray(logp, dtype=np.float64).reshape(P, -1) - Lo * np.log(self.y_std)[None, :]
+
     def close(self):
         self.gp.close()
 
@@ -387,7 +429,7 @@ def step_noise_weights(Yn, n_paths):
 
 def fit_path_models(trajs, clusters, inputs=("t",), targets=("x", "y"), devices=None, optimize=False,
                     lengthscale=0.25, variance=1.0, noise=0.05, step_noise=False, velocities=None, velocity_noise=0.05,
-                    learn_velocity_noise=False, **gp_kwargs):
+                    learn_velocity_noise=False, within_path=False, path_variance=0.25, path_lengthscale=None, **gp_kwargs):
     """One exact GP per cluster of ``clusters`` = {cluster id: [path ids]} — what
     :func:`kmeans` (``kmeansclustering``, GPmap.py:36-93) returns — modelling the cluster's paths
     as (x(t), y(t)); the modelling step the reference's title names and its clustering prepares
@@ -407,6 +449,11 @@ def fit_path_models(trajs, clusters, inputs=("t",), targets=("x", "y"), devices=
     noise variance in those normalised units (as ``noise`` is for the positions).  ``optimize`` keeps it fixed unless
     ``learn_velocity_noise`` is set: then each cluster that has velocities learns its own, starting from ``velocity_noise``
     (which must be > 0), and :attr:`PathModel.velocity_noise` reports it.
+    ``within_path``: fit the hierarchical model — every path is the cluster mean plus a deviation of its own, a GP with
+    variance ``path_variance`` (normalised target units) and lengthscale ``path_lengthscale`` (None: ``lengthscale``):
+    ``GP.fit(path_ids=repeat(arange(P), L))`` per cluster.  Whole-path likelihoods then stay calibrated however many paths
+    a cluster has, and :meth:`PathModel.forecast` / :func:`forecast_paths` continue a partly observed path.  Not with
+    ``velocities``; with ``optimize`` the search runs on central differences and the two are kept fixed.
     Returns {cluster id: :class:`PathModel`}; empty clusters are skipped."""
     import threading
     from concurrent.futures import ThreadPoolExecutor
@@ -425,6 +472,8 @@ def fit_path_models(trajs, clusters, inputs=("t",), targets=("x", "y"), devices=
     velocities = dict(velocities) if velocities else {}
     if velocities and "t" not in inputs:
         raise ValueError(f"velocities need 't' among the inputs, have {tuple(inputs)}")
+    if within_path and velocities:
+        raise ValueError("within_path cannot be combined with velocities (path ids and derivative observations)")
     jobs = []
     for cid, keys in clusters.items():
         keys = list(keys)
@@ -466,6 +515,9 @@ def fit_path_models(trajs, clusters, inputs=("t",), targets=("x", "y"), devices=
         sw = step_noise_weights(Yn, len(keys)) if step_noise else None
         w = None if sw is None else np.tile(sw, len(keys))
         kw = {} if der is None else dict(derivatives=der, derivative_noise=velocity_noise)
+        if within_path:
+            kw.update(path_ids=np.concatenate([np.full(len(trajs.pathdict[q]), p, dtype=np.int32) for p, q in enumerate(keys)]),
+                      path_variance=path_variance, path_lengthscale=path_lengthscale)
         try:
             if optimize:
                 if learn_velocity_noise and der is not None:
@@ -476,7 +528,8 @@ def fit_path_models(trajs, clusters, inputs=("t",), targets=("x", "y"), devices=
         except Exception:
             gp.close()
             raise
-        return cid, PathModel(gp, keys, lo, span, mu, sd, inputs, targets, step_weights=sw, has_velocities=der is not None)
+        return cid, PathModel(gp, keys, lo, span, mu, sd, inputs, targets, step_weights=sw, has_velocities=der is not None,
+                              within_path=within_path)
 
     by_dev = [[] for _ in devs]                    # one worker per device, its clusters in order
     for i, (cid, keys) in enumerate(jobs):
@@ -530,3 +583,20 @@ def assign_paths(trajs, models, keys=None):
     cids = list(models.keys())
     best = np.argmax(LL, axis=1) if keys else np.zeros(0, dtype=int)
     return {cid: [keys[p] for p in np.nonzero(best == c)[0]] for c, cid in enumerate(cids)}
+
+
+def forecast_paths(prefixes, t_future, models, include_noise=True):
+    """Continue partly observed paths under every cluster's model: ``prefixes`` (P, Lo, 3) raw (t, x, y), ``t_future`` (Lp,)
+    or (P, Lp), ``models`` = {cluster id: :class:`PathModel`} -> ``(weights (P, C), means, covs)``: ``weights[p, c]`` the
+    posterior probability (equal priors) that path p belongs to cluster c — the softmax over the clusters of the prefix
+    log-likelihoods summed over the targets, which come from the same call as the forecasts — and ``means`` / ``covs`` =
+    {cluster id: (P, Lp, k) / (P, k, Lp, Lp)}, :meth:`PathModel.forecast` under each cluster (column order = ``models``'
+    order).  The mixture over the clusters with these weights is the forecast of a path whose cluster is not known."""
+    P = np.asarray(prefixes).shape[0]
+    LL = np.empty((P, len(models)), dtype=np.float64)
+    means, covs = {}, {}
+    for c, (cid, m) in enumerate(models.items()):
+        means[cid], covs[cid], logp = m.forecast(prefixes, t_future, include_noise=include_noise, return_logp=True)
+        LL[:, c] = logp.sum(axis=1)
+    w = np.exp(LL - LL.max(axis=1, keepdims=True))
+    return w / w.sum(axis=1, keepdims=True), means, covs

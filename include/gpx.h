@@ -337,6 +337,43 @@ int gpx_set_observation_kinds(gpx_handle* h, const int32_t* kind, int64_t n, dou
 /* The kinds of the current fit, all -1 when it was made without any.  GPX_E_ARG without a fit. */
 int gpx_get_observation_kinds(gpx_handle* h, int32_t* out /* (N) host */);
 
+/* ---- within-path deviations: path ids on the observations (additive to ABI v6) ---------------------------------------------
+ * Model (hierarchical GP): y_p(t) = f(t) + g_p(t) + noise — f the function the handle models, g_p a GP of its own for every
+ * path p, independent between paths, of the handle's covariance family with variance sg2 and lengthscales ls_path:
+ *   K[(x, p), (x', p')] = sf2 k(x, x'; l) + [p == p' and p >= 0] sg2 k(x, x'; l_path)      (+ (sn2 w_i + jitter) on the diagonal)
+ * group[i] >= 0 names the path of observation i (ids need be neither contiguous nor sorted), -1 says "no path": that
+ * observation gets f alone.  EVERY PREDICTION CALL KEEPS ITS CODE AND MEANING: gpx_predict, gpx_predict_cov,
+ * gpx_predict_grad, gpx_sample_posterior and the mean-only route use K* = sf2 k(Xq, X) against the new factor, which is
+ * exactly the posterior of the cluster mean f.  gpx_score_blocks(_weighted) on such a fit treats every block as a NEW path:
+ * its covariance gains sg2 k(X_g, X_g; l_path).  gpx_forecast_blocks conditions a new path on its first points.
+ *
+ * gpx_set_path_groups copies n ids (host or device memory as mem_kind says), sg2 and the n_ls_path (1 or d; checked
+ * against d at the fit) lengthscales into the handle, for every later gpx_fit / gpx_fit_predict until replaced or cleared
+ * (group == NULL with n == 0).  GPX_E_ARG — nothing stored, the previous setting stays — for an id below -1, sg2 negative
+ * or not finite, a lengthscale not > 0 or not finite, n_ls_path < 1 or > 32.  A fit with N != n, or n_ls_path not 1 or d:
+ * GPX_E_ARG before anything is computed.  With every id -1, or sg2 == 0, a fit is the plain (or weighted) fit bit for bit.
+ * Otherwise GPX_E_UNSUPPORTED before anything is computed or exchanged, the previous fit still valid: a fit on device
+ * groups, shards, handles with a communicator, GPX_MIXED handles, and handles that also have observation kinds set; on a
+ * fit made with path ids: gpx_append / gpx_append_weighted (fit the concatenated data), gpx_lml_grad and
+ * gpx_lml_grad_full (these evaluate training-pair covariances matrix-free, without the path term). */
+int gpx_set_path_groups(gpx_handle* h, const int32_t* group, int64_t n, double sg2, const double* ls_path,
+                        int32_t n_ls_path, int32_t mem_kind);
+/* The path ids of the current fit, all -1 when it was made without any (or with sg2 == 0).  GPX_E_ARG without a fit. */
+int gpx_get_path_groups(gpx_handle* h, int32_t* out /* (N) host */);
+/* Forecast of partly observed new paths.  Xb (G (Lo + Lp), d): per block its Lo observed points, then its Lp points to
+ * forecast (1 <= Lo, 1 <= Lp, Lo + Lp <= 64); yo (G Lo, k) the observed targets; diag_add >= 0 goes on the diagonal of the
+ * observed part only (the observation noise).  The block prior is posterior(f) [+ sg2 k(., .; l_path) on a fit with path
+ * ids]; with S the joint (Lo + Lp)^2 covariance of a block, L_oo = chol(S_oo + diag_add I), B = S_po L_oo^-T and
+ * w = L_oo^-1 (yo - mean_o):
+ *   mean (G Lp, k) = mean_p + B w;   cov (G, Lp, Lp), may be NULL = S_pp - B B^T (latent, shared by the targets, exactly
+ *   symmetric);   var (G Lp), may be NULL = its diagonal;   logp (G, k), may be NULL = the joint log-density of the
+ *   observed prefix (gpx_score_blocks' number for the Lo points alone).
+ * *info = 1-based index of the first block whose conditioning matrix is not positive definite (its outputs are NaN, the
+ * others unaffected), 0 if none.  A block's numbers do not depend on G, its position or GPX_PRED_BATCH.  Single-device
+ * GPX_F64 / GPX_F32 handles (GPX_E_UNSUPPORTED otherwise, as gpx_score_blocks); any fit, with or without path ids. */
+int gpx_forecast_blocks(gpx_handle* h, const void* Xb, const void* yo, int64_t G, int32_t Lo, int32_t Lp, double diag_add,
+                        void* mean, void* cov, void* var, void* logp, int32_t mem_kind, int64_t* info);
+
 int gpx_get_alpha(gpx_handle* h, void* out /* (N,k) host */);
 /* Log marginal likelihood of the last fit and its gradient w.r.t. the LOG hyper-parameters —
  * SURVEY.md §8(f) row 1 ("log marginal likelihood + hyper-parameter gradient hooks"; no anchor
@@ -425,6 +462,12 @@ int gpx_kernel_deriv_matrix(int32_t kernel, const double* A, int64_t na, const d
 int gpx_kernel_dl_matrix(int32_t kernel, const double* A, const int32_t* ka, int64_t na, const double* B,
                          const int32_t* kb, int64_t nb, int32_t d, const double* lengthscale, int32_t n_ls, double sf2,
                          double* G /* (n_ls, na, nb) */);
+/* K (na, nb) host, fp64 = sf2 k(A_i, B_j; l) + [ga_i == gb_j and ga_i >= 0] sg2 k(A_i, B_j; l_path): the covariance of
+ * observations with path ids (gpx_set_path_groups), by the fit's builder; no diagonal term.  n_ls, n_ls_path: 1 or d.
+ * dtype GPX_F64 or GPX_F32 (the fp32 builder on the rounded inputs, returned widened). */
+int gpx_kernel_path_matrix(int32_t kernel, int32_t dtype, const double* A, const int32_t* ga, int64_t na, const double* B,
+                           const int32_t* gb, int64_t nb, int32_t d, const double* lengthscale, int32_t n_ls, double sf2,
+                           const double* ls_path, int32_t n_ls_path, double sg2, double* K);
 /* in-place lower Cholesky of A (n,n), lda = n; n multiple of 64.  The strictly upper
  * triangle is never read and is scratch on return (diagonal tiles are updated whole).
  * block = panel width (0 = default). */
