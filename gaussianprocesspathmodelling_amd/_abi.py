@@ -93,6 +93,7 @@ SIGNATURES = {
     "gpx_get_alpha": (C.c_int, [_P, _P]),
     "gpx_lml_grad": (C.c_int, [_P, _PD, _PD]),
     "gpx_lml_grad_full": (C.c_int, [_P, _PD, _PD]),
+    "gpx_lml_grad_paths": (C.c_int, [_P, _PD, _PD, _PD, C.c_int32]),
     "gpx_logdet": (C.c_int, [_P, _PD]),
     "gpx_release_scratch": (C.c_int, [_P]),
     "gpx_get_timings": (C.c_int, [_P, C.POINTER(GpxTimings)]),
@@ -109,6 +110,8 @@ SIGNATURES = {
                                           C.c_double, _PD]),
     "gpx_kernel_dl_matrix": (C.c_int, [C.c_int32, _PD, C.POINTER(C.c_int32), C.c_int64, _PD, C.POINTER(C.c_int32), C.c_int64,
                                        C.c_int32, _PD, C.c_int32, C.c_double, _PD]),
+    "gpx_kernel_path_dtheta_matrix": (C.c_int, [C.c_int32, _PD, C.POINTER(C.c_int32), C.c_int64, _PD, C.POINTER(C.c_int32),
+                                                C.c_int64, C.c_int32, _PD, C.c_int32, C.c_double, _PD]),
     "gpx_potrf": (C.c_int, [_PD, C.c_int64, C.c_int32, C.POINTER(C.c_int64)]),
     "gpx_trsm": (C.c_int, [_PD, C.c_int64, _PD, C.c_int64]),
     "gpx_gemm_nt": (C.c_int, [_PD, C.c_int64, C.c_int64, _PD, _PD, C.c_int64, C.c_int32]),

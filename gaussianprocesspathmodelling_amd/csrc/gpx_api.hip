@@ -182,6 +182,7 @@ struct gpx_handle {
   std::vector<double> q_fit;        // q_c = (l_c / l_path,c)^2 of the current fit (d entries; the source of Gq)
   DevBuf Gfit, Gdiag, Gq;           // the ids on the device, -1 up to the layout's capacity; the finished diagonal terms; q
   double sg2 = 0.0;
+  int n_lsp = 0;                    // the number of path lengthscales of the current fit (1 or d; grouped only)
   bool grouped = false;             // the current fit was built by the GROUPS builder (ids set, one >= 0, sg2 > 0)
   // event pool
   std::vector<hipEvent_t> ev_pool;
@@ -1214,6 +1215,7 @@ int stage_fit_groups(gpx_handle* h, int64_t N, int64_t cap, int d, const double*
   HIPCHK(h, hipStreamSynchronize(h->st));  // (groups_fit and q_fit are the sources of asynchronous copies of the fit before)
   h->groups_fit = h->groups_set;
   h->sg2 = h->sg2_set;
+  h->n_lsp = (int)h->lsp_set.size();
   h->q_fit.assign((size_t)d, 0.0);
   for (int c = 0; c < d; ++c) {
     const double r = lengthscale[n_ls == 1 ? 0 : c] / h->lsp_set[h->lsp_set.size() == 1 ? 0 : c];
@@ -2302,9 +2304,12 @@ int trtri_enqueue(gpx_handle* h, double* ZT, const double* L, int64_t ld, int64_
 // form are replicated work (O(N^2)), identical on every rank.
 // kinds (gpx_lml_grad_full on a fit with derivative observations; one device): the KINDS instantiations of both passes,
 // theta = (lengthscales..., sf2, sn2, sn2_deriv).
-int lml_grad_impl(gpx_handle* h, double* lml, double* grad, bool kinds = false) {
+// grad_path (gpx_lml_grad_paths on a fit with path ids; one device): the GROUPS instantiations of both passes, theta =
+// (lengthscales..., sf2, sn2, sg2, l_path...); the last 1 + n_lsp entries go to grad_path.
+int lml_grad_impl(gpx_handle* h, double* lml, double* grad, bool kinds = false, double* grad_path = nullptr) {
   const int64_t N = h->N, Npad = h->Npad, ld = h->ld;
-  const int d = h->d, k = h->k, ntheta = h->n_ls + (kinds ? 3 : 2), ard = h->n_ls > 1;
+  const bool paths = grad_path != nullptr;
+  const int d = h->d, k = h->k, ntheta = h->n_ls + (kinds ? 3 : paths ? 3 + h->n_lsp : 2), ard = h->n_ls > 1;
   Comm* cm = h->comm;
   const int P = cm ? cm->world : 1, rank = cm ? cm->rank : 0;
   // the gradient's sweeps keep their measured 1024-blocks whatever the fit's panel width (GPX_NB_GRAD overrides: A/B)
@@ -2364,6 +2369,9 @@ int lml_grad_impl(gpx_handle* h, double* lml, double* grad, bool kinds = false) 
         launch_kinv_trace_kinds(h->cfg.kernel, ZT, ld, Npad, N, (const double*)h->Xs.p, d, ard, h->sf2, h->sn2,
                                 h->sn2_deriv, (const int32_t*)h->Kfit.p, (const double*)h->ls.p, h->n_ls, part1, ntheta,
                                 st, wv);
+      else if (paths)
+        launch_kinv_trace_groups(h->cfg.kernel, ZT, ld, Npad, N, (const double*)h->Xs.p, d, ard, h->sf2, h->sn2, h->sg2,
+                                 (const int32_t*)h->Gfit.p, (const double*)h->Gq.p, h->n_lsp, part1, ntheta, st, wv);
       else
         launch_kinv_trace(h->cfg.kernel, ZT, ld, Npad, N, (const double*)h->Xs.p, d, ard, h->sf2, h->sn2, part1,
                           ntheta, P, rank, st, wv);
@@ -2372,6 +2380,10 @@ int lml_grad_impl(gpx_handle* h, double* lml, double* grad, bool kinds = false) 
       launch_alpha_quad_kinds(h->cfg.kernel, (const double*)h->alphaT, ld, k, Npad, N, (const double*)h->Xs.p, d, ard,
                               h->sf2, h->sn2, h->sn2_deriv, (const int32_t*)h->Kfit.p, (const double*)h->ls.p, h->n_ls,
                               part2, ntheta, st, wv);
+    else if (paths)
+      launch_alpha_quad_groups(h->cfg.kernel, (const double*)h->alphaT, ld, k, Npad, N, (const double*)h->Xs.p, d, ard,
+                               h->sf2, h->sn2, h->sg2, (const int32_t*)h->Gfit.p, (const double*)h->Gq.p, h->n_lsp, part2,
+                               ntheta, st, wv);
     else
       launch_alpha_quad(h->cfg.kernel, (const double*)h->alphaT, ld, k, Npad, N, (const double*)h->Xs.p, d, ard,
                         h->sf2, h->sn2, part2, ntheta, st, wv);
@@ -2380,10 +2392,12 @@ int lml_grad_impl(gpx_handle* h, double* lml, double* grad, bool kinds = false) 
     launch_dot_rhs((const double*)h->Y.p, (const double*)h->alphaT, ld, N, k, outv + 2 * ntheta, st);
     if (P > 1 && (rc = cm->allreduce(h, outv, (size_t)ntheta, COMM_SUM))) return rc;
   }
-  double host[2 * (MAX_D + 3) + 1];
+  double host[2 * (2 * MAX_D + 3) + 1];
   HIPCHK(h, hipMemcpyAsync(host, outv, (size_t)(2 * ntheta + 1) * 8, hipMemcpyDeviceToHost, st));
   if ((rc = finish_call(h))) return rc;
-  for (int t = 0; t < ntheta; ++t) grad[t] = 0.5 * (host[ntheta + t] - (double)k * host[t]);
+  const int nmain = paths ? h->n_ls + 2 : ntheta;
+  for (int t = 0; t < nmain; ++t) grad[t] = 0.5 * (host[ntheta + t] - (double)k * host[t]);
+  for (int t = nmain; t < ntheta; ++t) grad_path[t - nmain] = 0.5 * (host[ntheta + t] - (double)k * host[t]);
   if (kinds && h->sn2_deriv == 0.0) grad[ntheta - 1] = 0.0;  // (exactly: not -0, and no 0 x inf)
   *lml = -0.5 * host[2 * ntheta] - 0.5 * (double)k * h->logdet -
          0.5 * (double)N * (double)k * 1.8378770664093454835606594728112;  // log(2 pi)
@@ -3302,6 +3316,32 @@ int gpx_lml_grad_full(gpx_handle* h, double* lml, double* grad) try {
 }
 GPX_CATCH_ALL
 
+int gpx_lml_grad_paths(gpx_handle* h, double* lml, double* grad, double* grad_path, int32_t n_path) try {
+  if (!h) return GPX_E_ARG;
+  if (!h->fitted || !lml || !grad || n_path < 0 || (n_path > 0 && !grad_path))
+    return fail(h, GPX_E_ARG, "gpx_lml_grad_paths: no fit, null output or n_path < 0");
+  if (h->cfg.dtype != GPX_F64) return fail(h, GPX_E_UNSUPPORTED, "gpx_lml_grad_paths: fp64 handles only");
+  if (h->group || h->comm || h->cfg.world > 1)
+    return fail(h, GPX_E_UNSUPPORTED, "gpx_lml_grad_paths: single-device handles only (no fit with path ids exists on shards "
+                                      "and groups; gpx_lml_grad there)");
+  if (h->has_deriv)
+    return fail(h, GPX_E_UNSUPPORTED, "gpx_lml_grad_paths: the fit has derivative observations (gpx_set_observation_kinds), "
+                                      "which exclude path ids: call gpx_lml_grad_full");
+  if (h->grouped && n_path != 1 + h->n_lsp) {
+    char buf[200];
+    snprintf(buf, sizeof buf, "gpx_lml_grad_paths: the fit has %d path lengthscale(s): grad_path needs n_path = %d, not %d",
+             h->n_lsp, 1 + h->n_lsp, (int)n_path);
+    return fail(h, GPX_E_ARG, buf);
+  }
+  int rc;
+  if ((rc = begin_call(h))) return rc;
+  if (h->grouped) return lml_grad_impl(h, lml, grad, false, grad_path);
+  if ((rc = lml_grad_impl(h, lml, grad))) return rc;  // no effective path ids: gpx_lml_grad's launches and numbers
+  for (int32_t t = 0; t < n_path; ++t) grad_path[t] = 0.0;
+  return GPX_OK;
+}
+GPX_CATCH_ALL
+
 int gpx_release_scratch(gpx_handle* h) try {
   if (!h) return GPX_E_ARG;
   std::vector<gpx_handle*> hs;
@@ -3587,6 +3627,62 @@ int gpx_kernel_dl_matrix(int32_t kernel, const double* A, const int32_t* ka, int
       memcpy(G + ((int64_t)c * na + i) * nb_, host.data() + ((int64_t)c * napad + i) * ld, (size_t)nb_ * 8);
 done:
   for (void* p : {(void*)dA, (void*)dB, (void*)dAs, (void*)dBs, (void*)dls, (void*)dG, (void*)dka, (void*)dkb})
+    if (p) (void)hipFree(p);
+  return rc;
+}
+GPX_CATCH_ALL
+
+int gpx_kernel_path_dtheta_matrix(int32_t kernel, const double* A, const int32_t* ga, int64_t na, const double* B,
+                                  const int32_t* gb, int64_t nb_, int32_t d, const double* ls_path, int32_t n_ls_path,
+                                  double sg2, double* G) try {
+  if (!A || !B || !ga || !gb || !G || !ls_path || na <= 0 || nb_ <= 0 || d <= 0 || d > MAX_D ||
+      (n_ls_path != 1 && n_ls_path != d))
+    return GPX_E_ARG;
+  if (!cov::known(kernel)) return GPX_E_ARG;
+  if (!(sg2 >= 0.0) || !std::isfinite(sg2)) return GPX_E_ARG;
+  for (int32_t c = 0; c < n_ls_path; ++c)
+    if (!(ls_path[c] > 0.0) || !std::isfinite(ls_path[c])) return GPX_E_ARG;
+  for (int64_t i = 0; i < na; ++i)
+    if (ga[i] < -1) return GPX_E_ARG;
+  for (int64_t i = 0; i < nb_; ++i)
+    if (gb[i] < -1) return GPX_E_ARG;
+  Scratch sc;
+  if (!sc.ok) return GPX_E_HIP;
+  hipStream_t st = sc.h.st;
+  // the points are scaled by l_path itself, so q = 1: r_p^2 = sum_c ((x_ic - x_jc) / l_path,c)^2 as in a fit with l = l_path
+  const int64_t napad = round_up(na, 64), nbpad = round_up(nb_, 64), ld = nbpad;
+  const int nt = 1 + n_ls_path;
+  double *dA = nullptr, *dB = nullptr, *dAs = nullptr, *dBs = nullptr, *dls = nullptr, *dq = nullptr, *dG = nullptr;
+  int32_t *dga = nullptr, *dgb = nullptr;
+  std::vector<double> host((size_t)nt * napad * ld), q((size_t)d, 1.0);
+  int rc = GPX_OK;
+  TCHK(hipMalloc(&dA, (size_t)na * d * 8));
+  TCHK(hipMalloc(&dB, (size_t)nb_ * d * 8));
+  TCHK(hipMalloc(&dAs, (size_t)napad * d * 8));
+  TCHK(hipMalloc(&dBs, (size_t)nbpad * d * 8));
+  TCHK(hipMalloc(&dls, MAX_D * 8));
+  TCHK(hipMalloc(&dq, MAX_D * 8));
+  TCHK(hipMalloc(&dga, (size_t)na * sizeof(int32_t)));
+  TCHK(hipMalloc(&dgb, (size_t)nb_ * sizeof(int32_t)));
+  TCHK(hipMalloc(&dG, (size_t)nt * napad * ld * 8));
+  TCHK(hipMemcpyAsync(dA, A, (size_t)na * d * 8, hipMemcpyHostToDevice, st));
+  TCHK(hipMemcpyAsync(dB, B, (size_t)nb_ * d * 8, hipMemcpyHostToDevice, st));
+  TCHK(hipMemcpyAsync(dls, ls_path, (size_t)n_ls_path * 8, hipMemcpyHostToDevice, st));
+  TCHK(hipMemcpyAsync(dq, q.data(), (size_t)d * 8, hipMemcpyHostToDevice, st));
+  TCHK(hipMemcpyAsync(dga, ga, (size_t)na * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  TCHK(hipMemcpyAsync(dgb, gb, (size_t)nb_ * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  TCHK(hipMemsetAsync(dG, 0, (size_t)nt * napad * ld * 8, st));
+  launch_scale_points(dA, na, napad, d, dls, n_ls_path, dAs, st);
+  launch_scale_points(dB, nb_, nbpad, d, dls, n_ls_path, dBs, st);
+  launch_path_dtheta_matrix(kernel, dAs, dga, na, napad, dBs, dgb, nb_, d, dq, n_ls_path, sg2, dG, ld, st);
+  TCHK(hipMemcpyAsync(host.data(), dG, (size_t)nt * napad * ld * 8, hipMemcpyDeviceToHost, st));
+  TCHK(hipStreamSynchronize(st));
+  TCHK(hipGetLastError());
+  for (int32_t t = 0; t < nt; ++t)
+    for (int64_t i = 0; i < na; ++i)
+      memcpy(G + ((int64_t)t * na + i) * nb_, host.data() + ((int64_t)t * napad + i) * ld, (size_t)nb_ * 8);
+done:
+  for (void* p : {(void*)dA, (void*)dB, (void*)dAs, (void*)dBs, (void*)dls, (void*)dq, (void*)dG, (void*)dga, (void*)dgb})
     if (p) (void)hipFree(p);
   return rc;
 }

@@ -172,6 +172,31 @@ __device__ __forceinline__ void value_kd(T r2, T sf2, T& v, T& kd, E ex = {}) {
   }
 }
 
+// The within-path term sg2 k(r_p) of a pair with path ids (ga, gb) and its derivatives by the log path parameters (the LML
+// gradient of a fit with path ids) — the one place they exist.  pa / pb: the pair's SCALED points (x / l), q_c = (l_c /
+// l_path,c)^2, so r_p^2 = sum_c q_c e_c^2 with e = pa - pb (the kernel build's own operation order).  A same-path pair
+// (ga == gb >= 0) returns true with v = sg2 k(r_p) = d / dlog sg2 and
+//   c >= 0:  dl = kd(r_p; sg2) q_c e_c^2 = d / dlog l_path,c        c < 0:  dl = kd r_p^2, their sum (one l_path for all)
+// Any other pair returns false with v = dl = 0 and evaluates no exponential.  e enters only squared: swapping the two
+// sides gives the same bits.
+template <int KERNEL, typename T>
+__device__ __forceinline__ bool path_dtheta(int ga, int gb, const T* pa, const T* pb, const T* q, int d, T sg2, int c, T& v,
+                                            T& dl) {
+  v = dl = (T)0;
+  if (ga < 0 || ga != gb) return false;
+  T rp2 = (T)0, tc = (T)0;
+  for (int j = 0; j < d; ++j) {
+    const T e = pa[j] - pb[j];
+    const T t = q[j] * (e * e);
+    rp2 += t;
+    if (j == c) tc = t;
+  }
+  T kd;
+  value_kd<KERNEL>(rp2, sg2, v, kd);
+  dl = kd * (c < 0 ? rp2 : tc);
+  return true;
+}
+
 // f(std::integral_constant<int, id>{}) for the family `kernel` (the API refuses unknown ids before any launch)
 template <typename F>
 void dispatch(int kernel, F&& f) {

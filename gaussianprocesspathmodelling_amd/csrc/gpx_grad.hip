@@ -23,6 +23,17 @@
 // gpx_cov.h).  W A stays in the accumulators for the per-dimension pass exactly as W kd does; W B is summed per row (the
 // rows of kind >= 0) and per column of the thread's elements and goes to the dimension that row's / column's kind names.
 // theta = (lengthscales..., sf2, sn2, sn2_deriv): the diagonal sum is split by the row's kind.
+//
+// Fits with path ids (GROUPS instantiations of both kernels; gpx_lml_grad_paths): K = sf2 k(r) + m sg2 k(r_p)
+// + diag with m_ij = [id_i == id_j >= 0] and r_p^2 = sum_c q_c e_c^2 (gpx_cov.h: path_dtheta).  The path term does not depend
+// on l (q_c e_c^2 = ((x_ic - x_jc) / l_path,c)^2), so the entries of l, sf2 (the f part alone) and sn2 are the plain ones;
+// theta = (lengthscales..., sf2, sn2, sg2, l_path...) gets  dK/dlog sg2 = m sg2 k(r_p),  dK/dlog l_path,c = m kd(r_p; sg2) q_c e_c^2.
+// The accumulators have no room for a second retained set, so the path passes run FIRST, while the accumulators still hold
+// W: one pass for sg2 (and the single l_path), then one per path dimension with r_p and kd recomputed per element — only
+// in tiles that can hold a same-path pair (the ranges of the non-negative row and column ids overlap: workgroup-uniform, as
+// kbuild_kernel's), the others write exact zeros and evaluate no extra exponential.
+#include <climits>
+
 #include "gpx_cov.h"
 #include "gpx_internal.h"
 #include "gpx_tile.h"
@@ -50,7 +61,10 @@ __device__ __forceinline__ double wg_sum(double v, double* red) {
 // changes what the unweighted kernel spills.
 // KINDS: the fit has derivative observations — kind (readable up to npad, -1 there), ls (n_ls) and sn2_deriv are read, wv
 // may be null (WEIGHTED is not used), ntheta = n_ls + 3.  Instantiations of their own for the same reason.
-template <int KERNEL, int D, bool WEIGHTED, bool KINDS = false>
+// GROUPS (never with KINDS or WEIGHTED): the fit has path ids — the side channels are reused as kbuild_kernel's are: kind
+// holds the ids (readable up to npad, -1 there), ls the d entries of q, n_ls is n_ls_path (1 or d) and sn2_deriv is sg2; wv
+// may be null.  part[..] = (l_0.., sf2, sn2, sg2, l_path,0..), ntheta = (ard ? d : 1) + 3 + n_ls_path.
+template <int KERNEL, int D, bool WEIGHTED, bool KINDS = false, bool GROUPS = false>
 __global__ __launch_bounds__(256, 2) void kinv_trace_kernel(const double* __restrict__ ZT, int64_t ld,
                                                             int tiles, int64_t npad, int64_t n,
                                                             const double* __restrict__ Xs, int d_rt, int ard,
@@ -107,6 +121,7 @@ __global__ __launch_bounds__(256, 2) void kinv_trace_kernel(const double* __rest
   const int* ska = nullptr;
   const int* skb = nullptr;
   const double* sil = nullptr;
+  [[maybe_unused]] const int* srng = nullptr;
   if constexpr (KINDS) {  // the tile's row and column kinds and 1 / l, beside the points
     __shared__ int kab[2 * BT];
     __shared__ double ilv[MAX_D];
@@ -114,9 +129,86 @@ __global__ __launch_bounds__(256, 2) void kinv_trace_kernel(const double* __rest
     if (tid < d) ilv[tid] = 1.0 / ls[n_ls == 1 ? 0 : tid];
     ska = kab, skb = kab + BT, sil = ilv;
   }
+  if constexpr (GROUPS) {  // the tile's row and column ids and q, beside the points; the id ranges of the two sides
+    static_assert(!KINDS && !WEIGHTED, "a fit has path ids or kinds, and the GROUPS instantiation reads wv when it is set");
+    __shared__ int gab[2 * BT];
+    __shared__ int rng[8];  // per wave (0, 1: the rows, 2, 3: the columns) the lowest / highest non-negative id
+    __shared__ double qv[MAX_D];
+    const int id = kind[(tid < BT ? (int64_t)ti * BT : (int64_t)tj * BT - BT) + tid];
+    gab[tid] = id;
+    int lo = id >= 0 ? id : INT_MAX, hi = id;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      lo = min(lo, __shfl_xor(lo, o));
+      hi = max(hi, __shfl_xor(hi, o));
+    }
+    if ((tid & 63) == 0) rng[2 * (tid >> 6)] = lo, rng[2 * (tid >> 6) + 1] = hi;
+    if (tid < d) qv[tid] = ls[tid];
+    ska = gab, skb = gab + BT, sil = qv, srng = rng;
+  }
   __syncthreads();
   const int lane = tid & 63, wave = tid >> 6;
   const int wr = wave >> 1, wc = wave & 1, l15 = lane & 15, l4 = lane >> 4;
+  if constexpr (GROUPS) {  // the path entries, while the accumulators hold W (the loop below overwrites them)
+    const int nlp = n_ls;
+    double* outp = part + lin * ntheta + (ntheta - nlp - 1);  // (sg2, l_path...)
+    const double wp = (ti == tj) ? 1.0 : 2.0;
+    // The noise entry first, and here rather than in the loop below: its load of wv is what makes the WEIGHTED loop spill
+    // half as much again as the plain one, and every scratch access of that loop is a round trip to memory (measured:
+    // the trace pass of this instantiation ran 8 % behind the plain one at d = 3 with the entry formed there).  Only a
+    // diagonal tile holds diagonal elements, at il == jl.
+    double sdiag = 0.0;
+    if (ti == tj) {
+#pragma unroll
+      for (int m = 0; m < 4; ++m)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int il = wr * 64 + m * 16 + l4 + 4 * r;
+          const int64_t gi = (int64_t)ti * BT + il;
+#pragma unroll
+          for (int nn = 0; nn < 4; ++nn)
+            if (il == wc * 64 + nn * 16 + l15 && gi < n) sdiag += wv ? acc[m][nn][r] * wv[gi] : acc[m][nn][r];
+        }
+      sdiag = wg_sum(sdiag, red);
+    }
+    if (tid == 0) outp[-1] = sdiag * sn2;
+    // can the tile hold a same-path pair?  (no id >= 0 on a side: lo = INT_MAX, hi < 0)
+    const bool mixed = min(srng[0], srng[2]) <= max(srng[5], srng[7]) && min(srng[4], srng[6]) <= max(srng[1], srng[3]);
+    if (!mixed) {
+      if (tid <= nlp) outp[tid] = 0.0;
+    } else {
+      // pass 0: sg2 and, with one l_path, its entry (the sum over the dimensions); pass 1 + c: l_path,c
+      for (int pass = 0; pass <= (nlp > 1 ? d : 0); ++pass) {
+        double s = 0.0, s1 = 0.0;
+#pragma unroll
+        for (int m = 0; m < 4; ++m)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int il = wr * 64 + m * 16 + l4 + 4 * r;
+#pragma unroll
+            for (int nn = 0; nn < 4; ++nn) {
+              const int jl = wc * 64 + nn * 16 + l15;
+              double pv, pdl;  // (padded rows and columns have id -1: no pair)
+              if (cov::path_dtheta<KERNEL>(ska[il], skb[jl], xa + il * d, xb + jl * d, sil, d, sn2_deriv, pass - 1, pv, pdl)) {
+                s += acc[m][nn][r] * (pass == 0 ? pv : pdl);
+                s1 += acc[m][nn][r] * pdl;
+              }
+              __builtin_amdgcn_sched_barrier(0);  // (as below)
+            }
+          }
+        s = wg_sum(s, red);
+        if (pass == 0) {
+          if (nlp == 1) s1 = wg_sum(s1, red);
+          if (tid == 0) {
+            outp[0] = wp * s;
+            if (nlp == 1) outp[1] = wp * s1;
+          }
+        } else if (tid == 0) {
+          outp[pass] = wp * s;
+        }
+      }
+    }
+  }
   double Sf = 0.0, Sn = 0.0, Sl = 0.0;
   // KINDS: the diagonal sum of the derivative rows, and W B summed over the thread's elements of a row / of a column
   [[maybe_unused]] double Sd = 0.0, RB[4][4] = {}, CB[4] = {};
@@ -169,7 +261,9 @@ __global__ __launch_bounds__(256, 2) void kinv_trace_kernel(const double* __rest
           double kf, kd;
           cov::value_kd<KERNEL>(r2, sf2, kf, kd);
           Sf += v * kf;
-          if (WEIGHTED) {
+          if constexpr (GROUPS) {
+            // (the noise entry is formed before the path passes)
+          } else if (WEIGHTED) {
             if (gi == gj && gi < n) Sn += v * wv[gi];
           } else {
             if (gi == gj) Sn += v;
@@ -186,7 +280,7 @@ __global__ __launch_bounds__(256, 2) void kinv_trace_kernel(const double* __rest
     }
   const double w = (ti == tj) ? 1.0 : 2.0;
   double* out = part + lin * ntheta;
-  const int nls = ntheta - (KINDS ? 3 : 2);
+  const int nls = ntheta - (KINDS ? 3 : GROUPS ? 3 + n_ls : 2);
   if (!ard) {
     if constexpr (KINDS) {  // one lengthscale: every dimension a kind names is that one
 #pragma unroll
@@ -225,6 +319,11 @@ __global__ __launch_bounds__(256, 2) void kinv_trace_kernel(const double* __rest
       if (tid == 0) out[c] = w * s;
     }
   }
+  if constexpr (GROUPS) {
+    const double sf = wg_sum(Sf, red);
+    if (tid == 0) out[nls] = w * sf;
+    return;
+  }
   const double sf = wg_sum(Sf, red), sn = wg_sum(Sn, red);
   if (tid == 0) {
     out[nls] = w * sf;
@@ -247,8 +346,8 @@ __device__ __forceinline__ void tri_coords64(int64_t t, int& ti, int& tj) {
   tj = (int)(t - i * (i + 1) / 2);
 }
 
-// KINDS: as kinv_trace_kernel's.
-template <int KERNEL, int D, bool KINDS = false>
+// KINDS, GROUPS: as kinv_trace_kernel's.
+template <int KERNEL, int D, bool KINDS = false, bool GROUPS = false>
 __global__ __launch_bounds__(256) void alpha_quad_kernel(const double* __restrict__ alphaT, int64_t ld, int k,
                                                         int64_t n, const double* __restrict__ Xs, int d_rt,
                                                         int ard, double sf2, double sn2,
@@ -280,6 +379,27 @@ __global__ __launch_bounds__(256) void alpha_quad_kernel(const double* __restric
     else if (tid - 2 * KT < d) ilv[tid - 2 * KT] = 1.0 / ls[n_ls == 1 ? 0 : tid - 2 * KT];
     ska = kab, skb = kab + KT, sil = ilv;
   }
+  [[maybe_unused]] const int* srng = nullptr;
+  if constexpr (GROUPS) {  // wave 0: the row ids, wave 1: the column ids, and their ranges; q
+    static_assert(!KINDS, "a fit has path ids or kinds");
+    __shared__ int gab[2 * KT];
+    __shared__ int rng[4];
+    __shared__ double qv[MAX_D];
+    if (tid < 2 * KT) {
+      const int id = kind[(tid < KT ? i0 : j0 - KT) + tid];
+      gab[tid] = id;
+      int lo = id >= 0 ? id : INT_MAX, hi = id;
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) {
+        lo = min(lo, __shfl_xor(lo, o));
+        hi = max(hi, __shfl_xor(hi, o));
+      }
+      if ((tid & 63) == 0) rng[2 * (tid >> 6)] = lo, rng[2 * (tid >> 6) + 1] = hi;
+    } else if (tid - 2 * KT < d) {
+      qv[tid - 2 * KT] = ls[tid - 2 * KT];
+    }
+    ska = gab, skb = gab + KT, sil = qv, srng = rng;
+  }
   __syncthreads();
   const int jl0 = (tid & 31) * 2, rg = tid >> 5;
   // weights of this thread's 8 rows x 2 columns
@@ -294,6 +414,42 @@ __global__ __launch_bounds__(256) void alpha_quad_kernel(const double* __restric
       const double ai = a[i0 + rg + 8 * r];
       wt[r][0] += ai * b0;
       wt[r][1] += ai * b1;
+    }
+  }
+  if constexpr (GROUPS) {  // the path entries, while wt holds the weights (kinv_trace_kernel's passes)
+    const int nlp = n_ls;
+    double* outp = part + (int64_t)blockIdx.x * ntheta + (ntheta - nlp - 1);  // (sg2, l_path...)
+    const double wp = (ti == tj) ? 1.0 : 2.0;
+    const bool mixed = srng[0] <= srng[3] && srng[2] <= srng[1];  // (no id >= 0 on a side: lo = INT_MAX, hi < 0)
+    if (!mixed) {
+      if (tid <= nlp) outp[tid] = 0.0;
+    } else {
+      for (int pass = 0; pass <= (nlp > 1 ? d : 0); ++pass) {
+        double s = 0.0, s1 = 0.0;
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+          const int il = rg + 8 * r;
+#pragma unroll
+          for (int q = 0; q < 2; ++q) {
+            const int jl = jl0 + q;
+            double pv, pdl;  // (padded rows and columns have id -1: no pair)
+            if (cov::path_dtheta<KERNEL>(ska[il], skb[jl], xa + il * d, xb + jl * d, sil, d, sn2_deriv, pass - 1, pv, pdl)) {
+              s += wt[r][q] * (pass == 0 ? pv : pdl);
+              s1 += wt[r][q] * pdl;
+            }
+          }
+        }
+        s = wg_sum(s, red);
+        if (pass == 0) {
+          if (nlp == 1) s1 = wg_sum(s1, red);
+          if (tid == 0) {
+            outp[0] = wp * s;
+            if (nlp == 1) outp[1] = wp * s1;
+          }
+        } else if (tid == 0) {
+          outp[pass] = wp * s;
+        }
+      }
     }
   }
   double Sf = 0.0, Sn = 0.0, Sl = 0.0;
@@ -346,7 +502,7 @@ __global__ __launch_bounds__(256) void alpha_quad_kernel(const double* __restric
   }
   const double w = (ti == tj) ? 1.0 : 2.0;
   double* out = part + (int64_t)blockIdx.x * ntheta;
-  const int nls = ntheta - (KINDS ? 3 : 2);
+  const int nls = ntheta - (KINDS ? 3 : GROUPS ? 3 + n_ls : 2);
   if (!ard) {
     if constexpr (KINDS) {
 #pragma unroll
@@ -460,17 +616,48 @@ __global__ __launch_bounds__(256) void dl_matrix_kernel(const double* __restrict
   }
 }
 
+// ---- d (within-path term) / d log (sg2, l_path,c) as a matrix (gpx_kernel_path_dtheta_matrix: the unit test of
+// cov::path_dtheta) -----
+// G[t][i][j] (1 + n_lsp blocks of napad x ld): t = 0 the term m sg2 k(r_p) itself, t = 1 + c its derivative by log l_path,c
+// (n_lsp == 1: by the one l_path); ids ga at the scaled points As against gb at Bs, q (d entries).
+template <int KERNEL>
+__global__ __launch_bounds__(256) void path_dtheta_matrix_kernel(const double* __restrict__ As, const int32_t* __restrict__ ga,
+                                                                int64_t na, int64_t napad, const double* __restrict__ Bs,
+                                                                const int32_t* __restrict__ gb, int64_t nb, int d,
+                                                                const double* __restrict__ q, int n_lsp, double sg2,
+                                                                double* __restrict__ G, int64_t ld) {
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= na * nb) return;
+  const int64_t i = e / nb, j = e - i * nb;
+  double v, dl;
+  for (int t = 0; t < n_lsp; ++t) {
+    cov::path_dtheta<KERNEL>(ga[i], gb[j], As + i * d, Bs + j * d, q, d, sg2, n_lsp == 1 ? -1 : t, v, dl);
+    if (t == 0) G[i * ld + j] = v;
+    G[((int64_t)(1 + t) * napad + i) * ld + j] = dl;
+  }
+}
+
 template <int KERNEL>
 void launch_kinv_trace_k(const double* ZT, int64_t ld, int64_t npad, int64_t n, const double* Xs, int d, int ard,
                          double sf2, double sn2, double* part, int ntheta, int P, int rank, int dc_nb, int dc_P,
                          int dc_r, int64_t dc_cols, int dc_snake, const double* wv, hipStream_t st,
-                         const int32_t* kind = nullptr, const double* ls = nullptr, int n_ls = 0, double sn2_deriv = 0.0) {
+                         const int32_t* kind = nullptr, const double* ls = nullptr, int n_ls = 0, double sn2_deriv = 0.0,
+                         bool groups = false) {
   const int tiles = (int)(npad / 128);
   const int64_t ts = (tiles + 7) / 8;
   const int64_t nslots = ts * (ts - 1) / 2 * 64 + ts * 36;
   const int64_t octets = (nslots + 511) / 512, mine = octets > rank ? (octets - rank + P - 1) / P : 0;
   if (mine == 0) return;
   dim3 grid((unsigned)(mine * 512)), block(256);  // whole octets of 8 x 64 slots
+  if (groups) {  // kind: the path ids, ls: q, n_ls: n_ls_path, sn2_deriv: sg2
+    switch (d) {
+      case 1: hipLaunchKernelGGL((kinv_trace_kernel<KERNEL, 1, false, false, true>), grid, block, 0, st, ZT, ld, tiles, npad, n, Xs, d, ard, sf2, sn2, part, ntheta, nslots, P, rank, dc_nb, dc_P, dc_r, dc_cols, dc_snake, wv, kind, ls, n_ls, sn2_deriv); break;
+      case 2: hipLaunchKernelGGL((kinv_trace_kernel<KERNEL, 2, false, false, true>), grid, block, 0, st, ZT, ld, tiles, npad, n, Xs, d, ard, sf2, sn2, part, ntheta, nslots, P, rank, dc_nb, dc_P, dc_r, dc_cols, dc_snake, wv, kind, ls, n_ls, sn2_deriv); break;
+      case 3: hipLaunchKernelGGL((kinv_trace_kernel<KERNEL, 3, false, false, true>), grid, block, 0, st, ZT, ld, tiles, npad, n, Xs, d, ard, sf2, sn2, part, ntheta, nslots, P, rank, dc_nb, dc_P, dc_r, dc_cols, dc_snake, wv, kind, ls, n_ls, sn2_deriv); break;
+      default: hipLaunchKernelGGL((kinv_trace_kernel<KERNEL, 0, false, false, true>), grid, block, 0, st, ZT, ld, tiles, npad, n, Xs, d, ard, sf2, sn2, part, ntheta, nslots, P, rank, dc_nb, dc_P, dc_r, dc_cols, dc_snake, wv, kind, ls, n_ls, sn2_deriv); break;
+    }
+    return;
+  }
   if (kind) {
     if constexpr (cov::differentiable(KERNEL)) {
       switch (d) {
@@ -502,9 +689,17 @@ void launch_kinv_trace_k(const double* ZT, int64_t ld, int64_t npad, int64_t n, 
 template <int KERNEL>
 void launch_alpha_quad_k(const double* alphaT, int64_t ld, int k, int64_t npad, int64_t n, const double* Xs, int d,
                          int ard, double sf2, double sn2, double* part, int ntheta, const double* wv, hipStream_t st,
-                         const int32_t* kind = nullptr, const double* ls = nullptr, int n_ls = 0, double sn2_deriv = 0.0) {
+                         const int32_t* kind = nullptr, const double* ls = nullptr, int n_ls = 0, double sn2_deriv = 0.0,
+                         bool groups = false) {
   const int64_t T = npad / 64;
   dim3 grid((unsigned)(T * (T + 1) / 2)), block(256);
+  if (groups) {
+    if (d == 3)
+      hipLaunchKernelGGL((alpha_quad_kernel<KERNEL, 3, false, true>), grid, block, 0, st, alphaT, ld, k, n, Xs, d, ard, sf2, sn2, part, ntheta, wv, kind, ls, n_ls, sn2_deriv);
+    else
+      hipLaunchKernelGGL((alpha_quad_kernel<KERNEL, 0, false, true>), grid, block, 0, st, alphaT, ld, k, n, Xs, d, ard, sf2, sn2, part, ntheta, wv, kind, ls, n_ls, sn2_deriv);
+    return;
+  }
   if (kind) {
     if constexpr (cov::differentiable(KERNEL)) {
       if (d == 3)
@@ -553,6 +748,27 @@ void launch_alpha_quad_kinds(int kernel, const double* alphaT, int64_t ld, int k
                              const int32_t* kind, const double* ls, int n_ls, double* part, int ntheta, hipStream_t st,
                              const double* wv) {
   cov::dispatch_differentiable(kernel, [&](auto fam) { launch_alpha_quad_k<fam>(alphaT, ld, k, npad, n, Xs, d, ard, sf2, sn2, part, ntheta, wv, st, kind, ls, n_ls, sn2_deriv); });
+}
+
+void launch_kinv_trace_groups(int kernel, const double* ZT, int64_t ld, int64_t npad, int64_t n, const double* Xs, int d,
+                              int ard, double sf2, double sn2, double sg2, const int32_t* group, const double* q,
+                              int n_lsp, double* part, int ntheta, hipStream_t st, const double* wv) {
+  cov::dispatch(kernel, [&](auto fam) { launch_kinv_trace_k<fam>(ZT, ld, npad, n, Xs, d, ard, sf2, sn2, part, ntheta, 1, 0, 0, 0, 0, 0, 0, wv, st, group, q, n_lsp, sg2, true); });
+}
+
+void launch_alpha_quad_groups(int kernel, const double* alphaT, int64_t ld, int k, int64_t npad, int64_t n,
+                              const double* Xs, int d, int ard, double sf2, double sn2, double sg2, const int32_t* group,
+                              const double* q, int n_lsp, double* part, int ntheta, hipStream_t st, const double* wv) {
+  cov::dispatch(kernel, [&](auto fam) { launch_alpha_quad_k<fam>(alphaT, ld, k, npad, n, Xs, d, ard, sf2, sn2, part, ntheta, wv, st, group, q, n_lsp, sg2, true); });
+}
+
+void launch_path_dtheta_matrix(int kernel, const double* As, const int32_t* ga, int64_t na, int64_t napad, const double* Bs,
+                               const int32_t* gb, int64_t nb, int d, const double* q, int n_lsp, double sg2, double* G,
+                               int64_t ld, hipStream_t st) {
+  cov::dispatch(kernel, [&](auto fam) {
+    hipLaunchKernelGGL(path_dtheta_matrix_kernel<fam>, dim3((unsigned)((na * nb + 255) / 256)), dim3(256), 0, st, As, ga, na,
+                       napad, Bs, gb, nb, d, q, n_lsp, sg2, G, ld);
+  });
 }
 
 void launch_dl_matrix(int kernel, const double* As, const int32_t* ka, int64_t na, int64_t napad, const double* Bs,

@@ -288,6 +288,20 @@ void launch_alpha_quad_kinds(int kernel, const double* alphaT, int64_t ld, int k
                              const double* Xs, int d, int ard, double sf2, double sn2, double sn2_deriv,
                              const int32_t* kind, const double* ls, int n_ls, double* part, int ntheta, hipStream_t st,
                              const double* wv = nullptr);
+// Both passes for a fit with path ids (every family; group: the ids, readable up to npad, -1 there; q (d entries) on the
+// device): theta = (lengthscale[0..n_ls), sf2, sn2, sg2, l_path[0..n_lsp)), ntheta = n_ls + 3 + n_lsp; one device
+void launch_kinv_trace_groups(int kernel, const double* ZT, int64_t ld, int64_t npad, int64_t n, const double* Xs, int d,
+                              int ard, double sf2, double sn2, double sg2, const int32_t* group, const double* q,
+                              int n_lsp, double* part, int ntheta, hipStream_t st, const double* wv = nullptr);
+void launch_alpha_quad_groups(int kernel, const double* alphaT, int64_t ld, int k, int64_t npad, int64_t n,
+                              const double* Xs, int d, int ard, double sf2, double sn2, double sg2, const int32_t* group,
+                              const double* q, int n_lsp, double* part, int ntheta, hipStream_t st,
+                              const double* wv = nullptr);
+// G (1 + n_lsp blocks of napad x ld): [0] the within-path term m sg2 k(r_p) of ids ga at As against gb at Bs, [1 + c] its
+// derivative by log l_path,c (cov::path_dtheta); scaled points, q (d entries) on the device
+void launch_path_dtheta_matrix(int kernel, const double* As, const int32_t* ga, int64_t na, int64_t napad, const double* Bs,
+                               const int32_t* gb, int64_t nb, int d, const double* q, int n_lsp, double sg2, double* G,
+                               int64_t ld, hipStream_t st);
 // G (n_ls blocks of napad x ld)[c][i][j] = d cov(obs of kind ka[i] at As_i, obs of kind kb[j] at Bs_j) / d log l_c, i < na,
 // j < nb (cov::element_dl); scaled points, ka / kb null: values; a kind >= 0 needs a differentiable family
 void launch_dl_matrix(int kernel, const double* As, const int32_t* ka, int64_t na, int64_t napad, const double* Bs,

@@ -164,6 +164,7 @@ class GP:
         self._groups_set = False   # gpx_set_path_groups holds path ids for the next fits
         self.path_variance = 0.0   # within-path variance sg2 of the last fit(path_ids=) (0 without any)
         self.path_lengthscale = None  # ... and its lengthscale(s) (None without path ids)
+        self._n_path_ls = 1        # path lengthscales of the last fit: entries of lml_gradient(path=True) after path_variance
         self._alpha = None
         self.info_ = 0
         self.jitter_used_ = self.jitter
@@ -299,13 +300,17 @@ class GP:
                 self._check(self._lib.gpx_set_path_groups(self._h, None, 0, 0.0, None, 0, _abi.MEM_HOST))
                 self._groups_set = False
             self.path_variance, self.path_lengthscale = 0.0, None
+            self._n_path_ls = 1 if lengthscale is None else int(np.size(lengthscale))
             return  # (a model that never had path ids makes no call at all)
         lsp = self.lengthscale if lengthscale is None else lengthscale
         lsp = np.ascontiguousarray(lsp, dtype=np.float64)
+        # an effective fit (one id >= 0, variance > 0) has the lengthscales the library gets; any other the ones given, else 1
+        effective = float(variance) > 0 and bool(np.any(ids >= 0))
         self._check(self._lib.gpx_set_path_groups(self._h, C.c_void_p(ids.ctypes.data), ids.size, float(variance),
                                                   _abi.dptr(lsp), lsp.size, _abi.MEM_HOST))
         self._groups_set = True
         self.path_variance, self.path_lengthscale = float(variance), lsp.copy()
+        self._n_path_ls = lsp.size if effective or lengthscale is not None else 1
 
     @property
     def path_ids_(self):
@@ -394,7 +399,8 @@ class GP:
         path_lengthscale)``) and :meth:`forecast_blocks` forecasts one from its first points.  The attributes
         ``path_variance``, ``path_lengthscale`` and ``path_ids_`` keep what the fit used.  ``path_variance=0`` or ids that
         are all -1 are the plain fit bit for bit; None (the default) means none — also after such a fit.  float64 /
-        float32 on one device, not with ``derivatives``; :meth:`update` and :meth:`lml_gradient` refuse such a fit."""
+        float32 on one device, not with ``derivatives``; :meth:`update` refuses such a fit, and its gradient is
+        ``lml_gradient(path=True)``."""
         ids, pvar, plsp = check_path_args(path_ids, path_variance, path_lengthscale, derivatives=derivatives)
         X, y, noise_weights, kinds = self._with_derivatives(X, y, derivatives, noise_weights)
         return self._fit_rows(X, y, noise_weights, kinds, derivative_noise, (ids, pvar, plsp))
@@ -911,7 +917,7 @@ class GP:
         return float(-0.5 * np.sum(Y * A) - 0.5 * k * self.log_det_
                      - 0.5 * n * k * np.log(2.0 * np.pi))
 
-    def lml_gradient(self, derivative_noise=False):
+    def lml_gradient(self, derivative_noise=False, path=False):
         """``(lml, grad)`` of the last ``fit``: the log marginal likelihood and its analytic
         gradient w.r.t. the LOG hyper-parameters, ordered (lengthscale[0..n_ls), variance, noise)
         — R&W eq. 5.9, 1/2 tr((alpha alpha^T - K^-1) dK/dtheta) (with ``noise_weights``: dK/dlog noise =
@@ -927,10 +933,27 @@ class GP:
         ``derivative_noise=True`` (``gpx_lml_grad_full``; one device, float64): one more entry at the end, the derivative
         by log ``derivative_noise`` — 0 for a fit without derivative observations or with ``derivative_noise == 0``.
         This is the call for a fit with ``derivatives=``, which the default call refuses (its gradient has no room for
-        that entry); on any other fit the leading entries and ``lml`` are the default call's bit for bit."""
+        that entry); on any other fit the leading entries and ``lml`` are the default call's bit for bit.
+
+        ``path=True`` (``gpx_lml_grad_paths``; one device, float64): the gradient of a fit with ``path_ids=``, which the
+        other two calls refuse — ``(lengthscale.., variance, noise, path_variance, path_lengthscale..)``, at the default
+        call's cost (the path terms are evaluated only in the tiles that can hold a pair of one path).  ``variance`` is the
+        derivative of the ``f`` part alone, and the lengthscale entries do not see the path term.  On a fit without
+        effective path ids (none, all -1, or ``path_variance == 0``) ``lml`` and the leading entries are the default call's
+        bit for bit and the path entries are zeros: one for ``path_variance`` and one per entry of the ``path_lengthscale``
+        given to the fit (1 if none was given).  Not together with ``derivative_noise=True`` (``ValueError``): a fit has
+        path ids or derivative observations."""
+        if path and derivative_noise:
+            raise ValueError("path=True and derivative_noise=True exclude each other: a fit has path ids or derivatives")
         if not self._fitted:
             raise RuntimeError("lml_gradient() before a successful fit()")
         lml = C.c_double(0.0)
+        if path:
+            grad = np.empty(self.lengthscale.size + 3 + self._n_path_ls, dtype=np.float64)
+            n_main = self.lengthscale.size + 2
+            self._check(self._lib.gpx_lml_grad_paths(self._h, C.byref(lml), _abi.dptr(grad[:n_main]), _abi.dptr(grad[n_main:]),
+                                                     grad.size - n_main))
+            return float(lml.value), grad
         grad = np.empty(self.lengthscale.size + (3 if derivative_noise else 2), dtype=np.float64)
         call = self._lib.gpx_lml_grad_full if derivative_noise else self._lib.gpx_lml_grad
         self._check(call(self._h, C.byref(lml), _abi.dptr(grad)))
@@ -957,10 +980,10 @@ class GP:
         and the attribute ``derivative_noise`` holds the result (``ValueError`` without ``derivatives`` or when it starts
         at 0: log-space cannot leave 0).  Left out of ``params`` it stays fixed.
 
-        ``path_ids``, ``path_variance`` and ``path_lengthscale`` as for :meth:`fit`.  A model with path ids has no
-        analytic gradient yet, so the search then runs on central differences; ``params`` may name ``"path_variance"``
-        (which must start above 0) and ``"path_lengthscale"`` (every entry moves), and the attributes of those names
-        hold the result."""
+        ``path_ids``, ``path_variance`` and ``path_lengthscale`` as for :meth:`fit`.  The analytic gradient of such a
+        model is ``lml_gradient(path=True)``, at the same cost (float64 on one device; anything else, and
+        ``jac="3-point"``, runs on central differences); ``params`` may name ``"path_variance"`` (which must start above
+        0) and ``"path_lengthscale"`` (every entry moves), and the attributes of those names hold the result."""
         from scipy.optimize import minimize
         known = ("lengthscale", "variance", "noise", "derivative_noise", "path_variance", "path_lengthscale")
         names = [p for p in known if p in params]
@@ -1013,7 +1036,8 @@ class GP:
                     i += 1
 
         best = {"f": np.inf, "v": pack()}
-        analytic = jac == "analytic" and self.dtype == "float64" and ids is None  # (no analytic gradient with path ids)
+        path_grad = ids is not None   # a fit with path ids: the gradient with the path_variance / path_lengthscale entries
+        analytic = jac == "analytic" and self.dtype == "float64"
         if analytic and (self.world > 1 or self._is_group or self._host_comm is not None):
             # sharded: the gradient needs the replicated-factor mode, which the library picks from N
             # and the card's memory at fit time — ask it once (every rank gets the same answer)
@@ -1024,13 +1048,16 @@ class GP:
                 analytic = False
             except np.linalg.LinAlgError:
                 pass
-        # columns of the full gradient (lengthscale.., variance, noise, derivative_noise) that move
+        # columns of the full gradient that move: (lengthscale.., variance, noise, derivative_noise), or with path ids
+        # (lengthscale.., variance, noise, path_variance, path_lengthscale..)
         cols = []
         for p in names:
-            if p in ("path_variance", "path_lengthscale"):
-                continue  # (central differences only: `cols` is not read then)
-            cols.extend(range(n_ls) if p == "lengthscale" else
-                        [n_ls + ("variance", "noise", "derivative_noise").index(p)])
+            if p == "lengthscale":
+                cols.extend(range(n_ls))
+            elif p == "path_lengthscale":
+                cols.extend(range(n_ls + 3, n_ls + 3 + self.path_lengthscale.size))
+            else:
+                cols.append(n_ls + ("variance", "noise", "path_variance" if path_grad else "derivative_noise").index(p))
 
         class _NoAnalyticGradient(Exception):
             pass
@@ -1042,7 +1069,8 @@ class GP:
                 self.fit(X, y, **fit_kw())
                 if analytic:
                     try:
-                        lml, full = self.lml_gradient(derivative_noise=full_grad)
+                        lml, full = (self.lml_gradient(path=True) if path_grad else
+                                     self.lml_gradient(derivative_noise=full_grad))
                     except _abi.GpxError as e:
                         # no gradient for this model after all (factor only held distributed, or no
                         # room for the N x N L^-T buffer): free what the attempt allocated and let the

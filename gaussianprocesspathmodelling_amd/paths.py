@@ -429,7 +429,8 @@ def step_noise_weights(Yn, n_paths):
 
 def fit_path_models(trajs, clusters, inputs=("t",), targets=("x", "y"), devices=None, optimize=False,
                     lengthscale=0.25, variance=1.0, noise=0.05, step_noise=False, velocities=None, velocity_noise=0.05,
-                    learn_velocity_noise=False, within_path=False, path_variance=0.25, path_lengthscale=None, **gp_kwargs):
+                    learn_velocity_noise=False, within_path=False, path_variance=0.25, path_lengthscale=None,
+                    learn_path_parameters=False, **gp_kwargs):
     """One exact GP per cluster of ``clusters`` = {cluster id: [path ids]} — what
     :func:`kmeans` (``kmeansclustering``, GPmap.py:36-93) returns — modelling the cluster's paths
     as (x(t), y(t)); the modelling step the reference's title names and its clustering prepares
@@ -453,7 +454,10 @@ def fit_path_models(trajs, clusters, inputs=("t",), targets=("x", "y"), devices=
     variance ``path_variance`` (normalised target units) and lengthscale ``path_lengthscale`` (None: ``lengthscale``):
     ``GP.fit(path_ids=repeat(arange(P), L))`` per cluster.  Whole-path likelihoods then stay calibrated however many paths
     a cluster has, and :meth:`PathModel.forecast` / :func:`forecast_paths` continue a partly observed path.  Not with
-    ``velocities``; with ``optimize`` the search runs on central differences and the two are kept fixed.
+    ``velocities``.  ``optimize`` keeps the two fixed unless ``learn_path_parameters`` is set: then each cluster learns its
+    own with the others (analytic gradient, ``GP.lml_gradient(path=True)``), starting from the values passed, and the
+    model's ``gp.path_variance`` and ``gp.path_lengthscale`` report them (``ValueError`` without ``within_path`` or without
+    ``optimize``).
     Returns {cluster id: :class:`PathModel`}; empty clusters are skipped."""
     import threading
     from concurrent.futures import ThreadPoolExecutor
@@ -474,6 +478,8 @@ def fit_path_models(trajs, clusters, inputs=("t",), targets=("x", "y"), devices=
         raise ValueError(f"velocities need 't' among the inputs, have {tuple(inputs)}")
     if within_path and velocities:
         raise ValueError("within_path cannot be combined with velocities (path ids and derivative observations)")
+    if learn_path_parameters and not (within_path and optimize):
+        raise ValueError("learn_path_parameters needs within_path=True and optimize=True")
     jobs = []
     for cid, keys in clusters.items():
         keys = list(keys)
@@ -522,6 +528,8 @@ def fit_path_models(trajs, clusters, inputs=("t",), targets=("x", "y"), devices=
             if optimize:
                 if learn_velocity_noise and der is not None:
                     kw["params"] = ("lengthscale", "variance", "noise", "derivative_noise")
+                if learn_path_parameters:
+                    kw["params"] = ("lengthscale", "variance", "noise", "path_variance", "path_lengthscale")
                 gp.optimize(X, Yn, noise_weights=w, **kw)  # leaves the model fitted at the best point
             else:
                 gp.fit(X, Yn, noise_weights=w, **kw)

@@ -355,7 +355,8 @@ int gpx_get_observation_kinds(gpx_handle* h, int32_t* out /* (N) host */);
  * Otherwise GPX_E_UNSUPPORTED before anything is computed or exchanged, the previous fit still valid: a fit on device
  * groups, shards, handles with a communicator, GPX_MIXED handles, and handles that also have observation kinds set; on a
  * fit made with path ids: gpx_append / gpx_append_weighted (fit the concatenated data), gpx_lml_grad and
- * gpx_lml_grad_full (these evaluate training-pair covariances matrix-free, without the path term). */
+ * gpx_lml_grad_full (these evaluate training-pair covariances matrix-free, without the path term; gpx_lml_grad_paths is
+ * the gradient of such a fit). */
 int gpx_set_path_groups(gpx_handle* h, const int32_t* group, int64_t n, double sg2, const double* ls_path,
                         int32_t n_ls_path, int32_t mem_kind);
 /* The path ids of the current fit, all -1 when it was made without any (or with sg2 == 0).  GPX_E_ARG without a fit. */
@@ -398,6 +399,20 @@ int gpx_lml_grad(gpx_handle* h, double* lml, double* grad);
  * (no fit with a derivative row exists there: gpx_lml_grad is their call).  A failed call writes nothing and leaves the
  * fit valid. */
 int gpx_lml_grad_full(gpx_handle* h, double* lml, double* grad /* n_ls + 3 */);
+/* The gradient of a fit with path ids (gpx_set_path_groups; additive to ABI v6): grad as gpx_lml_grad's, and grad_path[0] =
+ * d lml / d log sg2, grad_path[1 + c] = d lml / d log l_path,c.  With e_c = (x_ic - x_jc) / l_c, q_c = (l_c / l_path,c)^2,
+ * r_p^2 = sum_c q_c e_c^2 and m_ij = [id_i == id_j >= 0]:  dK / dlog sg2 = m sg2 k(r_p),  dK / dlog l_path,c = m kd(r_p; sg2)
+ * q_c e_c^2 (kd of the family, csrc/gpx_cov.h: path_dtheta; n_ls_path == 1: the sum over c);  dK / dlog sf2 = sf2 k(r), the f
+ * part alone, and dK / dlog l_c is the plain one: the path term does not depend on l.  Evaluated in the epilogue of the same
+ * fused K^-1 trace pass, only in tiles that can hold a same-path pair: the cost is gpx_lml_grad's.  On a fit made by the
+ * path builder n_path must be 1 + n_ls_path of that fit (GPX_E_ARG otherwise).  On any other fit — no ids, every id -1 or
+ * sg2 == 0 — *lml and grad are gpx_lml_grad's bit for bit, by the same launches, and the n_path >= 0 entries of grad_path
+ * are set to exactly 0 (grad_path may be NULL when n_path == 0).  Single-device GPX_F64 handles, with or without noise
+ * weights.  GPX_E_UNSUPPORTED on other element types, on shards, device groups and handles that own a communicator (no fit
+ * with path ids exists there) and on a fit with derivative rows (gpx_lml_grad_full is its gradient).  A failed call writes
+ * nothing and leaves the fit valid.  Timings: grad_trtri, grad_trace, grad_total, as for the other two. */
+int gpx_lml_grad_paths(gpx_handle* h, double* lml, double* grad /* n_ls + 2, as gpx_lml_grad */,
+                       double* grad_path /* n_path: d/dlog sg2, then d/dlog l_path,c */, int32_t n_path);
 int gpx_logdet(gpx_handle* h, double* out);
 /* Frees what only the NEXT predict / gradient call would use (the V^T batch, the L^-T buffer of
  * gpx_lml_grad, per-tile partials, compact block buffers, the buffers of the joint-posterior calls); the fit itself (factor, alpha, block
@@ -468,6 +483,15 @@ int gpx_kernel_dl_matrix(int32_t kernel, const double* A, const int32_t* ka, int
 int gpx_kernel_path_matrix(int32_t kernel, int32_t dtype, const double* A, const int32_t* ga, int64_t na, const double* B,
                            const int32_t* gb, int64_t nb, int32_t d, const double* lengthscale, int32_t n_ls, double sf2,
                            const double* ls_path, int32_t n_ls_path, double sg2, double* K);
+/* kernel unit-test entry point (host buffers, fp64; additive to ABI v6): G (1 + n_ls_path, na, nb): G[0][a][b] = [ga_a == gb_b
+ * and ga_a >= 0] sg2 k(A_a, B_b; l_path), the within-path term of gpx_kernel_path_matrix, and G[1 + c] its derivative by
+ * log l_path,c (n_ls_path == 1: by the one l_path) — what gpx_lml_grad_paths contracts with K^-1, by the device function its
+ * epilogues call.  Every family, GPX_KERNEL_MATERN12 included (its derivative is 0 at coincident points).  GPX_E_ARG, before
+ * any device call: a NULL pointer, na or nb < 1, d outside [1, 32], n_ls_path not 1 or d, an unknown family, sg2 negative or
+ * not finite, a lengthscale not > 0 or not finite, an id below -1. */
+int gpx_kernel_path_dtheta_matrix(int32_t kernel, const double* A, const int32_t* ga, int64_t na, const double* B,
+                                  const int32_t* gb, int64_t nb, int32_t d, const double* ls_path, int32_t n_ls_path,
+                                  double sg2, double* G /* (1 + n_ls_path, na, nb) */);
 /* in-place lower Cholesky of A (n,n), lda = n; n multiple of 64.  The strictly upper
  * triangle is never read and is scratch on return (diagonal tiles are updated whole).
  * block = panel width (0 = default). */

@@ -6,7 +6,13 @@ With --devices n: the same gradient on a device group of n ranks (one GPU box: t
 card, so this checks the sharded gradient at scale against the single-GPU one, it is not a speed-up).
 With --derivatives: a quarter of the ntrain rows are derivative observations (gpx_lml_grad_full, the KINDS instantiations
 of the trace kernels), beside the value-only gradient at the same N in the same run, and the wall time of
-GP.optimize(maxiter=3) on the same data with the analytic gradient and with central differences."""
+GP.optimize(maxiter=3) on the same data with the analytic gradient and with central differences.
+With --paths: the gradient of a fit with path ids (gpx_lml_grad_paths, the GROUPS instantiations of the trace kernels) at
+N = 16896 = 512 paths x 33, Matern-3/2, for d = 1 and for d = 3 ARD: grad_total / grad_trace on the grouped fit beside
+gpx_lml_grad on the plain fit of the same data on the same handle, alternating, one warm-up and five repeats each (medians
+and every repeat are reported); the same with the rows shuffled (every tile then takes the path passes); and the wall time
+of GP.optimize(maxiter=3) over all five (d = 1) or nine (d = 3) parameters with the analytic gradient and with
+jac="3-point".  --ntrain sets N (rounded down to whole paths)."""
 import argparse, json, os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -17,8 +23,68 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--ntrain", type=int, default=65536)
 ap.add_argument("--devices", type=int, default=0)
 ap.add_argument("--derivatives", action="store_true")
+ap.add_argument("--paths", action="store_true")
 a = ap.parse_args()
 N = a.ntrain
+if a.paths:
+    L, REPS = 33, 5
+    P = (16896 if a.ntrain == 65536 else a.ntrain) // L          # (the default size of this mode is 512 paths)
+    N = P * L
+    keys = ("grad_total", "grad_trtri", "grad_trace")
+    out = {"config": f"N={N} ({P} paths x {L}) Matern-3/2 fp64, sf2 1.5 sg2 0.4 sn2 1e-2, 1 warm-up + {REPS} repeats, medians"}
+
+    def data(d, rng):
+        # one cluster mean for all, a smooth deviation per path, noise: what fit_path_models sees (sorted ids)
+        t = np.sort(rng.uniform(0.0, 1.0, (P, L)), axis=1)
+        cols = [t] + [np.sin((c + 1.0) * t) + 0.02 * rng.standard_normal(t.shape) for c in range(1, d)]
+        X = np.stack(cols, axis=-1).reshape(N, d)
+        ph, am = rng.uniform(0.0, 6.28, (P, 1)), 0.6 * rng.standard_normal((P, 1))
+        y = (np.sin(5.0 * t) + 0.5 * np.cos(11.0 * t) + am * np.sin(9.0 * t + ph) + 0.1 * rng.standard_normal(t.shape)).reshape(N)
+        return np.ascontiguousarray(X), np.ascontiguousarray(y), np.repeat(np.arange(P), L).astype(np.int32)
+
+    def med(rows):
+        return {k + "_ms": float(np.median([r[k] for r in rows])) for k in keys} | {"repeats": rows}
+
+    for d in (1, 3):
+        rng = np.random.default_rng(12345 + d)
+        X, y, ids = data(d, rng)
+        ls = np.array([0.25]) if d == 1 else np.linspace(0.25, 0.4, d)
+        lsp = np.array([0.1]) if d == 1 else np.linspace(0.1, 0.15, d)
+        res = {}
+        with GP("matern32", ls, 1.5, 1e-2) as gp:
+            for order in ("sorted", "shuffled"):
+                if order == "shuffled":
+                    perm = rng.permutation(N)
+                    X, y, ids = np.ascontiguousarray(X[perm]), np.ascontiguousarray(y[perm]), np.ascontiguousarray(ids[perm])
+                kw = dict(path_ids=ids, path_variance=0.4, path_lengthscale=lsp)
+                rows = {"plain": [], "paths": []}
+                for rep in range(1 + REPS):                        # alternating; the first round is the warm-up
+                    gp.fit(X, y); gp.lml_gradient()
+                    if rep:
+                        rows["plain"].append({k: gp.timings_[k] for k in keys})
+                    gp.fit(X, y, **kw); lml, grad = gp.lml_gradient(path=True)
+                    if rep:
+                        rows["paths"].append({k: gp.timings_[k] for k in keys})
+                r = {"plain_gpx_lml_grad": med(rows["plain"]), "gpx_lml_grad_paths": med(rows["paths"]), "lml": lml,
+                     "grad": grad.tolist()}
+                r["grad_total_ratio"] = r["gpx_lml_grad_paths"]["grad_total_ms"] / r["plain_gpx_lml_grad"]["grad_total_ms"]
+                r["trace_ratio"] = r["gpx_lml_grad_paths"]["grad_trace_ms"] / r["plain_gpx_lml_grad"]["grad_trace_ms"]
+                res[order] = r
+            X, y, ids = data(d, np.random.default_rng(12345 + d))   # the sorted rows again
+            params = ("lengthscale", "variance", "noise", "path_variance", "path_lengthscale")
+            for jac in ("analytic", "3-point"):
+                walls = []
+                for rep in range(2):                               # (the first run imports the optimiser)
+                    gp.lengthscale, gp.variance, gp.noise = ls.copy(), 1.5, 1e-2
+                    t0 = time.perf_counter()
+                    o = gp.optimize(X, y, params=params, maxiter=3, jac=jac, path_ids=ids, path_variance=0.4,
+                                    path_lengthscale=lsp)
+                    walls.append(time.perf_counter() - t0)
+                res[f"optimize_maxiter3_{jac}"] = {"wall_s": walls[1], "first_wall_s": walls[0], "nfev": int(o.nfev),
+                                                   "lml": -float(o.fun), "parameters": int(o.x.size)}
+        out[f"d{d}"] = res
+    print(json.dumps(out))
+    sys.exit(0)
 if a.derivatives:
     rng = np.random.default_rng(12345)
     Nd = N // 4
