@@ -1384,6 +1384,8 @@ int fit_impl(gpx_handle* h, const void* X, const void* y, int64_t N, int32_t d, 
 // for), and the point, block-inverse and panel buffers grow with it.  Every allocation happens before anything is touched:
 // on GPX_E_NOMEM the fit is as it was.
 // with_weights: the fit has noise weights, or the new points bring some — the weight vector follows the same capacity.
+// So do the kinds or path ids of a fit that has them and its finished diagonal terms: the N entries of the fit are kept,
+// and the kinds / ids are -1 from there to the new capacity (the builders read them up to the padded size).
 template <typename T>
 int append_room(gpx_handle* h, int64_t Nnew, bool with_weights) {
   const int64_t skew = ld_skew<T>(), cap0 = h->ld - skew, NpadNew = round_up(Nnew, TILE), want = round_up(h->reserve, TILE);
@@ -1395,12 +1397,17 @@ int append_room(gpx_handle* h, int64_t Nnew, bool with_weights) {
     DevBuf* buf;
     size_t need, keep;
     DevBuf fresh;
+    bool minus_one = false;  // kinds / ids: the fresh buffer holds -1 before the kept entries are copied in
   } g[] = {{&h->X, (size_t)cap * d * sizeof(T), (size_t)N * d * sizeof(T), {}},
            {&h->Y, (size_t)cap * k * sizeof(T), (size_t)N * k * sizeof(T), {}},
            {&h->Xs, (size_t)cap * d * sizeof(T), (size_t)Npad * d * sizeof(T), {}},
            {&h->Winv, (size_t)(cap / KB) * KB * KB * sizeof(T), (size_t)(Npad / KB) * KB * KB * sizeof(T), {}},
            {&h->Wblk, (size_t)((cap + nb - 1) / nb) * nb * nb * sizeof(T), (size_t)(R0 / nb) * nb * nb * sizeof(T), {}},
-           {&h->Wfit, with_weights ? (size_t)cap * sizeof(T) : 0, h->weighted ? (size_t)N * sizeof(T) : 0, {}}};
+           {&h->Wfit, with_weights ? (size_t)cap * sizeof(T) : 0, h->weighted ? (size_t)N * sizeof(T) : 0, {}},
+           {&h->Kfit, h->kinded ? (size_t)cap * sizeof(int32_t) : 0, (size_t)N * sizeof(int32_t), {}, true},
+           {&h->Dfit, h->kinded ? (size_t)cap * sizeof(T) : 0, (size_t)N * sizeof(T), {}},
+           {&h->Gfit, h->grouped ? (size_t)cap * sizeof(int32_t) : 0, (size_t)N * sizeof(int32_t), {}, true},
+           {&h->Gdiag, h->grouped ? (size_t)cap * sizeof(T) : 0, (size_t)N * sizeof(T), {}}};
   const size_t kbytes = (size_t)(cap + RHS_ROWS) * ld * sizeof(T);
   const size_t pbytes = (size_t)2 * (cap + RHS_ROWS) * h->ldp * sizeof(T);
   const bool newK = relayout || h->K.cap < kbytes, newP = h->P.cap < pbytes;
@@ -1432,8 +1439,10 @@ int append_room(gpx_handle* h, int64_t Nnew, bool with_weights) {
     (void)hipGetLastError();
     return fail(h, GPX_E_NOMEM, msg);  // (the fresh buffers free themselves; the fit is untouched)
   }
-  for (Grow& x : g)
+  for (Grow& x : g) {
+    if (x.fresh.p && x.minus_one) HIPCHK(h, hipMemsetAsync(x.fresh.p, 0xFF, x.need, h->st));
     if (x.fresh.p && x.keep) HIPCHK(h, hipMemcpyAsync(x.fresh.p, x.buf->p, x.keep, hipMemcpyDeviceToDevice, h->st));
+  }
   T* zT = (T*)h->zT;
   if (newK) {  // the factor's lower triangle; z^T keeps its row (append_restart moves it when Npad changes)
     T* dst = (T*)Knew.p;
@@ -1500,14 +1509,36 @@ int append_restart(gpx_handle* h, int64_t Nold, int64_t Nnew, const void* Xnew, 
       }
       launch_scale_points<T>((const T*)h->X.p + R1 * d, Nnew - R1, rows, d, (const double*)h->ls.p, h->n_ls, Xs + R1 * d,
                              h->st);
-      if (R0 > 0)  // left part of the 128-row tiles that hold a new point: K(x_i, x_j), j < R0
-        launch_kbuild_cross<T>(h->cfg.kernel, Xs + R1 * d, Nnew - R1, rows, Xs, R0, R0, d, h->sf2, dK + R1 * ld, ld, h->st);
-      if (h->weighted)  // the rebuilt square needs the stored weights of rows [R0, Nold) beside the new points'
-        launch_kbuild_sym_w<T>(h->cfg.kernel, Xs + R0 * d, Nnew - R0, np, d, h->sf2, (const T*)h->Wfit.p + R0, h->sn2, h->jitter,
-                               dK + R0 * ld + R0, ld, h->st);
-      else
-        launch_kbuild_sym<T>(h->cfg.kernel, Xs + R0 * d, Nnew - R0, np, d, h->sf2, h->sn2 + h->jitter, dK + R0 * ld + R0, ld,
-                             h->st);
+      // A fit with kinds or path ids: the same two builds by the KINDS / GROUPS builders, with the side channel of the rows
+      // ([R1, Nnew) of the left part, [R0, Nnew) of the square: both offsets are multiples of 128, and the entries from Nnew
+      // to the capacity are -1) and the finished diagonal terms of rows [R0, Nnew) from the stored and the new weights.
+      const T* wfit = h->weighted ? (const T*)h->Wfit.p + R0 : nullptr;
+      if (h->grouped) {
+        const int32_t* G = (const int32_t*)h->Gfit.p;
+        launch_kinds_diag<T>(G + R0, wfit, Nnew - R0, h->sn2, h->sn2, h->jitter, (T*)h->Gdiag.p + R0, h->st);
+        if (R0 > 0)  // (a tile of new rows whose ids meet none of its columns' skips the path term)
+          launch_kbuild_cross_g<T>(h->cfg.kernel, Xs + R1 * d, G + R1, Nnew - R1, rows, Xs, G, R0, R0, d, h->sf2,
+                                   (const double*)h->Gq.p, h->sg2, dK + R1 * ld, ld, h->st);
+        launch_kbuild_sym_g<T>(h->cfg.kernel, Xs + R0 * d, Nnew - R0, np, d, h->sf2, G + R0, (const double*)h->Gq.p, h->sg2,
+                               (const T*)h->Gdiag.p + R0, dK + R0 * ld + R0, ld, h->st);
+      } else if (h->kinded) {
+        const int32_t* Kd = (const int32_t*)h->Kfit.p;
+        launch_kinds_diag<T>(Kd + R0, wfit, Nnew - R0, h->sn2, h->sn2_deriv, h->jitter, (T*)h->Dfit.p + R0, h->st);
+        if (R0 > 0)
+          launch_kbuild_cross_kk<T>(h->cfg.kernel, Xs + R1 * d, Kd + R1, Nnew - R1, rows, Xs, Kd, R0, R0, d, h->sf2,
+                                    (const double*)h->ls.p, h->n_ls, dK + R1 * ld, ld, h->st);
+        launch_kbuild_sym_k<T>(h->cfg.kernel, Xs + R0 * d, Nnew - R0, np, d, h->sf2, Kd + R0, (const double*)h->ls.p, h->n_ls,
+                               (const T*)h->Dfit.p + R0, dK + R0 * ld + R0, ld, h->st);
+      } else {
+        if (R0 > 0)  // left part of the 128-row tiles that hold a new point: K(x_i, x_j), j < R0
+          launch_kbuild_cross<T>(h->cfg.kernel, Xs + R1 * d, Nnew - R1, rows, Xs, R0, R0, d, h->sf2, dK + R1 * ld, ld, h->st);
+        if (h->weighted)  // the rebuilt square needs the stored weights of rows [R0, Nold) beside the new points'
+          launch_kbuild_sym_w<T>(h->cfg.kernel, Xs + R0 * d, Nnew - R0, np, d, h->sf2, (const T*)h->Wfit.p + R0, h->sn2,
+                                 h->jitter, dK + R0 * ld + R0, ld, h->st);
+        else
+          launch_kbuild_sym<T>(h->cfg.kernel, Xs + R0 * d, Nnew - R0, np, d, h->sf2, h->sn2 + h->jitter, dK + R0 * ld + R0,
+                               ld, h->st);
+      }
     }
     {
       PhaseScope ps(h, &tm.chol);
@@ -1531,9 +1562,12 @@ int append_restart(gpx_handle* h, int64_t Nold, int64_t Nnew, const void* Xnew, 
   return finish_call(h);
 }
 
+// side (gpx_append_rows on a fit with kinds or path ids; host, m entries, checked): the new rows' kinds (h->kinded) or path
+// ids (h->grouped).  They are staged behind the fit's own on the device before the restart; the host copies and has_deriv
+// follow once the restart has gone through, and a failed append takes the staged entries back (-1).
 template <typename T>
 int append_impl(gpx_handle* h, const void* Xnew, const void* ynew, const void* wnew, int64_t m, int32_t mem_kind,
-                int64_t* info) {
+                int64_t* info, const int32_t* side = nullptr) {
   const int64_t Nold = h->N, Nnew = Nold + m;
   gpx_timings& tm = h->tm;
   tm.h2d = tm.kbuild = tm.chol = tm.solve = tm.logdet = tm.fit_total = 0;
@@ -1559,6 +1593,11 @@ int append_impl(gpx_handle* h, const void* Xnew, const void* ynew, const void* w
     }
     h->weighted = true;
   }
+  int32_t* dside = !side ? nullptr : (int32_t*)(h->grouped ? h->Gfit.p : h->Kfit.p);
+  if (side) {  // (the caller's host copy is only read inside this block: an early return below leaves no copy in flight)
+    HIPCHK(h, hipMemcpyAsync(dside + Nold, side, (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice, h->st));
+    HIPCHK(h, hipStreamSynchronize(h->st));
+  }
   h->fitted = false;  // until the restart (or the restart back) has gone through
   h->alphaT = nullptr;
   h->alpha_ready = false;
@@ -1581,10 +1620,16 @@ int append_impl(gpx_handle* h, const void* Xnew, const void* ynew, const void* w
   if (*info > 0) {  // not positive definite with the new points: the same restart with none of them is the previous fit
     int back = 0;
     if ((rc = begin_call(h))) return rc;
+    if (side) HIPCHK(h, hipMemsetAsync(dside + Nold, 0xFF, (size_t)m * sizeof(int32_t), h->st));  // -1 beyond the fit again
     if ((rc = restart(Nold, nullptr, nullptr, &back))) return rc;
     if (back != INT_MAX) return fail(h, GPX_E_HIP, "gpx_append: the previous fit could not be restored");
     Nfit = Nold;
     h->weighted = was_weighted;  // (the weights of the first Nold points were never touched)
+  } else if (side) {  // (the restart has finished: nothing reads the host vectors asynchronously any more)
+    std::vector<int32_t>& host = h->grouped ? h->groups_fit : h->kinds_fit;
+    host.insert(host.end(), side, side + m);
+    if (h->kinded)
+      for (int64_t i = 0; i < m; ++i) h->has_deriv |= side[i] >= 0;
   }
   h->N = Nfit;
   h->Npad = round_up(Nfit, TILE);
@@ -3071,6 +3116,54 @@ int gpx_append_weighted(gpx_handle* h, const void* Xnew, const void* ynew, const
 }
 GPX_CATCH_ALL
 
+int gpx_append_rows(gpx_handle* h, const void* Xnew, const void* ynew, const void* wnew, const int32_t* kind_new,
+                    const int32_t* group_new, int64_t m, int32_t mem_kind, int64_t* info) try {
+  if (!h) return GPX_E_ARG;
+  if (!Xnew || !ynew || !info || m <= 0) return fail(h, GPX_E_ARG, "gpx_append_rows: bad argument");
+  if (mem_kind != GPX_MEM_HOST && mem_kind != GPX_MEM_DEVICE) return fail(h, GPX_E_ARG, "gpx_append_rows: bad mem_kind");
+  int rc;
+  if ((rc = posterior_refused(h, "gpx_append_rows"))) return rc;
+  if (!h->fitted) return fail(h, GPX_E_ARG, "gpx_append_rows: handle has no successful fit");
+  if (m > (int64_t)INT_MAX - 4096 - h->N) return fail(h, GPX_E_ARG, "gpx_append_rows: N + m too large");
+  // the kinds and the ids are checked in host copies (NULL: all -1), which also feed the fit's host vectors afterwards
+  std::vector<int32_t> kinds((size_t)m, -1), ids((size_t)m, -1);
+  auto fetch = [&](const int32_t* src, std::vector<int32_t>& dst) -> int {
+    if (!src) return GPX_OK;
+    if (mem_kind == GPX_MEM_HOST) {
+      std::copy(src, src + m, dst.begin());
+      return GPX_OK;
+    }
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    HIPCHK(h, hipMemcpy(dst.data(), src, (size_t)m * sizeof(int32_t), hipMemcpyDefault));
+    return GPX_OK;
+  };
+  if ((rc = fetch(kind_new, kinds)) || (rc = fetch(group_new, ids))) return rc;
+  bool deriv = false, path = false;
+  for (int64_t i = 0; i < m; ++i) {
+    if (kinds[i] < -1 || kinds[i] >= h->d)
+      return fail(h, GPX_E_ARG, "gpx_append_rows: a kind is -1 (a value) or a dimension in [0, d)");
+    if (ids[i] < -1) return fail(h, GPX_E_ARG, "gpx_append_rows: a path id is -1 (no path) or >= 0");
+    deriv |= kinds[i] >= 0;
+    path |= ids[i] >= 0;
+  }
+  if (deriv && !cov::differentiable(h->cfg.kernel))
+    return fail(h, GPX_E_UNSUPPORTED, "gpx_append_rows: derivative observations: " MATERN12_NO_GRAD);
+  if (deriv && !h->kinded)
+    return fail(h, GPX_E_ARG, "gpx_append_rows: a derivative row needs a fit made with observation kinds set "
+                              "(gpx_set_observation_kinds): this fit has no sn2_deriv");
+  if (path && !h->grouped)
+    return fail(h, GPX_E_ARG, "gpx_append_rows: a path id >= 0 needs a fit made with path ids (gpx_set_path_groups, sg2 > 0)");
+  // a plain or weighted fit (then every kind and id is -1): gpx_append_weighted itself.  A fit made with kinds set stays
+  // one, also when neither it nor the new rows hold a derivative: it keeps its sn2_deriv for the rows of a later append.
+  if (!h->kinded && !h->grouped) return append_entry(h, Xnew, ynew, wnew, m, mem_kind, info);
+  if ((rc = begin_call(h))) return rc;
+  if (wnew && (rc = check_weights(h, "gpx_append_rows", wnew, m, mem_kind, h->cfg.dtype == GPX_F32 ? 4 : 8, h->st)))
+    return rc;
+  const int32_t* side = h->grouped ? ids.data() : kinds.data();
+  return BY_DTYPE(h, append_impl, h, Xnew, ynew, wnew, m, mem_kind, info, side);
+}
+GPX_CATCH_ALL
+
 int gpx_set_noise_weights(gpx_handle* h, const void* w, int64_t n, int32_t mem_kind) try {
   if (!h) return GPX_E_ARG;
   if (mem_kind != GPX_MEM_HOST && mem_kind != GPX_MEM_DEVICE) return fail(h, GPX_E_ARG, "gpx_set_noise_weights: bad mem_kind");
@@ -3570,6 +3663,76 @@ int gpx_kernel_path_matrix(int32_t kernel, int32_t dtype, const double* A, const
   if (dtype == GPX_F32)
     return kernel_path_matrix_t<float>(kernel, A, ga, na, B, gb, nb_, d, lengthscale, n_ls, sf2, ls_path, n_ls_path, sg2, K);
   return kernel_path_matrix_t<double>(kernel, A, ga, na, B, gb, nb_, d, lengthscale, n_ls, sf2, ls_path, n_ls_path, sg2, K);
+}
+GPX_CATCH_ALL
+
+extern "C++" {
+namespace {
+template <typename T>
+int kernel_mixed_matrix_t(int32_t kernel, const double* A, const int32_t* ka, int64_t na, const double* B, const int32_t* kb,
+                          int64_t nb_, int32_t d, const double* lengthscale, int32_t n_ls, double sf2, double* K) {
+  Scratch sc;
+  if (!sc.ok) return GPX_E_HIP;
+  hipStream_t st = sc.h.st;
+  const int64_t napad = round_up(na, 64), nbpad = round_up(nb_, 64), ld = nbpad;
+  T *dA = nullptr, *dB = nullptr, *dAs = nullptr, *dBs = nullptr, *dK = nullptr;
+  double* dls = nullptr;
+  int32_t *dka = nullptr, *dkb = nullptr;
+  std::vector<T> hA(A, A + na * d), hB(B, B + nb_ * d), host((size_t)napad * ld);  // (rounded to T on the host)
+  int rc = GPX_OK;
+  TCHK(hipMalloc(&dA, (size_t)na * d * sizeof(T)));
+  TCHK(hipMalloc(&dB, (size_t)nb_ * d * sizeof(T)));
+  TCHK(hipMalloc(&dAs, (size_t)napad * d * sizeof(T)));
+  TCHK(hipMalloc(&dBs, (size_t)nbpad * d * sizeof(T)));
+  TCHK(hipMalloc(&dls, MAX_D * 8));
+  TCHK(hipMalloc(&dka, (size_t)napad * 4));
+  TCHK(hipMalloc(&dkb, (size_t)nbpad * 4));
+  TCHK(hipMalloc(&dK, (size_t)napad * ld * sizeof(T)));
+  TCHK(hipMemcpyAsync(dA, hA.data(), (size_t)na * d * sizeof(T), hipMemcpyHostToDevice, st));
+  TCHK(hipMemcpyAsync(dB, hB.data(), (size_t)nb_ * d * sizeof(T), hipMemcpyHostToDevice, st));
+  TCHK(hipMemcpyAsync(dls, lengthscale, (size_t)n_ls * 8, hipMemcpyHostToDevice, st));
+  TCHK(hipMemsetAsync(dka, 0xFF, (size_t)napad * 4, st));  // -1 beyond the valid kinds, and for a side without any
+  TCHK(hipMemsetAsync(dkb, 0xFF, (size_t)nbpad * 4, st));
+  if (ka) TCHK(hipMemcpyAsync(dka, ka, (size_t)na * 4, hipMemcpyHostToDevice, st));
+  if (kb) TCHK(hipMemcpyAsync(dkb, kb, (size_t)nb_ * 4, hipMemcpyHostToDevice, st));
+  launch_scale_points<T>(dA, na, napad, d, dls, n_ls, dAs, st);
+  launch_scale_points<T>(dB, nb_, nbpad, d, dls, n_ls, dBs, st);
+  if (cov::differentiable(kernel))
+    launch_kbuild_cross_kk<T>(kernel, dAs, dka, na, napad, dBs, dkb, nb_, nbpad, d, sf2, dls, n_ls, dK, ld, st);
+  else  // (Matern-1/2: values only, and the fit builds them with the plain builder)
+    launch_kbuild_cross<T>(kernel, dAs, na, napad, dBs, nb_, nbpad, d, sf2, dK, ld, st);
+  TCHK(hipMemcpyAsync(host.data(), dK, (size_t)napad * ld * sizeof(T), hipMemcpyDeviceToHost, st));
+  TCHK(hipStreamSynchronize(st));
+  TCHK(hipGetLastError());
+  for (int64_t i = 0; i < na; ++i)
+    for (int64_t j = 0; j < nb_; ++j) K[i * nb_ + j] = (double)host[(size_t)i * ld + j];
+done:
+  for (void* p : {(void*)dA, (void*)dB, (void*)dAs, (void*)dBs, (void*)dK, (void*)dls, (void*)dka, (void*)dkb})
+    if (p) (void)hipFree(p);
+  return rc;
+}
+}  // namespace
+}  // extern "C++"
+
+int gpx_kernel_mixed_matrix(int32_t kernel, int32_t dtype, const double* A, const int32_t* ka, int64_t na, const double* B,
+                            const int32_t* kb, int64_t nb_, int32_t d, const double* lengthscale, int32_t n_ls, double sf2,
+                            double* K) try {
+  if (!A || !B || !K || !lengthscale || na <= 0 || nb_ <= 0 || d <= 0 || d > MAX_D || (n_ls != 1 && n_ls != d))
+    return GPX_E_ARG;
+  if (!cov::known(kernel) || (dtype != GPX_F64 && dtype != GPX_F32)) return GPX_E_ARG;
+  bool deriv = false;
+  for (int64_t i = 0; ka && i < na; ++i) {
+    if (ka[i] < -1 || ka[i] >= d) return GPX_E_ARG;
+    deriv |= ka[i] >= 0;
+  }
+  for (int64_t j = 0; kb && j < nb_; ++j) {
+    if (kb[j] < -1 || kb[j] >= d) return GPX_E_ARG;
+    deriv |= kb[j] >= 0;
+  }
+  if (deriv && !cov::differentiable(kernel))
+    return fail(nullptr, GPX_E_UNSUPPORTED, "gpx_kernel_mixed_matrix: " MATERN12_NO_GRAD);
+  if (dtype == GPX_F32) return kernel_mixed_matrix_t<float>(kernel, A, ka, na, B, kb, nb_, d, lengthscale, n_ls, sf2, K);
+  return kernel_mixed_matrix_t<double>(kernel, A, ka, na, B, kb, nb_, d, lengthscale, n_ls, sf2, K);
 }
 GPX_CATCH_ALL
 

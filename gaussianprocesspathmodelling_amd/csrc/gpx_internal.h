@@ -115,6 +115,12 @@ void launch_kbuild_sym_k(int kernel, const T* Xs, int64_t n, int64_t npad, int d
 template <typename T>
 void launch_kbuild_cross_k(int kernel, const T* As, int64_t m, int64_t mpad, const T* Bs, int64_t n, int64_t npad, int d,
                            double sf2, const int32_t* kind_b, const double* ls, int n_ls, T* K, int64_t ld, hipStream_t st);
+// ... with kinds on the rows too (kind_a: readable up to mpad, -1 beyond m): the left part of appended rows
+// (append_restart), gpx_kernel_mixed_matrix
+template <typename T>
+void launch_kbuild_cross_kk(int kernel, const T* As, const int32_t* kind_a, int64_t m, int64_t mpad, const T* Bs,
+                            const int32_t* kind_b, int64_t n, int64_t npad, int d, double sf2, const double* ls, int n_ls,
+                            T* K, int64_t ld, hipStream_t st);
 
 // Observations with path ids (id >= 0 names the path of an observation, -1 none; the arrays are readable up
 // to the padded sizes and hold -1 there): + sg2 k(x, x'; l_path) where the ids of a pair match.  q (d entries, device) =

@@ -346,6 +346,18 @@ void launch_kbuild_cross_k(int kernel, const T* As, int64_t m, int64_t mpad, con
   });
 }
 
+// as launch_kbuild_cross_k with kinds on the rows too (kind_a: readable up to mpad, -1 beyond m): the left part of appended
+// rows, whose new observations may be derivatives
+template <typename T>
+void launch_kbuild_cross_kk(int kernel, const T* As, const int32_t* kind_a, int64_t m, int64_t mpad, const T* Bs,
+                            const int32_t* kind_b, int64_t n, int64_t npad, int d, double sf2, const double* ls, int n_ls,
+                            T* K, int64_t ld, hipStream_t st) {
+  const int64_t tm = mpad / KT, tn = npad / KT;
+  cov::dispatch_differentiable(kernel, [&](auto fam) {
+    dispatch_d_k<T, fam, false>(As, m, Bs, n, d, tm * tn, (int)tn, sf2, kind_a, kind_b, ls, n_ls, nullptr, K, ld, st);
+  });
+}
+
 template <typename T>
 void launch_kbuild_sym_g(int kernel, const T* Xs, int64_t n, int64_t npad, int d, double sf2, const int32_t* group,
                          const double* q, double sg2, const T* diag, T* K, int64_t ld, hipStream_t st) {
@@ -383,7 +395,9 @@ void launch_kbuild_cross_g(int kernel, const T* As, const int32_t* group_a, int6
   template void launch_kbuild_cross_g<T>(int, const T*, const int32_t*, int64_t, int64_t, const T*, const int32_t*, int64_t, \
                                          int64_t, int, double, const double*, double, T*, int64_t, hipStream_t); \
   template void launch_kbuild_cross_k<T>(int, const T*, int64_t, int64_t, const T*, int64_t, int64_t, int, double, \
-                                         const int32_t*, const double*, int, T*, int64_t, hipStream_t);
+                                         const int32_t*, const double*, int, T*, int64_t, hipStream_t); \
+  template void launch_kbuild_cross_kk<T>(int, const T*, const int32_t*, int64_t, int64_t, const T*, const int32_t*, \
+                                          int64_t, int64_t, int, double, const double*, int, T*, int64_t, hipStream_t);
 GPX_INSTANTIATE_KBUILD(double)
 GPX_INSTANTIATE_KBUILD(float)
 

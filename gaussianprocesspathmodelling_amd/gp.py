@@ -399,8 +399,8 @@ class GP:
         path_lengthscale)``) and :meth:`forecast_blocks` forecasts one from its first points.  The attributes
         ``path_variance``, ``path_lengthscale`` and ``path_ids_`` keep what the fit used.  ``path_variance=0`` or ids that
         are all -1 are the plain fit bit for bit; None (the default) means none — also after such a fit.  float64 /
-        float32 on one device, not with ``derivatives``; :meth:`update` refuses such a fit, and its gradient is
-        ``lml_gradient(path=True)``."""
+        float32 on one device, not with ``derivatives``; :meth:`update` appends to such a fit when it is given the new
+        rows' ``path_ids``, and its gradient is ``lml_gradient(path=True)``."""
         ids, pvar, plsp = check_path_args(path_ids, path_variance, path_lengthscale, derivatives=derivatives)
         X, y, noise_weights, kinds = self._with_derivatives(X, y, derivatives, noise_weights)
         return self._fit_rows(X, y, noise_weights, kinds, derivative_noise, (ids, pvar, plsp))
@@ -453,7 +453,18 @@ class GP:
         self.log_det_ = float(ld.value)
         return self
 
-    def update(self, X_new, y_new, noise_weights=None):
+    def _side_input(self, a, kind, dev):
+        """(m,) int32 kinds or path ids of appended rows -> pointer and keepalive, where ``kind`` says the rows live"""
+        if a is None:
+            return None, None
+        if kind == _abi.MEM_DEVICE:
+            import torch
+            t = torch.from_numpy(a).to(dev)
+            torch.cuda.current_stream(dev).synchronize()
+            return C.c_void_p(t.data_ptr()), t
+        return C.c_void_p(a.ctypes.data), a
+
+    def update(self, X_new, y_new, noise_weights=None, derivatives=None, path_ids=None):
         """Append observations to the fitted model without factorising the old ones again (``gpx_append``): afterwards
         the model is, to rounding, what ``fit`` of the concatenated data with the same hyper-parameters and the jitter
         the fit needed would be.  Inputs as for :meth:`fit`: NumPy arrays or device tensors, both of the same kind,
@@ -462,9 +473,28 @@ class GP:
         ``numpy.linalg.LinAlgError`` when the kernel matrix with the new points is not positive definite: the model is
         then unchanged (the previous fit, every call valid).  float64 / float32 models on one device.
         ``noise_weights`` (m,): the new points' noise weights (``gpx_append_weighted``), of the same kind as ``X_new``;
-        None appends with weight 1, on a weighted model too.  Returns ``self``."""
+        None appends with weight 1, on a weighted model too.  Returns ``self``.
+
+        On a fit with path ids, ``path_ids`` (m,) ints >= -1 (as :meth:`fit`'s) name the path of every new row — a new
+        id is a new path, an id the fit holds already brings more points of that path — and the rows go through
+        ``gpx_append_rows``; ``path_ids_`` then has N + m entries.  Without the keyword such a fit stays refused: the
+        caller has to say which path the rows belong to.  On a fit made with ``derivatives=`` (an empty one included),
+        ``derivatives = (Xd, dims, yd)`` appends the m value rows followed by the Nd derivative rows (``X_new`` may be
+        (0, d)); ``noise_weights`` may have length m or m + Nd, as in :meth:`fit`, and ``observation_kinds_``,
+        ``alpha_`` and ``noise_weights_`` cover all rows afterwards.  ``ValueError`` before any library call:
+        ``path_ids`` on a fit without path ids, ``derivatives`` on a fit made without the keyword, or both at once."""
         if not self._fitted:
             raise RuntimeError("update() before a successful fit()")
+        if path_ids is not None and derivatives is not None:
+            raise ValueError("path_ids cannot be combined with derivatives=: no builder evaluates both")
+        if path_ids is not None and not self._groups_set:
+            raise ValueError("path_ids given, but the model was fitted without path ids")
+        if derivatives is not None and not self._kinds_set:
+            raise ValueError("derivatives given, but the model was fitted without derivatives= (pass an empty "
+                             "derivatives=(Xd, dims, yd) to fit() to allow derivative rows later)")
+        kinds = None
+        if derivatives is not None:
+            X_new, y_new, noise_weights, kinds = self._with_derivatives(X_new, y_new, derivatives, noise_weights)
         px, kx, keepx, devx, sx = self._as_input(X_new, "X_new")
         py, ky, keepy, devy, sy = self._as_input(y_new, "y_new")
         if len(sx) != 2 or sx[1] != self._d:
@@ -479,10 +509,15 @@ class GP:
         if kx != ky:
             raise ValueError("X_new and y_new must both be host arrays or both be device tensors")
         pw, keepw = self._weights_input(noise_weights, m, kx, "noise_weights", "X_new")
+        ids = None if path_ids is None else check_path_args(path_ids, 0.0, None, n=m)[0]
         if m == 0:
             return self
         info = C.c_int64(0)
-        if pw is None:
+        if kinds is not None or ids is not None:
+            pk, keepk = self._side_input(kinds, kx, devx)
+            pg, keepg = self._side_input(ids, kx, devx)
+            self._check(self._lib.gpx_append_rows(self._h, px, py, pw, pk, pg, m, kx, C.byref(info)))
+        elif pw is None:
             self._check(self._lib.gpx_append(self._h, px, py, m, kx, C.byref(info)))
         else:
             self._check(self._lib.gpx_append_weighted(self._h, px, py, pw, m, kx, C.byref(info)))

@@ -243,13 +243,14 @@ class PathModel:
     :meth:`predict`.  ``step_weights`` (L,), or None: the per-step noise weights the model was fitted with
     (``fit_path_models(step_noise=True)``); :meth:`add_paths` and :meth:`log_likelihood` then use them too.
     ``has_velocities``: the model was also conditioned on observed velocities (``fit_path_models(velocities=)``: derivative
-    observations along ``"t"``); every prediction works unchanged, :meth:`add_paths` does not (``GP.update`` cannot append
-    to such a fit).  ``velocity_noise``: the noise variance of those velocities in the model's normalised units, as given
+    observations along ``"t"``); every prediction works unchanged, and :meth:`append_paths` adds paths with or without
+    velocities (:meth:`add_paths`, which takes none, refuses such a model).  ``velocity_noise``: the noise variance of those velocities in the model's normalised units, as given
     or as learnt (``fit_path_models(learn_velocity_noise=True)``); None without velocities.
     ``within_path``: the model is the hierarchical one (``fit_path_models(within_path=True)``): every path is the cluster
     mean plus a deviation of its own.  :meth:`predict`, :meth:`sample` and :meth:`velocity` are then about the cluster
     mean, :meth:`log_likelihood` scores a path as a new member of the cluster, :meth:`forecast` continues one from its
-    first points; :meth:`add_paths` does not work (``GP.update`` cannot append to such a fit)."""
+    first points; :meth:`append_paths` adds paths under new ids (:meth:`add_paths` refuses such a model).
+    Which method adds paths: :meth:`add_paths` on plain and step-noise models, :meth:`append_paths` on every model."""
 
     def __init__(self, gp, keys, in_lo, in_span, y_mean, y_std, inputs, targets, step_weights=None, has_velocities=False,
                  within_path=False):
@@ -334,21 +335,53 @@ class PathModel:
         ``in_span``, ``y_mean``, ``y_std``), so the result is the GP of all the cluster's paths under that normalisation.
         A model with ``step_weights`` appends with them, tiled over the new paths (which must have its path length).
         Extends ``keys``; returns ``self``."""
-        keys = list(keys)
         if self.has_velocities:
-            raise ValueError("add_paths: the model is conditioned on velocities (derivative observations), and a fit with "
-                             "derivative observations cannot be appended to: fit the cluster again with fit_path_models")
+            raise ValueError("add_paths: the model is conditioned on velocities (derivative observations), and the new paths "
+                             "may bring velocities of their own: call append_paths(trajs, keys, velocities=)")
         if self.within_path:
-            raise ValueError("add_paths: the model has within-path deviations (path ids), and a fit with path ids cannot be "
-                             "appended to: fit the cluster again with fit_path_models")
+            raise ValueError("add_paths: the model has within-path deviations (path ids), and the new paths need ids of "
+                             "their own: call append_paths(trajs, keys), which numbers them")
+        return self.append_paths(trajs, keys)
+
+    def append_paths(self, trajs, keys, velocities=None):
+        """:meth:`add_paths` for every model (``GP.update`` with the rows' path ids or derivative rows where the model has
+        them).  On a ``within_path`` model path i of ``keys`` gets the id ``len(self.keys) + i``, which continues the
+        numbering of :func:`fit_path_models`.  On a model with velocities, ``velocities`` = {key: (L, k)} in raw units
+        (target per unit of ``"t"``) become derivative rows under the model's normalisation, as at the fit; a key without
+        an entry appends its values only.  ``velocities`` on a model without them: ``ValueError``.  Extends ``keys``;
+        returns ``self``."""
+        keys = list(keys)
+        if velocities is not None and not self.has_velocities:
+            raise ValueError("append_paths: velocities given, but the model was fitted without velocities")
         if not keys:
             return self
         if self.step_weights is not None and any(len(trajs.pathdict[q]) != len(self.step_weights) for q in keys):
-            raise ValueError(f"add_paths: the model has per-step noise weights for paths of {len(self.step_weights)} points")
+            raise ValueError(f"append_paths: the model has per-step noise weights for paths of {len(self.step_weights)} points")
         X, Y, _ = to_gp_inputs(trajs, keys, inputs=self.inputs, targets=self.targets, normalise=False)
         Xn = np.ascontiguousarray((X - self.in_lo) / self.in_span)
         Yn = np.ascontiguousarray((Y - self.y_mean) / self.y_std)
-        self.gp.update(Xn, Yn, noise_weights=self._tiled_weights(len(Xn), "add_paths"))
+        kw = {}
+        if self.within_path:
+            first = len(self.keys)
+            kw["path_ids"] = np.concatenate([np.full(len(trajs.pathdict[q]), first + i, dtype=np.int32)
+                                             for i, q in enumerate(keys)])
+        if self.has_velocities:
+            jt = self.inputs.index("t")
+            rows, vals, at = [], [], 0
+            for q in keys:
+                L = len(trajs.pathdict[q])
+                if velocities is not None and q in velocities:
+                    v = np.asarray(velocities[q], dtype=np.float64)
+                    if v.shape != (L, len(self.targets)):
+                        raise ValueError(f"velocities[{q!r}] must be ({L}, {len(self.targets)}): one row per path point, "
+                                         f"one column per target")
+                    rows.append(np.arange(at, at + L))
+                    vals.append(v * self.in_span[jt] / self.y_std[None, :])
+                at += L
+            at_rows = np.concatenate(rows) if rows else np.zeros(0, dtype=int)
+            yd = np.concatenate(vals) if vals else np.zeros((0, len(self.targets)))
+            kw["derivatives"] = (np.ascontiguousarray(Xn[at_rows]), jt, np.ascontiguousarray(yd))
+        self.gp.update(Xn, Yn, noise_weights=self._tiled_weights(len(Xn), "append_paths"), **kw)
         self.keys.extend(keys)
         return self
 
@@ -586,7 +619,8 @@ def path_log_likelihood_matrix(trajs, models, keys=None):
 
 def assign_paths(trajs, models, keys=None):
     """{cluster id: [path ids]} by the largest whole-path log-likelihood (first maximum on ties) — the shape
-    :func:`kmeans` returns, so each list can go straight to that cluster's :meth:`PathModel.add_paths`."""
+    :func:`kmeans` returns, so each list can go straight to that cluster's :meth:`PathModel.append_paths` (every model;
+    :meth:`PathModel.add_paths` serves plain and step-noise models only)."""
     keys, LL = path_log_likelihood_matrix(trajs, models, keys)
     cids = list(models.keys())
     best = np.argmax(LL, axis=1) if keys else np.zeros(0, dtype=int)

@@ -331,7 +331,7 @@ int gpx_score_blocks_weighted(gpx_handle* h, const void* Xs, const void* ys, con
  * Matern-1/2 handle (not differentiable; kinds that are all -1 fit as the plain model there); a fit with kinds set on
  * GPX_MIXED handles, device groups, shards and handles that own a communicator (the set call itself succeeds, and once
  * the kinds are cleared the handle fits as before); gpx_lml_grad (gpx_lml_grad_full is the gradient of such a fit),
- * gpx_append and gpx_append_weighted on a fit that has a derivative row.  gpx_predict_grad without variances takes the batch route on such a fit (its matrix-free product knows
+ * gpx_append and gpx_append_weighted on a fit that has a derivative row (gpx_append_rows appends to such a fit).  gpx_predict_grad without variances takes the batch route on such a fit (its matrix-free product knows
  * value columns only).  With no kinds set a handle launches the kernels it launched before and allocates nothing more. */
 int gpx_set_observation_kinds(gpx_handle* h, const int32_t* kind, int64_t n, double sn2_deriv, int32_t mem_kind);
 /* The kinds of the current fit, all -1 when it was made without any.  GPX_E_ARG without a fit. */
@@ -354,13 +354,41 @@ int gpx_get_observation_kinds(gpx_handle* h, int32_t* out /* (N) host */);
  * GPX_E_ARG before anything is computed.  With every id -1, or sg2 == 0, a fit is the plain (or weighted) fit bit for bit.
  * Otherwise GPX_E_UNSUPPORTED before anything is computed or exchanged, the previous fit still valid: a fit on device
  * groups, shards, handles with a communicator, GPX_MIXED handles, and handles that also have observation kinds set; on a
- * fit made with path ids: gpx_append / gpx_append_weighted (fit the concatenated data), gpx_lml_grad and
+ * fit made with path ids: gpx_append / gpx_append_weighted (the rows would come without ids: gpx_append_rows takes them),
+ * gpx_lml_grad and
  * gpx_lml_grad_full (these evaluate training-pair covariances matrix-free, without the path term; gpx_lml_grad_paths is
  * the gradient of such a fit). */
 int gpx_set_path_groups(gpx_handle* h, const int32_t* group, int64_t n, double sg2, const double* ls_path,
                         int32_t n_ls_path, int32_t mem_kind);
 /* The path ids of the current fit, all -1 when it was made without any (or with sg2 == 0).  GPX_E_ARG without a fit. */
 int gpx_get_path_groups(gpx_handle* h, int32_t* out /* (N) host */);
+/* ---- appending rows with kinds or path ids (additive to ABI v6) -----------------------------------------------------------
+ * gpx_append_weighted for every fit: the m new rows bring their weights wnew, kinds kind_new and path ids group_new (m
+ * entries each; mem_kind says where all five arrays live).  wnew, kind_new and group_new may each be NULL: ones for the
+ * weights, all -1 for the kinds and the ids.  Afterwards the handle is, to rounding, what gpx_fit of the concatenated rows
+ * would have left — with the concatenated weights, kinds and ids in the same row order and the fit's hyper-parameters,
+ * sn2_deriv, sg2, l_path and jitter — and every later call works on N + m rows: the predict family,
+ * gpx_score_blocks(_weighted), gpx_forecast_blocks, gpx_get_alpha, gpx_logdet, gpx_lml_grad_full / gpx_lml_grad_paths,
+ * gpx_get_observation_kinds, gpx_get_path_groups, gpx_get_noise_weights, a further append.
+ * The restart is gpx_append's, through the builders of the fit: on a fit with kinds the left part of the new rows is the
+ * rectangular KINDS build with kinds on rows and columns and the rebuilt square [R0, N + m)^2 the symmetric one; on a fit
+ * with path ids the GROUPS builds, whose per-tile test "can this tile hold a same-path pair" skips the path term wherever
+ * the ids of the new rows meet none of the columns'.  The kinds / ids and the finished diagonal terms follow the factor's
+ * capacity rules (gpx_reserve) as the weights do.
+ * Plain and weighted fits (made without kinds and without effective path ids): every kind and id is then NULL or -1 and
+ * the call is gpx_append_weighted — the same launches, the same bits.  A fit made with kinds set stays one, also when
+ * neither it nor the new rows hold a derivative: it keeps sn2_deriv, and gpx_get_observation_kinds returns N + m entries.
+ * Kinds: a kind >= 0 needs a fit made with kinds set (gpx_set_observation_kinds; kinds that were all -1 count), else
+ * GPX_E_ARG: the fit has no sn2_deriv.  A kind outside [-1, d): GPX_E_ARG.  A kind >= 0 on a GPX_KERNEL_MATERN12 handle:
+ * GPX_E_UNSUPPORTED.  On a fit with a derivative row, kinds that are all -1 append values of f.
+ * Path ids: an id >= 0 needs a fit built with path ids (one id >= 0 and sg2 > 0 at the fit), else GPX_E_ARG; an id below
+ * -1: GPX_E_ARG.  An id may be new (a new path) or one the fit holds already (more points of a known path).
+ * Every check, and the GPX_E_NOMEM of a layout that has to grow, comes before anything of the fit is touched.  Refusals
+ * as for gpx_append (GPX_MIXED handles, shards, device groups, handles with a communicator).
+ * *info > 0: as gpx_append — the call returns 0 and the handle holds the previous fit again, with its kinds, ids, weights
+ * and finished diagonal terms; the getters return the old N entries. */
+int gpx_append_rows(gpx_handle* h, const void* Xnew, const void* ynew, const void* wnew, const int32_t* kind_new,
+                    const int32_t* group_new, int64_t m, int32_t mem_kind, int64_t* info);
 /* Forecast of partly observed new paths.  Xb (G (Lo + Lp), d): per block its Lo observed points, then its Lp points to
  * forecast (1 <= Lo, 1 <= Lp, Lo + Lp <= 64); yo (G Lo, k) the observed targets; diag_add >= 0 goes on the diagonal of the
  * observed part only (the observation noise).  The block prior is posterior(f) [+ sg2 k(., .; l_path) on a fit with path
@@ -483,6 +511,13 @@ int gpx_kernel_dl_matrix(int32_t kernel, const double* A, const int32_t* ka, int
 int gpx_kernel_path_matrix(int32_t kernel, int32_t dtype, const double* A, const int32_t* ga, int64_t na, const double* B,
                            const int32_t* gb, int64_t nb, int32_t d, const double* lengthscale, int32_t n_ls, double sf2,
                            const double* ls_path, int32_t n_ls_path, double sg2, double* K);
+/* K (na, nb) host, fp64 = the covariance between an observation of kind ka[a] at A_a and one of kind kb[b] at B_b (kinds as
+ * in gpx_set_observation_kinds; ka / kb == NULL: all values), by the fit's rectangular builder with kinds on rows and
+ * columns — the left part of rows appended by gpx_append_rows; no diagonal term.  n_ls: 1 or d.  dtype GPX_F64 or GPX_F32
+ * (the fp32 builder on the rounded inputs, returned widened).  Refusals as gpx_kernel_dl_matrix's. */
+int gpx_kernel_mixed_matrix(int32_t kernel, int32_t dtype, const double* A, const int32_t* ka, int64_t na, const double* B,
+                            const int32_t* kb, int64_t nb, int32_t d, const double* lengthscale, int32_t n_ls, double sf2,
+                            double* K);
 /* kernel unit-test entry point (host buffers, fp64; additive to ABI v6): G (1 + n_ls_path, na, nb): G[0][a][b] = [ga_a == gb_b
  * and ga_a >= 0] sg2 k(A_a, B_b; l_path), the within-path term of gpx_kernel_path_matrix, and G[1 + c] its derivative by
  * log l_path,c (n_ls_path == 1: by the one l_path) — what gpx_lml_grad_paths contracts with K^-1, by the device function its
