@@ -111,6 +111,7 @@ struct gpx_handle {
   // needs them and that no fitted state lives in.  A buffer is scratch by being declared here, and only so.
   struct ScratchBufs {
     DevBuf Q, Qs, VT, MT;  // predict: query points (raw, scaled), K* -> V^T of one batch, mean^T
+    DevBuf Qg, Qz;         // the *_paths calls: the query points' path ids (-1 up to the padded size), a zeroed diagonal vector
     DevBuf Tsol;           // predict: compact solved blocks of V^T (2 x batch x (nb + skew))
     DevBuf MTpart;         // split-K partial tiles of the posterior-mean product
     DevBuf ZT, gpart;      // gpx_lml_grad: L^-T (Npad x ld) and the per-tile partial sums
@@ -1080,6 +1081,16 @@ int upload_queries(gpx_handle* h, const void* Xq, int64_t M, int32_t mem_kind) {
   return GPX_OK;
 }
 
+// The query points' path ids (the *_paths calls; gq in the memory kind of the query points) into Qg next to Qs, -1 from M
+// to the padded size: the GROUPS builders read the ids of whole tiles.  Inside the caller's phase, as upload_queries.
+int upload_query_ids(gpx_handle* h, const int32_t* gq, int64_t M, int32_t mem_kind) {
+  const int64_t Mpad = round_up(M, TILE);
+  int rc;
+  if ((rc = ensure(h, h->scr.Qg, (size_t)Mpad * sizeof(int32_t)))) return rc;
+  HIPCHK(h, hipMemsetAsync(h->scr.Qg.p, 0xFF, (size_t)Mpad * sizeof(int32_t), h->st));  // -1
+  return copy_in(h, h->scr.Qg.p, gq, (size_t)M * sizeof(int32_t), mem_kind);
+}
+
 // Dense block solves for solve_fwd_enqueue over `rows` rows: the fit's explicit block inverses and two compact result
 // buffers in `buf`.  *sw stays empty (slab solves) when the solve's block width is not the inverses' or the handle keeps
 // no whole factor.
@@ -1139,7 +1150,7 @@ int deliver_mean_var(gpx_handle* h, void* mean, void* var, int64_t M, int32_t me
 }
 
 template <typename T>
-int predict_core(gpx_handle* h, const void* Xq, int64_t M, bool want_var, int32_t mem_kind);
+int predict_core(gpx_handle* h, const void* Xq, int64_t M, bool want_var, int32_t mem_kind, const int32_t* gq = nullptr);
 bool few_solver_applies(const gpx_handle* h);
 template <typename T>
 int solve_few(gpx_handle* h, T* RT, int k, const T* L, int64_t ld, int64_t n, const T* W, int nb, bool forward = true,
@@ -1231,10 +1242,15 @@ int stage_fit_groups(gpx_handle* h, int64_t N, int64_t cap, int d, const double*
 }
 
 // K* of value rows As (m valid of mpad) against the training set of the current fit: the KINDS builder on a fit with kinds
-// (a fit with path ids takes the plain builder: query rows are values of f, and Cov[f(x*), y_i] = sf2 k(x*, x_i))
+// (a fit with path ids takes the plain builder: query rows are values of f, and Cov[f(x*), y_i] = sf2 k(x*, x_i)).
+// ga != null (a fit with path ids; readable up to mpad, -1 beyond m): row i with ga[i] >= 0 is a value of f + g_p of that
+// path, and the GROUPS builder adds sg2 k(x*, x_i; l_path) where the ids match.
 template <typename T>
-void kbuild_cross_fit(gpx_handle* h, const T* As, int64_t m, int64_t mpad, T* K, int64_t ld) {
-  if (h->kinded)
+void kbuild_cross_fit(gpx_handle* h, const T* As, int64_t m, int64_t mpad, T* K, int64_t ld, const int32_t* ga = nullptr) {
+  if (ga)
+    launch_kbuild_cross_g<T>(h->cfg.kernel, As, ga, m, mpad, (const T*)h->Xs.p, (const int32_t*)h->Gfit.p, h->N, h->Npad,
+                             h->d, h->sf2, (const double*)h->Gq.p, h->sg2, K, ld, h->st);
+  else if (h->kinded)
     launch_kbuild_cross_k<T>(h->cfg.kernel, As, m, mpad, (const T*)h->Xs.p, h->N, h->Npad, h->d, h->sf2,
                              (const int32_t*)h->Kfit.p, (const double*)h->ls.p, h->n_ls, K, ld, h->st);
   else
@@ -1703,8 +1719,9 @@ int ensure_alpha(gpx_handle* h) {
 
 // K*, variance solve, mean and variance of M query points; results stay on the device in
 // h->meanout (M x k) and h->var (M).  Reads the factor through h->Lfac (whole L).
+// gq != null (gpx_predict_paths; a fit with path ids): the query points' path ids, staged in scr.Qg; a batch reads its own.
 template <typename T>
-int predict_core(gpx_handle* h, const void* Xq, int64_t M, bool want_var, int32_t mem_kind) {
+int predict_core(gpx_handle* h, const void* Xq, int64_t M, bool want_var, int32_t mem_kind, const int32_t* gq) {
   if (M <= 0) return GPX_OK;  // a rank whose slice of the query points is empty
   const int64_t N = h->N, Npad = h->Npad, ld = h->ld;
   const int d = h->d, k = h->k;
@@ -1730,13 +1747,15 @@ int predict_core(gpx_handle* h, const void* Xq, int64_t M, bool want_var, int32_
   {
     PhaseScope ps(h, &tm.kstar);
     if ((rc = upload_queries<T>(h, Xq, M, mem_kind))) return rc;
+    if (gq && (rc = upload_query_ids(h, gq, M, mem_kind))) return rc;
   }
+  const int32_t* dg = gq ? (const int32_t*)h->scr.Qg.p : nullptr;
   for (int64_t m0 = 0; m0 < Mpad; m0 += MB) {  // batches of query points through one V^T buffer
     const int64_t mp = std::min(MB, Mpad - m0);       // padded rows of this batch
     const int64_t mv = std::min<int64_t>(mp, M - m0);  // valid rows
     {
       PhaseScope ps(h, &tm.kstar);
-      kbuild_cross_fit<T>(h, (const T*)h->scr.Qs.p + m0 * d, mv, mp, dVT, ld);
+      kbuild_cross_fit<T>(h, (const T*)h->scr.Qs.p + m0 * d, mv, mp, dVT, ld, dg ? dg + m0 : nullptr);
     }
     if (want_var) {
       PhaseScope ps(h, &tm.trsm);
@@ -1749,7 +1768,7 @@ int predict_core(gpx_handle* h, const void* Xq, int64_t M, bool want_var, int32_
     }
     if (want_var) {
       PhaseScope ps(h, &tm.var);
-      launch_var_rows<T>(dVT, ld, mv, Npad, h->sf2, (T*)h->var.p + m0, h->st);
+      launch_var_rows<T>(dVT, ld, mv, Npad, h->sf2, (T*)h->var.p + m0, h->st, dg ? dg + m0 : nullptr, h->sg2);
     }
   }
   {
@@ -1760,12 +1779,13 @@ int predict_core(gpx_handle* h, const void* Xq, int64_t M, bool want_var, int32_
 }
 
 template <typename T>
-int predict_impl(gpx_handle* h, const void* Xq, int64_t M, void* mean, void* var, int32_t mem_kind) {
+int predict_impl(gpx_handle* h, const void* Xq, int64_t M, void* mean, void* var, int32_t mem_kind,
+                 const int32_t* gq = nullptr) {
   reset_predict_clocks(h->tm);
   int rc;
   {
     PhaseScope total(h, &h->tm.predict_total);
-    if ((rc = predict_core<T>(h, Xq, M, var != nullptr, mem_kind))) return rc;
+    if ((rc = predict_core<T>(h, Xq, M, var != nullptr, mem_kind, gq))) return rc;
     if ((rc = deliver_mean_var<T>(h, mean, var, M, mem_kind))) return rc;
   }
   return finish_call(h);
@@ -1836,9 +1856,10 @@ int posterior_check(gpx_handle* h, const char* fn, int64_t M, int64_t S, bool sa
   return GPX_OK;
 }
 
-// mean (h->meanout, M x k) and the LOWER triangle of Sigma (h->scr.JSig, Mpad x lds; padded rows identity)
+// mean (h->meanout, M x k) and the LOWER triangle of Sigma (h->scr.JSig, Mpad x lds; padded rows identity).
+// gq != null (the *_paths calls; a fit with path ids): the query points' path ids — K* and K(Xs, Xs) by the GROUPS builders.
 template <typename T>
-int posterior_cov_core(gpx_handle* h, const void* Xq, int64_t M, int32_t mem_kind) {
+int posterior_cov_core(gpx_handle* h, const void* Xq, int64_t M, int32_t mem_kind, const int32_t* gq = nullptr) {
   const int64_t N = h->N, Npad = h->Npad, ld = h->ld;
   const int d = h->d, k = h->k;
   const int64_t Mpad = round_up(M, TILE), lds = Mpad + ld_skew<T>(), ldm = Mpad + ld_skew<T>();
@@ -1852,12 +1873,18 @@ int posterior_cov_core(gpx_handle* h, const void* Xq, int64_t M, int32_t mem_kin
   if ((rc = ensure(h, h->meanout, (size_t)M * k * sizeof(T)))) return rc;
   SolveWork<T> sw;  // dense block solves, as predict
   if ((rc = dense_solve_work<T>(h, h->scr.JTsol, Mpad, &sw))) return rc;
+  if (gq && (rc = ensure(h, h->scr.Qz, (size_t)Mpad * sizeof(T)))) return rc;
   T* dVT = (T*)h->scr.JVT.p;
   T* dSig = (T*)h->scr.JSig.p;
+  const int32_t* dg = nullptr;
   {
     PhaseScope ps(h, &tm.kstar);
     if ((rc = upload_queries<T>(h, Xq, M, mem_kind))) return rc;
-    kbuild_cross_fit<T>(h, (const T*)h->scr.Qs.p, M, Mpad, dVT, ld);
+    if (gq) {
+      if ((rc = upload_query_ids(h, gq, M, mem_kind))) return rc;
+      dg = (const int32_t*)h->scr.Qg.p;
+    }
+    kbuild_cross_fit<T>(h, (const T*)h->scr.Qs.p, M, Mpad, dVT, ld, dg);
   }
   {
     PhaseScope ps(h, &tm.trsm);
@@ -1873,14 +1900,21 @@ int posterior_cov_core(gpx_handle* h, const void* Xq, int64_t M, int32_t mem_kin
      // not built: zero it first), then one SYRK over the lower triangle
     PhaseScope ps(h, &tm.var);
     HIPCHK(h, hipMemsetAsync(dSig, 0, (size_t)Mpad * lds * sizeof(T), h->st));
-    launch_kbuild_sym<T>(h->cfg.kernel, (const T*)h->scr.Qs.p, M, Mpad, d, h->sf2, 0.0, dSig, lds, h->st);
+    if (dg) {  // (the GROUPS builder reads a finished per-row diagonal term: none here)
+      HIPCHK(h, hipMemsetAsync(h->scr.Qz.p, 0, (size_t)Mpad * sizeof(T), h->st));
+      launch_kbuild_sym_g<T>(h->cfg.kernel, (const T*)h->scr.Qs.p, M, Mpad, d, h->sf2, dg, (const double*)h->Gq.p, h->sg2,
+                             (const T*)h->scr.Qz.p, dSig, lds, h->st);
+    } else {
+      launch_kbuild_sym<T>(h->cfg.kernel, (const T*)h->scr.Qs.p, M, Mpad, d, h->sf2, 0.0, dSig, lds, h->st);
+    }
     launch_gemm_nt<T>(128, dSig, lds, dVT, ld, dVT, ld, Mpad, Mpad, Npad, 1, 0, h->st);
   }
   return GPX_OK;
 }
 
 template <typename T>
-int predict_cov_impl(gpx_handle* h, const void* Xq, int64_t M, void* mean, void* cov, int32_t mem_kind) {
+int predict_cov_impl(gpx_handle* h, const void* Xq, int64_t M, void* mean, void* cov, int32_t mem_kind,
+                     const int32_t* gq = nullptr) {
   gpx_timings& tm = h->tm;
   reset_predict_clocks(tm);
   int rc;
@@ -1888,7 +1922,7 @@ int predict_cov_impl(gpx_handle* h, const void* Xq, int64_t M, void* mean, void*
   const int64_t Mpad = round_up(M, TILE), lds = Mpad + ld_skew<T>();
   {
     PhaseScope total(h, &tm.predict_total);
-    if ((rc = posterior_cov_core<T>(h, Xq, M, mem_kind))) return rc;
+    if ((rc = posterior_cov_core<T>(h, Xq, M, mem_kind, gq))) return rc;
     {
       PhaseScope ps(h, &tm.var);
       launch_mirror_lower<T>((T*)h->scr.JSig.p, lds, Mpad, 0, h->st);  // bit-symmetric copy-out
@@ -1905,7 +1939,7 @@ int predict_cov_impl(gpx_handle* h, const void* Xq, int64_t M, void* mean, void*
 template <typename T>
 int sample_posterior_impl(gpx_handle* h, const void* Xq, int64_t M, int64_t S, uint64_t seed, const void* z,
                           double diag_add, double jitter, int32_t max_tries, void* out, double* jitter_used, int64_t* info,
-                          int32_t mem_kind) {
+                          int32_t mem_kind, const int32_t* gq = nullptr) {
   gpx_timings& tm = h->tm;
   reset_predict_clocks(tm);
   const bool host = mem_kind == GPX_MEM_HOST;
@@ -1946,7 +1980,7 @@ int sample_posterior_impl(gpx_handle* h, const void* Xq, int64_t M, int64_t S, u
   int hinfo = INT_MAX;
   {
     PhaseScope total_ps(h, &tm.predict_total);
-    if ((rc = posterior_cov_core<T>(h, Xq, M, mem_kind))) return rc;
+    if ((rc = posterior_cov_core<T>(h, Xq, M, mem_kind, gq))) return rc;
     const T* dSig = (const T*)h->scr.JSig.p;  // (allocated by the core)
     if (z && host) {
       PhaseScope ps(h, &tm.kstar);
@@ -2151,16 +2185,22 @@ int score_impl(gpx_handle* h, const void* Xq, const void* yq, const void* wq, in
 // together) -> row norms against the per-block prior -> unpack.  Every buffer is scratch of its own (G*): the fit is only
 // read, so gpx_predict afterwards is bit-identical.
 
-// prior[b] of the row blocks: sf2 (value rows), then Var[d f / d x_j] = cov::grad_prior sf2 / l_j^2
-int grad_priors(gpx_handle* h, bool with_value, double* prior) {
+// prior[b] of the row blocks: sf2 (value rows), then Var[d f / d x_j] = cov::grad_prior sf2 / l_j^2.
+// prior_path != null (a fit with path ids): what a query point with a path id adds, sg2 and
+// Var[d g_p / d x_j] = cov::grad_prior sg2 / l_path,j^2 = cov::grad_prior sg2 q_j / l_j^2.
+int grad_priors(gpx_handle* h, bool with_value, double* prior, double* prior_path = nullptr) {
   double ls[MAX_D];
   HIPCHK(h, hipMemcpyAsync(ls, h->ls.p, (size_t)h->n_ls * sizeof(double), hipMemcpyDeviceToHost, h->st));
   HIPCHK(h, hipStreamSynchronize(h->st));
   int b = 0;
-  if (with_value) prior[b++] = h->sf2;
+  if (with_value) {
+    if (prior_path) prior_path[b] = h->sg2;
+    prior[b++] = h->sf2;
+  }
   const double c = cov::grad_prior(h->cfg.kernel);
   for (int j = 0; j < h->d; ++j) {
     const double l = ls[h->n_ls == 1 ? 0 : j];
+    if (prior_path) prior_path[b] = c * h->sg2 * h->q_fit[(size_t)j] / (l * l);
     prior[b++] = c * h->sf2 / (l * l);
   }
   return GPX_OK;
@@ -2197,7 +2237,7 @@ int predict_grad_mean_only(gpx_handle* h, const void* Xq, int64_t M, void* mean,
 
 template <typename T>
 int predict_grad_var(gpx_handle* h, const void* Xq, int64_t M, void* mean, void* var, void* dmean, void* dvar,
-                     int32_t mem_kind, const char* fn) {
+                     int32_t mem_kind, const char* fn, const int32_t* gq = nullptr) {
   const int64_t N = h->N, Npad = h->Npad, ld = h->ld;
   const int d = h->d, k = h->k;
   const size_t E = sizeof(T);
@@ -2226,9 +2266,9 @@ int predict_grad_var(gpx_handle* h, const void* Xq, int64_t M, void* mean, void*
   const int64_t MB = std::min(pred_batch_rows(h, Mpad, 0, false), std::max<int64_t>(128, fit));
   const int64_t RB = nblk * MB;                 // rows of the largest batch
   const int64_t ldm = RB + ld_skew<T>();        // z^T V of one batch
-  double prior[MAX_D + 1];
+  double prior[MAX_D + 1], prior_path[MAX_D + 1];
   int rc;
-  if ((rc = grad_priors(h, with_value, prior))) return rc;
+  if ((rc = grad_priors(h, with_value, prior, gq ? prior_path : nullptr))) return rc;
   if ((rc = ensure_queries<T>(h, M))) return rc;
   if ((rc = ensure(h, h->scr.GV, (size_t)RB * ld * E))) return rc;
   if ((rc = ensure(h, h->scr.GMT, (size_t)RHS_ROWS * ldm * E))) return rc;
@@ -2244,7 +2284,9 @@ int predict_grad_var(gpx_handle* h, const void* Xq, int64_t M, void* mean, void*
   {
     PhaseScope ps(h, &tm.kstar);
     if ((rc = upload_queries<T>(h, Xq, M, mem_kind))) return rc;
+    if (gq && (rc = upload_query_ids(h, gq, M, mem_kind))) return rc;
   }
+  const int32_t* dg = gq ? (const int32_t*)h->scr.Qg.p : nullptr;  // (a fit with path ids: the query points' own)
   for (int64_t m0 = 0; m0 < Mpad; m0 += MB) {
     const int64_t mp = std::min(MB, Mpad - m0);        // padded rows of this batch (a multiple of 128)
     const int64_t mv = std::min<int64_t>(mp, M - m0);  // valid rows
@@ -2252,9 +2294,14 @@ int predict_grad_var(gpx_handle* h, const void* Xq, int64_t M, void* mean, void*
     const int64_t ldb = R + ld_skew<T>();
     {
       PhaseScope ps(h, &tm.kstar);
-      launch_kgrad_build<T>(h->cfg.kernel, (const T*)h->scr.Qs.p + m0 * d, mv, mp, (const T*)h->Xs.p, N, Npad, d, h->sf2,
-                            (const double*)h->ls.p, h->n_ls, with_value ? 1 : 0, dV, ld, h->st,
-                            h->kinded ? (const int32_t*)h->Kfit.p : nullptr);
+      if (dg)
+        launch_kgrad_build_g<T>(h->cfg.kernel, (const T*)h->scr.Qs.p + m0 * d, dg + m0, mv, mp, (const T*)h->Xs.p,
+                                (const int32_t*)h->Gfit.p, N, Npad, d, h->sf2, (const double*)h->ls.p, h->n_ls,
+                                (const double*)h->Gq.p, h->sg2, with_value ? 1 : 0, dV, ld, h->st);
+      else
+        launch_kgrad_build<T>(h->cfg.kernel, (const T*)h->scr.Qs.p + m0 * d, mv, mp, (const T*)h->Xs.p, N, Npad, d, h->sf2,
+                              (const double*)h->ls.p, h->n_ls, with_value ? 1 : 0, dV, ld, h->st,
+                              h->kinded ? (const int32_t*)h->Kfit.p : nullptr);
     }
     {
       PhaseScope ps(h, &tm.trsm);
@@ -2267,7 +2314,7 @@ int predict_grad_var(gpx_handle* h, const void* Xq, int64_t M, void* mean, void*
     }
     {
       PhaseScope ps(h, &tm.var);
-      launch_grad_norms<T>(dV, ld, mp, mv, nblk, Npad, prior, (T*)h->scr.GVN.p, h->st);
+      launch_grad_norms<T>(dV, ld, mp, mv, nblk, Npad, prior, (T*)h->scr.GVN.p, h->st, dg ? dg + m0 : nullptr, prior_path);
     }
     {
       PhaseScope ps(h, &tm.mean);
@@ -2285,15 +2332,17 @@ int predict_grad_var(gpx_handle* h, const void* Xq, int64_t M, void* mean, void*
 
 template <typename T>
 int predict_grad_impl(gpx_handle* h, const void* Xq, int64_t M, void* mean, void* var, void* dmean, void* dvar,
-                      int32_t mem_kind) {
+                      int32_t mem_kind, const int32_t* gq = nullptr) {
   reset_predict_clocks(h->tm);
   int rc;
   {
     PhaseScope total(h, &h->tm.predict_total);
-    if (!var && !dvar && !h->has_deriv)  // (the matrix-free product knows no derivative columns: the batch route then)
+    // (the matrix-free product knows neither derivative columns nor path ids: the batch route then)
+    if (!var && !dvar && !h->has_deriv && !gq)
       rc = predict_grad_mean_only<T>(h, Xq, M, mean, dmean, mem_kind);
     else
-      rc = predict_grad_var<T>(h, Xq, M, mean, var, dmean, dvar, mem_kind, "gpx_predict_grad");
+      rc = predict_grad_var<T>(h, Xq, M, mean, var, dmean, dvar, mem_kind, gq ? "gpx_predict_grad_paths" : "gpx_predict_grad",
+                               gq);
     if (rc) return rc;
   }
   return finish_call(h);
@@ -3051,6 +3100,105 @@ int gpx_predict_grad(gpx_handle* h, const void* Xq, int64_t M, void* mean, void*
 }
 GPX_CATCH_ALL
 
+// ---- the path itself, f + g_p: the four posterior calls with a path id per query point --------------------
+namespace {
+// What the *_paths calls refuse beyond their plain twins' argument checks, before anything is computed: handles the
+// joint-posterior calls refuse, a fit without effective path ids, a null gq or an id below -1 (ids on the device are read
+// back for the check).
+int query_ids_refused(gpx_handle* h, const char* fn, const int32_t* gq, int64_t M, int32_t mem_kind) {
+  char buf[256];
+  int rc;
+  if (!gq) {
+    snprintf(buf, sizeof buf, "%s: bad argument", fn);
+    return fail(h, GPX_E_ARG, buf);
+  }
+  if ((rc = posterior_refused(h, fn))) return rc;
+  if (!h->grouped) {
+    snprintf(buf, sizeof buf, "%s: the current fit has no path ids (gpx_set_path_groups with an id >= 0 and sg2 > 0 before the fit)",
+             fn);
+    return fail(h, GPX_E_UNSUPPORTED, buf);
+  }
+  std::vector<int32_t> dev;
+  const int32_t* ids = gq;
+  if (mem_kind == GPX_MEM_DEVICE) {
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    dev.resize((size_t)M);
+    HIPCHK(h, hipMemcpy(dev.data(), gq, (size_t)M * sizeof(int32_t), hipMemcpyDeviceToHost));
+    ids = dev.data();
+  }
+  for (int64_t i = 0; i < M; ++i)
+    if (ids[i] < -1) {
+      snprintf(buf, sizeof buf, "%s: path id %d of query point %lld is below -1", fn, (int)ids[i], (long long)i);
+      return fail(h, GPX_E_ARG, buf);
+    }
+  return GPX_OK;
+}
+}  // namespace
+
+int gpx_predict_paths(gpx_handle* h, const void* Xq, const int32_t* gq, int64_t M, void* mean, void* var,
+                      int32_t mem_kind) try {
+  if (!h) return GPX_E_ARG;
+  if (!h->fitted) return fail(h, GPX_E_ARG, "gpx_predict_paths: handle has no successful fit");
+  if (!Xq || !mean || M <= 0) return fail(h, GPX_E_ARG, "gpx_predict_paths: bad argument");
+  if (mem_kind != GPX_MEM_HOST && mem_kind != GPX_MEM_DEVICE) return fail(h, GPX_E_ARG, "gpx_predict_paths: bad mem_kind");
+  if (M > (int64_t)INT_MAX - 4096) return fail(h, GPX_E_ARG, "gpx_predict_paths: M too large");
+  int rc;
+  if ((rc = query_ids_refused(h, "gpx_predict_paths", gq, M, mem_kind))) return rc;
+  if ((rc = begin_call(h))) return rc;
+  return BY_DTYPE(h, predict_impl, h, Xq, M, mean, var, mem_kind, gq);
+}
+GPX_CATCH_ALL
+
+int gpx_predict_cov_paths(gpx_handle* h, const void* Xq, const int32_t* gq, int64_t M, void* mean, void* cov,
+                          int32_t mem_kind) try {
+  if (!h) return GPX_E_ARG;
+  if (!Xq || !cov || M <= 0) return fail(h, GPX_E_ARG, "gpx_predict_cov_paths: bad argument");
+  if (mem_kind != GPX_MEM_HOST && mem_kind != GPX_MEM_DEVICE) return fail(h, GPX_E_ARG, "gpx_predict_cov_paths: bad mem_kind");
+  if (!h->fitted) return fail(h, GPX_E_ARG, "gpx_predict_cov_paths: handle has no successful fit");
+  if (M > (int64_t)INT_MAX - 4096) return fail(h, GPX_E_ARG, "gpx_predict_cov_paths: M too large");
+  int rc;
+  if ((rc = query_ids_refused(h, "gpx_predict_cov_paths", gq, M, mem_kind))) return rc;
+  if ((rc = begin_call(h))) return rc;
+  return BY_DTYPE(h, predict_cov_impl, h, Xq, M, mean, cov, mem_kind, gq);
+}
+GPX_CATCH_ALL
+
+int gpx_sample_posterior_paths(gpx_handle* h, const void* Xq, const int32_t* gq, int64_t M, int64_t S, uint64_t seed,
+                               const void* z, double diag_add, double jitter, int32_t max_tries, void* out,
+                               double* jitter_used, int64_t* info, int32_t mem_kind) try {
+  if (!h) return GPX_E_ARG;
+  if (!Xq || !out || !info || !jitter_used || M <= 0 || S <= 0)
+    return fail(h, GPX_E_ARG, "gpx_sample_posterior_paths: bad argument");
+  if (mem_kind != GPX_MEM_HOST && mem_kind != GPX_MEM_DEVICE)
+    return fail(h, GPX_E_ARG, "gpx_sample_posterior_paths: bad mem_kind");
+  if (!(diag_add >= 0.0) || !(jitter >= 0.0) || max_tries < 1)
+    return fail(h, GPX_E_ARG, "gpx_sample_posterior_paths: need diag_add >= 0, jitter >= 0, max_tries >= 1");
+  if (!h->fitted) return fail(h, GPX_E_ARG, "gpx_sample_posterior_paths: handle has no successful fit");
+  if (M > (int64_t)INT_MAX - 4096 || S > (int64_t)1 << 40)
+    return fail(h, GPX_E_ARG, "gpx_sample_posterior_paths: M or S too large");
+  int rc;
+  if ((rc = query_ids_refused(h, "gpx_sample_posterior_paths", gq, M, mem_kind))) return rc;
+  if ((rc = begin_call(h))) return rc;
+  return BY_DTYPE(h, sample_posterior_impl, h, Xq, M, S, seed, z, diag_add, jitter, max_tries, out, jitter_used, info,
+                  mem_kind, gq);
+}
+GPX_CATCH_ALL
+
+int gpx_predict_grad_paths(gpx_handle* h, const void* Xq, const int32_t* gq, int64_t M, void* mean, void* var, void* dmean,
+                           void* dvar, int32_t mem_kind) try {
+  if (!h) return GPX_E_ARG;
+  if (!Xq || !dmean || M <= 0) return fail(h, GPX_E_ARG, "gpx_predict_grad_paths: bad argument");
+  if (mem_kind != GPX_MEM_HOST && mem_kind != GPX_MEM_DEVICE) return fail(h, GPX_E_ARG, "gpx_predict_grad_paths: bad mem_kind");
+  if (!h->fitted) return fail(h, GPX_E_ARG, "gpx_predict_grad_paths: handle has no successful fit");
+  if (M > (int64_t)INT_MAX - 4096) return fail(h, GPX_E_ARG, "gpx_predict_grad_paths: M too large");
+  if (!cov::differentiable(h->cfg.kernel)) return fail(h, GPX_E_UNSUPPORTED, "gpx_predict_grad_paths: " MATERN12_NO_GRAD);
+  int rc;
+  if ((rc = query_ids_refused(h, "gpx_predict_grad_paths", gq, M, mem_kind))) return rc;
+  if ((rc = begin_call(h))) return rc;
+  return BY_DTYPE(h, predict_grad_impl, h, Xq, M, mean, var, dmean, dvar, mem_kind, gq);
+}
+GPX_CATCH_ALL
+
 namespace {
 // gpx_score_blocks (wq null) and gpx_score_blocks_weighted: one body, so the refusals are the same
 int score_blocks_entry(gpx_handle* h, const void* Xs, const void* ys, const void* wq, int64_t G, int32_t Lg, double diag_add,
@@ -3595,18 +3743,19 @@ GPX_CATCH_ALL
 
 extern "C++" {
 namespace {
+// grad: K (d, na, nb) = the d derivative matrices by A (gpx_kernel_path_grad_matrix), else K (na, nb) (gpx_kernel_path_matrix)
 template <typename T>
 int kernel_path_matrix_t(int32_t kernel, const double* A, const int32_t* ga, int64_t na, const double* B, const int32_t* gb,
                          int64_t nb_, int32_t d, const double* lengthscale, int32_t n_ls, double sf2, const double* ls_path,
-                         int32_t n_ls_path, double sg2, double* K) {
+                         int32_t n_ls_path, double sg2, double* K, bool grad = false) {
   Scratch sc;
   if (!sc.ok) return GPX_E_HIP;
   hipStream_t st = sc.h.st;
-  const int64_t napad = round_up(na, 64), nbpad = round_up(nb_, 64), ld = nbpad;
+  const int64_t napad = round_up(na, 64), nbpad = round_up(nb_, 64), ld = nbpad, nblk = grad ? d : 1;
   T *dA = nullptr, *dB = nullptr, *dAs = nullptr, *dBs = nullptr, *dK = nullptr;
   double *dls = nullptr, *dq = nullptr;
   int32_t *dga = nullptr, *dgb = nullptr;
-  std::vector<T> hA(A, A + na * d), hB(B, B + nb_ * d), host((size_t)napad * ld);  // (rounded to T on the host)
+  std::vector<T> hA(A, A + na * d), hB(B, B + nb_ * d), host((size_t)nblk * napad * ld);  // (rounded to T on the host)
   std::vector<double> q((size_t)d);
   for (int c = 0; c < d; ++c) {
     const double r = lengthscale[n_ls == 1 ? 0 : c] / ls_path[n_ls_path == 1 ? 0 : c];
@@ -3621,7 +3770,7 @@ int kernel_path_matrix_t(int32_t kernel, const double* A, const int32_t* ga, int
   TCHK(hipMalloc(&dq, MAX_D * 8));
   TCHK(hipMalloc(&dga, (size_t)napad * 4));
   TCHK(hipMalloc(&dgb, (size_t)nbpad * 4));
-  TCHK(hipMalloc(&dK, (size_t)napad * ld * sizeof(T)));
+  TCHK(hipMalloc(&dK, (size_t)nblk * napad * ld * sizeof(T)));
   TCHK(hipMemcpyAsync(dA, hA.data(), (size_t)na * d * sizeof(T), hipMemcpyHostToDevice, st));
   TCHK(hipMemcpyAsync(dB, hB.data(), (size_t)nb_ * d * sizeof(T), hipMemcpyHostToDevice, st));
   TCHK(hipMemcpyAsync(dls, lengthscale, (size_t)n_ls * 8, hipMemcpyHostToDevice, st));
@@ -3632,12 +3781,16 @@ int kernel_path_matrix_t(int32_t kernel, const double* A, const int32_t* ga, int
   TCHK(hipMemcpyAsync(dgb, gb, (size_t)nb_ * 4, hipMemcpyHostToDevice, st));
   launch_scale_points<T>(dA, na, napad, d, dls, n_ls, dAs, st);
   launch_scale_points<T>(dB, nb_, nbpad, d, dls, n_ls, dBs, st);
-  launch_kbuild_cross_g<T>(kernel, dAs, dga, na, napad, dBs, dgb, nb_, nbpad, d, sf2, dq, sg2, dK, ld, st);
-  TCHK(hipMemcpyAsync(host.data(), dK, (size_t)napad * ld * sizeof(T), hipMemcpyDeviceToHost, st));
+  if (grad)
+    launch_kgrad_build_g<T>(kernel, dAs, dga, na, napad, dBs, dgb, nb_, nbpad, d, sf2, dls, n_ls, dq, sg2, 0, dK, ld, st);
+  else
+    launch_kbuild_cross_g<T>(kernel, dAs, dga, na, napad, dBs, dgb, nb_, nbpad, d, sf2, dq, sg2, dK, ld, st);
+  TCHK(hipMemcpyAsync(host.data(), dK, (size_t)nblk * napad * ld * sizeof(T), hipMemcpyDeviceToHost, st));
   TCHK(hipStreamSynchronize(st));
   TCHK(hipGetLastError());
-  for (int64_t i = 0; i < na; ++i)
-    for (int64_t j = 0; j < nb_; ++j) K[i * nb_ + j] = (double)host[(size_t)i * ld + j];
+  for (int64_t b = 0; b < nblk; ++b)
+    for (int64_t i = 0; i < na; ++i)
+      for (int64_t j = 0; j < nb_; ++j) K[(b * na + i) * nb_ + j] = (double)host[(size_t)(b * napad + i) * ld + j];
 done:
   for (void* p : {(void*)dA, (void*)dB, (void*)dAs, (void*)dBs, (void*)dK, (void*)dls, (void*)dq, (void*)dga, (void*)dgb})
     if (p) (void)hipFree(p);
@@ -3663,6 +3816,30 @@ int gpx_kernel_path_matrix(int32_t kernel, int32_t dtype, const double* A, const
   if (dtype == GPX_F32)
     return kernel_path_matrix_t<float>(kernel, A, ga, na, B, gb, nb_, d, lengthscale, n_ls, sf2, ls_path, n_ls_path, sg2, K);
   return kernel_path_matrix_t<double>(kernel, A, ga, na, B, gb, nb_, d, lengthscale, n_ls, sf2, ls_path, n_ls_path, sg2, K);
+}
+GPX_CATCH_ALL
+
+int gpx_kernel_path_grad_matrix(int32_t kernel, int32_t dtype, const double* A, const int32_t* ga, int64_t na,
+                                const double* B, const int32_t* gb, int64_t nb_, int32_t d, const double* lengthscale,
+                                int32_t n_ls, double sf2, const double* ls_path, int32_t n_ls_path, double sg2,
+                                double* G) try {
+  if (!A || !B || !ga || !gb || !G || !lengthscale || !ls_path || na <= 0 || nb_ <= 0 || d <= 0 || d > MAX_D ||
+      (n_ls != 1 && n_ls != d) || (n_ls_path != 1 && n_ls_path != d))
+    return GPX_E_ARG;
+  if (!cov::known(kernel) || (dtype != GPX_F64 && dtype != GPX_F32)) return GPX_E_ARG;
+  if (!(sg2 >= 0.0) || !std::isfinite(sg2)) return GPX_E_ARG;
+  for (int32_t c = 0; c < n_ls_path; ++c)
+    if (!(ls_path[c] > 0.0) || !std::isfinite(ls_path[c])) return GPX_E_ARG;
+  for (int64_t i = 0; i < na; ++i)
+    if (ga[i] < -1) return GPX_E_ARG;
+  for (int64_t i = 0; i < nb_; ++i)
+    if (gb[i] < -1) return GPX_E_ARG;
+  if (!cov::differentiable(kernel)) return fail(nullptr, GPX_E_UNSUPPORTED, "gpx_kernel_path_grad_matrix: " MATERN12_NO_GRAD);
+  if (dtype == GPX_F32)
+    return kernel_path_matrix_t<float>(kernel, A, ga, na, B, gb, nb_, d, lengthscale, n_ls, sf2, ls_path, n_ls_path, sg2, G,
+                                       true);
+  return kernel_path_matrix_t<double>(kernel, A, ga, na, B, gb, nb_, d, lengthscale, n_ls, sf2, ls_path, n_ls_path, sg2, G,
+                                      true);
 }
 GPX_CATCH_ALL
 

@@ -8,6 +8,7 @@
 //                   z^T V (mean and dmean together) -> row norms with a per-row-block prior -> unpack
 // All stores are plain vector stores; every reduction runs in a fixed order (bit-reproducible).
 #include <algorithm>
+#include <climits>
 
 #include "gpx_cov.h"
 #include "gpx_internal.h"
@@ -23,12 +24,22 @@ constexpr int GT = 64;      // tile edge of the build, query rows per workgroup 
 // KINDS: the columns are observations with a kind (gpx_cov.h; kcol readable up to the padded size, -1 there): against a
 // derivative column the value rows hold the (-1, j) element and the d_i K* rows the (i, j) element (cov::element).  A tile
 // whose 64 column kinds are all -1 — decided once per workgroup — takes the path, and gives the numbers, of the plain build.
-template <typename T, int KERNEL, int D, bool KINDS = false>
+// GROUPS (never with KINDS): rows and columns carry path ids (krow / kcol, readable up to the padded sizes, -1 there) and a
+// same-path pair gets + sg2 k(., .; l_path) and its derivative; q holds q_c = (l_c / l_path,c)^2 (d
+// entries).  The 64 + 64 ids and q are staged beside the points; whether the tile can hold a same-path pair — the ranges of
+// the non-negative row and column ids overlap — is decided once per workgroup, wave-uniform, as kbuild_kernel does.  A tile
+// that cannot takes the path, and gives the numbers, of the plain build.  Otherwise r_path^2 = sum_c q_c e_c^2 beside r^2, from
+// the same differences e_c, and where the ids match the value row gains cov::value_g's v and row block j gains -g_path q_j e_j / l_j: with u' = x / l_path, u'_j - u'_j' = sqrt(q_j) e_j and
+// d / d x_j = -g_path (u'_j - u'_j') / l_path,j.  One more exponential per matching pair, none for the others.
+template <typename T, int KERNEL, int D, bool KINDS = false, bool GROUPS = false>
 __global__ __launch_bounds__(256) void kgrad_build_kernel(const T* __restrict__ As, int64_t m, const T* __restrict__ Bs,
                                                          int64_t n, int d_rt, int tiles_n, T sf2,
                                                          const double* __restrict__ ls, int n_ls, int with_value,
                                                          T* __restrict__ V, int64_t ld, int64_t mpad,
-                                                         const int32_t* __restrict__ kcol = nullptr) {
+                                                         const int32_t* __restrict__ kcol = nullptr,
+                                                         const int32_t* __restrict__ krow = nullptr,
+                                                         const double* __restrict__ q = nullptr, T sg2 = (T)0) {
+  static_assert(!(KINDS && GROUPS), "a fit has kinds or path ids, never both");
   const int d = (D > 0) ? D : d_rt;
   __shared__ T xa[GT * (D > 0 ? D : MAX_D)];
   __shared__ T xb[GT * (D > 0 ? D : MAX_D)];
@@ -43,6 +54,7 @@ __global__ __launch_bounds__(256) void kgrad_build_kernel(const T* __restrict__ 
   if (tid < d) il[tid] = (T)(1.0 / ls[n_ls == 1 ? 0 : tid]);
   bool mixed = false;
   const int* skb = nullptr;
+  [[maybe_unused]] const T* sq = nullptr;
   if constexpr (KINDS) {
     __shared__ int kbs[GT];
     int deriv = 0;
@@ -53,6 +65,28 @@ __global__ __launch_bounds__(256) void kgrad_build_kernel(const T* __restrict__ 
     }
     mixed = __syncthreads_or(deriv) != 0;
     skb = kbs;
+  } else if constexpr (GROUPS) {
+    __shared__ int gab[2 * GT];
+    __shared__ int rng[4];  // lowest / highest non-negative id of the rows, of the columns
+    __shared__ T qv[D > 0 ? D : MAX_D];
+    if (tid >= 256 - 2 * GT) {  // wave 2: the rows, wave 3: the columns (the first ones stage 1 / l)
+      const int t = tid - (256 - 2 * GT);
+      const int id = t < GT ? krow[i0 + t] : kcol[j0 + t - GT];
+      gab[t] = id;
+      int lo = id >= 0 ? id : INT_MAX, hi = id;
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) {
+        lo = min(lo, __shfl_xor(lo, o));
+        hi = max(hi, __shfl_xor(hi, o));
+      }
+      if ((t & 63) == 0) rng[2 * (t >> 6)] = lo, rng[2 * (t >> 6) + 1] = hi;
+    } else if (tid >= GT && tid - GT < d) {
+      qv[tid - GT] = (T)q[tid - GT];
+    }
+    __syncthreads();
+    mixed = rng[0] <= rng[3] && rng[2] <= rng[1];  // (no id >= 0 on a side: lo = INT_MAX, hi < 0)
+    skb = gab;
+    sq = qv;
   } else {
     __syncthreads();
   }
@@ -61,6 +95,56 @@ __global__ __launch_bounds__(256) void kgrad_build_kernel(const T* __restrict__ 
   const int64_t col0 = j0 + c2, col1 = col0 + 1;
   const int64_t blk = mpad * ld;  // elements per row block
   typedef T pair_t __attribute__((ext_vector_type(2)));
+  if constexpr (GROUPS) {
+    // A tile that can hold a same-path pair has a loop of its own, so that the loop below stays, statement for statement,
+    // the plain build's: the compiler contracts (1 + s) e and its like by what else uses the operands, and a shared body
+    // gave the value rows of Matern-3/2 other last bits than the plain kernel's.  One row in flight: two hold the path
+    // term's registers twice.
+    if (mixed) {
+#pragma unroll 1
+      for (int r = 0; r < 8; ++r) {
+        const int ir = rg + 8 * r;
+        const int64_t row = i0 + ir;
+        T s0 = (T)0, s1 = (T)0, p0 = (T)0, p1 = (T)0;  // r^2 and r_path^2 of the lane's two pairs
+        for (int c = 0; c < d; ++c) {
+          const T a = xa[ir * d + c];
+          const T e0 = a - xb[c2 * d + c], e1 = a - xb[(c2 + 1) * d + c];
+          s0 += e0 * e0;
+          s1 += e1 * e1;
+          p0 += sq[c] * (e0 * e0);
+          p1 += sq[c] * (e1 * e1);
+        }
+        T v0, g0, v1, g1;
+        cov::value_g<KERNEL>(s0, sf2, v0, g0);
+        cov::value_g<KERNEL>(s1, sf2, v1, g1);
+        const bool ok0 = row < m && col0 < n, ok1 = row < m && col1 < n;
+        T* out = V + row * ld + col0;
+        const int ga = skb[ir];
+        // One branch for the lane's two pairs, not one each: two divergent regions cost 8 - 20 VGPRs and an occupancy step
+        // (compiler's resource report).  A pair of two paths keeps pv = pg = 0: -g e - 0 below.
+        T pv0 = (T)0, pg0 = (T)0, pv1 = (T)0, pg1 = (T)0;
+        const bool m0 = ga >= 0 && ga == skb[GT + c2], m1 = ga >= 0 && ga == skb[GT + c2 + 1];
+        if (m0 || m1) {
+          cov::value_g<KERNEL>(p0, sg2, pv0, pg0);
+          cov::value_g<KERNEL>(p1, sg2, pv1, pg1);
+          if (!m0) pv0 = pg0 = (T)0;
+          if (!m1) pv1 = pg1 = (T)0;
+        }
+        if (with_value) {
+          pair_t w = {ok0 ? v0 + pv0 : (T)0, ok1 ? v1 + pv1 : (T)0};
+          __builtin_nontemporal_store(w, reinterpret_cast<pair_t*>(out));
+          out += blk;
+        }
+        for (int c = 0; c < d; ++c) {
+          const T a = xa[ir * d + c];
+          const T e0 = (a - xb[c2 * d + c]) * il[c], e1 = (a - xb[(c2 + 1) * d + c]) * il[c];
+          pair_t w = {ok0 ? -g0 * e0 - pg0 * (sq[c] * e0) : (T)0, ok1 ? -g1 * e1 - pg1 * (sq[c] * e1) : (T)0};
+          __builtin_nontemporal_store(w, reinterpret_cast<pair_t*>(out + c * blk));
+        }
+      }
+      return;
+    }
+  }
 #pragma unroll 2
   for (int r = 0; r < 8; ++r) {
     const int ir = rg + 8 * r;
@@ -221,10 +305,12 @@ __device__ __forceinline__ double block_sum(double v, double* red) {
 }
 
 // one workgroup per valid row i of row block b = blockIdx.y:  out[b mp + i] = prior[b] - sum_j V[b mp + i][j]^2
-// (fp64 accumulation, var_rows_kernel's fixed order)
+// (fp64 accumulation, var_rows_kernel's fixed order).  ids != null: query point i with a path id >= 0 is a value of f + g_p,
+// and its prior is pr[b] + pg[b], the sum formed in fp64 before the same subtraction.
 template <typename T>
 __global__ __launch_bounds__(256) void grad_norms_kernel(const T* __restrict__ V, int64_t ld, int64_t mp, int64_t ncols,
-                                                        Priors pr, T* __restrict__ out) {
+                                                        Priors pr, T* __restrict__ out,
+                                                        const int32_t* __restrict__ ids = nullptr, Priors pg = {}) {
   typedef T pair_t __attribute__((ext_vector_type(2)));
   __shared__ double red[4];
   const int64_t r = (int64_t)blockIdx.y * mp + blockIdx.x;
@@ -236,7 +322,10 @@ __global__ __launch_bounds__(256) void grad_norms_kernel(const T* __restrict__ V
     s1 += (double)v.y * (double)v.y;
   }
   const double s = block_sum(s0 + s1, red);
-  if (threadIdx.x == 0) out[r] = (T)(pr.p[blockIdx.y] - s);
+  if (threadIdx.x == 0) {
+    const double prior = (ids && ids[blockIdx.x] >= 0) ? pr.p[blockIdx.y] + pg.p[blockIdx.y] : pr.p[blockIdx.y];
+    out[r] = (T)(prior - s);
+  }
 }
 
 // the permuting unpack of one batch: column b mp + i of MT (row c = target) and entry b mp + i of VN (norms) go to
@@ -271,11 +360,22 @@ unsigned grid_for(int64_t work) {
 
 template <typename T, int KERNEL>
 void build_d(const T* As, int64_t m, int64_t mpad, const T* Bs, int64_t n, int64_t npad, int d, double sf2,
-             const double* ls, int n_ls, int with_value, T* V, int64_t ld, hipStream_t st, const int32_t* kcol) {
+             const double* ls, int n_ls, int with_value, T* V, int64_t ld, hipStream_t st, const int32_t* kcol,
+             const int32_t* grow, const double* q, double sg2) {
   const int64_t tm = mpad / GT, tn = npad / GT;
   dim3 grid((unsigned)(tm * tn)), block(256);
   const T s = (T)sf2;
   const int tnn = (int)tn;
+  if (grow) {  // rows and columns with path ids (kcol: the columns')
+    const T sg = (T)sg2;
+    switch (d) {
+      case 1: hipLaunchKernelGGL((kgrad_build_kernel<T, KERNEL, 1, false, true>), grid, block, 0, st, As, m, Bs, n, d, tnn, s, ls, n_ls, with_value, V, ld, mpad, kcol, grow, q, sg); break;
+      case 2: hipLaunchKernelGGL((kgrad_build_kernel<T, KERNEL, 2, false, true>), grid, block, 0, st, As, m, Bs, n, d, tnn, s, ls, n_ls, with_value, V, ld, mpad, kcol, grow, q, sg); break;
+      case 3: hipLaunchKernelGGL((kgrad_build_kernel<T, KERNEL, 3, false, true>), grid, block, 0, st, As, m, Bs, n, d, tnn, s, ls, n_ls, with_value, V, ld, mpad, kcol, grow, q, sg); break;
+      default: hipLaunchKernelGGL((kgrad_build_kernel<T, KERNEL, 0, false, true>), grid, block, 0, st, As, m, Bs, n, d, tnn, s, ls, n_ls, with_value, V, ld, mpad, kcol, grow, q, sg); break;
+    }
+    return;
+  }
   if (kcol) {  // observations with kinds
     switch (d) {
       case 1: hipLaunchKernelGGL((kgrad_build_kernel<T, KERNEL, 1, true>), grid, block, 0, st, As, m, Bs, n, d, tnn, s, ls, n_ls, with_value, V, ld, mpad, kcol); break;
@@ -328,7 +428,14 @@ template <typename T>
 void launch_kgrad_build(int kernel, const T* As, int64_t m, int64_t mpad, const T* Bs, int64_t n, int64_t npad, int d,
                         double sf2, const double* ls, int n_ls, int with_value, T* V, int64_t ld, hipStream_t st,
                         const int32_t* kind_b) {
-  cov::dispatch_differentiable(kernel, [&](auto fam) { build_d<T, fam>(As, m, mpad, Bs, n, npad, d, sf2, ls, n_ls, with_value, V, ld, st, kind_b); });
+  cov::dispatch_differentiable(kernel, [&](auto fam) { build_d<T, fam>(As, m, mpad, Bs, n, npad, d, sf2, ls, n_ls, with_value, V, ld, st, kind_b, nullptr, nullptr, 0.0); });
+}
+
+template <typename T>
+void launch_kgrad_build_g(int kernel, const T* As, const int32_t* group_a, int64_t m, int64_t mpad, const T* Bs,
+                          const int32_t* group_b, int64_t n, int64_t npad, int d, double sf2, const double* ls, int n_ls,
+                          const double* q, double sg2, int with_value, T* V, int64_t ld, hipStream_t st) {
+  cov::dispatch_differentiable(kernel, [&](auto fam) { build_d<T, fam>(As, m, mpad, Bs, n, npad, d, sf2, ls, n_ls, with_value, V, ld, st, group_b, group_a, q, sg2); });
 }
 
 void kgrad_matvec_shape(int64_t M, int64_t npad, int d, int k, int* KC, int* S, int64_t* chunk) {
@@ -361,12 +468,14 @@ void launch_kgrad_matvec(int kernel, const T* As, int64_t M, const T* Bs, int64_
 
 template <typename T>
 void launch_grad_norms(const T* V, int64_t ld, int64_t mp, int64_t mv, int nblk, int64_t ncols, const double* prior,
-                       T* out, hipStream_t st) {
+                       T* out, hipStream_t st, const int32_t* ids, const double* prior_path) {
   if (mv <= 0 || nblk <= 0) return;
-  Priors pr{};
+  Priors pr{}, pg{};
   for (int b = 0; b < nblk && b <= MAX_D; ++b) pr.p[b] = prior[b];
+  if (ids)
+    for (int b = 0; b < nblk && b <= MAX_D; ++b) pg.p[b] = prior_path[b];
   hipLaunchKernelGGL(grad_norms_kernel<T>, dim3((unsigned)mv, (unsigned)nblk), dim3(256), 0, st, V, ld, mp, ncols, pr,
-                     out);
+                     out, ids, pg);
 }
 
 template <typename T>
@@ -382,8 +491,11 @@ void launch_grad_unpack(const T* MT, int64_t ldm, const T* VN, int64_t mp, int64
                                       const double*, int, int, T*, int64_t, hipStream_t, const int32_t*);             \
   template void launch_kgrad_matvec<T>(int, const T*, int64_t, const T*, int64_t, int, double, const T*, int64_t, int, \
                                        const double*, int, T*, T*, hipStream_t);                                      \
+  template void launch_kgrad_build_g<T>(int, const T*, const int32_t*, int64_t, int64_t, const T*, const int32_t*,    \
+                                        int64_t, int64_t, int, double, const double*, int, const double*, double,    \
+                                        int, T*, int64_t, hipStream_t);                                               \
   template void launch_grad_norms<T>(const T*, int64_t, int64_t, int64_t, int, int64_t, const double*, T*,            \
-                                     hipStream_t);                                                                    \
+                                     hipStream_t, const int32_t*, const double*);                                     \
   template void launch_grad_unpack<T>(const T*, int64_t, const T*, int64_t, int64_t, int, int, int, int, T*, T*, T*,  \
                                       T*, hipStream_t);
 GPX_INSTANTIATE_DERIV(double)

@@ -240,10 +240,11 @@ void launch_pack_rhs(const T* y, int64_t n, int k, T* YT, int64_t ld, int64_t np
 // out (n x k) <- rows [0,k) of YT (R x *, ld), scaled by `scale`.
 template <typename T>
 void launch_unpack_rhs(const T* YT, int64_t ld, int64_t n, int k, double scale, T* out, hipStream_t st);
-// var[i] = sf2 - sum_j VT[i, j]^2, i < m  (accumulated in fp64).
+// var[i] = sf2 - sum_j VT[i, j]^2, i < m  (accumulated in fp64).  ids != null (device, m entries): the prior of a row i with
+// ids[i] >= 0 is sf2 + sg2, summed in fp64.
 template <typename T>
 void launch_var_rows(const T* VT, int64_t ld, int64_t m, int64_t ncols, double sf2, T* var,
-                     hipStream_t st);
+                     hipStream_t st, const int32_t* ids = nullptr, double sg2 = 0.0);
 // dst (rows x cols, ldd) = src (rows x cols, lds), streaming; cols * sizeof(T) multiple of 16, 16-byte aligned rows
 template <typename T>
 void launch_copy2d(T* dst, int64_t ldd, const T* src, int64_t lds, int64_t rows, int64_t cols, hipStream_t st);
@@ -369,6 +370,12 @@ template <typename T>
 void launch_kgrad_build(int kernel, const T* As, int64_t m, int64_t mpad, const T* Bs, int64_t n, int64_t npad, int d,
                         double sf2, const double* ls, int n_ls, int with_value, T* V, int64_t ld, hipStream_t st,
                         const int32_t* kind_b = nullptr);
+// The same over rows and columns with path ids (launch_kbuild_cross_g's arguments): a same-path pair gets the value and the
+// derivative of sg2 k(., .; l_path) as well; a tile that can hold no such pair gives launch_kgrad_build's numbers.
+template <typename T>
+void launch_kgrad_build_g(int kernel, const T* As, const int32_t* group_a, int64_t m, int64_t mpad, const T* Bs,
+                          const int32_t* group_b, int64_t n, int64_t npad, int d, double sf2, const double* ls, int n_ls,
+                          const double* q, double sg2, int with_value, T* V, int64_t ld, hipStream_t st);
 // grid of the matrix-free product: KC targets per workgroup, S splits of `chunk` training columns; the partial buffer
 // holds S * k * d * round_up(M, 64) elements
 void kgrad_matvec_shape(int64_t M, int64_t npad, int d, int k, int* KC, int* S, int64_t* chunk);
@@ -378,10 +385,11 @@ template <typename T>
 void launch_kgrad_matvec(int kernel, const T* As, int64_t M, const T* Bs, int64_t npad, int d, double sf2,
                          const T* alphaT, int64_t lda, int k, const double* ls, int n_ls, T* part, T* dmean,
                          hipStream_t st);
-// out[b mp + i] = prior[b] - sum_{j < ncols} V[b mp + i][j]^2 for i < mv, b < nblk (<= 33; prior on the host)
+// out[b mp + i] = prior[b] - sum_{j < ncols} V[b mp + i][j]^2 for i < mv, b < nblk (<= 33; prior on the host).
+// ids != null (device, mv entries): the prior of a row i with ids[i] >= 0 is prior[b] + prior_path[b], summed in fp64
 template <typename T>
 void launch_grad_norms(const T* V, int64_t ld, int64_t mp, int64_t mv, int nblk, int64_t ncols, const double* prior,
-                       T* out, hipStream_t st);
+                       T* out, hipStream_t st, const int32_t* ids = nullptr, const double* prior_path = nullptr);
 // one batch of the variance route: column b mp + i of MT (RHS rows = targets) and entry b mp + i of VN, i < mv, into
 // mean (mv, k) / var (mv) (row block 0 when with_value) and dmean (mv, d, k) / dvar (mv, d); mean, var, dvar may be null
 template <typename T>

@@ -41,10 +41,12 @@ __device__ __forceinline__ double block_sum(double v, double* red) {
   return s;
 }
 
-// one workgroup per row: var[i] = sf2 - sum_j VT[i][j]^2  (fp64 accumulation, fixed order)
+// one workgroup per row: var[i] = sf2 - sum_j VT[i][j]^2  (fp64 accumulation, fixed order).  ids != null: a row whose query
+// point has a path id >= 0 is a value of f + g_p, prior sf2 + sg2 (the sum in fp64, then the same subtraction).
 template <typename T>
 __global__ __launch_bounds__(256) void var_rows_kernel(const T* __restrict__ VT, int64_t ld,
-                                                      int64_t ncols, double sf2, T* __restrict__ var) {
+                                                      int64_t ncols, double sf2, T* __restrict__ var,
+                                                      const int32_t* __restrict__ ids = nullptr, double sg2 = 0.0) {
   typedef T pair_t __attribute__((ext_vector_type(2)));
   __shared__ double red[4];
   const T* row = VT + (int64_t)blockIdx.x * ld;
@@ -55,7 +57,10 @@ __global__ __launch_bounds__(256) void var_rows_kernel(const T* __restrict__ VT,
     s1 += (double)v.y * (double)v.y;
   }
   const double s = block_sum(s0 + s1, red);
-  if (threadIdx.x == 0) var[blockIdx.x] = (T)(sf2 - s);
+  if (threadIdx.x == 0) {
+    const double prior = (ids && ids[blockIdx.x] >= 0) ? sf2 + sg2 : sf2;
+    var[blockIdx.x] = (T)(prior - s);
+  }
 }
 
 // dst (rows x cols, ldd) = src (rows x cols, lds); cols * sizeof(T) a multiple of 16, rows 16-byte
@@ -358,9 +363,10 @@ void launch_unpack_rhs(const T* YT, int64_t ld, int64_t n, int k, double scale, 
 }
 
 template <typename T>
-void launch_var_rows(const T* VT, int64_t ld, int64_t m, int64_t ncols, double sf2, T* var, hipStream_t st) {
+void launch_var_rows(const T* VT, int64_t ld, int64_t m, int64_t ncols, double sf2, T* var, hipStream_t st,
+                     const int32_t* ids, double sg2) {
   if (m <= 0) return;
-  hipLaunchKernelGGL(var_rows_kernel<T>, dim3((unsigned)m), dim3(256), 0, st, VT, ld, ncols, sf2, var);
+  hipLaunchKernelGGL(var_rows_kernel<T>, dim3((unsigned)m), dim3(256), 0, st, VT, ld, ncols, sf2, var, ids, sg2);
 }
 
 // ---- timing perturbation (test hook) -------------------------------------------------------------
@@ -475,7 +481,7 @@ void launch_logdet(const T* A, int64_t lda, int64_t n, double* out, hipStream_t 
 #define GPX_INSTANTIATE_MISC(T)                                                                    \
   template void launch_pack_rhs<T>(const T*, int64_t, int, T*, int64_t, int64_t, int, hipStream_t); \
   template void launch_unpack_rhs<T>(const T*, int64_t, int64_t, int, double, T*, hipStream_t);     \
-  template void launch_var_rows<T>(const T*, int64_t, int64_t, int64_t, double, T*, hipStream_t);   \
+  template void launch_var_rows<T>(const T*, int64_t, int64_t, int64_t, double, T*, hipStream_t, const int32_t*, double); \
   template void launch_logdet<T>(const T*, int64_t, int64_t, double*, hipStream_t);                 \
   template void launch_set_diag_one_t<T>(T*, int64_t, int64_t, hipStream_t);                        \
   template void launch_copy2d<T>(T*, int64_t, const T*, int64_t, int64_t, int64_t, hipStream_t);           \

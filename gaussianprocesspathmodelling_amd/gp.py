@@ -464,6 +464,22 @@ class GP:
             return C.c_void_p(t.data_ptr()), t
         return C.c_void_p(a.ctypes.data), a
 
+    def _query_ids(self, path_ids, M, kind, dev):
+        """``path_ids`` of M query points -> pointer and keepalive of (M,) int32 ids where the query points live: an int
+        names one path for every point, an array or tensor gives one id per point (-1: the cluster mean ``f``)."""
+        if _is_torch(path_ids):
+            path_ids = path_ids.detach().cpu().numpy()
+        a = np.asarray(path_ids)
+        if a.dtype.kind not in "iu":
+            raise ValueError("path_ids must be integers (-1: the cluster mean, p >= 0: the path p itself)")
+        if a.ndim == 0:
+            a = np.full((M,), int(a))
+        if a.shape != (M,):
+            raise ValueError(f"path_ids must be an int or ({M},), one id per query point")
+        if a.size and (a.min() < np.iinfo(np.int32).min or a.max() > np.iinfo(np.int32).max):
+            raise ValueError("path_ids must fit int32")
+        return self._side_input(np.ascontiguousarray(a, dtype=np.int32), kind, dev)
+
     def update(self, X_new, y_new, noise_weights=None, derivatives=None, path_ids=None):
         """Append observations to the fitted model without factorising the old ones again (``gpx_append``): afterwards
         the model is, to rounding, what ``fit`` of the concatenated data with the same hyper-parameters and the jitter
@@ -623,14 +639,21 @@ class GP:
             var += self.noise
         return mean, var
 
-    def predict(self, Xs, return_var=True, include_noise=False, return_cov=False):
+    def predict(self, Xs, return_var=True, include_noise=False, return_cov=False, path_ids=None):
         """Posterior at the query points ``Xs`` (M, d): ``mean`` ((M,) for a 1-D ``y``, else (M, k)) and, with
         ``return_var``, the per-point variance (M,).  ``return_cov=True`` returns ``(mean, cov)`` instead, ``cov`` the
         joint (M, M) posterior covariance of the latent function (``gpx_predict_cov``: one SYRK more than the variance;
         the same for every target column), with ``noise`` on its diagonal when ``include_noise``.  ``include_noise``
         adds ``noise`` times 1 also on a model fitted with ``noise_weights``: a query point has no weight of its own
         (scale the latent variance yourself for another one).  NumPy in, NumPy out; a device tensor in, device tensors
-        out."""
+        out.
+
+        ``path_ids`` (a model fitted with path ids; ``gpx_predict_paths`` / ``gpx_predict_cov_paths``): an int, or one
+        int per query point.  ``-1`` asks for the cluster mean ``f``, as without the argument; ``p >= 0`` asks for the
+        path ``p`` itself, ``f + g_p`` — where the path was, is or will be, conditioned on its own observations too.
+        An id no observation carries is a path nobody has seen: the mean of ``f``, the variance of ``f`` plus the
+        prior ``path_variance``.  Ids may be mixed in one call; the joint covariance couples points of one path
+        through ``g_p`` as well."""
         if not self._fitted:
             raise RuntimeError("predict() before a successful fit()")
         pq, kq, keepq, devq, sq = self._as_input(Xs, "Xs")
@@ -638,9 +661,13 @@ class GP:
             raise ValueError(f"Xs must be (M, {self._d})")
         M = sq[0]
         mshape = (M,) if self._y1d else (M, self._k)
+        pg, keepg = (None, None) if path_ids is None else self._query_ids(path_ids, M, kq, devq)
         if return_cov:
             mean, cov = self._empty(mshape, devq), self._empty((M, M), devq)
-            self._check(self._lib.gpx_predict_cov(self._h, pq, M, self._ptr(mean), self._ptr(cov), kq))
+            if pg is None:
+                self._check(self._lib.gpx_predict_cov(self._h, pq, M, self._ptr(mean), self._ptr(cov), kq))
+            else:
+                self._check(self._lib.gpx_predict_cov_paths(self._h, pq, pg, M, self._ptr(mean), self._ptr(cov), kq))
             if include_noise:
                 if devq is not None:
                     cov.diagonal().add_(self.noise)
@@ -659,20 +686,24 @@ class GP:
             var = np.empty((M,), dtype=self._np_dtype) if return_var else None
             pm = C.c_void_p(mean.ctypes.data)
             pv = C.c_void_p(var.ctypes.data) if return_var else None
-        self._check(self._lib.gpx_predict(self._h, pq, M, pm, pv, kq))
+        if pg is None:
+            self._check(self._lib.gpx_predict(self._h, pq, M, pm, pv, kq))
+        else:
+            self._check(self._lib.gpx_predict_paths(self._h, pq, pg, M, pm, pv, kq))
         if not return_var:
             return mean
         if include_noise:
             var += self.noise
         return mean, var
 
-    def predict_gradient(self, Xs, return_var=True, with_value=False):
+    def predict_gradient(self, Xs, return_var=True, with_value=False, path_ids=None):
         """Gradient of the posterior with respect to the query points ``Xs`` (M, d) (``gpx_predict_grad``): ``dmean``
         ((M, d) for a 1-D ``y``, else (M, d, k)) and, with ``return_var``, ``dvar`` (M, d), the latent variance of each
         partial derivative (no noise term: white noise has no derivative).  ``with_value=True`` returns
         ``(mean, var, dmean, dvar)`` from the same pass (``(mean, dmean)`` without ``return_var``), ``mean`` and ``var``
         shaped as :meth:`predict`'s.  Without variances the device contracts the kernel derivative with the cached
-        ``alpha`` matrix-free (no solve).  NumPy in, NumPy out; a device tensor in, device tensors out."""
+        ``alpha`` matrix-free (no solve).  NumPy in, NumPy out; a device tensor in, device tensors out.  ``path_ids``
+        as :meth:`predict`'s (``gpx_predict_grad_paths``): the gradient of ``f + g_p`` for ids ``>= 0``."""
         if not self._fitted:
             raise RuntimeError("predict_gradient() before a successful fit()")
         pq, kq, keepq, devq, sq = self._as_input(Xs, "Xs")
@@ -684,7 +715,11 @@ class GP:
         mean = self._empty((M,) if self._y1d else (M, k), devq) if with_value else None
         var = self._empty((M,), devq) if with_value and return_var else None
         p = lambda a: None if a is None else self._ptr(a)  # noqa: E731
-        self._check(self._lib.gpx_predict_grad(self._h, pq, M, p(mean), p(var), p(dmean), p(dvar), kq))
+        if path_ids is None:
+            self._check(self._lib.gpx_predict_grad(self._h, pq, M, p(mean), p(var), p(dmean), p(dvar), kq))
+        else:
+            pg, keepg = self._query_ids(path_ids, M, kq, devq)
+            self._check(self._lib.gpx_predict_grad_paths(self._h, pq, pg, M, p(mean), p(var), p(dmean), p(dvar), kq))
         if with_value:
             return (mean, var, dmean, dvar) if return_var else (mean, dmean)
         return (dmean, dvar) if return_var else dmean
@@ -823,7 +858,8 @@ class GP:
     def _ptr(a):
         return C.c_void_p(a.data_ptr() if _is_torch(a) else a.ctypes.data)
 
-    def sample_y(self, Xs, n_samples=1, random_state=0, include_noise=False, z=None, jitter=None, max_tries=8):
+    def sample_y(self, Xs, n_samples=1, random_state=0, include_noise=False, z=None, jitter=None, max_tries=8,
+                 path_ids=None):
         """Joint samples of the posterior at ``Xs`` (M, d), shaped as scikit-learn's ``sample_y``: (M, S) for a 1-D
         ``y``, (M, k, S) otherwise, S = ``n_samples``.  Sample s of target c is ``mean[:, c] + L_S z[s, :, c]`` with
         ``L_S = chol(cov + (diag_add + j) I)`` (``gpx_sample_posterior``), ``diag_add = noise`` when ``include_noise``.
@@ -831,7 +867,8 @@ class GP:
         ``random_state`` (an int; include/gpx.h specifies it, so a sample depends only on the seed, its index, M and k).
         ``jitter`` (None: the model's jitter for float64, 1e-6 variance for float32) is multiplied by 10 after a failed
         factorisation, at most ``max_tries`` attempts; the value that worked is ``sample_jitter_``.  Raises
-        ``numpy.linalg.LinAlgError`` when none did.  NumPy in, NumPy out; a device tensor in, a device tensor out."""
+        ``numpy.linalg.LinAlgError`` when none did.  NumPy in, NumPy out; a device tensor in, a device tensor out.
+        ``path_ids`` as :meth:`predict`'s (``gpx_sample_posterior_paths``): samples of the paths themselves."""
         if not self._fitted:
             raise RuntimeError("sample_y() before a successful fit()")
         pq, kq, keepq, devq, sq = self._as_input(Xs, "Xs")
@@ -861,9 +898,15 @@ class GP:
             pz = self._ptr(keepz)
         out = self._empty((S, M, k), devq)
         used, info = C.c_double(0.0), C.c_int64(0)
-        self._check(self._lib.gpx_sample_posterior(self._h, pq, M, S, seed, pz, self.noise if include_noise else 0.0,
-                                                   float(jitter), int(max_tries), self._ptr(out), C.byref(used),
-                                                   C.byref(info), kq))
+        diag_add = self.noise if include_noise else 0.0
+        if path_ids is None:
+            self._check(self._lib.gpx_sample_posterior(self._h, pq, M, S, seed, pz, diag_add, float(jitter), int(max_tries),
+                                                       self._ptr(out), C.byref(used), C.byref(info), kq))
+        else:
+            pg, keepg = self._query_ids(path_ids, M, kq, devq)
+            self._check(self._lib.gpx_sample_posterior_paths(self._h, pq, pg, M, S, seed, pz, diag_add, float(jitter),
+                                                             int(max_tries), self._ptr(out), C.byref(used),
+                                                             C.byref(info), kq))
         if info.value != 0:
             raise np.linalg.LinAlgError(
                 f"posterior covariance not positive definite (first bad pivot {info.value}) with jitter up to "

@@ -247,9 +247,10 @@ class PathModel:
     velocities (:meth:`add_paths`, which takes none, refuses such a model).  ``velocity_noise``: the noise variance of those velocities in the model's normalised units, as given
     or as learnt (``fit_path_models(learn_velocity_noise=True)``); None without velocities.
     ``within_path``: the model is the hierarchical one (``fit_path_models(within_path=True)``): every path is the cluster
-    mean plus a deviation of its own.  :meth:`predict`, :meth:`sample` and :meth:`velocity` are then about the cluster
-    mean, :meth:`log_likelihood` scores a path as a new member of the cluster, :meth:`forecast` continues one from its
-    first points; :meth:`append_paths` adds paths under new ids (:meth:`add_paths` refuses such a model).
+    mean plus a deviation of its own.  :meth:`predict`, :meth:`sample`, :meth:`predict_gradient` and :meth:`velocity` are
+    then about the cluster mean, or with ``path=key`` about that path of ``keys`` itself (the mean plus its own deviation:
+    where it was between, at and beyond its observations); :meth:`log_likelihood` scores a path as a new member of the
+    cluster, :meth:`forecast` continues one from its first points; :meth:`append_paths` adds paths under new ids (:meth:`add_paths` refuses such a model).
     Which method adds paths: :meth:`add_paths` on plain and step-noise models, :meth:`append_paths` on every model."""
 
     def __init__(self, gp, keys, in_lo, in_span, y_mean, y_std, inputs, targets, step_weights=None, has_velocities=False,
@@ -281,50 +282,71 @@ class PathModel:
             raise ValueError(f"queries must be (M,) or (M, {len(self.inputs)})")
         return np.ascontiguousarray((q - self.in_lo) / self.in_span)
 
-    def predict(self, q, return_var=True, include_noise=False, return_cov=False):
+    def _path_kw(self, path):
+        """``path`` (None, or a key of ``self.keys``) -> the ``path_ids`` keyword of the GP's methods: a path's id is its
+        index in ``keys`` (``fit_path_models`` and :meth:`append_paths` number them so)"""
+        if path is None:
+            return {}
+        if not self.within_path:
+            raise ValueError("path= needs a within_path model (fit_path_models(within_path=True)): only there has a path a "
+                             "deviation of its own")
+        try:
+            return {"path_ids": self.keys.index(path)}
+        except ValueError:
+            raise KeyError(path) from None
+
+    def predict(self, q, return_var=True, include_noise=False, return_cov=False, path=None):
         """Posterior at raw (un-normalised) inputs ``q`` (M,) or (M, d): mean (M, k) in the
         targets' own units and, with ``return_var``, the variance (M, k) per target.  ``return_cov=True``
-        returns ``(mean (M, k), cov (k, M, M))``: the joint covariance of each target over the queries."""
+        returns ``(mean (M, k), cov (k, M, M))``: the joint covariance of each target over the queries.
+        ``path`` (a key of ``keys``; ``within_path`` models): the posterior of that path itself instead of the cluster
+        mean.  ``ValueError`` on a model that is not ``within_path``, ``KeyError`` for a key the model does not hold."""
+        kw = self._path_kw(path)
         qn = self._queries(q)
         if return_cov:
-            mean, cov = self.gp.predict(qn, include_noise=include_noise, return_cov=True)
+            mean, cov = self.gp.predict(qn, include_noise=include_noise, return_cov=True, **kw)
             mean = mean.reshape(len(qn), -1) * self.y_std + self.y_mean
             return mean, cov[None, :, :] * (self.y_std ** 2)[:, None, None]
-        out = self.gp.predict(qn, return_var=return_var, include_noise=include_noise)
+        out = self.gp.predict(qn, return_var=return_var, include_noise=include_noise, **kw)
         mean = (out[0] if return_var else out).reshape(len(qn), -1) * self.y_std + self.y_mean
         if not return_var:
             return mean
         return mean, out[1][:, None] * (self.y_std ** 2)[None, :]
 
-    def sample(self, q, n_samples, seed=0, include_noise=False):
+    def sample(self, q, n_samples, seed=0, include_noise=False, path=None):
         """``n_samples`` plausible paths of this cluster: joint posterior samples over the raw inputs ``q`` (M,) or
-        (M, d), (n_samples, M, k) in the targets' own units (``GP.sample_y`` on the device, Philox stream ``seed``)."""
+        (M, d), (n_samples, M, k) in the targets' own units (``GP.sample_y`` on the device, Philox stream ``seed``).
+        ``path`` as :meth:`predict`'s: samples of that path itself, which pass near its observations."""
+        kw = self._path_kw(path)
         qn = self._queries(q)
-        s = self.gp.sample_y(qn, n_samples, random_state=seed, include_noise=include_noise)
+        s = self.gp.sample_y(qn, n_samples, random_state=seed, include_noise=include_noise, **kw)
         s = s.reshape(len(qn), -1, int(n_samples))                     # (M, k, n)
         return np.ascontiguousarray(s.transpose(2, 0, 1)) * self.y_std + self.y_mean
 
-    def predict_gradient(self, q, return_var=True):
+    def predict_gradient(self, q, return_var=True, path=None):
         """Gradient of the posterior with respect to the raw (un-normalised) inputs ``q`` (M,) or (M, d), in target units
         per input unit: ``dmean`` (M, d, k) and, with ``return_var``, ``dvar`` (M, d, k), the latent variance of each
-        partial derivative per target (``GP.predict_gradient`` on the device, rescaled by ``y_std[c] / in_span[j]``)."""
+        partial derivative per target (``GP.predict_gradient`` on the device, rescaled by ``y_std[c] / in_span[j]``).
+        ``path`` as :meth:`predict`'s: the gradient of that path itself."""
+        kw = self._path_kw(path)
         qn = self._queries(q)
         M, d = qn.shape
-        out = self.gp.predict_gradient(qn, return_var=return_var)
+        out = self.gp.predict_gradient(qn, return_var=return_var, **kw)
         scale = self.y_std[None, None, :] / np.asarray(self.in_span, dtype=np.float64)[None, :, None]   # (1, d, k)
         dmean = (out[0] if return_var else out).reshape(M, d, -1) * scale
         if not return_var:
             return dmean
         return dmean, out[1][:, :, None] * scale ** 2
 
-    def velocity(self, q, return_var=True):
+    def velocity(self, q, return_var=True, path=None):
         """Velocity of the modelled path at the raw time stamps ``q``: the ``"t"`` column of :meth:`predict_gradient`,
         (M, k) arrays, e.g. (dx/dt, dy/dt), and with ``return_var`` their latent variances (M, k).  ``q`` is (M,) when
-        ``t`` is the only input, else (M, d) as for :meth:`predict`."""
+        ``t`` is the only input, else (M, d) as for :meth:`predict`.  ``path`` as :meth:`predict`'s: that path's own
+        velocity."""
         if "t" not in self.inputs:
             raise ValueError(f"velocity() needs 't' among the model's inputs, have {self.inputs}")
         jt = self.inputs.index("t")
-        out = self.predict_gradient(q, return_var=return_var)
+        out = self.predict_gradient(q, return_var=return_var, path=path)
         if not return_var:
             return out[:, jt, :]
         return out[0][:, jt, :], out[1][:, jt, :]

@@ -402,6 +402,31 @@ int gpx_append_rows(gpx_handle* h, const void* Xnew, const void* ynew, const voi
  * GPX_F64 / GPX_F32 handles (GPX_E_UNSUPPORTED otherwise, as gpx_score_blocks); any fit, with or without path ids. */
 int gpx_forecast_blocks(gpx_handle* h, const void* Xb, const void* yo, int64_t G, int32_t Lo, int32_t Lp, double diag_add,
                         void* mean, void* cov, void* var, void* logp, int32_t mem_kind, int64_t* info);
+/* ---- predicting an observed path itself, f + g_p (additive to ABI v6) ------------------------------------
+ * The four posterior calls with one more argument: gq, M path ids (int32, in the memory kind of Xs, every entry >= -1), one
+ * per query point.  gq[i] == -1 asks for f(x_i), the plain call's meaning; gq[i] = p >= 0 asks for f(x_i) + g_p(x_i), the
+ * path p itself:
+ *   Cov[value(x*, p*), y_i]           = sf2 k(x*, x_i; l) + [p* == p_i and p* >= 0] sg2 k(x*, x_i; l_path)
+ *   Cov[value(x*, p*), value(x', p')] = sf2 k(x*, x'; l)  + [p* == p'  and p* >= 0] sg2 k(x*, x'; l_path)
+ * so the prior variance is sf2 + [p* >= 0] sg2, and that of d / d x_j is c sf2 / l_j^2 + [p* >= 0] c sg2 / l_path,j^2 (c the
+ * family's dpoly(0)).  An id no training row carries is a path nobody has seen: the mean of f, the (co)variance of f plus
+ * the prior sg2 k(., .; l_path).  Ids may be mixed freely in one call.  Outputs, batching, results on the device and every
+ * other argument are the plain call's; a call whose ids are all -1 returns the plain call's bits wherever it takes the
+ * plain call's route (gpx_predict_grad_paths without var and dvar takes the batch route, not the matrix-free product).  A
+ * point's results do not depend on M, its position or GPX_PRED_BATCH.  The fit and the results of plain calls afterwards
+ * are unchanged.
+ * Refusals, before anything is computed: GPX_E_ARG for gq == NULL, an id below -1, and what the plain call refuses;
+ * GPX_E_UNSUPPORTED ("path ids") when the current fit was not built with path ids (a plain, weighted or derivative fit, or
+ * sg2 == 0 or every id -1 at the fit); GPX_E_UNSUPPORTED on device groups, shards, handles with a communicator and
+ * GPX_MIXED handles; gpx_predict_grad_paths on GPX_KERNEL_MATERN12: GPX_E_UNSUPPORTED as gpx_predict_grad. */
+int gpx_predict_paths(gpx_handle* h, const void* Xs, const int32_t* gq, int64_t M, void* mean, void* var, int32_t mem_kind);
+int gpx_predict_cov_paths(gpx_handle* h, const void* Xs, const int32_t* gq, int64_t M, void* mean, void* cov,
+                          int32_t mem_kind);
+int gpx_sample_posterior_paths(gpx_handle* h, const void* Xs, const int32_t* gq, int64_t M, int64_t S, uint64_t seed,
+                               const void* z, double diag_add, double jitter, int32_t max_tries, void* out,
+                               double* jitter_used, int64_t* info, int32_t mem_kind);
+int gpx_predict_grad_paths(gpx_handle* h, const void* Xs, const int32_t* gq, int64_t M, void* mean, void* var, void* dmean,
+                           void* dvar, int32_t mem_kind);
 
 int gpx_get_alpha(gpx_handle* h, void* out /* (N,k) host */);
 /* Log marginal likelihood of the last fit and its gradient w.r.t. the LOG hyper-parameters —
@@ -511,6 +536,14 @@ int gpx_kernel_dl_matrix(int32_t kernel, const double* A, const int32_t* ka, int
 int gpx_kernel_path_matrix(int32_t kernel, int32_t dtype, const double* A, const int32_t* ga, int64_t na, const double* B,
                            const int32_t* gb, int64_t nb, int32_t d, const double* lengthscale, int32_t n_ls, double sf2,
                            const double* ls_path, int32_t n_ls_path, double sg2, double* K);
+/* kernel unit-test entry point (host buffers; additive to ABI v6): G (d, na, nb), G[j][a][b] = d / d A_aj of the entry
+ * K[a][b] of gpx_kernel_path_matrix — the d K* rows of gpx_predict_grad_paths, by its builder.  Arguments and GPX_E_ARG as
+ * gpx_kernel_path_matrix; GPX_KERNEL_MATERN12: GPX_E_UNSUPPORTED (not differentiable), as gpx_kernel_deriv_matrix.  G is
+ * written only on success. */
+int gpx_kernel_path_grad_matrix(int32_t kernel, int32_t dtype, const double* A, const int32_t* ga, int64_t na,
+                                const double* B, const int32_t* gb, int64_t nb, int32_t d, const double* lengthscale,
+                                int32_t n_ls, double sf2, const double* ls_path, int32_t n_ls_path, double sg2,
+                                double* G /* (d, na, nb) */);
 /* K (na, nb) host, fp64 = the covariance between an observation of kind ka[a] at A_a and one of kind kb[b] at B_b (kinds as
  * in gpx_set_observation_kinds; ka / kb == NULL: all values), by the fit's rectangular builder with kinds on rows and
  * columns — the left part of rows appended by gpx_append_rows; no diagonal term.  n_ls: 1 or d.  dtype GPX_F64 or GPX_F32
