@@ -96,6 +96,7 @@ SIGNATURES = {
                                               C.c_int32, C.c_double, _PD]),
     "gpx_append_weighted": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int32, C.POINTER(C.c_int64)]),
     "gpx_append_rows": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int64, C.c_int32, C.POINTER(C.c_int64)]),
+    "gpx_remove_rows": (C.c_int, [_P, C.c_int64, C.c_int64, C.POINTER(C.c_int64)]),
     "gpx_kernel_mixed_matrix": (C.c_int, [C.c_int32, C.c_int32, _PD, C.POINTER(C.c_int32), C.c_int64, _PD,
                                           C.POINTER(C.c_int32), C.c_int64, C.c_int32, _PD, C.c_int32, C.c_double, _PD]),
     "gpx_score_blocks_weighted": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int32, C.c_double, _P, _P, _P, C.c_int32,

@@ -126,6 +126,7 @@ struct gpx_handle {
     // block scoring (gpx_score_blocks, gpx_forecast_blocks): targets, per-slice Gram partials, batch mean^T, results + the bad-block word
     DevBuf SY, SPart, SMT, SOut;
     DevBuf SW;  // gpx_score_blocks_weighted: the query points' weights
+    DevBuf UW, UQ;  // gpx_remove_rows: per pass in flight (two) the carry ((N + 64) x UPD_W) and the panel's orthogonal factor (2 UPD_W square)
   } scr;
   // row-block shard (world > 1)
   Comm* comm = nullptr;  // RCCL, in-process or host-callback transport (gpx_shard.inc)
@@ -1652,6 +1653,179 @@ int append_impl(gpx_handle* h, const void* Xnew, const void* ynew, const void* w
   tm.handover_flags = chain_flag_enabled(h) ? 1.0 : 0.0;
   tm.handover_retries = (double)h->flag_retries;
   h->fitted = true;
+  return GPX_OK;
+}
+
+// ---- gpx_remove_rows: fewer observations without a new factorisation of the others -------------------
+// One pass takes rows [a, a + m) (m <= UPD_W) out of a factor of N rows (csrc/gpx_update.hip has the algebra).  Nothing is
+// evaluated: the factor, z^T and the carry are all the pass reads.  The bordered rows stay at `zT` (their place for the
+// N0 points the call started with) through every pass; remove_impl moves them once at the end.
+//
+// Who may write where (the overwrite hazard).  Panel j of a pass reads columns [b + j w, b + (j + 1) w) of L33 and of z^T
+// (b = a + m, w = UPD_W) and its new columns belong m to the left: [a + j w, a + (j + 1) w), rows m up.
+//   - Later launches read columns >= b + (j + 1) w only: to the right of everything panel j writes, for every m >= 0.
+//   - Inside panel j's own launch the written columns meet the read ones iff m < w, and then a band's destination rows
+//     are the unread source of the band above it.  So for m < w the strip writes into the panel buffer (h->P) and a
+//     second launch moves the panel into place: by then panel j has been consumed.  For m == w the two column ranges are
+//     disjoint — the strip writes columns [p0 - w, p0), which hold panel j - 1's source (consumed by the launch before) or
+//     the removed columns themselves — and the strip writes the factor directly.
+//   - The carry is a buffer of its own; a workgroup overwrites only the carry rows it has read itself.
+//   - L31 (columns [0, a), no arithmetic) moves m rows up through the panel buffer, a slab of rows at a time: copy out,
+//     then copy in — two launches in stream order, so a slab's destination may overlap any source row.
+// Two full passes (m == UPD_W) in a row run as a two-stage pipeline: the second pass, on st2, is one panel behind the
+// first.  Its panel j reads columns [a1 + j w, a1 + (j + 1) w) — exactly what panel j of the first pass has written
+// (lead->done[j] is recorded behind that strip) — and writes the w columns left of them; panels j' > j of the first pass
+// read and write columns from a1 + (j + 1) w on.  The second pass starts (carry, L31) once the first has moved its L31
+// (lead->moved), which holds the second's removed columns and its own L31; each pass has a carry and a Q of its own
+// (`slot`), and only the L31 moves touch the panel buffer (full passes write the factor directly).
+struct PassLink {
+  hipEvent_t moved = nullptr;
+  std::vector<hipEvent_t> done;
+};
+
+template <typename T>
+int remove_pass(gpx_handle* h, int64_t a, int64_t m, int64_t N, T* zT, int* dInfo, hipStream_t st, int slot,
+                PassLink* record, const PassLink* follow) {
+  const int64_t ld = h->ld, b = a + m, n3 = N - b;
+  if (n3 <= 0) return GPX_OK;  // the tail: a truncation
+  T* dK = (T*)h->K.p;
+  T* W = (T*)h->scr.UW.p + (size_t)slot * (h->scr.UW.cap / sizeof(T) / 2);
+  T* Q = (T*)h->scr.UQ.p + (size_t)slot * 4 * UPD_W * UPD_W;
+  T* P = (T*)h->P.p;
+  const int64_t pcap = (int64_t)(h->P.cap / sizeof(T));
+  if (follow) HIPCHK(h, hipStreamWaitEvent(st, follow->moved, 0));
+  launch_upd_carry_init<T>(dK, ld, a, (int)m, n3, zT, W, st);
+  if (a > 0) {
+    const int64_t R = std::max<int64_t>(1, pcap / a);
+    for (int64_t r0 = 0; r0 < n3; r0 += R) {
+      const int64_t rows = std::min(R, n3 - r0);
+      launch_upd_copy<T>(P, a, dK + (b + r0) * ld, ld, rows, a, st);
+      launch_upd_copy<T>(dK + (a + r0) * ld, ld, P, a, rows, a, st);
+    }
+  }
+  int rc;
+  if (record && (rc = record_event(h, st, "gpx_remove_rows", &record->moved))) return rc;
+  const bool direct = m == UPD_W;
+  for (int64_t j0 = 0; j0 < n3; j0 += UPD_W) {
+    const int64_t p0 = b + j0, nrows = n3 - j0;
+    const int nv = (int)std::min<int64_t>(UPD_W, nrows);
+    T* Wp = W + j0 * UPD_W;
+    T* Wz = W + n3 * UPD_W;
+    T* dstL = dK + (p0 - m) * ld + (p0 - m);
+    T* dstZ = zT + (p0 - m);
+    if (follow) HIPCHK(h, hipStreamWaitEvent(st, follow->done[(size_t)(j0 / UPD_W)], 0));
+    launch_upd_small<T>(dK, ld, p0, nv, Wp, Q, a + j0, dInfo, st);
+    if (direct) {
+      launch_upd_strip<T>(dK, ld, p0, nrows, nv, zT, Wp, Wz, Q, dstL, ld, dstZ, ld, st);
+    } else {
+      launch_upd_strip<T>(dK, ld, p0, nrows, nv, zT, Wp, Wz, Q, P, UPD_W, P + nrows * UPD_W, UPD_W, st);
+      launch_upd_unstage<T>(P, nrows, nv, dstL, ld, dstZ, ld, st);
+    }
+    if (record) {
+      hipEvent_t e;
+      if ((rc = record_event(h, st, "gpx_remove_rows", &e))) return rc;
+      record->done.push_back(e);
+    }
+  }
+  return GPX_OK;
+}
+
+// `bytes` bytes from byte offset `from` of buf to offset `to` < from (the ranges may overlap: through the panel buffer)
+int shift_down(gpx_handle* h, void* buf, size_t to, size_t from, size_t bytes) {
+  if (!bytes) return GPX_OK;
+  HIPCHK(h, hipMemcpyAsync(h->P.p, (const char*)buf + from, bytes, hipMemcpyDeviceToDevice, h->st));
+  HIPCHK(h, hipMemcpyAsync((char*)buf + to, h->P.p, bytes, hipMemcpyDeviceToDevice, h->st));
+  return GPX_OK;
+}
+
+template <typename T>
+int remove_impl(gpx_handle* h, int64_t start, int64_t count, int64_t* info) {
+  const int64_t N0 = h->N, Npad0 = h->Npad, ld = h->ld, N1 = N0 - count, Npad1 = round_up(N1, TILE);
+  const int64_t stop = start + count, tail = N0 - stop;
+  const int d = h->d, k = h->k;
+  gpx_timings& tm = h->tm;
+  tm.h2d = tm.kbuild = tm.chol = tm.solve = tm.logdet = tm.fit_total = 0;
+  tm.chol_diag = tm.chol_trsm = tm.chol_strip = tm.chol_syrk = tm.syrk_flops = tm.comm = 0;
+  tm.syrk_launches = 0;
+  tm.kbuild_bytes = 0;
+  int rc;
+  if ((rc = ensure(h, h->scr.UW, (size_t)2 * (N0 + 64) * UPD_W * sizeof(T)))) return rc;  // (the fit is untouched so far)
+  if ((rc = ensure(h, h->scr.UQ, (size_t)2 * 4 * UPD_W * UPD_W * sizeof(T)))) return rc;  // (two passes in flight)
+  T* dK = (T*)h->K.p;
+  T* zT = (T*)h->zT;
+  int* dInfo = (int*)h->info.p;
+  h->fitted = false;  // until the update has gone through: it cannot be taken back in place
+  h->alphaT = nullptr;
+  h->alpha_ready = false;
+  h->nbw = 0;  // the explicit inverses of the panel-wide diagonal blocks belong to the old rows' grid
+  {
+    PhaseScope total(h, &tm.fit_total);
+    {
+      PhaseScope ps(h, &tm.chol);
+      const int init = INT_MAX;
+      HIPCHK(h, hipMemcpyAsync(dInfo, &init, sizeof(int), hipMemcpyHostToDevice, h->st));
+      int64_t N = N0;
+      for (int64_t hi = stop; hi > start;) {  // from the highest rows down, one update width at a time
+        const int64_t lo = std::max(start, hi - UPD_W);
+        if (hi - start >= 2 * UPD_W && N > hi && h->st2) {  // two full passes with rows below them: the pipeline
+          PassLink link;
+          if ((rc = remove_pass<T>(h, lo, UPD_W, N, zT, dInfo, h->st, 0, &link, nullptr))) return rc;
+          if ((rc = remove_pass<T>(h, lo - UPD_W, UPD_W, N - UPD_W, zT, dInfo, h->st2, 1, nullptr, &link))) return rc;
+          if ((rc = stream_waits(h, h->st, h->st2, "gpx_remove_rows"))) return rc;
+          N -= 2 * UPD_W;
+          hi = lo - UPD_W;
+          continue;
+        }
+        if ((rc = remove_pass<T>(h, lo, hi - lo, N, zT, dInfo, h->st, 0, nullptr, nullptr))) return rc;
+        N -= hi - lo;
+        hi = lo;
+      }
+      // what a fit of N1 points leaves beyond them, the bordered rows at their place below Npad1 rows
+      launch_upd_pad<T>(dK, ld, N1, Npad1, zT, Npad0, h->st);
+      if (Npad1 != Npad0) {
+        T* z1 = dK + Npad1 * ld;
+        HIPCHK(h, hipMemsetAsync(z1, 0, (size_t)RHS_ROWS * ld * sizeof(T), h->st));
+        launch_upd_copy<T>(z1, ld, zT, ld, RHS_ROWS, N1, h->st);
+        h->zT = z1;
+      }
+      launch_upd_trinv<T>(dK, ld, start / KB, Npad1 / KB, (T*)h->Winv.p, h->st);
+      // the stored rows follow: points, scaled points (zero beyond N1), targets, weights, kinds / ids (-1 beyond N1)
+      // and their finished diagonal terms
+      if ((rc = shift_down(h, h->X.p, (size_t)start * d * sizeof(T), (size_t)stop * d * sizeof(T), (size_t)tail * d * sizeof(T)))) return rc;
+      if ((rc = shift_down(h, h->Y.p, (size_t)start * k * sizeof(T), (size_t)stop * k * sizeof(T), (size_t)tail * k * sizeof(T)))) return rc;
+      if ((rc = shift_down(h, h->Xs.p, (size_t)start * d * sizeof(T), (size_t)stop * d * sizeof(T), (size_t)tail * d * sizeof(T)))) return rc;
+      HIPCHK(h, hipMemsetAsync((T*)h->Xs.p + N1 * d, 0, (size_t)(Npad0 - N1) * d * sizeof(T), h->st));
+      if (h->weighted &&
+          (rc = shift_down(h, h->Wfit.p, (size_t)start * sizeof(T), (size_t)stop * sizeof(T), (size_t)tail * sizeof(T))))
+        return rc;
+      for (int side = 0; side < 2; ++side) {
+        if (!(side ? h->grouped : h->kinded)) continue;
+        DevBuf& ids = side ? h->Gfit : h->Kfit;
+        DevBuf& dg = side ? h->Gdiag : h->Dfit;
+        if ((rc = shift_down(h, ids.p, (size_t)start * 4, (size_t)stop * 4, (size_t)tail * 4))) return rc;
+        HIPCHK(h, hipMemsetAsync((int32_t*)ids.p + N1, 0xFF, (size_t)count * 4, h->st));
+        if ((rc = shift_down(h, dg.p, (size_t)start * sizeof(T), (size_t)stop * sizeof(T), (size_t)tail * sizeof(T)))) return rc;
+      }
+    }
+    {
+      PhaseScope ps(h, &tm.logdet);
+      launch_logdet<T>(dK, ld, Npad1, (double*)h->scalars.p, h->st);
+    }
+  }
+  int hinfo = 0;
+  HIPCHK(h, hipMemcpyAsync(&hinfo, dInfo, sizeof(int), hipMemcpyDeviceToHost, h->st));
+  HIPCHK(h, hipMemcpyAsync(&h->logdet, h->scalars.p, sizeof(double), hipMemcpyDeviceToHost, h->st));
+  if ((rc = finish_call(h))) return rc;
+  if (h->kinded && (int64_t)h->kinds_fit.size() == N0) {
+    h->kinds_fit.erase(h->kinds_fit.begin() + start, h->kinds_fit.begin() + stop);
+    h->has_deriv = false;
+    for (int32_t v : h->kinds_fit) h->has_deriv |= v >= 0;
+  }
+  if (h->grouped && (int64_t)h->groups_fit.size() == N0) h->groups_fit.erase(h->groups_fit.begin() + start, h->groups_fit.begin() + stop);
+  h->N = N1;
+  h->Npad = Npad1;
+  *info = (hinfo == INT_MAX) ? 0 : (int64_t)hinfo;
+  h->fitted = (*info == 0);
   return GPX_OK;
 }
 
@@ -3261,6 +3435,22 @@ GPX_CATCH_ALL
 int gpx_append_weighted(gpx_handle* h, const void* Xnew, const void* ynew, const void* wnew, int64_t m, int32_t mem_kind,
                         int64_t* info) try {
   return append_entry(h, Xnew, ynew, wnew, m, mem_kind, info);
+}
+GPX_CATCH_ALL
+
+int gpx_remove_rows(gpx_handle* h, int64_t start, int64_t count, int64_t* info) try {
+  if (!h) return GPX_E_ARG;
+  if (!info) return fail(h, GPX_E_ARG, "gpx_remove_rows: bad argument");
+  int rc;
+  if ((rc = posterior_refused(h, "gpx_remove_rows"))) return rc;
+  if (!h->fitted) return fail(h, GPX_E_ARG, "gpx_remove_rows: handle has no successful fit");
+  if (start < 0 || count < 0 || start > h->N || count > h->N - start)
+    return fail(h, GPX_E_ARG, "gpx_remove_rows: rows [start, start + count) must lie inside the fit");
+  if (count >= h->N) return fail(h, GPX_E_ARG, "gpx_remove_rows: a fit keeps at least one point");
+  *info = 0;
+  if (count == 0) return GPX_OK;
+  if ((rc = begin_call(h))) return rc;
+  return BY_DTYPE(h, remove_impl, h, start, count, info);
 }
 GPX_CATCH_ALL
 

@@ -423,6 +423,37 @@ void launch_block_forecast(int kernel, const double* part, int64_t nblk, int Lo,
                            const T* yo, const T* mean, int k, double sf2, double sg2, const double* q, double diag_add,
                            T* fmean, T* fcov, T* fvar, T* flogp, int64_t g0, int* bad, hipStream_t st);
 
+// ---- removal of observations (gpx_update.hip) -----------------------------------
+constexpr int UPD_W = 64;  // panel width of the rank-m update of the trailing factor = most columns m one pass removes
+// carry W ((n3 + 64) x UPD_W, compact): row i < n3 = columns [a, a + m) of row a + m + i of L, rows n3 + r those columns of
+// the 64 bordered rows zT; zero from column m on
+template <typename T>
+void launch_upd_carry_init(const T* L, int64_t ld, int64_t a, int m, int64_t n3, const T* zT, T* W, hipStream_t st);
+// the small step of the panel whose diagonal block sits at (p0, p0) of L (nv <= UPD_W valid rows) with carry rows Wj:
+// Q (2 UPD_W square, row-major, formed in fp64 and rounded once).  A pivot that is not > 0: atomicMin(info, gidx0 + its
+// 1-based place), gidx0 the 0-based index of the panel's first row in the remaining data.
+template <typename T>
+void launch_upd_small(const T* L, int64_t ld, int64_t p0, int nv, const T* Wj, T* Q, int64_t gidx0, int* info,
+                      hipStream_t st);
+// [ panel' | carry' ] = [ panel | carry ] Q over the nrows rows of L from p0 down (carry rows Wp) and the 64 bordered rows zT
+// (carry rows Wz): panel' to outL (ldo) / outZ (ldz) under the lower-triangle / nv masks, carry' over the carry
+template <typename T>
+void launch_upd_strip(const T* L, int64_t ld, int64_t p0, int64_t nrows, int nv, const T* zT, T* Wp, T* Wz, const T* Q,
+                      T* outL, int64_t ldo, T* outZ, int64_t ldz, hipStream_t st);
+// a staged panel ((nrows + 64) x UPD_W, compact) into its place under the same masks
+template <typename T>
+void launch_upd_unstage(const T* P, int64_t nrows, int nv, T* dstL, int64_t ldl, T* dstZ, int64_t ldz, hipStream_t st);
+// dst (rows x cols, ldd) = src (lds): any alignment; the two may not overlap
+template <typename T>
+void launch_upd_copy(T* dst, int64_t ldd, const T* src, int64_t lds, int64_t rows, int64_t cols, hipStream_t st);
+// what a fit leaves beyond n points: rows [n, npad) of A zero up to column npad with a one on the diagonal, columns
+// [n, nz) of the 64 rows of zT zero
+template <typename T>
+void launch_upd_pad(T* A, int64_t ld, int64_t n, int64_t npad, T* zT, int64_t nz, hipStream_t st);
+// Winv[q] = inverse of the 64 x 64 diagonal block q of L for q0 <= q < q1 (launch_potf2_64's layout)
+template <typename T>
+void launch_upd_trinv(const T* L, int64_t ld, int64_t q0, int64_t q1, T* Winv, hipStream_t st);
+
 // ---- row-block-cyclic shard helpers (gpx_misc.hip; T = double | float) ------------------------
 // A[i][i] = i < nvalid ? A[i][i] + add : 1   for i < n (diagonal of one local row block)
 template <typename T>

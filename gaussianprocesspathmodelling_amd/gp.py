@@ -554,6 +554,82 @@ class GP:
         self._check(self._lib.gpx_reserve(self._h, int(n)))
         return self
 
+    def remove(self, start=None, stop=None, path_ids=None):
+        """Take observations out of the fitted model without factorising the others again (``gpx_remove_rows``):
+        afterwards the model is, to rounding, what ``fit`` of the remaining rows (in their order, with their own noise
+        weights, kinds and path ids) with the same hyper-parameters and the jitter the fit needed would be.
+
+        ``remove(start, stop)`` takes rows ``[start, stop)``; ``remove(indices)`` any integer index array or sequence
+        (sorted, deduplicated and split into runs, which are removed from the highest down); ``remove(path_ids=[3, 7])``,
+        on a fit with path ids, every row of those paths.  A removed path id is afterwards an id the fit has never seen.
+        No covariance is evaluated, so every kind of fit is served (plain, weighted, with ``derivatives=``, with
+        ``path_ids=``); ``noise_weights_``, ``observation_kinds_``, ``path_ids_``, ``alpha_`` and ``log_det_`` follow.
+        The factor is compacted inside its buffer (a later :meth:`update` reuses the room).  Rows at the end cost nothing;
+        the cost grows with the number of rows BELOW the removed ones, and taking out more than roughly N / 12 rows at
+        the front costs as much as a new :meth:`fit`.  float64 / float32 models on one device.  Returns ``self``.
+
+        ``ValueError`` before anything is touched: indices that are not integers or out of range, removing every row,
+        ``path_ids=`` on a fit without path ids, both forms at once; ``RuntimeError`` before a fit."""
+        if not self._fitted:
+            raise RuntimeError("remove() before a successful fit()")
+        N = self._N
+        if path_ids is not None:
+            if start is not None or stop is not None:
+                raise ValueError("give rows (start, stop / indices) or path_ids=, not both")
+            if not self._groups_set:
+                raise ValueError("path_ids given, but the model was fitted without path ids")
+            if _is_torch(path_ids):
+                path_ids = path_ids.detach().cpu().numpy()
+            want = np.atleast_1d(np.asarray(path_ids))
+            if want.ndim != 1 or want.dtype.kind not in "iu" or np.any(want < 0):
+                raise ValueError("path_ids must be integers >= 0")
+            idx = np.flatnonzero(np.isin(self.path_ids_, want))
+        elif start is None:
+            raise ValueError("remove() needs rows (start, stop / indices) or path_ids=")
+        elif stop is not None:
+            for v in (start, stop):
+                if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                    raise ValueError("start and stop must be integers")
+            if not 0 <= start <= stop <= N:
+                raise ValueError(f"rows [{start}, {stop}) do not lie inside the {N} fitted rows")
+            idx = np.arange(int(start), int(stop))
+        else:
+            if _is_torch(start):
+                start = start.detach().cpu().numpy()
+            idx = np.atleast_1d(np.asarray(start))
+            if idx.ndim != 1 or (idx.size and idx.dtype.kind not in "iu"):
+                raise ValueError("indices must be a 1-D array of integers")
+            idx = idx.astype(np.int64)
+            if idx.size and (idx.min() < 0 or idx.max() >= N):
+                raise ValueError(f"indices must lie in [0, {N})")
+            idx = np.unique(idx)
+        if idx.size >= N:
+            raise ValueError("remove() cannot take out every row: a model keeps at least one observation")
+        if idx.size == 0:
+            return self
+        # runs of consecutive indices, highest first: the rows below a run keep their numbers while it is removed
+        cuts = np.flatnonzero(np.diff(idx) != 1) + 1
+        runs = [(int(r[0]), int(r.size)) for r in np.split(idx, cuts)]
+        for first, count in reversed(runs):
+            info = C.c_int64(0)
+            self._alpha = None
+            try:
+                self._check(self._lib.gpx_remove_rows(self._h, first, count, C.byref(info)))
+            except _abi.GpxError as e:
+                # a refusal comes before anything is touched; any other failure leaves the handle without a fit
+                self._fitted = e.code in (_abi.E_ARG, _abi.E_UNSUPPORTED)
+                raise
+            if info.value != 0:
+                self._fitted = False
+                raise np.linalg.LinAlgError(
+                    f"non-positive pivot {info.value} while removing rows (non-finite numbers in the factor?): the "
+                    f"model is left without a fit; fit the remaining data again")
+            self._N -= count
+        ld = C.c_double(0.0)
+        self._check(self._lib.gpx_logdet(self._h, C.byref(ld)))
+        self.log_det_ = float(ld.value)
+        return self
+
     def fit_predict(self, X, y, Xs, include_noise=False, noise_weights=None, derivatives=None, derivative_noise=0.0,
                     path_ids=None, path_variance=0.0, path_lengthscale=None):
         """``fit(X, y)`` and ``predict(Xs)`` (mean and variance) as ONE factorisation pass: the cross-kernel rows

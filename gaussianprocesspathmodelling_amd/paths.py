@@ -254,8 +254,13 @@ class PathModel:
     Which method adds paths: :meth:`add_paths` on plain and step-noise models, :meth:`append_paths` on every model."""
 
     def __init__(self, gp, keys, in_lo, in_span, y_mean, y_std, inputs, targets, step_weights=None, has_velocities=False,
-                 within_path=False):
+                 within_path=False, row_counts=None):
         self.gp, self.keys = gp, list(keys)
+        # what remove_paths needs: every key's path id (within_path: its index in keys until a path has been removed, and
+        # never reused after) and its number of value rows (row_counts: one per key, in order; None: not recorded)
+        self._ids = {q: i for i, q in enumerate(self.keys)}
+        self._next_id = len(self.keys)
+        self._rows = None if row_counts is None else {q: int(n) for q, n in zip(self.keys, row_counts)}
         self.in_lo, self.in_span, self.y_mean, self.y_std = in_lo, in_span, y_mean, y_std
         self.inputs, self.targets = tuple(inputs), tuple(targets)
         self.step_weights = None if step_weights is None else np.asarray(step_weights, dtype=np.float64)
@@ -284,16 +289,16 @@ class PathModel:
 
     def _path_kw(self, path):
         """``path`` (None, or a key of ``self.keys``) -> the ``path_ids`` keyword of the GP's methods: a path's id is its
-        index in ``keys`` (``fit_path_models`` and :meth:`append_paths` number them so)"""
+        index in ``keys`` (``fit_path_models`` and :meth:`append_paths` number them so) until :meth:`remove_paths` has
+        taken a path out; from then on new paths get ids no path has had"""
         if path is None:
             return {}
         if not self.within_path:
             raise ValueError("path= needs a within_path model (fit_path_models(within_path=True)): only there has a path a "
                              "deviation of its own")
-        try:
-            return {"path_ids": self.keys.index(path)}
-        except ValueError:
-            raise KeyError(path) from None
+        if path not in self._ids:
+            raise KeyError(path)
+        return {"path_ids": self._ids[path]}
 
     def predict(self, q, return_var=True, include_noise=False, return_cov=False, path=None):
         """Posterior at raw (un-normalised) inputs ``q`` (M,) or (M, d): mean (M, k) in the
@@ -368,7 +373,7 @@ class PathModel:
     def append_paths(self, trajs, keys, velocities=None):
         """:meth:`add_paths` for every model (``GP.update`` with the rows' path ids or derivative rows where the model has
         them).  On a ``within_path`` model path i of ``keys`` gets the id ``len(self.keys) + i``, which continues the
-        numbering of :func:`fit_path_models`.  On a model with velocities, ``velocities`` = {key: (L, k)} in raw units
+        numbering of :func:`fit_path_models` (after a :meth:`remove_paths`: the next id no path has had).  On a model with velocities, ``velocities`` = {key: (L, k)} in raw units
         (target per unit of ``"t"``) become derivative rows under the model's normalisation, as at the fit; a key without
         an entry appends its values only.  ``velocities`` on a model without them: ``ValueError``.  Extends ``keys``;
         returns ``self``."""
@@ -384,7 +389,7 @@ class PathModel:
         Yn = np.ascontiguousarray((Y - self.y_mean) / self.y_std)
         kw = {}
         if self.within_path:
-            first = len(self.keys)
+            first = self._next_id
             kw["path_ids"] = np.concatenate([np.full(len(trajs.pathdict[q]), first + i, dtype=np.int32)
                                              for i, q in enumerate(keys)])
         if self.has_velocities:
@@ -404,7 +409,54 @@ class PathModel:
             yd = np.concatenate(vals) if vals else np.zeros((0, len(self.targets)))
             kw["derivatives"] = (np.ascontiguousarray(Xn[at_rows]), jt, np.ascontiguousarray(yd))
         self.gp.update(Xn, Yn, noise_weights=self._tiled_weights(len(Xn), "append_paths"), **kw)
+        for i, q in enumerate(keys):
+            self._ids[q] = self._next_id + i
+            if self._rows is not None:
+                self._rows[q] = len(trajs.pathdict[q])
+        self._next_id += len(keys)
         self.keys.extend(keys)
+        return self
+
+    def remove_paths(self, keys):
+        """Take the paths ``keys`` out of this cluster's model (``GP.remove``: the factor of the other paths is updated, not
+        computed again) — a path that went stale, was assigned to another cluster, or was a bad recording.  The result is
+        the GP of the remaining paths under the normalisation fixed at the first fit.  A ``within_path`` model finds the
+        rows by the path's id, and that id is never given to a later path; other models by the row counts recorded at the
+        fit and at every append.  ``KeyError`` for a key the model does not hold (nothing is removed then);
+        ``ValueError`` on a model with velocities, whose derivative rows are interleaved by :meth:`append_paths` and not
+        recorded per key (``gp.remove(indices)`` remains available there), and when no path would be left.  Shortens
+        ``keys``; returns ``self``."""
+        keys = list(dict.fromkeys(keys))
+        if self.has_velocities:
+            raise ValueError("remove_paths: the model is conditioned on velocities, whose derivative rows are interleaved "
+                             "with the value rows by append_paths and are not recorded per key: remove rows with "
+                             "gp.remove(indices)")
+        for q in keys:
+            if q not in self._ids:
+                raise KeyError(q)
+        if not keys:
+            return self
+        if len(keys) >= len(self.keys):
+            raise ValueError("remove_paths: a model keeps at least one path")
+        if self.within_path:
+            self.gp.remove(path_ids=[self._ids[q] for q in keys])
+        else:
+            if self._rows is None:
+                raise ValueError("remove_paths: the model does not know its paths' row counts (it was not built by "
+                                 "fit_path_models)")
+            gone, at, idx = set(keys), 0, []
+            for q in self.keys:
+                n = self._rows[q]
+                if q in gone:
+                    idx.append(np.arange(at, at + n))
+                at += n
+            self.gp.remove(np.concatenate(idx))
+        for q in keys:
+            del self._ids[q]
+            if self._rows is not None:
+                del self._rows[q]
+        gone = set(keys)
+        self.keys = [q for q in self.keys if q not in gone]
         return self
 
     def log_likelihood(self, paths_txy, include_noise=True):
@@ -592,7 +644,7 @@ def fit_path_models(trajs, clusters, inputs=("t",), targets=("x", "y"), devices=
             gp.close()
             raise
         return cid, PathModel(gp, keys, lo, span, mu, sd, inputs, targets, step_weights=sw, has_velocities=der is not None,
-                              within_path=within_path)
+                              within_path=within_path, row_counts=[len(trajs.pathdict[q]) for q in keys])
 
     by_dev = [[] for _ in devs]                    # one worker per device, its clusters in order
     for i, (cid, keys) in enumerate(jobs):

@@ -389,6 +389,33 @@ int gpx_get_path_groups(gpx_handle* h, int32_t* out /* (N) host */);
  * and finished diagonal terms; the getters return the old N entries. */
 int gpx_append_rows(gpx_handle* h, const void* Xnew, const void* ynew, const void* wnew, const int32_t* kind_new,
                     const int32_t* group_new, int64_t m, int32_t mem_kind, int64_t* info);
+/* ---- removing observations (additive to ABI v6) -------------------------------------------------------------------------
+ * gpx_remove_rows: rows [start, start + count) of the fitted data leave the handle without a new factorisation of the
+ * others.  Afterwards the handle is, to rounding, what gpx_fit of the remaining N - count rows (in their order, with the
+ * same hyper-parameters, the fit's jitter and their own weights, kinds and path ids) would have left: every other call
+ * (gpx_predict, _cov, _grad and their _paths forms, gpx_sample_posterior, gpx_score_blocks, gpx_forecast_blocks,
+ * gpx_get_alpha, gpx_logdet, the three gpx_lml_grad*, a further append or remove) works on N - count points.
+ * Nothing of the covariance is evaluated, so every kind of fit is served alike (plain, weighted, with observation kinds,
+ * with path ids).  With a = start and b = start + count, rows [0, a) of L and the rows' columns [0, a) stay as they are
+ * and the trailing factor takes the positive update L33' L33'^T = L33 L33^T + L32 L32^T, at most 64 removed columns per
+ * pass (a longer range goes in chunks from its highest rows down), as orthogonal transformations of [L33 | L32] in column
+ * panels of 64; z^T = (L^-1 y)^T rides through them as bordered rows.  About n3^2 (w + 2 m + m^2 / w) flops per pass of m
+ * columns over n3 = N - b trailing rows (w = 64); removing the last rows is a truncation, the first rows the worst case:
+ * taking out more than about N / 12 of the first rows costs as much as gpx_fit.
+ * The factor is compacted inside its buffer: pointer, ld and capacity (gpx_factor_info) are unchanged and a later append
+ * reuses the room.  The stored points, targets, weights, kinds, ids and diagonal terms follow; has_deriv is taken again
+ * from the remaining kinds; the 64-block inverses are taken again from block start / 64 on; the explicit inverses of the
+ * panel-wide diagonal blocks are dropped (solves then go through the 64-block inverses) and alpha is solved on demand.
+ * count == 0: GPX_OK, nothing changes.  start < 0, count < 0, start + count > N or count == N (a fit keeps one point):
+ * GPX_E_ARG, the fit stays valid.
+ * *info: 0 on success.  The update is backward stable and in exact arithmetic meets no non-positive pivot; if one appears
+ * all the same (non-finite numbers in the factor), *info is its 1-based index in the remaining data, the call returns 0
+ * and the handle is left WITHOUT a fit (every later call but gpx_fit: GPX_E_ARG): the update works in place and cannot
+ * be taken back.
+ * Timings: the fit fields (chol, logdet, fit_total), zeroed at the start of the call.
+ * Single-device GPX_F64 / GPX_F32 handles after a successful fit (else GPX_E_ARG); GPX_MIXED handles, shards and device
+ * groups return GPX_E_UNSUPPORTED (nothing computed, the fit stays valid). */
+int gpx_remove_rows(gpx_handle* h, int64_t start, int64_t count, int64_t* info);
 /* Forecast of partly observed new paths.  Xb (G (Lo + Lp), d): per block its Lo observed points, then its Lp points to
  * forecast (1 <= Lo, 1 <= Lp, Lo + Lp <= 64); yo (G Lo, k) the observed targets; diag_add >= 0 goes on the diagonal of the
  * observed part only (the observation noise).  The block prior is posterior(f) [+ sg2 k(., .; l_path) on a fit with path
