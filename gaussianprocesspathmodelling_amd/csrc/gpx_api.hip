@@ -214,6 +214,36 @@ int fail(gpx_handle* h, int code, const char* msg) {
   return code;
 }
 
+// the same with the message "<fn>: <what>", fn the exported name of the call
+int fail(gpx_handle* h, int code, const char* fn, const char* what) {
+  return fail(h, code, (std::string(fn) + ": " + what).c_str());
+}
+
+bool bad_mem_kind(int32_t mem_kind) { return !(mem_kind == GPX_MEM_HOST || mem_kind == GPX_MEM_DEVICE); }
+
+// n int32 side values (kinds, path ids) from host or device memory into `out` (on the handle's device unless it fronts a group)
+int fetch_ids(gpx_handle* h, const int32_t* src, int64_t n, int32_t mem_kind, std::vector<int32_t>& out) {
+  out.resize((size_t)n);
+  if (mem_kind == GPX_MEM_HOST) {
+    std::copy(src, src + n, out.begin());
+    return GPX_OK;
+  }
+  if (!h->group) HIPCHK(h, hipSetDevice(h->cfg.device));
+  HIPCHK(h, hipMemcpy(out.data(), src, (size_t)n * sizeof(int32_t), hipMemcpyDefault));
+  return GPX_OK;
+}
+
+// the first of n ids below -1 (the only values no id or kind may take), or n
+int64_t first_below_minus_one(const int32_t* ids, int64_t n) {
+  return std::find_if(ids, ids + n, [](int32_t v) { return v < -1; }) - ids;
+}
+
+// a variance a caller may set (sg2, sn2_deriv): finite and >= 0; n path lengthscales: each finite and > 0
+bool variance_ok(double v) { return v >= 0.0 && std::isfinite(v); }
+bool path_ls_ok(const double* ls_path, int32_t n) {
+  return std::all_of(ls_path, ls_path + n, [](double l) { return l > 0.0 && std::isfinite(l); });
+}
+
 // the refusal of gpx_predict_grad / gpx_kernel_deriv_matrix: k = sf2 e^-r has a kink at r = 0
 #define MATERN12_NO_GRAD "Matern-1/2 is not differentiable (its sample paths have no derivative)"
 
@@ -2983,13 +3013,13 @@ namespace {
 // the argument checks of gpx_fit and gpx_fit_predict (with_queries: Xq, mean and M as well); `fn` heads the messages
 int check_fit_args(gpx_handle* h, const char* fn, bool with_queries, bool any_null, int64_t N, int64_t M, int32_t d, int32_t k,
                    const double* lengthscale, int32_t n_ls, double sf2, double sn2, double jitter, int32_t mem_kind) {
-  auto bad = [&](const char* what) { return fail(h, GPX_E_ARG, (std::string(fn) + ": " + what).c_str()); };
+  auto bad = [&](const char* what) { return fail(h, GPX_E_ARG, fn, what); };
   if (any_null) return bad("null argument");
   if (N <= 0 || d <= 0 || d > MAX_D || (with_queries && M <= 0))
     return bad(with_queries ? "need N, M > 0 and 1 <= d <= 32" : "need N > 0 and 1 <= d <= 32");
   if (k <= 0 || k > RHS_ROWS) return bad("need 1 <= k <= 64 target columns");
   if (n_ls != 1 && n_ls != d) return bad("n_ls must be 1 or d");
-  if (mem_kind != GPX_MEM_HOST && mem_kind != GPX_MEM_DEVICE) return bad("bad mem_kind");
+  if (bad_mem_kind(mem_kind)) return bad("bad mem_kind");
   if (!(sf2 > 0.0) || sn2 < 0.0 || jitter < 0.0) return bad("need sf2 > 0, sn2 >= 0, jitter >= 0");
   for (int i = 0; i < n_ls; ++i)
     if (!(lengthscale[i] > 0.0)) return bad("lengthscale must be > 0");
@@ -3198,21 +3228,6 @@ int gpx_fit_predict(gpx_handle* h, const void* X, const void* y, int64_t N, int3
 }
 GPX_CATCH_ALL
 
-int gpx_predict(gpx_handle* h, const void* Xq, int64_t M, void* mean, void* var, int32_t mem_kind) try {
-  if (!h) return GPX_E_ARG;
-  if (!h->fitted) return fail(h, GPX_E_ARG, "gpx_predict: handle has no successful fit");
-  if (!Xq || !mean || M <= 0) return fail(h, GPX_E_ARG, "gpx_predict: bad argument");
-  if (mem_kind != GPX_MEM_HOST && mem_kind != GPX_MEM_DEVICE)
-    return fail(h, GPX_E_ARG, "gpx_predict: bad mem_kind");
-  if (h->group) return group_predict(h, Xq, M, mean, var, mem_kind);
-  int rc;
-  if ((rc = begin_call(h))) return rc;
-  if (h->cfg.dtype == GPX_MIXED) return mixed_predict(h, Xq, M, mean, var, mem_kind);
-  if (h->cfg.world > 1 || h->comm) return BY_DTYPE(h, shard_predict, h, Xq, M, mean, var, mem_kind);
-  return BY_DTYPE(h, predict_impl, h, Xq, M, mean, var, mem_kind);
-}
-GPX_CATCH_ALL
-
 namespace {
 // the joint-posterior calls run on single-device fp64 / fp32 handles; anything else is refused before any work
 int posterior_refused(gpx_handle* h, const char* fn) {
@@ -3225,151 +3240,142 @@ int posterior_refused(gpx_handle* h, const char* fn) {
   snprintf(buf, sizeof buf, "%s: not supported on %s (single-device GPX_F64 / GPX_F32 handles only)", fn, why);
   return fail(h, GPX_E_UNSUPPORTED, buf);
 }
+
+// What the *_paths calls refuse beyond their plain twins' argument checks, before anything is computed: handles the
+// joint-posterior calls refuse, a fit without effective path ids, a null gq or an id below -1 (ids on the device are read
+// back for the check).
+int query_ids_refused(gpx_handle* h, const char* fn, const int32_t* gq, int64_t M, int32_t mem_kind) {
+  if (!gq) return fail(h, GPX_E_ARG, fn, "bad argument");
+  if (int rc = posterior_refused(h, fn)) return rc;
+  if (!h->grouped)
+    return fail(h, GPX_E_UNSUPPORTED, fn,
+                "the current fit has no path ids (gpx_set_path_groups with an id >= 0 and sg2 > 0 before the fit)");
+  std::vector<int32_t> ids;
+  if (int rc = fetch_ids(h, gq, M, mem_kind, ids)) return rc;
+  const int64_t i = first_below_minus_one(ids.data(), M);
+  if (i == M) return GPX_OK;
+  char buf[256];
+  snprintf(buf, sizeof buf, "%s: path id %d of query point %lld is below -1", fn, (int)ids[i], (long long)i);
+  return fail(h, GPX_E_ARG, buf);
+}
 }  // namespace
 
-int gpx_predict_cov(gpx_handle* h, const void* Xq, int64_t M, void* mean, void* cov, int32_t mem_kind) try {
+// ---- the four posterior calls and their *_paths twins (the path itself, f + g_p: a path id per query point; DESIGN.md
+// §3.4k): one body per call.  `fn`, the exported name, heads every message; `paths`: the call takes gq, and query_ids_refused
+// stands in for posterior_refused.
+extern "C++" {
+namespace {
+// What the three joint-posterior families refuse, in their common order, then begin_call: the family's argument test, the
+// mem_kind, its value test (bad_values: the message, or null), a handle without a fit, its size limit (too_large: the
+// message, or null), a kernel without derivatives (gradient), the handle's kind or — paths — the ids.
+int posterior_begin(gpx_handle* h, const char* fn, bool paths, const int32_t* gq, int64_t M, int32_t mem_kind, bool bad_args,
+                    const char* bad_values, const char* too_large, bool gradient = false) {
   if (!h) return GPX_E_ARG;
-  if (!Xq || !cov || M <= 0) return fail(h, GPX_E_ARG, "gpx_predict_cov: bad argument");
-  if (mem_kind != GPX_MEM_HOST && mem_kind != GPX_MEM_DEVICE) return fail(h, GPX_E_ARG, "gpx_predict_cov: bad mem_kind");
-  if (!h->fitted) return fail(h, GPX_E_ARG, "gpx_predict_cov: handle has no successful fit");
-  if (M > (int64_t)INT_MAX - 4096) return fail(h, GPX_E_ARG, "gpx_predict_cov: M too large");
+  if (bad_args) return fail(h, GPX_E_ARG, fn, "bad argument");
+  if (bad_mem_kind(mem_kind)) return fail(h, GPX_E_ARG, fn, "bad mem_kind");
+  if (bad_values) return fail(h, GPX_E_ARG, fn, bad_values);
+  if (!h->fitted) return fail(h, GPX_E_ARG, fn, "handle has no successful fit");
+  if (too_large) return fail(h, GPX_E_ARG, fn, too_large);
+  if (gradient && !cov::differentiable(h->cfg.kernel)) return fail(h, GPX_E_UNSUPPORTED, fn, MATERN12_NO_GRAD);
+  const int rc = paths ? query_ids_refused(h, fn, gq, M, mem_kind) : posterior_refused(h, fn);
+  return rc ? rc : begin_call(h);
+}
+
+// (gpx_predict alone tests the fit before the arguments, serves groups, shards and GPX_MIXED handles, and has no limit on M)
+int predict_entry(gpx_handle* h, const char* fn, bool paths, const void* Xq, const int32_t* gq, int64_t M, void* mean,
+                  void* var, int32_t mem_kind) {
+  if (!h) return GPX_E_ARG;
+  if (!h->fitted) return fail(h, GPX_E_ARG, fn, "handle has no successful fit");
+  if (!Xq || !mean || M <= 0) return fail(h, GPX_E_ARG, fn, "bad argument");
+  if (bad_mem_kind(mem_kind)) return fail(h, GPX_E_ARG, fn, "bad mem_kind");
   int rc;
-  if ((rc = posterior_refused(h, "gpx_predict_cov"))) return rc;
+  if (paths) {
+    if (M > (int64_t)INT_MAX - 4096) return fail(h, GPX_E_ARG, fn, "M too large");
+    if ((rc = query_ids_refused(h, fn, gq, M, mem_kind)) || (rc = begin_call(h))) return rc;
+    return BY_DTYPE(h, predict_impl, h, Xq, M, mean, var, mem_kind, gq);
+  }
+  if (h->group) return group_predict(h, Xq, M, mean, var, mem_kind);
   if ((rc = begin_call(h))) return rc;
-  return BY_DTYPE(h, predict_cov_impl, h, Xq, M, mean, cov, mem_kind);
+  if (h->cfg.dtype == GPX_MIXED) return mixed_predict(h, Xq, M, mean, var, mem_kind);
+  if (h->cfg.world > 1 || h->comm) return BY_DTYPE(h, shard_predict, h, Xq, M, mean, var, mem_kind);
+  return BY_DTYPE(h, predict_impl, h, Xq, M, mean, var, mem_kind);
+}
+
+int predict_cov_entry(gpx_handle* h, const char* fn, bool paths, const void* Xq, const int32_t* gq, int64_t M, void* mean,
+                      void* cov, int32_t mem_kind) {
+  const int rc = posterior_begin(h, fn, paths, gq, M, mem_kind, !Xq || !cov || M <= 0, nullptr,
+                                 M > (int64_t)INT_MAX - 4096 ? "M too large" : nullptr);
+  return rc ? rc : BY_DTYPE(h, predict_cov_impl, h, Xq, M, mean, cov, mem_kind, gq);
+}
+
+int sample_posterior_entry(gpx_handle* h, const char* fn, bool paths, const void* Xq, const int32_t* gq, int64_t M, int64_t S,
+                           uint64_t seed, const void* z, double diag_add, double jitter, int32_t max_tries, void* out,
+                           double* jitter_used, int64_t* info, int32_t mem_kind) {
+  const bool values_ok = diag_add >= 0.0 && jitter >= 0.0 && max_tries >= 1;
+  const int rc = posterior_begin(h, fn, paths, gq, M, mem_kind, !Xq || !out || !info || !jitter_used || M <= 0 || S <= 0,
+                                 values_ok ? nullptr : "need diag_add >= 0, jitter >= 0, max_tries >= 1",
+                                 M > (int64_t)INT_MAX - 4096 || S > (int64_t)1 << 40 ? "M or S too large" : nullptr);
+  if (rc) return rc;
+  return BY_DTYPE(h, sample_posterior_impl, h, Xq, M, S, seed, z, diag_add, jitter, max_tries, out, jitter_used, info,
+                  mem_kind, gq);
+}
+
+int predict_grad_entry(gpx_handle* h, const char* fn, bool paths, const void* Xq, const int32_t* gq, int64_t M, void* mean,
+                       void* var, void* dmean, void* dvar, int32_t mem_kind) {
+  const int rc = posterior_begin(h, fn, paths, gq, M, mem_kind, !Xq || !dmean || M <= 0, nullptr,
+                                 M > (int64_t)INT_MAX - 4096 ? "M too large" : nullptr, true);
+  return rc ? rc : BY_DTYPE(h, predict_grad_impl, h, Xq, M, mean, var, dmean, dvar, mem_kind, gq);
+}
+}  // namespace
+}  // extern "C++"
+
+int gpx_predict(gpx_handle* h, const void* Xq, int64_t M, void* mean, void* var, int32_t mem_kind) try {
+  return predict_entry(h, "gpx_predict", false, Xq, nullptr, M, mean, var, mem_kind);
+}
+GPX_CATCH_ALL
+
+int gpx_predict_paths(gpx_handle* h, const void* Xq, const int32_t* gq, int64_t M, void* mean, void* var,
+                      int32_t mem_kind) try {
+  return predict_entry(h, "gpx_predict_paths", true, Xq, gq, M, mean, var, mem_kind);
+}
+GPX_CATCH_ALL
+
+int gpx_predict_cov(gpx_handle* h, const void* Xq, int64_t M, void* mean, void* cov, int32_t mem_kind) try {
+  return predict_cov_entry(h, "gpx_predict_cov", false, Xq, nullptr, M, mean, cov, mem_kind);
+}
+GPX_CATCH_ALL
+
+int gpx_predict_cov_paths(gpx_handle* h, const void* Xq, const int32_t* gq, int64_t M, void* mean, void* cov,
+                          int32_t mem_kind) try {
+  return predict_cov_entry(h, "gpx_predict_cov_paths", true, Xq, gq, M, mean, cov, mem_kind);
 }
 GPX_CATCH_ALL
 
 int gpx_sample_posterior(gpx_handle* h, const void* Xq, int64_t M, int64_t S, uint64_t seed, const void* z,
                          double diag_add, double jitter, int32_t max_tries, void* out, double* jitter_used, int64_t* info,
                          int32_t mem_kind) try {
-  if (!h) return GPX_E_ARG;
-  if (!Xq || !out || !info || !jitter_used || M <= 0 || S <= 0)
-    return fail(h, GPX_E_ARG, "gpx_sample_posterior: bad argument");
-  if (mem_kind != GPX_MEM_HOST && mem_kind != GPX_MEM_DEVICE)
-    return fail(h, GPX_E_ARG, "gpx_sample_posterior: bad mem_kind");
-  if (!(diag_add >= 0.0) || !(jitter >= 0.0) || max_tries < 1)
-    return fail(h, GPX_E_ARG, "gpx_sample_posterior: need diag_add >= 0, jitter >= 0, max_tries >= 1");
-  if (!h->fitted) return fail(h, GPX_E_ARG, "gpx_sample_posterior: handle has no successful fit");
-  if (M > (int64_t)INT_MAX - 4096 || S > (int64_t)1 << 40) return fail(h, GPX_E_ARG, "gpx_sample_posterior: M or S too large");
-  int rc;
-  if ((rc = posterior_refused(h, "gpx_sample_posterior"))) return rc;
-  if ((rc = begin_call(h))) return rc;
-  return BY_DTYPE(h, sample_posterior_impl, h, Xq, M, S, seed, z, diag_add, jitter, max_tries, out, jitter_used, info, mem_kind);
-}
-GPX_CATCH_ALL
-
-int gpx_predict_grad(gpx_handle* h, const void* Xq, int64_t M, void* mean, void* var, void* dmean, void* dvar,
-                     int32_t mem_kind) try {
-  if (!h) return GPX_E_ARG;
-  if (!Xq || !dmean || M <= 0) return fail(h, GPX_E_ARG, "gpx_predict_grad: bad argument");
-  if (mem_kind != GPX_MEM_HOST && mem_kind != GPX_MEM_DEVICE) return fail(h, GPX_E_ARG, "gpx_predict_grad: bad mem_kind");
-  if (!h->fitted) return fail(h, GPX_E_ARG, "gpx_predict_grad: handle has no successful fit");
-  if (M > (int64_t)INT_MAX - 4096) return fail(h, GPX_E_ARG, "gpx_predict_grad: M too large");
-  if (!cov::differentiable(h->cfg.kernel)) return fail(h, GPX_E_UNSUPPORTED, "gpx_predict_grad: " MATERN12_NO_GRAD);
-  int rc;
-  if ((rc = posterior_refused(h, "gpx_predict_grad"))) return rc;
-  if ((rc = begin_call(h))) return rc;
-  return BY_DTYPE(h, predict_grad_impl, h, Xq, M, mean, var, dmean, dvar, mem_kind);
-}
-GPX_CATCH_ALL
-
-// ---- the path itself, f + g_p: the four posterior calls with a path id per query point --------------------
-namespace {
-// What the *_paths calls refuse beyond their plain twins' argument checks, before anything is computed: handles the
-// joint-posterior calls refuse, a fit without effective path ids, a null gq or an id below -1 (ids on the device are read
-// back for the check).
-int query_ids_refused(gpx_handle* h, const char* fn, const int32_t* gq, int64_t M, int32_t mem_kind) {
-  char buf[256];
-  int rc;
-  if (!gq) {
-    snprintf(buf, sizeof buf, "%s: bad argument", fn);
-    return fail(h, GPX_E_ARG, buf);
-  }
-  if ((rc = posterior_refused(h, fn))) return rc;
-  if (!h->grouped) {
-    snprintf(buf, sizeof buf, "%s: the current fit has no path ids (gpx_set_path_groups with an id >= 0 and sg2 > 0 before the fit)",
-             fn);
-    return fail(h, GPX_E_UNSUPPORTED, buf);
-  }
-  std::vector<int32_t> dev;
-  const int32_t* ids = gq;
-  if (mem_kind == GPX_MEM_DEVICE) {
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    dev.resize((size_t)M);
-    HIPCHK(h, hipMemcpy(dev.data(), gq, (size_t)M * sizeof(int32_t), hipMemcpyDeviceToHost));
-    ids = dev.data();
-  }
-  for (int64_t i = 0; i < M; ++i)
-    if (ids[i] < -1) {
-      snprintf(buf, sizeof buf, "%s: path id %d of query point %lld is below -1", fn, (int)ids[i], (long long)i);
-      return fail(h, GPX_E_ARG, buf);
-    }
-  return GPX_OK;
-}
-}  // namespace
-
-int gpx_predict_paths(gpx_handle* h, const void* Xq, const int32_t* gq, int64_t M, void* mean, void* var,
-                      int32_t mem_kind) try {
-  if (!h) return GPX_E_ARG;
-  if (!h->fitted) return fail(h, GPX_E_ARG, "gpx_predict_paths: handle has no successful fit");
-  if (!Xq || !mean || M <= 0) return fail(h, GPX_E_ARG, "gpx_predict_paths: bad argument");
-  if (mem_kind != GPX_MEM_HOST && mem_kind != GPX_MEM_DEVICE) return fail(h, GPX_E_ARG, "gpx_predict_paths: bad mem_kind");
-  if (M > (int64_t)INT_MAX - 4096) return fail(h, GPX_E_ARG, "gpx_predict_paths: M too large");
-  int rc;
-  if ((rc = query_ids_refused(h, "gpx_predict_paths", gq, M, mem_kind))) return rc;
-  if ((rc = begin_call(h))) return rc;
-  return BY_DTYPE(h, predict_impl, h, Xq, M, mean, var, mem_kind, gq);
-}
-GPX_CATCH_ALL
-
-int gpx_predict_cov_paths(gpx_handle* h, const void* Xq, const int32_t* gq, int64_t M, void* mean, void* cov,
-                          int32_t mem_kind) try {
-  if (!h) return GPX_E_ARG;
-  if (!Xq || !cov || M <= 0) return fail(h, GPX_E_ARG, "gpx_predict_cov_paths: bad argument");
-  if (mem_kind != GPX_MEM_HOST && mem_kind != GPX_MEM_DEVICE) return fail(h, GPX_E_ARG, "gpx_predict_cov_paths: bad mem_kind");
-  if (!h->fitted) return fail(h, GPX_E_ARG, "gpx_predict_cov_paths: handle has no successful fit");
-  if (M > (int64_t)INT_MAX - 4096) return fail(h, GPX_E_ARG, "gpx_predict_cov_paths: M too large");
-  int rc;
-  if ((rc = query_ids_refused(h, "gpx_predict_cov_paths", gq, M, mem_kind))) return rc;
-  if ((rc = begin_call(h))) return rc;
-  return BY_DTYPE(h, predict_cov_impl, h, Xq, M, mean, cov, mem_kind, gq);
+  return sample_posterior_entry(h, "gpx_sample_posterior", false, Xq, nullptr, M, S, seed, z, diag_add, jitter, max_tries, out,
+                                jitter_used, info, mem_kind);
 }
 GPX_CATCH_ALL
 
 int gpx_sample_posterior_paths(gpx_handle* h, const void* Xq, const int32_t* gq, int64_t M, int64_t S, uint64_t seed,
                                const void* z, double diag_add, double jitter, int32_t max_tries, void* out,
                                double* jitter_used, int64_t* info, int32_t mem_kind) try {
-  if (!h) return GPX_E_ARG;
-  if (!Xq || !out || !info || !jitter_used || M <= 0 || S <= 0)
-    return fail(h, GPX_E_ARG, "gpx_sample_posterior_paths: bad argument");
-  if (mem_kind != GPX_MEM_HOST && mem_kind != GPX_MEM_DEVICE)
-    return fail(h, GPX_E_ARG, "gpx_sample_posterior_paths: bad mem_kind");
-  if (!(diag_add >= 0.0) || !(jitter >= 0.0) || max_tries < 1)
-    return fail(h, GPX_E_ARG, "gpx_sample_posterior_paths: need diag_add >= 0, jitter >= 0, max_tries >= 1");
-  if (!h->fitted) return fail(h, GPX_E_ARG, "gpx_sample_posterior_paths: handle has no successful fit");
-  if (M > (int64_t)INT_MAX - 4096 || S > (int64_t)1 << 40)
-    return fail(h, GPX_E_ARG, "gpx_sample_posterior_paths: M or S too large");
-  int rc;
-  if ((rc = query_ids_refused(h, "gpx_sample_posterior_paths", gq, M, mem_kind))) return rc;
-  if ((rc = begin_call(h))) return rc;
-  return BY_DTYPE(h, sample_posterior_impl, h, Xq, M, S, seed, z, diag_add, jitter, max_tries, out, jitter_used, info,
-                  mem_kind, gq);
+  return sample_posterior_entry(h, "gpx_sample_posterior_paths", true, Xq, gq, M, S, seed, z, diag_add, jitter, max_tries,
+                                out, jitter_used, info, mem_kind);
+}
+GPX_CATCH_ALL
+
+int gpx_predict_grad(gpx_handle* h, const void* Xq, int64_t M, void* mean, void* var, void* dmean, void* dvar,
+                     int32_t mem_kind) try {
+  return predict_grad_entry(h, "gpx_predict_grad", false, Xq, nullptr, M, mean, var, dmean, dvar, mem_kind);
 }
 GPX_CATCH_ALL
 
 int gpx_predict_grad_paths(gpx_handle* h, const void* Xq, const int32_t* gq, int64_t M, void* mean, void* var, void* dmean,
                            void* dvar, int32_t mem_kind) try {
-  if (!h) return GPX_E_ARG;
-  if (!Xq || !dmean || M <= 0) return fail(h, GPX_E_ARG, "gpx_predict_grad_paths: bad argument");
-  if (mem_kind != GPX_MEM_HOST && mem_kind != GPX_MEM_DEVICE) return fail(h, GPX_E_ARG, "gpx_predict_grad_paths: bad mem_kind");
-  if (!h->fitted) return fail(h, GPX_E_ARG, "gpx_predict_grad_paths: handle has no successful fit");
-  if (M > (int64_t)INT_MAX - 4096) return fail(h, GPX_E_ARG, "gpx_predict_grad_paths: M too large");
-  if (!cov::differentiable(h->cfg.kernel)) return fail(h, GPX_E_UNSUPPORTED, "gpx_predict_grad_paths: " MATERN12_NO_GRAD);
-  int rc;
-  if ((rc = query_ids_refused(h, "gpx_predict_grad_paths", gq, M, mem_kind))) return rc;
-  if ((rc = begin_call(h))) return rc;
-  return BY_DTYPE(h, predict_grad_impl, h, Xq, M, mean, var, dmean, dvar, mem_kind, gq);
+  return predict_grad_entry(h, "gpx_predict_grad_paths", true, Xq, gq, M, mean, var, dmean, dvar, mem_kind);
 }
 GPX_CATCH_ALL
 
@@ -3381,7 +3387,7 @@ int score_blocks_entry(gpx_handle* h, const void* Xs, const void* ys, const void
   if (!Xs || !ys || !logp || !info || G <= 0) return fail(h, GPX_E_ARG, "gpx_score_blocks: bad argument");
   if (Lg < 1 || Lg > 64) return fail(h, GPX_E_ARG, "gpx_score_blocks: need 1 <= Lg <= 64");
   if (!(diag_add >= 0.0)) return fail(h, GPX_E_ARG, "gpx_score_blocks: need diag_add >= 0");
-  if (mem_kind != GPX_MEM_HOST && mem_kind != GPX_MEM_DEVICE) return fail(h, GPX_E_ARG, "gpx_score_blocks: bad mem_kind");
+  if (bad_mem_kind(mem_kind)) return fail(h, GPX_E_ARG, "gpx_score_blocks: bad mem_kind");
   if (!h->fitted) return fail(h, GPX_E_ARG, "gpx_score_blocks: handle has no successful fit");
   if (G > ((int64_t)INT_MAX - 4096) / Lg) return fail(h, GPX_E_ARG, "gpx_score_blocks: G * Lg too large");
   int rc;
@@ -3396,7 +3402,7 @@ int append_entry(gpx_handle* h, const void* Xnew, const void* ynew, const void* 
                  int64_t* info) {
   if (!h) return GPX_E_ARG;
   if (!Xnew || !ynew || !info || m <= 0) return fail(h, GPX_E_ARG, "gpx_append: bad argument");
-  if (mem_kind != GPX_MEM_HOST && mem_kind != GPX_MEM_DEVICE) return fail(h, GPX_E_ARG, "gpx_append: bad mem_kind");
+  if (bad_mem_kind(mem_kind)) return fail(h, GPX_E_ARG, "gpx_append: bad mem_kind");
   int rc;
   if ((rc = posterior_refused(h, "gpx_append"))) return rc;
   if (!h->fitted) return fail(h, GPX_E_ARG, "gpx_append: handle has no successful fit");
@@ -3458,24 +3464,16 @@ int gpx_append_rows(gpx_handle* h, const void* Xnew, const void* ynew, const voi
                     const int32_t* group_new, int64_t m, int32_t mem_kind, int64_t* info) try {
   if (!h) return GPX_E_ARG;
   if (!Xnew || !ynew || !info || m <= 0) return fail(h, GPX_E_ARG, "gpx_append_rows: bad argument");
-  if (mem_kind != GPX_MEM_HOST && mem_kind != GPX_MEM_DEVICE) return fail(h, GPX_E_ARG, "gpx_append_rows: bad mem_kind");
+  if (bad_mem_kind(mem_kind)) return fail(h, GPX_E_ARG, "gpx_append_rows: bad mem_kind");
   int rc;
   if ((rc = posterior_refused(h, "gpx_append_rows"))) return rc;
   if (!h->fitted) return fail(h, GPX_E_ARG, "gpx_append_rows: handle has no successful fit");
   if (m > (int64_t)INT_MAX - 4096 - h->N) return fail(h, GPX_E_ARG, "gpx_append_rows: N + m too large");
   // the kinds and the ids are checked in host copies (NULL: all -1), which also feed the fit's host vectors afterwards
   std::vector<int32_t> kinds((size_t)m, -1), ids((size_t)m, -1);
-  auto fetch = [&](const int32_t* src, std::vector<int32_t>& dst) -> int {
-    if (!src) return GPX_OK;
-    if (mem_kind == GPX_MEM_HOST) {
-      std::copy(src, src + m, dst.begin());
-      return GPX_OK;
-    }
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    HIPCHK(h, hipMemcpy(dst.data(), src, (size_t)m * sizeof(int32_t), hipMemcpyDefault));
-    return GPX_OK;
-  };
-  if ((rc = fetch(kind_new, kinds)) || (rc = fetch(group_new, ids))) return rc;
+  if ((kind_new && (rc = fetch_ids(h, kind_new, m, mem_kind, kinds))) ||
+      (group_new && (rc = fetch_ids(h, group_new, m, mem_kind, ids))))
+    return rc;
   bool deriv = false, path = false;
   for (int64_t i = 0; i < m; ++i) {
     if (kinds[i] < -1 || kinds[i] >= h->d)
@@ -3504,7 +3502,7 @@ GPX_CATCH_ALL
 
 int gpx_set_noise_weights(gpx_handle* h, const void* w, int64_t n, int32_t mem_kind) try {
   if (!h) return GPX_E_ARG;
-  if (mem_kind != GPX_MEM_HOST && mem_kind != GPX_MEM_DEVICE) return fail(h, GPX_E_ARG, "gpx_set_noise_weights: bad mem_kind");
+  if (bad_mem_kind(mem_kind)) return fail(h, GPX_E_ARG, "gpx_set_noise_weights: bad mem_kind");
   if (n < 0 || (n == 0) != (w == nullptr) || n > (int64_t)INT_MAX - 4096)
     return fail(h, GPX_E_ARG, "gpx_set_noise_weights: need n weights, or NULL and 0 to clear them");
   const size_t es = h->cfg.dtype == GPX_F32 ? 4 : 8;
@@ -3562,8 +3560,7 @@ GPX_CATCH_ALL
 
 int gpx_set_observation_kinds(gpx_handle* h, const int32_t* kind, int64_t n, double sn2_deriv, int32_t mem_kind) try {
   if (!h) return GPX_E_ARG;
-  if (mem_kind != GPX_MEM_HOST && mem_kind != GPX_MEM_DEVICE)
-    return fail(h, GPX_E_ARG, "gpx_set_observation_kinds: bad mem_kind");
+  if (bad_mem_kind(mem_kind)) return fail(h, GPX_E_ARG, "gpx_set_observation_kinds: bad mem_kind");
   if (n < 0 || (n == 0) != (kind == nullptr) || n > (int64_t)INT_MAX - 4096)
     return fail(h, GPX_E_ARG, "gpx_set_observation_kinds: need n kinds, or NULL and 0 to clear them");
   if (n == 0) {
@@ -3571,19 +3568,13 @@ int gpx_set_observation_kinds(gpx_handle* h, const int32_t* kind, int64_t n, dou
     h->sn2_deriv_set = 0.0;
     return GPX_OK;
   }
-  if (!(sn2_deriv >= 0.0) || !std::isfinite(sn2_deriv))
-    return fail(h, GPX_E_ARG, "gpx_set_observation_kinds: sn2_deriv must be finite and >= 0");
+  if (!variance_ok(sn2_deriv)) return fail(h, GPX_E_ARG, "gpx_set_observation_kinds: sn2_deriv must be finite and >= 0");
   // validated in a copy of the caller's array, before the handle's is replaced: a refused call leaves the kinds of the
   // call before in place
-  std::vector<int32_t> fresh((size_t)n);
-  if (mem_kind == GPX_MEM_HOST) {
-    std::copy(kind, kind + n, fresh.begin());
-  } else {
-    if (!h->group) HIPCHK(h, hipSetDevice(h->cfg.device));
-    HIPCHK(h, hipMemcpy(fresh.data(), kind, (size_t)n * sizeof(int32_t), hipMemcpyDefault));
-  }
-  for (int64_t i = 0; i < n; ++i)
-    if (fresh[i] < -1) return fail(h, GPX_E_ARG, "gpx_set_observation_kinds: a kind is -1 (a value) or a dimension >= 0");
+  std::vector<int32_t> fresh;
+  if (int rc = fetch_ids(h, kind, n, mem_kind, fresh)) return rc;
+  if (first_below_minus_one(fresh.data(), n) < n)
+    return fail(h, GPX_E_ARG, "gpx_set_observation_kinds: a kind is -1 (a value) or a dimension >= 0");
   h->kinds_set = std::move(fresh);
   h->sn2_deriv_set = sn2_deriv;
   return GPX_OK;
@@ -3605,7 +3596,7 @@ GPX_CATCH_ALL
 int gpx_set_path_groups(gpx_handle* h, const int32_t* group, int64_t n, double sg2, const double* ls_path,
                         int32_t n_ls_path, int32_t mem_kind) try {
   if (!h) return GPX_E_ARG;
-  if (mem_kind != GPX_MEM_HOST && mem_kind != GPX_MEM_DEVICE) return fail(h, GPX_E_ARG, "gpx_set_path_groups: bad mem_kind");
+  if (bad_mem_kind(mem_kind)) return fail(h, GPX_E_ARG, "gpx_set_path_groups: bad mem_kind");
   if (n < 0 || (n == 0) != (group == nullptr) || n > (int64_t)INT_MAX - 4096)
     return fail(h, GPX_E_ARG, "gpx_set_path_groups: need n path ids, or NULL and 0 to clear them");
   if (n == 0) {
@@ -3614,23 +3605,17 @@ int gpx_set_path_groups(gpx_handle* h, const int32_t* group, int64_t n, double s
     h->sg2_set = 0.0;
     return GPX_OK;
   }
-  if (!(sg2 >= 0.0) || !std::isfinite(sg2)) return fail(h, GPX_E_ARG, "gpx_set_path_groups: sg2 must be finite and >= 0");
+  if (!variance_ok(sg2)) return fail(h, GPX_E_ARG, "gpx_set_path_groups: sg2 must be finite and >= 0");
   if (!ls_path || n_ls_path < 1 || n_ls_path > MAX_D)
     return fail(h, GPX_E_ARG, "gpx_set_path_groups: need 1 or d path lengthscales");
-  for (int32_t c = 0; c < n_ls_path; ++c)
-    if (!(ls_path[c] > 0.0) || !std::isfinite(ls_path[c]))
-      return fail(h, GPX_E_ARG, "gpx_set_path_groups: path lengthscales must be finite and > 0");
+  if (!path_ls_ok(ls_path, n_ls_path))
+    return fail(h, GPX_E_ARG, "gpx_set_path_groups: path lengthscales must be finite and > 0");
   // validated in a copy of the caller's array, before the handle's is replaced: a refused call leaves the setting of the
   // call before in place
-  std::vector<int32_t> fresh((size_t)n);
-  if (mem_kind == GPX_MEM_HOST) {
-    std::copy(group, group + n, fresh.begin());
-  } else {
-    if (!h->group) HIPCHK(h, hipSetDevice(h->cfg.device));
-    HIPCHK(h, hipMemcpy(fresh.data(), group, (size_t)n * sizeof(int32_t), hipMemcpyDefault));
-  }
-  for (int64_t i = 0; i < n; ++i)
-    if (fresh[i] < -1) return fail(h, GPX_E_ARG, "gpx_set_path_groups: a path id is -1 (no path) or >= 0");
+  std::vector<int32_t> fresh;
+  if (int rc = fetch_ids(h, group, n, mem_kind, fresh)) return rc;
+  if (first_below_minus_one(fresh.data(), n) < n)
+    return fail(h, GPX_E_ARG, "gpx_set_path_groups: a path id is -1 (no path) or >= 0");
   h->groups_set = std::move(fresh);
   h->lsp_set.assign(ls_path, ls_path + n_ls_path);
   h->sg2_set = sg2;
@@ -3657,7 +3642,7 @@ int gpx_forecast_blocks(gpx_handle* h, const void* Xb, const void* yo, int64_t G
   if (Lo < 1 || Lp < 1 || (int64_t)Lo + Lp > 64)
     return fail(h, GPX_E_ARG, "gpx_forecast_blocks: need 1 <= Lo, 1 <= Lp and Lo + Lp <= 64");
   if (!(diag_add >= 0.0)) return fail(h, GPX_E_ARG, "gpx_forecast_blocks: need diag_add >= 0");
-  if (mem_kind != GPX_MEM_HOST && mem_kind != GPX_MEM_DEVICE) return fail(h, GPX_E_ARG, "gpx_forecast_blocks: bad mem_kind");
+  if (bad_mem_kind(mem_kind)) return fail(h, GPX_E_ARG, "gpx_forecast_blocks: bad mem_kind");
   if (!h->fitted) return fail(h, GPX_E_ARG, "gpx_forecast_blocks: handle has no successful fit");
   const int32_t Lg = Lo + Lp;
   if (G > ((int64_t)INT_MAX - 4096) / (Lg * (int64_t)Lp)) return fail(h, GPX_E_ARG, "gpx_forecast_blocks: G too large");
@@ -3815,73 +3800,187 @@ int gpx_get_timings(gpx_handle* h, gpx_timings* out) try {
 GPX_CATCH_ALL
 
 // ---- kernel unit-test entry points -------------------------------------------------------
+// Every HIP failure of these entry points is GPX_E_HIP, a failed allocation included, with the failing call in
+// gpx_last_error(NULL).  A call's Dev buffers are declared after its Scratch, so they free themselves before the streams go.
+#define UCHK(call)                                                              \
+  do {                                                                          \
+    if ((call) != hipSuccess) return fail(nullptr, GPX_E_HIP, #call " failed"); \
+  } while (0)
+
+extern "C++" {
 namespace {
 struct Scratch {  // a throw-away handle-like context for the host-buffer entry points
   gpx_handle h;
+  hipStream_t& st = h.st;  // the main stream: what an entry point enqueues goes here
   bool ok = false;
   Scratch() {
     int dev = 0;
     refresh_env(&h);  // the schedulers a unit-test entry point runs read h.env like any call
     if (hipGetDevice(&dev) != hipSuccess) return;
     h.cfg.device = dev;
-    ok = hipStreamCreateWithFlags(&h.st, hipStreamNonBlocking) == hipSuccess &&
-         hipStreamCreateWithFlags(&h.st2, hipStreamNonBlocking) == hipSuccess &&
-         hipStreamCreateWithFlags(&h.st3, hipStreamNonBlocking) == hipSuccess &&
-         hipStreamCreateWithFlags(&h.st4, hipStreamNonBlocking) == hipSuccess;
+    ok = true;
+    for (hipStream_t* s : {&h.st, &h.st2, &h.st3, &h.st4})
+      ok = ok && hipStreamCreateWithFlags(s, hipStreamNonBlocking) == hipSuccess;
+  }
+  int finish() {  // what the call enqueued on the main stream has run, and without an error
+    UCHK(hipStreamSynchronize(st));
+    UCHK(hipGetLastError());
+    return GPX_OK;
   }
 };  // (~gpx_handle tears down streams, events and whatever buffer a scheduler function allocated)
-#define TCHK(call)                                   \
-  do {                                               \
-    if ((call) != hipSuccess) {                      \
-      g_create_error = #call " failed";             \
-      rc = GPX_E_HIP;                                \
-      goto done;                                     \
-    }                                                \
-  } while (0)
+
+template <typename T>
+struct Dev : DevBuf {  // a DevBuf of `count` elements that reads as the T* it holds
+  operator T*() const { return (T*)p; }
+  int alloc(size_t count) {
+    UCHK(hipMalloc(&p, count * sizeof(T)));
+    return GPX_OK;
+  }
+  int upload(const T* src, size_t count, hipStream_t st, size_t room = 0) {  // room for max(count, room); count from the host
+    UCHK(hipMalloc(&p, std::max(count, room) * sizeof(T)));
+    UCHK(hipMemcpyAsync(p, src, count * sizeof(T), hipMemcpyHostToDevice, st));
+    return GPX_OK;
+  }
+};
+
+// What the kernel-matrix calls check alike, all of it GPX_E_ARG without a message: na x nb points of 1 <= d <= MAX_D
+// dimensions with n_ls = 1 or d lengthscales; the element type; path ids >= -1 with lengthscales and sg2 as
+// gpx_set_path_groups takes them.
+bool sizes_ok(int64_t na, int64_t nb, int32_t d, int32_t n_ls) {
+  return na > 0 && nb > 0 && d > 0 && d <= MAX_D && (n_ls == 1 || n_ls == d);
+}
+bool unit_dtype_ok(int32_t dtype) { return dtype == GPX_F64 || dtype == GPX_F32; }
+bool path_args_ok(const int32_t* ga, int64_t na, const int32_t* gb, int64_t nb, const double* ls_path, int32_t n_ls_path,
+                  double sg2) {
+  return variance_ok(sg2) && path_ls_ok(ls_path, n_ls_path) && first_below_minus_one(ga, na) == na &&
+         first_below_minus_one(gb, nb) == nb;
+}
+// the kinds of both sides (null: all values) lie in [-1, d); a derivative among them on Matern-1/2 is refused under fn
+int kinds_refused(const char* fn, int32_t kernel, const int32_t* ka, int64_t na, const int32_t* kb, int64_t nb, int32_t d) {
+  bool deriv = false;
+  for (auto [kind, n] : {std::pair{ka, na}, std::pair{kb, nb}})
+    for (int64_t i = 0; kind && i < n; ++i) {
+      if (kind[i] < -1 || kind[i] >= d) return GPX_E_ARG;
+      deriv |= kind[i] >= 0;
+    }
+  if (deriv && !cov::differentiable(kernel)) return fail(nullptr, GPX_E_UNSUPPORTED, fn, MATERN12_NO_GRAD);
+  return GPX_OK;
+}
+
+// The staging the seven kernel-matrix calls share, on a Scratch of its own: the points scaled by the lengthscales, the side
+// arrays and the output on the device, the result back in the caller's dense array.  An entry point is its argument
+// checks, these calls, its one launch, fetch.
+template <typename T>
+struct KernelCall {
+  Scratch sc;
+  hipStream_t st = sc.st;
+  int d = 0;
+  int64_t na = 0, nb = 0, napad = 0, nbpad = 0, ld = 0, nblk = 0;
+  std::vector<T> hA, hB, host;  // the points rounded to T, the padded result (the sources live until fetch has synchronised)
+  Dev<T> A, B, As, Bs, K;      // points raw and scaled (n x d, round_up(n, 64) x d), nblk blocks of napad x ld
+  Dev<double> ls, q;            // MAX_D entries each
+  Dev<int32_t> ga, gb;
+  int scaled(Dev<T>& raw, Dev<T>& scl, const std::vector<T>& h, int64_t n, int64_t npad, int32_t n_ls) {
+    if (int rc; (rc = raw.upload(h.data(), h.size(), st)) || (rc = scl.alloc((size_t)npad * d))) return rc;
+    launch_scale_points<T>(raw, n, npad, d, ls, n_ls, scl, st);
+    return GPX_OK;
+  }
+  // A (na x d) and B (nb x d; null: the symmetric call, nb = na) scaled by the n_ls lengthscales
+  int points(const double* A_, int64_t na_, const double* B_, int64_t nb_, int32_t d_, const double* lengthscale, int32_t n_ls) {
+    if (!sc.ok) return GPX_E_HIP;
+    d = d_, na = na_, nb = B_ ? nb_ : na_, napad = round_up(na, 64), nbpad = round_up(nb, 64), ld = nbpad;
+    hA.assign(A_, A_ + na * d);
+    if (B_) hB.assign(B_, B_ + nb * d);
+    if (int rc; (rc = ls.upload(lengthscale, n_ls, st, MAX_D)) || (rc = scaled(A, As, hA, na, napad, n_ls)) || !B_) return rc;
+    return scaled(B, Bs, hB, nb, nbpad, n_ls);
+  }
+  // One int32 array per side (ids or kinds).  padded: at the padded length, -1 beyond the values and on a side without any;
+  // else at n, and a null device pointer for a side without any.
+  int side(Dev<int32_t>& g, const int32_t* src, int64_t n, int64_t npad, bool padded) {
+    if (!padded) return src ? g.upload(src, n, st) : GPX_OK;
+    if (int rc = g.alloc(npad)) return rc;
+    UCHK(hipMemsetAsync(g, 0xFF, (size_t)npad * 4, st));
+    if (src) UCHK(hipMemcpyAsync(g, src, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    return GPX_OK;
+  }
+  int sides(const int32_t* a, const int32_t* b, bool padded, const double* q_ = nullptr) {  // q_: the caller's d entries of q
+    int rc;
+    if (q_ && (rc = q.upload(q_, d, st, MAX_D))) return rc;
+    return (rc = side(ga, a, na, napad, padded)) ? rc : side(gb, b, nb, nbpad, padded);
+  }
+  int output(int64_t nblk_, bool zero) {
+    host.resize((size_t)(nblk = nblk_) * napad * ld);
+    if (int rc = K.alloc(host.size())) return rc;
+    if (zero) UCHK(hipMemsetAsync(K, 0, host.size() * sizeof(T), st));
+    return GPX_OK;
+  }
+  int fetch(double* out) {  // -> (nblk, na, nb), dense
+    UCHK(hipMemcpyAsync(host.data(), K, host.size() * sizeof(T), hipMemcpyDeviceToHost, st));
+    if (int rc = sc.finish()) return rc;
+    for (int64_t b = 0; b < nblk; ++b)
+      for (int64_t i = 0; i < na; ++i)
+        for (int64_t j = 0; j < nb; ++j) out[(b * na + i) * nb + j] = (double)host[(size_t)(b * napad + i) * ld + j];
+    return GPX_OK;
+  }
+};
+
+// gpx_kernel_path_matrix, K (na, nb), and gpx_kernel_path_grad_matrix (grad), K (d, na, nb) = the d derivative matrices by
+// A: one body; fn names the call in the message
+int kernel_path_entry(const char* fn, bool grad, int32_t kernel, int32_t dtype, const double* A, const int32_t* ga, int64_t na,
+                      const double* B, const int32_t* gb, int64_t nb_, int32_t d, const double* lengthscale, int32_t n_ls,
+                      double sf2, const double* ls_path, int32_t n_ls_path, double sg2, double* K) {
+  if (!A || !B || !ga || !gb || !K || !lengthscale || !ls_path || !sizes_ok(na, nb_, d, n_ls) ||
+      (n_ls_path != 1 && n_ls_path != d))
+    return GPX_E_ARG;
+  if (!cov::known(kernel) || !unit_dtype_ok(dtype) || !path_args_ok(ga, na, gb, nb_, ls_path, n_ls_path, sg2)) return GPX_E_ARG;
+  if (grad && !cov::differentiable(kernel)) return fail(nullptr, GPX_E_UNSUPPORTED, fn, MATERN12_NO_GRAD);
+  std::vector<double> q((size_t)d);
+  for (int c = 0; c < d; ++c) q[c] = lengthscale[n_ls == 1 ? 0 : c] / ls_path[n_ls_path == 1 ? 0 : c];
+  for (double& r : q) r *= r;
+  auto run = [&](auto t) {
+    using T = decltype(t);
+    KernelCall<T> kc;
+    if (int rc; (rc = kc.points(A, na, B, nb_, d, lengthscale, n_ls)) || (rc = kc.sides(ga, gb, true, q.data())) ||
+        (rc = kc.output(grad ? d : 1, false)))
+      return rc;
+    if (grad)
+      launch_kgrad_build_g<T>(kernel, kc.As, kc.ga, na, kc.napad, kc.Bs, kc.gb, nb_, kc.nbpad, d, sf2, kc.ls, n_ls, kc.q, sg2, 0,
+                              kc.K, kc.ld, kc.st);
+    else
+      launch_kbuild_cross_g<T>(kernel, kc.As, kc.ga, na, kc.napad, kc.Bs, kc.gb, nb_, kc.nbpad, d, sf2, kc.q, sg2, kc.K, kc.ld,
+                               kc.st);
+    return kc.fetch(K);
+  };
+  return dtype == GPX_F32 ? run(float()) : run(double());
+}
+
+// the two MFMA probes: D (16 x 16) from A, B (64 entries each), in one buffer of 64 + 64 + 256 elements
+template <typename T>
+int mfma_probe_t(const T* A, const T* B, T* D, void (*launch)(const T*, const T*, T*, hipStream_t)) {
+  if (!A || !B || !D) return GPX_E_ARG;
+  Scratch sc;
+  if (!sc.ok) return GPX_E_HIP;
+  Dev<T> d;
+  if (int rc = d.upload(A, 64, sc.st, 64 + 64 + 256)) return rc;
+  UCHK(hipMemcpyAsync(d + 64, B, 64 * sizeof(T), hipMemcpyHostToDevice, sc.st));
+  launch(d, d + 64, d + 128, sc.st);
+  UCHK(hipMemcpyAsync(D, d + 128, 256 * sizeof(T), hipMemcpyDeviceToHost, sc.st));
+  return sc.finish();
+}
 }  // namespace
+}  // extern "C++"
 
 int gpx_kernel_matrix(int32_t kernel, const double* A, int64_t na, const double* B, int64_t nb_,
                       int32_t d, const double* lengthscale, int32_t n_ls, double sf2,
                       double diag_add, double* K) try {
-  if (!A || !K || !lengthscale || na <= 0 || d <= 0 || d > MAX_D || (n_ls != 1 && n_ls != d))
-    return GPX_E_ARG;
-  if (!cov::known(kernel)) return GPX_E_ARG;
-  const bool sym = (B == nullptr);
-  const int64_t nbb = sym ? na : nb_;
-  if (nbb <= 0) return GPX_E_ARG;
-  Scratch sc;
-  if (!sc.ok) return GPX_E_HIP;
-  hipStream_t st = sc.h.st;
-  const int64_t napad = round_up(na, 64), nbpad = round_up(nbb, 64), ld = nbpad;
-  double *dA = nullptr, *dB = nullptr, *dAs = nullptr, *dBs = nullptr, *dls = nullptr, *dK = nullptr;
-  std::vector<double> host((size_t)napad * ld);
-  int rc = GPX_OK;
-  TCHK(hipMalloc(&dA, (size_t)na * d * 8));
-  TCHK(hipMalloc(&dAs, (size_t)napad * d * 8));
-  TCHK(hipMalloc(&dls, MAX_D * 8));
-  TCHK(hipMalloc(&dK, (size_t)napad * ld * 8));
-  TCHK(hipMemcpyAsync(dA, A, (size_t)na * d * 8, hipMemcpyHostToDevice, st));
-  TCHK(hipMemcpyAsync(dls, lengthscale, (size_t)n_ls * 8, hipMemcpyHostToDevice, st));
-  TCHK(hipMemsetAsync(dK, 0, (size_t)napad * ld * 8, st));
-  launch_scale_points(dA, na, napad, d, dls, n_ls, dAs, st);
-  if (sym) {
-    launch_kbuild_sym(kernel, dAs, na, napad, d, sf2, diag_add, dK, ld, st);
-  } else {
-    TCHK(hipMalloc(&dB, (size_t)nbb * d * 8));
-    TCHK(hipMalloc(&dBs, (size_t)nbpad * d * 8));
-    TCHK(hipMemcpyAsync(dB, B, (size_t)nbb * d * 8, hipMemcpyHostToDevice, st));
-    launch_scale_points(dB, nbb, nbpad, d, dls, n_ls, dBs, st);
-    launch_kbuild_cross(kernel, dAs, na, napad, dBs, nbb, nbpad, d, sf2, dK, ld, st);
-  }
-  TCHK(hipMemcpyAsync(host.data(), dK, (size_t)napad * ld * 8, hipMemcpyDeviceToHost, st));
-  TCHK(hipStreamSynchronize(st));
-  TCHK(hipGetLastError());
-  for (int64_t i = 0; i < na; ++i)
-    memcpy(K + i * nbb, host.data() + i * ld, (size_t)nbb * 8);  // sym: upper part is zero (not built)
-done:
-  for (double* p : {dA, dB, dAs, dBs, dls, dK})
-    if (p) (void)hipFree(p);
-  return rc;
+  if (!A || !K || !lengthscale || !sizes_ok(na, B ? nb_ : na, d, n_ls) || !cov::known(kernel)) return GPX_E_ARG;
+  KernelCall<double> kc;
+  if (int rc; (rc = kc.points(A, na, B, nb_, d, lengthscale, n_ls)) || (rc = kc.output(1, true))) return rc;
+  if (B)
+    launch_kbuild_cross<double>(kernel, kc.As, na, kc.napad, kc.Bs, nb_, kc.nbpad, d, sf2, kc.K, kc.ld, kc.st);
+  else  // (the upper part is not built: it stays zero)
+    launch_kbuild_sym<double>(kernel, kc.As, na, kc.napad, d, sf2, diag_add, kc.K, kc.ld, kc.st);
+  return kc.fetch(K);
 }
 GPX_CATCH_ALL
 
@@ -3894,118 +3993,20 @@ int gpx_kernel_grad_matrix(int32_t kernel, const double* A, int64_t na, const do
 
 int gpx_kernel_deriv_matrix(int32_t kernel, const double* A, int64_t na, const double* B, int64_t nb_, int32_t d,
                             const double* lengthscale, int32_t n_ls, double sf2, double* G) try {
-  if (!A || !B || !G || !lengthscale || na <= 0 || nb_ <= 0 || d <= 0 || d > MAX_D || (n_ls != 1 && n_ls != d))
-    return GPX_E_ARG;
-  if (!cov::known(kernel)) return GPX_E_ARG;
-  if (!cov::differentiable(kernel)) return fail(nullptr, GPX_E_UNSUPPORTED, "gpx_kernel_deriv_matrix: " MATERN12_NO_GRAD);
-  Scratch sc;
-  if (!sc.ok) return GPX_E_HIP;
-  hipStream_t st = sc.h.st;
-  const int64_t napad = round_up(na, 64), nbpad = round_up(nb_, 64), ld = nbpad;
-  double *dA = nullptr, *dB = nullptr, *dAs = nullptr, *dBs = nullptr, *dls = nullptr, *dG = nullptr;
-  std::vector<double> host((size_t)d * napad * ld);
-  int rc = GPX_OK;
-  TCHK(hipMalloc(&dA, (size_t)na * d * 8));
-  TCHK(hipMalloc(&dB, (size_t)nb_ * d * 8));
-  TCHK(hipMalloc(&dAs, (size_t)napad * d * 8));
-  TCHK(hipMalloc(&dBs, (size_t)nbpad * d * 8));
-  TCHK(hipMalloc(&dls, MAX_D * 8));
-  TCHK(hipMalloc(&dG, (size_t)d * napad * ld * 8));
-  TCHK(hipMemcpyAsync(dA, A, (size_t)na * d * 8, hipMemcpyHostToDevice, st));
-  TCHK(hipMemcpyAsync(dB, B, (size_t)nb_ * d * 8, hipMemcpyHostToDevice, st));
-  TCHK(hipMemcpyAsync(dls, lengthscale, (size_t)n_ls * 8, hipMemcpyHostToDevice, st));
-  launch_scale_points(dA, na, napad, d, dls, n_ls, dAs, st);
-  launch_scale_points(dB, nb_, nbpad, d, dls, n_ls, dBs, st);
-  launch_kgrad_build(kernel, (const double*)dAs, na, napad, (const double*)dBs, nb_, nbpad, d, sf2, dls, n_ls, 0, dG, ld,
-                     st);
-  TCHK(hipMemcpyAsync(host.data(), dG, (size_t)d * napad * ld * 8, hipMemcpyDeviceToHost, st));
-  TCHK(hipStreamSynchronize(st));
-  TCHK(hipGetLastError());
-  for (int32_t j = 0; j < d; ++j)
-    for (int64_t i = 0; i < na; ++i)
-      memcpy(G + ((int64_t)j * na + i) * nb_, host.data() + ((int64_t)j * napad + i) * ld, (size_t)nb_ * 8);
-done:
-  for (double* p : {dA, dB, dAs, dBs, dls, dG})
-    if (p) (void)hipFree(p);
-  return rc;
+  if (!A || !B || !G || !lengthscale || !sizes_ok(na, nb_, d, n_ls) || !cov::known(kernel)) return GPX_E_ARG;
+  if (!cov::differentiable(kernel)) return fail(nullptr, GPX_E_UNSUPPORTED, "gpx_kernel_deriv_matrix", MATERN12_NO_GRAD);
+  KernelCall<double> kc;
+  if (int rc; (rc = kc.points(A, na, B, nb_, d, lengthscale, n_ls)) || (rc = kc.output(d, false))) return rc;
+  launch_kgrad_build<double>(kernel, kc.As, na, kc.napad, kc.Bs, nb_, kc.nbpad, d, sf2, kc.ls, n_ls, 0, kc.K, kc.ld, kc.st);
+  return kc.fetch(G);
 }
 GPX_CATCH_ALL
-
-extern "C++" {
-namespace {
-// grad: K (d, na, nb) = the d derivative matrices by A (gpx_kernel_path_grad_matrix), else K (na, nb) (gpx_kernel_path_matrix)
-template <typename T>
-int kernel_path_matrix_t(int32_t kernel, const double* A, const int32_t* ga, int64_t na, const double* B, const int32_t* gb,
-                         int64_t nb_, int32_t d, const double* lengthscale, int32_t n_ls, double sf2, const double* ls_path,
-                         int32_t n_ls_path, double sg2, double* K, bool grad = false) {
-  Scratch sc;
-  if (!sc.ok) return GPX_E_HIP;
-  hipStream_t st = sc.h.st;
-  const int64_t napad = round_up(na, 64), nbpad = round_up(nb_, 64), ld = nbpad, nblk = grad ? d : 1;
-  T *dA = nullptr, *dB = nullptr, *dAs = nullptr, *dBs = nullptr, *dK = nullptr;
-  double *dls = nullptr, *dq = nullptr;
-  int32_t *dga = nullptr, *dgb = nullptr;
-  std::vector<T> hA(A, A + na * d), hB(B, B + nb_ * d), host((size_t)nblk * napad * ld);  // (rounded to T on the host)
-  std::vector<double> q((size_t)d);
-  for (int c = 0; c < d; ++c) {
-    const double r = lengthscale[n_ls == 1 ? 0 : c] / ls_path[n_ls_path == 1 ? 0 : c];
-    q[c] = r * r;
-  }
-  int rc = GPX_OK;
-  TCHK(hipMalloc(&dA, (size_t)na * d * sizeof(T)));
-  TCHK(hipMalloc(&dB, (size_t)nb_ * d * sizeof(T)));
-  TCHK(hipMalloc(&dAs, (size_t)napad * d * sizeof(T)));
-  TCHK(hipMalloc(&dBs, (size_t)nbpad * d * sizeof(T)));
-  TCHK(hipMalloc(&dls, MAX_D * 8));
-  TCHK(hipMalloc(&dq, MAX_D * 8));
-  TCHK(hipMalloc(&dga, (size_t)napad * 4));
-  TCHK(hipMalloc(&dgb, (size_t)nbpad * 4));
-  TCHK(hipMalloc(&dK, (size_t)nblk * napad * ld * sizeof(T)));
-  TCHK(hipMemcpyAsync(dA, hA.data(), (size_t)na * d * sizeof(T), hipMemcpyHostToDevice, st));
-  TCHK(hipMemcpyAsync(dB, hB.data(), (size_t)nb_ * d * sizeof(T), hipMemcpyHostToDevice, st));
-  TCHK(hipMemcpyAsync(dls, lengthscale, (size_t)n_ls * 8, hipMemcpyHostToDevice, st));
-  TCHK(hipMemcpyAsync(dq, q.data(), (size_t)d * 8, hipMemcpyHostToDevice, st));
-  TCHK(hipMemsetAsync(dga, 0xFF, (size_t)napad * 4, st));  // -1 beyond the valid ids
-  TCHK(hipMemsetAsync(dgb, 0xFF, (size_t)nbpad * 4, st));
-  TCHK(hipMemcpyAsync(dga, ga, (size_t)na * 4, hipMemcpyHostToDevice, st));
-  TCHK(hipMemcpyAsync(dgb, gb, (size_t)nb_ * 4, hipMemcpyHostToDevice, st));
-  launch_scale_points<T>(dA, na, napad, d, dls, n_ls, dAs, st);
-  launch_scale_points<T>(dB, nb_, nbpad, d, dls, n_ls, dBs, st);
-  if (grad)
-    launch_kgrad_build_g<T>(kernel, dAs, dga, na, napad, dBs, dgb, nb_, nbpad, d, sf2, dls, n_ls, dq, sg2, 0, dK, ld, st);
-  else
-    launch_kbuild_cross_g<T>(kernel, dAs, dga, na, napad, dBs, dgb, nb_, nbpad, d, sf2, dq, sg2, dK, ld, st);
-  TCHK(hipMemcpyAsync(host.data(), dK, (size_t)nblk * napad * ld * sizeof(T), hipMemcpyDeviceToHost, st));
-  TCHK(hipStreamSynchronize(st));
-  TCHK(hipGetLastError());
-  for (int64_t b = 0; b < nblk; ++b)
-    for (int64_t i = 0; i < na; ++i)
-      for (int64_t j = 0; j < nb_; ++j) K[(b * na + i) * nb_ + j] = (double)host[(size_t)(b * napad + i) * ld + j];
-done:
-  for (void* p : {(void*)dA, (void*)dB, (void*)dAs, (void*)dBs, (void*)dK, (void*)dls, (void*)dq, (void*)dga, (void*)dgb})
-    if (p) (void)hipFree(p);
-  return rc;
-}
-}  // namespace
-}  // extern "C++"
 
 int gpx_kernel_path_matrix(int32_t kernel, int32_t dtype, const double* A, const int32_t* ga, int64_t na, const double* B,
                            const int32_t* gb, int64_t nb_, int32_t d, const double* lengthscale, int32_t n_ls, double sf2,
                            const double* ls_path, int32_t n_ls_path, double sg2, double* K) try {
-  if (!A || !B || !ga || !gb || !K || !lengthscale || !ls_path || na <= 0 || nb_ <= 0 || d <= 0 || d > MAX_D ||
-      (n_ls != 1 && n_ls != d) || (n_ls_path != 1 && n_ls_path != d))
-    return GPX_E_ARG;
-  if (!cov::known(kernel) || (dtype != GPX_F64 && dtype != GPX_F32)) return GPX_E_ARG;
-  if (!(sg2 >= 0.0) || !std::isfinite(sg2)) return GPX_E_ARG;
-  for (int32_t c = 0; c < n_ls_path; ++c)
-    if (!(ls_path[c] > 0.0) || !std::isfinite(ls_path[c])) return GPX_E_ARG;
-  for (int64_t i = 0; i < na; ++i)
-    if (ga[i] < -1) return GPX_E_ARG;
-  for (int64_t i = 0; i < nb_; ++i)
-    if (gb[i] < -1) return GPX_E_ARG;
-  if (dtype == GPX_F32)
-    return kernel_path_matrix_t<float>(kernel, A, ga, na, B, gb, nb_, d, lengthscale, n_ls, sf2, ls_path, n_ls_path, sg2, K);
-  return kernel_path_matrix_t<double>(kernel, A, ga, na, B, gb, nb_, d, lengthscale, n_ls, sf2, ls_path, n_ls_path, sg2, K);
+  return kernel_path_entry("gpx_kernel_path_matrix", false, kernel, dtype, A, ga, na, B, gb, nb_, d, lengthscale, n_ls, sf2,
+                           ls_path, n_ls_path, sg2, K);
 }
 GPX_CATCH_ALL
 
@@ -4013,208 +4014,59 @@ int gpx_kernel_path_grad_matrix(int32_t kernel, int32_t dtype, const double* A, 
                                 const double* B, const int32_t* gb, int64_t nb_, int32_t d, const double* lengthscale,
                                 int32_t n_ls, double sf2, const double* ls_path, int32_t n_ls_path, double sg2,
                                 double* G) try {
-  if (!A || !B || !ga || !gb || !G || !lengthscale || !ls_path || na <= 0 || nb_ <= 0 || d <= 0 || d > MAX_D ||
-      (n_ls != 1 && n_ls != d) || (n_ls_path != 1 && n_ls_path != d))
-    return GPX_E_ARG;
-  if (!cov::known(kernel) || (dtype != GPX_F64 && dtype != GPX_F32)) return GPX_E_ARG;
-  if (!(sg2 >= 0.0) || !std::isfinite(sg2)) return GPX_E_ARG;
-  for (int32_t c = 0; c < n_ls_path; ++c)
-    if (!(ls_path[c] > 0.0) || !std::isfinite(ls_path[c])) return GPX_E_ARG;
-  for (int64_t i = 0; i < na; ++i)
-    if (ga[i] < -1) return GPX_E_ARG;
-  for (int64_t i = 0; i < nb_; ++i)
-    if (gb[i] < -1) return GPX_E_ARG;
-  if (!cov::differentiable(kernel)) return fail(nullptr, GPX_E_UNSUPPORTED, "gpx_kernel_path_grad_matrix: " MATERN12_NO_GRAD);
-  if (dtype == GPX_F32)
-    return kernel_path_matrix_t<float>(kernel, A, ga, na, B, gb, nb_, d, lengthscale, n_ls, sf2, ls_path, n_ls_path, sg2, G,
-                                       true);
-  return kernel_path_matrix_t<double>(kernel, A, ga, na, B, gb, nb_, d, lengthscale, n_ls, sf2, ls_path, n_ls_path, sg2, G,
-                                      true);
+  return kernel_path_entry("gpx_kernel_path_grad_matrix", true, kernel, dtype, A, ga, na, B, gb, nb_, d, lengthscale, n_ls, sf2,
+                           ls_path, n_ls_path, sg2, G);
 }
 GPX_CATCH_ALL
-
-extern "C++" {
-namespace {
-template <typename T>
-int kernel_mixed_matrix_t(int32_t kernel, const double* A, const int32_t* ka, int64_t na, const double* B, const int32_t* kb,
-                          int64_t nb_, int32_t d, const double* lengthscale, int32_t n_ls, double sf2, double* K) {
-  Scratch sc;
-  if (!sc.ok) return GPX_E_HIP;
-  hipStream_t st = sc.h.st;
-  const int64_t napad = round_up(na, 64), nbpad = round_up(nb_, 64), ld = nbpad;
-  T *dA = nullptr, *dB = nullptr, *dAs = nullptr, *dBs = nullptr, *dK = nullptr;
-  double* dls = nullptr;
-  int32_t *dka = nullptr, *dkb = nullptr;
-  std::vector<T> hA(A, A + na * d), hB(B, B + nb_ * d), host((size_t)napad * ld);  // (rounded to T on the host)
-  int rc = GPX_OK;
-  TCHK(hipMalloc(&dA, (size_t)na * d * sizeof(T)));
-  TCHK(hipMalloc(&dB, (size_t)nb_ * d * sizeof(T)));
-  TCHK(hipMalloc(&dAs, (size_t)napad * d * sizeof(T)));
-  TCHK(hipMalloc(&dBs, (size_t)nbpad * d * sizeof(T)));
-  TCHK(hipMalloc(&dls, MAX_D * 8));
-  TCHK(hipMalloc(&dka, (size_t)napad * 4));
-  TCHK(hipMalloc(&dkb, (size_t)nbpad * 4));
-  TCHK(hipMalloc(&dK, (size_t)napad * ld * sizeof(T)));
-  TCHK(hipMemcpyAsync(dA, hA.data(), (size_t)na * d * sizeof(T), hipMemcpyHostToDevice, st));
-  TCHK(hipMemcpyAsync(dB, hB.data(), (size_t)nb_ * d * sizeof(T), hipMemcpyHostToDevice, st));
-  TCHK(hipMemcpyAsync(dls, lengthscale, (size_t)n_ls * 8, hipMemcpyHostToDevice, st));
-  TCHK(hipMemsetAsync(dka, 0xFF, (size_t)napad * 4, st));  // -1 beyond the valid kinds, and for a side without any
-  TCHK(hipMemsetAsync(dkb, 0xFF, (size_t)nbpad * 4, st));
-  if (ka) TCHK(hipMemcpyAsync(dka, ka, (size_t)na * 4, hipMemcpyHostToDevice, st));
-  if (kb) TCHK(hipMemcpyAsync(dkb, kb, (size_t)nb_ * 4, hipMemcpyHostToDevice, st));
-  launch_scale_points<T>(dA, na, napad, d, dls, n_ls, dAs, st);
-  launch_scale_points<T>(dB, nb_, nbpad, d, dls, n_ls, dBs, st);
-  if (cov::differentiable(kernel))
-    launch_kbuild_cross_kk<T>(kernel, dAs, dka, na, napad, dBs, dkb, nb_, nbpad, d, sf2, dls, n_ls, dK, ld, st);
-  else  // (Matern-1/2: values only, and the fit builds them with the plain builder)
-    launch_kbuild_cross<T>(kernel, dAs, na, napad, dBs, nb_, nbpad, d, sf2, dK, ld, st);
-  TCHK(hipMemcpyAsync(host.data(), dK, (size_t)napad * ld * sizeof(T), hipMemcpyDeviceToHost, st));
-  TCHK(hipStreamSynchronize(st));
-  TCHK(hipGetLastError());
-  for (int64_t i = 0; i < na; ++i)
-    for (int64_t j = 0; j < nb_; ++j) K[i * nb_ + j] = (double)host[(size_t)i * ld + j];
-done:
-  for (void* p : {(void*)dA, (void*)dB, (void*)dAs, (void*)dBs, (void*)dK, (void*)dls, (void*)dka, (void*)dkb})
-    if (p) (void)hipFree(p);
-  return rc;
-}
-}  // namespace
-}  // extern "C++"
 
 int gpx_kernel_mixed_matrix(int32_t kernel, int32_t dtype, const double* A, const int32_t* ka, int64_t na, const double* B,
                             const int32_t* kb, int64_t nb_, int32_t d, const double* lengthscale, int32_t n_ls, double sf2,
                             double* K) try {
-  if (!A || !B || !K || !lengthscale || na <= 0 || nb_ <= 0 || d <= 0 || d > MAX_D || (n_ls != 1 && n_ls != d))
-    return GPX_E_ARG;
-  if (!cov::known(kernel) || (dtype != GPX_F64 && dtype != GPX_F32)) return GPX_E_ARG;
-  bool deriv = false;
-  for (int64_t i = 0; ka && i < na; ++i) {
-    if (ka[i] < -1 || ka[i] >= d) return GPX_E_ARG;
-    deriv |= ka[i] >= 0;
-  }
-  for (int64_t j = 0; kb && j < nb_; ++j) {
-    if (kb[j] < -1 || kb[j] >= d) return GPX_E_ARG;
-    deriv |= kb[j] >= 0;
-  }
-  if (deriv && !cov::differentiable(kernel))
-    return fail(nullptr, GPX_E_UNSUPPORTED, "gpx_kernel_mixed_matrix: " MATERN12_NO_GRAD);
-  if (dtype == GPX_F32) return kernel_mixed_matrix_t<float>(kernel, A, ka, na, B, kb, nb_, d, lengthscale, n_ls, sf2, K);
-  return kernel_mixed_matrix_t<double>(kernel, A, ka, na, B, kb, nb_, d, lengthscale, n_ls, sf2, K);
+  if (!A || !B || !K || !lengthscale || !sizes_ok(na, nb_, d, n_ls)) return GPX_E_ARG;
+  if (!cov::known(kernel) || !unit_dtype_ok(dtype)) return GPX_E_ARG;
+  if (int rc = kinds_refused("gpx_kernel_mixed_matrix", kernel, ka, na, kb, nb_, d)) return rc;
+  auto run = [&](auto t) {
+    using T = decltype(t);
+    KernelCall<T> kc;
+    if (int rc; (rc = kc.points(A, na, B, nb_, d, lengthscale, n_ls)) || (rc = kc.sides(ka, kb, true)) || (rc = kc.output(1, false)))
+      return rc;
+    if (cov::differentiable(kernel))
+      launch_kbuild_cross_kk<T>(kernel, kc.As, kc.ga, na, kc.napad, kc.Bs, kc.gb, nb_, kc.nbpad, d, sf2, kc.ls, n_ls, kc.K,
+                                kc.ld, kc.st);
+    else  // (Matern-1/2: values only, and the fit builds them with the plain builder)
+      launch_kbuild_cross<T>(kernel, kc.As, na, kc.napad, kc.Bs, nb_, kc.nbpad, d, sf2, kc.K, kc.ld, kc.st);
+    return kc.fetch(K);
+  };
+  return dtype == GPX_F32 ? run(float()) : run(double());
 }
 GPX_CATCH_ALL
 
 int gpx_kernel_dl_matrix(int32_t kernel, const double* A, const int32_t* ka, int64_t na, const double* B,
                          const int32_t* kb, int64_t nb_, int32_t d, const double* lengthscale, int32_t n_ls, double sf2,
                          double* G) try {
-  if (!A || !B || !G || !lengthscale || na <= 0 || nb_ <= 0 || d <= 0 || d > MAX_D || (n_ls != 1 && n_ls != d))
-    return GPX_E_ARG;
-  if (!cov::known(kernel)) return GPX_E_ARG;
-  bool deriv = false;
-  for (int64_t i = 0; ka && i < na; ++i) {
-    if (ka[i] < -1 || ka[i] >= d) return GPX_E_ARG;
-    deriv |= ka[i] >= 0;
-  }
-  for (int64_t j = 0; kb && j < nb_; ++j) {
-    if (kb[j] < -1 || kb[j] >= d) return GPX_E_ARG;
-    deriv |= kb[j] >= 0;
-  }
-  if (deriv && !cov::differentiable(kernel))
-    return fail(nullptr, GPX_E_UNSUPPORTED, "gpx_kernel_dl_matrix: " MATERN12_NO_GRAD);
-  Scratch sc;
-  if (!sc.ok) return GPX_E_HIP;
-  hipStream_t st = sc.h.st;
-  const int64_t napad = round_up(na, 64), nbpad = round_up(nb_, 64), ld = nbpad;
-  double *dA = nullptr, *dB = nullptr, *dAs = nullptr, *dBs = nullptr, *dls = nullptr, *dG = nullptr;
-  int32_t *dka = nullptr, *dkb = nullptr;
-  std::vector<double> host((size_t)n_ls * napad * ld);
-  int rc = GPX_OK;
-  TCHK(hipMalloc(&dA, (size_t)na * d * 8));
-  TCHK(hipMalloc(&dB, (size_t)nb_ * d * 8));
-  TCHK(hipMalloc(&dAs, (size_t)napad * d * 8));
-  TCHK(hipMalloc(&dBs, (size_t)nbpad * d * 8));
-  TCHK(hipMalloc(&dls, MAX_D * 8));
-  TCHK(hipMalloc(&dG, (size_t)n_ls * napad * ld * 8));
-  TCHK(hipMemcpyAsync(dA, A, (size_t)na * d * 8, hipMemcpyHostToDevice, st));
-  TCHK(hipMemcpyAsync(dB, B, (size_t)nb_ * d * 8, hipMemcpyHostToDevice, st));
-  TCHK(hipMemcpyAsync(dls, lengthscale, (size_t)n_ls * 8, hipMemcpyHostToDevice, st));
-  if (ka) {
-    TCHK(hipMalloc(&dka, (size_t)na * sizeof(int32_t)));
-    TCHK(hipMemcpyAsync(dka, ka, (size_t)na * sizeof(int32_t), hipMemcpyHostToDevice, st));
-  }
-  if (kb) {
-    TCHK(hipMalloc(&dkb, (size_t)nb_ * sizeof(int32_t)));
-    TCHK(hipMemcpyAsync(dkb, kb, (size_t)nb_ * sizeof(int32_t), hipMemcpyHostToDevice, st));
-  }
-  TCHK(hipMemsetAsync(dG, 0, (size_t)n_ls * napad * ld * 8, st));
-  launch_scale_points(dA, na, napad, d, dls, n_ls, dAs, st);
-  launch_scale_points(dB, nb_, nbpad, d, dls, n_ls, dBs, st);
-  launch_dl_matrix(kernel, dAs, dka, na, napad, dBs, dkb, nb_, d, dls, n_ls, sf2, dG, ld, st);
-  TCHK(hipMemcpyAsync(host.data(), dG, (size_t)n_ls * napad * ld * 8, hipMemcpyDeviceToHost, st));
-  TCHK(hipStreamSynchronize(st));
-  TCHK(hipGetLastError());
-  for (int32_t c = 0; c < n_ls; ++c)
-    for (int64_t i = 0; i < na; ++i)
-      memcpy(G + ((int64_t)c * na + i) * nb_, host.data() + ((int64_t)c * napad + i) * ld, (size_t)nb_ * 8);
-done:
-  for (void* p : {(void*)dA, (void*)dB, (void*)dAs, (void*)dBs, (void*)dls, (void*)dG, (void*)dka, (void*)dkb})
-    if (p) (void)hipFree(p);
-  return rc;
+  if (!A || !B || !G || !lengthscale || !sizes_ok(na, nb_, d, n_ls) || !cov::known(kernel)) return GPX_E_ARG;
+  if (int rc = kinds_refused("gpx_kernel_dl_matrix", kernel, ka, na, kb, nb_, d)) return rc;
+  KernelCall<double> kc;
+  if (int rc; (rc = kc.points(A, na, B, nb_, d, lengthscale, n_ls)) || (rc = kc.sides(ka, kb, false)) || (rc = kc.output(n_ls, true)))
+    return rc;
+  launch_dl_matrix(kernel, kc.As, kc.ga, na, kc.napad, kc.Bs, kc.gb, nb_, d, kc.ls, n_ls, sf2, kc.K, kc.ld, kc.st);
+  return kc.fetch(G);
 }
 GPX_CATCH_ALL
 
 int gpx_kernel_path_dtheta_matrix(int32_t kernel, const double* A, const int32_t* ga, int64_t na, const double* B,
                                   const int32_t* gb, int64_t nb_, int32_t d, const double* ls_path, int32_t n_ls_path,
                                   double sg2, double* G) try {
-  if (!A || !B || !ga || !gb || !G || !ls_path || na <= 0 || nb_ <= 0 || d <= 0 || d > MAX_D ||
-      (n_ls_path != 1 && n_ls_path != d))
-    return GPX_E_ARG;
-  if (!cov::known(kernel)) return GPX_E_ARG;
-  if (!(sg2 >= 0.0) || !std::isfinite(sg2)) return GPX_E_ARG;
-  for (int32_t c = 0; c < n_ls_path; ++c)
-    if (!(ls_path[c] > 0.0) || !std::isfinite(ls_path[c])) return GPX_E_ARG;
-  for (int64_t i = 0; i < na; ++i)
-    if (ga[i] < -1) return GPX_E_ARG;
-  for (int64_t i = 0; i < nb_; ++i)
-    if (gb[i] < -1) return GPX_E_ARG;
-  Scratch sc;
-  if (!sc.ok) return GPX_E_HIP;
-  hipStream_t st = sc.h.st;
+  if (!A || !B || !ga || !gb || !G || !ls_path || !sizes_ok(na, nb_, d, n_ls_path)) return GPX_E_ARG;
+  if (!cov::known(kernel) || !path_args_ok(ga, na, gb, nb_, ls_path, n_ls_path, sg2)) return GPX_E_ARG;
   // the points are scaled by l_path itself, so q = 1: r_p^2 = sum_c ((x_ic - x_jc) / l_path,c)^2 as in a fit with l = l_path
-  const int64_t napad = round_up(na, 64), nbpad = round_up(nb_, 64), ld = nbpad;
-  const int nt = 1 + n_ls_path;
-  double *dA = nullptr, *dB = nullptr, *dAs = nullptr, *dBs = nullptr, *dls = nullptr, *dq = nullptr, *dG = nullptr;
-  int32_t *dga = nullptr, *dgb = nullptr;
-  std::vector<double> host((size_t)nt * napad * ld), q((size_t)d, 1.0);
-  int rc = GPX_OK;
-  TCHK(hipMalloc(&dA, (size_t)na * d * 8));
-  TCHK(hipMalloc(&dB, (size_t)nb_ * d * 8));
-  TCHK(hipMalloc(&dAs, (size_t)napad * d * 8));
-  TCHK(hipMalloc(&dBs, (size_t)nbpad * d * 8));
-  TCHK(hipMalloc(&dls, MAX_D * 8));
-  TCHK(hipMalloc(&dq, MAX_D * 8));
-  TCHK(hipMalloc(&dga, (size_t)na * sizeof(int32_t)));
-  TCHK(hipMalloc(&dgb, (size_t)nb_ * sizeof(int32_t)));
-  TCHK(hipMalloc(&dG, (size_t)nt * napad * ld * 8));
-  TCHK(hipMemcpyAsync(dA, A, (size_t)na * d * 8, hipMemcpyHostToDevice, st));
-  TCHK(hipMemcpyAsync(dB, B, (size_t)nb_ * d * 8, hipMemcpyHostToDevice, st));
-  TCHK(hipMemcpyAsync(dls, ls_path, (size_t)n_ls_path * 8, hipMemcpyHostToDevice, st));
-  TCHK(hipMemcpyAsync(dq, q.data(), (size_t)d * 8, hipMemcpyHostToDevice, st));
-  TCHK(hipMemcpyAsync(dga, ga, (size_t)na * sizeof(int32_t), hipMemcpyHostToDevice, st));
-  TCHK(hipMemcpyAsync(dgb, gb, (size_t)nb_ * sizeof(int32_t), hipMemcpyHostToDevice, st));
-  TCHK(hipMemsetAsync(dG, 0, (size_t)nt * napad * ld * 8, st));
-  launch_scale_points(dA, na, napad, d, dls, n_ls_path, dAs, st);
-  launch_scale_points(dB, nb_, nbpad, d, dls, n_ls_path, dBs, st);
-  launch_path_dtheta_matrix(kernel, dAs, dga, na, napad, dBs, dgb, nb_, d, dq, n_ls_path, sg2, dG, ld, st);
-  TCHK(hipMemcpyAsync(host.data(), dG, (size_t)nt * napad * ld * 8, hipMemcpyDeviceToHost, st));
-  TCHK(hipStreamSynchronize(st));
-  TCHK(hipGetLastError());
-  for (int32_t t = 0; t < nt; ++t)
-    for (int64_t i = 0; i < na; ++i)
-      memcpy(G + ((int64_t)t * na + i) * nb_, host.data() + ((int64_t)t * napad + i) * ld, (size_t)nb_ * 8);
-done:
-  for (void* p : {(void*)dA, (void*)dB, (void*)dAs, (void*)dBs, (void*)dls, (void*)dq, (void*)dG, (void*)dga, (void*)dgb})
-    if (p) (void)hipFree(p);
-  return rc;
+  KernelCall<double> kc;
+  const std::vector<double> q((size_t)d, 1.0);
+  if (int rc; (rc = kc.points(A, na, B, nb_, d, ls_path, n_ls_path)) || (rc = kc.sides(ga, gb, false, q.data())) ||
+      (rc = kc.output(1 + n_ls_path, true)))
+    return rc;
+  launch_path_dtheta_matrix(kernel, kc.As, kc.ga, na, kc.napad, kc.Bs, kc.gb, nb_, d, kc.q, n_ls_path, sg2, kc.K, kc.ld, kc.st);
+  return kc.fetch(G);
 }
 GPX_CATCH_ALL
 
@@ -4224,45 +4076,27 @@ int gpx_potrf(double* A, int64_t n, int32_t block, int64_t* info) try {
   if (nb % 128 != 0 || nb < 128) return GPX_E_ARG;
   Scratch sc;
   if (!sc.ok) return GPX_E_HIP;
-  hipStream_t st = sc.h.st;
   const int64_t ld = n + LD_SKEW, ldp = nb + LD_SKEW;
-  double *dA = nullptr, *dW = nullptr, *dP = nullptr, *dWb = nullptr, *dUb = nullptr;
-  int* dInfo = nullptr;
-  int hinfo = INT_MAX;
-  int rc = GPX_OK;
-  InvWork<double> iw;
-  TCHK(hipMalloc(&dA, (size_t)n * ld * 8));
-  TCHK(hipMalloc(&dW, (size_t)(n / 64) * 4096 * 8));
-  TCHK(hipMalloc(&dP, (size_t)2 * n * ldp * 8));
-  TCHK(hipMalloc(&dInfo, 64));
-  TCHK(hipMalloc(&dWb, (size_t)((n + nb - 1) / nb) * nb * nb * 8));
-  TCHK(hipMalloc(&dUb, (size_t)nb * ldp * 8));
-  iw.W = dWb;
-  iw.U = dUb;
-  iw.ldu = ldp;
-  iw.nbw = nb;
-  iw.aux = sc.h.st3;
-  if ((rc = flag_handover_probe(&sc.h))) {
-    g_create_error = sc.h.err;
-    goto done;
-  }
-  TCHK(hipMemcpy2DAsync(dA, (size_t)ld * 8, A, (size_t)n * 8, (size_t)n * 8, (size_t)n, hipMemcpyHostToDevice, st));
-  TCHK(hipMemcpyAsync(dInfo, &hinfo, sizeof(int), hipMemcpyHostToDevice, st));
-  if ((rc = chol_enqueue(&sc.h, dA, ld, n, nb, dW, dP, dP + n * ldp, ldp, dInfo, 0, false, 0, &iw))) goto done;
-  TCHK(hipMemcpy2DAsync(A, (size_t)n * 8, dA, (size_t)ld * 8, (size_t)n * 8, (size_t)n, hipMemcpyDeviceToHost, st));
-  TCHK(hipMemcpyAsync(&hinfo, dInfo, sizeof(int), hipMemcpyDeviceToHost, st));
-  TCHK(hipStreamSynchronize(st));
-  TCHK(hipGetLastError());
-  if (hinfo < 0) {
-    g_create_error = "a stream parked on a device flag timed out (kernels serialised across streams? set GPX_CHAIN_FLAG=0)";
-    rc = GPX_E_HIP;
-    goto done;
-  }
+  Dev<double> dA, dW, dP, dWb, dUb;
+  Dev<int> dInfo;
+  int hinfo = INT_MAX, rc;
+  if ((rc = dA.alloc((size_t)n * ld)) || (rc = dW.alloc((size_t)(n / 64) * 4096)) || (rc = dP.alloc((size_t)2 * n * ldp)) ||
+      (rc = dInfo.alloc(16)) || (rc = dWb.alloc((size_t)((n + nb - 1) / nb) * nb * nb)) || (rc = dUb.alloc((size_t)nb * ldp)))
+    return rc;
+  InvWork<double> iw{dWb, dUb, ldp, nb, sc.h.st3};  // W, U, ldu, nbw, aux
+  if ((rc = flag_handover_probe(&sc.h))) return fail(nullptr, rc, sc.h.err.c_str());
+  UCHK(hipMemcpy2DAsync(dA, (size_t)ld * 8, A, (size_t)n * 8, (size_t)n * 8, (size_t)n, hipMemcpyHostToDevice, sc.st));
+  UCHK(hipMemcpyAsync(dInfo, &hinfo, sizeof(int), hipMemcpyHostToDevice, sc.st));
+  if ((rc = chol_enqueue(&sc.h, (double*)dA, ld, n, nb, (double*)dW, (double*)dP, dP + n * ldp, ldp, dInfo, 0, false, 0, &iw)))
+    return rc;
+  UCHK(hipMemcpy2DAsync(A, (size_t)n * 8, dA, (size_t)ld * 8, (size_t)n * 8, (size_t)n, hipMemcpyDeviceToHost, sc.st));
+  UCHK(hipMemcpyAsync(&hinfo, dInfo, sizeof(int), hipMemcpyDeviceToHost, sc.st));
+  if ((rc = sc.finish())) return rc;
+  if (hinfo < 0)
+    return fail(nullptr, GPX_E_HIP,
+                "a stream parked on a device flag timed out (kernels serialised across streams? set GPX_CHAIN_FLAG=0)");
   *info = (hinfo == INT_MAX) ? 0 : hinfo;
-done:
-  for (void* p : {(void*)dA, (void*)dW, (void*)dP, (void*)dInfo, (void*)dWb, (void*)dUb})
-    if (p) (void)hipFree(p);
-  return rc;
+  return GPX_OK;
 }
 GPX_CATCH_ALL
 
@@ -4270,49 +4104,35 @@ int gpx_trsm(double* X, int64_t m, const double* L, int64_t nb) try {
   if (!X || !L || m <= 0 || nb <= 0 || m % 64 != 0 || nb % 64 != 0) return GPX_E_ARG;
   Scratch sc;
   if (!sc.ok) return GPX_E_HIP;
-  hipStream_t st = sc.h.st;
   const int64_t ldx = nb + LD_SKEW, ldl = nb + LD_SKEW;
-  double *dX = nullptr, *dL = nullptr, *dL2 = nullptr, *dW = nullptr;
-  int* dInfo = nullptr;
-  int hinfo = INT_MAX;
-  int rc = GPX_OK;
-  TCHK(hipMalloc(&dX, (size_t)m * ldx * 8));
-  TCHK(hipMalloc(&dL, (size_t)nb * ldl * 8));
-  TCHK(hipMalloc(&dL2, (size_t)nb * ldl * 8));
-  TCHK(hipMalloc(&dW, (size_t)(nb / 64) * 4096 * 8));
-  TCHK(hipMalloc(&dInfo, 64));
-  TCHK(hipMemcpy2DAsync(dX, (size_t)ldx * 8, X, (size_t)nb * 8, (size_t)nb * 8, (size_t)m, hipMemcpyHostToDevice, st));
-  TCHK(hipMemcpy2DAsync(dL, (size_t)ldl * 8, L, (size_t)nb * 8, (size_t)nb * 8, (size_t)nb, hipMemcpyHostToDevice, st));
-  TCHK(hipMemcpyAsync(dInfo, &hinfo, sizeof(int), hipMemcpyHostToDevice, st));
+  Dev<double> dX, dL, dL2, dW;
+  Dev<int> dInfo;
+  int hinfo = INT_MAX, rc;
+  if ((rc = dX.alloc((size_t)m * ldx)) || (rc = dL.alloc((size_t)nb * ldl)) || (rc = dL2.alloc((size_t)nb * ldl)) ||
+      (rc = dW.alloc((size_t)(nb / 64) * 4096)) || (rc = dInfo.alloc(16)))
+    return rc;
+  UCHK(hipMemcpy2DAsync(dX, (size_t)ldx * 8, X, (size_t)nb * 8, (size_t)nb * 8, (size_t)m, hipMemcpyHostToDevice, sc.st));
+  UCHK(hipMemcpy2DAsync(dL, (size_t)ldl * 8, L, (size_t)nb * 8, (size_t)nb * 8, (size_t)nb, hipMemcpyHostToDevice, sc.st));
+  UCHK(hipMemcpyAsync(dInfo, &hinfo, sizeof(int), hipMemcpyHostToDevice, sc.st));
   // inverse diagonal blocks of the GIVEN factor: potf2 of (L_qq L_qq^T) reproduces L_qq up to
   // rounding, so build them from a scratch copy of the products instead.
-  {
-    std::vector<double> G((size_t)nb / 64 * 4096);
-    for (int64_t q = 0; q < nb / 64; ++q)
-      for (int i = 0; i < 64; ++i)
-        for (int j = 0; j < 64; ++j) {
-          double s = 0.0;
-          for (int t = 0; t <= std::min(i, j); ++t)
-            s += L[(q * 64 + i) * nb + q * 64 + t] * L[(q * 64 + j) * nb + q * 64 + t];
-          G[(size_t)q * 4096 + i * 64 + j] = s;
-        }
-    TCHK(hipMemcpyAsync(dL2, G.data(), G.size() * 8, hipMemcpyHostToDevice, st));
-    TCHK(hipStreamSynchronize(st));
-  }
+  std::vector<double> G((size_t)nb / 64 * 4096);
   for (int64_t q = 0; q < nb / 64; ++q)
-    launch_potf2_64(dL2 + q * 4096, 64, dW + q * 4096, q * 64, dInfo, st);
-  launch_trsm_rlt<double>(dX, ldx, m, dL, ldl, dW, (int)nb, nullptr, 0, st);
-  if (take_launch_error()) {
-    rc = GPX_E_ARG;
-    goto done;
-  }
-  TCHK(hipMemcpy2DAsync(X, (size_t)nb * 8, dX, (size_t)ldx * 8, (size_t)nb * 8, (size_t)m, hipMemcpyDeviceToHost, st));
-  TCHK(hipStreamSynchronize(st));
-  TCHK(hipGetLastError());
-done:
-  for (void* p : {(void*)dX, (void*)dL, (void*)dL2, (void*)dW, (void*)dInfo})
-    if (p) (void)hipFree(p);
-  return rc;
+    for (int i = 0; i < 64; ++i)
+      for (int j = 0; j < 64; ++j) {
+        double s = 0.0;
+        for (int t = 0; t <= std::min(i, j); ++t)
+          s += L[(q * 64 + i) * nb + q * 64 + t] * L[(q * 64 + j) * nb + q * 64 + t];
+        G[(size_t)q * 4096 + i * 64 + j] = s;
+      }
+  UCHK(hipMemcpyAsync(dL2, G.data(), G.size() * 8, hipMemcpyHostToDevice, sc.st));
+  UCHK(hipStreamSynchronize(sc.st));
+  for (int64_t q = 0; q < nb / 64; ++q)
+    launch_potf2_64<double>(dL2 + q * 4096, 64, dW + q * 4096, q * 64, dInfo, sc.st);
+  launch_trsm_rlt<double>(dX, ldx, m, dL, ldl, dW, (int)nb, nullptr, 0, sc.st);
+  if (take_launch_error()) return GPX_E_ARG;
+  UCHK(hipMemcpy2DAsync(X, (size_t)nb * 8, dX, (size_t)ldx * 8, (size_t)nb * 8, (size_t)m, hipMemcpyDeviceToHost, sc.st));
+  return sc.finish();
 }
 GPX_CATCH_ALL
 
@@ -4322,95 +4142,41 @@ int gpx_gemm_nt(double* C, int64_t m, int64_t n, const double* A, const double* 
   if (lower && m != n) return GPX_E_ARG;
   Scratch sc;
   if (!sc.ok) return GPX_E_HIP;
-  hipStream_t st = sc.h.st;
   const int64_t ldc = n + LD_SKEW, lda = k + LD_SKEW;
   const int tile = (m % 128 == 0 && n % 128 == 0) ? 128 : 64;
-  double *dC = nullptr, *dA = nullptr, *dB = nullptr;
-  int rc = GPX_OK;
-  TCHK(hipMalloc(&dC, (size_t)m * ldc * 8));
-  TCHK(hipMalloc(&dA, (size_t)m * lda * 8));
-  TCHK(hipMalloc(&dB, (size_t)n * lda * 8));
-  TCHK(hipMemcpy2DAsync(dC, (size_t)ldc * 8, C, (size_t)n * 8, (size_t)n * 8, (size_t)m, hipMemcpyHostToDevice, st));
-  TCHK(hipMemcpy2DAsync(dA, (size_t)lda * 8, A, (size_t)k * 8, (size_t)k * 8, (size_t)m, hipMemcpyHostToDevice, st));
-  TCHK(hipMemcpy2DAsync(dB, (size_t)lda * 8, B, (size_t)k * 8, (size_t)k * 8, (size_t)n, hipMemcpyHostToDevice, st));
-  launch_gemm_nt_fixed(tile, dC, ldc, dA, lda, dB, lda, m, n, k, lower, 0, st);
-  TCHK(hipMemcpy2DAsync(C, (size_t)n * 8, dC, (size_t)ldc * 8, (size_t)n * 8, (size_t)m, hipMemcpyDeviceToHost, st));
-  TCHK(hipStreamSynchronize(st));
-  TCHK(hipGetLastError());
-done:
-  for (double* p : {dC, dA, dB})
-    if (p) (void)hipFree(p);
-  return rc;
+  Dev<double> dC, dA, dB;
+  if (int rc; (rc = dC.alloc((size_t)m * ldc)) || (rc = dA.alloc((size_t)m * lda)) || (rc = dB.alloc((size_t)n * lda))) return rc;
+  UCHK(hipMemcpy2DAsync(dC, (size_t)ldc * 8, C, (size_t)n * 8, (size_t)n * 8, (size_t)m, hipMemcpyHostToDevice, sc.st));
+  UCHK(hipMemcpy2DAsync(dA, (size_t)lda * 8, A, (size_t)k * 8, (size_t)k * 8, (size_t)m, hipMemcpyHostToDevice, sc.st));
+  UCHK(hipMemcpy2DAsync(dB, (size_t)lda * 8, B, (size_t)k * 8, (size_t)k * 8, (size_t)n, hipMemcpyHostToDevice, sc.st));
+  launch_gemm_nt_fixed<double>(tile, dC, ldc, dA, lda, dB, lda, m, n, k, lower, 0, sc.st);
+  UCHK(hipMemcpy2DAsync(C, (size_t)n * 8, dC, (size_t)ldc * 8, (size_t)n * 8, (size_t)m, hipMemcpyDeviceToHost, sc.st));
+  return sc.finish();
 }
 GPX_CATCH_ALL
 
-int gpx_mfma_probe(const double* A, const double* B, double* D) try {
-  if (!A || !B || !D) return GPX_E_ARG;
-  Scratch sc;
-  if (!sc.ok) return GPX_E_HIP;
-  hipStream_t st = sc.h.st;
-  double* d = nullptr;
-  int rc = GPX_OK;
-  TCHK(hipMalloc(&d, (64 + 64 + 256) * 8));
-  TCHK(hipMemcpyAsync(d, A, 64 * 8, hipMemcpyHostToDevice, st));
-  TCHK(hipMemcpyAsync(d + 64, B, 64 * 8, hipMemcpyHostToDevice, st));
-  launch_mfma_probe(d, d + 64, d + 128, st);
-  TCHK(hipMemcpyAsync(D, d + 128, 256 * 8, hipMemcpyDeviceToHost, st));
-  TCHK(hipStreamSynchronize(st));
-  TCHK(hipGetLastError());
-done:
-  if (d) (void)hipFree(d);
-  return rc;
-}
+int gpx_mfma_probe(const double* A, const double* B, double* D) try { return mfma_probe_t(A, B, D, launch_mfma_probe); }
+GPX_CATCH_ALL
+
+int gpx_mfma_probe_f32(const float* A, const float* B, float* D) try { return mfma_probe_t(A, B, D, launch_mfma_probe_f32); }
 GPX_CATCH_ALL
 
 int gpx_path_distance(const double* paths, int64_t P, const double* cents, int64_t C, int32_t L,
                       double* D, int32_t mem_kind) try {
   if (!paths || !cents || !D || P <= 0 || C <= 0 || L <= 0 || L > 64) return GPX_E_ARG;
-  if (mem_kind != GPX_MEM_HOST && mem_kind != GPX_MEM_DEVICE) return GPX_E_ARG;
+  if (bad_mem_kind(mem_kind)) return GPX_E_ARG;
   Scratch sc;
   if (!sc.ok) return GPX_E_HIP;
-  hipStream_t st = sc.h.st;
   const bool host = mem_kind == GPX_MEM_HOST;
-  double *dp = nullptr, *dc = nullptr, *dD = nullptr;
-  int rc = GPX_OK;
-  TCHK(hipMalloc(&dc, (size_t)C * L * 16));
-  TCHK(hipMemcpyAsync(dc, cents, (size_t)C * L * 16, host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, st));
-  if (host) {
-    TCHK(hipMalloc(&dp, (size_t)P * L * 16));
-    TCHK(hipMalloc(&dD, (size_t)P * C * 8));
-    TCHK(hipMemcpyAsync(dp, paths, (size_t)P * L * 16, hipMemcpyHostToDevice, st));
-  }
+  Dev<double> dp, dc, dD;
+  if (int rc = dc.alloc((size_t)C * L * 2)) return rc;
+  UCHK(hipMemcpyAsync(dc, cents, (size_t)C * L * 16, host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, sc.st));
+  if (int rc; host && ((rc = dp.upload(paths, (size_t)P * L * 2, sc.st)) || (rc = dD.alloc((size_t)P * C)))) return rc;
   for (int64_t c0 = 0; c0 < C; c0 += 64)
     launch_path_distance(host ? dp : paths, P, dc + c0 * L * 2, (int)std::min<int64_t>(64, C - c0), L,
-                         (host ? dD : D) + c0, C, st);
-  if (host) TCHK(hipMemcpyAsync(D, dD, (size_t)P * C * 8, hipMemcpyDeviceToHost, st));
-  TCHK(hipStreamSynchronize(st));
-  TCHK(hipGetLastError());
-done:
-  for (double* p : {dp, dc, dD})
-    if (p) (void)hipFree(p);
-  return rc;
-}
-GPX_CATCH_ALL
-
-int gpx_mfma_probe_f32(const float* A, const float* B, float* D) try {
-  if (!A || !B || !D) return GPX_E_ARG;
-  Scratch sc;
-  if (!sc.ok) return GPX_E_HIP;
-  hipStream_t st = sc.h.st;
-  float* d = nullptr;
-  int rc = GPX_OK;
-  TCHK(hipMalloc(&d, (64 + 64 + 256) * 4));
-  TCHK(hipMemcpyAsync(d, A, 64 * 4, hipMemcpyHostToDevice, st));
-  TCHK(hipMemcpyAsync(d + 64, B, 64 * 4, hipMemcpyHostToDevice, st));
-  launch_mfma_probe_f32(d, d + 64, d + 128, st);
-  TCHK(hipMemcpyAsync(D, d + 128, 256 * 4, hipMemcpyDeviceToHost, st));
-  TCHK(hipStreamSynchronize(st));
-  TCHK(hipGetLastError());
-done:
-  if (d) (void)hipFree(d);
-  return rc;
+                         (host ? dD : D) + c0, C, sc.st);
+  if (host) UCHK(hipMemcpyAsync(D, dD, (size_t)P * C * 8, hipMemcpyDeviceToHost, sc.st));
+  return sc.finish();
 }
 GPX_CATCH_ALL
 
@@ -4421,33 +4187,23 @@ template <typename T>
 int gemm_bench_t(int64_t n, int64_t k, int32_t lower, int32_t mode, int32_t iters, double* ms) {
   Scratch sc;
   if (!sc.ok) return GPX_E_HIP;
-  hipStream_t st = sc.h.st;
   const int64_t ldc = n + ld_skew<T>(), lda = k + ld_skew<T>();
-  T *dC = nullptr, *dA = nullptr;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
+  Dev<T> dC, dA;
   float t = 0.f;
-  int rc = GPX_OK;
-  TCHK(hipMalloc(&dC, (size_t)n * ldc * sizeof(T)));
-  TCHK(hipMalloc(&dA, (size_t)2 * n * lda * sizeof(T)));
-  TCHK(hipMemsetAsync(dC, 0, (size_t)n * ldc * sizeof(T), st));
-  TCHK(hipMemsetAsync(dA, 0, (size_t)2 * n * lda * sizeof(T), st));
-  TCHK(hipEventCreate(&e0));
-  TCHK(hipEventCreate(&e1));
-  launch_gemm_nt_fixed<T>(128, dC, ldc, dA, lda, dA + n * lda, lda, n, n, k, lower, mode, st);
-  TCHK(hipEventRecord(e0, st));
+  if (int rc; (rc = dC.alloc((size_t)n * ldc)) || (rc = dA.alloc((size_t)2 * n * lda))) return rc;
+  UCHK(hipMemsetAsync(dC, 0, (size_t)n * ldc * sizeof(T), sc.st));
+  UCHK(hipMemsetAsync(dA, 0, (size_t)2 * n * lda * sizeof(T), sc.st));
+  hipEvent_t e0 = next_event(&sc.h), e1 = next_event(&sc.h);  // (the Scratch handle's pool destroys them)
+  if (!e0 || !e1) return fail(nullptr, GPX_E_HIP, "hipEventCreate failed");
+  launch_gemm_nt_fixed<T>(128, dC, ldc, dA, lda, dA + n * lda, lda, n, n, k, lower, mode, sc.st);
+  UCHK(hipEventRecord(e0, sc.st));
   for (int i = 0; i < iters; ++i)
-    launch_gemm_nt_fixed<T>(128, dC, ldc, dA, lda, dA + n * lda, lda, n, n, k, lower, mode, st);
-  TCHK(hipEventRecord(e1, st));
-  TCHK(hipStreamSynchronize(st));
-  TCHK(hipGetLastError());
-  TCHK(hipEventElapsedTime(&t, e0, e1));
+    launch_gemm_nt_fixed<T>(128, dC, ldc, dA, lda, dA + n * lda, lda, n, n, k, lower, mode, sc.st);
+  UCHK(hipEventRecord(e1, sc.st));
+  if (int rc = sc.finish()) return rc;
+  UCHK(hipEventElapsedTime(&t, e0, e1));
   *ms = (double)t / iters;
-done:
-  if (e0) (void)hipEventDestroy(e0);
-  if (e1) (void)hipEventDestroy(e1);
-  if (dC) (void)hipFree(dC);
-  if (dA) (void)hipFree(dA);
-  return rc;
+  return GPX_OK;
 }
 }  // extern "C++"
 
@@ -4521,9 +4277,7 @@ int gpx_microbench(double* mfma_tflops, double* copy_gbs) try {
   if (!mfma_tflops || !copy_gbs) return GPX_E_ARG;
   Scratch sc;
   if (!sc.ok) return GPX_E_HIP;
-  hipStream_t st = sc.h.st;
-  double *sink = nullptr, *src = nullptr, *dst = nullptr;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
+  Dev<double> sink, src, dst;
   const int64_t count = (int64_t)1 << 28;  // 2 GiB per buffer
   const int64_t skew = 0;  // (round 3: a skewed destination measured slower than an aligned one: tools/copy_bw.hip)
   // 65536 iterations, ~0.23 s: long enough to be past the clock ramp (a 14 ms loop read 75 TF, the sustained rate is
@@ -4531,34 +4285,26 @@ int gpx_microbench(double* mfma_tflops, double* copy_gbs) try {
   const int iters = sc.h.env.microbench_iters;
   const int blocks = 256 * 8;
   float ms = 0.f;
-  int rc = GPX_OK;
-  TCHK(hipMalloc(&sink, 64));
-  TCHK(hipMalloc(&src, (size_t)count * 8));
-  TCHK(hipMalloc(&dst, (size_t)(count + skew) * 8));
-  TCHK(hipEventCreate(&e0));
-  TCHK(hipEventCreate(&e1));
-  TCHK(hipMemsetAsync(src, 0x11, (size_t)count * 8, st));
-  launch_mfma_loop(sink, 64, blocks, st);  // warm-up
-  TCHK(hipEventRecord(e0, st));
-  launch_mfma_loop(sink, iters, blocks, st);
-  TCHK(hipEventRecord(e1, st));
-  TCHK(hipEventSynchronize(e1));
-  TCHK(hipEventElapsedTime(&ms, e0, e1));
+  if (int rc; (rc = sink.alloc(8)) || (rc = src.alloc((size_t)count)) || (rc = dst.alloc((size_t)(count + skew)))) return rc;
+  hipEvent_t e0 = next_event(&sc.h), e1 = next_event(&sc.h);  // (the Scratch handle's pool destroys them)
+  if (!e0 || !e1) return fail(nullptr, GPX_E_HIP, "hipEventCreate failed");
+  UCHK(hipMemsetAsync(src, 0x11, (size_t)count * 8, sc.st));
+  launch_mfma_loop(sink, 64, blocks, sc.st);  // warm-up
+  UCHK(hipEventRecord(e0, sc.st));
+  launch_mfma_loop(sink, iters, blocks, sc.st);
+  UCHK(hipEventRecord(e1, sc.st));
+  UCHK(hipEventSynchronize(e1));
+  UCHK(hipEventElapsedTime(&ms, e0, e1));
   *mfma_tflops = (double)blocks * 4 * (double)iters * 16 * 2048.0 / (ms * 1e-3) / 1e12;
-  for (int r = 0; r < 4; ++r) launch_copy(src, dst + skew, count, st);  // warm-up
-  TCHK(hipEventRecord(e0, st));
-  for (int r = 0; r < 20; ++r) launch_copy(src, dst + skew, count, st);
-  TCHK(hipEventRecord(e1, st));
-  TCHK(hipEventSynchronize(e1));
-  TCHK(hipEventElapsedTime(&ms, e0, e1));
+  for (int r = 0; r < 4; ++r) launch_copy(src, dst + skew, count, sc.st);  // warm-up
+  UCHK(hipEventRecord(e0, sc.st));
+  for (int r = 0; r < 20; ++r) launch_copy(src, dst + skew, count, sc.st);
+  UCHK(hipEventRecord(e1, sc.st));
+  UCHK(hipEventSynchronize(e1));
+  UCHK(hipEventElapsedTime(&ms, e0, e1));
   *copy_gbs = 20.0 * 2.0 * (double)count * 8.0 / (ms * 1e-3) / 1e9;
-  TCHK(hipGetLastError());
-done:
-  if (e0) (void)hipEventDestroy(e0);
-  if (e1) (void)hipEventDestroy(e1);
-  for (double* p : {sink, src, dst})
-    if (p) (void)hipFree(p);
-  return rc;
+  UCHK(hipGetLastError());
+  return GPX_OK;
 }
 GPX_CATCH_ALL
 
