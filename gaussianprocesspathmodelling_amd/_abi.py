@@ -12,6 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libgpx.so")
 ABI_VERSION = 6
 
+BASIS_IDS = {None: 0, "constant": 1, "linear": 2, "quadratic": 3}
 KERNEL_IDS = {"rbf": 0, "matern52": 1, "matern32": 2, "matern12": 3}
 DTYPE_IDS = {"float64": 0, "float32": 1, "mixed": 2}
 MEM_HOST, MEM_DEVICE = 0, 1
@@ -81,6 +82,8 @@ SIGNATURES = {
     "gpx_get_observation_kinds": (C.c_int, [_P, _P]),
     "gpx_set_path_groups": (C.c_int, [_P, _P, C.c_int64, C.c_double, _PD, C.c_int32, C.c_int32]),
     "gpx_get_path_groups": (C.c_int, [_P, _P]),
+    "gpx_set_basis": (C.c_int, [_P, C.c_int32]),
+    "gpx_get_basis": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _PD, _PD]),
     "gpx_forecast_blocks": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_double, _P, _P, _P, _P, C.c_int32,
                                       C.POINTER(C.c_int64)]),
     "gpx_kernel_path_matrix": (C.c_int, [C.c_int32, C.c_int32, _PD, C.POINTER(C.c_int32), C.c_int64, _PD,

@@ -4,6 +4,7 @@
 //   fit:     K = sf2 k(X,X) + (sn2+jitter) I  ->  blocked Cholesky (in place, lower)
 //            (with gpx_set_noise_weights: + diag(sn2 w_i + jitter) — DESIGN.md §3.4f)
 //            ->  alpha = L^-T L^-1 y  ->  logdet
+//            (with gpx_set_basis: H^T rides in the bordered rows beside y^T, then beta and z' = z - Z_H beta — DESIGN.md §3.4m)
 //   predict: K* = sf2 k(Xs,X) -> mean = K* alpha -> V^T = K* L^-T -> var = sf2 - rowsumsq(V^T)
 // The reference has no such path (GPmap.py has no fit/predict/linalg beyond
 // np.linalg.norm at GPmap.py:120); the arithmetic follows oracle/gp_oracle.py
@@ -126,6 +127,7 @@ struct gpx_handle {
     // block scoring (gpx_score_blocks, gpx_forecast_blocks): targets, per-slice Gram partials, batch mean^T, results + the bad-block word
     DevBuf SY, SPart, SMT, SOut;
     DevBuf SW;  // gpx_score_blocks_weighted: the query points' weights
+    DevBuf BG, BU;  // a fit with basis functions: per-slice Gram of the bordered rows; u = L_A^-1 (h - Z_H^T v*) per query row (rows x 64, fp64)
     DevBuf UW, UQ;  // gpx_remove_rows: per pass in flight (two) the carry ((N + 64) x UPD_W) and the panel's orthogonal factor (2 UPD_W square)
   } scr;
   // row-block shard (world > 1)
@@ -186,6 +188,12 @@ struct gpx_handle {
   double sg2 = 0.0;
   int n_lsp = 0;                    // the number of path lengthscales of the current fit (1 or d; grouped only)
   bool grouped = false;             // the current fit was built by the GROUPS builder (ids set, one >= 0, sg2 > 0)
+  // explicit basis functions (gpx_set_basis).  Nothing here is allocated, and no kernel of gpx_basis.hip
+  // is launched, while no basis is set.
+  int basis_set = 0;  // the basis of the next fits (GPX_BASIS_*; 0: none)
+  int basis = 0;      // the basis of the CURRENT fit and its number of functions p (0: a plain fit)
+  int bp = 0;
+  DevBuf Bst;         // the current fit's beta | L_A | A^-1 (fp64; gpx_internal.h: BASIS_STATE)
   // event pool
   std::vector<hipEvent_t> ev_pool;
   size_t ev_used = 0;
@@ -1075,7 +1083,10 @@ int begin_call(gpx_handle* h) {
 
 int begin_fit(gpx_handle* h) {  // ... of a call that replaces the fit
   const int rc = begin_call(h);
-  if (rc == GPX_OK) h->fitted = false;
+  if (rc == GPX_OK) {
+    h->fitted = false;
+    h->basis = h->bp = 0;  // (fit_impl decides; the other engines never fit with a basis: check_fit_basis)
+  }
   return rc;
 }
 
@@ -1168,6 +1179,11 @@ void bordered_mean_var(gpx_handle* h, const T* VT, int64_t rows, int64_t rows_pa
   if (want_var) {
     PhaseScope ps(h, &h->tm.var);
     launch_var_rows<T>(VT, h->ld, rows, h->Npad, h->sf2, (T*)h->var.p, h->st);
+  }
+  if (h->bp) {  // (single-device fits only; the query points of the fused predict sit in scr.Q)
+    PhaseScope ps(h, want_var ? &h->tm.var : &h->tm.mean);
+    launch_basis_epilogue<T>((const double*)h->Bst.p, h->bp, h->k, h->d, (const T*)h->scr.MT.p, ldm, (const T*)h->scr.Q.p, rows,
+                             (T*)h->meanout.p, want_var ? (T*)h->var.p : nullptr, nullptr, h->st);
   }
 }
 
@@ -1336,6 +1352,11 @@ int fit_impl(gpx_handle* h, const void* X, const void* y, int64_t N, int32_t d, 
   if ((rc = stage_fit_weights<T>(h, N, cap))) return rc;
   if ((rc = stage_fit_kinds<T>(h, N, cap, sn2, jitter))) return rc;
   if ((rc = stage_fit_groups<T>(h, N, cap, d, lengthscale, n_ls, sn2, jitter))) return rc;
+  const int bp = basis_count(h->basis_set, d);  // (k + bp <= 64 and N >= bp: check_fit_basis)
+  h->basis = h->basis_set;
+  h->bp = bp;
+  if (bp && (rc = ensure(h, h->Bst, (size_t)BASIS_STATE * 8))) return rc;
+  if (bp && (rc = ensure(h, h->scr.BG, (size_t)basis_gram_slices(Npad) * RHS_ROWS * RHS_ROWS * 8))) return rc;
   InvWork<T> iw;
   iw.W = (T*)h->Wblk.p;
   iw.U = (T*)h->Ublk.p;
@@ -1385,9 +1406,16 @@ int fit_impl(gpx_handle* h, const void* X, const void* y, int64_t N, int32_t d, 
     {
       PhaseScope ps(h, &tm.chol);
       launch_pack_rhs<T>((const T*)h->Y.p, N, k, dYT, ld, Npad, RHS_ROWS, h->st);
+      if (bp) launch_basis_rows<T>((const T*)h->X.p, N, Npad, d, k, bp, dYT, ld, h->st);  // rows [k, k + bp): H^T -> Z_H^T
       if ((rc = chol_enqueue<T>(h, dK, ld, Npad, h->nb, (T*)h->Winv.p, (T*)h->P.p,
                                 (T*)h->P.p + (Npad + NX) * ldp, ldp, dInfo, 0, profile, NX, &iw, Mpad)))
         return rc;
+    }
+    if (bp) {  // beta = (Z_H^T Z_H)^-1 Z_H^T z, then z' = z - Z_H beta in place: every reader of zT from here on sees z'
+      PhaseScope ps(h, &tm.solve);
+      launch_bordered_gram<T>(dYT, ld, Npad, (double*)h->scr.BG.p, h->st);
+      launch_beta_solve((const double*)h->scr.BG.p, Npad, k, bp, N, (double*)h->Bst.p, dInfo, h->st);
+      launch_basis_project<T>(dYT, ld, Npad, k, bp, (const double*)h->Bst.p, h->st);
     }
     // The forward substitution happened inside the factorisation (bordered rows).  The
     // back substitution alpha = L^-T z is NOT on the fit+predict path: the posterior mean is
@@ -1979,6 +2007,11 @@ int predict_core(gpx_handle* h, const void* Xq, int64_t M, bool want_var, int32_
     PhaseScope ps(h, &tm.mean);
     launch_unpack_rhs<T>((const T*)h->scr.MT.p, ldm, M, k, 1.0, (T*)h->meanout.p, h->st);
   }
+  if (h->bp) {  // + h^T beta, + |u|^2 (rows [k, k + bp) of MT are Z_H^T v* on the variance route)
+    PhaseScope ps(h, want_var ? &tm.var : &tm.mean);
+    launch_basis_epilogue<T>((const double*)h->Bst.p, h->bp, k, d, (const T*)h->scr.MT.p, ldm, (const T*)h->scr.Q.p, M,
+                             (T*)h->meanout.p, want_var ? (T*)h->var.p : nullptr, nullptr, h->st);
+  }
   return GPX_OK;
 }
 
@@ -2078,6 +2111,7 @@ int posterior_cov_core(gpx_handle* h, const void* Xq, int64_t M, int32_t mem_kin
   SolveWork<T> sw;  // dense block solves, as predict
   if ((rc = dense_solve_work<T>(h, h->scr.JTsol, Mpad, &sw))) return rc;
   if (gq && (rc = ensure(h, h->scr.Qz, (size_t)Mpad * sizeof(T)))) return rc;
+  if (h->bp && (rc = ensure(h, h->scr.BU, (size_t)M * RHS_ROWS * 8))) return rc;
   T* dVT = (T*)h->scr.JVT.p;
   T* dSig = (T*)h->scr.JSig.p;
   const int32_t* dg = nullptr;
@@ -2099,6 +2133,9 @@ int posterior_cov_core(gpx_handle* h, const void* Xq, int64_t M, int32_t mem_kin
     PhaseScope ps(h, &tm.mean);
     mean_product<T>(h, (T*)h->scr.MT.p, ldm, (const T*)h->zT, dVT, Mpad, (T*)h->scr.MTpart.p, ldm);
     launch_unpack_rhs<T>((const T*)h->scr.MT.p, ldm, M, k, 1.0, (T*)h->meanout.p, h->st);
+    if (h->bp)
+      launch_basis_epilogue<T>((const double*)h->Bst.p, h->bp, k, d, (const T*)h->scr.MT.p, ldm, (const T*)h->scr.Q.p, M,
+                               (T*)h->meanout.p, nullptr, (double*)h->scr.BU.p, h->st);
   }
   {  // Sigma = K(Xs, Xs) - (V^T)(V^T)^T: lower 64-tiles of the kernel (the block above the diagonal inside a 128-tile is
      // not built: zero it first), then one SYRK over the lower triangle
@@ -2112,6 +2149,7 @@ int posterior_cov_core(gpx_handle* h, const void* Xq, int64_t M, int32_t mem_kin
       launch_kbuild_sym<T>(h->cfg.kernel, (const T*)h->scr.Qs.p, M, Mpad, d, h->sf2, 0.0, dSig, lds, h->st);
     }
     launch_gemm_nt<T>(128, dSig, lds, dVT, ld, dVT, ld, Mpad, Mpad, Npad, 1, 0, h->st);
+    if (h->bp) launch_cov_add_uut<T>(dSig, lds, M, h->bp, (const double*)h->scr.BU.p, h->st);  // + U U^T (lower; mirrored later)
   }
   return GPX_OK;
 }
@@ -2303,6 +2341,8 @@ int score_impl(gpx_handle* h, const void* Xq, const void* yq, const void* wq, in
   if ((rc = ensure_mean_partials<T>(h, h->scr.MTpart, ldmb))) return rc;
   if ((rc = ensure(h, h->meanout, (size_t)M * k * sizeof(T)))) return rc;
   if ((rc = ensure(h, h->scr.SPart, (size_t)bpb * S * LP * LP * sizeof(double)))) return rc;
+  if (h->bp && (rc = ensure(h, h->scr.BU, (size_t)bpb * Lg * RHS_ROWS * 8))) return rc;
+  const double* dU = h->bp ? (const double*)h->scr.BU.p : nullptr;  // a batch's u rows, from its first row
   const size_t out_elems = fc ? (size_t)G * Lp * (k + Lp + 1) + (size_t)G * k : (size_t)G * (2 * k + 1);
   const size_t bad_off = round_up((int64_t)(out_elems * sizeof(T)), 16);
   DevBuf& outbuf = h->scr.SOut;
@@ -2349,6 +2389,9 @@ int score_impl(gpx_handle* h, const void* Xq, const void* yq, const void* wq, in
         PhaseScope ps(h, &tm.mean);
         mean_product<T>(h, dMT, ldmb, (const T*)h->zT, dVT, mp, (T*)h->scr.MTpart.p, ldmb);
         launch_unpack_rhs<T>(dMT, ldmb, mv, k, 1.0, (T*)h->meanout.p + m0 * k, h->st);
+        if (h->bp)
+          launch_basis_epilogue<T>((const double*)h->Bst.p, h->bp, k, d, dMT, ldmb, (const T*)h->scr.Q.p + m0 * d, mv,
+                                   (T*)h->meanout.p + m0 * k, nullptr, (double*)h->scr.BU.p, h->st);
       }
       {
         PhaseScope ps(h, &tm.var);
@@ -2356,11 +2399,12 @@ int score_impl(gpx_handle* h, const void* Xq, const void* yq, const void* wq, in
         if (fc)
           launch_block_forecast<T>(h->cfg.kernel, (const double*)h->scr.SPart.p, nb, Lo, Lp, Npad, dQs + m0 * d, d,
                                    (const T*)h->scr.SY.p + g0 * Lo * k, (const T*)h->meanout.p + m0 * k, k, h->sf2, sg2, dq,
-                                   diag_add, dFmean, dFcov, dFvar, dLogp, g0, dBad, h->st);
+                                   diag_add, dFmean, dFcov, dFvar, dLogp, g0, dBad, h->st, dU, h->bp);
         else
           launch_block_score<T>(h->cfg.kernel, (const double*)h->scr.SPart.p, nb, Lg, Npad, dQs + m0 * d, d,
                                 (const T*)h->scr.SY.p + m0 * k, (const T*)h->meanout.p + m0 * k, k, h->sf2, diag_add, dLogp,
-                                dMaha, dLogdet, g0, dBad, h->st, wq ? (const T*)h->scr.SW.p + m0 : nullptr, sg2, dq);
+                                dMaha, dLogdet, g0, dBad, h->st, wq ? (const T*)h->scr.SW.p + m0 : nullptr, sg2, dq, dU,
+                                h->bp);
       }
     }
     PhaseScope ps(h, &tm.d2h);
@@ -3136,6 +3180,43 @@ int check_fit_groups(gpx_handle* h, const char* fn, int64_t N, int32_t d) {
   return GPX_OK;
 }
 
+// a fit on a handle with a basis set (gpx_set_basis), before anything is computed or exchanged and with the previous fit
+// still valid: GPX_E_UNSUPPORTED where the basis steps do not run, GPX_E_ARG for a basis that does not fit the call
+int check_fit_basis(gpx_handle* h, const char* fn, int64_t N, int32_t d, int32_t k) {
+  if (!h->basis_set) return GPX_OK;
+  char buf[320];
+  const char* where = h->group ? "device groups" : (h->cfg.world > 1 || h->comm) ? "sharded handles"
+                      : h->cfg.dtype == GPX_MIXED ? "GPX_MIXED handles"
+                      : !h->kinds_set.empty() ? "handles that also have observation kinds set"
+                      : groups_effective(h) ? "handles that also have path ids set" : nullptr;
+  if (where) {
+    snprintf(buf, sizeof buf, "%s: basis functions are not supported on %s (single-device GPX_F64 / GPX_F32 handles with "
+             "plain or weighted observations only; clear the basis with gpx_set_basis(h, GPX_BASIS_NONE))", fn, where);
+    return fail(h, GPX_E_UNSUPPORTED, buf);
+  }
+  const int p = basis_count(h->basis_set, d);
+  if (k + p > RHS_ROWS) {
+    snprintf(buf, sizeof buf, "%s: k = %d target columns and p = %d basis functions need k + p <= 64 bordered rows", fn, (int)k,
+             p);
+    return fail(h, GPX_E_ARG, buf);
+  }
+  if (N < p) {
+    snprintf(buf, sizeof buf, "%s: %lld observations cannot determine p = %d basis coefficients (need N >= p)", fn,
+             (long long)N, p);
+    return fail(h, GPX_E_ARG, buf);
+  }
+  return GPX_OK;
+}
+
+// what a fit with basis functions refuses (`what`: the call's own reason), before anything is computed
+int basis_refused(gpx_handle* h, const char* fn, const char* what) {
+  if (!h->fitted || !h->bp) return GPX_OK;
+  char buf[320];
+  snprintf(buf, sizeof buf, "%s: the fit has basis functions (gpx_set_basis): %s", fn, what);
+  return fail(h, GPX_E_UNSUPPORTED, buf);
+}
+#define BASIS_NO_UPDATE "beta and the projected right-hand sides are not updated in place: fit the changed data instead"
+
 // gpx_fit on one handle, behind its argument checks and begin_fit
 int fit_begun(gpx_handle* h, const void* X, const void* y, int64_t N, int32_t d, int32_t k, const double* lengthscale,
               int32_t n_ls, double sf2, double sn2, double jitter, int32_t mem_kind, int64_t* info) {
@@ -3170,6 +3251,7 @@ int gpx_fit(gpx_handle* h, const void* X, const void* y, int64_t N, int32_t d, i
   if ((rc = check_fit_weights(h, "gpx_fit", N))) return rc;
   if ((rc = check_fit_kinds(h, "gpx_fit", N, d))) return rc;
   if ((rc = check_fit_groups(h, "gpx_fit", N, d))) return rc;
+  if ((rc = check_fit_basis(h, "gpx_fit", N, d, k))) return rc;
   if (h->group) return group_fit(h, X, y, N, d, k, lengthscale, n_ls, sf2, sn2, jitter, mem_kind, info);
   if ((rc = begin_fit(h))) return rc;
   return fit_begun(h, X, y, N, d, k, lengthscale, n_ls, sf2, sn2, jitter, mem_kind, info);
@@ -3187,6 +3269,7 @@ int gpx_fit_predict(gpx_handle* h, const void* X, const void* y, int64_t N, int3
   if ((rc = check_fit_weights(h, "gpx_fit_predict", N))) return rc;
   if ((rc = check_fit_kinds(h, "gpx_fit_predict", N, d))) return rc;
   if ((rc = check_fit_groups(h, "gpx_fit_predict", N, d))) return rc;
+  if ((rc = check_fit_basis(h, "gpx_fit_predict", N, d, k))) return rc;
   if (h->group) return group_fit_predict(h, X, y, N, d, k, lengthscale, n_ls, sf2, sn2, jitter, Xq, M, mean, var, mem_kind, info);
   // Shards (round 4): every rank's slice of the query points rides through the sharded factorisation as bordered rows of
   // its local row set (shard_fit with query points + shard_fused_tail) — in the split schedule, up to 8192 rows per rank.
@@ -3247,6 +3330,7 @@ int posterior_refused(gpx_handle* h, const char* fn) {
 int query_ids_refused(gpx_handle* h, const char* fn, const int32_t* gq, int64_t M, int32_t mem_kind) {
   if (!gq) return fail(h, GPX_E_ARG, fn, "bad argument");
   if (int rc = posterior_refused(h, fn)) return rc;
+  if (int rc = basis_refused(h, fn, "a basis together with path ids is not supported")) return rc;
   if (!h->grouped)
     return fail(h, GPX_E_UNSUPPORTED, fn,
                 "the current fit has no path ids (gpx_set_path_groups with an id >= 0 and sg2 > 0 before the fit)");
@@ -3277,6 +3361,8 @@ int posterior_begin(gpx_handle* h, const char* fn, bool paths, const int32_t* gq
   if (!h->fitted) return fail(h, GPX_E_ARG, fn, "handle has no successful fit");
   if (too_large) return fail(h, GPX_E_ARG, fn, too_large);
   if (gradient && !cov::differentiable(h->cfg.kernel)) return fail(h, GPX_E_UNSUPPORTED, fn, MATERN12_NO_GRAD);
+  if (gradient)
+    if (int rc = basis_refused(h, fn, "the posterior gradient does not include the basis terms yet")) return rc;
   const int rc = paths ? query_ids_refused(h, fn, gq, M, mem_kind) : posterior_refused(h, fn);
   return rc ? rc : begin_call(h);
 }
@@ -3406,6 +3492,7 @@ int append_entry(gpx_handle* h, const void* Xnew, const void* ynew, const void* 
   int rc;
   if ((rc = posterior_refused(h, "gpx_append"))) return rc;
   if (!h->fitted) return fail(h, GPX_E_ARG, "gpx_append: handle has no successful fit");
+  if ((rc = basis_refused(h, "gpx_append", BASIS_NO_UPDATE))) return rc;
   if (m > (int64_t)INT_MAX - 4096 - h->N) return fail(h, GPX_E_ARG, "gpx_append: N + m too large");
   if (h->has_deriv)
     return fail(h, GPX_E_UNSUPPORTED, "gpx_append: the fit has derivative observations (gpx_set_observation_kinds): fit the "
@@ -3450,6 +3537,7 @@ int gpx_remove_rows(gpx_handle* h, int64_t start, int64_t count, int64_t* info) 
   int rc;
   if ((rc = posterior_refused(h, "gpx_remove_rows"))) return rc;
   if (!h->fitted) return fail(h, GPX_E_ARG, "gpx_remove_rows: handle has no successful fit");
+  if ((rc = basis_refused(h, "gpx_remove_rows", BASIS_NO_UPDATE))) return rc;
   if (start < 0 || count < 0 || start > h->N || count > h->N - start)
     return fail(h, GPX_E_ARG, "gpx_remove_rows: rows [start, start + count) must lie inside the fit");
   if (count >= h->N) return fail(h, GPX_E_ARG, "gpx_remove_rows: a fit keeps at least one point");
@@ -3468,6 +3556,7 @@ int gpx_append_rows(gpx_handle* h, const void* Xnew, const void* ynew, const voi
   int rc;
   if ((rc = posterior_refused(h, "gpx_append_rows"))) return rc;
   if (!h->fitted) return fail(h, GPX_E_ARG, "gpx_append_rows: handle has no successful fit");
+  if ((rc = basis_refused(h, "gpx_append_rows", BASIS_NO_UPDATE))) return rc;
   if (m > (int64_t)INT_MAX - 4096 - h->N) return fail(h, GPX_E_ARG, "gpx_append_rows: N + m too large");
   // the kinds and the ids are checked in host copies (NULL: all -1), which also feed the fit's host vectors afterwards
   std::vector<int32_t> kinds((size_t)m, -1), ids((size_t)m, -1);
@@ -3536,6 +3625,34 @@ int gpx_set_noise_weights(gpx_handle* h, const void* w, int64_t n, int32_t mem_k
   if ((rc = copy_in(h, h->Wset.p, w, (size_t)n * es, mem_kind))) return rc;
   HIPCHK(h, hipStreamSynchronize(h->st));
   h->nw_set = n;
+  return GPX_OK;
+}
+GPX_CATCH_ALL
+
+int gpx_set_basis(gpx_handle* h, int32_t basis) try {
+  if (!h) return GPX_E_ARG;
+  if (basis < GPX_BASIS_NONE || basis > GPX_BASIS_QUADRATIC)
+    return fail(h, GPX_E_ARG, "gpx_set_basis: need GPX_BASIS_NONE, _CONSTANT, _LINEAR or _QUADRATIC");
+  h->basis_set = basis;
+  return GPX_OK;
+}
+GPX_CATCH_ALL
+
+int gpx_get_basis(gpx_handle* h, int32_t* basis, int32_t* p, double* beta, double* beta_cov) try {
+  if (!h) return GPX_E_ARG;
+  if (!h->fitted || !basis || !p) return fail(h, GPX_E_ARG, "gpx_get_basis: no fit or null output");
+  *basis = h->basis;
+  *p = h->bp;
+  if (!h->bp || (!beta && !beta_cov)) return GPX_OK;
+  HIPCHK(h, hipSetDevice(h->cfg.device));
+  std::vector<double> st((size_t)BASIS_STATE);
+  HIPCHK(h, hipMemcpyAsync(st.data(), h->Bst.p, st.size() * 8, hipMemcpyDeviceToHost, h->st));
+  HIPCHK(h, hipStreamSynchronize(h->st));
+  const int bp = h->bp, k = h->k;
+  for (int j = 0; j < bp; ++j) {  // the state block's rows are 64 wide (gpx_internal.h: BASIS_STATE)
+    if (beta) std::copy(&st[(size_t)j * 64], &st[(size_t)j * 64 + k], beta + (size_t)j * k);
+    if (beta_cov) std::copy(&st[2 * 4096 + (size_t)j * 64], &st[2 * 4096 + (size_t)j * 64 + bp], beta_cov + (size_t)j * bp);
+  }
   return GPX_OK;
 }
 GPX_CATCH_ALL

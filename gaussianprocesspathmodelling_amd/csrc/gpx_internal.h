@@ -412,7 +412,10 @@ template <typename T>
 void launch_block_score(int kernel, const double* part, int64_t nblk, int Lg, int64_t npad, const T* Qs, int d,
                         const T* ys, const T* mean, int k, double sf2, double diag_add, T* logp, T* maha, T* logdet,
                         int64_t g0, int* bad, hipStream_t st, const T* wq = nullptr,  // wq (nblk Lg), from the batch's first
-                        double sg2 = 0.0, const double* q = nullptr);                 // row: + diag_add wq[i] per point
+                        double sg2 = 0.0, const double* q = nullptr,                  // row: + diag_add wq[i] per point
+                        const double* U = nullptr, int pu = 0);
+// U != null (a fit with basis functions; (nblk Lg) x 64 fp64 from the batch's first row, launch_basis_epilogue's): S gains
+// u_i . u_j over pu entries, and `mean` already includes h^T beta; null: today's bits.  The same for launch_block_forecast.
 // sg2 > 0 (a fit with path ids): every block is a new path, S gains sg2 k(Qs_b, Qs_b; l_path); q (d, device) = (l_c / l_path,c)^2
 // Block b < nblk of a batch of gpx_forecast_blocks: Lo observed rows, then Lp rows to forecast (Lo + Lp <= 64); part as
 // above with Lg = Lo + Lp; Qs and mean ((Lo + Lp) rows per block) and yo (Lo rows per block) start at the batch's first
@@ -421,7 +424,36 @@ void launch_block_score(int kernel, const double* part, int64_t nblk, int Lg, in
 template <typename T>
 void launch_block_forecast(int kernel, const double* part, int64_t nblk, int Lo, int Lp, int64_t npad, const T* Qs, int d,
                            const T* yo, const T* mean, int k, double sf2, double sg2, const double* q, double diag_add,
-                           T* fmean, T* fcov, T* fvar, T* flogp, int64_t g0, int* bad, hipStream_t st);
+                           T* fmean, T* fcov, T* fvar, T* flogp, int64_t g0, int* bad, hipStream_t st,
+                           const double* U = nullptr, int pu = 0);
+
+// ---- explicit basis functions (gpx_basis.hip) -------------------------------------
+// basis 1 | 2 | 3 (include/gpx.h): h(x) = [1] | [1, x_c] | [1, x_c, x_c^2] of the RAW inputs, p = 1 | 1 + d | 1 + 2 d functions
+inline int basis_count(int basis, int d) { return basis == 1 ? 1 : basis == 2 ? 1 + d : basis == 3 ? 1 + 2 * d : 0; }
+// the handle's state block (fp64, on the device): beta[j * 64 + c] | L_A[i * 64 + j] (lower) | A^-1[i * 64 + j]
+constexpr int BASIS_STATE = 3 * 64 * 64;
+// rows [k, k + p) of the bordered block YT (ld) = H^T over the columns < n, zero up to npad; X (n x d) the raw points
+template <typename T>
+void launch_basis_rows(const T* X, int64_t n, int64_t npad, int d, int k, int p, T* YT, int64_t ld, hipStream_t st);
+// Column slices of the bordered rows' Gram: a function of npad ONLY, one fp64 partial per slice, summed in slice order
+int basis_gram_slices(int64_t npad);
+// part [basis_gram_slices(npad)][64][64] (fp64) = per-slice zT zT^T of the 64 bordered rows zT (ld) over the columns [0, npad)
+template <typename T>
+void launch_bordered_gram(const T* zT, int64_t ld, int64_t npad, double* part, hipStream_t st);
+// one workgroup: A = G[k:k+p, k:k+p], L_A = chol A, beta = A^-1 G[k:k+p, 0:k], A^-1 into `state`.  A pivot j (1-based) of A
+// that is not > 0 or not finite: atomicMin(info, n + j), state left as it was.
+void launch_beta_solve(const double* part, int64_t npad, int k, int p, int64_t n, double* state, int* info, hipStream_t st);
+// zT[c] -= sum_j beta[j][c] zT[k + j] for c < k over the columns [0, npad), formed in fp64 and rounded once
+template <typename T>
+void launch_basis_project(T* zT, int64_t ld, int64_t npad, int k, int p, const double* state, hipStream_t st);
+// Query point m < rows (raw points Q, rows x d): mean[m][c] += h^T beta_c; with var or U: u = L_A^-1 (h - MT[k .. k + p, m]),
+// var[m] += |u|^2 (var may be null), U[m * 64 + j] = u_j (U may be null).  Neither: MT is not read (the mean-only route).
+template <typename T>
+void launch_basis_epilogue(const double* state, int p, int k, int d, const T* MT, int64_t ldm, const T* Q, int64_t rows,
+                           T* mean, T* var, double* U, hipStream_t st);
+// lower triangle of Sig (M x M, lds) += U U^T, U (M x 64, fp64) as launch_basis_epilogue leaves it
+template <typename T>
+void launch_cov_add_uut(T* Sig, int64_t lds, int64_t M, int p, const double* U, hipStream_t st);
 
 // ---- removal of observations (gpx_update.hip) -----------------------------------
 constexpr int UPD_W = 64;  // panel width of the rank-m update of the trailing factor = most columns m one pass removes

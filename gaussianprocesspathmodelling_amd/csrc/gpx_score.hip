@@ -140,10 +140,12 @@ __device__ __forceinline__ double quad_sum(double v) {
 // Lower triangle of S (Lg x Lg, stride SLD) of the block whose first row is row0: sf2 k + [sg2 k(., .; l_path)] - Gram, the
 // partials summed in slice order; + diag_add (times wq[i] if given) on the diagonal of the rows i < nd.  sg2 > 0 (a fit with
 // path ids: the block is a new path) adds the within-path term from the scaled queries with q_c = (l_c / l_path,c)^2.
+// U != null (a fit with basis functions, gpx_basis.hip): + u_i . u_j over pu entries; null: the same bits as without it.
 template <typename T, int KERNEL>
 __device__ __forceinline__ void block_build_s(double* Sm, const double* pb, int S, int LP, const T* __restrict__ Qs,
                                               int64_t row0, int d, int Lg, int nd, double sf2, double sg2,
-                                              const double* __restrict__ q, double diag_add, const T* __restrict__ wq) {
+                                              const double* __restrict__ q, double diag_add, const T* __restrict__ wq,
+                                              const double* __restrict__ U, int pu) {
   for (int e = threadIdx.x; e < Lg * Lg; e += 256) {
     const int i = e / Lg, j = e - i * Lg;
     if (j > i) continue;
@@ -164,7 +166,13 @@ __device__ __forceinline__ void block_build_s(double* Sm, const double* pb, int 
       v += cov::value<KERNEL, double>(rp2, sg2);
     }
     if (i == j && i < nd) v += wq ? diag_add * (double)wq[row0 + i] : diag_add;  // per-point weight of the added diagonal
-    Sm[i * SLD + j] = v - gram;
+    v -= gram;
+    if (U) {  // a fit with basis functions: + u_i . u_j (U: 64 fp64 per query row, from the batch's first row)
+      double uu = 0.0;
+      for (int c = 0; c < pu; ++c) uu += U[(row0 + i) * 64 + c] * U[(row0 + j) * 64 + c];
+      v += uu;
+    }
+    Sm[i * SLD + j] = v;
   }
 }
 
@@ -222,13 +230,15 @@ __global__ __launch_bounds__(256) void block_score_kernel(const double* __restri
                                                          double diag_add, T* __restrict__ logp, T* __restrict__ maha,
                                                          T* __restrict__ logdet, int64_t g0, int* __restrict__ bad,
                                                          const T* __restrict__ wq, double sg2,
-                                                         const double* __restrict__ q) {
+                                                         const double* __restrict__ q, const double* __restrict__ U,
+                                                         int pu) {
   __shared__ double Sm[64 * SLD];  // S, then its Cholesky factor (lower)
   __shared__ double Wm[64 * SLD];  // residuals r (Lg x k), then L^-1 r
   __shared__ double piv;
   const int tid = threadIdx.x;
   const int64_t b = blockIdx.x, row0 = b * Lg;
-  block_build_s<T, KERNEL>(Sm, part + b * S * (int64_t)(LP * LP), S, LP, Qs, row0, d, Lg, Lg, sf2, sg2, q, diag_add, wq);
+  block_build_s<T, KERNEL>(Sm, part + b * S * (int64_t)(LP * LP), S, LP, Qs, row0, d, Lg, Lg, sf2, sg2, q, diag_add, wq, U,
+                           pu);
   for (int e = tid; e < Lg * k; e += 256) {
     const int i = e / k, c = e - i * k;
     Wm[i * SLD + c] = (double)ys[row0 * k + e] - (double)mean[row0 * k + e];
@@ -265,14 +275,15 @@ __global__ __launch_bounds__(256) void block_forecast_kernel(const double* __res
                                                             double sg2, const double* __restrict__ q, double diag_add,
                                                             T* __restrict__ fmean, T* __restrict__ fcov,
                                                             T* __restrict__ fvar, T* __restrict__ flogp, int64_t g0,
-                                                            int* __restrict__ bad) {
+                                                            int* __restrict__ bad, const double* __restrict__ U,
+                                                            int pu) {
   __shared__ double Sm[64 * SLD];  // S; then L_oo, B below it, S_pp
   __shared__ double Wm[64 * SLD];  // rows < Lo: yo - mean_o, then w; rows >= Lo: mean_p
   __shared__ double piv;
   const int tid = threadIdx.x, Lg = Lo + Lp;
   const int64_t b = blockIdx.x, row0 = b * Lg;
   block_build_s<T, KERNEL>(Sm, part + b * S * (int64_t)(LP * LP), S, LP, Qs, row0, d, Lg, Lo, sf2, sg2, q, diag_add,
-                           (const T*)nullptr);
+                           (const T*)nullptr, U, pu);
   for (int e = tid; e < Lg * k; e += 256) {
     const int i = e / k, c = e - i * k;
     const double m = (double)mean[row0 * k + e];
@@ -332,24 +343,26 @@ void launch_block_gram(const T* VT, int64_t ld, int64_t nblk, int Lg, int64_t np
 template <typename T>
 void launch_block_score(int kernel, const double* part, int64_t nblk, int Lg, int64_t npad, const T* Qs, int d,
                         const T* ys, const T* mean, int k, double sf2, double diag_add, T* logp, T* maha, T* logdet,
-                        int64_t g0, int* bad, hipStream_t st, const T* wq, double sg2, const double* q) {
+                        int64_t g0, int* bad, hipStream_t st, const T* wq, double sg2, const double* q, const double* U,
+                        int pu) {
   debug_delay(st);
   const int S = score_slices(npad), LP = score_lp(Lg);
   cov::dispatch(kernel, [&](auto fam) {
     hipLaunchKernelGGL((block_score_kernel<T, fam>), dim3((unsigned)nblk), dim3(256), 0, st, part, S, LP, Qs, d, ys, mean,
-                       k, Lg, sf2, diag_add, logp, maha, logdet, g0, bad, wq, sg2, q);
+                       k, Lg, sf2, diag_add, logp, maha, logdet, g0, bad, wq, sg2, q, U, pu);
   });
 }
 
 template <typename T>
 void launch_block_forecast(int kernel, const double* part, int64_t nblk, int Lo, int Lp, int64_t npad, const T* Qs, int d,
                            const T* yo, const T* mean, int k, double sf2, double sg2, const double* q, double diag_add,
-                           T* fmean, T* fcov, T* fvar, T* flogp, int64_t g0, int* bad, hipStream_t st) {
+                           T* fmean, T* fcov, T* fvar, T* flogp, int64_t g0, int* bad, hipStream_t st, const double* U,
+                           int pu) {
   debug_delay(st);
   const int S = score_slices(npad), LP = score_lp(Lo + Lp);
   cov::dispatch(kernel, [&](auto fam) {
     hipLaunchKernelGGL((block_forecast_kernel<T, fam>), dim3((unsigned)nblk), dim3(256), 0, st, part, S, LP, Qs, d, yo,
-                       mean, k, Lo, Lp, sf2, sg2, q, diag_add, fmean, fcov, fvar, flogp, g0, bad);
+                       mean, k, Lo, Lp, sf2, sg2, q, diag_add, fmean, fcov, fvar, flogp, g0, bad, U, pu);
   });
 }
 
@@ -357,10 +370,10 @@ void launch_block_forecast(int kernel, const double* part, int64_t nblk, int Lo,
   template void launch_block_gram<T>(const T*, int64_t, int64_t, int, int64_t, double*, hipStream_t);                 \
   template void launch_block_score<T>(int, const double*, int64_t, int, int64_t, const T*, int, const T*, const T*,  \
                                       int, double, double, T*, T*, T*, int64_t, int*, hipStream_t, const T*, double,  \
-                                      const double*);                                                                  \
+                                      const double*, const double*, int);                                              \
   template void launch_block_forecast<T>(int, const double*, int64_t, int, int, int64_t, const T*, int, const T*,      \
                                          const T*, int, double, double, const double*, double, T*, T*, T*, T*, int64_t, \
-                                         int*, hipStream_t);
+                                         int*, hipStream_t, const double*, int);
 GPX_INSTANTIATE_SCORE(double)
 GPX_INSTANTIATE_SCORE(float)
 

@@ -162,6 +162,8 @@ class GP:
         self._kinds_set = False    # gpx_set_observation_kinds holds kinds for the next fits
         self.derivative_noise = 0.0  # noise variance of the derivative rows of the last fit(derivatives=) (0 without any)
         self._groups_set = False   # gpx_set_path_groups holds path ids for the next fits
+        self._basis_set = None     # gpx_set_basis holds a basis for the next fits (None: none)
+        self._basis_fit = None     # the basis of the last successful fit
         self.path_variance = 0.0   # within-path variance sg2 of the last fit(path_ids=) (0 without any)
         self.path_lengthscale = None  # ... and its lengthscale(s) (None without path ids)
         self._n_path_ls = 1        # path lengthscales of the last fit: entries of lml_gradient(path=True) after path_variance
@@ -312,6 +314,60 @@ class GP:
         self.path_variance, self.path_lengthscale = float(variance), lsp.copy()
         self._n_path_ls = lsp.size if effective or lengthscale is not None else 1
 
+    @staticmethod
+    def _check_basis(basis):
+        if basis not in _abi.BASIS_IDS:
+            raise ValueError(f"unknown basis {basis!r}; expected None, 'constant', 'linear' or 'quadratic'")
+        return basis
+
+    def _set_basis(self, basis):
+        """the basis of the fits that follow (``gpx_set_basis``); None clears it"""
+        if basis == self._basis_set:
+            return  # (a model that never had a basis makes no call at all)
+        self._check(self._lib.gpx_set_basis(self._h, _abi.BASIS_IDS[basis]))
+        self._basis_set = basis
+
+    def _refusal_keeps_fit(self, basis, prev):
+        """-> a handler for the GpxError of a fit made with ``basis``: the library refuses such a fit (GPX_E_ARG,
+        GPX_E_UNSUPPORTED) before it touches anything, so the model of the fit before — ``prev``, the Python side of
+        it — is still the one the handle holds."""
+        def handler(e):
+            if basis is not None and e.code in (_abi.E_ARG, _abi.E_UNSUPPORTED):
+                (self._fitted, self._N, self._d, self._k, self._y1d, self._alpha) = prev
+        return handler
+
+    def _fit_state(self):
+        return (self._fitted, getattr(self, "_N", 0), getattr(self, "_d", 0), getattr(self, "_k", 0),
+                getattr(self, "_y1d", True), self._alpha)
+
+    def _get_basis(self):
+        if not self._fitted:
+            raise RuntimeError("no fit")
+        b, p = C.c_int32(0), C.c_int32(0)
+        self._check(self._lib.gpx_get_basis(self._h, C.byref(b), C.byref(p), None, None))
+        beta = np.empty((p.value, self._k), dtype=np.float64)
+        cov = np.empty((p.value, p.value), dtype=np.float64)
+        if p.value:
+            self._check(self._lib.gpx_get_basis(self._h, C.byref(b), C.byref(p), _abi.dptr(beta), _abi.dptr(cov)))
+        name = {v: k for k, v in _abi.BASIS_IDS.items()}[b.value]
+        return name, (beta[:, 0].copy() if self._y1d else beta), cov
+
+    @property
+    def basis_(self):
+        """Basis of the fitted model (``fit(..., basis=)``): None, "constant", "linear" or "quadratic"."""
+        return self._get_basis()[0]
+
+    @property
+    def beta_(self):
+        """Generalised-least-squares coefficients of the basis functions, (p, k) — (p,) for a 1-D ``y`` — in the order
+        ``[1, x_1..x_d, x_1^2..x_d^2]`` and in the units of the raw inputs; p = 0 for a fit without a basis."""
+        return self._get_basis()[1]
+
+    @property
+    def beta_cov_(self):
+        """Covariance (p, p) of ``beta_`` under the flat prior, ``(H^T K^-1 H)^-1``, shared by the k targets."""
+        return self._get_basis()[2]
+
     @property
     def path_ids_(self):
         """Path id of every observation of the fitted model (N,) int32; all -1 for a fit without path ids (or with
@@ -375,7 +431,7 @@ class GP:
 
     # -- API ----------------------------------------------------------------------------
     def fit(self, X, y, noise_weights=None, derivatives=None, derivative_noise=0.0, path_ids=None, path_variance=0.0,
-            path_lengthscale=None):
+            path_lengthscale=None, basis=None):
         """Factorise and solve.  ``noise_weights`` (N,), of the same kind as ``X`` (NumPy array or device tensor): the
         diagonal of K gets ``noise * w_i + jitter`` instead of ``noise + jitter``; None (the default) means none — also
         after a weighted fit.
@@ -400,12 +456,33 @@ class GP:
         ``path_variance``, ``path_lengthscale`` and ``path_ids_`` keep what the fit used.  ``path_variance=0`` or ids that
         are all -1 are the plain fit bit for bit; None (the default) means none — also after such a fit.  float64 /
         float32 on one device, not with ``derivatives``; :meth:`update` appends to such a fit when it is given the new
-        rows' ``path_ids``, and its gradient is ``lml_gradient(path=True)``."""
+        rows' ``path_ids``, and its gradient is ``lml_gradient(path=True)``.
+
+        ``basis`` = "constant", "linear" or "quadratic" gives the model an explicit mean ``h(x)^T beta`` with
+        ``h = [1]``, ``[1, x_1..x_d]`` or ``[1, x_1..x_d, x_1^2..x_d^2]`` of the raw inputs and the coefficients
+        marginalised under a flat prior (``gpx_set_basis``; Rasmussen & Williams §2.7): away from the data the mean
+        reverts to the fitted trend instead of 0, and the uncertainty of ``beta`` is part of every variance,
+        covariance, sample, block score and forecast.  ``basis_``, ``beta_`` and ``beta_cov_`` describe the fit;
+        ``alpha_`` is ``K^-1 (y - H beta)``; :meth:`log_marginal_likelihood` is then the PROFILE likelihood at
+        ``beta_`` and :meth:`lml_gradient` its exact gradient.  k + p <= 64 and N >= p (``GpxError`` otherwise, the
+        model as it was).  float64 / float32 on one device, with ``noise_weights`` if wanted, not with
+        ``derivatives`` or ``path_ids``; :meth:`update`, :meth:`remove`, :meth:`predict_gradient` and ``path_ids=``
+        queries raise ``GpxError`` on such a fit.  None (the default) means none — also after such a fit.
+        ``ValueError`` for any other value, before any library call."""
+        self._check_basis(basis)
         ids, pvar, plsp = check_path_args(path_ids, path_variance, path_lengthscale, derivatives=derivatives)
         X, y, noise_weights, kinds = self._with_derivatives(X, y, derivatives, noise_weights)
-        return self._fit_rows(X, y, noise_weights, kinds, derivative_noise, (ids, pvar, plsp))
+        return self._fit_rows(X, y, noise_weights, kinds, derivative_noise, (ids, pvar, plsp), basis)
 
-    def _fit_rows(self, X, y, noise_weights, kinds, derivative_noise, paths=(None, 0.0, None)):
+    def _not_pd(self, N):
+        """the message of a fit whose jitter escalations ran out: a pivot of K, or (info > N) of the basis' H^T K^-1 H"""
+        if self.info_ > N:
+            return (f"the basis functions are linearly dependent on this data (pivot {self.info_ - N} of H^T K^-1 H is "
+                    f"not positive) after {self.max_tries} jitter escalations")
+        return (f"kernel matrix not positive definite (first bad pivot {self.info_}) after "
+                f"{self.max_tries} jitter escalations")
+
+    def _fit_rows(self, X, y, noise_weights, kinds, derivative_noise, paths=(None, 0.0, None), basis=None):
         """:meth:`fit` of observation rows that are concatenated already, ``kinds`` (None: all values) theirs"""
         px, kx, keepx, devx, sx = self._as_input(X, "X")
         py, ky, keepy, devy, sy = self._as_input(y, "y")
@@ -426,7 +503,9 @@ class GP:
         self._set_noise_weights(noise_weights, N, kx)  # (refused: the model is as it was)
         self._set_observation_kinds(kinds, derivative_noise)
         self._set_path_groups(*paths)
+        self._set_basis(basis)
         self.derivative_noise = 0.0 if kinds is None else float(derivative_noise)
+        refused = self._refusal_keeps_fit(basis, self._fit_state())
         self._y1d = len(sy) == 1
         self._N, self._d, self._k = N, d, k
         self._alpha = None
@@ -437,17 +516,20 @@ class GP:
         for _ in range(max(1, self.max_tries)):
             rc = self._lib.gpx_fit(self._h, px, py, N, d, k, _abi.dptr(ls), ls.size, self.variance,
                                    self.noise, jitter, kx, C.byref(info))
-            self._check(rc)
+            try:
+                self._check(rc)
+            except _abi.GpxError as e:
+                refused(e)
+                raise
             self.info_ = int(info.value)
             if self.info_ == 0:
                 break
             jitter = max(jitter, 1e-12 * self.variance) * 10.0
         else:
-            raise np.linalg.LinAlgError(
-                f"kernel matrix not positive definite (first bad pivot {self.info_}) after "
-                f"{self.max_tries} jitter escalations")
+            raise np.linalg.LinAlgError(self._not_pd(N))
         self.jitter_used_ = jitter
         self._fitted = True
+        self._basis_fit = basis
         ld = C.c_double(0.0)
         self._check(self._lib.gpx_logdet(self._h, C.byref(ld)))
         self.log_det_ = float(ld.value)
@@ -631,7 +713,7 @@ class GP:
         return self
 
     def fit_predict(self, X, y, Xs, include_noise=False, noise_weights=None, derivatives=None, derivative_noise=0.0,
-                    path_ids=None, path_variance=0.0, path_lengthscale=None):
+                    path_ids=None, path_variance=0.0, path_lengthscale=None, basis=None):
         """``fit(X, y)`` and ``predict(Xs)`` (mean and variance) as ONE factorisation pass: the cross-kernel rows
         of the query points ride through the blocked Cholesky as bordered rows (``gpx_fit_predict``), so the
         variance solve is part of the trailing updates instead of a pass of its own — the small-N schedule
@@ -639,12 +721,15 @@ class GP:
         On a shard or a device group every rank's slice of the query points rides through ITS part of the sharded
         factorisation (collective: every rank of a shard makes the call).  ``dtype="mixed"`` takes the two calls.
         ``noise_weights``, ``derivatives``, ``derivative_noise`` and the ``path_*`` keywords as for :meth:`fit` (with
-        path ids the prediction is the posterior of the cluster mean ``f``); ``include_noise`` as for :meth:`predict`."""
+        path ids the prediction is the posterior of the cluster mean ``f``); ``basis`` as for :meth:`fit` too (the
+        coefficients are solved between the factorisation and the prediction); ``include_noise`` as for
+        :meth:`predict`."""
+        self._check_basis(basis)
         paths = check_path_args(path_ids, path_variance, path_lengthscale, derivatives=derivatives)
         X, y, noise_weights, kinds = self._with_derivatives(X, y, derivatives, noise_weights)
 
         def two_calls():
-            return self._fit_rows(X, y, noise_weights, kinds, derivative_noise, paths).predict(
+            return self._fit_rows(X, y, noise_weights, kinds, derivative_noise, paths, basis).predict(
                 Xs, include_noise=include_noise)
 
         fused = self.dtype in ("float64", "float32")
@@ -671,6 +756,8 @@ class GP:
         self._set_noise_weights(noise_weights, N, kx)
         self._set_observation_kinds(kinds, derivative_noise)
         self._set_path_groups(*paths)
+        self._set_basis(basis)
+        refused = self._refusal_keeps_fit(basis, self._fit_state())
         self._y1d = len(sy) == 1
         self._N, self._d, self._k = N, d, k
         self._alpha = None
@@ -692,22 +779,26 @@ class GP:
         for _ in range(max(1, self.max_tries)):
             rc = self._lib.gpx_fit_predict(self._h, px, py, N, d, k, _abi.dptr(ls), ls.size, self.variance, self.noise,
                                            jitter, pq, M, pm, pv, kx, C.byref(info))
-            if rc == _abi.E_NOMEM or (rc == _abi.E_UNSUPPORTED and kinds is None and paths[0] is None):
+            if rc == _abi.E_NOMEM or (rc == _abi.E_UNSUPPORTED and kinds is None and paths[0] is None
+                                      and basis is None):
                 # the library's own limits decide (its batch cap honours GPX_PRED_BATCH; M more bordered rows of K and
                 # of the panel buffers may not fit beside the factor): the documented fallback is the two calls
                 # (with kinds set, GPX_E_UNSUPPORTED is the refusal of the model itself: raised below)
                 return two_calls()
-            self._check(rc)
+            try:
+                self._check(rc)
+            except _abi.GpxError as e:
+                refused(e)
+                raise
             self.info_ = int(info.value)
             if self.info_ == 0:
                 break
             jitter = max(jitter, 1e-12 * self.variance) * 10.0
         else:
-            raise np.linalg.LinAlgError(
-                f"kernel matrix not positive definite (first bad pivot {self.info_}) after "
-                f"{self.max_tries} jitter escalations")
+            raise np.linalg.LinAlgError(self._not_pd(N))
         self.jitter_used_ = jitter
         self._fitted = True
+        self._basis_fit = basis
         ld = C.c_double(0.0)
         self._check(self._lib.gpx_logdet(self._h, C.byref(ld)))
         self.log_det_ = float(ld.value)
@@ -1012,6 +1103,8 @@ class GP:
         if self._fitted:
             st["fitted"] = {"N": int(self._N), "d": int(self._d), "k": int(self._k),
                             "jitter_used": float(self.jitter_used_), "log_det": float(self.log_det_)}
+            if self._basis_fit is not None:
+                st["fitted"]["basis"] = self._basis_fit
             if self.path_lengthscale is not None:
                 st["fitted"].update(path_variance=float(self.path_variance),
                                     path_lengthscale=[float(v) for v in self.path_lengthscale])
@@ -1057,7 +1150,9 @@ class GP:
 
     def log_marginal_likelihood(self, y, derivatives=None, derivative_noise=0.0):
         """-1/2 y^T alpha - 1/2 logdet - N/2 log(2 pi), summed over target columns.  ``derivatives`` as passed to
-        :meth:`fit` (their targets follow ``y``; N counts both; ``derivative_noise`` is part of the fit already)."""
+        :meth:`fit` (their targets follow ``y``; N counts both; ``derivative_noise`` is part of the fit already).
+        On a fit with ``basis=`` this is the profile likelihood at ``beta_``: ``alpha_`` is ``K^-1 (y - H beta)`` and
+        ``H^T alpha = 0``, so ``y^T alpha = (y - H beta)^T alpha``; :meth:`lml_gradient` is its exact gradient."""
         if _is_torch(y):
             y = y.detach().cpu().numpy()
         if derivatives is not None:
@@ -1115,7 +1210,7 @@ class GP:
 
     def optimize(self, X, y, params=("lengthscale", "variance", "noise"), bounds=(1e-4, 1e4), maxiter=40,
                  rel_step=1e-4, jac="analytic", noise_weights=None, derivatives=None, derivative_noise=0.0,
-                 path_ids=None, path_variance=0.0, path_lengthscale=None):
+                 path_ids=None, path_variance=0.0, path_lengthscale=None, basis=None):
         """Fit the hyper-parameters by maximising the log marginal likelihood (SURVEY.md §8f
         rank 1: the natural step after ``fit``; the reference has no counterpart).
 
@@ -1137,8 +1232,12 @@ class GP:
         ``path_ids``, ``path_variance`` and ``path_lengthscale`` as for :meth:`fit`.  The analytic gradient of such a
         model is ``lml_gradient(path=True)``, at the same cost (float64 on one device; anything else, and
         ``jac="3-point"``, runs on central differences); ``params`` may name ``"path_variance"`` (which must start above
-        0) and ``"path_lengthscale"`` (every entry moves), and the attributes of those names hold the result."""
+        0) and ``"path_lengthscale"`` (every entry moves), and the attributes of those names hold the result.
+
+        ``basis`` as for :meth:`fit`: every fit of the search is made with it, the objective is the profile likelihood
+        at each point's own ``beta_`` and the analytic gradient is its exact gradient."""
         from scipy.optimize import minimize
+        self._check_basis(basis)
         known = ("lengthscale", "variance", "noise", "derivative_noise", "path_variance", "path_lengthscale")
         names = [p for p in known if p in params]
         if not names or len(names) != len(tuple(params)):
@@ -1162,7 +1261,7 @@ class GP:
             self.derivative_noise = float(derivative_noise)   # where the search starts; unpack() moves it when it is learnt
 
         def fit_kw():   # every fit of the search, the final one included, with the current derivative_noise
-            kw = dict(noise_weights=noise_weights, derivatives=derivatives,
+            kw = dict(noise_weights=noise_weights, derivatives=derivatives, basis=basis,
                       derivative_noise=self.derivative_noise if full_grad else derivative_noise)
             if ids is not None:
                 kw.update(path_ids=ids, path_variance=self.path_variance, path_lengthscale=self.path_lengthscale)

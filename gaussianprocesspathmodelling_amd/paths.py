@@ -251,11 +251,16 @@ class PathModel:
     then about the cluster mean, or with ``path=key`` about that path of ``keys`` itself (the mean plus its own deviation:
     where it was between, at and beyond its observations); :meth:`log_likelihood` scores a path as a new member of the
     cluster, :meth:`forecast` continues one from its first points; :meth:`append_paths` adds paths under new ids (:meth:`add_paths` refuses such a model).
-    Which method adds paths: :meth:`add_paths` on plain and step-noise models, :meth:`append_paths` on every model."""
+    Which method adds paths: :meth:`add_paths` on plain and step-noise models, :meth:`append_paths` on every model.
+    ``trend``: None, or the basis of the model's explicit mean (``fit_path_models(trend=)``: "constant", "linear",
+    "quadratic" in the normalised inputs, coefficients marginalised — ``GP.fit(basis=)``).  :meth:`predict`, :meth:`sample`,
+    :meth:`log_likelihood` and :meth:`forecast` include it and its uncertainty; :meth:`add_paths`, :meth:`append_paths`,
+    :meth:`remove_paths`, :meth:`predict_gradient` and :meth:`velocity` raise ``GpxError`` with the library's reason."""
 
     def __init__(self, gp, keys, in_lo, in_span, y_mean, y_std, inputs, targets, step_weights=None, has_velocities=False,
-                 within_path=False, row_counts=None):
+                 within_path=False, row_counts=None, trend=None):
         self.gp, self.keys = gp, list(keys)
+        self.trend = trend
         # what remove_paths needs: every key's path id (within_path: its index in keys until a path has been removed, and
         # never reused after) and its number of value rows (row_counts: one per key, in order; None: not recorded)
         self._ids = {q: i for i, q in enumerate(self.keys)}
@@ -537,7 +542,7 @@ def step_noise_weights(Yn, n_paths):
 def fit_path_models(trajs, clusters, inputs=("t",), targets=("x", "y"), devices=None, optimize=False,
                     lengthscale=0.25, variance=1.0, noise=0.05, step_noise=False, velocities=None, velocity_noise=0.05,
                     learn_velocity_noise=False, within_path=False, path_variance=0.25, path_lengthscale=None,
-                    learn_path_parameters=False, **gp_kwargs):
+                    learn_path_parameters=False, trend=None, **gp_kwargs):
     """One exact GP per cluster of ``clusters`` = {cluster id: [path ids]} — what
     :func:`kmeans` (``kmeansclustering``, GPmap.py:36-93) returns — modelling the cluster's paths
     as (x(t), y(t)); the modelling step the reference's title names and its clustering prepares
@@ -565,6 +570,10 @@ def fit_path_models(trajs, clusters, inputs=("t",), targets=("x", "y"), devices=
     own with the others (analytic gradient, ``GP.lml_gradient(path=True)``), starting from the values passed, and the
     model's ``gp.path_variance`` and ``gp.path_lengthscale`` report them (``ValueError`` without ``within_path`` or without
     ``optimize``).
+    ``trend`` = "constant", "linear" or "quadratic": every cluster's GP gets an explicit mean in its normalised inputs
+    with marginalised coefficients (``GP.fit(basis=)``), so the plug-in standardisation no longer has to carry the trend
+    and its uncertainty reaches the variances; stored on the model as ``trend``.  Not with ``velocities`` or
+    ``within_path``.  None (the default) changes nothing.
     Returns {cluster id: :class:`PathModel`}; empty clusters are skipped."""
     import threading
     from concurrent.futures import ThreadPoolExecutor
@@ -585,6 +594,10 @@ def fit_path_models(trajs, clusters, inputs=("t",), targets=("x", "y"), devices=
         raise ValueError(f"velocities need 't' among the inputs, have {tuple(inputs)}")
     if within_path and velocities:
         raise ValueError("within_path cannot be combined with velocities (path ids and derivative observations)")
+    GP._check_basis(trend)
+    if trend is not None and (velocities or within_path):
+        raise ValueError("trend cannot be combined with velocities or within_path (basis functions with derivative "
+                         "observations or path ids)")
     if learn_path_parameters and not (within_path and optimize):
         raise ValueError("learn_path_parameters needs within_path=True and optimize=True")
     jobs = []
@@ -628,6 +641,8 @@ def fit_path_models(trajs, clusters, inputs=("t",), targets=("x", "y"), devices=
         sw = step_noise_weights(Yn, len(keys)) if step_noise else None
         w = None if sw is None else np.tile(sw, len(keys))
         kw = {} if der is None else dict(derivatives=der, derivative_noise=velocity_noise)
+        if trend is not None:
+            kw["basis"] = trend
         if within_path:
             kw.update(path_ids=np.concatenate([np.full(len(trajs.pathdict[q]), p, dtype=np.int32) for p, q in enumerate(keys)]),
                       path_variance=path_variance, path_lengthscale=path_lengthscale)
@@ -644,7 +659,7 @@ def fit_path_models(trajs, clusters, inputs=("t",), targets=("x", "y"), devices=
             gp.close()
             raise
         return cid, PathModel(gp, keys, lo, span, mu, sd, inputs, targets, step_weights=sw, has_velocities=der is not None,
-                              within_path=within_path, row_counts=[len(trajs.pathdict[q]) for q in keys])
+                              within_path=within_path, row_counts=[len(trajs.pathdict[q]) for q in keys], trend=trend)
 
     by_dev = [[] for _ in devs]                    # one worker per device, its clusters in order
     for i, (cid, keys) in enumerate(jobs):

@@ -505,6 +505,47 @@ int gpx_get_timings(gpx_handle* h, gpx_timings* out);
  * prices the flag on ONE handle, same buffers).  Groups: applied to every member. */
 int gpx_set_flags(gpx_handle* h, int32_t flags);
 
+/* ---- explicit basis functions: a constant, linear or quadratic mean (additive to ABI v6) -------------------
+ * Model (Rasmussen & Williams §2.7): y = f(x) + h(x)^T beta + noise, f the zero-mean GP of the handle, beta with a flat
+ * prior and marginalised: its uncertainty reaches every predictive variance.  h is evaluated on the RAW inputs the caller
+ * passes (not on x / l), and beta is in their units:
+ *   GPX_BASIS_CONSTANT  h = [1]                               p = 1
+ *   GPX_BASIS_LINEAR    h = [1, x_1 .. x_d]                    p = 1 + d
+ *   GPX_BASIS_QUADRATIC h = [1, x_1 .. x_d, x_1^2 .. x_d^2]    p = 1 + 2 d
+ * With H = h(X) (N x p) and K = L L^T the matrix the fit factorises anyway:
+ *   Z_H = L^-1 H,  z = L^-1 y,  A = Z_H^T Z_H,  beta = A^-1 Z_H^T z  (generalised least squares),  cov(beta) = A^-1
+ *   z' = z - Z_H beta,  alpha' = L^-T z' = K^-1 (y - H beta)   (H^T alpha' = 0)
+ *   mean(x*) = k*^T alpha' + h(x*)^T beta
+ *   cov(x*, x') = k(x*, x') - v*^T v' + u*^T u',   v* = L^-1 k*,  u* = L_A^-1 (h(x*) - Z_H^T v*),  L_A = chol A
+ * H^T occupies p of the 64 bordered right-hand-side rows of the fit next to the k targets: k + p <= 64.  beta, L_A, A^-1 and
+ * u are fp64 whatever the handle's element type.  gpx_get_alpha returns alpha'; gpx_logdet stays log|K|; gpx_lml_grad
+ * returns the PROFILE likelihood -1/2 (y - H beta)^T alpha' - k/2 log|K| - N k / 2 log 2 pi at beta and its exact gradient
+ * (the derivative through beta vanishes because H^T alpha' = 0); gpx_lml_grad_full and gpx_lml_grad_paths are gpx_lml_grad
+ * on such a fit, as on any plain fit.  Noise weights compose freely (only K changes).
+ *
+ * gpx_set_basis stores the basis for every later gpx_fit / gpx_fit_predict until it is replaced; GPX_BASIS_NONE clears it.
+ * Any other value, or a NULL handle: GPX_E_ARG, the previous setting stays.  An existing fit is not touched.
+ * At the fit, before anything is computed and with the previous fit still valid: k + p > 64 or N < p is GPX_E_ARG.  *info
+ * of the fit: 0 < *info <= N a pivot of K as before; *info = N + j: pivot j (1-based) of A was not > 0 or not finite (the
+ * columns of H are linearly dependent on this data) — the call returns 0 and the handle holds no fit.
+ * Served on a fit with a basis: gpx_predict (both routes), gpx_predict_cov, gpx_sample_posterior (around the corrected mean,
+ * from the corrected covariance), gpx_score_blocks(_weighted), gpx_forecast_blocks, gpx_get_alpha, gpx_logdet, the three
+ * gradient calls.  GPX_E_UNSUPPORTED with "basis" in gpx_last_error, before anything is computed or exchanged and with the
+ * previous fit still valid: a fit with a basis set on GPX_MIXED handles, device groups, shards and handles that own a
+ * communicator (the set call itself succeeds there), or together with observation kinds or effective path ids; on a fit
+ * with a basis: gpx_append, gpx_append_weighted, gpx_append_rows, gpx_remove_rows, gpx_predict_grad and every *_paths
+ * posterior call.
+ * With no basis set a handle launches the kernels it launched before, allocates nothing more and returns the same bits. */
+#define GPX_BASIS_NONE 0
+#define GPX_BASIS_CONSTANT 1
+#define GPX_BASIS_LINEAR 2
+#define GPX_BASIS_QUADRATIC 3
+int gpx_set_basis(gpx_handle* h, int32_t basis);
+/* The basis of the current fit: its id, p, and — each may be NULL — beta and cov(beta) = A^-1.  A fit without a basis:
+ * basis = 0, p = 0, nothing else written.  GPX_E_ARG without a fit. */
+int gpx_get_basis(gpx_handle* h, int32_t* basis, int32_t* p, double* beta /* (p,k) host, fp64 */,
+                  double* beta_cov /* (p,p) host, fp64 */);
+
 /* ---- row-block sharding over RCCL ------------------------------ */
 /* Two process models run the same schedule: the single-process device group above
  * (gpx_config.ndev) and one process per GPU (below).
