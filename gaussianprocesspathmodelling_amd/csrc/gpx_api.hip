@@ -3776,7 +3776,9 @@ int gpx_reserve(gpx_handle* h, int64_t capacity) try {
   if (capacity < 0 || capacity > (int64_t)INT_MAX - 4096) return fail(h, GPX_E_ARG, "gpx_reserve: bad capacity");
   int rc;
   if ((rc = posterior_refused(h, "gpx_reserve"))) return rc;
-  if (h->fitted && capacity < h->N) return fail(h, GPX_E_ARG, "gpx_reserve: the handle already holds more points");
+  // (0 takes a reservation back: nothing of the current fit depends on it, an append without one grows the layout itself)
+  if (h->fitted && capacity > 0 && capacity < h->N)
+    return fail(h, GPX_E_ARG, "gpx_reserve: the handle already holds more points");
   h->reserve = capacity;  // laid out by the next gpx_fit / gpx_append
   return GPX_OK;
 }

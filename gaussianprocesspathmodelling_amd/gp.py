@@ -632,7 +632,9 @@ class GP:
 
     def reserve(self, n):
         """Lay the factor out for up to ``n`` points (``gpx_reserve``) at the next :meth:`fit` or :meth:`update`:
-        updates within it happen in place, nothing is reallocated or copied.  0 = what the fit itself needs."""
+        updates within it happen in place, nothing is reallocated or copied.  0 = what the fit itself needs: it takes an
+        earlier reservation back for the fits that follow, on a fitted model too (any other ``n`` below the number of
+        points the model holds is refused)."""
         self._check(self._lib.gpx_reserve(self._h, int(n)))
         return self
 

@@ -267,7 +267,8 @@ int gpx_score_blocks(gpx_handle* h, const void* Xs, const void* ys, int64_t G, i
 int gpx_append(gpx_handle* h, const void* Xnew, const void* ynew, int64_t m, int32_t mem_kind, int64_t* info);
 /* The next gpx_fit and later gpx_append lay the factor buffer out for up to `capacity` points (leading dimension from
  * round_up(capacity, 128)); appends within it happen in place.  0 (the default): what the fit itself needs — a handle
- * that never calls this fits exactly as before.  On a fitted handle a capacity below its N is GPX_E_ARG; a larger one
+ * that never calls this fits exactly as before, and 0 on a fitted handle takes a reservation back for the fits that
+ * follow (the current layout stays).  On a fitted handle any other capacity below its N is GPX_E_ARG; a larger one
  * takes effect with the next append (one move of the factor).  Refusals as for gpx_append. */
 int gpx_reserve(gpx_handle* h, int64_t capacity);
 /* Where the factor lives (single-device GPX_F64 / GPX_F32 handles after a successful fit): its device pointer (row-major,
