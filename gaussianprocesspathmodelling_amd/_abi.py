@@ -109,6 +109,7 @@ SIGNATURES = {
     "gpx_lml_grad": (C.c_int, [_P, _PD, _PD]),
     "gpx_lml_grad_full": (C.c_int, [_P, _PD, _PD]),
     "gpx_lml_grad_paths": (C.c_int, [_P, _PD, _PD, _PD, C.c_int32]),
+    "gpx_loo": (C.c_int, [_P, _PD, _PD, _PD, _PD]),
     "gpx_logdet": (C.c_int, [_P, _PD]),
     "gpx_release_scratch": (C.c_int, [_P]),
     "gpx_get_timings": (C.c_int, [_P, C.POINTER(GpxTimings)]),

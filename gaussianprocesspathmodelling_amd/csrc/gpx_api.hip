@@ -129,6 +129,7 @@ struct gpx_handle {
     DevBuf SW;  // gpx_score_blocks_weighted: the query points' weights
     DevBuf BG, BU;  // a fit with basis functions: per-slice Gram of the bordered rows; u = L_A^-1 (h - Z_H^T v*) per query row (rows x 64, fp64)
     DevBuf UW, UQ;  // gpx_remove_rows: per pass in flight (two) the carry ((N + 64) x UPD_W) and the panel's orthogonal factor (2 UPD_W square)
+    DevBuf LOO;     // gpx_loo: q (N) | var (N) | mean (N x k) | logp (N x k), fp64
   } scr;
   // row-block shard (world > 1)
   Comm* comm = nullptr;  // RCCL, in-process or host-callback transport (gpx_shard.inc)
@@ -2639,6 +2640,21 @@ int trtri_enqueue(gpx_handle* h, double* ZT, const double* L, int64_t ld, int64_
   return GPX_OK;
 }
 
+// the block width of the L^-T sweeps: their measured 1024-blocks whatever the fit's panel width (GPX_NB_GRAD overrides: A/B)
+int zt_block(const gpx_handle* h) { return h->env.nb_grad ? h->env.nb_grad : std::min(h->nb_pred, 1024); }
+
+// scr.ZT <- L^-T of the current fit, whole, on one device (lml_grad_impl with P = 1, loo_impl): N^3 / 3 flops on the tile
+// engine.  Always built anew — the handle does not remember that it holds one — and scratch afterwards.
+int build_zt(gpx_handle* h) {
+  const int64_t Npad = h->Npad, ld = h->ld;
+  int rc;
+  if ((rc = ensure(h, h->scr.ZT, (size_t)Npad * ld * 8))) return rc;
+  double* ZT = (double*)h->scr.ZT.p;
+  HIPCHK(h, hipMemsetAsync(ZT, 0, (size_t)Npad * ld * 8, h->st));
+  launch_set_diag_one(ZT, ld, Npad, h->st);
+  return trtri_enqueue(h, ZT, (const double*)h->Lfac, ld, Npad, zt_block(h), (const double*)h->Winv.p, 1, 0);
+}
+
 // Gradient of the log marginal likelihood.  Sharded handles (replicated factor: every rank holds
 // the whole L): L^-T in row blocks dealt over the ranks (no exchange), one all-gather of its
 // non-zero part (block b: rows x columns >= b nb, packed), the fused K^-1 trace pass with the
@@ -2654,8 +2670,7 @@ int lml_grad_impl(gpx_handle* h, double* lml, double* grad, bool kinds = false, 
   const int d = h->d, k = h->k, ntheta = h->n_ls + (kinds ? 3 : paths ? 3 + h->n_lsp : 2), ard = h->n_ls > 1;
   Comm* cm = h->comm;
   const int P = cm ? cm->world : 1, rank = cm ? cm->rank : 0;
-  // the gradient's sweeps keep their measured 1024-blocks whatever the fit's panel width (GPX_NB_GRAD overrides: A/B)
-  const int nb = h->env.nb_grad ? h->env.nb_grad : std::min(h->nb_pred, 1024);
+  const int nb = zt_block(h);
   gpx_timings& tm = h->tm;
   tm.grad_trtri = tm.grad_trace = tm.grad_total = 0;
   const int64_t s1n = kinv_trace_slots(Npad), s2n = alpha_quad_slots(Npad);
@@ -2682,17 +2697,16 @@ int lml_grad_impl(gpx_handle* h, double* lml, double* grad, bool kinds = false, 
     PhaseScope total(h, &tm.grad_total);
     {
       PhaseScope ps(h, &tm.grad_trtri);
-      HIPCHK(h, hipMemsetAsync(Zl, 0, (size_t)(P > 1 ? nloc : Npad) * ld * 8, st));
       if (P == 1) {
-        launch_set_diag_one(ZT, ld, Npad, st);
+        if ((rc = build_zt(h))) return rc;
       } else {
+        HIPCHK(h, hipMemsetAsync(Zl, 0, (size_t)nloc * ld * 8, st));
         int64_t j = 0;
         for (int64_t b = rank; b < nblk; b += P, ++j)
           launch_set_diag_one(Zl + j * nb * ld + b * nb, ld, std::min<int64_t>(nb, Npad - b * nb), st);
-      }
-      if ((rc = trtri_enqueue(h, Zl, (const double*)h->Lfac, ld, Npad, nb, (const double*)h->Winv.p, P, rank)))
-        return rc;
-      if (P > 1) {  // all-gather: block b from rank b % P, only the columns right of its zeros
+        if ((rc = trtri_enqueue(h, Zl, (const double*)h->Lfac, ld, Npad, nb, (const double*)h->Winv.p, P, rank)))
+          return rc;
+        // all-gather: block b from rank b % P, only the columns right of its zeros
         double* pack = (double*)h->scr.ZTpack.p;
         HIPCHK(h, hipMemsetAsync(ZT, 0, (size_t)Npad * ld * 8, st));
         for (int64_t b = 0; b < nblk; ++b) {
@@ -2743,6 +2757,42 @@ int lml_grad_impl(gpx_handle* h, double* lml, double* grad, bool kinds = false, 
   if (kinds && h->sn2_deriv == 0.0) grad[ntheta - 1] = 0.0;  // (exactly: not -0, and no 0 x inf)
   *lml = -0.5 * host[2 * ntheta] - 0.5 * (double)k * h->logdet -
          0.5 * (double)N * (double)k * 1.8378770664093454835606594728112;  // log(2 pi)
+  return GPX_OK;
+}
+
+// Leave-one-out predictions of the current fit (gpx_loo; one fp64 device): alpha, L^-T (the gradient's
+// stage), one pass over its upper triangle for Q_ii (a fit with basis functions: Q'_ii), the finish kernel, the copies.
+// `total` sums logp over the rows on the host, in row order.
+int loo_impl(gpx_handle* h, double* mean, double* var, double* logp, double* total) {
+  const int64_t N = h->N, ld = h->ld;
+  const int k = h->k, p = h->bp;
+  int rc;
+  if ((rc = ensure_alpha<double>(h))) return rc;
+  if ((rc = ensure(h, h->scr.LOO, (size_t)(2 * N + 2 * N * k) * 8))) return rc;
+  double* dq = (double*)h->scr.LOO.p;
+  double* dvar = dq + N;
+  double* dmean = dvar + N;
+  double* dlogp = dmean + N * k;
+  if ((rc = build_zt(h))) return rc;
+  hipStream_t st = h->st;
+  launch_loo_rows((const double*)h->scr.ZT.p, ld, N, p ? (const double*)h->zT + (int64_t)k * ld : nullptr, p,
+                  (const double*)h->Bst.p, dq, st);
+  launch_loo_finish(dq, (const double*)h->alphaT, ld, (const double*)h->Y.p, N, k, dmean, dvar, dlogp, st);
+  std::vector<double> lp;  // total without logp: the terms still come to the host
+  if (total && !logp) {
+    lp.resize((size_t)N * k);
+    logp = lp.data();
+  }
+  if (mean) HIPCHK(h, hipMemcpyAsync(mean, dmean, (size_t)N * k * 8, hipMemcpyDeviceToHost, st));
+  if (var) HIPCHK(h, hipMemcpyAsync(var, dvar, (size_t)N * 8, hipMemcpyDeviceToHost, st));
+  if (logp) HIPCHK(h, hipMemcpyAsync(logp, dlogp, (size_t)N * k * 8, hipMemcpyDeviceToHost, st));
+  if ((rc = finish_call(h))) return rc;
+  if (total)
+    for (int c = 0; c < k; ++c) {
+      double s = 0.0;
+      for (int64_t i = 0; i < N; ++i) s += logp[i * k + c];
+      total[c] = s;
+    }
   return GPX_OK;
 }
 
@@ -3874,6 +3924,17 @@ int gpx_lml_grad_paths(gpx_handle* h, double* lml, double* grad, double* grad_pa
   if ((rc = lml_grad_impl(h, lml, grad))) return rc;  // no effective path ids: gpx_lml_grad's launches and numbers
   for (int32_t t = 0; t < n_path; ++t) grad_path[t] = 0.0;
   return GPX_OK;
+}
+GPX_CATCH_ALL
+
+int gpx_loo(gpx_handle* h, double* mean, double* var, double* logp, double* total) try {
+  if (!h) return GPX_E_ARG;
+  if (!h->fitted || (!mean && !var && !logp && !total)) return fail(h, GPX_E_ARG, "gpx_loo: no fit or no output");
+  if (h->cfg.dtype != GPX_F64) return fail(h, GPX_E_UNSUPPORTED, "gpx_loo: fp64 handles only");
+  if (h->group || h->comm || h->cfg.world > 1) return fail(h, GPX_E_UNSUPPORTED, "gpx_loo: single-device handles only");
+  int rc;
+  if ((rc = begin_call(h))) return rc;
+  return loo_impl(h, mean, var, logp, total);
 }
 GPX_CATCH_ALL
 

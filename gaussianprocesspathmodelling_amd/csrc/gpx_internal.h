@@ -455,6 +455,18 @@ void launch_basis_epilogue(const double* state, int p, int k, int d, const T* MT
 template <typename T>
 void launch_cov_add_uut(T* Sig, int64_t lds, int64_t M, int p, const double* U, hipStream_t st);
 
+// ---- leave-one-out predictions (gpx_loo.hip; fp64) --------------------------------
+// q[i] = sum_{i <= j < n} ZT[i][j]^2 for i < n, ZT = L^-T (row-major, ld; rows 128-byte aligned).  p > 0 (a fit with basis
+// functions): ZHT = Z_H^T (p rows, ld: rows [k, k + p) of the bordered block), state the handle's basis state block;
+// q[i] = q_i - |L_A^-1 b_i|^2 with b_i = sum_j ZT[i][j] Z_H[j][:], or 0 where that is <= 64 * 2^-52 * q_i (a row the basis
+// coefficients alone determine).  Columns >= n are not read.  p = 0: neither ZHT nor state is read.
+void launch_loo_rows(const double* ZT, int64_t ld, int64_t n, const double* ZHT, int p, const double* state, double* q,
+                     hipStream_t st);
+// var[i] = 1 / q[i], mean[i k + c] = Y[i k + c] - alphaT[c ld + i] / q[i], logp[i k + c] = -1/2 log(2 pi / q[i]) -
+// alphaT[c ld + i]^2 / (2 q[i]) for i < n, c < k; q[i] = 0: var +inf, mean NaN, logp -inf
+void launch_loo_finish(const double* q, const double* alphaT, int64_t ld, const double* Y, int64_t n, int k, double* mean,
+                       double* var, double* logp, hipStream_t st);
+
 // ---- removal of observations (gpx_update.hip) -----------------------------------
 constexpr int UPD_W = 64;  // panel width of the rank-m update of the trailing factor = most columns m one pass removes
 // carry W ((n3 + 64) x UPD_W, compact): row i < n3 = columns [a, a + m) of row a + m + i of L, rows n3 + r those columns of

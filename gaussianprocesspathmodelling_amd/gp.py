@@ -1210,6 +1210,52 @@ class GP:
         self._check(call(self._h, C.byref(lml), _abi.dptr(grad)))
         return float(lml.value), grad
 
+    def _loo(self, want_mean, want_var, want_logp, want_total):
+        if not self._fitted:
+            raise RuntimeError("loo() before a successful fit()")
+        N, k = self._N, self._k
+        mean = np.empty((N, k), dtype=np.float64) if want_mean else None
+        var = np.empty(N, dtype=np.float64) if want_var else None
+        logp = np.empty((N, k), dtype=np.float64) if want_logp else None
+        total = np.empty(k, dtype=np.float64) if want_total else None
+        self._check(self._lib.gpx_loo(self._h, *(None if a is None else _abi.dptr(a) for a in (mean, var, logp, total))))
+        return mean, var, logp, total
+
+    def loo(self, return_var=True, return_logp=False):
+        """Leave-one-out predictions of the observations of the current fit, without refitting (``gpx_loo``; R&W §5.4.2):
+        ``mean``, then with ``return_var`` ``var`` (N,), then with ``return_logp`` ``logp``.  ``mean`` and ``logp`` are
+        shaped as ``alpha_`` is — (N,) for a 1-D ``y``, else (N, k); NumPy float64 arrays.
+
+        Row i is what the model fitted to every OTHER observation predicts for observation i: ``mean[i]``, the variance
+        ``var[i]`` of that OBSERVATION — its own noise (times its noise weight) and jitter included, not the latent
+        function's variance — and ``logp[i]``, the log-density of the observed ``y[i]`` under it.  ``(y - mean) /
+        sqrt(var)`` is the standardised residual: a bad recording is a row where it is large, and :meth:`remove` takes
+        such rows out.  On a fit with ``derivatives=`` the rows follow the fit's order (values, then derivative rows;
+        ``observation_kinds_``), and a derivative row's entry is the prediction of that derivative observation, with
+        ``derivative_noise`` in its variance.  On a fit with ``path_ids=`` the other points of the row's own path count
+        among "the others".  On a fit with ``basis=`` the coefficients are marginalised (flat prior), the trend is inside
+        ``mean``; a row that the coefficients alone determine (every row when N equals the number of basis functions)
+        gets ``var = inf``, ``mean = nan``, ``logp = -inf``.
+
+        Cost: one ``L^-T`` build — about the ``grad_trtri`` phase of a :meth:`lml_gradient` — one pass over it, and
+        N^2 * 8 bytes of scratch, which :meth:`release_scratch` frees.  Two calls return the same bits.  float64 models on
+        one device; anything else raises ``GpxError`` with the library's message."""
+        mean, var, logp, _ = self._loo(True, return_var, return_logp, False)
+        out = [mean[:, 0].copy() if self._y1d else mean]
+        if return_var:
+            out.append(var)
+        if return_logp:
+            out.append(logp[:, 0].copy() if self._y1d else logp)
+        return out[0] if len(out) == 1 else tuple(out)
+
+    def loo_log_likelihood(self):
+        """The leave-one-out log predictive density of the current fit, ``sum_i logp[i]`` of :meth:`loo` (R&W eq. 5.11): a
+        float, or (k,) for several targets.  The second yardstick beside :meth:`log_marginal_likelihood` for comparing
+        kernel families, path terms and trends; ``-inf`` where a row is undetermined (see :meth:`loo`).  Same cost as
+        :meth:`loo`."""
+        total = self._loo(False, False, False, True)[3]
+        return float(total[0]) if self._y1d else total
+
     def optimize(self, X, y, params=("lengthscale", "variance", "noise"), bounds=(1e-4, 1e4), maxiter=40,
                  rel_step=1e-4, jac="analytic", noise_weights=None, derivatives=None, derivative_noise=0.0,
                  path_ids=None, path_variance=0.0, path_lengthscale=None, basis=None):

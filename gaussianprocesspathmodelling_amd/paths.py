@@ -464,6 +464,53 @@ class PathModel:
         self.keys = [q for q in self.keys if q not in gone]
         return self
 
+    def _value_rows(self):
+        """{key: indices of the key's value rows among the fit's rows}: by path id on a ``within_path`` model, else by the
+        recorded row counts in ``keys`` order (value rows only: a model with velocities skips its derivative rows)"""
+        if self.within_path:
+            ids = np.asarray(self.gp.path_ids_)
+            return {q: np.flatnonzero(ids == self._ids[q]) for q in self.keys}
+        if self._rows is None:
+            raise ValueError("loo: the model does not know its paths' row counts (it was not built by fit_path_models)")
+        if self.has_velocities:
+            values = np.flatnonzero(np.asarray(self.gp.observation_kinds_) == -1)
+        else:
+            values = np.arange(self.gp._N)
+        if sum(self._rows[q] for q in self.keys) != len(values):
+            raise ValueError("loo: the recorded row counts do not add up to the fit's value rows (rows were removed or "
+                             "appended through the GP itself)")
+        out, at = {}, 0
+        for q in self.keys:
+            out[q] = values[at:at + self._rows[q]]
+            at += self._rows[q]
+        return out
+
+    def loo(self, keys=None):
+        """Leave-one-out check of the model against its own paths (``GP.loo``; no refit): {key: (mean (L_key, k), std
+        (L_key, k), z (L_key, k))} for ``keys`` (default: every path of the model), in the targets' own units.  Row s of a
+        key is what the model fitted to every other observation — the other points of the same path included — predicts
+        for point s of that path: ``mean``, the standard deviation ``std`` of that observation (its own noise included),
+        and the standardised residual ``z = (y - mean) / std``.  A glitch in a recording is the (key, step) with the
+        largest ``|z|``.  Only value rows are reported (a model with velocities leaves its derivative rows out).  Works on
+        every model, also after :meth:`append_paths` / :meth:`remove_paths`; ``KeyError`` for a key the model does not
+        hold, ``ValueError`` when the paths' row counts are not recorded (a model not built by
+        :func:`fit_path_models`, unless it is ``within_path``)."""
+        keys = self.keys if keys is None else list(keys)
+        for q in keys:
+            if q not in self._ids:
+                raise KeyError(q)
+        rows = self._value_rows()
+        mean, var = self.gp.loo(return_var=True)
+        mean = np.asarray(mean, dtype=np.float64).reshape(len(var), -1)
+        alpha = np.asarray(self.gp.alpha_, dtype=np.float64).reshape(len(var), -1)
+        resid = alpha * var[:, None]  # y - mean = alpha / Q_ii, in the model's normalised units
+        std = np.sqrt(var)[:, None]
+        out = {}
+        for q in keys:
+            r = rows[q]
+            out[q] = (mean[r] * self.y_std + self.y_mean, std[r] * self.y_std[None, :], resid[r] / std[r])
+        return out
+
     def log_likelihood(self, paths_txy, include_noise=True):
         """How likely whole paths are under this cluster's model: ``paths_txy`` (P, L, 3) raw (t, x, y) paths of one
         length L <= 64 -> (P, k) log-densities of each path's targets, in the targets' own units, under the joint

@@ -494,6 +494,20 @@ int gpx_lml_grad_full(gpx_handle* h, double* lml, double* grad /* n_ls + 3 */);
  * nothing and leaves the fit valid.  Timings: grad_trtri, grad_trace, grad_total, as for the other two. */
 int gpx_lml_grad_paths(gpx_handle* h, double* lml, double* grad /* n_ls + 2, as gpx_lml_grad */,
                        double* grad_path /* n_path: d/dlog sg2, then d/dlog l_path,c */, int32_t n_path);
+/* Leave-one-out predictive distribution of every observation of the current fit (R&W 5.10-5.12).  Host buffers, fp64;
+ * any of them may be NULL, not all.  total: k sums of logp over the rows, in row order.
+ * With Q = K^-1 of the fit as it stands (noise, weights, jitter, derivative rows and the path term included) and
+ * q_i = Q_ii: var_i = 1 / q_i is the predictive variance of OBSERVATION i given all the others, its own noise included;
+ * mean_ic = y_ic - alpha_ic / q_i; logp_ic = -1/2 log(2 pi / q_i) - alpha_ic^2 / (2 q_i).  A derivative row's entries are
+ * about that derivative observation.  A fit with basis functions marginalises the coefficients (flat prior):
+ * q'_i = q_i - |L_A^-1 (K^-1 H)_i|^2 replaces q_i, and h^T beta is inside mean.  A row that the basis coefficients alone
+ * determine (q'_i <= 64 * 2^-52 * q_i; every row when N = p) is undetermined: var = +inf, mean = NaN, logp = -inf, and
+ * total = -inf.
+ * Cost: one L^-T (N^3 / 3 flops: the grad_trtri phase of a gradient, and its N^2 * 8 bytes of scratch, which
+ * gpx_release_scratch frees) and one pass over it; every kernel family.  The sums have one order: two calls return the
+ * same bits.  GPX_E_ARG without a fit or with four NULL outputs; GPX_E_UNSUPPORTED on GPX_F32 / GPX_MIXED handles and on
+ * shards, device groups and handles that own a communicator.  A failed call writes nothing and leaves the fit valid. */
+int gpx_loo(gpx_handle* h, double* mean /* (N,k) */, double* var /* (N) */, double* logp /* (N,k) */, double* total /* (k) */);
 int gpx_logdet(gpx_handle* h, double* out);
 /* Frees what only the NEXT predict / gradient call would use (the V^T batch, the L^-T buffer of
  * gpx_lml_grad, per-tile partials, compact block buffers, the buffers of the joint-posterior calls); the fit itself (factor, alpha, block
