@@ -37,6 +37,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <new>
 #include <string>
 #include <vector>
@@ -621,10 +622,15 @@ int panel_solve_enqueue(gpx_handle* h, T* A, int64_t ld, int64_t o, int nbp, int
 // the next diagonal block and panel solve beside the rest of the same launch.  The bordered rows'
 // update of panel p+1 moves behind the panel solve on the look-ahead stream (it touches no row of
 // the matrix proper), i.e. off the chain and inside the previous update.
+// of nr bordered rows (x nc columns), those that go out in 128-tiles when nr is no multiple of 128: all but the remainder
+inline int64_t split_rows_128(int64_t nr, int64_t nc) {
+  return (nr > 128 && nr % 128 != 0 && nc % 128 == 0) ? nr / 128 * 128 : nr;
+}
+
 template <typename T>
 int chol_enqueue(gpx_handle* h, T* A, int64_t ld, int64_t n, int nb, T* Winv, T* P0, T* P1,
                  int64_t ldp, int* info, int64_t gidx0, bool profile, int64_t nx = 0,
-                 InvWork<T>* iw = nullptr, int64_t nx_side = 0) {
+                 InvWork<T>* iw = nullptr, int64_t nx_side = 0, int rest_split_arg = -1) {
   hipStream_t s0 = h->st, s1 = h->st2;
   T* Pbuf[2] = {P0, P1};
   int rc;
@@ -658,8 +664,14 @@ int chol_enqueue(gpx_handle* h, T* A, int64_t ld, int64_t n, int nb, T* Winv, T*
     const int nbp = (int)std::min<int64_t>(nb, n - o);
     const int64_t t0 = o + nbp, ntrail = n - t0;
     if (nr <= 0 || nc <= 0) return;
-    launch_gemm_nt<T>(nr % 128 == 0 && nc % 128 == 0 ? 128 : 64, A + (n + r0) * ld + c0, ld, Pc + (ntrail + r0) * ldp, ldp,
-                      Pc + (c0 - t0) * ldp, ldp, nr, nc, nbp, 0, 0, s);
+    // many rows plus a 64-row remainder (the left block column of the two-level factorisation with the right-hand
+    // sides below it): the 128-multiple in 128-tiles, the remainder in a launch of its own
+    const int64_t na = split_rows_128(nr, nc);
+    launch_gemm_nt<T>(na % 128 == 0 && nc % 128 == 0 ? 128 : 64, A + (n + r0) * ld + c0, ld, Pc + (ntrail + r0) * ldp, ldp,
+                      Pc + (c0 - t0) * ldp, ldp, na, nc, nbp, 0, 0, s);
+    if (na < nr)
+      launch_gemm_nt<T>(64, A + (n + r0 + na) * ld + c0, ld, Pc + (ntrail + r0 + na) * ldp, ldp, Pc + (c0 - t0) * ldp, ldp,
+                        nr - na, nc, nbp, 0, 0, s);
   };
   // does a 128-tile trailing update run beside the look-ahead chain of the panel behind offset o?  If not,
   // the chain's small launches are alone on the GPU and take the latency mode of the 64-tile engine.
@@ -674,7 +686,8 @@ int chol_enqueue(gpx_handle* h, T* A, int64_t ld, int64_t n, int nb, T* Winv, T*
   };
   const bool split_env = split_strip_in_force(h);  // (the fused update keeps its own hand-over)
   const bool top_env = env.solve_top;              // GPX_SOLVE_TOP=0: the whole panel solve on the chain (A/B)
-  const int rest_split = env.rest_split;  // trailing rows (in panels) up to which the REST hands its first column block over early
+  // trailing rows (in panels) up to which the REST hands its first column block over early (a caller's own: the two-level schedule)
+  const int rest_split = rest_split_arg >= 0 ? rest_split_arg : env.rest_split;
   // The LAST nx_side bordered rows (the query points of gpx_fit_predict: a multiple of 128) are the main stream's
   // business alone in the split schedule: their panel solves, like their updates, are throughput work no step of the
   // chain waits for (tried: a stream of their own that trails the factorisation panel by panel, reading L from A —
@@ -691,8 +704,10 @@ int chol_enqueue(gpx_handle* h, T* A, int64_t ld, int64_t n, int nb, T* Winv, T*
       return GPX_OK;
     }
     HIPCHK(h, hipStreamWaitEvent(s, iw->ready, 0));
-    launch_gemm_nt<T>(nxs % 128 == 0 && nbp % 128 == 0 ? 128 : 64, Pside, ldp, Aside, ld,
-                      iw->W + (o / iw->nbw) * (int64_t)iw->nbw * iw->nbw, iw->nbw, nxs, nbp, nbp, 4, 1, s);
+    const T* Wp = iw->W + (o / iw->nbw) * (int64_t)iw->nbw * iw->nbw;
+    const int64_t na = split_rows_128(nxs, nbp);  // (as bordered_block)
+    launch_gemm_nt<T>(na % 128 == 0 && nbp % 128 == 0 ? 128 : 64, Pside, ldp, Aside, ld, Wp, iw->nbw, na, nbp, nbp, 4, 1, s);
+    if (na < nxs) launch_gemm_nt<T>(64, Pside + na * ldp, ldp, Aside + na * ld, ld, Wp, iw->nbw, nxs - na, nbp, nbp, 4, 1, s);
     launch_copy2d<T>(Aside, ld, Pside, ldp, nxs, nbp, s);
     return GPX_OK;
   };
@@ -910,6 +925,94 @@ int chol_enqueue(gpx_handle* h, T* A, int64_t ld, int64_t n, int nb, T* Winv, T*
       if ((rc = stream_waits(h, s0, sj, "join"))) return rc;
   }
   return GPX_OK;
+}
+
+// ---- two-level Cholesky: the arguments of chol_enqueue ---------------------------------------
+// The matrix is split at the panel boundary c nearest n / 2, and from n >= GPX_TWO_LEVEL_FROM on (0: never) the
+// factorisation runs as
+//   1. chol_enqueue of the left block column: A11 = L11 L11^T with rows [c, n + nx) — A21 and the bordered rows — as
+//      its bordered rows.  They go in as SIDE rows (nx_side: all of them): the side rows' panel solves and updates are
+//      the main stream's throughput work that no step of the chain waits for, which is what A21 is; the chain's rows
+//      must come first among the bordered rows and the right-hand sides lie BELOW A21, so those ride as side rows too.
+//   2. A22 -= L21 L21^T in ONE update at K = c (the deep update: main stream), beside it on the look-ahead stream the
+//      bordered rows' columns [c, n) (a long serial walk of few tiles), joined before 3.
+//   3. chol_enqueue of A22 with the bordered rows, pivots counted from gidx0 + c; block inverses, panel buffers and the
+//      step flag as gpx_append's restart takes them (a fresh InvWork: the flag is reset in front of its first block).
+// With GPX_STRASSEN_MIN > 0 the off-diagonal block of the deep update — rows [hh, np) x columns [0, hh) of A22, hh = half
+// of np = n - c in whole 128-tiles — goes through strassen_nt when its quadrants are at least that large, the two
+// diagonal halves stay classical triangular launches; GPX_STRASSEN_DIAG splits the two halves once more in the same way.
+// The deep update is booked under chol_syrk, syrk_flops counting the flops executed.
+template <typename T>
+int chol_two_level_enqueue(gpx_handle* h, T* A, int64_t ld, int64_t n, int nb, T* Winv, T* P0, T* P1, int64_t ldp,
+                           int* info, int64_t gidx0, bool profile, int64_t nx = 0, InvWork<T>* iw = nullptr,
+                           int64_t nx_side = 0) {
+  const EnvKnobs& env = h->env;
+  const int64_t c = std::max<int64_t>(1, (n / 2 + nb / 2) / nb) * nb, np = n - c;
+  // The temporaries of the Strassen levels are the two panel buffers — P0 and P1 are the halves of ONE allocation
+  // [P0, P0 + 2 (P1 - P0)), idle between phase 1 and phase 3 (everything that read or wrote them is ordered in front of
+  // the main stream's next launch when chol_enqueue returns) — so the level costs no memory.  They hold the level of
+  // Npad = 65536 at 2048-wide panels and nothing larger (Npad <= 32 nb): beyond that, and in fp32 unless
+  // GPX_STRASSEN_SINGLE says otherwise (the variance at full size), the one-level schedule, as
+  // wherever the split has no level to enable (by itself it only costs).
+  const int64_t smin = env.strassen_min;
+  const int depth = smin > 0 ? (env.strassen_diag ? 2 : 1) : 0;
+  const int64_t hh = np / 2 / 128 * 128, ldt = c / 2 + ld_skew<T>();
+  const bool fits = P1 > P0 && strassen_temp_elems(np - hh, hh, c, ld_skew<T>()) <= 2 * (size_t)(P1 - P0);
+  const bool wanted = depth == 0 || (fits && (sizeof(T) == 8 || env.strassen_f32));
+  if (env.two_level_from <= 0 || n < env.two_level_from || !iw || nx_side != 0 || np < 256 || n % 128 != 0 || nb % 128 != 0 ||
+      (nx != 0 && nx != RHS_ROWS) || !wanted)
+    return chol_enqueue<T>(h, A, ld, n, nb, Winv, P0, P1, ldp, info, gidx0, profile, nx, iw, nx_side);
+  int rc;
+  hipStream_t s0 = h->st, s1 = h->st2;
+  T *TA = P0, *TB = nullptr;
+  // 1. the left block column
+  // (each phase has half the panels, and in phase 1 the side rows keep the main stream busy beside the chain: the REST's
+  //  early hand-over — GPX_REST_SPLIT, tuned on the one-level schedule — from half as many trailing panels on; N = 65536:
+  //  1513.3 against 1521.6 ms)
+  const int rs = env.rest_split / 2;
+  if ((rc = chol_enqueue<T>(h, A, ld, c, nb, Winv, P0, P1, ldp, info, gidx0, profile, np + nx, iw, np + nx, rs))) return rc;
+  // 2. the deep update
+  T* A22 = A + c * ld + c;
+  const T* L21 = A + c * ld;
+  hipEvent_t e_rows = nullptr;
+  if (nx > 0) {
+    if ((rc = stream_waits(h, s1, s0, "deep update"))) return rc;
+    PhaseScope ps(h, &h->tm.chol_strip, profile, s1);
+    launch_gemm_nt<T>(64, A + n * ld + c, ld, A + n * ld, ld, L21, ld, nx, np, c, 0, 0, s1);
+    if ((rc = record_event(h, s1, "deep update", &e_rows))) return rc;
+  }
+  {
+    PhaseScope ps(h, &h->tm.chol_syrk, profile);
+    // rows and columns [o, o + sz) of A22, lower triangle; `lv` levels of splitting left
+    std::function<void(int64_t, int64_t, int)> deep = [&](int64_t o, int64_t sz, int lv) {
+      const int64_t s1z = sz / 2 / 128 * 128, s2z = sz - s1z;
+      if (lv <= 0 || s1z < 256 || std::min(s1z, s2z) / 256 * 128 < smin) {
+        launch_gemm_nt<T>(128, A22 + o * ld + o, ld, L21 + o * ld, ld, L21 + o * ld, ld, sz, sz, c, 1, 0, s0);
+        h->tm.syrk_flops += (double)sz * (double)(sz + 1) * (double)c;
+        h->tm.syrk_launches += 1;
+        return;
+      }
+      deep(o, s1z, lv - 1);
+      TB = TA + (s2z / 256 * 128) * ldt;
+      h->tm.syrk_flops += strassen_nt<T>(A22 + (o + s1z) * ld + o, ld, L21 + (o + s1z) * ld, ld, L21 + o * ld, ld, s2z, s1z,
+                                         c, TA, TB, ldt, s0);
+      h->tm.syrk_launches += 7;
+      deep(o + s1z, s2z, lv - 1);
+    };
+    deep(0, np, depth);
+  }
+  if (e_rows) HIPCHK(h, hipStreamWaitEvent(s0, e_rows, 0));
+  // 3. the right block
+  InvWork<T> iw2;
+  iw2.W = iw->W + (c / iw->nbw) * (int64_t)iw->nbw * iw->nbw;
+  iw2.U = iw->U;
+  iw2.ldu = iw->ldu;
+  iw2.nbw = iw->nbw;
+  iw2.aux = iw->aux;
+  rc = chol_enqueue<T>(h, A22, ld, np, nb, Winv + (c / KB) * (KB * KB), P0, P0 + (np + nx) * ldp, ldp, info, gidx0 + c, profile,
+                       nx, &iw2, 0, rs);
+  iw->seq = iw2.seq;
+  return rc;
 }
 
 // XT (rows x n, ld) <- XT * L^-T   (i.e. X <- L^-1 X for X = XT^T), block forward substitution.
@@ -1408,9 +1511,15 @@ int fit_impl(gpx_handle* h, const void* X, const void* y, int64_t N, int32_t d, 
       PhaseScope ps(h, &tm.chol);
       launch_pack_rhs<T>((const T*)h->Y.p, N, k, dYT, ld, Npad, RHS_ROWS, h->st);
       if (bp) launch_basis_rows<T>((const T*)h->X.p, N, Npad, d, k, bp, dYT, ld, h->st);  // rows [k, k + bp): H^T -> Z_H^T
-      if ((rc = chol_enqueue<T>(h, dK, ld, Npad, h->nb, (T*)h->Winv.p, (T*)h->P.p,
-                                (T*)h->P.p + (Npad + NX) * ldp, ldp, dInfo, 0, profile, NX, &iw, Mpad)))
-        return rc;
+      // gpx_fit proper on two levels from GPX_TWO_LEVEL_FROM rows on (chol_two_level_enqueue); gpx_fit_predict's query
+      // rows and the mixed mode's fp32 fit keep the one-level schedule
+      if (!Xq && h->cfg.dtype != GPX_MIXED)
+        rc = chol_two_level_enqueue<T>(h, dK, ld, Npad, h->nb, (T*)h->Winv.p, (T*)h->P.p, (T*)h->P.p + (Npad + NX) * ldp, ldp,
+                                       dInfo, 0, profile, NX, &iw, Mpad);
+      else
+        rc = chol_enqueue<T>(h, dK, ld, Npad, h->nb, (T*)h->Winv.p, (T*)h->P.p, (T*)h->P.p + (Npad + NX) * ldp, ldp, dInfo, 0,
+                             profile, NX, &iw, Mpad);
+      if (rc) return rc;
     }
     if (bp) {  // beta = (Z_H^T Z_H)^-1 Z_H^T z, then z' = z - Z_H beta in place: every reader of zT from here on sees z'
       PhaseScope ps(h, &tm.solve);
@@ -4267,7 +4376,8 @@ int gpx_potrf(double* A, int64_t n, int32_t block, int64_t* info) try {
   if ((rc = flag_handover_probe(&sc.h))) return fail(nullptr, rc, sc.h.err.c_str());
   UCHK(hipMemcpy2DAsync(dA, (size_t)ld * 8, A, (size_t)n * 8, (size_t)n * 8, (size_t)n, hipMemcpyHostToDevice, sc.st));
   UCHK(hipMemcpyAsync(dInfo, &hinfo, sizeof(int), hipMemcpyHostToDevice, sc.st));
-  if ((rc = chol_enqueue(&sc.h, (double*)dA, ld, n, nb, (double*)dW, (double*)dP, dP + n * ldp, ldp, dInfo, 0, false, 0, &iw)))
+  if ((rc = chol_two_level_enqueue(&sc.h, (double*)dA, ld, n, nb, (double*)dW, (double*)dP, dP + n * ldp, ldp, dInfo, 0, false,
+                                   0, &iw)))
     return rc;
   UCHK(hipMemcpy2DAsync(A, (size_t)n * 8, dA, (size_t)ld * 8, (size_t)n * 8, (size_t)n, hipMemcpyDeviceToHost, sc.st));
   UCHK(hipMemcpyAsync(&hinfo, dInfo, sizeof(int), hipMemcpyDeviceToHost, sc.st));
@@ -4329,7 +4439,17 @@ int gpx_gemm_nt(double* C, int64_t m, int64_t n, const double* A, const double* 
   UCHK(hipMemcpy2DAsync(dC, (size_t)ldc * 8, C, (size_t)n * 8, (size_t)n * 8, (size_t)m, hipMemcpyHostToDevice, sc.st));
   UCHK(hipMemcpy2DAsync(dA, (size_t)lda * 8, A, (size_t)k * 8, (size_t)k * 8, (size_t)m, hipMemcpyHostToDevice, sc.st));
   UCHK(hipMemcpy2DAsync(dB, (size_t)lda * 8, B, (size_t)k * 8, (size_t)k * 8, (size_t)n, hipMemcpyHostToDevice, sc.st));
-  launch_gemm_nt_fixed<double>(tile, dC, ldc, dA, lda, dB, lda, m, n, k, lower, 0, sc.st);
+  // GPX_STRASSEN_MIN > 0: a rectangular product whose quadrants are at least that large takes one Strassen level
+  const int64_t smin = sc.h.env.strassen_min;
+  if (!lower && smin > 0 && std::min(m, n) >= 256 && std::min(m, n) / 256 * 128 >= smin) {
+    Dev<double> dT;
+    const int64_t ldt = k / 2 + LD_SKEW;
+    if (int rc = dT.alloc(strassen_temp_elems(m, n, k, LD_SKEW))) return rc;
+    strassen_nt<double>(dC, ldc, dA, lda, dB, lda, m, n, k, dT, dT + (m / 256 * 128) * ldt, ldt, sc.st);
+    UCHK(hipStreamSynchronize(sc.st));  // (dT goes out of scope)
+  } else {
+    launch_gemm_nt_fixed<double>(tile, dC, ldc, dA, lda, dB, lda, m, n, k, lower, 0, sc.st);
+  }
   UCHK(hipMemcpy2DAsync(C, (size_t)n * 8, dC, (size_t)ldc * 8, (size_t)n * 8, (size_t)m, hipMemcpyDeviceToHost, sc.st));
   return sc.finish();
 }
@@ -4375,10 +4495,20 @@ int gemm_bench_t(int64_t n, int64_t k, int32_t lower, int32_t mode, int32_t iter
   UCHK(hipMemsetAsync(dA, 0, (size_t)2 * n * lda * sizeof(T), sc.st));
   hipEvent_t e0 = next_event(&sc.h), e1 = next_event(&sc.h);  // (the Scratch handle's pool destroys them)
   if (!e0 || !e1) return fail(nullptr, GPX_E_HIP, "hipEventCreate failed");
-  launch_gemm_nt_fixed<T>(128, dC, ldc, dA, lda, dA + n * lda, lda, n, n, k, lower, mode, sc.st);
+  Dev<T> dT;  // mode 2: C -= A A'^T through strassen_nt (one launch = the whole level: ten sums, seven products)
+  const int64_t ldt = k / 2 + ld_skew<T>();
+  if (mode == 2) {
+    if (int rc = dT.alloc(strassen_temp_elems(n, n, k, ld_skew<T>()))) return rc;
+  }
+  auto once = [&] {
+    if (mode == 2)
+      strassen_nt<T>(dC, ldc, dA, lda, dA + n * lda, lda, n, n, k, dT, dT + (n / 256 * 128) * ldt, ldt, sc.st);
+    else
+      launch_gemm_nt_fixed<T>(128, dC, ldc, dA, lda, dA + n * lda, lda, n, n, k, lower, mode, sc.st);
+  };
+  once();
   UCHK(hipEventRecord(e0, sc.st));
-  for (int i = 0; i < iters; ++i)
-    launch_gemm_nt_fixed<T>(128, dC, ldc, dA, lda, dA + n * lda, lda, n, n, k, lower, mode, sc.st);
+  for (int i = 0; i < iters; ++i) once();
   UCHK(hipEventRecord(e1, sc.st));
   if (int rc = sc.finish()) return rc;
   UCHK(hipEventElapsedTime(&t, e0, e1));
@@ -4390,7 +4520,7 @@ int gemm_bench_t(int64_t n, int64_t k, int32_t lower, int32_t mode, int32_t iter
 int gpx_debug_gemm_bench(int32_t dtype, int64_t n, int64_t k, int32_t lower, int32_t mode, int32_t iters,
                          double* ms_per_launch) try {
   if (!ms_per_launch || n <= 0 || n % 128 || k <= 0 || k % 32 || iters <= 0 || (lower != 0 && lower != 1) ||
-      (mode != 0 && mode != 1) || n > 131072 || k > 8192)
+      (mode != 0 && mode != 1 && mode != 2) || (mode == 2 && (lower != 0 || n % 256 || k % 64)) || n > 131072 || k > 32768)
     return GPX_E_ARG;
   if (dtype == GPX_F64) return gemm_bench_t<double>(n, k, lower, mode, iters, ms_per_launch);
   if (dtype == GPX_F32) return gemm_bench_t<float>(n, k, lower, mode, iters, ms_per_launch);

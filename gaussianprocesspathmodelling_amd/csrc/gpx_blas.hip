@@ -189,6 +189,43 @@ __global__ __launch_bounds__(256, (BT == 64 && KSUB >= 4) ? 1 : 2) void gemm_nt_
 #endif
 }
 
+// ---- the products of a Strassen level (strassen_nt) -------------------------------------------------
+// acc = A B^T on the rectangular 128-tile grid of gemm_nt_kernel<T, 128, false, ...>, then C1 += s1 acc and (C2 not
+// null) C2 += s2 acc: the same k-loop, the two-target epilogue (store_tile_two).  C1 and C2 are quadrants of one
+// matrix (one ldc).
+template <typename T, int BT>
+__global__ __launch_bounds__(256, 2) void gemm_nt_two_kernel(T* __restrict__ C1, T* __restrict__ C2, int64_t ldc, T s1,
+                                                             T s2, const T* __restrict__ A, int64_t lda,
+                                                             const T* __restrict__ B, int64_t ldb, int tiles_m,
+                                                             int tiles_n, int sh, int K) {
+  __shared__ __attribute__((aligned(16))) T smem[TileShapeG<T, BT, BT, 1>::SMEM_ELEMS];
+  const int64_t lin = xcd_chunk_id(blockIdx.x, gridDim.x);
+  int ti, tj;
+  if (!tile_coords<false>(lin, tiles_m, tiles_n, sh, 0, BcMask{0, 1, 0}, ti, tj)) return;
+  typename Num<T>::v4 acc[BT / 32][BT / 32];
+  zero_acc(acc);
+  gemm_tile_g<T, BT, BT, 2, 1>(A + (int64_t)ti * BT * lda, lda, B + (int64_t)tj * BT * ldb, ldb, K, acc, smem);
+  const int64_t o = (int64_t)ti * BT * ldc + (int64_t)tj * BT;
+  store_tile_two<T, BT, BT>(C1 + o, C2 ? C2 + o : nullptr, ldc, s1, s2, acc);
+}
+
+// out (rows x cols, ldo) = X + sign * Y: the operand sums of a Strassen level.  One 16-byte element per lane,
+// non-temporal, the grid sized to the data (the form of a copy that reaches the stream rate on this chip; a
+// grid-stride loop does not).  cols is a multiple of 16 / sizeof(T); rows of all three start on 16-byte boundaries.
+template <typename T>
+__global__ __launch_bounds__(256) void operand_sum_kernel(T* __restrict__ out, int64_t ldo, const T* __restrict__ X,
+                                                          int64_t ldx, const T* __restrict__ Y, int64_t ldy,
+                                                          int64_t rows, int vpr, T sign) {
+  typedef T V __attribute__((ext_vector_type(16 / sizeof(T))));
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t r = idx / vpr;
+  if (r >= rows) return;
+  const int64_t c = (idx - r * vpr) * (int64_t)(16 / sizeof(T));
+  const V x = __builtin_nontemporal_load(reinterpret_cast<const V*>(X + r * ldx + c));
+  const V y = __builtin_nontemporal_load(reinterpret_cast<const V*>(Y + r * ldy + c));
+  __builtin_nontemporal_store(x + sign * y, reinterpret_cast<V*>(out + r * ldo + c));
+}
+
 // block id -> tile of the fused launch (also replayed on the host: gpx_debug_tile_map kind 2)
 __host__ __device__ __forceinline__ bool fused_coords(int64_t bid, int64_t grid, int S, int tiles_m, int tiles_s, int sh,
                                                      int& ti, int& tj) {
@@ -1325,6 +1362,74 @@ void launch_gemm_nt(int tile, T* C, int64_t ldc, const T* A, int64_t lda, const 
   launch_gemm_nt_fixed<T>(gemm_nt_tile(tile, m, n, lower), C, ldc, A, lda, B, ldb, m, n, k, lower, mode, st);
 }
 
+// ---- C -= A B^T with one Strassen level (Strassen 1969: seven half-size products instead of eight) ------------------
+// The part with m, n multiples of 256 and k a multiple of two k-steps goes through the level; what is ragged — the last
+// < 256 rows or columns, the k remainder — is peeled off and done by the classical launches.  With the quadrants
+//   A = [A1 A2; A3 A4]  (rows x k),   B = [B1 B2; B3 B4]  (rows x k),   C = [C11 C12; C21 C22]:
+//   M1 = (A1 + A4)(B1 + B4)^T -> C11, C22      M2 = (A3 + A4) B1^T -> C21, -C22     M3 = A1 (B3 - B4)^T -> C12, C22
+//   M4 = A4 (B2 - B1)^T -> C11, C21            M5 = (A1 + A2) B4^T -> -C11, C12     M6 = (A3 - A1)(B1 + B3)^T -> C22
+//   M7 = (A2 - A4)(B2 + B4)^T -> C11           (the targets take -M; a minus sign in the list: +M)
+// TA (m/2 rows) and TB (n/2 rows), k/2 columns at ldt, hold the operand sums: ten passes, five each.
+// ORDER: everything goes out on ONE stream in the order written here — sum(s), product, next sum(s) ... — so a
+// temporary is rewritten only after the product that read it, every element of a C quadrant receives at most one addend
+// per launch, and the addends arrive in the fixed order M1 .. M7, then the peeled parts: the result is deterministic and
+// repeatable bit for bit, whatever runs beside it.
+// Returns the flops executed (2 m n k where classical, 7/8 of that for the part that went through the level).
+size_t strassen_temp_elems(int64_t m, int64_t n, int64_t k, int skew) {
+  const int64_t m0 = m / 256 * 256, n0 = n / 256 * 256;
+  return (size_t)((m0 + n0) / 2) * (size_t)(k / 2 + skew);
+}
+
+template <typename T>
+double strassen_nt(T* C, int64_t ldc, const T* A, int64_t lda, const T* B, int64_t ldb, int64_t m, int64_t n,
+                   int64_t k, T* TA, T* TB, int64_t ldt, hipStream_t st) {
+  constexpr int64_t K2 = 2 * Num<T>::BK, VE = 16 / sizeof(T);
+  const int64_t m0 = m / 256 * 256, n0 = n / 256 * 256, k0 = k / K2 * K2;
+  auto classical = [&](T* Cc, const T* Ac, const T* Bc, int64_t mm, int64_t nn, int64_t kk) {
+    if (mm <= 0 || nn <= 0 || kk <= 0) return;
+    launch_gemm_nt<T>((mm % 128 == 0 && nn % 128 == 0) ? 128 : 64, Cc, ldc, Ac, lda, Bc, ldb, mm, nn, kk, 0, 0, st);
+  };
+  auto aligned = [](const void* p, int64_t ld) { return (uintptr_t)p % 16 == 0 && ld % VE == 0; };
+  const bool level = m0 > 0 && n0 > 0 && k0 > 0 && TA && TB && ldt >= k0 / 2 && aligned(A, lda) && aligned(B, ldb) &&
+                     aligned(TA, ldt) && aligned(TB, ldt);
+  if (!level) {
+    classical(C, A, B, m, n, k);
+    return 2.0 * (double)m * (double)n * (double)k;
+  }
+  const int64_t mh = m0 / 2, nh = n0 / 2, kh = k0 / 2;
+  const T *A1 = A, *A2 = A + kh, *A3 = A + mh * lda, *A4 = A3 + kh;
+  const T *B1 = B, *B2 = B + kh, *B3 = B + nh * ldb, *B4 = B3 + kh;
+  T *C11 = C, *C12 = C + nh, *C21 = C + mh * ldc, *C22 = C21 + nh;
+  const int vpr = (int)(kh / VE);
+  auto sum = [&](T* out, const T* X, const T* Y, int64_t ldxy, int64_t rows, T sign) {
+    debug_delay(st);
+    hipLaunchKernelGGL(operand_sum_kernel<T>, dim3((unsigned)((rows * vpr + 255) / 256)), dim3(256), 0, st, out, ldt, X,
+                       ldxy, Y, ldxy, rows, vpr, sign);
+  };
+  int sh;
+  const dim3 grid((unsigned)rect_grid(mh / 128, nh / 128, sh));
+  // C1 += s1 X Y^T, C2 += s2 X Y^T (C2 may be null)
+  auto product = [&](const T* X, int64_t ldx, const T* Y, int64_t ldy, T* C1, T s1, T* C2, T s2) {
+    debug_delay(st);
+    hipLaunchKernelGGL((gemm_nt_two_kernel<T, 128>), grid, dim3(256), 0, st, C1, C2, ldc, s1, s2, X, ldx, Y, ldy,
+                       (int)(mh / 128), (int)(nh / 128), sh, (int)kh);
+  };
+  const T p = (T)1, q = (T)-1;
+  sum(TA, A1, A4, lda, mh, p), sum(TB, B1, B4, ldb, nh, p), product(TA, ldt, TB, ldt, C11, q, C22, q);  // M1
+  sum(TA, A3, A4, lda, mh, p), product(TA, ldt, B1, ldb, C21, q, C22, p);                               // M2
+  sum(TB, B3, B4, ldb, nh, q), product(A1, lda, TB, ldt, C12, q, C22, q);                               // M3
+  sum(TB, B2, B1, ldb, nh, q), product(A4, lda, TB, ldt, C11, q, C21, q);                               // M4
+  sum(TA, A1, A2, lda, mh, p), product(TA, ldt, B4, ldb, C11, p, C12, q);                               // M5
+  sum(TA, A3, A1, lda, mh, q), sum(TB, B1, B3, ldb, nh, p), product(TA, ldt, TB, ldt, C22, q, (T*)nullptr, p);  // M6
+  sum(TA, A2, A4, lda, mh, q), sum(TB, B2, B4, ldb, nh, p), product(TA, ldt, TB, ldt, C11, q, (T*)nullptr, p);  // M7
+  // the peeled parts, classical: the k remainder of the level's block, the columns right of it, the rows below it
+  classical(C, A + k0, B + k0, m0, n0, k - k0);
+  classical(C + n0, A, B + n0 * ldb, m0, n - n0, k);
+  classical(C + m0 * ldc, A + m0 * lda, B, m - m0, n, k);
+  const double full = 2.0 * (double)m * (double)n * (double)k, lvl = 2.0 * (double)m0 * (double)n0 * (double)k0;
+  return full - lvl / 8.0;
+}
+
 // The fused trailing update (gemm_nt_fused_kernel): C (n x n) -= P P^T, lower part, strip of `ns`
 // columns first; returns the number of strip slots (each adds 1 to *ctr when its tile is released).
 template <typename T>
@@ -1447,6 +1552,8 @@ extern "C" int gpx_debug_read_syrk_clock(long long* out) {
                                      int64_t, int64_t, const BcMask&, hipStream_t);                     \
   template void launch_gemm_nn<T>(T*, int64_t, const T*, int64_t, const T*, int64_t, int64_t, int64_t,  \
                                   int64_t, hipStream_t);                                                \
+  template double strassen_nt<T>(T*, int64_t, const T*, int64_t, const T*, int64_t, int64_t, int64_t,   \
+                                 int64_t, T*, T*, int64_t, hipStream_t);                                \
   template void launch_gemm_nt_splitk<T>(T*, int64_t, const T*, int64_t, const T*, int64_t, int64_t,    \
                                          int64_t, int64_t, int, T*, int64_t, hipStream_t);
 GPX_INSTANTIATE_BLAS(double)

@@ -49,7 +49,12 @@ inline int64_t in_range(int64_t v, int64_t lo, int64_t hi, int64_t otherwise) { 
   X("GPX_RESV_ALL", resv_all, Flag, call, false, env_rule::flag(e))                                                    \
   X("GPX_RESV_CHAIN", resv_chain, Int, call, 1, atoi(e))                                                               \
   X("GPX_RESV_FORM", resv_form, Int, call, 1, atoi(e))                                                                 \
-  /* widths and batches */                                                                                             \
+  /* the two-level Cholesky (chol_two_level_enqueue) and its Strassen level (strassen_nt) */                           \
+  X("GPX_TWO_LEVEL_FROM", two_level_from, I64, call, 65536, env_rule::in_range(atoll(e), 0, 1L << 40, 0))                  \
+  X("GPX_STRASSEN_MIN", strassen_min, I64, call, 4096, env_rule::in_range(atoll(e), 0, 1L << 40, 0) / 128 * 128)          \
+  X("GPX_STRASSEN_DIAG", strassen_diag, Flag, call, false, env_rule::flag(e))                                          \
+  X("GPX_STRASSEN_SINGLE", strassen_f32, Flag, call, false, env_rule::flag(e))                                            \
+  /* widths and batches */                                                                                          \
   X("GPX_NB_WIDE_FROM", nb_wide_from, I64, call, 40960, (int64_t)atoll(e))                                             \
   X("GPX_NB_GRAD", nb_grad, Int, call, 0, env_rule::block(e, 4096, 0))                                                 \
   X("GPX_NB_SOLVE", nb_solve, Int, create, 256, env_rule::block(e, 4096, 256))                                         \

@@ -200,6 +200,14 @@ int gemm_nt_tile(int tile, int64_t m, int64_t n, int lower);
 template <typename T>
 void launch_gemm_nt_fixed(int tile, T* C, int64_t ldc, const T* A, int64_t lda, const T* B, int64_t ldb,
                     int64_t m, int64_t n, int64_t k, int lower, int mode, hipStream_t st);
+// C (m x n) -= A B^T with one Strassen level on the part with m, n multiples of 256 (gpx_blas.hip: the order of its
+// launches, and why the result is repeatable bit for bit); m, n multiples of 64, k a multiple of the k-step.  TA | TB:
+// strassen_temp_elems(m, n, k, skew) elements, TB = TA + (m / 256 * 128) * ldt, ldt = k / 2 + skew.  Null temporaries,
+// or a shape with nothing for the level: the classical launch.  Returns the flops executed.
+size_t strassen_temp_elems(int64_t m, int64_t n, int64_t k, int skew);
+template <typename T>
+double strassen_nt(T* C, int64_t ldc, const T* A, int64_t lda, const T* B, int64_t ldb, int64_t m, int64_t n,
+                   int64_t k, T* TA, T* TB, int64_t ldt, hipStream_t st);
 // The whole trailing update of a panel in one launch: C (n x n, 128-tiles, lower) -= P P^T (P: n x k, ldp)
 // with the first ns columns (the strip that becomes the next panel) enumerated first; every strip slot
 // adds 1 to *ctr once its tile is released at device scope.  Returns the number of strip slots.

@@ -309,6 +309,31 @@ __device__ __forceinline__ void store_tile(T* C, int64_t ldc,
   }
 }
 
+// Two-target form of MODE 0 (the products of strassen_nt): C1 += s1 * acc and, when C2 is not null, C2 += s2 * acc, s1 and
+// s2 each +1 or -1 (the multiplication is exact).  As in MODE 0 every element of either target receives exactly ONE addend
+// per launch, by a no-return atomic.  A function of its own, so that store_tile's instantiations stay what they are.
+template <typename T, int BM, int BN, int WVM = 2>
+__device__ __forceinline__ void store_tile_two(T* C1, T* C2, int64_t ldc, T s1, T s2,
+                                               const typename Num<T>::v4 (&acc)[BM / (16 * WVM)][BN / 32]) {
+  constexpr int NT = BN / 32;
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const int wr = wave >> 1, wc = wave & 1;
+  const int l4 = lane >> 4;
+  const int64_t w0 = (int64_t)(wr * (BM / WVM)) * ldc + wc * (BN / 2) + (lane & 15);
+#pragma unroll
+  for (int m = 0; m < BM / (16 * WVM); ++m) {
+#pragma unroll
+    for (int n = 0; n < NT; ++n)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int64_t o = w0 + (int64_t)(m * 16 + Num<T>::drow(l4, r)) * ldc + n * 16;
+        unsafeAtomicAdd(C1 + o, s1 * acc[m][n][r]);
+        if (C2) unsafeAtomicAdd(C2 + o, s2 * acc[m][n][r]);
+      }
+  }
+}
+
 // blocks are dealt round-robin over the 8 XCDs; give each XCD one contiguous chunk of
 // the logical tile order so that neighbouring tiles share an L2 (speed only).
 __host__ __device__ __forceinline__ int64_t xcd_chunk_id(int64_t bid, int64_t nblk) {
