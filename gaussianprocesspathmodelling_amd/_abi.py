@@ -97,6 +97,11 @@ SIGNATURES = {
     "gpx_kernel_path_grad_matrix": (C.c_int, [C.c_int32, C.c_int32, _PD, C.POINTER(C.c_int32), C.c_int64, _PD,
                                               C.POINTER(C.c_int32), C.c_int64, C.c_int32, _PD, C.c_int32, C.c_double, _PD,
                                               C.c_int32, C.c_double, _PD]),
+    "gpx_predict_hess": (C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int32]),
+    "gpx_predict_hess_paths": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, C.c_int32]),
+    "gpx_kernel_hess_matrix": (C.c_int, [C.c_int32, C.c_int32, _PD, C.POINTER(C.c_int32), C.c_int64, _PD,
+                                         C.POINTER(C.c_int32), C.c_int64, C.c_int32, _PD, C.c_int32, C.c_double, _PD,
+                                         C.c_int32, C.c_double, _PD]),
     "gpx_append_weighted": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int32, C.POINTER(C.c_int64)]),
     "gpx_append_rows": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int64, C.c_int32, C.POINTER(C.c_int64)]),
     "gpx_remove_rows": (C.c_int, [_P, C.c_int64, C.c_int64, C.POINTER(C.c_int64)]),

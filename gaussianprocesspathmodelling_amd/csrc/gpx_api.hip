@@ -256,6 +256,10 @@ bool path_ls_ok(const double* ls_path, int32_t n) {
 
 // the refusal of gpx_predict_grad / gpx_kernel_deriv_matrix: k = sf2 e^-r has a kink at r = 0
 #define MATERN12_NO_GRAD "Matern-1/2 is not differentiable (its sample paths have no derivative)"
+// the refusals of gpx_predict_hess / gpx_kernel_hess_matrix
+#define NOT_TWICE_DIFFERENTIABLE \
+  "the kernel is not twice differentiable (only RBF and Matern-5/2 sample paths have a second derivative)"
+#define HESS_D_LIMIT "second derivatives are built for at most 8 input dimensions (d > 8)"
 
 #define LAUNCHCHK(h)                                                                                  \
   do {                                                                                                \
@@ -2542,15 +2546,30 @@ int score_impl(gpx_handle* h, const void* Xq, const void* yq, const void* wq, in
 // (nblk row blocks of mp rows each) -> ONE forward solve over the nblk mp rows -> ONE split-K z^T V (mean and dmean
 // together) -> row norms against the per-block prior -> unpack.  Every buffer is scratch of its own (G*): the fit is only
 // read, so gpx_predict afterwards is bit-identical.
+// gpx_predict_hess is the same two routes with `order` = 2: the hess_pairs(d) second derivatives per query
+// point in place of the d first ones (nd below), no value rows, gpx_hess.hip's build and matrix-free product.
 
 // prior[b] of the row blocks: sf2 (value rows), then Var[d f / d x_j] = cov::grad_prior sf2 / l_j^2.
 // prior_path != null (a fit with path ids): what a query point with a path id adds, sg2 and
 // Var[d g_p / d x_j] = cov::grad_prior sg2 / l_path,j^2 = cov::grad_prior sg2 q_j / l_j^2.
-int grad_priors(gpx_handle* h, bool with_value, double* prior, double* prior_path = nullptr) {
+// order 2 (gpx_predict_hess): the pairs (i, j), i <= j, instead: Var[d_i d_j f] = c2 sf2 / (l_i^2 l_j^2), three
+// times that for i == j, c2 = cov::hess_prior; a path id adds the same in sg2 and l_path (1 / l_path,j^2 = q_j / l_j^2).
+int grad_priors(gpx_handle* h, bool with_value, double* prior, double* prior_path = nullptr, int order = 1) {
   double ls[MAX_D];
   HIPCHK(h, hipMemcpyAsync(ls, h->ls.p, (size_t)h->n_ls * sizeof(double), hipMemcpyDeviceToHost, h->st));
   HIPCHK(h, hipStreamSynchronize(h->st));
   int b = 0;
+  if (order == 2) {
+    const double c2 = cov::hess_prior(h->cfg.kernel);
+    for (int i = 0; i < h->d; ++i)
+      for (int j = i; j < h->d; ++j) {
+        const double li = ls[h->n_ls == 1 ? 0 : i], lj = ls[h->n_ls == 1 ? 0 : j];
+        const double w = (i == j ? 3.0 : 1.0) * c2 / (li * li * lj * lj);
+        if (prior_path) prior_path[b] = w * h->sg2 * h->q_fit[(size_t)i] * h->q_fit[(size_t)j];
+        prior[b++] = w * h->sf2;
+      }
+    return GPX_OK;
+  }
   if (with_value) {
     if (prior_path) prior_path[b] = h->sg2;
     prior[b++] = h->sf2;
@@ -2565,8 +2584,9 @@ int grad_priors(gpx_handle* h, bool with_value, double* prior, double* prior_pat
 }
 
 template <typename T>
-int predict_grad_mean_only(gpx_handle* h, const void* Xq, int64_t M, void* mean, void* dmean, int32_t mem_kind) {
+int predict_grad_mean_only(gpx_handle* h, const void* Xq, int64_t M, void* mean, void* dmean, int32_t mem_kind, int order) {
   const int d = h->d, k = h->k;
+  const int nd = order == 2 ? hess_pairs(d) : d;  // derivatives per query point and target
   gpx_timings& tm = h->tm;
   int rc;
   int KC = 1, S = 1;
@@ -2580,35 +2600,36 @@ int predict_grad_mean_only(gpx_handle* h, const void* Xq, int64_t M, void* mean,
     PhaseScope ps(h, &tm.kstar);
     if ((rc = upload_queries<T>(h, Xq, M, mem_kind))) return rc;
   }
-  if ((rc = ensure(h, h->scr.GPart, (size_t)S * k * d * round_up(M, 64) * sizeof(T)))) return rc;
-  if ((rc = ensure(h, h->scr.GOut, (size_t)M * d * k * sizeof(T)))) return rc;
+  if ((rc = ensure(h, h->scr.GPart, (size_t)S * k * nd * round_up(M, 64) * sizeof(T)))) return rc;
+  if ((rc = ensure(h, h->scr.GOut, (size_t)M * nd * k * sizeof(T)))) return rc;
   {
     PhaseScope ps(h, &tm.mean);
-    launch_kgrad_matvec<T>(h->cfg.kernel, (const T*)h->scr.Qs.p, M, (const T*)h->Xs.p, h->Npad, d, h->sf2,
-                           (const T*)h->alphaT, h->ld, k, (const double*)h->ls.p, h->n_ls, (T*)h->scr.GPart.p,
-                           (T*)h->scr.GOut.p, h->st);
+    const auto matvec = order == 2 ? launch_khess_matvec<T> : launch_kgrad_matvec<T>;  // (one signature)
+    matvec(h->cfg.kernel, (const T*)h->scr.Qs.p, M, (const T*)h->Xs.p, h->Npad, d, h->sf2, (const T*)h->alphaT, h->ld, k,
+           (const double*)h->ls.p, h->n_ls, (T*)h->scr.GPart.p, (T*)h->scr.GOut.p, h->st);
   }
   PhaseScope ps(h, &tm.d2h);
   if (mean && (rc = copy_out(h, mean, h->meanout.p, (size_t)M * k * sizeof(T), mem_kind))) return rc;
-  return copy_out(h, dmean, h->scr.GOut.p, (size_t)M * d * k * sizeof(T), mem_kind);
+  return copy_out(h, dmean, h->scr.GOut.p, (size_t)M * nd * k * sizeof(T), mem_kind);
 }
 
 template <typename T>
 int predict_grad_var(gpx_handle* h, const void* Xq, int64_t M, void* mean, void* var, void* dmean, void* dvar,
-                     int32_t mem_kind, const char* fn, const int32_t* gq = nullptr) {
+                     int32_t mem_kind, const char* fn, const int32_t* gq, int order) {
   const int64_t N = h->N, Npad = h->Npad, ld = h->ld;
   const int d = h->d, k = h->k;
+  const int nd = order == 2 ? hess_pairs(d) : d;  // derivatives per query point and target: dmean (M, nd, k), dvar (M, nd)
   const size_t E = sizeof(T);
   const int64_t Mpad = round_up(M, TILE);
-  const bool with_value = mean || var;
-  const int nblk = d + (with_value ? 1 : 0);
+  const bool with_value = mean || var;  // (never with order 2)
+  const int nblk = nd + (with_value ? 1 : 0);
   const int ksplit = splitk_splits(Npad);
   const bool dense = h->nbw == h->nb_pred;  // the fit's block inverses, same block width: dense block solves
   const int64_t ldt = h->nbw + ld_skew<T>();
   // device bytes per padded query point of a batch (V, block-solve buffers, z^T V and its split-K partials, norms),
   // and the fixed part (queries, outputs, the skew columns of the product buffers)
   const double per_pt = (double)E * nblk * ((double)ld + (dense ? 2.0 * ldt : 0.0) + RHS_ROWS * (1.0 + ksplit) + 1.0);
-  const double fixed = (double)E * ((double)M * d + (double)Mpad * d + (double)M * (k + 1) * (d + 1) +
+  const double fixed = (double)E * ((double)M * d + (double)Mpad * d + (double)M * (k + 1) * (nd + 1) +
                                     (double)RHS_ROWS * ld_skew<T>() * (1 + ksplit)) + 4096.0;
   const size_t have = h->scr.GV.cap + h->scr.GTsol.cap + h->scr.GMT.cap + h->scr.GMTpart.cap + h->scr.GVN.cap + h->scr.GOut.cap;
   size_t freeb = 0, totalb = 0;
@@ -2624,15 +2645,15 @@ int predict_grad_var(gpx_handle* h, const void* Xq, int64_t M, void* mean, void*
   const int64_t MB = std::min(pred_batch_rows(h, Mpad, 0, false), std::max<int64_t>(128, fit));
   const int64_t RB = nblk * MB;                 // rows of the largest batch
   const int64_t ldm = RB + ld_skew<T>();        // z^T V of one batch
-  double prior[MAX_D + 1], prior_path[MAX_D + 1];
+  double prior[PRIOR_SLOTS], prior_path[PRIOR_SLOTS];
   int rc;
-  if ((rc = grad_priors(h, with_value, prior, gq ? prior_path : nullptr))) return rc;
+  if ((rc = grad_priors(h, with_value, prior, gq ? prior_path : nullptr, order))) return rc;
   if ((rc = ensure_queries<T>(h, M))) return rc;
   if ((rc = ensure(h, h->scr.GV, (size_t)RB * ld * E))) return rc;
   if ((rc = ensure(h, h->scr.GMT, (size_t)RHS_ROWS * ldm * E))) return rc;
   if ((rc = ensure_mean_partials<T>(h, h->scr.GMTpart, ldm))) return rc;
   if ((rc = ensure(h, h->scr.GVN, (size_t)RB * E))) return rc;
-  const int64_t o_dvar = M * d * k, o_mean = o_dvar + M * d, o_var = o_mean + M * k;
+  const int64_t o_dvar = M * nd * k, o_mean = o_dvar + M * nd, o_var = o_mean + M * k;
   if ((rc = ensure(h, h->scr.GOut, (size_t)(o_var + M) * E))) return rc;
   SolveWork<T> sw;
   if ((rc = dense_solve_work<T>(h, h->scr.GTsol, RB, &sw))) return rc;
@@ -2652,14 +2673,18 @@ int predict_grad_var(gpx_handle* h, const void* Xq, int64_t M, void* mean, void*
     const int64_t ldb = R + ld_skew<T>();
     {
       PhaseScope ps(h, &tm.kstar);
-      if (dg)
+      const int32_t* kfit = h->kinded ? (const int32_t*)h->Kfit.p : nullptr;
+      if (order == 2)
+        launch_khess_build<T>(h->cfg.kernel, (const T*)h->scr.Qs.p + m0 * d, dg ? dg + m0 : nullptr, mv, mp, (const T*)h->Xs.p,
+                              dg ? (const int32_t*)h->Gfit.p : kfit, N, Npad, d, h->sf2, (const double*)h->ls.p, h->n_ls,
+                              dg ? (const double*)h->Gq.p : nullptr, h->sg2, dV, ld, h->st);
+      else if (dg)
         launch_kgrad_build_g<T>(h->cfg.kernel, (const T*)h->scr.Qs.p + m0 * d, dg + m0, mv, mp, (const T*)h->Xs.p,
                                 (const int32_t*)h->Gfit.p, N, Npad, d, h->sf2, (const double*)h->ls.p, h->n_ls,
                                 (const double*)h->Gq.p, h->sg2, with_value ? 1 : 0, dV, ld, h->st);
       else
         launch_kgrad_build<T>(h->cfg.kernel, (const T*)h->scr.Qs.p + m0 * d, mv, mp, (const T*)h->Xs.p, N, Npad, d, h->sf2,
-                              (const double*)h->ls.p, h->n_ls, with_value ? 1 : 0, dV, ld, h->st,
-                              h->kinded ? (const int32_t*)h->Kfit.p : nullptr);
+                              (const double*)h->ls.p, h->n_ls, with_value ? 1 : 0, dV, ld, h->st, kfit);
     }
     {
       PhaseScope ps(h, &tm.trsm);
@@ -2676,13 +2701,13 @@ int predict_grad_var(gpx_handle* h, const void* Xq, int64_t M, void* mean, void*
     }
     {
       PhaseScope ps(h, &tm.mean);
-      launch_grad_unpack<T>((const T*)h->scr.GMT.p, ldb, (const T*)h->scr.GVN.p, mp, mv, nblk, d, k, with_value ? 1 : 0,
-                            out + o_mean + m0 * k, out + o_var + m0, out + m0 * d * k, out + o_dvar + m0 * d, h->st);
+      launch_grad_unpack<T>((const T*)h->scr.GMT.p, ldb, (const T*)h->scr.GVN.p, mp, mv, nblk, nd, k, with_value ? 1 : 0,
+                            out + o_mean + m0 * k, out + o_var + m0, out + m0 * nd * k, out + o_dvar + m0 * nd, h->st);
     }
   }
   PhaseScope ps(h, &tm.d2h);
-  if ((rc = copy_out(h, dmean, out, (size_t)M * d * k * E, mem_kind))) return rc;
-  if (dvar && (rc = copy_out(h, dvar, out + o_dvar, (size_t)M * d * E, mem_kind))) return rc;
+  if ((rc = copy_out(h, dmean, out, (size_t)M * nd * k * E, mem_kind))) return rc;
+  if (dvar && (rc = copy_out(h, dvar, out + o_dvar, (size_t)M * nd * E, mem_kind))) return rc;
   if (mean && (rc = copy_out(h, mean, out + o_mean, (size_t)M * k * E, mem_kind))) return rc;
   if (var && (rc = copy_out(h, var, out + o_var, (size_t)M * E, mem_kind))) return rc;
   return GPX_OK;
@@ -2690,17 +2715,16 @@ int predict_grad_var(gpx_handle* h, const void* Xq, int64_t M, void* mean, void*
 
 template <typename T>
 int predict_grad_impl(gpx_handle* h, const void* Xq, int64_t M, void* mean, void* var, void* dmean, void* dvar,
-                      int32_t mem_kind, const int32_t* gq = nullptr) {
+                      int32_t mem_kind, const int32_t* gq, const char* fn, int order) {
   reset_predict_clocks(h->tm);
   int rc;
   {
     PhaseScope total(h, &h->tm.predict_total);
     // (the matrix-free product knows neither derivative columns nor path ids: the batch route then)
     if (!var && !dvar && !h->has_deriv && !gq)
-      rc = predict_grad_mean_only<T>(h, Xq, M, mean, dmean, mem_kind);
+      rc = predict_grad_mean_only<T>(h, Xq, M, mean, dmean, mem_kind, order);
     else
-      rc = predict_grad_var<T>(h, Xq, M, mean, var, dmean, dvar, mem_kind, gq ? "gpx_predict_grad_paths" : "gpx_predict_grad",
-                               gq);
+      rc = predict_grad_var<T>(h, Xq, M, mean, var, dmean, dvar, mem_kind, fn, gq, order);
     if (rc) return rc;
   }
   return finish_call(h);
@@ -3510,18 +3534,23 @@ extern "C++" {
 namespace {
 // What the three joint-posterior families refuse, in their common order, then begin_call: the family's argument test, the
 // mem_kind, its value test (bad_values: the message, or null), a handle without a fit, its size limit (too_large: the
-// message, or null), a kernel without derivatives (gradient), the handle's kind or — paths — the ids.
+// message, or null), a kernel without the derivatives of `order` (1: gradient, 2: second derivatives, which also stop at
+// MAX_HESS_D dimensions), the handle's kind or — paths — the ids.
 int posterior_begin(gpx_handle* h, const char* fn, bool paths, const int32_t* gq, int64_t M, int32_t mem_kind, bool bad_args,
-                    const char* bad_values, const char* too_large, bool gradient = false) {
+                    const char* bad_values, const char* too_large, int order = 0) {
   if (!h) return GPX_E_ARG;
   if (bad_args) return fail(h, GPX_E_ARG, fn, "bad argument");
   if (bad_mem_kind(mem_kind)) return fail(h, GPX_E_ARG, fn, "bad mem_kind");
   if (bad_values) return fail(h, GPX_E_ARG, fn, bad_values);
   if (!h->fitted) return fail(h, GPX_E_ARG, fn, "handle has no successful fit");
   if (too_large) return fail(h, GPX_E_ARG, fn, too_large);
-  if (gradient && !cov::differentiable(h->cfg.kernel)) return fail(h, GPX_E_UNSUPPORTED, fn, MATERN12_NO_GRAD);
-  if (gradient)
-    if (int rc = basis_refused(h, fn, "the posterior gradient does not include the basis terms yet")) return rc;
+  if (order == 2 && !cov::twice_differentiable(h->cfg.kernel)) return fail(h, GPX_E_UNSUPPORTED, fn, NOT_TWICE_DIFFERENTIABLE);
+  if (order && !cov::differentiable(h->cfg.kernel)) return fail(h, GPX_E_UNSUPPORTED, fn, MATERN12_NO_GRAD);
+  if (order == 2 && h->d > MAX_HESS_D) return fail(h, GPX_E_UNSUPPORTED, fn, HESS_D_LIMIT);
+  if (order)
+    if (int rc = basis_refused(h, fn, order == 2 ? "the posterior second derivatives do not include the basis terms yet"
+                                                 : "the posterior gradient does not include the basis terms yet"))
+      return rc;
   const int rc = paths ? query_ids_refused(h, fn, gq, M, mem_kind) : posterior_refused(h, fn);
   return rc ? rc : begin_call(h);
 }
@@ -3568,8 +3597,16 @@ int sample_posterior_entry(gpx_handle* h, const char* fn, bool paths, const void
 int predict_grad_entry(gpx_handle* h, const char* fn, bool paths, const void* Xq, const int32_t* gq, int64_t M, void* mean,
                        void* var, void* dmean, void* dvar, int32_t mem_kind) {
   const int rc = posterior_begin(h, fn, paths, gq, M, mem_kind, !Xq || !dmean || M <= 0, nullptr,
-                                 M > (int64_t)INT_MAX - 4096 ? "M too large" : nullptr, true);
-  return rc ? rc : BY_DTYPE(h, predict_grad_impl, h, Xq, M, mean, var, dmean, dvar, mem_kind, gq);
+                                 M > (int64_t)INT_MAX - 4096 ? "M too large" : nullptr, 1);
+  return rc ? rc : BY_DTYPE(h, predict_grad_impl, h, Xq, M, mean, var, dmean, dvar, mem_kind, gq, fn, 1);
+}
+
+// gpx_predict_hess and its twin: the gradient's stages on the d (d + 1) / 2 second derivatives, no value rows
+int predict_hess_entry(gpx_handle* h, const char* fn, bool paths, const void* Xq, const int32_t* gq, int64_t M, void* hmean,
+                       void* hvar, int32_t mem_kind) {
+  const int rc = posterior_begin(h, fn, paths, gq, M, mem_kind, !Xq || !hmean || M <= 0, nullptr,
+                                 M > ((int64_t)INT_MAX - 4096) / hess_pairs(MAX_HESS_D) ? "M too large" : nullptr, 2);
+  return rc ? rc : BY_DTYPE(h, predict_grad_impl, h, Xq, M, nullptr, nullptr, hmean, hvar, mem_kind, gq, fn, 2);
 }
 }  // namespace
 }  // extern "C++"
@@ -3621,6 +3658,17 @@ GPX_CATCH_ALL
 int gpx_predict_grad_paths(gpx_handle* h, const void* Xq, const int32_t* gq, int64_t M, void* mean, void* var, void* dmean,
                            void* dvar, int32_t mem_kind) try {
   return predict_grad_entry(h, "gpx_predict_grad_paths", true, Xq, gq, M, mean, var, dmean, dvar, mem_kind);
+}
+GPX_CATCH_ALL
+
+int gpx_predict_hess(gpx_handle* h, const void* Xq, int64_t M, void* hmean, void* hvar, int32_t mem_kind) try {
+  return predict_hess_entry(h, "gpx_predict_hess", false, Xq, nullptr, M, hmean, hvar, mem_kind);
+}
+GPX_CATCH_ALL
+
+int gpx_predict_hess_paths(gpx_handle* h, const void* Xq, const int32_t* gq, int64_t M, void* hmean, void* hvar,
+                           int32_t mem_kind) try {
+  return predict_hess_entry(h, "gpx_predict_hess_paths", true, Xq, gq, M, hmean, hvar, mem_kind);
 }
 GPX_CATCH_ALL
 
@@ -4325,6 +4373,38 @@ int gpx_kernel_mixed_matrix(int32_t kernel, int32_t dtype, const double* A, cons
     else  // (Matern-1/2: values only, and the fit builds them with the plain builder)
       launch_kbuild_cross<T>(kernel, kc.As, na, kc.napad, kc.Bs, nb_, kc.nbpad, d, sf2, kc.K, kc.ld, kc.st);
     return kc.fetch(K);
+  };
+  return dtype == GPX_F32 ? run(float()) : run(double());
+}
+GPX_CATCH_ALL
+
+int gpx_kernel_hess_matrix(int32_t kernel, int32_t dtype, const double* A, const int32_t* ga, int64_t na, const double* B,
+                           const int32_t* side_b, int64_t nb_, int32_t d, const double* lengthscale, int32_t n_ls, double sf2,
+                           const double* ls_path, int32_t n_ls_path, double sg2, double* G) try {
+  const char* fn = "gpx_kernel_hess_matrix";
+  if (!A || !B || !G || !lengthscale || !sizes_ok(na, nb_, d, n_ls) || !cov::known(kernel) || !unit_dtype_ok(dtype))
+    return GPX_E_ARG;
+  std::vector<double> q;
+  if (ga) {  // path ids on both sides
+    if (!side_b || !ls_path || (n_ls_path != 1 && n_ls_path != d) || !path_args_ok(ga, na, side_b, nb_, ls_path, n_ls_path, sg2))
+      return GPX_E_ARG;
+    for (int c = 0; c < d; ++c) q.push_back(lengthscale[n_ls == 1 ? 0 : c] / ls_path[n_ls_path == 1 ? 0 : c]);
+    for (double& r : q) r *= r;
+  } else if (side_b) {  // kinds of the columns
+    if (int rc = kinds_refused(fn, kernel, nullptr, 0, side_b, nb_, d)) return rc;
+  }
+  if (!cov::twice_differentiable(kernel)) return fail(nullptr, GPX_E_UNSUPPORTED, fn, NOT_TWICE_DIFFERENTIABLE);
+  if (d > MAX_HESS_D) return fail(nullptr, GPX_E_UNSUPPORTED, fn, HESS_D_LIMIT);
+  auto run = [&](auto t) {
+    using T = decltype(t);
+    KernelCall<T> kc;
+    if (int rc; (rc = kc.points(A, na, B, nb_, d, lengthscale, n_ls)) ||
+                (rc = kc.sides(ga, side_b, true, ga ? q.data() : nullptr)) || (rc = kc.output(hess_pairs(d), false)))
+      return rc;
+    launch_khess_build<T>(kernel, kc.As, ga ? (const int32_t*)kc.ga : nullptr, na, kc.napad, kc.Bs,
+                          side_b ? (const int32_t*)kc.gb : nullptr, nb_, kc.nbpad, d, sf2, kc.ls, n_ls,
+                          ga ? (const double*)kc.q : nullptr, sg2, kc.K, kc.ld, kc.st);
+    return kc.fetch(G);
   };
   return dtype == GPX_F32 ? run(float()) : run(double());
 }

@@ -122,6 +122,24 @@ __host__ __device__ __forceinline__ T element(int ka, int kb, T v, T g, T h, T u
   return ((ka == kb ? g : (T)0) - h * (ua * ub)) * (ila * ilb);
 }
 
+// Second derivatives by the query point (gpx_hess.hip).  k is twice mean-square differentiable for RBF
+// and Matern-5/2 only (h(0) is unbounded for Matern-3/2 and absent for Matern-1/2), and there
+//   prior Var[d_i d_j f] = hess_prior sf2 / (l_i^2 l_j^2)  (i != j),   3 hess_prior sf2 / l_i^4  (i == j),   hess_prior = h(0) / sf2
+constexpr bool twice_differentiable(int kernel) { return kernel == GPX_KERNEL_RBF || kernel == GPX_KERNEL_MATERN52; }
+constexpr double hess_prior(int kernel) { return kernel == GPX_KERNEL_MATERN52 ? 25.0 / 3.0 : 1.0; }
+
+// The covariance of d^2 f / d x_i d x_j at x_a with an observation of kind kb at x_b, u = (x_a - x_b) / l:
+//   kb < 0   (h u_i u_j - g delta_ij) / (l_i l_j), the negative of element(i, j) — its bits
+//   kb = c   (p u_i u_j u_c - h (delta_ic u_j + delta_jc u_i + delta_ij u_c)) / (l_i l_j l_c)
+// ub = u_kb and ilb = 1 / l_kb (anything when kb < 0); p as value_ghp forms it.
+template <typename T>
+__host__ __device__ __forceinline__ T hess_element(int i, int j, int kb, T v, T g, T h, T p, T ui, T uj, T ub, T ili, T ilj,
+                                                   T ilb) {
+  if (kb < 0) return -element<T>(i, j, v, g, h, ui, uj, ili, ilj);
+  const T s = (i == kb ? uj : (T)0) + (j == kb ? ui : (T)0) + (i == j ? ub : (T)0);
+  return (p * ((ui * uj) * ub) - h * s) * ((ili * ilj) * ilb);
+}
+
 // v, g and h as value_gh forms them (the same bits), and p
 template <int KERNEL, typename T, typename E = Exp>
 __device__ __forceinline__ void value_ghp(T r2, T sf2, T& v, T& g, T& h, T& p, E ex = {}) {

@@ -290,7 +290,7 @@ __global__ __launch_bounds__(256) void kgrad_finish_kernel(const T* __restrict__
 }
 
 struct Priors {
-  double p[MAX_D + 1];
+  double p[PRIOR_SLOTS];
 };
 
 __device__ __forceinline__ double block_sum(double v, double* red) {
@@ -471,9 +471,9 @@ void launch_grad_norms(const T* V, int64_t ld, int64_t mp, int64_t mv, int nblk,
                        T* out, hipStream_t st, const int32_t* ids, const double* prior_path) {
   if (mv <= 0 || nblk <= 0) return;
   Priors pr{}, pg{};
-  for (int b = 0; b < nblk && b <= MAX_D; ++b) pr.p[b] = prior[b];
+  for (int b = 0; b < nblk && b < PRIOR_SLOTS; ++b) pr.p[b] = prior[b];
   if (ids)
-    for (int b = 0; b < nblk && b <= MAX_D; ++b) pg.p[b] = prior_path[b];
+    for (int b = 0; b < nblk && b < PRIOR_SLOTS; ++b) pg.p[b] = prior_path[b];
   hipLaunchKernelGGL(grad_norms_kernel<T>, dim3((unsigned)mv, (unsigned)nblk), dim3(256), 0, st, V, ld, mp, ncols, pr,
                      out, ids, pg);
 }

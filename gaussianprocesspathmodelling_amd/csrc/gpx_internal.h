@@ -10,6 +10,10 @@ namespace gpx {
 constexpr int KB = 64;      // innermost Cholesky block (one-workgroup POTF2 + inverse)
 constexpr int TILE = 128;   // trailing-update tile; every padded dimension is a multiple
 constexpr int MAX_D = 32;   // max input dimension d (the kernels stage points in LDS arrays of this width)
+constexpr int MAX_HESS_D = 8;  // ... of the posterior second derivatives (gpx_hess.hip): d (d + 1) / 2 row blocks per point
+constexpr int hess_pairs(int d) { return d * (d + 1) / 2; }  // the pairs (i, j), i <= j, row-major
+// row blocks with a prior of their own in launch_grad_norms: value + d of the gradient, the pairs of the Hessian
+constexpr int PRIOR_SLOTS = hess_pairs(MAX_HESS_D) > MAX_D + 1 ? hess_pairs(MAX_HESS_D) : MAX_D + 1;
 // Leading-dimension skew against power-of-two strides: ONE 128-byte line, so that every row of
 // every matrix starts on a 128-byte boundary (hipMalloc bases are 256-byte aligned; all padded
 // dimensions are multiples of 64 elements).  trsm_rlt_kernel DEPENDS on this: it round-trips a
@@ -393,7 +397,7 @@ template <typename T>
 void launch_kgrad_matvec(int kernel, const T* As, int64_t M, const T* Bs, int64_t npad, int d, double sf2,
                          const T* alphaT, int64_t lda, int k, const double* ls, int n_ls, T* part, T* dmean,
                          hipStream_t st);
-// out[b mp + i] = prior[b] - sum_{j < ncols} V[b mp + i][j]^2 for i < mv, b < nblk (<= 33; prior on the host).
+// out[b mp + i] = prior[b] - sum_{j < ncols} V[b mp + i][j]^2 for i < mv, b < nblk (<= PRIOR_SLOTS; prior on the host).
 // ids != null (device, mv entries): the prior of a row i with ids[i] >= 0 is prior[b] + prior_path[b], summed in fp64
 template <typename T>
 void launch_grad_norms(const T* V, int64_t ld, int64_t mp, int64_t mv, int nblk, int64_t ncols, const double* prior,
@@ -403,6 +407,23 @@ void launch_grad_norms(const T* V, int64_t ld, int64_t mp, int64_t mv, int nblk,
 template <typename T>
 void launch_grad_unpack(const T* MT, int64_t ldm, const T* VN, int64_t mp, int64_t mv, int nblk, int d, int k,
                         int with_value, T* mean, T* var, T* dmean, T* dvar, hipStream_t st);
+
+// ---- posterior second derivatives (gpx_hess.hip) -----------------------------------------------
+// hess_pairs(d) row blocks of V (each mpad rows, ld; mpad a multiple of 64), block (i, j), i <= j, row-major =
+// d^2 k(As, Bs) / d As_i d As_j; zero beyond m rows / n columns.  RBF and Matern-5/2, d <= MAX_HESS_D (nothing is launched
+// otherwise).  group_a == null, side_b == null: the plain build; side_b alone: the columns' kinds (launch_kgrad_build's
+// kind_b; a derivative column holds the third derivative); both: path ids of rows and columns with q and sg2
+// (launch_kgrad_build_g's).  A tile without a derivative column / a possible same-path pair gives the plain build's numbers.
+template <typename T>
+void launch_khess_build(int kernel, const T* As, const int32_t* group_a, int64_t m, int64_t mpad, const T* Bs,
+                        const int32_t* side_b, int64_t n, int64_t npad, int d, double sf2, const double* ls, int n_ls,
+                        const double* q, double sg2, T* V, int64_t ld, hipStream_t st);
+// hmean (M, hess_pairs(d), k)[m][(i, j)][c] = sum_n d^2 k(As_m, Bs_n) / d As_mi d As_mj alphaT[c][n], matrix-free:
+// launch_kgrad_matvec's arguments and grid (kgrad_matvec_shape), part of S * k * hess_pairs(d) * round_up(M, 64) elements
+template <typename T>
+void launch_khess_matvec(int kernel, const T* As, int64_t M, const T* Bs, int64_t npad, int d, double sf2,
+                         const T* alphaT, int64_t lda, int k, const double* ls, int n_ls, T* part, T* hmean,
+                         hipStream_t st);
 
 // ---- joint density of blocks of query points (gpx_score.hip) -----------------------------------
 // Column slices of V^T per block in launch_block_gram: a function of npad ONLY (a block's partial sums, and with them its

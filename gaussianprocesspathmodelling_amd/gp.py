@@ -63,7 +63,8 @@ class GP:
     kernel : "rbf" | "matern52" | "matern32" | "matern12" — scikit-learn's ``RBF`` and ``Matern(nu=2.5 | 1.5 | 0.5)``
         (include/gpx.h).  Matern-3/2 is the usual prior for trajectories (a velocity, no acceleration);
         Matern-1/2 (exponential / Ornstein-Uhlenbeck) has no derivative, so :meth:`predict_gradient` raises
-        ``GpxError`` for it.  Every other call runs for all four.
+        ``GpxError`` for it; :meth:`predict_hessian` (second derivatives: acceleration, curvature) needs a twice
+        differentiable prior and runs for "rbf" and "matern52" only.  Every other call runs for all four.
     lengthscale : float or array of d floats (ARD)
     variance : signal variance sf2
     noise : observation-noise variance sn2 (added to the diagonal).  ``fit(..., noise_weights=w)`` makes it the LEVEL of a
@@ -892,6 +893,43 @@ class GP:
         if with_value:
             return (mean, var, dmean, dvar) if return_var else (mean, dmean)
         return (dmean, dvar) if return_var else dmean
+
+    def predict_hessian(self, Xs, return_var=True, path_ids=None, full=False):
+        """Second derivatives of the posterior with respect to the query points ``Xs`` (M, d) (``gpx_predict_hess``):
+        ``hmean`` ((M, D2) for a 1-D ``y``, else (M, D2, k)) over the ``D2 = d (d + 1) / 2`` pairs ``(i, j)``, ``i <= j``,
+        row-major, and, with ``return_var``, ``hvar`` (M, D2), the latent variance of each second derivative (raw, not
+        clamped).  ``full=True`` expands both on the host to the symmetric (M, d, d[, k]) and (M, d, d).  Without
+        variances the device contracts the kernel's second derivative with the cached ``alpha`` matrix-free (no solve).
+        RBF and Matern-5/2 only: Matern-3/2 and Matern-1/2 paths have no second derivative, and ``GpxError`` says so; so
+        it does for ``d > 8``, a fit with a basis, ``dtype="mixed"`` and sharded handles.  NumPy in, NumPy out; a device
+        tensor in, device tensors out.  ``path_ids`` as :meth:`predict`'s (``gpx_predict_hess_paths``): the second
+        derivatives of ``f + g_p`` for ids ``>= 0``."""
+        if not self._fitted:
+            raise RuntimeError("predict_hessian() before a successful fit()")
+        pq, kq, keepq, devq, sq = self._as_input(Xs, "Xs")
+        if len(sq) != 2 or sq[1] != self._d:
+            raise ValueError(f"Xs must be (M, {self._d})")
+        M, d, k = sq[0], self._d, self._k
+        d2 = d * (d + 1) // 2
+        hmean = self._empty((M, d2) if self._y1d else (M, d2, k), devq)
+        hvar = self._empty((M, d2), devq) if return_var else None
+        pv = None if hvar is None else self._ptr(hvar)
+        if path_ids is None:
+            self._check(self._lib.gpx_predict_hess(self._h, pq, M, self._ptr(hmean), pv, kq))
+        else:
+            pg, keepg = self._query_ids(path_ids, M, kq, devq)
+            self._check(self._lib.gpx_predict_hess_paths(self._h, pq, pg, M, self._ptr(hmean), pv, kq))
+        if full:
+            # pair number of (i, j): the upper triangle row-major, mirrored below the diagonal
+            idx = np.zeros((d, d), dtype=np.int64)
+            idx[np.triu_indices(d)] = np.arange(d2)
+            idx = np.maximum(idx, idx.T).reshape(-1)
+            if devq is not None:
+                import torch
+                idx = torch.from_numpy(idx).to(devq)
+            hmean = hmean[:, idx].reshape((M, d, d) + tuple(hmean.shape[2:]))
+            hvar = None if hvar is None else hvar[:, idx].reshape(M, d, d)
+        return (hmean, hvar) if return_var else hmean
 
     def score_blocks(self, Xs, ys, block, include_noise=True, return_parts=False, on_bad="raise", noise_weights=None):
         """Joint log predictive density of whole blocks of query points (``gpx_score_blocks``): ``Xs`` (G * block, d)

@@ -255,7 +255,9 @@ class PathModel:
     ``trend``: None, or the basis of the model's explicit mean (``fit_path_models(trend=)``: "constant", "linear",
     "quadratic" in the normalised inputs, coefficients marginalised — ``GP.fit(basis=)``).  :meth:`predict`, :meth:`sample`,
     :meth:`log_likelihood` and :meth:`forecast` include it and its uncertainty; :meth:`add_paths`, :meth:`append_paths`,
-    :meth:`remove_paths`, :meth:`predict_gradient` and :meth:`velocity` raise ``GpxError`` with the library's reason."""
+    :meth:`remove_paths`, :meth:`predict_gradient`, :meth:`velocity`, :meth:`predict_hessian`, :meth:`acceleration` and
+    :meth:`curvature` raise ``GpxError`` with the library's reason.  :meth:`acceleration` and :meth:`curvature` (second
+    derivatives) need an "rbf" or "matern52" model."""
 
     def __init__(self, gp, keys, in_lo, in_span, y_mean, y_std, inputs, targets, step_weights=None, has_velocities=False,
                  within_path=False, row_counts=None, trend=None):
@@ -360,6 +362,52 @@ class PathModel:
         if not return_var:
             return out[:, jt, :]
         return out[0][:, jt, :], out[1][:, jt, :]
+
+    def predict_hessian(self, q, return_var=True, path=None):
+        """Second derivatives of the posterior with respect to the raw (un-normalised) inputs ``q`` (M,) or (M, d), in
+        target units per input unit squared: ``hmean`` (M, D2, k) over the pairs ``(i, j)``, ``i <= j``, of the inputs,
+        row-major (``D2 = d (d + 1) / 2``), and, with ``return_var``, ``hvar`` (M, D2, k), the latent variance of each
+        (``GP.predict_hessian`` on the device, rescaled by ``y_std[c] / (in_span[i] in_span[j])``, variances by its
+        square).  RBF and Matern-5/2 models only.  ``path`` as :meth:`predict`'s: that path itself."""
+        kw = self._path_kw(path)
+        qn = self._queries(q)
+        M, d = qn.shape
+        out = self.gp.predict_hessian(qn, return_var=return_var, **kw)
+        span = np.asarray(self.in_span, dtype=np.float64).reshape(-1)
+        i, j = np.triu_indices(d)
+        scale = self.y_std[None, None, :] / (span[i] * span[j])[None, :, None]   # (1, D2, k)
+        hmean = (out[0] if return_var else out).reshape(M, len(i), -1) * scale
+        if not return_var:
+            return hmean
+        return hmean, out[1][:, :, None] * scale ** 2
+
+    def acceleration(self, q, return_var=True, path=None):
+        """Acceleration of the modelled path at the raw time stamps ``q``: the ``("t", "t")`` entry of
+        :meth:`predict_hessian`, (M, k) arrays, e.g. (d2x/dt2, d2y/dt2), and with ``return_var`` their latent variances
+        (M, k).  ``q`` and ``path`` as :meth:`velocity`'s."""
+        if "t" not in self.inputs:
+            raise ValueError(f"acceleration() needs 't' among the model's inputs, have {self.inputs}")
+        jt, d = self.inputs.index("t"), len(self.inputs)
+        b = jt * d - jt * (jt - 1) // 2   # the pair (jt, jt) in the row-major upper triangle
+        out = self.predict_hessian(q, return_var=return_var, path=path)
+        if not return_var:
+            return out[:, b, :]
+        return out[0][:, b, :], out[1][:, b, :]
+
+    def curvature(self, q, path=None):
+        """Signed curvature of the posterior MEAN path of a model with exactly two targets (x, y) at the raw time stamps
+        ``q``, (M,), in raw units (1 / length): ``(x' y'' - y' x'') / (x'^2 + y'^2)^(3/2)`` from the means of
+        :meth:`velocity` and :meth:`acceleration`; counter-clockwise is positive, NaN where the mean speed is 0.  It is a
+        plug-in value: the curvature of the mean path, not the mean of the curvature, and it comes with no uncertainty
+        (the joint covariance of velocity and acceleration is not computed)."""
+        if len(self.targets) != 2:
+            raise ValueError(f"curvature() needs a model with exactly two targets, have {self.targets}")
+        v = self.velocity(q, return_var=False, path=path)
+        a = self.acceleration(q, return_var=False, path=path)
+        speed2 = v[:, 0] ** 2 + v[:, 1] ** 2
+        with np.errstate(divide="ignore", invalid="ignore"):
+            kappa = (v[:, 0] * a[:, 1] - v[:, 1] * a[:, 0]) / speed2 ** 1.5
+        return np.where(speed2 > 0.0, kappa, np.nan)
 
     def add_paths(self, trajs, keys):
         """Append the paths ``keys`` of ``trajs`` to this cluster's model (``GP.update``: the factor of the paths already

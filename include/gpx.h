@@ -456,6 +456,34 @@ int gpx_sample_posterior_paths(gpx_handle* h, const void* Xs, const int32_t* gq,
 int gpx_predict_grad_paths(gpx_handle* h, const void* Xs, const int32_t* gq, int64_t M, void* mean, void* var, void* dmean,
                            void* dvar, int32_t mem_kind);
 
+/* ---- posterior second derivatives (additive to ABI v6) --------------------------------------------------
+ * The second derivatives of the posterior by the query point (for a path model: the acceleration).  The pairs (i, j),
+ * i <= j, are numbered row-major, D2 = d (d + 1) / 2 of them.  With u = (x* - x) / l and g, h, p of the family (v = sf2 k):
+ *   d^2 k(x*, x) / d x*_i d x*_j          = (h u_i u_j - g delta_ij) / (l_i l_j)
+ *   d^3 k(x*, x) / d x*_i d x*_j d x_c    = (p u_i u_j u_c - h (delta_ic u_j + delta_jc u_i + delta_ij u_c)) / (l_i l_j l_c)
+ *                                           (against a derivative observation of kind c, gpx_set_observation_kinds)
+ *   prior Var[d_i d_j f] = h(0) / (l_i^2 l_j^2) for i != j, 3 h(0) / l_i^4 for i == j;  h(0) = sf2 (RBF), (25/3) sf2 (Matern-5/2)
+ *   RBF: g = h = p = v;  Matern-5/2: g = sf2 (5/3)(1 + s) e^-s, h = sf2 (25/3) e^-s, p = sf2 (125/3) e^-s / s, s = sqrt5 r
+ * With d_ij K* the (M, N) matrix of those entries:
+ *   hmean[m, (i,j), c] = (d_ij K* alpha)[m, c]
+ *   hvar[m, (i,j)]     = prior_ij - ||L^-1 (d_ij K*)_m^T||^2     (latent, raw, not clamped; the same for every target)
+ * hvar == NULL on a fit without derivative rows: hmean is computed matrix-free from the cached alpha (one exponential per
+ * query / training pair, no solve).  Otherwise the query points go in batches (GPX_PRED_BATCH, shrunk to the card) through
+ * gpx_predict_grad's stages: the D2 row blocks of a batch by one fused kernel, ONE forward substitution, one z^T V, row
+ * norms; GPX_E_NOMEM before any allocation when not even one batch of 128 points fits.  A point's results do not depend on
+ * M, its position or GPX_PRED_BATCH.  Handles, element type, memory kinds, scratch (gpx_release_scratch) and timings are
+ * gpx_predict_grad's; the fit is only read (gpx_predict afterwards is bit-identical).
+ * gpx_predict_hess_paths: gq as gpx_predict_grad_paths' — a query point with gq >= 0 is a point of f + g_p, whose
+ * covariance with a same-path row gains the second derivative of sg2 k(., .; l_path) and whose prior gains the same formula in
+ * sg2 and l_path; always the batch route; every id -1: the bits of gpx_predict_hess's batch route.
+ * GPX_E_UNSUPPORTED before anything is computed (gpx_last_error says why; the fit stays valid): GPX_KERNEL_MATERN32 and
+ * GPX_KERNEL_MATERN12 (not twice differentiable), d > 8, a fit with a basis, GPX_MIXED handles, shards, device groups and
+ * handles with a communicator; gpx_predict_hess_paths on a fit without effective path ids.  GPX_E_ARG as gpx_predict_grad. */
+int gpx_predict_hess(gpx_handle* h, const void* Xs, int64_t M, void* hmean /* (M, D2, k) */, void* hvar /* (M, D2), may be NULL */,
+                     int32_t mem_kind);
+int gpx_predict_hess_paths(gpx_handle* h, const void* Xs, const int32_t* gq, int64_t M, void* hmean, void* hvar,
+                           int32_t mem_kind);
+
 int gpx_get_alpha(gpx_handle* h, void* out /* (N,k) host */);
 /* Log marginal likelihood of the last fit and its gradient w.r.t. the LOG hyper-parameters —
  * SURVEY.md §8(f) row 1 ("log marginal likelihood + hyper-parameter gradient hooks"; no anchor
@@ -634,6 +662,19 @@ int gpx_kernel_path_grad_matrix(int32_t kernel, int32_t dtype, const double* A, 
 int gpx_kernel_mixed_matrix(int32_t kernel, int32_t dtype, const double* A, const int32_t* ka, int64_t na, const double* B,
                             const int32_t* kb, int64_t nb, int32_t d, const double* lengthscale, int32_t n_ls, double sf2,
                             double* K);
+/* kernel unit-test entry point (host buffers; additive to ABI v6): G (D2, na, nb), G[(i,j)][a][b] = the second derivative by
+ * A_ai and A_aj of the covariance of a value at A_a with the observation b — the row blocks of gpx_predict_hess(_paths), by
+ * its builder (pairs i <= j row-major, D2 = d (d + 1) / 2).  What the observation b is:
+ *   ga == NULL, side_b == NULL   a value: the plain build (ls_path, n_ls_path, sg2 are not read)
+ *   ga == NULL, side_b != NULL   an observation of kind side_b[b] in [-1, d) (gpx_set_observation_kinds): the KINDS build
+ *   ga != NULL                   a value with path id side_b[b], the rows' ids in ga (all >= -1; ls_path, n_ls_path = 1 or d
+ *                                and sg2 as gpx_kernel_path_matrix's): the build with path ids
+ * n_ls: 1 or d; dtype GPX_F64 or GPX_F32 (the fp32 builder on the rounded inputs, returned widened).  GPX_E_ARG as
+ * gpx_kernel_path_grad_matrix / gpx_kernel_mixed_matrix; GPX_E_UNSUPPORTED (gpx_last_error(NULL) says why) for
+ * GPX_KERNEL_MATERN32, GPX_KERNEL_MATERN12 and d > 8.  G is written only on success. */
+int gpx_kernel_hess_matrix(int32_t kernel, int32_t dtype, const double* A, const int32_t* ga, int64_t na, const double* B,
+                           const int32_t* side_b, int64_t nb, int32_t d, const double* lengthscale, int32_t n_ls, double sf2,
+                           const double* ls_path, int32_t n_ls_path, double sg2, double* G /* (D2, na, nb) */);
 /* kernel unit-test entry point (host buffers, fp64; additive to ABI v6): G (1 + n_ls_path, na, nb): G[0][a][b] = [ga_a == gb_b
  * and ga_a >= 0] sg2 k(A_a, B_b; l_path), the within-path term of gpx_kernel_path_matrix, and G[1 + c] its derivative by
  * log l_path,c (n_ls_path == 1: by the one l_path) — what gpx_lml_grad_paths contracts with K^-1, by the device function its
