@@ -115,6 +115,11 @@ SIGNATURES = {
     "gpx_lml_grad_full": (C.c_int, [_P, _PD, _PD]),
     "gpx_lml_grad_paths": (C.c_int, [_P, _PD, _PD, _PD, C.c_int32]),
     "gpx_loo": (C.c_int, [_P, _PD, _PD, _PD, _PD]),
+    "gpx_pathwise_draw": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_uint64, _P, C.c_int32]),
+    "gpx_pathwise_eval": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int64, _P, C.c_int32]),
+    "gpx_pathwise_info": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "gpx_pathwise_eval_raw": (C.c_int, [C.c_int32, C.c_int32, _PD, C.c_int64, _PD, C.c_int64, C.c_int32, _PD, C.c_int32,
+                                        C.c_double, _PD, C.c_int64, _PD, _PD, C.c_int64, _PD]),
     "gpx_logdet": (C.c_int, [_P, _PD]),
     "gpx_release_scratch": (C.c_int, [_P]),
     "gpx_get_timings": (C.c_int, [_P, C.POINTER(GpxTimings)]),

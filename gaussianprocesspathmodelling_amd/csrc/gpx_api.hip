@@ -131,6 +131,7 @@ struct gpx_handle {
     DevBuf BG, BU;  // a fit with basis functions: per-slice Gram of the bordered rows; u = L_A^-1 (h - Z_H^T v*) per query row (rows x 64, fp64)
     DevBuf UW, UQ;  // gpx_remove_rows: per pass in flight (two) the carry ((N + 64) x UPD_W) and the panel's orthogonal factor (2 UPD_W square)
     DevBuf LOO;     // gpx_loo: q (N) | var (N) | mean (N x k) | logp (N x k), fp64
+    DevBuf PWZ, PWpart, PWout, PWres;  // gpx_pathwise_*: a host caller's normals, the splits' partials, OutT of one batch, results for a host caller
   } scr;
   // row-block shard (world > 1)
   Comm* comm = nullptr;  // RCCL, in-process or host-callback transport (gpx_shard.inc)
@@ -196,6 +197,12 @@ struct gpx_handle {
   int basis = 0;      // the basis of the CURRENT fit and its number of functions p (0: a plain fit)
   int bp = 0;
   DevBuf Bst;         // the current fit's beta | L_A | A^-1 (fp64; gpx_internal.h: BASIS_STATE)
+  // pathwise posterior function samples (gpx_pathwise_draw): the stored draw of the CURRENT fit — state,
+  // not scratch.  S == 0: none.  Whatever changes the factor drops it (drop_pathwise).
+  struct Pathwise {
+    DevBuf Om, W, V;  // Omega (F x d, fp64), W (Cpad x ldw), V = R K_y^-1 (Cpad x ld, rows as alphaT's)
+    int64_t S = 0, F = 0, ldw = 0, n_normals = 0;
+  } pw;
   // event pool
   std::vector<hipEvent_t> ev_pool;
   size_t ev_used = 0;
@@ -1194,6 +1201,7 @@ int begin_fit(gpx_handle* h) {  // ... of a call that replaces the fit
   if (rc == GPX_OK) {
     h->fitted = false;
     h->basis = h->bp = 0;  // (fit_impl decides; the other engines never fit with a basis: check_fit_basis)
+    h->pw = {};            // a stored pathwise draw belongs to the fit it was drawn against
   }
   return rc;
 }
@@ -2929,6 +2937,109 @@ int loo_impl(gpx_handle* h, double* mean, double* var, double* logp, double* tot
   return GPX_OK;
 }
 
+// ---- pathwise posterior function samples (gpx_pathwise_draw / _eval) -------------------------------------
+// The draw: Omega and W from the stream, the prior draws at the training points by the evaluation kernel with its V term
+// off (written straight into the rows that become V), the residual rows in place, and V = R K_y^-1 by the rows-layout
+// solves against the fit's factor — one 64-row slab at a time, so that a column's bits do not depend on how many columns
+// the draw has (the solves pick their tiles by the row count).  Built aside and moved into the handle at the end: a call
+// that fails keeps the draw of the call before.
+constexpr int64_t PW_ROWS = 8192;  // training points per launch of the draw's feature pass (bounds the partial buffer)
+
+template <typename T>
+int pathwise_draw_impl(gpx_handle* h, int64_t S, int64_t F, uint64_t seed, const void* z, int32_t mem_kind) {
+  gpx_timings& tm = h->tm;
+  reset_predict_clocks(tm);
+  const int64_t N = h->N, Npad = h->Npad, ld = h->ld;
+  const int d = h->d, k = h->k, q = pathwise_chi_dof(h->cfg.kernel);
+  const int64_t C = S * k, Cpad = round_up(C, RHS_ROWS), ldw = round_up(2 * F, 64) + ld_skew<T>();
+  const int64_t nn = F * (d + q) + C * (2 * F + N);
+  const int64_t MB = std::min(PW_ROWS, Npad);
+  const int nz = pathwise_splits(Npad, F, false);
+  gpx_handle::Pathwise fresh;
+  int rc;
+  if ((rc = ensure(h, fresh.Om, (size_t)F * d * sizeof(double)))) return rc;
+  if ((rc = ensure(h, fresh.W, (size_t)Cpad * ldw * sizeof(T)))) return rc;
+  if ((rc = ensure(h, fresh.V, (size_t)Cpad * ld * sizeof(T)))) return rc;
+  if ((rc = ensure(h, h->scr.PWpart, (size_t)nz * Cpad * MB * sizeof(T)))) return rc;
+  const T* dz = (const T*)z;
+  T* dV = (T*)fresh.V.p;
+  {
+    PhaseScope total(h, &tm.predict_total);
+    {
+      PhaseScope ps(h, &tm.kstar);  // the feature half of the draw
+      if (z && mem_kind == GPX_MEM_HOST) {
+        if ((rc = ensure(h, h->scr.PWZ, (size_t)nn * sizeof(T)))) return rc;
+        if ((rc = copy_in(h, h->scr.PWZ.p, z, (size_t)nn * sizeof(T), GPX_MEM_HOST))) return rc;
+        dz = (const T*)h->scr.PWZ.p;
+      }
+      launch_pathwise_draw<T>(dz, seed, F, d, q, C, Cpad, N, (double*)fresh.Om.p, (T*)fresh.W.p, ldw, h->st);
+      for (int64_t m0 = 0; m0 < Npad; m0 += MB)
+        launch_pathwise_eval<T>(h->cfg.kernel, (const T*)h->Xs.p + m0 * d, std::min(MB, Npad - m0), (const T*)h->Xs.p, Npad, d,
+                                h->sf2, nullptr, 0, (const double*)fresh.Om.p, F, (const T*)fresh.W.p, ldw, Cpad,
+                                (T*)h->scr.PWpart.p, dV + m0, ld, h->st);
+      launch_pathwise_resid<T>((const T*)h->Y.p, dV, ld, h->weighted ? (const T*)h->Wfit.p : nullptr, h->sn2, dz, seed,
+                               F * (d + q), F, N, Npad, k, C, Cpad, dV, ld, h->st);
+    }
+    {
+      PhaseScope ps(h, &tm.trsm);
+      for (int64_t r = 0; r < Cpad; r += RHS_ROWS) {
+        if ((rc = solve_fwd_enqueue<T>(h, dV + r * ld, RHS_ROWS, (const T*)h->Lfac, ld, Npad, h->nb_solve, (const T*)h->Winv.p)))
+          return rc;
+        solve_bwd_enqueue<T>(h, dV + r * ld, RHS_ROWS, (const T*)h->Lfac, ld, Npad, h->nb_solve, (const T*)h->Winv.p);
+      }
+    }
+  }
+  if ((rc = finish_call(h))) return rc;
+  fresh.S = S, fresh.F = F, fresh.ldw = ldw, fresh.n_normals = nn;
+  h->pw = std::move(fresh);
+  return GPX_OK;
+}
+
+// Samples [s0, s0 + S) of the stored draw at M query points, in batches of query rows (rows are independent and the
+// kernel's splits do not depend on M: batching changes no bit).  Only the 64-column blocks the samples touch are evaluated.
+template <typename T>
+int pathwise_eval_impl(gpx_handle* h, const void* Xq, int64_t M, int64_t s0, int64_t S, void* out, int32_t mem_kind) {
+  gpx_timings& tm = h->tm;
+  reset_predict_clocks(tm);
+  const int64_t Npad = h->Npad, ld = h->ld, F = h->pw.F, ldw = h->pw.ldw;
+  const int d = h->d, k = h->k;
+  const int64_t cb0 = s0 * k / RHS_ROWS * RHS_ROWS, csel = round_up((s0 + S) * k, RHS_ROWS) - cb0;
+  const int nz = pathwise_splits(Npad, F, true);
+  const int64_t Mpad = round_up(M, TILE);
+  const int64_t MB = pred_batch_rows(h, Mpad, (size_t)(nz + 1) * csel * sizeof(T), true);
+  const bool host = mem_kind == GPX_MEM_HOST;
+  const size_t outn = (size_t)S * M * k;
+  int rc;
+  if ((rc = ensure_queries<T>(h, M))) return rc;
+  if ((rc = ensure(h, h->scr.PWpart, (size_t)nz * csel * MB * sizeof(T)))) return rc;
+  if ((rc = ensure(h, h->scr.PWout, (size_t)csel * MB * sizeof(T)))) return rc;
+  if (host && (rc = ensure(h, h->scr.PWres, outn * sizeof(T)))) return rc;
+  T* dout = host ? (T*)h->scr.PWres.p : (T*)out;
+  {
+    PhaseScope total(h, &tm.predict_total);
+    {
+      PhaseScope ps(h, &tm.kstar);
+      if ((rc = upload_queries<T>(h, Xq, M, mem_kind))) return rc;
+    }
+    {
+      PhaseScope ps(h, &tm.mean);
+      for (int64_t m0 = 0; m0 < Mpad; m0 += MB) {
+        const int64_t mv = std::min<int64_t>(std::min(MB, Mpad - m0), M - m0);
+        if (mv <= 0) break;
+        launch_pathwise_eval<T>(h->cfg.kernel, (const T*)h->scr.Qs.p + m0 * d, round_up(mv, 64), (const T*)h->Xs.p, Npad, d,
+                                h->sf2, (const T*)h->pw.V.p + cb0 * ld, ld, (const double*)h->pw.Om.p, F,
+                                (const T*)h->pw.W.p + cb0 * ldw, ldw, csel, (T*)h->scr.PWpart.p, (T*)h->scr.PWout.p, MB, h->st);
+        launch_pathwise_unpack<T>((const T*)h->scr.PWout.p, MB, cb0, s0, S, M, m0, mv, k, dout, h->st);
+      }
+    }
+    if (host) {
+      PhaseScope ps(h, &tm.d2h);
+      if ((rc = copy_out(h, out, dout, outn * sizeof(T), mem_kind))) return rc;
+    }
+  }
+  return finish_call(h);
+}
+
 // ---- GPX_MIXED: fp32 factorisation, fp64 refinement of alpha, fp64 mean --------------------------
 constexpr int MIXED_KMAX = 8;
 constexpr int MIXED_MAX_ITERS = 12;   // refine == 0: cap of the adaptive refinement
@@ -3709,6 +3820,7 @@ int append_entry(gpx_handle* h, const void* Xnew, const void* ynew, const void* 
                                       "built without the within-path covariance: fit the concatenated data instead");
   h->kinded = false;  // (kinds all -1: the plain model, and from here on the plain builders' — the same numbers)
   if ((rc = begin_call(h))) return rc;
+  h->pw = {};  // the factor changes: a stored pathwise draw goes
   if (wnew && (rc = check_weights(h, "gpx_append_weighted", wnew, m, mem_kind, h->cfg.dtype == GPX_F32 ? 4 : 8, h->st)))
     return rc;
   return BY_DTYPE(h, append_impl, h, Xnew, ynew, wnew, m, mem_kind, info);
@@ -3751,6 +3863,7 @@ int gpx_remove_rows(gpx_handle* h, int64_t start, int64_t count, int64_t* info) 
   *info = 0;
   if (count == 0) return GPX_OK;
   if ((rc = begin_call(h))) return rc;
+  h->pw = {};  // the factor changes: a stored pathwise draw goes
   return BY_DTYPE(h, remove_impl, h, start, count, info);
 }
 GPX_CATCH_ALL
@@ -3789,6 +3902,7 @@ int gpx_append_rows(gpx_handle* h, const void* Xnew, const void* ynew, const voi
   // one, also when neither it nor the new rows hold a derivative: it keeps its sn2_deriv for the rows of a later append.
   if (!h->kinded && !h->grouped) return append_entry(h, Xnew, ynew, wnew, m, mem_kind, info);
   if ((rc = begin_call(h))) return rc;
+  h->pw = {};  // the factor changes: a stored pathwise draw goes
   if (wnew && (rc = check_weights(h, "gpx_append_rows", wnew, m, mem_kind, h->cfg.dtype == GPX_F32 ? 4 : 8, h->st)))
     return rc;
   const int32_t* side = h->grouped ? ids.data() : kinds.data();
@@ -3810,6 +3924,7 @@ int gpx_set_noise_weights(gpx_handle* h, const void* w, int64_t n, int32_t mem_k
   }
   if (n == 0 && h->nw_set == 0) return GPX_OK;
   HIPCHK(h, hipSetDevice(h->cfg.device));
+  h->pw = {};  // the noise model the draw's eps was sampled under is being replaced: a stored pathwise draw goes
   if (n == 0) {
     HIPCHK(h, hipStreamSynchronize(h->st));
     h->Wset = DevBuf();
@@ -4092,6 +4207,63 @@ int gpx_loo(gpx_handle* h, double* mean, double* var, double* logp, double* tota
   int rc;
   if ((rc = begin_call(h))) return rc;
   return loo_impl(h, mean, var, logp, total);
+}
+GPX_CATCH_ALL
+
+namespace {
+// what the pathwise calls refuse beyond their arguments, before anything is computed: the handles the joint-posterior calls
+// refuse, and the fits whose covariance is not the plain k(x, x') the features approximate
+int pathwise_refused(gpx_handle* h, const char* fn) {
+  if (int rc = posterior_refused(h, fn)) return rc;
+  if (h->has_deriv)
+    return fail(h, GPX_E_UNSUPPORTED, fn, "the fit has derivative observations (gpx_set_observation_kinds): not supported");
+  if (h->grouped) return fail(h, GPX_E_UNSUPPORTED, fn, "the fit has path ids (gpx_set_path_groups): not supported");
+  return basis_refused(h, fn, "the sampled functions do not include the basis terms");
+}
+}  // namespace
+
+int gpx_pathwise_draw(gpx_handle* h, int64_t S, int64_t F, uint64_t seed, const void* z, int32_t mem_kind) try {
+  if (!h) return GPX_E_ARG;
+  if (bad_mem_kind(mem_kind)) return fail(h, GPX_E_ARG, "gpx_pathwise_draw", "bad mem_kind");
+  if (!h->fitted) return fail(h, GPX_E_ARG, "gpx_pathwise_draw", "handle has no successful fit");
+  if (S < 0 || (S > 0 && F < 1)) return fail(h, GPX_E_ARG, "gpx_pathwise_draw", "need S >= 0 samples and F >= 1 frequencies");
+  int rc;
+  if ((rc = pathwise_refused(h, "gpx_pathwise_draw"))) return rc;
+  if (S > 0 && (S > ((int64_t)1 << 20) / h->k || F > (int64_t)1 << 24))
+    return fail(h, GPX_E_ARG, "gpx_pathwise_draw", "S k (at most 2^20 columns) or F (at most 2^24) too large");
+  if ((rc = begin_call(h))) return rc;
+  if (S == 0) {
+    h->pw = {};
+    return GPX_OK;
+  }
+  return BY_DTYPE(h, pathwise_draw_impl, h, S, F, seed, z, mem_kind);
+}
+GPX_CATCH_ALL
+
+int gpx_pathwise_eval(gpx_handle* h, const void* Xs, int64_t M, int64_t s0, int64_t S, void* out, int32_t mem_kind) try {
+  if (!h) return GPX_E_ARG;
+  if (!Xs || !out || M <= 0 || S <= 0 || s0 < 0) return fail(h, GPX_E_ARG, "gpx_pathwise_eval", "bad argument");
+  if (bad_mem_kind(mem_kind)) return fail(h, GPX_E_ARG, "gpx_pathwise_eval", "bad mem_kind");
+  if (!h->fitted) return fail(h, GPX_E_ARG, "gpx_pathwise_eval", "handle has no successful fit");
+  int rc;
+  if ((rc = pathwise_refused(h, "gpx_pathwise_eval"))) return rc;
+  if (h->pw.S == 0)
+    return fail(h, GPX_E_ARG, "gpx_pathwise_eval",
+                "no live draw: call gpx_pathwise_draw first (a fit, append, removal or new noise weights drops the draw)");
+  if (s0 > h->pw.S || S > h->pw.S - s0)
+    return fail(h, GPX_E_ARG, "gpx_pathwise_eval", "samples [s0, s0 + S) must lie inside the draw");
+  if (M > (int64_t)INT_MAX - 4096) return fail(h, GPX_E_ARG, "gpx_pathwise_eval", "M too large");
+  if ((rc = begin_call(h))) return rc;
+  return BY_DTYPE(h, pathwise_eval_impl, h, Xs, M, s0, S, out, mem_kind);
+}
+GPX_CATCH_ALL
+
+int gpx_pathwise_info(gpx_handle* h, int64_t* S, int64_t* F, int64_t* n_normals) try {
+  if (!h) return GPX_E_ARG;
+  if (S) *S = h->pw.S;
+  if (F) *F = h->pw.F;
+  if (n_normals) *n_normals = h->pw.n_normals;
+  return GPX_OK;
 }
 GPX_CATCH_ALL
 
@@ -4436,6 +4608,41 @@ int gpx_kernel_path_dtheta_matrix(int32_t kernel, const double* A, const int32_t
     return rc;
   launch_path_dtheta_matrix(kernel, kc.As, kc.ga, na, kc.napad, kc.Bs, kc.gb, nb_, d, kc.q, n_ls_path, sg2, kc.K, kc.ld, kc.st);
   return kc.fetch(G);
+}
+GPX_CATCH_ALL
+
+int gpx_pathwise_eval_raw(int32_t kernel, int32_t dtype, const double* Xq, int64_t M, const double* X, int64_t N, int32_t d,
+                          const double* ls, int32_t n_ls, double sf2, const double* Omega, int64_t F, const double* W,
+                          const double* V, int64_t C, double* out) try {
+  if (!Xq || !X || !ls || !Omega || !W || !V || !out || !sizes_ok(M, N, d, n_ls) || F < 1 || C < 1) return GPX_E_ARG;
+  if (!cov::known(kernel) || !unit_dtype_ok(dtype) || M > (1 << 24) || N > (1 << 24) || F > (1 << 24) || C > (1 << 20))
+    return GPX_E_ARG;
+  auto run = [&](auto t) -> int {
+    using T = decltype(t);
+    KernelCall<T> kc;  // the points scaled as the fit's and the queries' are; its output block is not used
+    if (int rc = kc.points(Xq, M, X, N, d, ls, n_ls)) return rc;
+    const int64_t cpad = round_up(C, 64), ldw = round_up(2 * F, 64), ldv = kc.nbpad, mpad = kc.napad;
+    const int nz = pathwise_splits(kc.nbpad, F, true);
+    std::vector<T> hW((size_t)cpad * ldw, (T)0), hV((size_t)cpad * ldv, (T)0), hO((size_t)cpad * mpad);
+    for (int64_t c = 0; c < C; ++c) {
+      for (int64_t j = 0; j < 2 * F; ++j) hW[c * ldw + j] = (T)W[c * 2 * F + j];
+      for (int64_t n = 0; n < N; ++n) hV[c * ldv + n] = (T)V[c * N + n];
+    }
+    Dev<T> dW, dV, part, outT;
+    Dev<double> dOm;
+    if (int rc; (rc = dW.upload(hW.data(), hW.size(), kc.st)) || (rc = dV.upload(hV.data(), hV.size(), kc.st)) ||
+                (rc = dOm.upload(Omega, (size_t)F * d, kc.st)) || (rc = part.alloc((size_t)nz * cpad * mpad)) ||
+                (rc = outT.alloc((size_t)cpad * mpad)))
+      return rc;
+    launch_pathwise_eval<T>(kernel, kc.As, mpad, kc.Bs, kc.nbpad, d, sf2, dV, ldv, dOm, F, dW, ldw, cpad, part, outT, mpad,
+                            kc.st);
+    UCHK(hipMemcpyAsync(hO.data(), outT, hO.size() * sizeof(T), hipMemcpyDeviceToHost, kc.st));
+    if (int rc = kc.sc.finish()) return rc;
+    for (int64_t c = 0; c < C; ++c)
+      for (int64_t m = 0; m < M; ++m) out[c * M + m] = (double)hO[c * mpad + m];
+    return GPX_OK;
+  };
+  return dtype == GPX_F32 ? run(float()) : run(double());
 }
 GPX_CATCH_ALL
 

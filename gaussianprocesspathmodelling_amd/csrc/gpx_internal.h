@@ -496,6 +496,33 @@ void launch_loo_rows(const double* ZT, int64_t ld, int64_t n, const double* ZHT,
 void launch_loo_finish(const double* q, const double* alphaT, int64_t ld, const double* Y, int64_t n, int k, double* mean,
                        double* var, double* logp, hipStream_t st);
 
+// ---- pathwise posterior function samples (gpx_pathwise.hip) ------------------------
+// q of include/gpx.h: the chi-square degrees of freedom of the family's spectral density (0: RBF, Gaussian frequencies)
+int pathwise_chi_dof(int kernel);
+// splits of launch_pathwise_eval's contraction: feature chunks, then (with_v) training chunks — functions of (npad, F) only
+int pathwise_splits(int64_t npad, int64_t F, bool with_v);
+// outT (cpad x mpad, ldo) = W Phi(As)^T + V K(As, Bs)^T, matrix-free on the MFMA units.  As (mpad x d, mpad a multiple of
+// 64) and Bs (npad x d, npad a multiple of 64): scaled points, rows beyond the valid ones zero; V (cpad x ldv, cpad a
+// multiple of 64, zero beyond the valid columns; null: the feature term alone); Om (F x d, fp64); W (cpad x ldw, ldw >=
+// round_up(2 F, 64), zero beyond 2 F); part: pathwise_splits(npad, F, V != null) * cpad * mpad elements.
+template <typename T>
+void launch_pathwise_eval(int kernel, const T* As, int64_t mpad, const T* Bs, int64_t npad, int d, double sf2, const T* V,
+                          int64_t ldv, const double* Om, int64_t F, const T* W, int64_t ldw, int64_t cpad, T* part, T* outT,
+                          int64_t ldo, hipStream_t st);
+// Om and W (every element of cpad x ldw) from the call's stream of normals: z (the caller's, device) or Philox `seed`
+template <typename T>
+void launch_pathwise_draw(const T* z, uint64_t seed, int64_t F, int d, int q, int64_t C, int64_t cpad, int64_t N, double* Om,
+                          T* W, int64_t ldw, hipStream_t st);
+// R (cpad x npad of ldr) = y^T - FT - sqrt(sn2 w) E for col < C, n < N, zero elsewhere; ebase = F (d + q); R may be FT
+template <typename T>
+void launch_pathwise_resid(const T* y, const T* FT, int64_t ldf, const T* wv, double sn2, const T* z, uint64_t seed,
+                           int64_t ebase, int64_t F, int64_t N, int64_t npad, int k, int64_t C, int64_t cpad, T* R,
+                           int64_t ldr, hipStream_t st);
+// out (S, M, k)[s][m0 + mm][c] = outT[(s0 + s) k + c - r0][mm] for mm < mv
+template <typename T>
+void launch_pathwise_unpack(const T* outT, int64_t ldo, int64_t r0, int64_t s0, int64_t S, int64_t M, int64_t m0, int64_t mv,
+                            int k, T* out, hipStream_t st);
+
 // ---- removal of observations (gpx_update.hip) -----------------------------------
 constexpr int UPD_W = 64;  // panel width of the rank-m update of the trailing factor = most columns m one pass removes
 // carry W ((n3 + 64) x UPD_W, compact): row i < n3 = columns [a, a + m) of row a + m + i of L, rows n3 + r those columns of

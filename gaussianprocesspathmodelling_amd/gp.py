@@ -1125,6 +1125,39 @@ class GP:
             res = out.permute(1, 2, 0) if devq is not None else out.transpose(1, 2, 0)
         return res.contiguous() if devq is not None else np.ascontiguousarray(res)
 
+    def sample_functions(self, n_samples, n_features=4096, random_state=0, z=None):
+        """Draw ``n_samples`` posterior sample FUNCTIONS once; evaluate them anywhere, as often as needed
+        (:class:`PosteriorFunctions`; ``gpx_pathwise_draw`` / ``gpx_pathwise_eval``, pathwise conditioning after Wilson
+        et al. 2020).  Where :meth:`sample_y` builds and factorises an M x M covariance for every new ``Xs``, the draw here
+        costs one solve against the factor the fit already holds, and an evaluation one matrix-free pass over
+        ``k(Xs, X)``: M can be millions, and evaluating again elsewhere gives the same functions.
+
+        What is exact and what is not: the conditioning on the data (the update ``k(x, X) K_y^-1 (y - f~(X) - eps)``) is
+        exact.  The prior draw ``f~`` is approximate: a sum of ``n_features`` random Fourier features whose covariance
+        misses the kernel by O(1 / sqrt(n_features)).  ``profiles/pathwise_bias.json`` tabulates the resulting bias of
+        the posterior variance per family for 256, 1024 and 4096 features.
+
+        ``random_state`` (an int) seeds the device's Philox stream; ``z`` instead supplies the call's
+        ``F (d + q) + S k (2 F + N)`` standard normals in the layout include/gpx.h specifies.  Sample s depends on
+        (seed, s, n_features, N, d, k, kernel) only.  A model that is fitted again, updated or reduced drops the draw:
+        the object then raises ``RuntimeError``.  One draw is live per model; a new one replaces it."""
+        if not self._fitted:
+            raise RuntimeError("sample_functions() before a successful fit()")
+        S, F = int(n_samples), int(n_features)
+        if S < 1 or F < 1:
+            raise ValueError("n_samples and n_features must be >= 1")
+        seed = 0 if random_state is None else int(random_state) & 0xFFFFFFFFFFFFFFFF
+        pz, kz, keepz = None, _abi.MEM_HOST, None
+        if z is not None:
+            pz, kz, keepz, _, sz = self._as_input(z, "z")
+            q = {"rbf": 0, "matern52": 5, "matern32": 3, "matern12": 1}[self.kernel]
+            nn = F * (self._d + q) + S * self._k * (2 * F + self._N)
+            if int(np.prod(sz)) != nn:
+                raise ValueError(f"z must hold F (d + q) + S k (2 F + N) = {nn} standard normals")
+        self._check(self._lib.gpx_pathwise_draw(self._h, S, F, seed, pz, kz))
+        self._pw_token = getattr(self, "_pw_token", 0) + 1
+        return PosteriorFunctions(self, S, F, self._pw_token)
+
     # -- checkpoint / resume (SURVEY.md §5: optional get_state) ------------------------------
     def get_state(self):
         """Plain-data description of the model (JSON-serialisable): kernel, hyper-parameters,
@@ -1445,3 +1478,59 @@ class GP:
         self.fit(X, y, **fit_kw())
         res.x, res.fun = best["v"], best["f"]
         return res
+
+
+class PosteriorFunctions:
+    """Posterior sample functions of a fitted :class:`GP` (:meth:`GP.sample_functions`): drawn once, evaluated anywhere.
+
+    Calling the object evaluates the SAME functions at whatever points it is given: a coarse grid now, a finer one or
+    another consumer's points later.  The conditioning on the data is exact; the prior draw behind it is a sum of
+    ``n_features`` random Fourier features, approximate with O(1 / sqrt(n_features)) error in its covariance
+    (``profiles/pathwise_bias.json``).  The draw lives in the model's handle: fitting, updating or reducing the model, or
+    drawing again, ends it, and the object raises ``RuntimeError`` from then on."""
+
+    def __init__(self, gp, n_samples, n_features, token):
+        self._gp, self.n_samples, self.n_features, self._token = gp, int(n_samples), int(n_features), token
+
+    def _live(self):
+        gp = self._gp
+        if gp is None or getattr(gp, "_h", None) is None or getattr(gp, "_pw_token", None) != self._token:
+            return False
+        S = C.c_int64(0)
+        gp._check(gp._lib.gpx_pathwise_info(gp._h, C.byref(S), None, None))
+        return S.value == self.n_samples
+
+    def __call__(self, Xs, samples=None):
+        """The functions at ``Xs`` (M, d): (M, S) for a 1-D ``y``, (M, k, S) otherwise, as :meth:`GP.sample_y` shapes its
+        result.  ``samples``: None (all), an int count or a ``slice`` with step 1 — the functions to evaluate.  NumPy in,
+        NumPy out; a device tensor in, a device tensor out."""
+        if not self._live():
+            raise RuntimeError("the model changed (or drew again) after sample_functions(): these functions are gone")
+        gp = self._gp
+        if samples is None:
+            s0, s1 = 0, self.n_samples
+        elif isinstance(samples, slice):
+            s0, s1, step = samples.indices(self.n_samples)
+            if step != 1:
+                raise ValueError("samples must be a contiguous slice")
+        else:
+            s0, s1 = 0, int(samples)
+        if not 0 <= s0 < s1 <= self.n_samples:
+            raise ValueError(f"samples must select at least one of the {self.n_samples} functions")
+        pq, kq, keepq, devq, sq = gp._as_input(Xs, "Xs")
+        if len(sq) != 2 or sq[1] != gp._d:
+            raise ValueError(f"Xs must be (M, {gp._d})")
+        M, k, S = sq[0], gp._k, s1 - s0
+        out = gp._empty((S, M, k), devq)
+        gp._check(gp._lib.gpx_pathwise_eval(gp._h, pq, M, s0, S, gp._ptr(out), kq))
+        if gp._y1d:
+            res = out[:, :, 0].T
+        else:
+            res = out.permute(1, 2, 0) if devq is not None else out.transpose(1, 2, 0)
+        return res.contiguous() if devq is not None else np.ascontiguousarray(res)
+
+    def close(self):
+        """Free the draw's device memory (if it is still this one's)."""
+        if self._gp is not None and self._live():
+            self._gp._check(self._gp._lib.gpx_pathwise_draw(self._gp._h, 0, 0, 0, None, _abi.MEM_HOST))
+        self._gp = None

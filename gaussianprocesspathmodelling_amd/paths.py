@@ -335,6 +335,29 @@ class PathModel:
         s = s.reshape(len(qn), -1, int(n_samples))                     # (M, k, n)
         return np.ascontiguousarray(s.transpose(2, 0, 1)) * self.y_std + self.y_mean
 
+    def sample_functions(self, n_samples, n_features=4096, seed=0):
+        """``n_samples`` plausible paths of this cluster as FUNCTIONS (``GP.sample_functions``: drawn once, evaluated
+        anywhere).  Returns a callable: ``paths(q)`` takes raw inputs ``q`` (M,) or (M, d) and returns (n_samples, M, k) in
+        the targets' own units, like :meth:`sample` — the same paths on any grid, as fine as needed, at no cost in M^2.
+        The prior behind the draw is approximate (``n_features`` random features; see ``GP.sample_functions``).  Raises
+        ``ValueError`` on models that are ``within_path``, have a trend or have velocities.  The callable raises
+        ``RuntimeError`` once the model has changed."""
+        for flag, why in ((self.within_path, "the model is within_path (path ids)"),
+                          (self.trend is not None, "the model has a trend (basis functions)"),
+                          (self.has_velocities, "the model has velocities (derivative observations)")):
+            if flag:
+                raise ValueError(f"sample_functions: {why}: pathwise sampling does not cover it")
+        fs = self.gp.sample_functions(n_samples, n_features=n_features, random_state=seed)
+        n = int(n_samples)
+
+        def paths(q):
+            qn = self._queries(q)
+            s = fs(qn).reshape(len(qn), -1, n)                             # (M, k, n)
+            return np.ascontiguousarray(s.transpose(2, 0, 1)) * self.y_std + self.y_mean
+
+        paths.functions = fs
+        return paths
+
     def predict_gradient(self, q, return_var=True, path=None):
         """Gradient of the posterior with respect to the raw (un-normalised) inputs ``q`` (M,) or (M, d), in target units
         per input unit: ``dmean`` (M, d, k) and, with ``return_var``, ``dvar`` (M, d, k), the latent variance of each

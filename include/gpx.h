@@ -536,6 +536,47 @@ int gpx_lml_grad_paths(gpx_handle* h, double* lml, double* grad /* n_ls + 2, as 
  * same bits.  GPX_E_ARG without a fit or with four NULL outputs; GPX_E_UNSUPPORTED on GPX_F32 / GPX_MIXED handles and on
  * shards, device groups and handles that own a communicator.  A failed call writes nothing and leaves the fit valid. */
 int gpx_loo(gpx_handle* h, double* mean /* (N,k) */, double* var /* (N) */, double* logp /* (N,k) */, double* total /* (k) */);
+
+/* ---- pathwise posterior function samples (additive to ABI v6) ------------------------------------------
+ * Matheron's rule with a random-Fourier-feature prior (Wilson et al. 2020): a posterior sample is a FUNCTION, drawn once
+ * and evaluated anywhere, again and again.  With u = x / l (per dimension for ARD), F frequencies, C = S k columns,
+ * col = s k + c, and K_y the matrix the fit factorised (noise, weights and jitter included):
+ *   q                 = 2 nu of the family: 5 Matern-5/2, 3 Matern-3/2, 1 Matern-1/2; 0 for RBF
+ *   Omega (F, d)      scaled frequencies shared by all columns: Omega_f = g_f sqrt(q / chi_f), g_f d standard normals, chi_f
+ *                     the sum of squares of q further normals, in order (a Student-t draw; chi_f = 0, which only a
+ *                     caller's all-zero z produces: Omega_f = 0); RBF: Omega_f = g_f
+ *   theta_f(x)        = sum_j Omega_fj u_j
+ *   f~_col(x)         = sqrt(sf2 / F) sum_f [ W[col, f] cos theta_f(x) + W[col, F + f] sin theta_f(x) ],  W (C, 2F) normals
+ *   R[col, n]         = y[n, c] - f~_col(x_n) - sqrt(sn2 w_n) E[col, n],  E (C, N) normals, w_n the noise weight (1 without
+ *                     weights); the factor's jitter is not sampled
+ *   V                 = R K_y^-1, rows as alpha^T
+ *   out[s, m, c]      = f~_col(x_m) + sum_n sf2 k(x_m, x_n) V[col, n]
+ * The conditioning on the data is exact; only the prior draw is approximate: its covariance Phi Phi^T misses sf2 k by
+ * O(1 / sqrt(F)) (profiles/pathwise_bias.json tabulates the effect on the posterior variance).
+ *
+ * One flat stream of n_normals = F (d + q) + C (2F + N) standard normals feeds a draw: numbers [f (d + q), (f + 1)(d + q))
+ * are g_f followed by the chi normals of frequency f; after that block every column has 2F + N numbers, W[col, :] then
+ * E[col, :].  z == NULL: number i is normal number i of the Philox stream `seed` that gpx_sample_posterior specifies.
+ * Otherwise z holds the n_normals values, in the handle's element type and the memory kind of the call.  Consequence:
+ * sample s depends on (seed, s, F, N, d, k, kernel) only — the first S' samples of a larger draw are the draw with S'.
+ *
+ * gpx_pathwise_draw stores Omega, W and V in the handle: state of the fit, not scratch (gpx_release_scratch keeps it).
+ * S = 0 drops the stored draw.  Whatever changes the factor drops it too: gpx_fit, gpx_fit_predict, gpx_append(_weighted,
+ * _rows), gpx_remove_rows; and gpx_set_noise_weights.  Cost: one pass of the evaluation kernel over the training points and
+ * one pair of triangular solves per 64 columns (a column's bits do not depend on how many columns the draw has).
+ * gpx_pathwise_eval writes samples [s0, s0 + S) of the stored draw at the M query points Xs into out (S, M, k), element
+ * type and memory kind as gpx_predict; nothing of size M N or M M is stored, query points go in batches (any M), and
+ * evaluating the same point again — alone, in another batch, with other samples — returns the same bits.  Without a live
+ * draw: GPX_E_ARG, and gpx_last_error says so.  It only reads the fit: gpx_predict afterwards is bit-identical.
+ * gpx_pathwise_info: the stored draw's S, F and n_normals (0, 0, 0 without one); each pointer may be NULL.
+ * Single-device GPX_F64 / GPX_F32 handles, every family, scalar or ARD lengthscales, with or without noise weights.
+ * GPX_E_UNSUPPORTED with a message, nothing computed and the fit still valid: GPX_MIXED handles, shards, device groups,
+ * fits with derivative observations, with path ids or with a basis.  Timings: kstar (the draw: normals, features, residual
+ * rows; eval: the query points), trsm (the draw's solves), mean (eval's kernel), d2h, predict_total. */
+int gpx_pathwise_draw(gpx_handle* h, int64_t S, int64_t F, uint64_t seed, const void* z, int32_t mem_kind);
+int gpx_pathwise_eval(gpx_handle* h, const void* Xs, int64_t M, int64_t s0, int64_t S, void* out /* (S,M,k) */,
+                      int32_t mem_kind);
+int gpx_pathwise_info(gpx_handle* h, int64_t* S, int64_t* F, int64_t* n_normals);
 int gpx_logdet(gpx_handle* h, double* out);
 /* Frees what only the NEXT predict / gradient call would use (the V^T batch, the L^-T buffer of
  * gpx_lml_grad, per-tile partials, compact block buffers, the buffers of the joint-posterior calls); the fit itself (factor, alpha, block
@@ -684,6 +725,14 @@ int gpx_kernel_hess_matrix(int32_t kernel, int32_t dtype, const double* A, const
 int gpx_kernel_path_dtheta_matrix(int32_t kernel, const double* A, const int32_t* ga, int64_t na, const double* B,
                                   const int32_t* gb, int64_t nb, int32_t d, const double* ls_path, int32_t n_ls_path,
                                   double sg2, double* G /* (1 + n_ls_path, na, nb) */);
+/* kernel unit-test entry point (host buffers; additive to ABI v6): the evaluation kernel of gpx_pathwise_eval apart from any
+ * factor.  out (C, M)[c][m] = sqrt(sf2 / F) sum_f (W[c][f] cos theta_f(Xq_m) + W[c][F + f] sin theta_f(Xq_m))
+ * + sum_n sf2 k(Xq_m, X_n) V[c][n], with Omega (F, d), W (C, 2F), V (C, N) as given.  dtype GPX_F64 or GPX_F32 (the fp32
+ * kernel on the rounded inputs, phases still in fp64, returned widened).  GPX_E_ARG, before any device call: a NULL
+ * pointer, a size < 1, d outside [1, 32], n_ls not 1 or d, an unknown family or dtype. */
+int gpx_pathwise_eval_raw(int32_t kernel, int32_t dtype, const double* Xq, int64_t M, const double* X, int64_t N, int32_t d,
+                          const double* ls, int32_t n_ls, double sf2, const double* Omega, int64_t F,
+                          const double* W /* (C,2F) */, const double* V /* (C,N) */, int64_t C, double* out /* (C,M) */);
 /* in-place lower Cholesky of A (n,n), lda = n; n multiple of 64.  The strictly upper
  * triangle is never read and is scratch on return (diagonal tiles are updated whole).
  * block = panel width (0 = default). */
