@@ -638,10 +638,20 @@ inline int64_t split_rows_128(int64_t nr, int64_t nc) {
   return (nr > 128 && nr % 128 != 0 && nc % 128 == 0) ? nr / 128 * 128 : nr;
 }
 
+// The two-level factorisation's deferred product (chol_two_level_enqueue), split schedule only:
+// while o < c1 the 128-multiple of the side rows is updated in columns [t0, c1) only, and right behind the side step of
+// the last panel left of c1 ONE product at K = c1 gives their columns [c1, n) what those panels owe them.
+struct DeferLeft {
+  int64_t c1 = 0;    // a panel boundary in (0, n)
+  int64_t smin = 0;  // strassen_nt from quadrants of this size on; 0: one classical launch
+  size_t temp = 0;   // elements of ONE panel buffer: the level's temporaries live in the buffer of that last panel
+};
+
 template <typename T>
 int chol_enqueue(gpx_handle* h, T* A, int64_t ld, int64_t n, int nb, T* Winv, T* P0, T* P1,
                  int64_t ldp, int* info, int64_t gidx0, bool profile, int64_t nx = 0,
-                 InvWork<T>* iw = nullptr, int64_t nx_side = 0, int rest_split_arg = -1) {
+                 InvWork<T>* iw = nullptr, int64_t nx_side = 0, int rest_split_arg = -1,
+                 const DeferLeft* defer = nullptr) {
   hipStream_t s0 = h->st, s1 = h->st2;
   T* Pbuf[2] = {P0, P1};
   int rc;
@@ -721,6 +731,36 @@ int chol_enqueue(gpx_handle* h, T* A, int64_t ld, int64_t n, int nb, T* Winv, T*
     if (na < nxs) launch_gemm_nt<T>(64, Pside + na * ldp, ldp, Aside + na * ld, ld, Wp, iw->nbw, nxs - na, nbp, nbp, 4, 1, s);
     launch_copy2d<T>(Aside, ld, Pside, ldp, nxs, nbp, s);
     return GPX_OK;
+  };
+  // The deferred product (DeferLeft): A[side rows, c1:n) -= L[side rows, 0:c1) L[c1:n, 0:c1)^T for the dna side rows that go
+  // out in 128-tiles; the remainder (the right-hand sides) stays right-looking.
+  const int64_t dna0 = (defer && iw && nxs > 0 && !fuse_env && defer->c1 > 0 && defer->c1 < n && defer->c1 % nb == 0 && n % 128 == 0)
+                           ? split_rows_128(nxs, n - defer->c1)
+                           : 0;
+  const int64_t dna = dna0 % 128 == 0 ? dna0 : 0, dc1 = dna > 0 ? defer->c1 : 0;
+  auto deferred_product = [&](T* Tbuf, hipStream_t s) {
+    T* Cd = A + (n + nxc) * ld + dc1;
+    const T *Ad = A + (n + nxc) * ld, *Bd = A + dc1 * ld;
+    const int64_t nd = n - dc1, kd = dc1, ldt = kd / 2 + ld_skew<T>();
+    // through a Strassen level in row chunks, in a fixed order: the fewest chunks whose temporaries fit the panel buffer,
+    // as long as their quadrants are large enough for a level; else one classical launch
+    int64_t mch = 0;
+    for (int64_t parts = 1; defer->smin > 0 && parts <= dna / 256; ++parts) {
+      const int64_t m = round_up((dna + parts - 1) / parts, 256);
+      if (std::min(m, nd) / 256 * 128 < defer->smin) break;
+      if (strassen_temp_elems(m, nd, kd, ld_skew<T>()) <= defer->temp) {
+        mch = m;
+        break;
+      }
+    }
+    if (mch == 0) {
+      launch_gemm_nt<T>(128, Cd, ld, Ad, ld, Bd, ld, dna, nd, kd, 0, 0, s);
+      return;
+    }
+    for (int64_t r = 0; r < dna; r += mch) {
+      const int64_t m = std::min(mch, dna - r);
+      strassen_nt<T>(Cd + r * ld, ld, Ad + r * ld, ld, Bd, ld, m, nd, kd, Tbuf, Tbuf + (m / 256 * 128) * ldt, ldt, s);
+    }
   };
   LatencyGuard latency_guard;
   set_latency_mode(1);  // panel 0: nothing runs beside it
@@ -810,6 +850,9 @@ int chol_enqueue(gpx_handle* h, T* A, int64_t ld, int64_t n, int nb, T* Winv, T*
         PhaseScope ps(h, &h->tm.chol_strip, profile, s1);
         launch_gemm_nt<T>(tile, A + t0 * ld + t0, ld, Pc, ldp, Pc, ldp, nbn, nbn, nbp, 1, 0, s1);
       }
+      // the deferred product takes this panel's buffer for its temporaries: behind this launch, its reader on the chain
+      hipEvent_t e_stripd = nullptr;
+      if (t0 == dc1 && (rc = record_event(h, s1, "deferred product", &e_stripd))) return rc;
       // The host enqueues the main stream's whole iteration BEFORE the diagonal chain's ~50 small launches: the
       // GPU runs the chain about as fast as the host can enqueue it (N = 8192: the update used to reach the GPU
       // 0.5 ms after the panel it needs, and then collided with the NEXT panel solve and diagonal-block update).
@@ -856,7 +899,24 @@ int chol_enqueue(gpx_handle* h, T* A, int64_t ld, int64_t n, int nb, T* Winv, T*
         PhaseScope ps(h, &h->tm.chol_strip, profile, sm);
         bordered_block(o, Pc, sm, t0 + nbn, nrest, 0, nxc);
         if ((rc = side_solve(o, Pc, sm))) return rc;
-        bordered_block(o, Pc, sm, t0, ntrail, nxc, nxs);
+        if (o < dc1) {
+          // deferral: the 128-tile rows only in columns [t0, c1) — in the tiles the whole launch would take, so that
+          // those columns receive the same addends bit for bit — and the remainder's launch as it is
+          if (dc1 > t0)
+            launch_gemm_nt_fixed<T>(gemm_nt_tile(128, dna, ntrail, 0), A + (n + nxc) * ld + t0, ld, Pc + (ntrail + nxc) * ldp, ldp,
+                                    Pc, ldp, dna, dc1 - t0, nbp, 0, 0, sm);
+          bordered_block(o, Pc, sm, t0, ntrail, nxc + dna, nxs - dna);
+          if (t0 == dc1) {
+            // B operand: rows [c1, n) of the panels so far are in A once this panel's copy-back is (the copy stream
+            // runs in order).  Temporaries: this panel's buffer, behind its copy-back and behind STRIP_D on the chain;
+            // its next writer, the solve of the panel after next, waits for the next "rows below" event of this stream.
+            if (iw->copied[step & 1]) HIPCHK(h, hipStreamWaitEvent(sm, iw->copied[step & 1], 0));
+            HIPCHK(h, hipStreamWaitEvent(sm, e_stripd, 0));
+            deferred_product(Pc, sm);
+          }
+        } else {
+          bordered_block(o, Pc, sm, t0, ntrail, nxc, nxs);
+        }
       }
       set_reserve_mode(0);
       {
@@ -981,7 +1041,17 @@ int chol_two_level_enqueue(gpx_handle* h, T* A, int64_t ld, int64_t n, int nb, T
   //  early hand-over — GPX_REST_SPLIT, tuned on the one-level schedule — from half as many trailing panels on; N = 65536:
   //  1513.3 against 1521.6 ms)
   const int rs = env.rest_split / 2;
-  if ((rc = chol_enqueue<T>(h, A, ld, c, nb, Winv, P0, P1, ldp, info, gidx0, profile, np + nx, iw, np + nx, rs))) return rc;
+  // GPX_DEFER_LEFT: the panels left of c1 — the panel boundary nearest c / 2, at least one panel on each side — leave
+  // A21's columns [c1, c) alone, and one product at K = c1 (large in all three dimensions: a Strassen level pays, which
+  // it cannot at K = nb) makes up for it.  Unset: on where the level is; 1 with the level off: a classical product.
+  DeferLeft defer;
+  defer.c1 = std::min<int64_t>(std::max<int64_t>(1, (c / 2 + nb / 2) / nb) * nb, c - nb);
+  defer.smin = depth > 0 ? smin : 0;
+  defer.temp = (size_t)(P1 - P0);
+  const bool defer_on = (env.defer_left < 0 ? depth > 0 : env.defer_left != 0) && defer.c1 > 0;
+  if ((rc = chol_enqueue<T>(h, A, ld, c, nb, Winv, P0, P1, ldp, info, gidx0, profile, np + nx, iw, np + nx, rs,
+                            defer_on ? &defer : nullptr)))
+    return rc;
   // 2. the deep update
   T* A22 = A + c * ld + c;
   const T* L21 = A + c * ld;

@@ -54,6 +54,7 @@ inline int64_t in_range(int64_t v, int64_t lo, int64_t hi, int64_t otherwise) { 
   X("GPX_STRASSEN_MIN", strassen_min, I64, call, 4096, env_rule::in_range(atoll(e), 0, 1L << 40, 0) / 128 * 128)          \
   X("GPX_STRASSEN_DIAG", strassen_diag, Flag, call, false, env_rule::flag(e))                                          \
   X("GPX_STRASSEN_SINGLE", strassen_f32, Flag, call, false, env_rule::flag(e))                                            \
+  X("GPX_DEFER_LEFT", defer_left, Opt, call, -1, env_rule::flag(e))                                                    \
   /* widths and batches */                                                                                          \
   X("GPX_NB_WIDE_FROM", nb_wide_from, I64, call, 40960, (int64_t)atoll(e))                                             \
   X("GPX_NB_GRAD", nb_grad, Int, call, 0, env_rule::block(e, 4096, 0))                                                 \

@@ -7,6 +7,9 @@ lengthscale 0.25, sf2 1.5, sn2 1e-2) at N = 4096 and 8192, factorised
   two_level    split at the panel boundary c nearest N / 2: left block column, ONE update A22 -= L21 L21^T, right block,
   strassen     the same with one Strassen level on the off-diagonal block of that update,
   strassen2    and on the off-diagonal blocks of its two diagonal halves as well,
+  deferred     strassen, and in the left block column the panels left of c1 (the panel boundary nearest c / 2) leave
+               A21[:, c1:c] alone: ONE product A21[:, c1:c] -= L21[:, :c1] L11[c1:c, :c1]^T behind them (GPX_DEFER_LEFT),
+  deferred_strassen   the same with that product through a Strassen level (in two row halves, as at N = 65536),
 
 each followed by z = L^-1 y, alpha = L^-T z, mean = K* alpha, var = k** - |L^-1 K*^T|^2 and log det.  Errors are those of
 tests/test_full_size_gpu.py against OracleGP (LAPACK): mean and variance elementwise relative (floors 1e-6, 1e-6 sf2),
@@ -43,16 +46,27 @@ def strassen_nt(C, A, B):
     M = (A2 - A4) @ (B2 + B4).T; C11 -= M
 
 
-def chol_blocked(A, nb, rows_below=0):
+def chol_blocked(A, nb, rows_below=0, defer=None):
     """right-looking, in place: the leading n x n block of A (n = A.shape[0] - rows_below) is factorised, the rows below it
-    ride along as bordered rows (solved and updated, never factorised)"""
+    ride along as bordered rows (solved and updated, never factorised).  defer = "classical" / "strassen": the deferred
+    product of the bordered rows' columns [c1, n)"""
     n = A.shape[0] - rows_below
+    c1 = min(max(1, (n // 2 + nb // 2) // nb) * nb, n - nb) if defer else 0
     for o in range(0, n, nb):
         e = min(o + nb, n)
         A[o:e, o:e] = cholesky(A[o:e, o:e], lower=True)
         if e < A.shape[0]:
             A[e:, o:e] = solve_triangular(A[o:e, o:e], A[e:, o:e].T, lower=True).T
-            if e < n:
+            if e < n and o < c1:
+                A[e:n, e:n] -= A[e:n, o:e] @ A[e:n, o:e].T
+                A[n:, e:c1] -= A[n:, o:e] @ A[e:c1, o:e].T
+                if e == c1 and defer == "classical":
+                    A[n:, c1:n] -= A[n:, :c1] @ A[c1:n, :c1].T
+                elif e == c1:
+                    h = rows_below // 2
+                    strassen_nt(A[n:n + h, c1:n], A[n:n + h, :c1], A[c1:n, :c1])
+                    strassen_nt(A[n + h:, c1:n], A[n + h:, :c1], A[c1:n, :c1])
+            elif e < n:
                 A[e:, e:n] -= A[e:, o:e] @ A[e:n, o:e].T
     return A
 
@@ -69,11 +83,11 @@ def deep_update(A22, L21, levels):
     deep_update(A22[h:, h:], L21[h:], levels - 1)
 
 
-def chol_two_level(K, nb, levels):
+def chol_two_level(K, nb, levels, defer=None):
     n = K.shape[0]
     c = max(1, (n // 2 + nb // 2) // nb) * nb
     A = K.copy()
-    chol_blocked(A[:, :c], nb, rows_below=n - c)       # L11, L21 (A21 rides as bordered rows)
+    chol_blocked(A[:, :c], nb, rows_below=n - c, defer=defer)       # L11, L21 (A21 rides as bordered rows)
     deep_update(A[c:, c:], A[c:, :c], levels)
     chol_blocked(A[c:, c:], nb)
     return A
@@ -104,9 +118,12 @@ def run(N, M, nb):
     kss = np.full(M, SF2)
     row = {"N": N, "M": M, "nb": nb}
     for name, L in (("blocked", chol_blocked(K.copy(), nb)), ("two_level", chol_two_level(K, nb, 0)),
-                    ("strassen", chol_two_level(K, nb, 1)), ("strassen2", chol_two_level(K, nb, 2))):
+                    ("strassen", chol_two_level(K, nb, 1)), ("strassen2", chol_two_level(K, nb, 2)),
+                    ("deferred", chol_two_level(K, nb, 1, "classical")),
+                    ("deferred_strassen", chol_two_level(K, nb, 1, "strassen"))):
         row[name] = errors(outputs(np.tril(L), y, Ks, kss), ref)
-    worst = max(row[s][q] / max(row["blocked"][q], 1e-17) for s in ("strassen", "strassen2") for q in row["blocked"])
+    worst = max(row[s][q] / max(row["blocked"][q], 1e-17)
+                for s in ("strassen", "strassen2", "deferred", "deferred_strassen") for q in row["blocked"])
     row["worst_ratio_to_blocked"] = worst
     return row
 
