@@ -5,7 +5,8 @@ Everything numerical lives in ``csrc/libgpx.so`` (HIP, gfx950) behind the C ABI 
 not load the library; constructing a :class:`GP` does, and raises if it is missing.
 """
 from .gp import GP, PosteriorFunctions  # noqa: F401
+from .sparse import SparseGP  # noqa: F401
 from ._abi import GpxError  # noqa: F401
 
-__all__ = ["GP", "GpxError", "PosteriorFunctions"]
+__all__ = ["GP", "GpxError", "PosteriorFunctions", "SparseGP"]
 __version__ = "0.1.0"

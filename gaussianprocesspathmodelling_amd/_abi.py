@@ -120,6 +120,15 @@ SIGNATURES = {
     "gpx_pathwise_info": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "gpx_pathwise_eval_raw": (C.c_int, [C.c_int32, C.c_int32, _PD, C.c_int64, _PD, C.c_int64, C.c_int32, _PD, C.c_int32,
                                         C.c_double, _PD, C.c_int64, _PD, _PD, C.c_int64, _PD]),
+    "gpx_sparse_fit": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int32, C.c_int32, _P, C.c_int64, _PD, C.c_int32, C.c_double,
+                                 C.c_double, C.c_double, C.c_int64, C.c_int32, C.POINTER(C.c_int64)]),
+    "gpx_sparse_predict": (C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int32]),
+    "gpx_sparse_predict_cov": (C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int32]),
+    "gpx_sparse_elbo": (C.c_int, [_P, _PD]),
+    "gpx_sparse_info": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                  C.POINTER(C.c_int64)]),
+    "gpx_syrk_tn": (C.c_int, [_PD, C.c_int64, _PD, C.c_int64, C.c_int32]),
+    "gpx_debug_syrk_tn_bench": (C.c_int, [C.c_int64, C.c_int64, C.c_int32, C.c_int32, _PD]),
     "gpx_logdet": (C.c_int, [_P, _PD]),
     "gpx_release_scratch": (C.c_int, [_P]),
     "gpx_get_timings": (C.c_int, [_P, C.POINTER(GpxTimings)]),

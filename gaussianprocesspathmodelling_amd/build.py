@@ -12,8 +12,8 @@ import subprocess
 import sys
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
-SOURCES = ["gpx_api.hip", "gpx_blas.hip", "gpx_grad.hip", "gpx_kbuild.hip", "gpx_misc.hip", "gpx_mixed.hip", "gpx_paths.hip", "gpx_posterior.hip", "gpx_deriv.hip", "gpx_hess.hip", "gpx_score.hip", "gpx_update.hip", "gpx_basis.hip", "gpx_loo.hip", "gpx_pathwise.hip"]
-HEADERS = ["gpx_internal.h", "gpx_tile.h", "gpx_cov.h", "gpx_env.h", "gpx_shard.inc", "gpx_group.inc", os.path.join("..", "..", "include", "gpx.h")]
+SOURCES = ["gpx_api.hip", "gpx_blas.hip", "gpx_grad.hip", "gpx_kbuild.hip", "gpx_misc.hip", "gpx_mixed.hip", "gpx_paths.hip", "gpx_posterior.hip", "gpx_deriv.hip", "gpx_hess.hip", "gpx_score.hip", "gpx_update.hip", "gpx_basis.hip", "gpx_loo.hip", "gpx_pathwise.hip", "gpx_sparse.hip"]
+HEADERS = ["gpx_internal.h", "gpx_tile.h", "gpx_cov.h", "gpx_env.h", "gpx_shard.inc", "gpx_group.inc", "gpx_sparse.inc", os.path.join("..", "..", "include", "gpx.h")]
 LIB = os.path.join(CSRC, "libgpx.so")
 ARCH = "gfx950"
 

@@ -131,6 +131,7 @@ struct gpx_handle {
     DevBuf BG, BU;  // a fit with basis functions: per-slice Gram of the bordered rows; u = L_A^-1 (h - Z_H^T v*) per query row (rows x 64, fp64)
     DevBuf UW, UQ;  // gpx_remove_rows: per pass in flight (two) the carry ((N + 64) x UPD_W) and the panel's orthogonal factor (2 UPD_W square)
     DevBuf LOO;     // gpx_loo: q (N) | var (N) | mean (N x k) | logp (N x k), fp64
+    DevBuf SV1, SV2, SS2;  // gpx_sparse_predict(_cov): T1^T and T2^T of one batch of query rows; T2^T T2
     DevBuf PWZ, PWpart, PWout, PWres;  // gpx_pathwise_*: a host caller's normals, the splits' partials, OutT of one batch, results for a host caller
   } scr;
   // row-block shard (world > 1)
@@ -203,6 +204,19 @@ struct gpx_handle {
     DevBuf Om, W, V;  // Omega (F x d, fp64), W (Cpad x ldw), V = R K_y^-1 (Cpad x ld, rows as alphaT's)
     int64_t S = 0, F = 0, ldw = 0, n_normals = 0;
   } pw;
+  // inducing-point fit (gpx_sparse_fit; gpx_sparse.inc).  A handle holds a dense fit (`fitted`) or a sparse
+  // one (`sp.fitted`), never both: begin_fit drops this state, gpx_sparse_fit drops the dense factor.  Every matrix here has
+  // the leading dimension ld = mpad + 64 + skew (the chunk carries 64 bordered columns, and the solves take one ld).
+  struct Sparse {
+    bool fitted = false;
+    int64_t N = 0, m = 0, mpad = 0, chunk = 0, ld = 0;
+    double elbo[8] = {};
+    DevBuf Z, Zs;             // inducing points: raw (m x d), scaled (mpad x d)
+    DevBuf L, WinvL;          // chol(Kuu) and its 64-block inverses
+    DevBuf B, WinvB;          // chol(I + A A^T) with c^T as bordered rows [mpad, mpad + 64), and its 64-block inverses
+    DevBuf P, Wblk, Ublk, info, scal;  // the factorisations' panels, block inverses, two info blocks, the bound's scalars
+    DevBuf Xc, Xsc, Yc, Wc, Kc, part;  // one chunk: points (raw, scaled), targets, weights, bordered rows; the TN partials
+  } sp;
   // event pool
   std::vector<hipEvent_t> ev_pool;
   size_t ev_used = 0;
@@ -228,6 +242,9 @@ namespace {
 
 int fail(gpx_handle* h, int code, const char* msg) {
   if (h) h->err = msg; else g_create_error = msg;
+  // a dense entry point that finds no dense fit on a handle with a sparse one: say where that fit is served
+  if (h && h->sp.fitted && code == GPX_E_ARG && (strstr(msg, "no successful fit") || strstr(msg, "no fit")))
+    h->err += " (the handle holds an inducing-point fit: use the gpx_sparse_* calls)";
   return code;
 }
 
@@ -1272,6 +1289,10 @@ int begin_fit(gpx_handle* h) {  // ... of a call that replaces the fit
     h->fitted = false;
     h->basis = h->bp = 0;  // (fit_impl decides; the other engines never fit with a basis: check_fit_basis)
     h->pw = {};            // a stored pathwise draw belongs to the fit it was drawn against
+    if (h->sp.fitted || h->sp.L.p) {  // a dense fit replaces an inducing-point fit: its state leaves with it
+      HIPCHK(h, hipDeviceSynchronize());
+      h->sp = {};
+    }
   }
   return rc;
 }
@@ -4974,5 +4995,7 @@ int gpx_microbench(double* mfma_tflops, double* copy_gbs) try {
   return GPX_OK;
 }
 GPX_CATCH_ALL
+
+#include "gpx_sparse.inc"
 
 }  // extern "C"

@@ -523,6 +523,27 @@ template <typename T>
 void launch_pathwise_unpack(const T* outT, int64_t ldo, int64_t r0, int64_t s0, int64_t S, int64_t M, int64_t m0, int64_t mv,
                             int k, T* out, hipStream_t st);
 
+// ---- inducing-point GP (gpx_sparse.hip; fp64) --------------------------------------
+// The TN product: lower 64-tiles of C (n x n, ldc; n a multiple of 64) (+)= X^T X, X (rows x n, ldx; 16-byte aligned rows)
+// row-major — the contraction runs over the ROWS.  The rows are dealt to syrk_tn_splits(n, rows_nominal) splits of equal
+// length (a function of those two only; rows <= rows_nominal), each tile's partial sums (part: syrk_tn_part_elems
+// elements) are added in split order, each split walks its rows in ascending order.  Nothing above the diagonal is written.
+int syrk_tn_splits(int64_t n, int64_t rows_nominal);
+int64_t syrk_tn_part_elems(int64_t n, int64_t rows_nominal);
+void launch_syrk_tn(double* C, int64_t ldc, int64_t n, const double* X, int64_t ldx, int64_t rows, int64_t rows_nominal,
+                    double* part, int accumulate, hipStream_t st);
+// XT (cols x rows, ldt) = X (rows x cols, ldx)^T; rows, cols multiples of 32 (gpx_debug_syrk_tn_bench's transpose + NT route)
+void launch_transpose(const double* X, int64_t ldx, int64_t rows, int64_t cols, double* XT, int64_t ldt, hipStream_t st);
+// A chunk Kc (rows valid of rows_pad, ld) of cross-kernel rows over mpad columns: row r / s_r, s_r = sqrt(sn2 w[r]) (w null:
+// 1), and columns [mpad, mpad + 64) = y[r][0..k) / s_r, zero beyond k and on the padded rows
+void launch_sparse_border(double* Kc, int64_t ld, int64_t rows, int64_t rows_pad, int64_t mpad, const double* y, int k,
+                          const double* w, double sn2, hipStream_t st);
+// scal[0] = trace of B[0:mpad, 0:mpad], scal[1 + c] = B[mpad + c][mpad + c] (c < k), then B[j][j] += 1 for j < mpad
+void launch_sparse_close(double* B, int64_t ld, int64_t mpad, int k, double* scal, hipStream_t st);
+// var[i] = (sf2 - |V1[i]|^2) + |V2[i]|^2 + add over ncols columns, i < m
+void launch_sparse_var(const double* V1, const double* V2, int64_t ld, int64_t m, int64_t ncols, double sf2, double add,
+                       double* var, hipStream_t st);
+
 // ---- removal of observations (gpx_update.hip) -----------------------------------
 constexpr int UPD_W = 64;  // panel width of the rank-m update of the trailing factor = most columns m one pass removes
 // carry W ((n3 + 64) x UPD_W, compact): row i < n3 = columns [a, a + m) of row a + m + i of L, rows n3 + r those columns of

@@ -236,6 +236,19 @@ def kmeans(trajs, k, too_close=MIN_TRAVEL, init_keys=None, rng=None, movement_st
 
 
 # ---- one GP per path cluster (independent replicas) ---------------------------------------------
+def _dense_only(method):
+    """a :class:`PathModel` method that needs the dense factor: on a sparse model it raises, naming itself"""
+    import functools
+
+    @functools.wraps(method)
+    def guarded(self, *args, **kwargs):
+        if self.sparse:
+            raise ValueError(f"PathModel.{method.__name__}: the model is sparse (fit_path_models(inducing=)); an "
+                             "inducing-point fit serves predict() only")
+        return method(self, *args, **kwargs)
+    return guarded
+
+
 class PathModel:
     """GP model of one cluster of paths: inputs (by default the time stamp, mapped to [0, 1]) ->
     (x, y) as two targets sharing ONE Cholesky factor.  Targets are
@@ -257,12 +270,16 @@ class PathModel:
     :meth:`log_likelihood` and :meth:`forecast` include it and its uncertainty; :meth:`add_paths`, :meth:`append_paths`,
     :meth:`remove_paths`, :meth:`predict_gradient`, :meth:`velocity`, :meth:`predict_hessian`, :meth:`acceleration` and
     :meth:`curvature` raise ``GpxError`` with the library's reason.  :meth:`acceleration` and :meth:`curvature` (second
-    derivatives) need an "rbf" or "matern52" model."""
+    derivatives) need an "rbf" or "matern52" model.
+    ``sparse``: the model is an inducing-point fit (``fit_path_models(inducing=m)``; ``gp`` is a ``SparseGP``), for
+    clusters with more observations than a dense factor holds.  :meth:`predict` (mean, variance, ``return_cov``) works as
+    on any model; every other method raises ``ValueError`` naming itself."""
 
     def __init__(self, gp, keys, in_lo, in_span, y_mean, y_std, inputs, targets, step_weights=None, has_velocities=False,
-                 within_path=False, row_counts=None, trend=None):
+                 within_path=False, row_counts=None, trend=None, sparse=False):
         self.gp, self.keys = gp, list(keys)
         self.trend = trend
+        self.sparse = bool(sparse)
         # what remove_paths needs: every key's path id (within_path: its index in keys until a path has been removed, and
         # never reused after) and its number of value rows (row_counts: one per key, in order; None: not recorded)
         self._ids = {q: i for i, q in enumerate(self.keys)}
@@ -325,6 +342,7 @@ class PathModel:
             return mean
         return mean, out[1][:, None] * (self.y_std ** 2)[None, :]
 
+    @_dense_only
     def sample(self, q, n_samples, seed=0, include_noise=False, path=None):
         """``n_samples`` plausible paths of this cluster: joint posterior samples over the raw inputs ``q`` (M,) or
         (M, d), (n_samples, M, k) in the targets' own units (``GP.sample_y`` on the device, Philox stream ``seed``).
@@ -335,6 +353,7 @@ class PathModel:
         s = s.reshape(len(qn), -1, int(n_samples))                     # (M, k, n)
         return np.ascontiguousarray(s.transpose(2, 0, 1)) * self.y_std + self.y_mean
 
+    @_dense_only
     def sample_functions(self, n_samples, n_features=4096, seed=0):
         """``n_samples`` plausible paths of this cluster as FUNCTIONS (``GP.sample_functions``: drawn once, evaluated
         anywhere).  Returns a callable: ``paths(q)`` takes raw inputs ``q`` (M,) or (M, d) and returns (n_samples, M, k) in
@@ -358,6 +377,7 @@ class PathModel:
         paths.functions = fs
         return paths
 
+    @_dense_only
     def predict_gradient(self, q, return_var=True, path=None):
         """Gradient of the posterior with respect to the raw (un-normalised) inputs ``q`` (M,) or (M, d), in target units
         per input unit: ``dmean`` (M, d, k) and, with ``return_var``, ``dvar`` (M, d, k), the latent variance of each
@@ -373,6 +393,7 @@ class PathModel:
             return dmean
         return dmean, out[1][:, :, None] * scale ** 2
 
+    @_dense_only
     def velocity(self, q, return_var=True, path=None):
         """Velocity of the modelled path at the raw time stamps ``q``: the ``"t"`` column of :meth:`predict_gradient`,
         (M, k) arrays, e.g. (dx/dt, dy/dt), and with ``return_var`` their latent variances (M, k).  ``q`` is (M,) when
@@ -386,6 +407,7 @@ class PathModel:
             return out[:, jt, :]
         return out[0][:, jt, :], out[1][:, jt, :]
 
+    @_dense_only
     def predict_hessian(self, q, return_var=True, path=None):
         """Second derivatives of the posterior with respect to the raw (un-normalised) inputs ``q`` (M,) or (M, d), in
         target units per input unit squared: ``hmean`` (M, D2, k) over the pairs ``(i, j)``, ``i <= j``, of the inputs,
@@ -404,6 +426,7 @@ class PathModel:
             return hmean
         return hmean, out[1][:, :, None] * scale ** 2
 
+    @_dense_only
     def acceleration(self, q, return_var=True, path=None):
         """Acceleration of the modelled path at the raw time stamps ``q``: the ``("t", "t")`` entry of
         :meth:`predict_hessian`, (M, k) arrays, e.g. (d2x/dt2, d2y/dt2), and with ``return_var`` their latent variances
@@ -417,6 +440,7 @@ class PathModel:
             return out[:, b, :]
         return out[0][:, b, :], out[1][:, b, :]
 
+    @_dense_only
     def curvature(self, q, path=None):
         """Signed curvature of the posterior MEAN path of a model with exactly two targets (x, y) at the raw time stamps
         ``q``, (M,), in raw units (1 / length): ``(x' y'' - y' x'') / (x'^2 + y'^2)^(3/2)`` from the means of
@@ -432,6 +456,7 @@ class PathModel:
             kappa = (v[:, 0] * a[:, 1] - v[:, 1] * a[:, 0]) / speed2 ** 1.5
         return np.where(speed2 > 0.0, kappa, np.nan)
 
+    @_dense_only
     def add_paths(self, trajs, keys):
         """Append the paths ``keys`` of ``trajs`` to this cluster's model (``GP.update``: the factor of the paths already
         modelled is kept).  Inputs and targets go through the normalisation fixed at the first fit (``in_lo``,
@@ -446,6 +471,7 @@ class PathModel:
                              "their own: call append_paths(trajs, keys), which numbers them")
         return self.append_paths(trajs, keys)
 
+    @_dense_only
     def append_paths(self, trajs, keys, velocities=None):
         """:meth:`add_paths` for every model (``GP.update`` with the rows' path ids or derivative rows where the model has
         them).  On a ``within_path`` model path i of ``keys`` gets the id ``len(self.keys) + i``, which continues the
@@ -493,6 +519,7 @@ class PathModel:
         self.keys.extend(keys)
         return self
 
+    @_dense_only
     def remove_paths(self, keys):
         """Take the paths ``keys`` out of this cluster's model (``GP.remove``: the factor of the other paths is updated, not
         computed again) — a path that went stale, was assigned to another cluster, or was a bad recording.  The result is
@@ -556,6 +583,7 @@ class PathModel:
             at += self._rows[q]
         return out
 
+    @_dense_only
     def loo(self, keys=None):
         """Leave-one-out check of the model against its own paths (``GP.loo``; no refit): {key: (mean (L_key, k), std
         (L_key, k), z (L_key, k))} for ``keys`` (default: every path of the model), in the targets' own units.  Row s of a
@@ -582,6 +610,7 @@ class PathModel:
             out[q] = (mean[r] * self.y_std + self.y_mean, std[r] * self.y_std[None, :], resid[r] / std[r])
         return out
 
+    @_dense_only
     def log_likelihood(self, paths_txy, include_noise=True):
         """How likely whole paths are under this cluster's model: ``paths_txy`` (P, L, 3) raw (t, x, y) paths of one
         length L <= 64 -> (P, k) log-densities of each path's targets, in the targets' own units, under the joint
@@ -605,6 +634,7 @@ class PathModel:
                                     noise_weights=self._tiled_weights(P * L, "log_likelihood"))
         return np.asarray(logp, dtype=np.float64).reshape(P, -1) - L * np.log(self.y_std)[None, :]
 
+    @_dense_only
     def forecast(self, prefix_txy, t_future, include_noise=True, return_logp=False):
         """Where partly observed paths of this cluster go: ``prefix_txy`` (P, Lo, 3) raw (t, x, y), the first Lo points
         of P new paths, ``t_future`` (Lp,) raw time stamps shared by the paths or (P, Lp) (``t`` must be the model's only
@@ -660,7 +690,7 @@ def step_noise_weights(Yn, n_paths):
 def fit_path_models(trajs, clusters, inputs=("t",), targets=("x", "y"), devices=None, optimize=False,
                     lengthscale=0.25, variance=1.0, noise=0.05, step_noise=False, velocities=None, velocity_noise=0.05,
                     learn_velocity_noise=False, within_path=False, path_variance=0.25, path_lengthscale=None,
-                    learn_path_parameters=False, trend=None, **gp_kwargs):
+                    learn_path_parameters=False, trend=None, inducing=None, **gp_kwargs):
     """One exact GP per cluster of ``clusters`` = {cluster id: [path ids]} — what
     :func:`kmeans` (``kmeansclustering``, GPmap.py:36-93) returns — modelling the cluster's paths
     as (x(t), y(t)); the modelling step the reference's title names and its clustering prepares
@@ -692,10 +722,27 @@ def fit_path_models(trajs, clusters, inputs=("t",), targets=("x", "y"), devices=
     with marginalised coefficients (``GP.fit(basis=)``), so the plug-in standardisation no longer has to carry the trend
     and its uncertainty reaches the variances; stored on the model as ``trend``.  Not with ``velocities`` or
     ``within_path``.  None (the default) changes nothing.
+    ``inducing`` = m (an int): every cluster gets an inducing-point fit (``SparseGP``: m points, equally spaced over the
+    cluster's normalised inputs when there is one input, else a seeded subset of its distinct rows) instead of a dense
+    one — for clusters of tens of thousands of paths, whose observations no dense factor holds.  The models are
+    ``sparse`` (:class:`PathModel`): ``predict`` only.  Of ``gp_kwargs`` only ``kernel``, ``jitter`` (None: 1e-8 *
+    ``variance``, on K_uu — a change of model, not of noise) and ``chunk`` apply.  Not with ``velocities``,
+    ``within_path``, ``trend`` or ``optimize`` (``ValueError``).  None (the default) changes nothing.
     Returns {cluster id: :class:`PathModel`}; empty clusters are skipped."""
     import threading
     from concurrent.futures import ThreadPoolExecutor
     from .gp import GP
+    if inducing is not None:
+        if isinstance(inducing, bool) or not isinstance(inducing, (int, np.integer)) or inducing < 1:
+            raise ValueError("inducing must be None or an int >= 1 (the number of inducing points per cluster)")
+        for name, on in (("velocities", bool(velocities)), ("within_path", within_path), ("trend", trend is not None),
+                         ("optimize", optimize)):
+            if on:
+                raise ValueError(f"inducing cannot be combined with {name}: an inducing-point fit takes plain value "
+                                 "observations and fixed hyper-parameters")
+        extra = sorted(set(gp_kwargs) - {"kernel", "jitter", "chunk"})
+        if extra:
+            raise ValueError(f"inducing: a sparse model takes kernel, jitter and chunk, not {extra}")
     if devices is None:
         devs = [None]
     elif isinstance(devices, (int, np.integer)):
@@ -753,6 +800,17 @@ def fit_path_models(trajs, clusters, inputs=("t",), targets=("x", "y"), devices=
         sd = Y.std(axis=0)
         sd = np.where(sd > 0, sd, 1.0)
         Yn = np.ascontiguousarray((Y - mu) / sd)
+        if inducing is not None:
+            from .sparse import SparseGP
+            sw = step_noise_weights(Yn, len(keys)) if step_noise else None
+            gp = SparseGP(lengthscale=lengthscale, variance=variance, noise=noise, device=devs[slot % len(devs)], **gp_kwargs)
+            try:
+                gp.fit(X, Yn, inducing=int(inducing), noise_weights=None if sw is None else np.tile(sw, len(keys)))
+            except Exception:
+                gp.close()
+                raise
+            return cid, PathModel(gp, keys, lo, span, mu, sd, inputs, targets, step_weights=sw,
+                                  row_counts=[len(trajs.pathdict[q]) for q in keys], sparse=True)
         der = cluster_velocities(keys, X, span, sd)
         gp = GP(lengthscale=lengthscale, variance=variance, noise=noise, device=devs[slot % len(devs)],
                 **gp_kwargs)

@@ -577,6 +577,40 @@ int gpx_pathwise_draw(gpx_handle* h, int64_t S, int64_t F, uint64_t seed, const 
 int gpx_pathwise_eval(gpx_handle* h, const void* Xs, int64_t M, int64_t s0, int64_t S, void* out /* (S,M,k) */,
                       int32_t mem_kind);
 int gpx_pathwise_info(gpx_handle* h, int64_t* S, int64_t* F, int64_t* n_normals);
+
+/* ---- inducing-point GP: the collapsed variational bound of Titsias 2009 ("SGPR") ----------------------
+ * For data with more observations than a dense factor can hold: m inducing points Z stand for the N observations, the cost
+ * is O(N m^2) and the memory O(m^2 + chunk m).  With s_n^2 = sn2 w_n (w_n = 1 when w == NULL), S = diag(s^2), yt = S^-1/2 y:
+ *   Kuu = sf2 k(Z,Z) + jitter I,  L = chol(Kuu);   A = L^-1 sf2 k(Z,X) S^-1/2;   B = I + A A^T,  LB = chol(B);   c = LB^-1 A yt
+ *   ELBO_c = -N/2 log 2 pi - sum log LB_ii - 1/2 sum log s_n^2 - 1/2 |yt_c|^2 + 1/2 |c_c|^2 - 1/2 sum sf2 / s_n^2 + 1/2 tr(A A^T)
+ *   predict: T1 = L^-1 sf2 k(Z,Xs), T2 = LB^-1 T1;  mean = T2^T c,  var = sf2 - colsumsq(T1) + colsumsq(T2),
+ *            cov = sf2 k(Xs,Xs) - T1^T T1 + T2^T T2   (the latent f: no noise term)
+ * The cross-kernel rows are whitened by L^-1 BEFORE the contraction over the observations (the cheaper order loses the
+ * result: DESIGN.md).  jitter is added to Kuu only: it is a (tiny) change of the model, not of the noise.
+ * gpx_sparse_fit streams X, y, w in chunks of `chunk` observations (rounded up to a multiple of 128; 0: the library's
+ * choice, a function of m alone); results depend on (m, chunk) but on nothing else of the machine, and two calls with the
+ * same arguments agree bit for bit.  1 <= d <= 32, 1 <= k <= 8, 1 <= m <= 65536, n_ls 1 or d, sf2 > 0, sn2 > 0, jitter >= 0.
+ * w: per-observation noise weights, finite and > 0 (GPX_E_ARG otherwise: a waypoint, w = 0, has no place in S^-1; the
+ * weights of gpx_set_noise_weights are not used here).  X, y, w, Z, Xs and the outputs are fp64 in the memory kind given.
+ * *info = 0, or the 1-based pivot of Kuu that was not > 0, or m + the pivot of B (which cannot happen in exact arithmetic);
+ * the call returns 0 then and the handle is left without a fit.  Single-device GPX_F64 handles only: GPX_F32 / GPX_MIXED
+ * handles, shards, handles with a communicator and device groups return GPX_E_UNSUPPORTED.  A size the card cannot hold
+ * returns GPX_E_NOMEM before anything is allocated.
+ * A handle holds a dense fit or a sparse fit, never both: either fit call replaces the other state, every other dense entry
+ * point refuses a sparse-fitted handle with GPX_E_ARG (gpx_last_error names gpx_sparse_*), and the sparse entry points refuse
+ * a dense-fitted handle the same way; the existing fit stays valid.  Not available on a sparse fit: the gradient of the
+ * bound, update / remove / loo, derivative observations, path ids, basis functions.
+ * Timings: kbuild (Kuu and the chunks' cross-kernel rows), chol (both factorisations), solve (whitening and contraction),
+ * logdet, fit_total; kstar, trsm, mean, var, d2h, predict_total. */
+int gpx_sparse_fit(gpx_handle* h, const void* X, const void* y, const void* w /* (N) or NULL */, int64_t N, int32_t d, int32_t k,
+                   const void* Z, int64_t m, const double* lengthscale, int32_t n_ls, double sf2, double sn2, double jitter,
+                   int64_t chunk /* 0: library's choice */, int32_t mem_kind, int64_t* info);
+int gpx_sparse_predict(gpx_handle* h, const void* Xs, int64_t M, void* mean /* (M,k) */, void* var /* (M) | NULL */,
+                       int32_t mem_kind);
+int gpx_sparse_predict_cov(gpx_handle* h, const void* Xs, int64_t M, void* mean /* (M,k) | NULL */, void* cov /* (M,M) */,
+                           int32_t mem_kind);
+int gpx_sparse_elbo(gpx_handle* h, double* elbo /* (k) */);
+int gpx_sparse_info(gpx_handle* h, int64_t* N, int64_t* m, int64_t* k, int64_t* chunk);
 int gpx_logdet(gpx_handle* h, double* out);
 /* Frees what only the NEXT predict / gradient call would use (the V^T batch, the L^-T buffer of
  * gpx_lml_grad, per-tile partials, compact block buffers, the buffers of the joint-posterior calls); the fit itself (factor, alpha, block
@@ -743,6 +777,13 @@ int gpx_trsm(double* X, int64_t m, const double* L, int64_t nb);
  * (m == n required).  m,n multiples of 128, k multiple of 16. */
 int gpx_gemm_nt(double* C, int64_t m, int64_t n, const double* A, const double* B, int64_t k,
                 int32_t lower);
+/* The TN product of the inducing-point fit: the lower triangle of C (n,n) = X^T X (accumulate == 0) or += X^T X, X (rows,n)
+ * row-major; nothing above the diagonal is written.  n a multiple of 64, rows >= 1. */
+int gpx_syrk_tn(double* C, int64_t n, const double* X, int64_t rows, int32_t accumulate);
+/* That contraction alone on zero-filled resident operands, `iters` repeats after a warm-up; *ms_per_call = the mean time.
+ * route 0: the TN kernel as the fit launches it; 1: a transpose of X, then the NT tile engine (128-tiles, lower); 2: that NT
+ * launch alone.  n a multiple of 128 (<= 16384), rows a multiple of 64.  tools/sparse_bench.py. */
+int gpx_debug_syrk_tn_bench(int64_t n, int64_t rows, int32_t route, int32_t iters, double* ms_per_call);
 /* fp64 MFMA layout probe: D (16,16) = A (16,4) B (4,16) through one
  * v_mfma_f64_16x16x4_f64. */
 int gpx_mfma_probe(const double* A, const double* B, double* D);
