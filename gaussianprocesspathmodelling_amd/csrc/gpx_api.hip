@@ -148,6 +148,7 @@ struct gpx_handle {
   DevBuf X64, Y64, Xs64, A64, Aprev, R64, X32, Y32, RT32, rn, Zfew;
   int refine = 0;    // GPX_MIXED: 0 = adaptive, > 0 = fixed iteration count
   DevBuf resv_ring;  // device counters of the self-reserving trailing updates ([1024][8] unsigned; GPX_CU_SELF_RESERVE)
+  DevBuf strassen2;  // temporaries of strassen_nt's second level (chol_two_level_enqueue: the deep update and the deferred product share it)
   DevBuf Wblk, Ublk; // explicit inverses of the nb x nb diagonal blocks of L ([Npad/nb][nb][nb]) + scratch
   int nbw = 0;       // block width of Wblk (0: not built)
   int nb_shard = 512;  // distribution block = panel width of the sharded factorisation (chosen per fit)
@@ -299,6 +300,21 @@ int ensure(gpx_handle* h, DevBuf& b, size_t bytes) {
   HIPCHK(h, hipMalloc(&b.p, bytes));
   b.cap = bytes;
   return GPX_OK;
+}
+
+// the same for a buffer the caller can do without: false, and no error on the handle, when the memory is not there
+bool try_ensure(gpx_handle* h, DevBuf& b, size_t bytes) {
+  if (b.cap >= bytes && b.p) return true;
+  if (b.p) (void)hipFree(b.p);
+  b.p = nullptr;
+  b.cap = 0;
+  if (hipMalloc(&b.p, bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    b.p = nullptr;
+    return false;
+  }
+  b.cap = bytes;
+  return true;
 }
 
 hipEvent_t next_event(gpx_handle* h) {
@@ -662,6 +678,9 @@ struct DeferLeft {
   int64_t c1 = 0;    // a panel boundary in (0, n)
   int64_t smin = 0;  // strassen_nt from quadrants of this size on; 0: one classical launch
   size_t temp = 0;   // elements of ONE panel buffer: the level's temporaries live in the buffer of that last panel
+  int64_t smin2 = 0;        // strassen_nt's second level from quadrants of this size on; 0: one level
+  void* temp2 = nullptr;    // its temporaries (the handle's strassen2) and their size in elements
+  size_t temp2_elems = 0;
 };
 
 template <typename T>
@@ -774,9 +793,10 @@ int chol_enqueue(gpx_handle* h, T* A, int64_t ld, int64_t n, int nb, T* Winv, T*
       launch_gemm_nt<T>(128, Cd, ld, Ad, ld, Bd, ld, dna, nd, kd, 0, 0, s);
       return;
     }
+    const StrassenL2<T> l2{defer->smin2, (T*)defer->temp2, defer->temp2_elems};
     for (int64_t r = 0; r < dna; r += mch) {
       const int64_t m = std::min(mch, dna - r);
-      strassen_nt<T>(Cd + r * ld, ld, Ad + r * ld, ld, Bd, ld, m, nd, kd, Tbuf, Tbuf + (m / 256 * 128) * ldt, ldt, s);
+      strassen_nt<T>(Cd + r * ld, ld, Ad + r * ld, ld, Bd, ld, m, nd, kd, Tbuf, Tbuf + (m / 256 * 128) * ldt, ldt, s, &l2);
     }
   };
   LatencyGuard latency_guard;
@@ -1066,6 +1086,25 @@ int chol_two_level_enqueue(gpx_handle* h, T* A, int64_t ld, int64_t n, int nb, T
   defer.smin = depth > 0 ? smin : 0;
   defer.temp = (size_t)(P1 - P0);
   const bool defer_on = (env.defer_left < 0 ? depth > 0 : env.defer_left != 0) && defer.c1 > 0;
+  // The second level's temporaries (GPX_STRASSEN_MIN_TWO): ONE buffer of the handle's, sized here, before anything is
+  // enqueued, for the larger of its two users — the deep update's off-diagonal block and the deferred product's largest
+  // chunk run on the main stream one after the other.  Without it (no memory left) the second level does not run.
+  StrassenL2<T> l2;
+  if (depth > 0 && env.strassen_min2 > 0 && sizeof(T) == 8) {  // (fp64 only, whatever GPX_STRASSEN_SINGLE says)
+    auto quadrants2 = [](int64_t m, int64_t nn) { return std::min(m, nn) / 256 * 128 / 256 * 128; };
+    size_t need = 0;
+    if (quadrants2(np - hh, hh) >= env.strassen_min2) need = strassen_temp2_elems<T>(np - hh, hh, c);
+    if (defer_on && quadrants2(np, c - defer.c1) >= env.strassen_min2)
+      need = std::max(need, strassen_temp2_elems<T>(round_up(np, 256), c - defer.c1, defer.c1));
+    if (need > 0 && try_ensure(h, h->strassen2, need * sizeof(T))) {
+      l2.min2 = env.strassen_min2;
+      l2.buf = (T*)h->strassen2.p;
+      l2.elems = h->strassen2.cap / sizeof(T);
+    }
+  }
+  defer.smin2 = l2.min2;
+  defer.temp2 = l2.buf;
+  defer.temp2_elems = l2.elems;
   if ((rc = chol_enqueue<T>(h, A, ld, c, nb, Winv, P0, P1, ldp, info, gidx0, profile, np + nx, iw, np + nx, rs,
                             defer_on ? &defer : nullptr)))
     return rc;
@@ -1092,9 +1131,10 @@ int chol_two_level_enqueue(gpx_handle* h, T* A, int64_t ld, int64_t n, int nb, T
       }
       deep(o, s1z, lv - 1);
       TB = TA + (s2z / 256 * 128) * ldt;
+      bool two = false;
       h->tm.syrk_flops += strassen_nt<T>(A22 + (o + s1z) * ld + o, ld, L21 + (o + s1z) * ld, ld, L21 + o * ld, ld, s2z, s1z,
-                                         c, TA, TB, ldt, s0);
-      h->tm.syrk_launches += 7;
+                                         c, TA, TB, ldt, s0, &l2, &two);
+      h->tm.syrk_launches += two ? 49 : 7;
       deep(o + s1z, s2z, lv - 1);
     };
     deep(0, np, depth);
@@ -4823,7 +4863,16 @@ int gpx_gemm_nt(double* C, int64_t m, int64_t n, const double* A, const double* 
     Dev<double> dT;
     const int64_t ldt = k / 2 + LD_SKEW;
     if (int rc = dT.alloc(strassen_temp_elems(m, n, k, LD_SKEW))) return rc;
-    strassen_nt<double>(dC, ldc, dA, lda, dB, lda, m, n, k, dT, dT + (m / 256 * 128) * ldt, ldt, sc.st);
+    // GPX_STRASSEN_MIN_TWO > 0: its seven products take a second level by the same rule
+    Dev<double> dT2;
+    StrassenL2<double> l2;
+    l2.min2 = sc.h.env.strassen_min2;
+    l2.elems = strassen_temp2_elems<double>(m, n, k);
+    if (l2.min2 > 0 && l2.elems > 0) {
+      if (int rc = dT2.alloc(l2.elems)) return rc;
+      l2.buf = dT2;
+    }
+    strassen_nt<double>(dC, ldc, dA, lda, dB, lda, m, n, k, dT, dT + (m / 256 * 128) * ldt, ldt, sc.st, &l2);
     UCHK(hipStreamSynchronize(sc.st));  // (dT goes out of scope)
   } else {
     launch_gemm_nt_fixed<double>(tile, dC, ldc, dA, lda, dB, lda, m, n, k, lower, 0, sc.st);
@@ -4874,13 +4923,21 @@ int gemm_bench_t(int64_t n, int64_t k, int32_t lower, int32_t mode, int32_t iter
   hipEvent_t e0 = next_event(&sc.h), e1 = next_event(&sc.h);  // (the Scratch handle's pool destroys them)
   if (!e0 || !e1) return fail(nullptr, GPX_E_HIP, "hipEventCreate failed");
   Dev<T> dT;  // mode 2: C -= A A'^T through strassen_nt (one launch = the whole level: ten sums, seven products)
+  Dev<T> dT2;  // mode 3: the same with the second level in each of the seven, whatever the size of their quadrants
+  StrassenL2<T> l2;
   const int64_t ldt = k / 2 + ld_skew<T>();
-  if (mode == 2) {
+  if (mode >= 2) {
     if (int rc = dT.alloc(strassen_temp_elems(n, n, k, ld_skew<T>()))) return rc;
   }
+  if (mode == 3) {
+    l2.min2 = 128;
+    l2.elems = strassen_temp2_elems<T>(n, n, k);
+    if (int rc = dT2.alloc(l2.elems)) return rc;
+    l2.buf = dT2;
+  }
   auto once = [&] {
-    if (mode == 2)
-      strassen_nt<T>(dC, ldc, dA, lda, dA + n * lda, lda, n, n, k, dT, dT + (n / 256 * 128) * ldt, ldt, sc.st);
+    if (mode >= 2)
+      strassen_nt<T>(dC, ldc, dA, lda, dA + n * lda, lda, n, n, k, dT, dT + (n / 256 * 128) * ldt, ldt, sc.st, &l2);
     else
       launch_gemm_nt_fixed<T>(128, dC, ldc, dA, lda, dA + n * lda, lda, n, n, k, lower, mode, sc.st);
   };
@@ -4898,7 +4955,8 @@ int gemm_bench_t(int64_t n, int64_t k, int32_t lower, int32_t mode, int32_t iter
 int gpx_debug_gemm_bench(int32_t dtype, int64_t n, int64_t k, int32_t lower, int32_t mode, int32_t iters,
                          double* ms_per_launch) try {
   if (!ms_per_launch || n <= 0 || n % 128 || k <= 0 || k % 32 || iters <= 0 || (lower != 0 && lower != 1) ||
-      (mode != 0 && mode != 1 && mode != 2) || (mode == 2 && (lower != 0 || n % 256 || k % 64)) || n > 131072 || k > 32768)
+      mode < 0 || mode > 3 || (mode == 2 && (lower != 0 || n % 256 || k % 64)) || (mode == 3 && (lower != 0 || n % 512 || k % 128)) ||
+      n > 131072 || k > 32768)
     return GPX_E_ARG;
   if (dtype == GPX_F64) return gemm_bench_t<double>(n, k, lower, mode, iters, ms_per_launch);
   if (dtype == GPX_F32) return gemm_bench_t<float>(n, k, lower, mode, iters, ms_per_launch);

@@ -209,6 +209,22 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_two_kernel(T* __restrict__ C1,
   store_tile_two<T, BT, BT>(C1 + o, C2 ? C2 + o : nullptr, ldc, s1, s2, acc);
 }
 
+// The products of strassen_nt's second level, and what it peels: the same grid and k-loop, the epilogue with up to four
+// targets (store_tile_four).  No product is materialised in a temporary.
+template <typename T, int BT>
+__global__ __launch_bounds__(256, 2) void gemm_nt_four_kernel(TileTargets<T> tg, int64_t ldc, const T* __restrict__ A,
+                                                              int64_t lda, const T* __restrict__ B, int64_t ldb,
+                                                              int tiles_m, int tiles_n, int sh, int K) {
+  __shared__ __attribute__((aligned(16))) T smem[TileShapeG<T, BT, BT, 1>::SMEM_ELEMS];
+  const int64_t lin = xcd_chunk_id(blockIdx.x, gridDim.x);
+  int ti, tj;
+  if (!tile_coords<false>(lin, tiles_m, tiles_n, sh, 0, BcMask{0, 1, 0}, ti, tj)) return;
+  typename Num<T>::v4 acc[BT / 32][BT / 32];
+  zero_acc(acc);
+  gemm_tile_g<T, BT, BT, 2, 1>(A + (int64_t)ti * BT * lda, lda, B + (int64_t)tj * BT * ldb, ldb, K, acc, smem);
+  store_tile_four<T, BT, BT>(tg, (int64_t)ti * BT * ldc + (int64_t)tj * BT, ldc, acc);
+}
+
 // out (rows x cols, ldo) = X + sign * Y: the operand sums of a Strassen level.  One 16-byte element per lane,
 // non-temporal, the grid sized to the data (the form of a copy that reaches the stream rate on this chip; a
 // grid-stride loop does not).  cols is a multiple of 16 / sizeof(T); rows of all three start on 16-byte boundaries.
@@ -1362,7 +1378,7 @@ void launch_gemm_nt(int tile, T* C, int64_t ldc, const T* A, int64_t lda, const 
   launch_gemm_nt_fixed<T>(gemm_nt_tile(tile, m, n, lower), C, ldc, A, lda, B, ldb, m, n, k, lower, mode, st);
 }
 
-// ---- C -= A B^T with one Strassen level (Strassen 1969: seven half-size products instead of eight) ------------------
+// ---- C -= A B^T with one or two Strassen levels (Strassen 1969: seven half-size products instead of eight) ----------
 // The part with m, n multiples of 256 and k a multiple of two k-steps goes through the level; what is ragged — the last
 // < 256 rows or columns, the k remainder — is peeled off and done by the classical launches.  With the quadrants
 //   A = [A1 A2; A3 A4]  (rows x k),   B = [B1 B2; B3 B4]  (rows x k),   C = [C11 C12; C21 C22]:
@@ -1375,14 +1391,31 @@ void launch_gemm_nt(int tile, T* C, int64_t ldc, const T* A, int64_t lda, const 
 // per launch, and the addends arrive in the fixed order M1 .. M7, then the peeled parts: the result is deterministic and
 // repeatable bit for bit, whatever runs beside it.
 // Returns the flops executed (2 m n k where classical, 7/8 of that for the part that went through the level).
+// THE SECOND LEVEL (l2: a threshold and temporaries of its own).  Each of the seven products X Y^T (mh x nh x kh) with its
+// targets C1 += s1 X Y^T, C2 += s2 X Y^T is itself split as above when its quadrants are at least l2->min2 rows and
+// columns and l2->buf holds strassen_temp2_elems: the same ten sums (into TA2 | TB2 in l2->buf, ldt2 = kh / 2 + skew)
+// and seven products of a quarter of m, n and k, each landing in one or two quadrants of C1 and of C2 with the product of
+// the two levels' signs (gemm_nt_four_kernel: up to four targets, nothing materialised).  What is ragged at that level —
+// rows or columns of the half beyond a multiple of 256, the half's k beyond a multiple of two k-steps — is peeled off as
+// at the first, into both targets with their signs (the same kernel with two targets; mh and nh are multiples of 128).
+// The ORDER above holds across both levels: TA2 | TB2 are rewritten only behind the product that read them, TA | TB only
+// behind the last product of the first-level product that read them.  The part that took both levels executes 49/64 of
+// its classical flops.  l2 null, min2 = 0 or no buffer: the launches, their order and the bits of one level.
 size_t strassen_temp_elems(int64_t m, int64_t n, int64_t k, int skew) {
   const int64_t m0 = m / 256 * 256, n0 = n / 256 * 256;
   return (size_t)((m0 + n0) / 2) * (size_t)(k / 2 + skew);
 }
 
+// the second level's temporaries for a product of m x n x k: the first level's for one of its half-size products
+template <typename T>
+size_t strassen_temp2_elems(int64_t m, int64_t n, int64_t k) {
+  return strassen_temp_elems(m / 256 * 128, n / 256 * 128, k / (2 * Num<T>::BK) * Num<T>::BK, ld_skew<T>());
+}
+
 template <typename T>
 double strassen_nt(T* C, int64_t ldc, const T* A, int64_t lda, const T* B, int64_t ldb, int64_t m, int64_t n,
-                   int64_t k, T* TA, T* TB, int64_t ldt, hipStream_t st) {
+                   int64_t k, T* TA, T* TB, int64_t ldt, hipStream_t st, const StrassenL2<T>* l2, bool* two_levels) {
+  if (two_levels) *two_levels = false;
   constexpr int64_t K2 = 2 * Num<T>::BK, VE = 16 / sizeof(T);
   const int64_t m0 = m / 256 * 256, n0 = n / 256 * 256, k0 = k / K2 * K2;
   auto classical = [&](T* Cc, const T* Ac, const T* Bc, int64_t mm, int64_t nn, int64_t kk) {
@@ -1408,8 +1441,67 @@ double strassen_nt(T* C, int64_t ldc, const T* A, int64_t lda, const T* B, int64
   };
   int sh;
   const dim3 grid((unsigned)rect_grid(mh / 128, nh / 128, sh));
+  // the second level: quadrants of the halves
+  const int64_t m2 = mh / 256 * 256, n2 = nh / 256 * 256, k2 = kh / K2 * K2, mq = m2 / 2, nq = n2 / 2, kq = k2 / 2;
+  const int64_t ldt2 = kh / 2 + ld_skew<T>();
+  T *TA2 = l2 ? l2->buf : nullptr, *TB2 = TA2 ? TA2 + mq * ldt2 : nullptr;
+  const bool second = l2 && l2->min2 > 0 && TA2 && mq > 0 && nq > 0 && kq > 0 && std::min(mq, nq) >= l2->min2 &&
+                      strassen_temp2_elems<T>(m, n, k) <= l2->elems && aligned(TA2, ldt2) && aligned(TB2, ldt2);
+  if (two_levels) *two_levels = second;
+  // C1 + o1 += s1 t X Y^T, C2 + o2 += s2 t X Y^T for each (offset o, sign t) given — o2 < 0: one offset only — and each
+  // of C1, C2 that is not null: a product of mm x nn x kk with up to four targets
+  auto product4 = [&](const T* X, int64_t ldx, const T* Y, int64_t ldy, int64_t mm, int64_t nn, int64_t kk, T* C1, T s1,
+                      T* C2, T s2, int64_t o1, T t1, int64_t o2, T t2) {
+    if (mm <= 0 || nn <= 0 || kk <= 0) return;
+    TileTargets<T> tg = {{nullptr, nullptr, nullptr, nullptr}, {(T)0, (T)0, (T)0, (T)0}};
+    int c = 0;
+    for (int b = 0; b < 2; ++b) {
+      T* base = b ? C2 : C1;
+      const T sb = b ? s2 : s1;
+      if (!base) continue;
+      tg.C[c] = base + o1, tg.s[c++] = sb * t1;
+      if (o2 >= 0) tg.C[c] = base + o2, tg.s[c++] = sb * t2;
+    }
+    int sh4;
+    const dim3 grid4((unsigned)rect_grid(mm / 128, nn / 128, sh4));
+    debug_delay(st);
+    hipLaunchKernelGGL((gemm_nt_four_kernel<T, 128>), grid4, dim3(256), 0, st, tg, ldc, X, ldx, Y, ldy, (int)(mm / 128),
+                       (int)(nn / 128), sh4, (int)kk);
+  };
+  const int vpr2 = (int)(kq / VE);
+  auto sum2 = [&](T* out, const T* X, const T* Y, int64_t ldxy, int64_t rows, T sign) {
+    debug_delay(st);
+    hipLaunchKernelGGL(operand_sum_kernel<T>, dim3((unsigned)((rows * vpr2 + 255) / 256)), dim3(256), 0, st, out, ldt2, X,
+                       ldxy, Y, ldxy, rows, vpr2, sign);
+  };
+  // one first-level product through the second level: P = X Y^T (mh x nh x kh), C1 += s1 P, C2 += s2 P.  The list is
+  // the first level's with X, Y for A, B; a target that takes -M there takes +M of P here, hence the signs u = -q, v = -p.
+  auto product_l2 = [&](const T* X, int64_t ldx, const T* Y, int64_t ldy, T* C1, T s1, T* C2, T s2) {
+    const T *X1 = X, *X2 = X + kq, *X3 = X + mq * ldx, *X4 = X3 + kq;
+    const T *Y1 = Y, *Y2 = Y + kq, *Y3 = Y + nq * ldy, *Y4 = Y3 + kq;
+    const int64_t o11 = 0, o12 = nq, o21 = mq * ldc, o22 = o21 + nq, none = -1;
+    const T u = (T)1, v = (T)-1;
+    auto prod = [&](const T* Xs, int64_t ldxs, const T* Ys, int64_t ldys, int64_t o1, T t1, int64_t o2, T t2) {
+      product4(Xs, ldxs, Ys, ldys, mq, nq, kq, C1, s1, C2, s2, o1, t1, o2, t2);
+    };
+    sum2(TA2, X1, X4, ldx, mq, u), sum2(TB2, Y1, Y4, ldy, nq, u), prod(TA2, ldt2, TB2, ldt2, o11, u, o22, u);    // M1
+    sum2(TA2, X3, X4, ldx, mq, u), prod(TA2, ldt2, Y1, ldy, o21, u, o22, v);                                     // M2
+    sum2(TB2, Y3, Y4, ldy, nq, v), prod(X1, ldx, TB2, ldt2, o12, u, o22, u);                                     // M3
+    sum2(TB2, Y2, Y1, ldy, nq, v), prod(X4, ldx, TB2, ldt2, o11, u, o21, u);                                     // M4
+    sum2(TA2, X1, X2, ldx, mq, u), prod(TA2, ldt2, Y4, ldy, o11, v, o12, u);                                     // M5
+    sum2(TA2, X3, X1, ldx, mq, v), sum2(TB2, Y1, Y3, ldy, nq, u), prod(TA2, ldt2, TB2, ldt2, o22, u, none, u);   // M6
+    sum2(TA2, X2, X4, ldx, mq, v), sum2(TB2, Y2, Y4, ldy, nq, u), prod(TA2, ldt2, TB2, ldt2, o11, u, none, u);   // M7
+    // peeled at this level: the half's k remainder, the columns right of the level's block, the rows below it
+    product4(X + k2, ldx, Y + k2, ldy, m2, n2, kh - k2, C1, s1, C2, s2, 0, u, none, u);
+    product4(X, ldx, Y + n2 * ldy, ldy, m2, nh - n2, kh, C1, s1, C2, s2, n2, u, none, u);
+    product4(X + m2 * ldx, ldx, Y, ldy, mh - m2, nh, kh, C1, s1, C2, s2, m2 * ldc, u, none, u);
+  };
   // C1 += s1 X Y^T, C2 += s2 X Y^T (C2 may be null)
   auto product = [&](const T* X, int64_t ldx, const T* Y, int64_t ldy, T* C1, T s1, T* C2, T s2) {
+    if (second) {
+      product_l2(X, ldx, Y, ldy, C1, s1, C2, s2);
+      return;
+    }
     debug_delay(st);
     hipLaunchKernelGGL((gemm_nt_two_kernel<T, 128>), grid, dim3(256), 0, st, C1, C2, ldc, s1, s2, X, ldx, Y, ldy,
                        (int)(mh / 128), (int)(nh / 128), sh, (int)kh);
@@ -1427,7 +1519,9 @@ double strassen_nt(T* C, int64_t ldc, const T* A, int64_t lda, const T* B, int64
   classical(C + n0, A, B + n0 * ldb, m0, n - n0, k);
   classical(C + m0 * ldc, A + m0 * lda, B, m - m0, n, k);
   const double full = 2.0 * (double)m * (double)n * (double)k, lvl = 2.0 * (double)m0 * (double)n0 * (double)k0;
-  return full - lvl / 8.0;
+  // (each of the seven halves' products saves an eighth of its own level's block)
+  const double lvl2 = second ? 7.0 * 2.0 * (double)m2 * (double)n2 * (double)k2 : 0.0;
+  return full - lvl / 8.0 - lvl2 / 8.0;
 }
 
 // The fused trailing update (gemm_nt_fused_kernel): C (n x n) -= P P^T, lower part, strip of `ns`
@@ -1553,7 +1647,8 @@ extern "C" int gpx_debug_read_syrk_clock(long long* out) {
   template void launch_gemm_nn<T>(T*, int64_t, const T*, int64_t, const T*, int64_t, int64_t, int64_t,  \
                                   int64_t, hipStream_t);                                                \
   template double strassen_nt<T>(T*, int64_t, const T*, int64_t, const T*, int64_t, int64_t, int64_t,   \
-                                 int64_t, T*, T*, int64_t, hipStream_t);                                \
+                                 int64_t, T*, T*, int64_t, hipStream_t, const StrassenL2<T>*, bool*);   \
+  template size_t strassen_temp2_elems<T>(int64_t, int64_t, int64_t);                                   \
   template void launch_gemm_nt_splitk<T>(T*, int64_t, const T*, int64_t, const T*, int64_t, int64_t,    \
                                          int64_t, int64_t, int, T*, int64_t, hipStream_t);
 GPX_INSTANTIATE_BLAS(double)

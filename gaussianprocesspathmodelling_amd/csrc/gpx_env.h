@@ -52,6 +52,7 @@ inline int64_t in_range(int64_t v, int64_t lo, int64_t hi, int64_t otherwise) { 
   /* the two-level Cholesky (chol_two_level_enqueue) and its Strassen level (strassen_nt) */                           \
   X("GPX_TWO_LEVEL_FROM", two_level_from, I64, call, 65536, env_rule::in_range(atoll(e), 0, 1L << 40, 0))                  \
   X("GPX_STRASSEN_MIN", strassen_min, I64, call, 4096, env_rule::in_range(atoll(e), 0, 1L << 40, 0) / 128 * 128)          \
+  X("GPX_STRASSEN_MIN_TWO", strassen_min2, I64, call, 4096, env_rule::in_range(atoll(e), 0, 1L << 40, 0) / 128 * 128)        \
   X("GPX_STRASSEN_DIAG", strassen_diag, Flag, call, false, env_rule::flag(e))                                          \
   X("GPX_STRASSEN_SINGLE", strassen_f32, Flag, call, false, env_rule::flag(e))                                            \
   X("GPX_DEFER_LEFT", defer_left, Opt, call, -1, env_rule::flag(e))                                                    \

@@ -208,10 +208,22 @@ void launch_gemm_nt_fixed(int tile, T* C, int64_t ldc, const T* A, int64_t lda, 
 // launches, and why the result is repeatable bit for bit); m, n multiples of 64, k a multiple of the k-step.  TA | TB:
 // strassen_temp_elems(m, n, k, skew) elements, TB = TA + (m / 256 * 128) * ldt, ldt = k / 2 + skew.  Null temporaries,
 // or a shape with nothing for the level: the classical launch.  Returns the flops executed.
+// l2 (optional): the seven products take a second level where their own quadrants are at least l2->min2 rows and columns
+// (GPX_STRASSEN_MIN_TWO) and l2->buf holds strassen_temp2_elems<T>(m, n, k) of l2->elems elements; otherwise — null, min2 = 0,
+// no or too small a buffer — exactly the one-level launches.  *two_levels (optional) says whether it ran.
 size_t strassen_temp_elems(int64_t m, int64_t n, int64_t k, int skew);
 template <typename T>
+size_t strassen_temp2_elems(int64_t m, int64_t n, int64_t k);
+template <typename T>
+struct StrassenL2 {
+  int64_t min2 = 0;
+  T* buf = nullptr;
+  size_t elems = 0;
+};
+template <typename T>
 double strassen_nt(T* C, int64_t ldc, const T* A, int64_t lda, const T* B, int64_t ldb, int64_t m, int64_t n,
-                   int64_t k, T* TA, T* TB, int64_t ldt, hipStream_t st);
+                   int64_t k, T* TA, T* TB, int64_t ldt, hipStream_t st, const StrassenL2<T>* l2 = nullptr,
+                   bool* two_levels = nullptr);
 // The whole trailing update of a panel in one launch: C (n x n, 128-tiles, lower) -= P P^T (P: n x k, ldp)
 // with the first ns columns (the strip that becomes the next panel) enumerated first; every strip slot
 // adds 1 to *ctr once its tile is released at device scope.  Returns the number of strip slots.

@@ -334,6 +334,40 @@ __device__ __forceinline__ void store_tile_two(T* C1, T* C2, int64_t ldc, T s1, 
   }
 }
 
+// Up to four targets (the products of strassen_nt's second level: one or two quadrants of each of the first-level
+// product's one or two targets): C[t] += s[t] * acc for every t in front of the first null C[t], s[t] each +1 or -1.
+// C[0] is never null.  The targets are distinct quadrants of one matrix (one ldc), so as in store_tile_two every element
+// receives exactly ONE addend per launch, by a no-return atomic.
+template <typename T>
+struct TileTargets {
+  T* C[4];
+  T s[4];
+};
+
+template <typename T, int BM, int BN, int WVM = 2>
+__device__ __forceinline__ void store_tile_four(const TileTargets<T>& tg, int64_t tile_off, int64_t ldc,
+                                                const typename Num<T>::v4 (&acc)[BM / (16 * WVM)][BN / 32]) {
+  constexpr int NT = BN / 32;
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const int wr = wave >> 1, wc = wave & 1;
+  const int l4 = lane >> 4;
+  const int64_t w0 = tile_off + (int64_t)(wr * (BM / WVM)) * ldc + wc * (BN / 2) + (lane & 15);
+#pragma unroll
+  for (int m = 0; m < BM / (16 * WVM); ++m) {
+#pragma unroll
+    for (int n = 0; n < NT; ++n)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int64_t o = w0 + (int64_t)(m * 16 + Num<T>::drow(l4, r)) * ldc + n * 16;
+        unsafeAtomicAdd(tg.C[0] + o, tg.s[0] * acc[m][n][r]);
+        if (tg.C[1]) unsafeAtomicAdd(tg.C[1] + o, tg.s[1] * acc[m][n][r]);
+        if (tg.C[2]) unsafeAtomicAdd(tg.C[2] + o, tg.s[2] * acc[m][n][r]);
+        if (tg.C[3]) unsafeAtomicAdd(tg.C[3] + o, tg.s[3] * acc[m][n][r]);
+      }
+  }
+}
+
 // blocks are dealt round-robin over the 8 XCDs; give each XCD one contiguous chunk of
 // the logical tile order so that neighbouring tiles share an L2 (speed only).
 __host__ __device__ __forceinline__ int64_t xcd_chunk_id(int64_t bid, int64_t nblk) {

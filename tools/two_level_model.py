@@ -10,6 +10,8 @@ lengthscale 0.25, sf2 1.5, sn2 1e-2) at N = 4096 and 8192, factorised
   deferred     strassen, and in the left block column the panels left of c1 (the panel boundary nearest c / 2) leave
                A21[:, c1:c] alone: ONE product A21[:, c1:c] -= L21[:, :c1] L11[c1:c, :c1]^T behind them (GPX_DEFER_LEFT),
   deferred_strassen   the same with that product through a Strassen level (in two row halves, as at N = 65536),
+  strassen_l2, deferred_strassen_l2   strassen / deferred_strassen with a second level in each of the seven products of
+               every Strassen level (GPX_STRASSEN_MIN_TWO),
 
 each followed by z = L^-1 y, alpha = L^-T z, mean = K* alpha, var = k** - |L^-1 K*^T|^2 and log det.  Errors are those of
 tests/test_full_size_gpu.py against OracleGP (LAPACK): mean and variance elementwise relative (floors 1e-6, 1e-6 sf2),
@@ -31,22 +33,35 @@ from oracle.gp_oracle import OracleGP, kernel_matrix, synthetic_problem  # noqa:
 KERNEL, LS, SF2, SN2 = "rbf", 0.25, 1.5, 1e-2
 
 
-def strassen_nt(C, A, B):
-    """C -= A B^T with one Strassen level (even dimensions); the products and targets of csrc/gpx_blas.hip"""
+def strassen_nt(C, A, B, levels=1, targets=None):
+    """C -= A B^T with `levels` Strassen levels (dimensions multiples of 2^levels); the products and targets of
+    csrc/gpx_blas.hip.  targets: [(C, s), ...] instead of C — every one takes s * A B^T (the second level: the sums of a
+    product of the first land in its targets' quadrants, in the order M1 .. M7, nothing in between is rounded twice)"""
+    if targets is None:
+        targets = [(C, -1.0)]
     m, n, k = A.shape[0] // 2, B.shape[0] // 2, A.shape[1] // 2
     A1, A2, A3, A4 = A[:m, :k], A[:m, k:], A[m:, :k], A[m:, k:]
     B1, B2, B3, B4 = B[:n, :k], B[:n, k:], B[n:, :k], B[n:, k:]
-    C11, C12, C21, C22 = C[:m, :n], C[:m, n:], C[m:, :n], C[m:, n:]
-    M = (A1 + A4) @ (B1 + B4).T; C11 -= M; C22 -= M
-    M = (A3 + A4) @ B1.T;        C21 -= M; C22 += M
-    M = A1 @ (B3 - B4).T;        C12 -= M; C22 -= M
-    M = A4 @ (B2 - B1).T;        C11 -= M; C21 -= M
-    M = (A1 + A2) @ B4.T;        C11 += M; C12 -= M
-    M = (A3 - A1) @ (B1 + B3).T; C22 -= M
-    M = (A2 - A4) @ (B2 + B4).T; C11 -= M
+    q11, q12, q21, q22 = (np.s_[:m, :n], np.s_[:m, n:], np.s_[m:, :n], np.s_[m:, n:])
+
+    def product(X, Y, *where):  # where: (quadrant, sign of the product in A B^T)
+        tg = [(T[q], s * t) for T, s in targets for q, t in where]
+        if levels > 1:
+            strassen_nt(None, X, Y, levels - 1, tg)
+        else:
+            M = X @ Y.T
+            for Tq, st in tg:
+                Tq += st * M
+    product(A1 + A4, B1 + B4, (q11, 1.0), (q22, 1.0))
+    product(A3 + A4, B1, (q21, 1.0), (q22, -1.0))
+    product(A1, B3 - B4, (q12, 1.0), (q22, 1.0))
+    product(A4, B2 - B1, (q11, 1.0), (q21, 1.0))
+    product(A1 + A2, B4, (q11, -1.0), (q12, 1.0))
+    product(A3 - A1, B1 + B3, (q22, 1.0))
+    product(A2 - A4, B2 + B4, (q11, 1.0))
 
 
-def chol_blocked(A, nb, rows_below=0, defer=None):
+def chol_blocked(A, nb, rows_below=0, defer=None, slevels=1):
     """right-looking, in place: the leading n x n block of A (n = A.shape[0] - rows_below) is factorised, the rows below it
     ride along as bordered rows (solved and updated, never factorised).  defer = "classical" / "strassen": the deferred
     product of the bordered rows' columns [c1, n)"""
@@ -64,31 +79,32 @@ def chol_blocked(A, nb, rows_below=0, defer=None):
                     A[n:, c1:n] -= A[n:, :c1] @ A[c1:n, :c1].T
                 elif e == c1:
                     h = rows_below // 2
-                    strassen_nt(A[n:n + h, c1:n], A[n:n + h, :c1], A[c1:n, :c1])
-                    strassen_nt(A[n + h:, c1:n], A[n + h:, :c1], A[c1:n, :c1])
+                    strassen_nt(A[n:n + h, c1:n], A[n:n + h, :c1], A[c1:n, :c1], slevels)
+                    strassen_nt(A[n + h:, c1:n], A[n + h:, :c1], A[c1:n, :c1], slevels)
             elif e < n:
                 A[e:, e:n] -= A[e:, o:e] @ A[e:n, o:e].T
     return A
 
 
-def deep_update(A22, L21, levels):
-    """A22 -= L21 L21^T (lower triangle); `levels` Strassen levels on the off-diagonal blocks"""
+def deep_update(A22, L21, levels, slevels=1):
+    """A22 -= L21 L21^T (lower triangle); `levels` levels of splitting, the off-diagonal blocks through strassen_nt with
+    `slevels` Strassen levels"""
     n = A22.shape[0]
     if levels <= 0 or n < 4:
         A22 -= L21 @ L21.T
         return
     h = n // 2
-    deep_update(A22[:h, :h], L21[:h], levels - 1)
-    strassen_nt(A22[h:, :h], L21[h:], L21[:h])
-    deep_update(A22[h:, h:], L21[h:], levels - 1)
+    deep_update(A22[:h, :h], L21[:h], levels - 1, slevels)
+    strassen_nt(A22[h:, :h], L21[h:], L21[:h], slevels)
+    deep_update(A22[h:, h:], L21[h:], levels - 1, slevels)
 
 
-def chol_two_level(K, nb, levels, defer=None):
+def chol_two_level(K, nb, levels, defer=None, slevels=1):
     n = K.shape[0]
     c = max(1, (n // 2 + nb // 2) // nb) * nb
     A = K.copy()
-    chol_blocked(A[:, :c], nb, rows_below=n - c, defer=defer)       # L11, L21 (A21 rides as bordered rows)
-    deep_update(A[c:, c:], A[c:, :c], levels)
+    chol_blocked(A[:, :c], nb, rows_below=n - c, defer=defer, slevels=slevels)  # L11, L21 (A21 rides as bordered rows)
+    deep_update(A[c:, c:], A[c:, :c], levels, slevels)
     chol_blocked(A[c:, c:], nb)
     return A
 
@@ -120,10 +136,13 @@ def run(N, M, nb):
     for name, L in (("blocked", chol_blocked(K.copy(), nb)), ("two_level", chol_two_level(K, nb, 0)),
                     ("strassen", chol_two_level(K, nb, 1)), ("strassen2", chol_two_level(K, nb, 2)),
                     ("deferred", chol_two_level(K, nb, 1, "classical")),
-                    ("deferred_strassen", chol_two_level(K, nb, 1, "strassen"))):
+                    ("deferred_strassen", chol_two_level(K, nb, 1, "strassen")),
+                    ("strassen_l2", chol_two_level(K, nb, 1, slevels=2)),
+                    ("deferred_strassen_l2", chol_two_level(K, nb, 1, "strassen", slevels=2))):
         row[name] = errors(outputs(np.tril(L), y, Ks, kss), ref)
     worst = max(row[s][q] / max(row["blocked"][q], 1e-17)
-                for s in ("strassen", "strassen2", "deferred", "deferred_strassen") for q in row["blocked"])
+                for s in ("strassen", "strassen2", "deferred", "deferred_strassen", "strassen_l2", "deferred_strassen_l2")
+                for q in row["blocked"])
     row["worst_ratio_to_blocked"] = worst
     return row
 
