@@ -481,12 +481,6 @@ bool retry_with_events(gpx_handle* h, bool retried) {
   return true;
 }
 
-struct LatencyGuard {  // set_latency_mode(0) on every exit path of a scheduler function
-  ~LatencyGuard() { set_latency_mode(0); }
-};
-struct ReserveGuard {  // reserve mode off on every exit path of chol_enqueue
-  ~ReserveGuard() { reserve_ring(nullptr, 0); }
-};
 constexpr int RESV_RING = 1024;  // self-reserving launches per factorisation (more: plain kernels)
 
 // ---- blocked right-looking Cholesky, in place on the lower triangle -------------------
@@ -520,9 +514,10 @@ struct InvWork {
 // diagonal block [o, o+nbp) on stream s.  iw != null: after the POTF2 of every 64-column step the
 // auxiliary stream extends the block's inverse by one column block of U / row block of W
 // (launch_inv_extend) — one event per step, nothing on the critical chain.
+// lm: how every launch of the block goes out (the POTF2 and the slab solves read its chain side, the rest `latency`).
 template <typename T>
 int diag_enqueue(gpx_handle* h, T* A, int64_t ld, int64_t o, int nbp, T* Winv, int* info, int64_t gidx0,
-                 hipStream_t s, InvWork<T>* iw = nullptr) {
+                 hipStream_t s, InvWork<T>* iw = nullptr, LaunchMode lm = {}) {
   T* Wp = nullptr;
   // Hand-over to the side stream WITHOUT events on the chain (round 3): POTF2 of step i publishes i + 1 in
   // info[9] after a device-scope release; the side stream is parked on wait_counter_kernel in front of each
@@ -571,14 +566,14 @@ int diag_enqueue(gpx_handle* h, T* A, int64_t ld, int64_t o, int nbp, T* Winv, i
     T* Wq = Winv + (oq / KB) * (KB * KB);
     seq += 2;  // POTF2 writes seq - 1 when it starts ("everything before it on the chain is complete") and seq when it is done
     if (w == 2)
-      launch_potf2_128<T>(Aqq, ld, Wq, gidx0 + oq, info, s, iw && use_flag ? dflag : nullptr, seq);
+      launch_potf2_128<T>(Aqq, ld, Wq, gidx0 + oq, info, s, iw && use_flag ? dflag : nullptr, seq, lm);
     else
       launch_potf2_64<T>(Aqq, ld, Wq, gidx0 + oq, info, s, iw && use_flag ? dflag : nullptr, seq);
     const int64_t rem = o + nbp - (oq + w * KB);
     if (rem > 0) {
       T* panel = A + (oq + w * KB) * ld + oq;
-      launch_trsm_rlt<T>(panel, ld, rem, Aqq, ld, Wq, w * KB, nullptr, 0, s);
-      launch_gemm_nt<T>(64, A + (oq + w * KB) * ld + (oq + w * KB), ld, panel, ld, panel, ld, rem, rem, w * KB, 1, 0, s);
+      launch_trsm_rlt<T>(panel, ld, rem, Aqq, ld, Wq, w * KB, nullptr, 0, s, lm);
+      launch_gemm_nt<T>(64, A + (oq + w * KB) * ld + (oq + w * KB), ld, panel, ld, panel, ld, rem, rem, w * KB, 1, 0, s, lm);
     }
     if (iw) {  // column blocks q .. q + w - 1 of the inverse, behind this step's POTF2
       if (use_flag) {
@@ -587,16 +582,16 @@ int diag_enqueue(gpx_handle* h, T* A, int64_t ld, int64_t o, int nbp, T* Winv, i
         if (q > 0) {
           launch_wait_counter(dflag, seq - 1, info, iw->aux);
           launch_inv_extend<T>(iw->U, iw->ldu, A + o * ld + o, ld, Winv + (o / KB) * (KB * KB), q, q + w, Wp,
-                               iw->nbw, iw->aux, 1);
+                               iw->nbw, iw->aux, 1, lm);
         }
         launch_wait_counter(dflag, seq, info, iw->aux);
       } else {  // the same two launches (the same arithmetic, bit for bit), both behind the step's event
         if (int rc = stream_waits(h, iw->aux, s, "block inverse")) return rc;
         launch_inv_extend<T>(iw->U, iw->ldu, A + o * ld + o, ld, Winv + (o / KB) * (KB * KB), q, q + w, Wp, iw->nbw,
-                             iw->aux, 1);
+                             iw->aux, 1, lm);
       }
       launch_inv_extend<T>(iw->U, iw->ldu, A + o * ld + o, ld, Winv + (o / KB) * (KB * KB), q, q + w, Wp, iw->nbw,
-                           iw->aux, 2);
+                           iw->aux, 2, lm);
     }
     q += w;
   }
@@ -617,8 +612,8 @@ int diag_enqueue(gpx_handle* h, T* A, int64_t ld, int64_t o, int nbp, T* Winv, i
 // records the new one (both parts' copies run in order on the copy stream).
 template <typename T>
 int panel_solve_enqueue(gpx_handle* h, T* A, int64_t ld, int64_t o, int nbp, int64_t rows_main, int64_t nx,
-                        const T* Winv, T* P, int64_t ldp, hipStream_t s, InvWork<T>* iw, int set, int64_t row0 = 0,
-                        hipEvent_t prev = nullptr, bool last = true) {
+                        const T* Winv, T* P, int64_t ldp, hipStream_t s, InvWork<T>* iw, int set, LaunchMode lm,
+                        int64_t row0 = 0, hipEvent_t prev = nullptr, bool last = true) {
   T* Apanel = A + (o + nbp + row0) * ld + o;
   P += row0 * ldp;
   const int64_t rows = rows_main + nx;
@@ -629,7 +624,7 @@ int panel_solve_enqueue(gpx_handle* h, T* A, int64_t ld, int64_t o, int nbp, int
     return GPX_OK;
   }
   if (!iw) {
-    launch_trsm_rlt<T>(Apanel, ld, rows, A + o * ld + o, ld, Winv + (o / KB) * (KB * KB), nbp, P, ldp, s);
+    launch_trsm_rlt<T>(Apanel, ld, rows, A + o * ld + o, ld, Winv + (o / KB) * (KB * KB), nbp, P, ldp, s, lm);
     return GPX_OK;
   }
   const T* Wp = iw->W + (o / iw->nbw) * (int64_t)iw->nbw * iw->nbw;
@@ -640,12 +635,12 @@ int panel_solve_enqueue(gpx_handle* h, T* A, int64_t ld, int64_t o, int nbp, int
   if (rows_main > 0 && nx > 0 && tile_main == 64) {
     // the bordered rows lie directly below the matrix rows, in A and in P: with 64-tiles on both, ONE launch
     // (as a launch of its own the 64-row product is a serial K = nb walk of ~37 us on the chain)
-    launch_gemm_nt_fixed<T>(64, P, ldp, Apanel, ld, Wp, iw->nbw, rows, nbp, nbp, 4, 1, s);
+    launch_gemm_nt_fixed<T>(64, P, ldp, Apanel, ld, Wp, iw->nbw, rows, nbp, nbp, 4, 1, s, lm);
   } else {
-    if (rows_main > 0) launch_gemm_nt_fixed<T>(tile_main, P, ldp, Apanel, ld, Wp, iw->nbw, rows_main, nbp, nbp, 4, 1, s);
+    if (rows_main > 0) launch_gemm_nt_fixed<T>(tile_main, P, ldp, Apanel, ld, Wp, iw->nbw, rows_main, nbp, nbp, 4, 1, s, lm);
     if (nx > 0)
       launch_gemm_nt<T>(64, P + rows_main * ldp, ldp, Apanel + rows_main * ld, ld, Wp, iw->nbw, nx, nbp, nbp, 4, 1,
-                        s);
+                        s, lm);
   }
   if (int rc = stream_waits(h, h->st4, s, "panel copy")) return rc;
   launch_copy2d<T>(Apanel, ld, P, ldp, rows, nbp, h->st4);
@@ -683,98 +678,99 @@ struct DeferLeft {
   size_t temp2_elems = 0;
 };
 
+// The panel at offset o of an n x n factorisation in panels of nb, and what lies behind it.
+struct PanelGeom {
+  int64_t o;
+  int nbp;         // width of the panel
+  int64_t t0;      // first trailing row/col
+  int64_t ntrail;  // trailing rows (<= 0: the last panel; o >= n: 0)
+  int nbn;         // width of the next panel
+  int64_t nrest;   // trailing rows beyond the next panel
+  int tile;        // of the trailing update's launches
+  PanelGeom(int64_t n, int nb, int64_t o_)
+      : o(o_), nbp((int)std::min<int64_t>(nb, n - o)), t0(o + nbp), ntrail(n - t0), nbn((int)std::min<int64_t>(nb, ntrail)),
+        nrest(ntrail - nbn), tile((ntrail % 128 == 0 && nbn % 128 == 0) ? 128 : 64) {}
+  // does a 128-tile trailing update run beside the look-ahead chain of the panel behind this one?  If not,
+  // the chain's small launches are alone on the GPU and take the latency mode of the 64-tile engine.
+  bool update_is_big() const { return nrest > 0 && tile == 128 && gemm_nt_tile(128, nrest, nrest, 1) == 128; }
+  // can the trailing update of this panel be one fused launch?  (128-tiles for strip and rest)
+  bool fusable() const { return update_is_big() && gemm_nt_tile(128, ntrail, nbn, 2) == 128; }
+};
+
+// What the three per-panel schedules of chol_enqueue share: its arguments, the streams, and what one panel hands to the
+// next.  Built once per factorisation.  Every launch names its LaunchMode; the launchers remember nothing.
 template <typename T>
-int chol_enqueue(gpx_handle* h, T* A, int64_t ld, int64_t n, int nb, T* Winv, T* P0, T* P1,
-                 int64_t ldp, int* info, int64_t gidx0, bool profile, int64_t nx = 0,
-                 InvWork<T>* iw = nullptr, int64_t nx_side = 0, int rest_split_arg = -1,
-                 const DeferLeft* defer = nullptr) {
-  hipStream_t s0 = h->st, s1 = h->st2;
-  T* Pbuf[2] = {P0, P1};
-  int rc;
-  // The schedule is a function of the arguments and the handle: its switches are h->env, the snapshot the call took
-  // when it began (gpx_env.h), and nothing below reads the environment.
-  const EnvKnobs& env = h->env;
-  const bool fuse_env = fused_strip_in_force(h);  // default OFF: measured equal, see DESIGN.md §5.2
-  unsigned* ctr = reinterpret_cast<unsigned*>(info + 8);  // the info buffer is 64 bytes: [0] pivot, [8] strip counter
-  unsigned target = 0;
-  // is the trailing update of the panel at offset o one fused launch?  (128-tiles for strip and rest)
-  auto is_fused = [&](int64_t o) -> bool {
-    if (!fuse_env || o >= n) return false;
-    const int nbp = (int)std::min<int64_t>(nb, n - o);
-    const int64_t ntrail = n - (o + nbp);
-    if (ntrail <= 0) return false;
-    const int nbn = (int)std::min<int64_t>(nb, ntrail);
-    const int64_t nrest = ntrail - nbn;
-    if (nrest <= 0 || ntrail % 128 != 0 || nbn % 128 != 0) return false;
-    return gemm_nt_tile(128, nrest, nrest, 1) == 128 && gemm_nt_tile(128, ntrail, nbn, 2) == 128;
-  };
-  // bordered rows [n, n+nx) x trailing columns of the panel at offset o (solved panel in Pc)
-  auto bordered_update = [&](int64_t o, const T* Pc, hipStream_t s) {
-    const int nbp = (int)std::min<int64_t>(nb, n - o);
-    const int64_t t0 = o + nbp, ntrail = n - t0;
-    if (nx <= 0 || ntrail <= 0) return;
-    launch_gemm_nt<T>(nx % 128 == 0 && ntrail % 128 == 0 ? 128 : 64, A + n * ld + t0, ld, Pc + ntrail * ldp, ldp, Pc,
-                      ldp, nx, ntrail, nbp, 0, 0, s);
-  };
-  // bordered rows [n + r0, n + r0 + nr) x matrix columns [c0, c0 + nc), panel at offset o (split schedule)
-  auto bordered_block = [&](int64_t o, const T* Pc, hipStream_t s, int64_t c0, int64_t nc, int64_t r0, int64_t nr) {
-    const int nbp = (int)std::min<int64_t>(nb, n - o);
-    const int64_t t0 = o + nbp, ntrail = n - t0;
+struct CholSched {
+  gpx_handle* h;
+  T* A;
+  int64_t ld, n;
+  int nb;
+  T* Winv;
+  int64_t ldp;
+  int* info;
+  int64_t gidx0;
+  bool profile;
+  int64_t nx;
+  InvWork<T>* iw;
+  const DeferLeft* defer;
+  hipStream_t s0, s1;
+  T* Pbuf[2];
+  bool fuse_env;    // default OFF: measured equal, see DESIGN.md §5.2
+  bool top_env;     // GPX_SOLVE_TOP=0: the whole panel solve on the chain (A/B)
+  int rest_split;   // trailing rows (in panels) up to which the REST hands its first column block over early
+  int64_t nxs, nxc;  // side rows (the main stream's business alone) and the chain's bordered rows: nx = nxc + nxs
+  int64_t dna, dc1;  // the deferred product: its rows and the column it starts at (0: none)
+  unsigned* ctr;     // the info buffer is 64 bytes: [0] pivot, [8] strip counter
+  unsigned target;   // strip slots released so far (fused step)
+  hipEvent_t e_main;  // split strip: "the main stream's work on the trailing matrix so far is complete"
+  int resv_k;         // GPX_CU_SELF_RESERVE, and the ring of this factorisation (null: off)
+  ReserveRing* ring;
+
+  // is the trailing update of the panel g one fused launch?
+  bool is_fused(const PanelGeom& g) const { return fuse_env && g.fusable(); }
+  // bordered rows [n, n+nx) x trailing columns of the panel g (solved panel in Pc)
+  void bordered_update(const PanelGeom& g, const T* Pc, hipStream_t s, LaunchMode lm) const {
+    if (nx <= 0 || g.ntrail <= 0) return;
+    launch_gemm_nt<T>(nx % 128 == 0 && g.ntrail % 128 == 0 ? 128 : 64, A + n * ld + g.t0, ld, Pc + g.ntrail * ldp, ldp, Pc,
+                      ldp, nx, g.ntrail, g.nbp, 0, 0, s, lm);
+  }
+  // bordered rows [n + r0, n + r0 + nr) x matrix columns [c0, c0 + nc), panel g (split schedule)
+  void bordered_block(const PanelGeom& g, const T* Pc, hipStream_t s, int64_t c0, int64_t nc, int64_t r0, int64_t nr,
+                      LaunchMode lm) const {
     if (nr <= 0 || nc <= 0) return;
     // many rows plus a 64-row remainder (the left block column of the two-level factorisation with the right-hand
     // sides below it): the 128-multiple in 128-tiles, the remainder in a launch of its own
     const int64_t na = split_rows_128(nr, nc);
-    launch_gemm_nt<T>(na % 128 == 0 && nc % 128 == 0 ? 128 : 64, A + (n + r0) * ld + c0, ld, Pc + (ntrail + r0) * ldp, ldp,
-                      Pc + (c0 - t0) * ldp, ldp, na, nc, nbp, 0, 0, s);
+    launch_gemm_nt<T>(na % 128 == 0 && nc % 128 == 0 ? 128 : 64, A + (n + r0) * ld + c0, ld, Pc + (g.ntrail + r0) * ldp, ldp,
+                      Pc + (c0 - g.t0) * ldp, ldp, na, nc, g.nbp, 0, 0, s, lm);
     if (na < nr)
-      launch_gemm_nt<T>(64, A + (n + r0 + na) * ld + c0, ld, Pc + (ntrail + r0 + na) * ldp, ldp, Pc + (c0 - t0) * ldp, ldp,
-                        nr - na, nc, nbp, 0, 0, s);
-  };
-  // does a 128-tile trailing update run beside the look-ahead chain of the panel behind offset o?  If not,
-  // the chain's small launches are alone on the GPU and take the latency mode of the 64-tile engine.
-  auto update_is_big = [&](int64_t o) -> bool {
-    if (o >= n) return false;
-    const int nbp = (int)std::min<int64_t>(nb, n - o);
-    const int64_t ntrail = n - (o + nbp);
-    if (ntrail <= 0) return false;
-    const int nbn = (int)std::min<int64_t>(nb, ntrail);
-    const int64_t nrest = ntrail - nbn;
-    return nrest > 0 && ntrail % 128 == 0 && nbn % 128 == 0 && gemm_nt_tile(128, nrest, nrest, 1) == 128;
-  };
-  const bool split_env = split_strip_in_force(h);  // (the fused update keeps its own hand-over)
-  const bool top_env = env.solve_top;              // GPX_SOLVE_TOP=0: the whole panel solve on the chain (A/B)
-  // trailing rows (in panels) up to which the REST hands its first column block over early (a caller's own: the two-level schedule)
-  const int rest_split = rest_split_arg >= 0 ? rest_split_arg : env.rest_split;
-  // The LAST nx_side bordered rows (the query points of gpx_fit_predict: a multiple of 128) are the main stream's
-  // business alone in the split schedule: their panel solves, like their updates, are throughput work no step of the
-  // chain waits for (tried: a stream of their own that trails the factorisation panel by panel, reading L from A —
-  // slower, N = 8192: 12.4 against 11.6 ms; one more stream's worth of serial block solves).  The other bordered
-  // rows (the right-hand sides) ride in the chain's panel solves as before.
-  const int64_t nxs = split_env ? nx_side : 0, nxc = nx - nxs;
-  auto side_solve = [&](int64_t o, T* Pp, hipStream_t s) -> int {  // side rows of the panel at offset o -> P and back into A
+      launch_gemm_nt<T>(64, A + (n + r0 + na) * ld + c0, ld, Pc + (g.ntrail + r0 + na) * ldp, ldp, Pc + (c0 - g.t0) * ldp, ldp,
+                        nr - na, nc, g.nbp, 0, 0, s, lm);
+  }
+  // side rows of the panel g -> P and back into A
+  int side_solve(const PanelGeom& g, T* Pp, hipStream_t s, LaunchMode lm) const {
     if (nxs <= 0) return GPX_OK;
-    const int nbp = (int)std::min<int64_t>(nb, n - o);
+    const int64_t o = g.o;
+    const int nbp = g.nbp;
     T* Aside = A + (n + nxc) * ld + o;
     T* Pside = Pp + ((n - o - nbp) + nxc) * ldp;
     if (!iw) {
-      launch_trsm_rlt<T>(Aside, ld, nxs, A + o * ld + o, ld, Winv + (o / KB) * (KB * KB), nbp, Pside, ldp, s);
+      launch_trsm_rlt<T>(Aside, ld, nxs, A + o * ld + o, ld, Winv + (o / KB) * (KB * KB), nbp, Pside, ldp, s, lm);
       return GPX_OK;
     }
     HIPCHK(h, hipStreamWaitEvent(s, iw->ready, 0));
     const T* Wp = iw->W + (o / iw->nbw) * (int64_t)iw->nbw * iw->nbw;
     const int64_t na = split_rows_128(nxs, nbp);  // (as bordered_block)
-    launch_gemm_nt<T>(na % 128 == 0 && nbp % 128 == 0 ? 128 : 64, Pside, ldp, Aside, ld, Wp, iw->nbw, na, nbp, nbp, 4, 1, s);
-    if (na < nxs) launch_gemm_nt<T>(64, Pside + na * ldp, ldp, Aside + na * ld, ld, Wp, iw->nbw, nxs - na, nbp, nbp, 4, 1, s);
+    launch_gemm_nt<T>(na % 128 == 0 && nbp % 128 == 0 ? 128 : 64, Pside, ldp, Aside, ld, Wp, iw->nbw, na, nbp, nbp, 4, 1, s, lm);
+    if (na < nxs)
+      launch_gemm_nt<T>(64, Pside + na * ldp, ldp, Aside + na * ld, ld, Wp, iw->nbw, nxs - na, nbp, nbp, 4, 1, s, lm);
     launch_copy2d<T>(Aside, ld, Pside, ldp, nxs, nbp, s);
     return GPX_OK;
-  };
+  }
   // The deferred product (DeferLeft): A[side rows, c1:n) -= L[side rows, 0:c1) L[c1:n, 0:c1)^T for the dna side rows that go
-  // out in 128-tiles; the remainder (the right-hand sides) stays right-looking.
-  const int64_t dna0 = (defer && iw && nxs > 0 && !fuse_env && defer->c1 > 0 && defer->c1 < n && defer->c1 % nb == 0 && n % 128 == 0)
-                           ? split_rows_128(nxs, n - defer->c1)
-                           : 0;
-  const int64_t dna = dna0 % 128 == 0 ? dna0 : 0, dc1 = dna > 0 ? defer->c1 : 0;
-  auto deferred_product = [&](T* Tbuf, hipStream_t s) {
+  // out in 128-tiles; the remainder (the right-hand sides) stays right-looking.  lm reaches the classical launches: the
+  // one below and strassen_nt's peeled parts, not the level's products.
+  void deferred_product(T* Tbuf, hipStream_t s, LaunchMode lm) const {
     T* Cd = A + (n + nxc) * ld + dc1;
     const T *Ad = A + (n + nxc) * ld, *Bd = A + dc1 * ld;
     const int64_t nd = n - dc1, kd = dc1, ldt = kd / 2 + ld_skew<T>();
@@ -790,243 +786,302 @@ int chol_enqueue(gpx_handle* h, T* A, int64_t ld, int64_t n, int nb, T* Winv, T*
       }
     }
     if (mch == 0) {
-      launch_gemm_nt<T>(128, Cd, ld, Ad, ld, Bd, ld, dna, nd, kd, 0, 0, s);
+      launch_gemm_nt<T>(128, Cd, ld, Ad, ld, Bd, ld, dna, nd, kd, 0, 0, s, lm);
       return;
     }
     const StrassenL2<T> l2{defer->smin2, (T*)defer->temp2, defer->temp2_elems};
     for (int64_t r = 0; r < dna; r += mch) {
       const int64_t m = std::min(mch, dna - r);
-      strassen_nt<T>(Cd + r * ld, ld, Ad + r * ld, ld, Bd, ld, m, nd, kd, Tbuf, Tbuf + (m / 256 * 128) * ldt, ldt, s, &l2);
+      strassen_nt<T>(Cd + r * ld, ld, Ad + r * ld, ld, Bd, ld, m, nd, kd, Tbuf, Tbuf + (m / 256 * 128) * ldt, ldt, s, &l2, nullptr,
+                     lm);
     }
-  };
-  LatencyGuard latency_guard;
-  set_latency_mode(1);  // panel 0: nothing runs beside it
+  }
+
+  int fused_step(const PanelGeom& g, int step, hipEvent_t e_panel);
+  int split_step(const PanelGeom& g, int step, hipEvent_t e_panel);
+  int lookahead_step(const PanelGeom& g, int step, hipEvent_t e_panel);
+};
+
+// FUSED step (GPX_FUSED_STRIP=1): STRIP and REST of the panel g are one launch; the look-ahead stream is parked on the
+// strip counter and then runs diagonal block p+1 and panel p+1 beside the rest of the same launch.
+template <typename T>
+int CholSched<T>::fused_step(const PanelGeom& g, int step, hipEvent_t e_panel) {
+  const int64_t t0 = g.t0, ntrail = g.ntrail, nrest = g.nrest;
+  const int nbp = g.nbp, nbn = g.nbn;
+  T *Pc = Pbuf[step & 1], *Pn = Pbuf[(step + 1) & 1];  // panel of this step, rows [t0, n + nx), and the next
+  const LaunchMode beside{!g.update_is_big()};  // for everything this step enqueues (chain, solve, bordered rows)
+  int rc;
+  {  // main stream: the whole trailing update, strip first
+    PhaseScope ps(h, &h->tm.chol_syrk, profile);
+    target += launch_gemm_nt_fused<T>(A + t0 * ld + t0, ld, Pc, ldp, ntrail, nbn, nbp, ctr, s0);
+    h->tm.syrk_flops += (double)ntrail * (double)(ntrail + 1) * (double)nbp;
+    h->tm.syrk_launches += 1;
+  }
+  // look-ahead stream: parked until the strip is released, then diagonal block p+1, panel p+1
+  launch_wait_counter(ctr, target, info, s1);
+  {
+    PhaseScope ps(h, &h->tm.chol_diag, profile, s1);
+    if ((rc = diag_enqueue(h, A, ld, t0, nbn, Winv, info, gidx0, s1, iw, beside))) return rc;
+  }
+  {
+    PhaseScope ps(h, &h->tm.chol_trsm, profile, s1);
+    if ((rc = panel_solve_enqueue(h, A, ld, t0, nbn, nrest, nx, Winv, Pn, ldp, s1, iw, (step + 1) & 1, beside))) return rc;
+  }
+  HIPCHK(h, hipEventRecord(e_panel, s1));
+  const PanelGeom gn(n, nb, t0);
+  if (is_fused(gn)) bordered_update(gn, Pn, s1, beside);  // for update p+1: off the chain, beside the rest of update p
+  HIPCHK(h, hipStreamWaitEvent(s0, e_panel, 0));
+  return GPX_OK;
+}
+
+// SPLIT step (round 3, the default), with the deferred product of the two-level factorisation's left block column.
+template <typename T>
+int CholSched<T>::split_step(const PanelGeom& g, int step, hipEvent_t e_panel) {
+  const EnvKnobs& env = h->env;
+  const int64_t t0 = g.t0, ntrail = g.ntrail, nrest = g.nrest;
+  const int nbp = g.nbp, nbn = g.nbn, tile = g.tile;
+  T *Pc = Pbuf[step & 1], *Pn = Pbuf[(step + 1) & 1];  // panel of this step, rows [t0, n + nx), and the next
+  hipStream_t sm = s0;
+  int rc;
+  // self-reserving main-stream products where the chain sets the pace (the criterion of the REST's early hand-over)
+  const int resv_it = (resv_k > 0 && (env.resv_all || ntrail <= (int64_t)(rest_split + 1) * nb)) ? resv_k : 0;
+  // The modes of this step.  Does a large update run beside its small launches (PanelGeom::update_is_big)?
+  const bool latency = !g.update_is_big();
+  const LaunchMode beside{latency};                     // the look-ahead stream's products
+  const LaunchMode on_main{latency, resv_it, 0, ring};  // everything the main stream runs beside the next diagonal chain
+  const LaunchMode on_chain{latency, 0, resv_it > 0 ? env.resv_chain : 0, ring};  // the diagonal chain beside such products
+  // SPLIT STRIP (round 3, the default): of the strip only the next DIAGONAL block is on the chain.  It is
+  // updated on the look-ahead stream itself, right behind the panel solve that produced its operand (no
+  // hand-over between streams on the chain; 64-tiles in latency mode: a K = nb walk of a 64-tile is a
+  // quarter of a 128-tile's), after the previous panel's REST (which also touched the block) is complete.
+  // The rows BELOW it are needed only by the next panel solve, one diagonal chain later: they are updated
+  // on the main stream, beside that chain, followed by the REST.
+  if (e_main) HIPCHK(h, hipStreamWaitEvent(s1, e_main, 0));
+  {
+    PhaseScope ps(h, &h->tm.chol_strip, profile, s1);
+    launch_gemm_nt<T>(tile, A + t0 * ld + t0, ld, Pc, ldp, Pc, ldp, nbn, nbn, nbp, 1, 0, s1, beside);
+  }
+  // the deferred product takes this panel's buffer for its temporaries: behind this launch, its reader on the chain
+  hipEvent_t e_stripd = nullptr;
+  if (t0 == dc1 && (rc = record_event(h, s1, "deferred product", &e_stripd))) return rc;
+  // The host enqueues the main stream's whole iteration BEFORE the diagonal chain's ~50 small launches: the
+  // GPU runs the chain about as fast as the host can enqueue it (N = 8192: the update used to reach the GPU
+  // 0.5 ms after the panel it needs, and then collided with the NEXT panel solve and diagonal-block update).
+  {  // rows below the diagonal block in the next panel's columns; the chain's bordered rows in a small launch
+    PhaseScope ps(h, &h->tm.chol_strip, profile, sm);
+    if (nrest > 0)
+      launch_gemm_nt<T>(tile, A + (t0 + nbn) * ld + t0, ld, Pc + (int64_t)nbn * ldp, ldp, Pc, ldp, nrest, nbn, nbp, 0,
+                        0, sm, on_main);
+    bordered_block(g, Pc, sm, t0, nbn, 0, nxc, on_main);
+  }
+  hipEvent_t e_below;
+  if ((rc = record_event(h, sm, "look-ahead", &e_below))) return rc;
+  // REST.  Where the chain, not the update, sets the pace (the last `rest_split` panels' worth of trailing
+  // rows: all of N = 8192, the tail of N = 65536), the column block of the panel AFTER next goes first, as a
+  // launch of its own, and the look-ahead stream's next diagonal-block update waits for that launch only:
+  // the chain then never waits for the bulk of an update (it used to, for every early panel of N = 8192,
+  // where update and chain take about the same time).  The panel buffer this update reads is rewritten two
+  // panel solves later, behind the next "rows below" event of this stream, i.e. behind all of this update.
+  const int nbn2 = (int)std::min<int64_t>(nb, nrest);
+  const bool ahead = nrest > nbn2 && nrest <= (int64_t)rest_split * nb;
+  T* Cr = A + (t0 + nbn) * ld + (t0 + nbn);
+  const T* Pr = Pc + (int64_t)nbn * ldp;
+  if (ahead) {
+    {
+      PhaseScope ps(h, &h->tm.chol_strip, profile, sm);
+      launch_gemm_nt<T>(tile, Cr, ld, Pr, ldp, Pr, ldp, nrest, nbn2, nbp, 2, 0, sm, on_main);
+    }
+    if ((rc = record_event(h, sm, "look-ahead", &e_main))) return rc;
+  }
+  const int64_t nr = ahead ? nrest - nbn2 : nrest, off = ahead ? nbn2 : 0;
+  if (nr > 0) {
+    const bool big = gemm_nt_tile(tile, nr, nr, 1) == 128;
+    PhaseScope ps(h, big ? &h->tm.chol_syrk : &h->tm.chol_strip, profile, sm);
+    launch_gemm_nt<T>(tile, Cr + off * ld + off, ld, Pr + off * ldp, ldp, Pr + off * ldp, ldp, nr, nr, nbp, 1, 0, sm, on_main);
+    if (big) {
+      h->tm.syrk_flops += (double)nr * (double)(nr + 1) * (double)nbp;
+      h->tm.syrk_launches += 1;
+    }
+  }
+  if (!ahead && (rc = record_event(h, sm, "look-ahead", &e_main))) return rc;
+  {  // the bordered rows' share of the REST (columns beyond the next panel); the side rows' whole step — their
+     // panel solve and the update of every column to the right — behind everything the chain waits for
+    PhaseScope ps(h, &h->tm.chol_strip, profile, sm);
+    bordered_block(g, Pc, sm, t0 + nbn, nrest, 0, nxc, on_main);
+    if ((rc = side_solve(g, Pc, sm, on_main))) return rc;
+    if (g.o < dc1) {
+      // deferral: the 128-tile rows only in columns [t0, c1) — in the tiles the whole launch would take, so that
+      // those columns receive the same addends bit for bit — and the remainder's launch as it is
+      if (dc1 > t0)
+        launch_gemm_nt_fixed<T>(gemm_nt_tile(128, dna, ntrail, 0), A + (n + nxc) * ld + t0, ld, Pc + (ntrail + nxc) * ldp, ldp,
+                                Pc, ldp, dna, dc1 - t0, nbp, 0, 0, sm, on_main);
+      bordered_block(g, Pc, sm, t0, ntrail, nxc + dna, nxs - dna, on_main);
+      if (t0 == dc1) {
+        // B operand: rows [c1, n) of the panels so far are in A once this panel's copy-back is (the copy stream
+        // runs in order).  Temporaries: this panel's buffer, behind its copy-back and behind STRIP_D on the chain;
+        // its next writer, the solve of the panel after next, waits for the next "rows below" event of this stream.
+        if (iw->copied[step & 1]) HIPCHK(h, hipStreamWaitEvent(sm, iw->copied[step & 1], 0));
+        HIPCHK(h, hipStreamWaitEvent(sm, e_stripd, 0));
+        deferred_product(Pc, sm, on_main);
+      }
+    } else {
+      bordered_block(g, Pc, sm, t0, ntrail, nxc, nxs, on_main);
+    }
+  }
+  {
+    PhaseScope ps(h, &h->tm.chol_diag, profile, s1);
+    if ((rc = diag_enqueue(h, A, ld, t0, nbn, Winv, info, gidx0, s1, iw, on_chain))) return rc;
+  }
+  HIPCHK(h, hipStreamWaitEvent(s1, e_below, 0));
+  // Panel solve p+1: only the rows of the NEXT diagonal block (what STRIP_D(p+1) and the B operands need) on the
+  // chain; the rows below them, and the chain's bordered rows, on the main stream in front of its next update
+  // (their inputs are the main stream's own work plus W_{p+1}) — with the block inverse only.
+  const int64_t top = (iw && top_env) ? std::min<int64_t>(nrest, nb) : nrest;
+  hipEvent_t prev_copied = iw ? iw->copied[(step + 1) & 1] : nullptr;
+  {
+    PhaseScope ps(h, &h->tm.chol_trsm, profile, s1);
+    if (top < nrest || (iw && top_env)) {
+      if ((rc = panel_solve_enqueue(h, A, ld, t0, nbn, top, 0, Winv, Pn, ldp, s1, iw, (step + 1) & 1, beside, 0, prev_copied,
+                                    false)))
+        return rc;
+    } else if ((rc = panel_solve_enqueue(h, A, ld, t0, nbn, nrest, nxc, Winv, Pn, ldp, s1, iw, (step + 1) & 1, beside))) {
+      return rc;
+    }
+  }
+  HIPCHK(h, hipEventRecord(e_panel, s1));
+  HIPCHK(h, hipStreamWaitEvent(sm, e_panel, 0));
+  if (top < nrest || (iw && top_env)) {  // runs beside the NEXT diagonal chain
+    PhaseScope ps(h, &h->tm.chol_trsm, profile, sm);
+    if ((rc = panel_solve_enqueue(h, A, ld, t0, nbn, nrest - top, nxc, Winv, Pn, ldp, sm, iw, (step + 1) & 1, on_main, top,
+                                  prev_copied, true)))
+      return rc;
+  }
+  return GPX_OK;
+}
+
+// Round-2 LOOK-AHEAD step (GPX_SPLIT_STRIP=0): the whole STRIP on the main stream, then diagonal block p+1 and panel
+// p+1 on the look-ahead stream beside the REST.
+template <typename T>
+int CholSched<T>::lookahead_step(const PanelGeom& g, int step, hipEvent_t e_panel) {
+  const int64_t t0 = g.t0, ntrail = g.ntrail, nrest = g.nrest;
+  const int nbp = g.nbp, nbn = g.nbn, tile = g.tile;
+  T *Pc = Pbuf[step & 1], *Pn = Pbuf[(step + 1) & 1];  // panel of this step, rows [t0, n + nx), and the next
+  const LaunchMode alone{true};                 // the strip runs alone (the look-ahead stream waits for it)
+  const LaunchMode beside{!g.update_is_big()};  // everything else this step enqueues (chain, solve, rest)
+  int rc;
+  {  // STRIP: rows [t0, n) x cols [t0, t0+nbn), tiles on/below the diagonal
+    PhaseScope ps(h, &h->tm.chol_strip, profile);
+    launch_gemm_nt<T>(tile, A + t0 * ld + t0, ld, Pc, ldp, Pc, ldp, ntrail, nbn, nbp, 2, 0, s0, alone);
+    // bordered rows [n, n+nx) x all trailing cols: their own small launch, so that the
+    // SYRK grids (and their XCD balance) stay exactly those of the plain factorisation
+    bordered_update(g, Pc, s0, beside);
+  }
+  // the two streams touch the same matrix: an event that cannot be created / recorded /
+  // waited on must fail the call, never let the streams run unordered
+  if ((rc = stream_waits(h, s1, s0, "look-ahead"))) return rc;
+  {  // look-ahead stream: factor diagonal block p+1, solve panel p+1
+    {
+      PhaseScope ps(h, &h->tm.chol_diag, profile, s1);
+      if ((rc = diag_enqueue(h, A, ld, t0, nbn, Winv, info, gidx0, s1, iw, beside))) return rc;
+    }
+    {
+      PhaseScope ps(h, &h->tm.chol_trsm, profile, s1);
+      if ((rc = panel_solve_enqueue(h, A, ld, t0, nbn, nrest, nx, Winv, Pn, ldp, s1, iw, (step + 1) & 1, beside))) return rc;
+    }
+  }
+  HIPCHK(h, hipEventRecord(e_panel, s1));
+  if (nrest > 0) {  // REST: lower triangle of the trailing matrix beyond the strip
+    // the roofline bookkeeping (time, flops, launches) follows ONE kernel, the 128-tile triangular
+    // update; the last few, under-filled updates run as 64-tiles and are booked with the strips
+    const bool big = gemm_nt_tile(tile, nrest, nrest, 1) == 128;
+    PhaseScope ps(h, big ? &h->tm.chol_syrk : &h->tm.chol_strip, profile);
+    launch_gemm_nt<T>(tile, A + (t0 + nbn) * ld + (t0 + nbn), ld, Pc + (int64_t)nbn * ldp, ldp,
+                      Pc + (int64_t)nbn * ldp, ldp, nrest, nrest, nbp, 1, 0, s0, beside);
+    if (big) {
+      h->tm.syrk_flops += (double)nrest * (double)(nrest + 1) * (double)nbp;
+      h->tm.syrk_launches += 1;
+    }
+  }
+  HIPCHK(h, hipStreamWaitEvent(s0, e_panel, 0));
+  return GPX_OK;
+}
+
+template <typename T>
+int chol_enqueue(gpx_handle* h, T* A, int64_t ld, int64_t n, int nb, T* Winv, T* P0, T* P1,
+                 int64_t ldp, int* info, int64_t gidx0, bool profile, int64_t nx = 0,
+                 InvWork<T>* iw = nullptr, int64_t nx_side = 0, int rest_split_arg = -1,
+                 const DeferLeft* defer = nullptr) {
+  hipStream_t s0 = h->st, s1 = h->st2;
+  int rc;
+  // The schedule is a function of the arguments and the handle: its switches are h->env, the snapshot the call took
+  // when it began (gpx_env.h), and nothing below reads the environment.
+  const EnvKnobs& env = h->env;
+  const bool split_env = split_strip_in_force(h);  // (the fused update keeps its own hand-over)
+  CholSched<T> c{};
+  c.h = h, c.A = A, c.ld = ld, c.n = n, c.nb = nb, c.Winv = Winv, c.ldp = ldp, c.info = info, c.gidx0 = gidx0;
+  c.profile = profile, c.nx = nx, c.iw = iw, c.defer = defer, c.s0 = s0, c.s1 = s1, c.Pbuf[0] = P0, c.Pbuf[1] = P1;
+  c.fuse_env = fused_strip_in_force(h);
+  c.top_env = env.solve_top;
+  // (a caller's own rest_split: the two-level schedule)
+  c.rest_split = rest_split_arg >= 0 ? rest_split_arg : env.rest_split;
+  c.ctr = reinterpret_cast<unsigned*>(info + 8);
+  // The LAST nx_side bordered rows (the query points of gpx_fit_predict: a multiple of 128) are the main stream's
+  // business alone in the split schedule: their panel solves, like their updates, are throughput work no step of the
+  // chain waits for (tried: a stream of their own that trails the factorisation panel by panel, reading L from A —
+  // slower, N = 8192: 12.4 against 11.6 ms; one more stream's worth of serial block solves).  The other bordered
+  // rows (the right-hand sides) ride in the chain's panel solves as before.
+  c.nxs = split_env ? nx_side : 0, c.nxc = nx - c.nxs;
+  // the deferred product's rows: the side rows that go out in 128-tiles (CholSched::deferred_product)
+  const int64_t dna0 = (defer && iw && c.nxs > 0 && !c.fuse_env && defer->c1 > 0 && defer->c1 < n && defer->c1 % nb == 0 && n % 128 == 0)
+                           ? split_rows_128(c.nxs, n - defer->c1)
+                           : 0;
+  c.dna = dna0 % 128 == 0 ? dna0 : 0, c.dc1 = c.dna > 0 ? defer->c1 : 0;
+  const LaunchMode alone{true};  // panel 0, and the last panel's side rows: nothing runs beside them
   // GPX_CU_SELF_RESERVE = k (round 4): where the chain sets the pace, the main stream's products leave k CUs per XCD to it
   // by themselves (gemm_nt_resv_kernel: persistent grids that exit on the reserved CUs).  Split schedule only.
   // GPX_RESV_ALL=1 (experiment): every panel's main-stream products, not only the chain-bound ones.  GPX_RESV_CHAIN: 0
   // chain untouched, 1 (default) POTF2 padded to 130 KB of LDS, 2 also its slab launches.  GPX_RESV_FORM: the grid of the
   // self-reserving launches (launch_gemm_nt).
-  const int resv_k = env.cu_self_reserve;
-  ReserveGuard reserve_guard;
-  if (resv_k > 0 && split_env) {
+  c.resv_k = env.cu_self_reserve;
+  ReserveRing ring;  // this factorisation's: `used` counts from 0
+  if (c.resv_k > 0 && split_env) {
     if ((rc = ensure(h, h->resv_ring, (size_t)RESV_RING * 8 * sizeof(unsigned)))) return rc;
     HIPCHK(h, hipMemsetAsync(h->resv_ring.p, 0, (size_t)RESV_RING * 8 * sizeof(unsigned), s0));
-    reserve_ring((unsigned*)h->resv_ring.p, RESV_RING, env.resv_form);
+    ring.ctr = (unsigned*)h->resv_ring.p, ring.cap = RESV_RING, ring.form = env.resv_form;
+    c.ring = &ring;
   }
-  const bool any_fused = is_fused(0);
-  if (any_fused) HIPCHK(h, hipMemsetAsync(ctr, 0, sizeof(unsigned), s0));
+  const PanelGeom g0(n, nb, 0);
+  const bool any_fused = c.is_fused(g0);
+  if (any_fused) HIPCHK(h, hipMemsetAsync(c.ctr, 0, sizeof(unsigned), s0));
   // prologue: panel 0 on the main stream
   {
-    const int nb0 = (int)std::min<int64_t>(nb, n);
+    const int nb0 = g0.nbp;
     {
       PhaseScope ps(h, &h->tm.chol_diag, profile);
-      if ((rc = diag_enqueue(h, A, ld, 0, nb0, Winv, info, gidx0, s0, iw))) return rc;
+      if ((rc = diag_enqueue(h, A, ld, 0, nb0, Winv, info, gidx0, s0, iw, alone))) return rc;
     }
     {
       PhaseScope ps(h, &h->tm.chol_trsm, profile);
-      if ((rc = panel_solve_enqueue(h, A, ld, 0, nb0, n - nb0, nxc, Winv, Pbuf[0], ldp, s0, iw, 0))) return rc;
+      if ((rc = panel_solve_enqueue(h, A, ld, 0, nb0, n - nb0, c.nxc, Winv, P0, ldp, s0, iw, 0, alone))) return rc;
     }
     if (any_fused) {
-      bordered_update(0, Pbuf[0], s0);
+      c.bordered_update(g0, P0, s0, alone);
       if ((rc = stream_waits(h, s1, s0, "look-ahead"))) return rc;  // counter reset + panel 0 before the parked stream's first poll
     }
   }
-  hipEvent_t e_main = nullptr;  // split strip: "the main stream's work on the trailing matrix so far is complete"
-  if (split_env && n > nb && (rc = record_event(h, s0, "look-ahead", &e_main))) return rc;  // panel 0 ran on the main stream
+  if (split_env && n > nb && (rc = record_event(h, s0, "look-ahead", &c.e_main))) return rc;  // panel 0 ran on the main stream
   int step = 0;
   for (int64_t o = 0; o < n; o += nb, ++step) {
-    const int nbp = (int)std::min<int64_t>(nb, n - o);
-    const int64_t t0 = o + nbp;          // first trailing row/col
-    const int64_t ntrail = n - t0;
-    if (ntrail <= 0) {  // the last panel: nothing to update, but the side rows still take their solve
-      if ((rc = side_solve(o, Pbuf[step & 1], s0))) return rc;
+    const PanelGeom g(n, nb, o);
+    if (g.ntrail <= 0) {  // the last panel: nothing to update, but the side rows still take their solve
+      // (alone: the step before it had no REST, and a single panel follows the prologue)
+      if ((rc = c.side_solve(g, c.Pbuf[step & 1], s0, alone))) return rc;
       break;
     }
-    T* Pc = Pbuf[step & 1];              // panel of this step, rows [t0, n + nx)
-    T* Pn = Pbuf[(step + 1) & 1];
-    const int nbn = (int)std::min<int64_t>(nb, ntrail);  // width of the next panel
-    const int64_t nrest = ntrail - nbn;
-    const int tile = (ntrail % 128 == 0 && nbn % 128 == 0) ? 128 : 64;
     hipEvent_t e_panel = next_event(h);
     if (!e_panel) return fail(h, GPX_E_HIP, "hipEventCreate failed (look-ahead)");
-    set_latency_mode(update_is_big(o) ? 0 : 1);  // for everything this iteration enqueues (strip, chain, solve, rest)
-    if (is_fused(o)) {
-      {  // main stream: the whole trailing update, strip first
-        PhaseScope ps(h, &h->tm.chol_syrk, profile);
-        target += launch_gemm_nt_fused<T>(A + t0 * ld + t0, ld, Pc, ldp, ntrail, nbn, nbp, ctr, s0);
-        h->tm.syrk_flops += (double)ntrail * (double)(ntrail + 1) * (double)nbp;
-        h->tm.syrk_launches += 1;
-      }
-      // look-ahead stream: parked until the strip is released, then diagonal block p+1, panel p+1
-      launch_wait_counter(ctr, target, info, s1);
-      {
-        PhaseScope ps(h, &h->tm.chol_diag, profile, s1);
-        if ((rc = diag_enqueue(h, A, ld, t0, nbn, Winv, info, gidx0, s1, iw))) return rc;
-      }
-      {
-        PhaseScope ps(h, &h->tm.chol_trsm, profile, s1);
-        if ((rc = panel_solve_enqueue(h, A, ld, t0, nbn, nrest, nx, Winv, Pn, ldp, s1, iw, (step + 1) & 1))) return rc;
-      }
-      HIPCHK(h, hipEventRecord(e_panel, s1));
-      if (is_fused(t0)) bordered_update(t0, Pn, s1);  // for update p+1: off the chain, beside the rest of update p
-      HIPCHK(h, hipStreamWaitEvent(s0, e_panel, 0));
-      continue;
-    }
-    if (split_env) {
-      hipStream_t sm = s0;
-      // self-reserving main-stream products where the chain sets the pace (the criterion of the REST's early hand-over)
-      const int resv_it = (resv_k > 0 && (env.resv_all || ntrail <= (int64_t)(rest_split + 1) * nb)) ? resv_k : 0;
-      // SPLIT STRIP (round 3, the default): of the strip only the next DIAGONAL block is on the chain.  It is
-      // updated on the look-ahead stream itself, right behind the panel solve that produced its operand (no
-      // hand-over between streams on the chain; 64-tiles in latency mode: a K = nb walk of a 64-tile is a
-      // quarter of a 128-tile's), after the previous panel's REST (which also touched the block) is complete.
-      // The rows BELOW it are needed only by the next panel solve, one diagonal chain later: they are updated
-      // on the main stream, beside that chain, followed by the REST.
-      if (e_main) HIPCHK(h, hipStreamWaitEvent(s1, e_main, 0));
-      {
-        PhaseScope ps(h, &h->tm.chol_strip, profile, s1);
-        launch_gemm_nt<T>(tile, A + t0 * ld + t0, ld, Pc, ldp, Pc, ldp, nbn, nbn, nbp, 1, 0, s1);
-      }
-      // the deferred product takes this panel's buffer for its temporaries: behind this launch, its reader on the chain
-      hipEvent_t e_stripd = nullptr;
-      if (t0 == dc1 && (rc = record_event(h, s1, "deferred product", &e_stripd))) return rc;
-      // The host enqueues the main stream's whole iteration BEFORE the diagonal chain's ~50 small launches: the
-      // GPU runs the chain about as fast as the host can enqueue it (N = 8192: the update used to reach the GPU
-      // 0.5 ms after the panel it needs, and then collided with the NEXT panel solve and diagonal-block update).
-      set_reserve_mode(resv_it);  // everything the main stream runs beside the next diagonal chain
-      {  // rows below the diagonal block in the next panel's columns; the chain's bordered rows in a small launch
-        PhaseScope ps(h, &h->tm.chol_strip, profile, sm);
-        if (nrest > 0)
-          launch_gemm_nt<T>(tile, A + (t0 + nbn) * ld + t0, ld, Pc + (int64_t)nbn * ldp, ldp, Pc, ldp, nrest, nbn, nbp, 0,
-                            0, sm);
-        bordered_block(o, Pc, sm, t0, nbn, 0, nxc);
-      }
-      hipEvent_t e_below;
-      if ((rc = record_event(h, sm, "look-ahead", &e_below))) return rc;
-      // REST.  Where the chain, not the update, sets the pace (the last `rest_split` panels' worth of trailing
-      // rows: all of N = 8192, the tail of N = 65536), the column block of the panel AFTER next goes first, as a
-      // launch of its own, and the look-ahead stream's next diagonal-block update waits for that launch only:
-      // the chain then never waits for the bulk of an update (it used to, for every early panel of N = 8192,
-      // where update and chain take about the same time).  The panel buffer this update reads is rewritten two
-      // panel solves later, behind the next "rows below" event of this stream, i.e. behind all of this update.
-      const int nbn2 = (int)std::min<int64_t>(nb, nrest);
-      const bool ahead = nrest > nbn2 && nrest <= (int64_t)rest_split * nb;
-      T* Cr = A + (t0 + nbn) * ld + (t0 + nbn);
-      const T* Pr = Pc + (int64_t)nbn * ldp;
-      if (ahead) {
-        {
-          PhaseScope ps(h, &h->tm.chol_strip, profile, sm);
-          launch_gemm_nt<T>(tile, Cr, ld, Pr, ldp, Pr, ldp, nrest, nbn2, nbp, 2, 0, sm);
-        }
-        if ((rc = record_event(h, sm, "look-ahead", &e_main))) return rc;
-      }
-      const int64_t nr = ahead ? nrest - nbn2 : nrest, off = ahead ? nbn2 : 0;
-      if (nr > 0) {
-        const bool big = gemm_nt_tile(tile, nr, nr, 1) == 128;
-        PhaseScope ps(h, big ? &h->tm.chol_syrk : &h->tm.chol_strip, profile, sm);
-        launch_gemm_nt<T>(tile, Cr + off * ld + off, ld, Pr + off * ldp, ldp, Pr + off * ldp, ldp, nr, nr, nbp, 1, 0, sm);
-        if (big) {
-          h->tm.syrk_flops += (double)nr * (double)(nr + 1) * (double)nbp;
-          h->tm.syrk_launches += 1;
-        }
-      }
-      if (!ahead && (rc = record_event(h, sm, "look-ahead", &e_main))) return rc;
-      {  // the bordered rows' share of the REST (columns beyond the next panel); the side rows' whole step — their
-         // panel solve and the update of every column to the right — behind everything the chain waits for
-        PhaseScope ps(h, &h->tm.chol_strip, profile, sm);
-        bordered_block(o, Pc, sm, t0 + nbn, nrest, 0, nxc);
-        if ((rc = side_solve(o, Pc, sm))) return rc;
-        if (o < dc1) {
-          // deferral: the 128-tile rows only in columns [t0, c1) — in the tiles the whole launch would take, so that
-          // those columns receive the same addends bit for bit — and the remainder's launch as it is
-          if (dc1 > t0)
-            launch_gemm_nt_fixed<T>(gemm_nt_tile(128, dna, ntrail, 0), A + (n + nxc) * ld + t0, ld, Pc + (ntrail + nxc) * ldp, ldp,
-                                    Pc, ldp, dna, dc1 - t0, nbp, 0, 0, sm);
-          bordered_block(o, Pc, sm, t0, ntrail, nxc + dna, nxs - dna);
-          if (t0 == dc1) {
-            // B operand: rows [c1, n) of the panels so far are in A once this panel's copy-back is (the copy stream
-            // runs in order).  Temporaries: this panel's buffer, behind its copy-back and behind STRIP_D on the chain;
-            // its next writer, the solve of the panel after next, waits for the next "rows below" event of this stream.
-            if (iw->copied[step & 1]) HIPCHK(h, hipStreamWaitEvent(sm, iw->copied[step & 1], 0));
-            HIPCHK(h, hipStreamWaitEvent(sm, e_stripd, 0));
-            deferred_product(Pc, sm);
-          }
-        } else {
-          bordered_block(o, Pc, sm, t0, ntrail, nxc, nxs);
-        }
-      }
-      set_reserve_mode(0);
-      {
-        PhaseScope ps(h, &h->tm.chol_diag, profile, s1);
-        set_reserve_chain(resv_it > 0 ? env.resv_chain : 0);
-        rc = diag_enqueue(h, A, ld, t0, nbn, Winv, info, gidx0, s1, iw);
-        set_reserve_chain(0);
-        if (rc) return rc;
-      }
-      HIPCHK(h, hipStreamWaitEvent(s1, e_below, 0));
-      // Panel solve p+1: only the rows of the NEXT diagonal block (what STRIP_D(p+1) and the B operands need) on the
-      // chain; the rows below them, and the chain's bordered rows, on the main stream in front of its next update
-      // (their inputs are the main stream's own work plus W_{p+1}) — with the block inverse only.
-      const int64_t top = (iw && top_env) ? std::min<int64_t>(nrest, nb) : nrest;
-      hipEvent_t prev_copied = iw ? iw->copied[(step + 1) & 1] : nullptr;
-      {
-        PhaseScope ps(h, &h->tm.chol_trsm, profile, s1);
-        if (top < nrest || (iw && top_env)) {
-          if ((rc = panel_solve_enqueue(h, A, ld, t0, nbn, top, 0, Winv, Pn, ldp, s1, iw, (step + 1) & 1, 0, prev_copied,
-                                        false)))
-            return rc;
-        } else if ((rc = panel_solve_enqueue(h, A, ld, t0, nbn, nrest, nxc, Winv, Pn, ldp, s1, iw, (step + 1) & 1))) {
-          return rc;
-        }
-      }
-      HIPCHK(h, hipEventRecord(e_panel, s1));
-      HIPCHK(h, hipStreamWaitEvent(sm, e_panel, 0));
-      if (top < nrest || (iw && top_env)) {
-        PhaseScope ps(h, &h->tm.chol_trsm, profile, sm);
-        set_reserve_mode(resv_it);  // runs beside the NEXT diagonal chain
-        rc = panel_solve_enqueue(h, A, ld, t0, nbn, nrest - top, nxc, Winv, Pn, ldp, sm, iw, (step + 1) & 1, top, prev_copied,
-                                 true);
-        set_reserve_mode(0);
-        if (rc) return rc;
-      }
-      continue;
-    }
-    {  // STRIP: rows [t0, n) x cols [t0, t0+nbn), tiles on/below the diagonal
-      PhaseScope ps(h, &h->tm.chol_strip, profile);
-      set_latency_mode(1);  // the strip runs alone (the look-ahead stream waits for it)
-      launch_gemm_nt<T>(tile, A + t0 * ld + t0, ld, Pc, ldp, Pc, ldp, ntrail, nbn, nbp, 2, 0, s0);
-      set_latency_mode(update_is_big(o) ? 0 : 1);
-      // bordered rows [n, n+nx) x all trailing cols: their own small launch, so that the
-      // SYRK grids (and their XCD balance) stay exactly those of the plain factorisation
-      bordered_update(o, Pc, s0);
-    }
-    // the two streams touch the same matrix: an event that cannot be created / recorded /
-    // waited on must fail the call, never let the streams run unordered
-    if ((rc = stream_waits(h, s1, s0, "look-ahead"))) return rc;
-    {  // look-ahead stream: factor diagonal block p+1, solve panel p+1
-      {
-        PhaseScope ps(h, &h->tm.chol_diag, profile, s1);
-        if ((rc = diag_enqueue(h, A, ld, t0, nbn, Winv, info, gidx0, s1, iw))) return rc;
-      }
-      {
-        PhaseScope ps(h, &h->tm.chol_trsm, profile, s1);
-        if ((rc = panel_solve_enqueue(h, A, ld, t0, nbn, nrest, nx, Winv, Pn, ldp, s1, iw, (step + 1) & 1))) return rc;
-      }
-    }
-    HIPCHK(h, hipEventRecord(e_panel, s1));
-    if (nrest > 0) {  // REST: lower triangle of the trailing matrix beyond the strip
-      // the roofline bookkeeping (time, flops, launches) follows ONE kernel, the 128-tile triangular
-      // update; the last few, under-filled updates run as 64-tiles and are booked with the strips
-      const bool big = gemm_nt_tile(tile, nrest, nrest, 1) == 128;
-      PhaseScope ps(h, big ? &h->tm.chol_syrk : &h->tm.chol_strip, profile);
-      launch_gemm_nt<T>(tile, A + (t0 + nbn) * ld + (t0 + nbn), ld, Pc + (int64_t)nbn * ldp, ldp,
-                        Pc + (int64_t)nbn * ldp, ldp, nrest, nrest, nbp, 1, 0, s0);
-      if (big) {
-        h->tm.syrk_flops += (double)nrest * (double)(nrest + 1) * (double)nbp;
-        h->tm.syrk_launches += 1;
-      }
-    }
-    HIPCHK(h, hipStreamWaitEvent(s0, e_panel, 0));
+    rc = c.is_fused(g) ? c.fused_step(g, step, e_panel) : split_env ? c.split_step(g, step, e_panel) : c.lookahead_step(g, step, e_panel);
+    if (rc) return rc;
   }
   if (iw) {  // join the side and copy streams: the last inverse and every panel copy-back are in W / A
     for (hipStream_t sj : {iw->aux, h->st4})
@@ -1171,17 +1226,16 @@ int solve_fwd_enqueue(gpx_handle* h, T* XT, int64_t rows, const T* L, int64_t ld
                       const T* Winv, const SolveWork<T>* wb = nullptr) {
   hipStream_t s0 = h->st, s1 = h->st2;
   const int tile = (rows % 128 == 0) ? 128 : 64;
-  LatencyGuard latency_guard;
-  set_latency_mode(1);  // one stream, nothing beside it; below: until a large update runs beside the block solves
+  const LaunchMode alone{true};  // one stream, nothing beside it; below: until a large update runs beside the block solves
   if (rows < 128 || !s1) {
     for (int64_t o = 0; o < n; o += nb) {
       const int nbp = (int)std::min<int64_t>(nb, n - o);
       launch_trsm_rlt<T>(XT + o, ld, rows, L + o * ld + o, ld, Winv + (o / KB) * (KB * KB), nbp, nullptr,
-                         0, s0);
+                         0, s0, alone);
       const int64_t ntrail = n - (o + nbp);
       if (ntrail > 0)
         launch_gemm_nt<T>((ntrail % 128 == 0) ? tile : 64, XT + o + nbp, ld, XT + o, ld,
-                          L + (o + nbp) * ld + o, ld, rows, ntrail, nbp, 0, 0, s0);
+                          L + (o + nbp) * ld + o, ld, rows, ntrail, nbp, 0, 0, s0, alone);
     }
     return GPX_OK;
   }
@@ -1193,14 +1247,14 @@ int solve_fwd_enqueue(gpx_handle* h, T* XT, int64_t rows, const T* L, int64_t ld
   T* Ts[2] = {dense ? wb->T0 : nullptr, dense ? wb->T1 : nullptr};
   hipEvent_t e_copy[2] = {nullptr, nullptr};
   const int64_t ldt = dense ? wb->ldt : 0;
-  auto block_solve = [&](int64_t o, int nbp, int set, hipStream_t s) -> int {
+  auto block_solve = [&](int64_t o, int nbp, int set, hipStream_t s, LaunchMode lm) -> int {
     if (!dense) {
-      launch_trsm_rlt<T>(XT + o, ld, rows, L + o * ld + o, ld, Winv + (o / KB) * (KB * KB), nbp, nullptr, 0, s);
+      launch_trsm_rlt<T>(XT + o, ld, rows, L + o * ld + o, ld, Winv + (o / KB) * (KB * KB), nbp, nullptr, 0, s, lm);
       return GPX_OK;
     }
     if (e_copy[set]) HIPCHK(h, hipStreamWaitEvent(s, e_copy[set], 0));  // Ts[set] is free again
     launch_gemm_nt<T>((rows % 128 == 0 && nbp % 128 == 0) ? 128 : 64, Ts[set], ldt, XT + o, ld,
-                      wb->W + (o / nb) * (int64_t)nb * nb, nb, rows, nbp, nbp, 4, 1, s);
+                      wb->W + (o / nb) * (int64_t)nb * nb, nb, rows, nbp, nbp, 4, 1, s, lm);
     hipEvent_t e = next_event(h);
     e_copy[set] = next_event(h);
     if (!e || !e_copy[set]) return fail(h, GPX_E_HIP, "hipEventCreate failed (block solve)");
@@ -1211,7 +1265,7 @@ int solve_fwd_enqueue(gpx_handle* h, T* XT, int64_t rows, const T* L, int64_t ld
     return GPX_OK;
   };
   int rc;
-  if ((rc = block_solve(0, (int)std::min<int64_t>(nb, n), 0, s0))) return rc;
+  if ((rc = block_solve(0, (int)std::min<int64_t>(nb, n), 0, s0, alone))) return rc;
   int step = 0;
   for (int64_t o = 0; o < n; o += nb, ++step) {
     const int nbp = (int)std::min<int64_t>(nb, n - o);
@@ -1223,18 +1277,18 @@ int solve_fwd_enqueue(gpx_handle* h, T* XT, int64_t rows, const T* L, int64_t ld
     const int cur = step & 1;
     const T* Ablk = dense ? Ts[cur] : XT + o;  // the solved block o (rows x nbp)
     const int64_t lda = dense ? ldt : ld;
-    set_latency_mode(1);  // the STRIP runs alone: the look-ahead stream waits for it, the previous REST is over
-    launch_gemm_nt<T>(tl, XT + t0, ld, Ablk, lda, L + t0 * ld + o, ld, rows, nbn, nbp, 0, 0, s0);  // STRIP
-    set_latency_mode(nrest > 0 && gemm_nt_tile(tl, rows, nrest, 0) == 128 ? 0 : 1);  // a 128-tile REST runs beside block p+1's solve
+    // the STRIP runs alone: the look-ahead stream waits for it, the previous REST is over
+    launch_gemm_nt<T>(tl, XT + t0, ld, Ablk, lda, L + t0 * ld + o, ld, rows, nbn, nbp, 0, 0, s0, alone);  // STRIP
+    const LaunchMode beside{!(nrest > 0 && gemm_nt_tile(tl, rows, nrest, 0) == 128)};  // a 128-tile REST runs beside block p+1's solve
     hipEvent_t e_strip = next_event(h), e_panel = next_event(h);
     if (!e_strip || !e_panel) return fail(h, GPX_E_HIP, "hipEventCreate failed (look-ahead)");
     HIPCHK(h, hipEventRecord(e_strip, s0));
     HIPCHK(h, hipStreamWaitEvent(s1, e_strip, 0));
-    if ((rc = block_solve(t0, nbn, cur ^ 1, s1))) return rc;
+    if ((rc = block_solve(t0, nbn, cur ^ 1, s1, beside))) return rc;
     HIPCHK(h, hipEventRecord(e_panel, s1));
     if (nrest > 0)  // REST
       launch_gemm_nt<T>(tl, XT + t0 + nbn, ld, Ablk, lda, L + (t0 + nbn) * ld + o, ld, rows, nrest, nbp, 0, 0,
-                        s0);
+                        s0, beside);
     HIPCHK(h, hipStreamWaitEvent(s0, e_panel, 0));
   }
   if (dense) {  // every block is back in XT

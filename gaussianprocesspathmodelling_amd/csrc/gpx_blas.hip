@@ -1082,19 +1082,8 @@ int64_t rect_grid(int64_t tm, int64_t tn, int& sh) {
 // co-resident pair.  Matters for the panel / block solves and the strips of small
 // problems (BASELINE.json configs[1]); large launches are unaffected.
 // see launch_gemm_nt_t: several k-steps per barrier for 64-tile launches, only when the caller says that
-// nothing large runs beside them (per host thread: a handle is driven by one thread at a time)
-thread_local int g_latency_mode = 0;
-// reserve mode of the calling host thread (set_reserve_mode): k > 0 — the launches of launch_gemm_nt go out in their
-// self-reserving form, each with 8 zeroed device counters of its own out of the caller's ring
-struct ReserveState {
-  int k = 0;
-  unsigned* ring = nullptr;  // [cap][8] counters, zeroed by the caller before the first launch of a fit
-  int cap = 0, used = 0;
-  int form = 1;              // grid of the self-reserving launches: 1 turnover, 0 persistent (GPX_RESV_FORM; launch_gemm_nt_t)
-  int chain = 0;             // narrow slab launches of the chain ask for a whole CU's worth of LDS (see launch_trsm_rlt)
-};
-thread_local ReserveState g_resv;
-
+// nothing large runs beside them (LaunchMode::latency); with lm.resv_k > 0 and a ring the launch goes out in its
+// self-reserving form, with 8 zeroed device counters of its own out of the caller's ring
 inline int cu_count() {
   static const int n = [] {
     int dev = 0, v = 0;
@@ -1108,7 +1097,7 @@ inline int cu_count() {
 
 template <typename T, int BT>
 void launch_gemm_nt_t(T* C, int64_t ldc, const T* A, int64_t lda, const T* B, int64_t ldb, int64_t m,
-                      int64_t n, int64_t k, int lower, int mode, BcMask bc, hipStream_t st) {
+                      int64_t n, int64_t k, int lower, int mode, BcMask bc, hipStream_t st, LaunchMode lm) {
   const int64_t tm = m / BT, tn = n / BT;
   dim3 block(256);
   const int64_t live = lower == 1   ? tm * (tm + 1) / 2
@@ -1121,18 +1110,19 @@ void launch_gemm_nt_t(T* C, int64_t ldc, const T* A, int64_t lda, const T* B, in
   // tiles lets the LDS afford — up to one tile per CU: 4 (fp64; 128 KB, one workgroup per CU anyway), up to
   // four per CU: 2 (64 KB, two workgroups per CU), beyond that the plain engine at four workgroups per CU,
   // whose occupancy hides the latency.  k is a multiple of 64 inside the library.
-  // ONLY in latency mode (set_latency_mode: the caller knows that no large update runs beside this launch):
+  // ONLY in latency mode (lm.latency: the caller knows that no large update runs beside this launch):
   // under a 128-tile trailing update a 64-tile workgroup must fit BESIDE the two resident update workgroups
   // (2 x 64 KB of the CU's 160 KB: 32 KB is all that is left) — with 64 or 128 KB it waits for a CU to drain,
   // and at N = 65536 the chain's kernels then took 6x as long (measured: 1242 ms of chain instead of 214).
   int ks = 1;
-  if (BT == 64 && g_latency_mode) {
+  if (BT == 64 && lm.latency) {
     if (live <= 4 * cu_count() && k % (2 * Num<T>::BK) == 0) ks = 2;
     if (Num<T>::KS64 == 4 && live <= cu_count() && k % (4 * Num<T>::BK) == 0) ks = 4;
   }
   // self-reserving form?  (block-cyclic masks never: the sharded update has its own kernel)
   unsigned* rctr = nullptr;
-  if (g_resv.k > 0 && bc.P == 0 && lower != 3 && g_resv.used < g_resv.cap) rctr = g_resv.ring + 8 * (size_t)g_resv.used++;
+  const int resv_k = lm.ring ? lm.resv_k : 0;
+  if (resv_k > 0 && bc.P == 0 && lower != 3 && lm.ring->used < lm.ring->cap) rctr = lm.ring->ctr + 8 * (size_t)lm.ring->used++;
   // persistent grid: the chip's slots for this kernel (two 64 KB workgroups per CU; 64-tiles: up to four) plus what
   // the reserved CUs burn (their workgroups exit at once and the dispatcher refills those slots)
   // Two forms (GPX_RESV_FORM).  1, "turnover" (default): one tile per workgroup as in the static launch — slots keep
@@ -1141,17 +1131,17 @@ void launch_gemm_nt_t(T* C, int64_t ldc, const T* A, int64_t lda, const T* B, in
   // once there) and a tail of persistent "sweepers" that finish whatever the burnt ones left.  0, "persistent": about
   // as many workgroups as the chip has slots, all looping (measured: the chain's wide launches then only get the
   // reserved CUs until the update retires — C2 13.3 against 12.5 ms).
-  const int form = g_resv.form;
+  const int form = lm.ring ? lm.ring->form : 1;
   unsigned sweep0 = 0;
   auto resv_grid = [&](int64_t total) {
     const int per_cu = BT == 128 ? 2 : (ks == 4 ? 1 : ks == 2 ? 2 : 4);
     const int64_t slots = (int64_t)cu_count() * per_cu;
     if (form == 0) {
       sweep0 = 0;
-      return dim3((unsigned)(std::min<int64_t>(total, slots) + 64 * g_resv.k));
+      return dim3((unsigned)(std::min<int64_t>(total, slots) + 64 * resv_k));
     }
     const int64_t sweepers = std::min<int64_t>(total, slots / 2);
-    const int64_t ones = total - sweepers + 256 * g_resv.k;  // one-tile workgroups incl. what the reserved CUs will burn
+    const int64_t ones = total - sweepers + 256 * resv_k;  // one-tile workgroups incl. what the reserved CUs will burn
     sweep0 = (unsigned)ones;
     return dim3((unsigned)(ones + sweepers));
   };
@@ -1162,13 +1152,13 @@ void launch_gemm_nt_t(T* C, int64_t ldc, const T* A, int64_t lda, const T* B, in
       const dim3 pg_ = resv_grid(total_);                                                                                      \
       if (ks == 4)                                                                                                             \
         hipLaunchKernelGGL((gemm_nt_resv_kernel<T, BT, TRI_, MODE_, (BT == 64 ? 4 : 1)>), pg_, block, 0, st, C, ldc, A, lda,   \
-                           B, ldb, (int)tm, (int)tn, SH_, MASK_, (int)k, total_, rctr, g_resv.k, sweep0);                              \
+                           B, ldb, (int)tm, (int)tn, SH_, MASK_, (int)k, total_, rctr, resv_k, sweep0);                              \
       else if (ks == 2)                                                                                                        \
         hipLaunchKernelGGL((gemm_nt_resv_kernel<T, BT, TRI_, MODE_, (BT == 64 ? 2 : 1)>), pg_, block, 0, st, C, ldc, A, lda,   \
-                           B, ldb, (int)tm, (int)tn, SH_, MASK_, (int)k, total_, rctr, g_resv.k, sweep0);                              \
+                           B, ldb, (int)tm, (int)tn, SH_, MASK_, (int)k, total_, rctr, resv_k, sweep0);                              \
       else                                                                                                                     \
         hipLaunchKernelGGL((gemm_nt_resv_kernel<T, BT, TRI_, MODE_, 1>), pg_, block, 0, st, C, ldc, A, lda, B, ldb, (int)tm,   \
-                           (int)tn, SH_, MASK_, (int)k, total_, rctr, g_resv.k, sweep0);                                               \
+                           (int)tn, SH_, MASK_, (int)k, total_, rctr, resv_k, sweep0);                                               \
     } else if (ks == 4)                                                                                                        \
       hipLaunchKernelGGL((gemm_nt_kernel<T, BT, TRI_, MODE_, (BT == 64 ? 4 : 1)>), grid, block, spread, st, C, ldc, A, lda, B, \
                          ldb, (int)tm, (int)tn, SH_, MASK_, bc, (int)k);                                                       \
@@ -1193,11 +1183,11 @@ void launch_gemm_nt_t(T* C, int64_t ldc, const T* A, int64_t lda, const T* B, in
       const unsigned total_ = grid.x;
       const dim3 pg_ = resv_grid(total_);
       if (ks == 4)
-        hipLaunchKernelGGL((gemm_nt_ltri_resv_kernel<T, BT, (BT == 64 ? 4 : 1)>), pg_, block, 0, st, C, ldc, A, lda, B, ldb, (int)tm, (int)tn, sh, (int)k, total_, rctr, g_resv.k, sweep0);
+        hipLaunchKernelGGL((gemm_nt_ltri_resv_kernel<T, BT, (BT == 64 ? 4 : 1)>), pg_, block, 0, st, C, ldc, A, lda, B, ldb, (int)tm, (int)tn, sh, (int)k, total_, rctr, resv_k, sweep0);
       else if (ks == 2)
-        hipLaunchKernelGGL((gemm_nt_ltri_resv_kernel<T, BT, (BT == 64 ? 2 : 1)>), pg_, block, 0, st, C, ldc, A, lda, B, ldb, (int)tm, (int)tn, sh, (int)k, total_, rctr, g_resv.k, sweep0);
+        hipLaunchKernelGGL((gemm_nt_ltri_resv_kernel<T, BT, (BT == 64 ? 2 : 1)>), pg_, block, 0, st, C, ldc, A, lda, B, ldb, (int)tm, (int)tn, sh, (int)k, total_, rctr, resv_k, sweep0);
       else
-        hipLaunchKernelGGL((gemm_nt_ltri_resv_kernel<T, BT, 1>), pg_, block, 0, st, C, ldc, A, lda, B, ldb, (int)tm, (int)tn, sh, (int)k, total_, rctr, g_resv.k, sweep0);
+        hipLaunchKernelGGL((gemm_nt_ltri_resv_kernel<T, BT, 1>), pg_, block, 0, st, C, ldc, A, lda, B, ldb, (int)tm, (int)tn, sh, (int)k, total_, rctr, resv_k, sweep0);
     } else if (ks == 4)
       hipLaunchKernelGGL((gemm_nt_ltri_kernel<T, BT, (BT == 64 ? 4 : 1)>), grid, block, spread, st, C, ldc, A, lda, B, ldb, (int)tm, (int)tn, sh, (int)k);
     else if (ks == 2)
@@ -1220,18 +1210,6 @@ void launch_gemm_nt_t(T* C, int64_t ldc, const T* A, int64_t lda, const T* B, in
 
 // A launcher that refuses its operands (the 128-byte row alignment trsm_rlt_kernel depends on)
 // launches nothing and raises this flag; every API entry point turns it into an error return.
-void set_latency_mode(int on) { g_latency_mode = on; }
-void reserve_ring(unsigned* ring, int cap, int form) {
-  g_resv.ring = ring;
-  g_resv.form = form;
-  g_resv.cap = ring ? cap : 0;
-  g_resv.used = 0;
-  g_resv.k = 0;
-  g_resv.chain = 0;
-}
-void set_reserve_mode(int k) { g_resv.k = g_resv.ring ? k : 0; }
-void set_reserve_chain(int on) { g_resv.chain = g_resv.ring ? on : 0; }
-
 static thread_local int g_launch_error = 0;  // per host thread = per API call in flight (a handle is used by one thread at a time)
 int take_launch_error() {
   const int e = g_launch_error;
@@ -1248,13 +1226,13 @@ void launch_potf2_64(T* A, int64_t lda, T* Winv, int64_t gidx0, int* info, hipSt
 
 template <typename T>
 void launch_potf2_128(T* A, int64_t lda, T* Winv, int64_t gidx0, int* info, hipStream_t st, unsigned* flag,
-                      unsigned flag_val) {
+                      unsigned flag_val, LaunchMode lm) {
   debug_delay(st);
   // Reserve mode, chain side: the POTF2 asks for so much LDS (130 KB in all) that no CU holding even ONE update workgroup
   // (32 KB at least) can take it — it lands on a CU the self-reserving update leaves alone, where its fp64 vector work has
   // the double-precision pipe to itself.  (Small-LDS kernels — the side stream's slabs — may still share that CU.)
   unsigned pad = 0;
-  if (g_resv.chain) {
+  if (lm.ring && lm.resv_chain) {
     static const unsigned pad130 = [] {
       hipFuncAttributes fa;
       if (hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(potf2_128_kernel<T>)) != hipSuccess) return 0u;
@@ -1273,7 +1251,7 @@ void launch_potf2_128(T* A, int64_t lda, T* Winv, int64_t gidx0, int* info, hipS
 
 template <typename T>
 void launch_trsm_rlt(T* X, int64_t ldx, int64_t rows, const T* L, int64_t ldl, const T* Winv, int nb,
-                     T* P, int64_t ldp, hipStream_t st) {
+                     T* P, int64_t ldp, hipStream_t st, LaunchMode lm) {
   debug_delay(st);
   // the kernel's L1 invariant (see trsm_rlt_kernel): 128-byte aligned rows of X.  Every caller
   // builds ldx from ld_skew<T>(); a violation is a programming error in this library, caught
@@ -1286,7 +1264,7 @@ void launch_trsm_rlt(T* X, int64_t ldx, int64_t rows, const T* L, int64_t ldl, c
   // per barrier; many slabs: the plain engine, whose occupancy hides the latency
   // (reserve mode, chain side: a narrow slab launch takes the KS64 form too — 128 KB of LDS per workgroup, which only an
   // empty CU holds, i.e. one the self-reserving update leaves alone)
-  if ((g_latency_mode && rows / 64 <= cu_count()) || (g_resv.chain > 1 && rows / 64 <= 16))
+  if ((lm.latency && rows / 64 <= cu_count()) || (lm.ring && lm.resv_chain > 1 && rows / 64 <= 16))
     hipLaunchKernelGGL((trsm_rlt_kernel<T, Num<T>::KS64>), dim3((unsigned)(rows / 64)), dim3(256), 0, st, X, ldx, L, ldl,
                        Winv, 0, nb / 64, P, ldp, 0, (T*)nullptr, (int64_t)0, 0);
   else
@@ -1296,7 +1274,7 @@ void launch_trsm_rlt(T* X, int64_t ldx, int64_t rows, const T* L, int64_t ldl, c
 
 template <typename T>
 void launch_inv_extend(T* U, int64_t ldu, const T* L, int64_t ldl, const T* Winv, int q0, int q1, T* W,
-                       int64_t ldw, hipStream_t st, int phase) {
+                       int64_t ldw, hipStream_t st, int phase, LaunchMode lm) {
   debug_delay(st);
   if (((uintptr_t)U | (uintptr_t)(ldu * (int64_t)sizeof(T))) % 128 != 0) {
     g_launch_error = 1;
@@ -1305,7 +1283,7 @@ void launch_inv_extend(T* U, int64_t ldu, const T* L, int64_t ldl, const T* Winv
   if (phase == 1 && q0 == 0) return;  // nothing lies left of the first block
   // "pre": only the slabs that start left of block q0 have work, one workgroup per (slab, block)
   const dim3 grid = phase == 1 ? dim3((unsigned)q0, (unsigned)(q1 - q0)) : dim3((unsigned)q1);
-  if (g_latency_mode)
+  if (lm.latency)
     hipLaunchKernelGGL((trsm_rlt_kernel<T, Num<T>::KS64>), grid, dim3(256), 0, st, U, ldu, L, ldl, Winv, q0, q1,
                        (T*)nullptr, (int64_t)0, 1, W, ldw, phase);
   else
@@ -1343,14 +1321,14 @@ void launch_gemm_nt_splitk(T* C, int64_t ldc, const T* A, int64_t lda, const T* 
 
 template <typename T>
 void launch_gemm_nt_fixed(int tile, T* C, int64_t ldc, const T* A, int64_t lda, const T* B, int64_t ldb,
-                          int64_t m, int64_t n, int64_t k, int lower, int mode, hipStream_t st) {
+                          int64_t m, int64_t n, int64_t k, int lower, int mode, hipStream_t st, LaunchMode lm) {
   debug_delay(st);
   if (m <= 0 || n <= 0) return;
   const BcMask bc{0, 1, 0};
   if (tile == 128)
-    launch_gemm_nt_t<T, 128>(C, ldc, A, lda, B, ldb, m, n, k, lower, mode, bc, st);
+    launch_gemm_nt_t<T, 128>(C, ldc, A, lda, B, ldb, m, n, k, lower, mode, bc, st, lm);
   else
-    launch_gemm_nt_t<T, 64>(C, ldc, A, lda, B, ldb, m, n, k, lower, mode, bc, st);
+    launch_gemm_nt_t<T, 64>(C, ldc, A, lda, B, ldb, m, n, k, lower, mode, bc, st, lm);
 }
 
 // The library's own products: `tile` is the largest tile the shape allows; a 128-tile grid that
@@ -1374,8 +1352,8 @@ int gemm_nt_tile(int tile, int64_t m, int64_t n, int lower) {
 
 template <typename T>
 void launch_gemm_nt(int tile, T* C, int64_t ldc, const T* A, int64_t lda, const T* B, int64_t ldb,
-                    int64_t m, int64_t n, int64_t k, int lower, int mode, hipStream_t st) {
-  launch_gemm_nt_fixed<T>(gemm_nt_tile(tile, m, n, lower), C, ldc, A, lda, B, ldb, m, n, k, lower, mode, st);
+                    int64_t m, int64_t n, int64_t k, int lower, int mode, hipStream_t st, LaunchMode lm) {
+  launch_gemm_nt_fixed<T>(gemm_nt_tile(tile, m, n, lower), C, ldc, A, lda, B, ldb, m, n, k, lower, mode, st, lm);
 }
 
 // ---- C -= A B^T with one or two Strassen levels (Strassen 1969: seven half-size products instead of eight) ----------
@@ -1414,13 +1392,14 @@ size_t strassen_temp2_elems(int64_t m, int64_t n, int64_t k) {
 
 template <typename T>
 double strassen_nt(T* C, int64_t ldc, const T* A, int64_t lda, const T* B, int64_t ldb, int64_t m, int64_t n,
-                   int64_t k, T* TA, T* TB, int64_t ldt, hipStream_t st, const StrassenL2<T>* l2, bool* two_levels) {
+                   int64_t k, T* TA, T* TB, int64_t ldt, hipStream_t st, const StrassenL2<T>* l2, bool* two_levels,
+                   LaunchMode lm) {
   if (two_levels) *two_levels = false;
   constexpr int64_t K2 = 2 * Num<T>::BK, VE = 16 / sizeof(T);
   const int64_t m0 = m / 256 * 256, n0 = n / 256 * 256, k0 = k / K2 * K2;
   auto classical = [&](T* Cc, const T* Ac, const T* Bc, int64_t mm, int64_t nn, int64_t kk) {
     if (mm <= 0 || nn <= 0 || kk <= 0) return;
-    launch_gemm_nt<T>((mm % 128 == 0 && nn % 128 == 0) ? 128 : 64, Cc, ldc, Ac, lda, Bc, ldb, mm, nn, kk, 0, 0, st);
+    launch_gemm_nt<T>((mm % 128 == 0 && nn % 128 == 0) ? 128 : 64, Cc, ldc, Ac, lda, Bc, ldb, mm, nn, kk, 0, 0, st, lm);
   };
   auto aligned = [](const void* p, int64_t ld) { return (uintptr_t)p % 16 == 0 && ld % VE == 0; };
   const bool level = m0 > 0 && n0 > 0 && k0 > 0 && TA && TB && ldt >= k0 / 2 && aligned(A, lda) && aligned(B, ldb) &&
@@ -1548,7 +1527,7 @@ void launch_gemm_nt_bc(T* C, int64_t ldc, const T* A, int64_t lda, const T* B, i
   const int64_t tm = m / 128, tn = n / 128;
   const int64_t nsr = (tm + 7) / 8;
   if (nsr > STAIR_MAX) {  // beyond the by-value map: bounding rectangle with the mask
-    launch_gemm_nt_t<T, 128>(C, ldc, A, lda, B, ldb, m, n, k, 3, 0, bc, st);
+    launch_gemm_nt_t<T, 128>(C, ldc, A, lda, B, ldb, m, n, k, 3, 0, bc, st, LaunchMode{});
     return;
   }
   StairMap map;
@@ -1630,16 +1609,17 @@ extern "C" int gpx_debug_read_syrk_clock(long long* out) {
 
 #define GPX_INSTANTIATE_BLAS(T)                                                                         \
   template void launch_potf2_64<T>(T*, int64_t, T*, int64_t, int*, hipStream_t, unsigned*, unsigned);   \
-  template void launch_potf2_128<T>(T*, int64_t, T*, int64_t, int*, hipStream_t, unsigned*, unsigned);  \
+  template void launch_potf2_128<T>(T*, int64_t, T*, int64_t, int*, hipStream_t, unsigned*, unsigned,   \
+                                    LaunchMode);                                                        \
   template void launch_trsm_rlt<T>(T*, int64_t, int64_t, const T*, int64_t, const T*, int, T*, int64_t, \
-                                   hipStream_t);                                                        \
+                                   hipStream_t, LaunchMode);                                            \
   template void launch_trsm_rln<T>(T*, int64_t, int64_t, const T*, int64_t, const T*, int, hipStream_t); \
   template void launch_inv_extend<T>(T*, int64_t, const T*, int64_t, const T*, int, int, T*, int64_t,   \
-                                     hipStream_t, int);                                                 \
+                                     hipStream_t, int, LaunchMode);                                     \
   template void launch_gemm_nt<T>(int, T*, int64_t, const T*, int64_t, const T*, int64_t, int64_t,      \
-                                  int64_t, int64_t, int, int, hipStream_t);                             \
+                                  int64_t, int64_t, int, int, hipStream_t, LaunchMode);                 \
   template void launch_gemm_nt_fixed<T>(int, T*, int64_t, const T*, int64_t, const T*, int64_t, int64_t, \
-                                        int64_t, int64_t, int, int, hipStream_t);                       \
+                                        int64_t, int64_t, int, int, hipStream_t, LaunchMode);           \
   template unsigned launch_gemm_nt_fused<T>(T*, int64_t, const T*, int64_t, int64_t, int64_t, int64_t,  \
                                             unsigned*, hipStream_t);                                    \
   template void launch_gemm_nt_bc<T>(T*, int64_t, const T*, int64_t, const T*, int64_t, int64_t,        \
@@ -1647,7 +1627,8 @@ extern "C" int gpx_debug_read_syrk_clock(long long* out) {
   template void launch_gemm_nn<T>(T*, int64_t, const T*, int64_t, const T*, int64_t, int64_t, int64_t,  \
                                   int64_t, hipStream_t);                                                \
   template double strassen_nt<T>(T*, int64_t, const T*, int64_t, const T*, int64_t, int64_t, int64_t,   \
-                                 int64_t, T*, T*, int64_t, hipStream_t, const StrassenL2<T>*, bool*);   \
+                                 int64_t, T*, T*, int64_t, hipStream_t, const StrassenL2<T>*, bool*,    \
+                                 LaunchMode);                                                           \
   template size_t strassen_temp2_elems<T>(int64_t, int64_t, int64_t);                                   \
   template void launch_gemm_nt_splitk<T>(T*, int64_t, const T*, int64_t, const T*, int64_t, int64_t,    \
                                          int64_t, int64_t, int, T*, int64_t, hipStream_t);

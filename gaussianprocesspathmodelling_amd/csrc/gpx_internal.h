@@ -139,6 +139,27 @@ void launch_kbuild_cross_g(int kernel, const T* As, const int32_t* group_a, int6
                            T* K, int64_t ld, hipStream_t st);
 
 // ---- dense blocks (gpx_blas.hip) ---------------------------------------------------
+// How a launch goes out — the last argument of the launchers below that have variants (default: the plain kernels).
+// Nothing is remembered between launches: what a launch gets is what its call site says.
+struct ReserveRing {  // [cap][8] device counters, owned by the factorisation that zeroed them (gemm_nt_resv_kernel in gpx_blas.hip)
+  unsigned* ctr = nullptr;
+  int cap = 0, used = 0;  // launches beyond cap are the plain kernels
+  int form = 1;           // grid of the self-reserving launches: 1 turnover, 0 persistent (GPX_RESV_FORM)
+};
+struct LaunchMode {
+  // The caller knows nothing large runs beside this launch: the 64-tile launches (launch_gemm_nt with an under-filled
+  // 128-grid, launch_trsm_rlt / launch_inv_extend with few slabs) then stage several k-steps per barrier — 64 or 128 KB
+  // of LDS per workgroup instead of 32 — which shortens every latency-bound K walk when the GPU is otherwise idle and
+  // must NOT be used beside a large trailing update (see gpx_blas.hip).
+  bool latency = false;
+  // > 0 (round 4), with a ring: the products of launch_gemm_nt go out as persistent grids whose workgroups leave resv_k
+  // CUs per XCD alone (they exit at once there) and take their tiles from the next 8 counters of *ring.
+  int resv_k = 0;
+  // with a ring, the chain's side (GPX_RESV_CHAIN): != 0 — launch_potf2_128 asks for 130 KB of LDS; > 1 — the narrow slab
+  // launches too (launch_trsm_rlt, <= 16 slabs) ask for a whole CU's LDS, so that they land on the CUs the update leaves alone.
+  int resv_chain = 0;
+  ReserveRing* ring = nullptr;  // null: resv_k and resv_chain count for nothing
+};
 // In-place Cholesky of one 64x64 diagonal block (lower) + its inverse Winv (64x64,
 // row-major, upper part zero).  gidx0 = global index of the block's first row (info).
 template <typename T>
@@ -151,36 +172,21 @@ void launch_potf2_64(T* A, int64_t lda, T* Winv, int64_t gidx0, int* info, hipSt
 // on launch_wait_counter(flag, flag_val) waits for.
 template <typename T>
 void launch_potf2_128(T* A, int64_t lda, T* Winv, int64_t gidx0, int* info, hipStream_t st, unsigned* flag = nullptr,
-                      unsigned flag_val = 0);
+                      unsigned flag_val = 0, LaunchMode lm = {});
 // X (rows x nb, ldx) <- X * L^-T; L (nb x nb, ldl) lower, Winv = nb/64 inverse diag
 // blocks.  rows, nb multiples of 64.  If P != null the result is also written to the
 // compact panel P (rows x nb, ldp).
 template <typename T>
 void launch_trsm_rlt(T* X, int64_t ldx, int64_t rows, const T* L, int64_t ldl, const T* Winv, int nb,
-                     T* P, int64_t ldp, hipStream_t st);
+                     T* P, int64_t ldp, hipStream_t st, LaunchMode lm = {});
 // Building the explicit inverse of a diagonal block L (nbw x nbw, ldl) next to its
 // factorisation: U (ldu) holds (L^-1)^T column blocks [0, q0) already and the identity elsewhere;
 // this solves column blocks [q0, q1) of U for row blocks 0..q1-1 and writes them transposed into
 // row blocks [q0, q1) of W = L^-1 (ldw).  Needs the 64-block inverses and rows of L up to q1.
 template <typename T>
 void launch_inv_extend(T* U, int64_t ldu, const T* L, int64_t ldl, const T* Winv, int q0, int q1, T* W,
-                       int64_t ldw, hipStream_t st, int phase = 0);  // 0 whole, 1 "pre" (left of block q0 only), 2 "post"
-// Latency mode of the calling host thread (default off): the 64-tile launches (launch_gemm_nt with an
-// under-filled 128-grid, launch_trsm_rlt / launch_inv_extend with few slabs) then stage several k-steps per
-// barrier — 64 or 128 KB of LDS per workgroup instead of 32 — which shortens every latency-bound K walk
-// when the GPU is otherwise idle and must NOT be used beside a large trailing update (see gpx_blas.hip).
-void set_latency_mode(int on);
-// Reserve mode of the calling host thread (round 4; gemm_nt_resv_kernel in gpx_blas.hip).
-// reserve_ring(ring, cap, form): start of a factorisation — `ring` = [cap][8] device counters the caller has zeroed (null:
-//   off); form = grid of the self-reserving launches, 1 turnover / 0 persistent (GPX_RESV_FORM).
-// set_reserve_mode(k): k > 0 — the products launch_gemm_nt enqueues from now on go out as persistent grids whose
-//   workgroups leave k CUs per XCD alone (they exit at once there) and take their tiles from the next 8 counters of
-//   the ring; launches beyond cap, and k = 0, are the plain kernels.
-// set_reserve_chain(1): the chain's narrow slab launches (launch_trsm_rlt, <= 16 slabs) ask for a whole CU's LDS, so
-//   that they land on the CUs the update leaves alone.
-void reserve_ring(unsigned* ring, int cap, int form = 1);
-void set_reserve_mode(int k);
-void set_reserve_chain(int on);
+                       int64_t ldw, hipStream_t st, int phase = 0,  // 0 whole, 1 "pre" (left of block q0 only), 2 "post"
+                       LaunchMode lm = {});
 // 1 if a launcher CALLED BY THIS HOST THREAD since the last call refused misaligned operands (and launched nothing);
 // clears the flag.  Thread-local: an API call enqueues and checks on one thread, so a handle only ever sees its own
 // launches' errors (distinct handles on distinct threads: include/gpx.h)
@@ -197,13 +203,13 @@ void launch_trsm_rln(T* X, int64_t ldx, int64_t rows, const T* L, int64_t ldl, c
 //   tile = 128 (m,n multiples of 128) or 64 (multiples of 64); k multiple of 64.
 template <typename T>
 void launch_gemm_nt(int tile, T* C, int64_t ldc, const T* A, int64_t lda, const T* B, int64_t ldb,
-                    int64_t m, int64_t n, int64_t k, int lower, int mode, hipStream_t st);
+                    int64_t m, int64_t n, int64_t k, int lower, int mode, hipStream_t st, LaunchMode lm = {});
 // the tile size launch_gemm_nt really uses for (tile, m, n, lower): 64 when the 128-grid is under-filled
 int gemm_nt_tile(int tile, int64_t m, int64_t n, int lower);
 // the same with the tile size taken literally (unit-test entry point, engine benchmark)
 template <typename T>
 void launch_gemm_nt_fixed(int tile, T* C, int64_t ldc, const T* A, int64_t lda, const T* B, int64_t ldb,
-                    int64_t m, int64_t n, int64_t k, int lower, int mode, hipStream_t st);
+                    int64_t m, int64_t n, int64_t k, int lower, int mode, hipStream_t st, LaunchMode lm = {});
 // C (m x n) -= A B^T with one Strassen level on the part with m, n multiples of 256 (gpx_blas.hip: the order of its
 // launches, and why the result is repeatable bit for bit); m, n multiples of 64, k a multiple of the k-step.  TA | TB:
 // strassen_temp_elems(m, n, k, skew) elements, TB = TA + (m / 256 * 128) * ldt, ldt = k / 2 + skew.  Null temporaries,
@@ -211,6 +217,7 @@ void launch_gemm_nt_fixed(int tile, T* C, int64_t ldc, const T* A, int64_t lda, 
 // l2 (optional): the seven products take a second level where their own quadrants are at least l2->min2 rows and columns
 // (GPX_STRASSEN_MIN_TWO) and l2->buf holds strassen_temp2_elems<T>(m, n, k) of l2->elems elements; otherwise — null, min2 = 0,
 // no or too small a buffer — exactly the one-level launches.  *two_levels (optional) says whether it ran.
+// lm reaches the classical launches only (the no-level fallback and the three peeled parts), not the level's products.
 size_t strassen_temp_elems(int64_t m, int64_t n, int64_t k, int skew);
 template <typename T>
 size_t strassen_temp2_elems(int64_t m, int64_t n, int64_t k);
@@ -223,7 +230,7 @@ struct StrassenL2 {
 template <typename T>
 double strassen_nt(T* C, int64_t ldc, const T* A, int64_t lda, const T* B, int64_t ldb, int64_t m, int64_t n,
                    int64_t k, T* TA, T* TB, int64_t ldt, hipStream_t st, const StrassenL2<T>* l2 = nullptr,
-                   bool* two_levels = nullptr);
+                   bool* two_levels = nullptr, LaunchMode lm = {});
 // The whole trailing update of a panel in one launch: C (n x n, 128-tiles, lower) -= P P^T (P: n x k, ldp)
 // with the first ns columns (the strip that becomes the next panel) enumerated first; every strip slot
 // adds 1 to *ctr once its tile is released at device scope.  Returns the number of strip slots.

@@ -31,7 +31,7 @@ pytestmark = pytest.mark.gpu
 
 SF2, SN2, LS, M = 1.5, 1e-2, 0.25, 300
 SWITCHES = ("GPX_TWO_LEVEL_FROM", "GPX_STRASSEN_MIN", "GPX_STRASSEN_DIAG", "GPX_STRASSEN_SINGLE", "GPX_NB_WIDE_FROM",
-            "GPX_NB_PRED", "GPX_DEFER_LEFT")
+            "GPX_NB_PRED", "GPX_DEFER_LEFT", "GPX_CU_SELF_RESERVE")
 STRASSEN = {"GPX_TWO_LEVEL_FROM": "1024", "GPX_STRASSEN_MIN": "128"}
 SPLIT = {"GPX_TWO_LEVEL_FROM": "1024", "GPX_STRASSEN_MIN": "0"}
 OFF, ON = {"GPX_DEFER_LEFT": "0"}, {"GPX_DEFER_LEFT": "1"}
@@ -184,6 +184,19 @@ def test_classical_deferred_fit_matches_the_oracle():
     N, _, _, _, c, c1 = CASES["n2900_b512"]
     check_structure("n2900_b512 classical", fit_run("n2900_b512", {**SPLIT, **OFF})["L"],
                     fit_run("n2900_b512", {**SPLIT, **ON})["L"], reference(N)["L"], N, c, c1)
+
+
+@pytest.mark.parametrize("k", [1, 4])
+def test_self_reserving_launches_give_the_same_deferred_fit(k):
+    """GPX_CU_SELF_RESERVE=k reaches the deferred product: at n2900_b512 strassen_nt peels 128 rows off through the
+    classical launch, which then goes out in its self-reserving form (with rest_split / 2 = 8 every panel of phase 1 is
+    chain-bound, so the reserve mode is on throughout).  The same arithmetic per tile under another launch geometry:
+    bit-identical to the plain launches, as test_schedule_variants_give_the_same_factorisation asserts for the one-level
+    fit."""
+    a = fit_run("n2900_b512", {**STRASSEN, **ON})
+    b = fit_run("n2900_b512", {**STRASSEN, **ON, "GPX_CU_SELF_RESERVE": str(k)})
+    for q in ("L", "mean", "var", "alpha"):
+        assert np.array_equal(a[q], b[q]), q
 
 
 def test_deferred_fit_is_repeatable_bit_for_bit():
