@@ -127,6 +127,10 @@ SIGNATURES = {
     "gpx_sparse_elbo": (C.c_int, [_P, _PD]),
     "gpx_sparse_info": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                   C.POINTER(C.c_int64)]),
+    "gpx_sparse_elbo_grad": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int32, _PD, _PD]),
+    "gpx_cross_dtheta_contract": (C.c_int, [C.c_int32, _PD, C.c_int64, _PD, C.c_int64, C.c_int32, _PD, _PD, C.c_int32,
+                                            C.c_double, _PD]),
+    "gpx_debug_cross_dtheta_bench": (C.c_int, [C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _PD]),
     "gpx_syrk_tn": (C.c_int, [_PD, C.c_int64, _PD, C.c_int64, C.c_int32]),
     "gpx_debug_syrk_tn_bench": (C.c_int, [C.c_int64, C.c_int64, C.c_int32, C.c_int32, _PD]),
     "gpx_logdet": (C.c_int, [_P, _PD]),

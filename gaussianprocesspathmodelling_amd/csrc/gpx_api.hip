@@ -132,6 +132,8 @@ struct gpx_handle {
     DevBuf UW, UQ;  // gpx_remove_rows: per pass in flight (two) the carry ((N + 64) x UPD_W) and the panel's orthogonal factor (2 UPD_W square)
     DevBuf LOO;     // gpx_loo: q (N) | var (N) | mean (N x k) | logp (N x k), fp64
     DevBuf SV1, SV2, SS2;  // gpx_sparse_predict(_cov): T1^T and T2^T of one batch of query rows; T2^T T2
+    // gpx_sparse_elbo_grad: [H | ch^T], LB^-T -> LB -> L^-T M, M -> Guu, L^-T, H' = L^-T [H | ch], a chunk of T, partials + sums
+    DevBuf SGH, SGZ, SGM, SGZL, SGHp, SGT, SGpart;
     DevBuf PWZ, PWpart, PWout, PWres;  // gpx_pathwise_*: a host caller's normals, the splits' partials, OutT of one batch, results for a host caller
   } scr;
   // row-block shard (world > 1)
@@ -212,6 +214,7 @@ struct gpx_handle {
     bool fitted = false;
     int64_t N = 0, m = 0, mpad = 0, chunk = 0, ld = 0;
     double elbo[8] = {};
+    double sum_inv_s2 = 0;    // sum_n 1 / s_n^2 of the fit's observations (the gradient's sf2 and sn2 entries)
     DevBuf Z, Zs;             // inducing points: raw (m x d), scaled (mpad x d)
     DevBuf L, WinvL;          // chol(Kuu) and its 64-block inverses
     DevBuf B, WinvB;          // chol(I + A A^T) with c^T as bordered rows [mpad, mpad + 64), and its 64-block inverses

@@ -562,6 +562,20 @@ void launch_sparse_close(double* B, int64_t ld, int64_t mpad, int k, double* sca
 // var[i] = (sf2 - |V1[i]|^2) + |V2[i]|^2 + add over ncols columns, i < m
 void launch_sparse_var(const double* V1, const double* V2, int64_t ld, int64_t m, int64_t ncols, double sf2, double add,
                        double* var, hipStream_t st);
+// The rectangular derivative contraction of the bound's gradient: acc[t] += sum_{n < na, i < nb} W[n][i] r_n (dK / dlog
+// theta_t)(As_n, Bs_i) for theta = (lengthscale[0..n_ls), sf2), r_n = 1 / sqrt(rsn2 rw[n]) (rw null: 1 / sqrt(rsn2); rsn2 = 1
+// without rw: W as it is).  W (napad x ldw, ldw even, rows 16-byte aligned) is readable over napad x nbpad (multiples of 64)
+// and may hold anything beyond na x nb; As (napad x d) and Bs (nbpad x d) are scaled points.  part: cross_dtheta_part_elems
+// elements, one partial per (64-tile, theta), summed in tile order: two calls agree bit for bit.
+int64_t cross_dtheta_part_elems(int64_t rows_pad, int64_t cols_pad, int n_ls);
+void launch_cross_dtheta(int kernel, const double* W, int64_t ldw, int64_t na, int64_t napad, int64_t nb, int64_t nbpad,
+                         const double* As, const double* Bs, int d, int n_ls, double sf2, const double* rw, double rsn2,
+                         double* part, double* acc, hipStream_t st);
+// H (in: B^-1) and M (in: B), both mpad x mpad at ld, become H = k (I - B^-1) - ch ch^T and M = H - k (B - I); chT (k rows, ld)
+void launch_sparse_grad_weights(double* H, double* M, int64_t ld, int64_t mpad, const double* chT, int k, hipStream_t st);
+// out[0] = trace of Binv over its mpad rows, out[1] = sum of squares of the k rows of chT over mpad columns
+void launch_sparse_grad_scalars(const double* Binv, int64_t ld, int64_t mpad, const double* chT, int k, double* out,
+                                hipStream_t st);
 
 // ---- removal of observations (gpx_update.hip) -----------------------------------
 constexpr int UPD_W = 64;  // panel width of the rank-m update of the trailing factor = most columns m one pass removes

@@ -14,6 +14,17 @@
 // Determinism: one workgroup owns one (tile, split) pair and walks its rows in ascending order; the splits of a tile are
 // summed in split order by a second launch.  The number of splits is a function of (n, rows_nominal) only — for a fit: of
 // (m, chunk) — never of the device, the free memory or the number of valid rows.  No atomics.
+//
+// The gradient of the bound (gpx_sparse_elbo_grad) adds the rectangular derivative contraction, cross_dtheta_kernel:
+//   part[tile][t] = sum over a 64 x 64 tile of  W[n][i] r_n (dK / dlog theta_t)(a_n, b_i),   theta = (lengthscales..., sf2)
+// with the weights LOADED from a row-major matrix W (one read of rows x cols doubles: the kernel is bound by that read) and
+// dK regenerated from the two staged point sets exactly as alpha_quad_kernel (gpx_grad.hip) does — without its symmetry
+// factor and its diagonal: the grid is the whole rectangle.  r_n = 1 / sqrt(rsn2 rw_n) is the row scale 1 / s_n of the
+// streamed pass (rw null: 1; rsn2 = 1 and no rw: the weights as they are, exactly).  One partial per (tile, theta) through the
+// workgroup reduction in fixed order; partials_acc_kernel adds a launch's partials onto a device accumulator, launch after
+// launch in chunk order.  Rows >= na and columns >= nb contribute exact zeros whatever W holds there; a coincident pair
+// contributes its finite value (cov::value_kd: Matern-1/2 has kd = 0 at r = 0).
+#include "gpx_cov.h"
 #include "gpx_internal.h"
 
 namespace gpx {
@@ -181,6 +192,141 @@ __global__ __launch_bounds__(256) void transpose_kernel(const double* __restrict
   for (int i = ty; i < 32; i += 8) XT[(c0 + i) * ldt + r0 + tx] = tile[tx][i];
 }
 
+// sum over the 256 threads of a workgroup in a fixed order, every thread gets the result (gpx_grad.hip's wg_sum)
+__device__ __forceinline__ double wg_sum(double v, double* red) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  __syncthreads();  // red[] may still be read from the previous call
+  if (lane == 0) red[wave] = v;
+  __syncthreads();
+  return (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// grid (column tiles, row tiles); As (>= 64 gridDim.y rows) and Bs (>= 64 gridDim.x rows): scaled points, d columns;
+// W readable over the whole padded rectangle, rows 16-byte aligned (ldw even).  part[(by * gridDim.x + bx) * nth + t],
+// nth = (ard ? d : 1) + 1.  D > 0: the dimension at compile time (the LDS image is 64 D doubles per side instead of 64 MAX_D).
+template <int KERNEL, int D>
+__global__ __launch_bounds__(256) void cross_dtheta_kernel(const double* __restrict__ W, int64_t ldw, int64_t na, int64_t nb,
+                                                          const double* __restrict__ As, const double* __restrict__ Bs,
+                                                          int d_rt, int ard, double sf2, const double* __restrict__ rw,
+                                                          double rsn2, double* __restrict__ part) {
+  constexpr int KT = 64, DL = D > 0 ? D : MAX_D;
+  __shared__ double xa[KT * DL];
+  __shared__ double xb[KT * DL];
+  __shared__ double rs[KT];
+  __shared__ double red[4];
+  const int d = (D > 0) ? D : d_rt;
+  const int64_t i0 = (int64_t)blockIdx.y * KT, j0 = (int64_t)blockIdx.x * KT;
+  const int tid = threadIdx.x;
+  for (int e = tid; e < KT * d; e += 256) {
+    xa[e] = As[i0 * d + e];
+    xb[e] = Bs[j0 * d + e];
+  }
+  if (tid < KT) {
+    const int64_t gi = i0 + tid;
+    rs[tid] = gi < na ? 1.0 / sqrt(rsn2 * (rw ? rw[gi] : 1.0)) : 0.0;
+  }
+  __syncthreads();
+  const int jl0 = (tid & 31) * 2, rg = tid >> 5;  // this thread's 8 rows x 2 columns: a wave reads 2 rows x 512 bytes of W
+  const bool c0 = j0 + jl0 < nb, c1 = j0 + jl0 + 1 < nb;
+  double wt[8][2];
+#pragma unroll
+  for (int r = 0; r < 8; ++r) {
+    const int il = rg + 8 * r;
+    const double2 w2 = *reinterpret_cast<const double2*>(W + (i0 + il) * ldw + j0 + jl0);
+    const bool row = i0 + il < na;
+    wt[r][0] = (row && c0) ? w2.x * rs[il] : 0.0;
+    wt[r][1] = (row && c1) ? w2.y * rs[il] : 0.0;
+  }
+  double Sf = 0.0, Sl = 0.0;
+#pragma unroll
+  for (int r = 0; r < 8; ++r) {
+    const int il = rg + 8 * r;
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      const int jl = jl0 + q;
+      double r2 = 0.0;
+      for (int c = 0; c < d; ++c) {
+        const double e = xa[il * d + c] - xb[jl * d + c];
+        r2 += e * e;
+      }
+      double kf, kd;
+      cov::value_kd<KERNEL>(r2, sf2, kf, kd);
+      const double v = wt[r][q];
+      Sf += v * kf;
+      const double t = v * kd;
+      Sl += t * r2;
+      wt[r][q] = t;
+    }
+  }
+  const int nls = ard ? d : 1;
+  double* out = part + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * (nls + 1);
+  if (!ard) {
+    const double s = wg_sum(Sl, red);
+    if (tid == 0) out[0] = s;
+  } else {
+    for (int c = 0; c < d; ++c) {
+      double s = 0.0;
+#pragma unroll
+      for (int r = 0; r < 8; ++r) {
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+          const double e = xa[(rg + 8 * r) * d + c] - xb[(jl0 + q) * d + c];
+          s += wt[r][q] * e * e;
+        }
+      }
+      s = wg_sum(s, red);
+      if (tid == 0) out[c] = s;
+    }
+  }
+  const double sf = wg_sum(Sf, red);
+  if (tid == 0) out[nls] = sf;
+}
+
+// acc[t] += sum_tile part[tile * nth + t]; one workgroup per theta, fixed order (reduce_partials_kernel's, accumulating)
+__global__ __launch_bounds__(256) void partials_acc_kernel(const double* __restrict__ part, int64_t ntile, int nth,
+                                                          double* __restrict__ acc) {
+  __shared__ double red[4];
+  const int t = blockIdx.x;
+  double s = 0.0;
+  for (int64_t i = threadIdx.x; i < ntile; i += 256) s += part[i * nth + t];
+  s = wg_sum(s, red);
+  if (threadIdx.x == 0) acc[t] += s;
+}
+
+// The two m x m weights of the gradient from B^-1 (in H), the rebuilt B = LB LB^T (in M) and ch^T (64 rows, ld):
+//   H = kk (I - B^-1) - ch ch^T        M = H - kk (B - I)  =  kk (2 I - B^-1 - B) - ch ch^T
+// element by element over the padded square (padded rows and columns of both come out exactly zero: B = B^-1 = I, ch = 0 there)
+__global__ __launch_bounds__(256) void sparse_grad_weights_kernel(double* __restrict__ H, double* __restrict__ M, int64_t ld,
+                                                                 int64_t mpad, const double* __restrict__ chT, int k) {
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= mpad * mpad) return;
+  const int64_t i = e / mpad, j = e - i * mpad;
+  const double kk = (double)k, dij = i == j ? 1.0 : 0.0;
+  double cc = 0.0;
+  for (int c = 0; c < k; ++c) cc += chT[c * ld + i] * chT[c * ld + j];
+  const double h = kk * (dij - H[i * ld + j]) - cc;
+  H[i * ld + j] = h;
+  M[i * ld + j] = h - kk * (M[i * ld + j] - dij);
+}
+
+// one workgroup, fixed trees: out[0] = trace of Binv over mpad (a padded row adds exactly 1), out[1] = sum over the k rows
+// of chT of their squares
+__global__ __launch_bounds__(256) void sparse_grad_scalars_kernel(const double* __restrict__ Binv, int64_t ld, int64_t mpad,
+                                                                 const double* __restrict__ chT, int k,
+                                                                 double* __restrict__ out) {
+  __shared__ double red[4];
+  double tr = 0.0, ss = 0.0;
+  for (int64_t j = threadIdx.x; j < mpad; j += 256) {
+    tr += Binv[j * ld + j];
+    for (int c = 0; c < k; ++c) ss += chT[c * ld + j] * chT[c * ld + j];
+  }
+  tr = wg_sum(tr, red);
+  ss = wg_sum(ss, red);
+  if (threadIdx.x == 0) out[0] = tr, out[1] = ss;
+}
+
 }  // namespace
 
 int syrk_tn_splits(int64_t n, int64_t rows_nominal) {
@@ -223,6 +369,36 @@ void launch_sparse_close(double* B, int64_t ld, int64_t mpad, int k, double* sca
 void launch_sparse_var(const double* V1, const double* V2, int64_t ld, int64_t m, int64_t ncols, double sf2, double add,
                        double* var, hipStream_t st) {
   hipLaunchKernelGGL(sparse_var_kernel, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, st, V1, V2, ld, m, ncols, sf2, add, var);
+}
+
+int64_t cross_dtheta_part_elems(int64_t rows_pad, int64_t cols_pad, int n_ls) {
+  return (rows_pad / 64) * (cols_pad / 64) * (n_ls + 1);
+}
+
+void launch_cross_dtheta(int kernel, const double* W, int64_t ldw, int64_t na, int64_t napad, int64_t nb, int64_t nbpad,
+                         const double* As, const double* Bs, int d, int n_ls, double sf2, const double* rw, double rsn2,
+                         double* part, double* acc, hipStream_t st) {
+  const dim3 grid((unsigned)(nbpad / 64), (unsigned)(napad / 64)), block(256);
+  const int ard = n_ls > 1;
+  cov::dispatch(kernel, [&](auto fam) {
+    if (d == 1)
+      hipLaunchKernelGGL((cross_dtheta_kernel<fam, 1>), grid, block, 0, st, W, ldw, na, nb, As, Bs, d, ard, sf2, rw, rsn2, part);
+    else if (d == 3)
+      hipLaunchKernelGGL((cross_dtheta_kernel<fam, 3>), grid, block, 0, st, W, ldw, na, nb, As, Bs, d, ard, sf2, rw, rsn2, part);
+    else
+      hipLaunchKernelGGL((cross_dtheta_kernel<fam, 0>), grid, block, 0, st, W, ldw, na, nb, As, Bs, d, ard, sf2, rw, rsn2, part);
+  });
+  hipLaunchKernelGGL(partials_acc_kernel, dim3((unsigned)(n_ls + 1)), dim3(256), 0, st, (const double*)part,
+                     (napad / 64) * (nbpad / 64), n_ls + 1, acc);
+}
+
+void launch_sparse_grad_weights(double* H, double* M, int64_t ld, int64_t mpad, const double* chT, int k, hipStream_t st) {
+  hipLaunchKernelGGL(sparse_grad_weights_kernel, dim3((unsigned)(mpad * mpad / 256)), dim3(256), 0, st, H, M, ld, mpad, chT, k);
+}
+
+void launch_sparse_grad_scalars(const double* Binv, int64_t ld, int64_t mpad, const double* chT, int k, double* out,
+                                hipStream_t st) {
+  hipLaunchKernelGGL(sparse_grad_scalars_kernel, dim3(1), dim3(256), 0, st, Binv, ld, mpad, chT, k, out);
 }
 
 }  // namespace gpx

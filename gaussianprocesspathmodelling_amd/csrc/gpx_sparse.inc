@@ -72,7 +72,7 @@ int sparse_fit_impl(gpx_handle* h, const void* X, const void* y, const void* w, 
     }
   }
   sp.fitted = false;
-  sp.N = N, sp.m = m, sp.mpad = mpad, sp.chunk = C, sp.ld = ld;
+  sp.N = N, sp.m = m, sp.mpad = mpad, sp.chunk = C, sp.ld = ld, sp.sum_inv_s2 = sum_inv_s2;
   h->N = N, h->d = d, h->k = k, h->n_ls = n_ls, h->sf2 = sf2, h->sn2 = sn2, h->jitter = jitter;
   gpx_timings& tm = h->tm;
   tm.h2d = tm.kbuild = tm.chol = tm.solve = tm.logdet = tm.fit_total = 0;
@@ -302,6 +302,120 @@ int sparse_predict_cov_impl(gpx_handle* h, const void* Xq, int64_t M, void* mean
   return finish_call(h);
 }
 
+// The gradient of the bound F = sum_c ELBO_c by the log parameters (lengthscales..., sf2, sn2) of the handle's fit
+// (DESIGN.md §3.4r "The gradient of the bound").  With ch = LB^-T c,  H = k (I - B^-1) - ch ch^T  and
+// M = k (2 I - B^-1 - B) - ch ch^T:   dF / dKuf^T = T with rows t_n = L^-T (H a_n + ch yt_n^T) / s_n,   dF / dKuu = Guu =
+// 1/2 L^-T M L^-1.  Stage 1, O(m^3), all on the tile engine: LB^-T and L^-T by trtri_enqueue, B^-1 = LB^-T LB^-1 and the
+// rebuilt B = LB LB^T (the fit's own B was overwritten by its factor, and the fit is not touched), H' = L^-T [H | ch] and
+// 2 Guu = (L^-T M) L^-1 as NT products.  Stage 2 streams the observations once more in the fit's own chunks with the fit's
+// own launches up to the whitened bordered rows [a_n^T | yt_n^T], forms T = rows H'^T in one NT product per chunk — the ch
+// yt^T term rides in the 64 border columns — and contracts T r_n against dKfu / dtheta (launch_cross_dtheta).  The noise
+// entry needs no pass: it is a sum of scalars.  Only scratch and the fit's chunk buffers are written: the fit stays as it is.
+int sparse_grad_impl(gpx_handle* h, const void* X, const void* y, const void* w, int32_t mem_kind, double* elbo, double* grad) {
+  gpx_handle::Sparse& sp = h->sp;
+  gpx_handle::ScratchBufs& sc = h->scr;
+  const int64_t N = sp.N, m = sp.m, mpad = sp.mpad, nb_ = mpad + RHS_ROWS, ld = sp.ld, C = sp.chunk;
+  const int64_t cb = std::min(C, round_up(N, TILE));
+  const int d = h->d, k = h->k, n_ls = h->n_ls, nth = n_ls + 1, kernel = h->cfg.kernel;
+  const double sf2 = h->sf2, sn2 = h->sn2;
+  const int64_t npart = std::max(cross_dtheta_part_elems(cb, mpad, n_ls), cross_dtheta_part_elems(mpad, mpad, n_ls));
+  const size_t tail = (size_t)(2 * nth + 2);  // behind the partials: the sums of the Kfu term, of the Kuu term, tr B^-1, |ch|^2
+  int rc;
+  {  // one more chunk buffer and the m x m temporaries, against what is free plus what the handle holds of them already
+    const double need = 8.0 * ((double)nb_ * ld + 4.0 * mpad * ld + (double)cb * ld + (double)npart + (double)tail +
+                               (double)cb * (2 * d + k + 1)) + 4096;
+    const double have = (double)sc.SGH.cap + sc.SGZ.cap + sc.SGM.cap + sc.SGZL.cap + sc.SGHp.cap + sc.SGT.cap + sc.SGpart.cap +
+                        sp.Xc.cap + sp.Xsc.cap + sp.Yc.cap + sp.Wc.cap;
+    size_t freeb = 0, totalb = 0;
+    HIPCHK(h, hipMemGetInfo(&freeb, &totalb));
+    if (need > (double)freeb + have) {
+      char buf[256];
+      snprintf(buf, sizeof buf, "gpx_sparse_elbo_grad: m = %lld inducing points with chunks of %lld rows need %.3f GB more of "
+               "device memory, %.3f GB are free", (long long)m, (long long)cb, need / 1e9, ((double)freeb + have) / 1e9);
+      return fail(h, GPX_E_NOMEM, buf);
+    }
+  }
+  if ((rc = ensure(h, sc.SGH, (size_t)nb_ * ld * 8)) || (rc = ensure(h, sc.SGZ, (size_t)mpad * ld * 8)) ||
+      (rc = ensure(h, sc.SGM, (size_t)mpad * ld * 8)) || (rc = ensure(h, sc.SGZL, (size_t)mpad * ld * 8)) ||
+      (rc = ensure(h, sc.SGHp, (size_t)mpad * ld * 8)) || (rc = ensure(h, sc.SGT, (size_t)cb * ld * 8)) ||
+      (rc = ensure(h, sc.SGpart, ((size_t)npart + tail) * 8)))
+    return rc;
+  if ((rc = ensure(h, sp.Xc, (size_t)cb * d * 8)) || (rc = ensure(h, sp.Xsc, (size_t)cb * d * 8)) ||
+      (rc = ensure(h, sp.Yc, (size_t)cb * k * 8)) || (w && (rc = ensure(h, sp.Wc, (size_t)cb * 8))))
+    return rc;
+  double* GH = (double*)sc.SGH.p;    // [H | ch^T]: mpad rows of B^-1, then H; ch^T in the 64 rows below
+  double* GZ = (double*)sc.SGZ.p;    // LB^-T, then LB with a zero upper triangle, then L^-T M
+  double* GM = (double*)sc.SGM.p;    // B rebuilt, then M, then 2 Guu
+  double* GZL = (double*)sc.SGZL.p;  // L^-T
+  double* GHp = (double*)sc.SGHp.p;  // H' = L^-T [H | ch] (mpad x nb_)
+  double* GT = (double*)sc.SGT.p;    // T of one chunk
+  double* part = (double*)sc.SGpart.p;
+  double* accx = part + npart;
+  double* accu = accx + nth;
+  double* gsc = accu + nth;
+  double* chT = GH + mpad * ld;
+  const double* dL = (const double*)sp.L.p;
+  const double* dB = (const double*)sp.B.p;
+  const double* dZs = (const double*)sp.Zs.p;
+  double* dKc = (double*)sp.Kc.p;
+  gpx_timings& tm = h->tm;
+  tm.grad_trtri = tm.grad_trace = tm.grad_total = 0;
+  hipStream_t st = h->st;
+  {
+    PhaseScope total(h, &tm.grad_total);
+    {
+      PhaseScope ps(h, &tm.grad_trtri);
+      HIPCHK(h, hipMemsetAsync(accx, 0, tail * 8, st));
+      HIPCHK(h, hipMemsetAsync(GZ, 0, (size_t)mpad * ld * 8, st));
+      launch_set_diag_one(GZ, ld, mpad, st);
+      if ((rc = trtri_enqueue(h, GZ, dB, ld, mpad, SP_NB, (const double*)sp.WinvB.p, 1, 0))) return rc;
+      HIPCHK(h, hipMemsetAsync(GH, 0, (size_t)nb_ * ld * 8, st));
+      launch_gemm_nt<double>(64, chT, ld, dB + mpad * ld, ld, GZ, ld, RHS_ROWS, mpad, mpad, 0, 1, st);  // ch^T = c^T LB^-1
+      launch_gemm_nt<double>(128, GH, ld, GZ, ld, GZ, ld, mpad, mpad, mpad, 0, 1, st);                  // B^-1
+      launch_sparse_grad_scalars(GH, ld, mpad, chT, k, gsc, st);
+      launch_copy_lower<double>(GZ, ld, dB, ld, mpad, st);
+      launch_mirror_lower<double>(GZ, ld, mpad, 1, st);
+      launch_gemm_nt<double>(128, GM, ld, GZ, ld, GZ, ld, mpad, mpad, mpad, 0, 1, st);  // B = LB LB^T
+      launch_sparse_grad_weights(GH, GM, ld, mpad, chT, k, st);
+      HIPCHK(h, hipMemsetAsync(GZL, 0, (size_t)mpad * ld * 8, st));
+      launch_set_diag_one(GZL, ld, mpad, st);
+      if ((rc = trtri_enqueue(h, GZL, dL, ld, mpad, SP_NB, (const double*)sp.WinvL.p, 1, 0))) return rc;
+      launch_gemm_nt<double>(64, GHp, ld, GZL, ld, GH, ld, mpad, nb_, mpad, 0, 1, st);
+      launch_gemm_nt<double>(128, GZ, ld, GZL, ld, GM, ld, mpad, mpad, mpad, 0, 1, st);  // L^-T M (M is symmetric)
+      launch_gemm_nt<double>(128, GM, ld, GZ, ld, GZL, ld, mpad, mpad, mpad, 0, 1, st);  // 2 Guu
+      launch_cross_dtheta(kernel, GM, ld, m, mpad, m, mpad, dZs, dZs, d, n_ls, sf2, nullptr, 1.0, part, accu, st);
+    }
+    PhaseScope ps(h, &tm.grad_trace);
+    for (int64_t c0 = 0; c0 < N; c0 += C) {  // the fit's chunks, the fit's launches up to the whitened rows
+      const int64_t rows = std::min(C, N - c0), rp = round_up(rows, TILE);
+      if ((rc = copy_in(h, sp.Xc.p, (const double*)X + c0 * d, (size_t)rows * d * 8, mem_kind))) return rc;
+      if ((rc = copy_in(h, sp.Yc.p, (const double*)y + c0 * k, (size_t)rows * k * 8, mem_kind))) return rc;
+      if (w && (rc = copy_in(h, sp.Wc.p, (const double*)w + c0, (size_t)rows * 8, mem_kind))) return rc;
+      launch_scale_points<double>((const double*)sp.Xc.p, rows, rp, d, (const double*)h->ls.p, n_ls, (double*)sp.Xsc.p, st);
+      launch_kbuild_cross<double>(kernel, (const double*)sp.Xsc.p, rows, rp, dZs, m, mpad, d, sf2, dKc, ld, st);
+      launch_sparse_border(dKc, ld, rows, rp, mpad, (const double*)sp.Yc.p, k, w ? (const double*)sp.Wc.p : nullptr, sn2, st);
+      if ((rc = solve_fwd_enqueue<double>(h, dKc, rp, dL, ld, mpad, SP_NB, (const double*)sp.WinvL.p))) return rc;
+      launch_gemm_nt<double>(128, GT, ld, dKc, ld, GHp, ld, rp, mpad, nb_, 0, 1, st);
+      launch_cross_dtheta(kernel, GT, ld, rows, rp, m, mpad, (const double*)sp.Xsc.p, dZs, d, n_ls, sf2,
+                          w ? (const double*)sp.Wc.p : nullptr, sn2, part, accx, st);
+    }
+  }
+  double scal[32], sums[2 * (MAX_D + 1) + 2];
+  HIPCHK(h, hipMemcpyAsync(scal, sp.scal.p, sizeof scal, hipMemcpyDeviceToHost, st));
+  HIPCHK(h, hipMemcpyAsync(sums, accx, tail * 8, hipMemcpyDeviceToHost, st));
+  if ((rc = finish_call(h))) return rc;
+  const double kk = (double)k, inv = sp.sum_inv_s2;
+  double yy = 0.0, cc = 0.0;
+  for (int c = 0; c < k; ++c) yy += scal[1 + c], cc += scal[17 + c];
+  for (int t = 0; t < nth; ++t) grad[t] = sums[t] + 0.5 * sums[nth + t];
+  grad[n_ls] -= 0.5 * kk * sf2 * inv;
+  const double trBinv_pad = sums[2 * nth], chch = sums[2 * nth + 1];  // (the mpad - m padded rows of B^-1 add one each)
+  grad[n_ls + 1] = 0.5 * kk * ((double)mpad - trBinv_pad) - 0.5 * kk * (double)N + 0.5 * yy - cc + 0.5 * (cc - chch) +
+                   0.5 * kk * sf2 * inv - 0.5 * kk * scal[0];
+  if (elbo) std::copy(sp.elbo, sp.elbo + k, elbo);
+  return GPX_OK;
+}
+
 }  // namespace
 }  // extern "C++"
 
@@ -401,6 +515,43 @@ int gpx_sparse_info(gpx_handle* h, int64_t* N, int64_t* m, int64_t* k, int64_t* 
 }
 GPX_CATCH_ALL
 
+int gpx_sparse_elbo_grad(gpx_handle* h, const void* X, const void* y, const void* w, int64_t N, int32_t mem_kind, double* elbo,
+                         double* grad) try {
+  const char* fn = "gpx_sparse_elbo_grad";
+  if (!h) return GPX_E_ARG;
+  int rc;
+  if ((rc = sparse_handle_refused(h, fn)) || (rc = sparse_unfitted(h, fn))) return rc;
+  if (!X || !y || !grad) return fail(h, GPX_E_ARG, fn, "null argument");
+  if (bad_mem_kind(mem_kind)) return fail(h, GPX_E_ARG, fn, "bad mem_kind");
+  if (N != h->sp.N) return fail(h, GPX_E_ARG, fn, "N differs from the fit's: pass the observations the handle was fitted to");
+  if ((rc = begin_call(h))) return rc;
+  return sparse_grad_impl(h, X, y, w, mem_kind, elbo, grad);
+}
+GPX_CATCH_ALL
+
+int gpx_cross_dtheta_contract(int32_t kernel, const double* A, int64_t na, const double* B, int64_t nb_, int32_t d,
+                              const double* W, const double* lengthscale, int32_t n_ls, double sf2, double* out) try {
+  if (!A || !B || !W || !out || !lengthscale || !sizes_ok(na, nb_, d, n_ls) || !cov::known(kernel)) return GPX_E_ARG;
+  if (na > ((int64_t)1 << 20) || nb_ > ((int64_t)1 << 20) || round_up(na, 64) * round_up(nb_, 64) > ((int64_t)1 << 28))
+    return GPX_E_ARG;
+  KernelCall<double> kc;
+  if (int rc = kc.points(A, na, B, nb_, d, lengthscale, n_ls)) return rc;
+  const int64_t ldw = kc.nbpad, npart = cross_dtheta_part_elems(kc.napad, kc.nbpad, n_ls);
+  Dev<double> dW, dPart;
+  if (int rc; (rc = dW.alloc((size_t)kc.napad * ldw)) || (rc = dPart.alloc((size_t)npart + n_ls + 1))) return rc;
+  double* acc = dPart + npart;
+  UCHK(hipMemsetAsync(dW, 0, (size_t)kc.napad * ldw * 8, kc.st));
+  UCHK(hipMemsetAsync(acc, 0, (size_t)(n_ls + 1) * 8, kc.st));
+  UCHK(hipMemcpy2DAsync(dW, (size_t)ldw * 8, W, (size_t)nb_ * 8, (size_t)nb_ * 8, (size_t)na, hipMemcpyHostToDevice, kc.st));
+  launch_cross_dtheta(kernel, dW, ldw, na, kc.napad, nb_, kc.nbpad, kc.As, kc.Bs, d, n_ls, sf2, nullptr, 1.0, dPart, acc, kc.st);
+  std::vector<double> res((size_t)n_ls + 1);
+  UCHK(hipMemcpyAsync(res.data(), acc, res.size() * 8, hipMemcpyDeviceToHost, kc.st));
+  if (int rc = kc.sc.finish()) return rc;
+  std::copy(res.begin(), res.end(), out);
+  return GPX_OK;
+}
+GPX_CATCH_ALL
+
 int gpx_syrk_tn(double* C, int64_t n, const double* X, int64_t rows, int32_t accumulate) try {
   if (!C || !X || n <= 0 || n % 64 != 0 || n > 16384 || rows <= 0 || rows > ((int64_t)1 << 24)) return GPX_E_ARG;
   Scratch sc;
@@ -446,6 +597,42 @@ int gpx_debug_syrk_tn_bench(int64_t n, int64_t rows, int32_t route, int32_t iter
     }
     if (route == 1) launch_transpose(dX, ldx, rows, n, dXT, ldt, sc.st);
     launch_gemm_nt_fixed<double>(128, dC, ldc, dXT, ldt, dXT, ldt, n, n, rows, 1, 0, sc.st);
+  };
+  once();
+  UCHK(hipEventRecord(e0, sc.st));
+  for (int i = 0; i < iters; ++i) once();
+  UCHK(hipEventRecord(e1, sc.st));
+  if (int rc = sc.finish()) return rc;
+  UCHK(hipEventElapsedTime(&t, e0, e1));
+  *ms_per_call = (double)t / iters;
+  return GPX_OK;
+}
+GPX_CATCH_ALL
+
+// The derivative contraction of the bound's gradient alone, operands resident and zero-filled: W (rows x cols at the fit's
+// leading dimension cols + 64 + skew) against rows x cols points of d dimensions, n_ls lengthscales, `iters` back-to-back
+// repeats after one warm-up; *ms = mean time of one (the kernel and its reduction).  rows, cols multiples of 64.
+int gpx_debug_cross_dtheta_bench(int32_t kernel, int64_t rows, int64_t cols, int32_t d, int32_t n_ls, int32_t iters,
+                                 double* ms_per_call) try {
+  if (!ms_per_call || !cov::known(kernel) || !sizes_ok(rows, cols, d, n_ls) || rows % 64 || cols % 64 || rows > ((int64_t)1 << 22) ||
+      cols > 65536 || iters <= 0)
+    return GPX_E_ARG;
+  Scratch sc;
+  if (!sc.ok) return GPX_E_HIP;
+  const int64_t ldw = cols + RHS_ROWS + LD_SKEW, npart = cross_dtheta_part_elems(rows, cols, n_ls);
+  Dev<double> dW, dA, dB, dPart;
+  float t = 0.f;
+  if (int rc; (rc = dW.alloc((size_t)rows * ldw)) || (rc = dA.alloc((size_t)rows * d)) || (rc = dB.alloc((size_t)cols * d)) ||
+              (rc = dPart.alloc((size_t)npart + n_ls + 1)))
+    return rc;
+  UCHK(hipMemsetAsync(dW, 0, (size_t)rows * ldw * 8, sc.st));
+  UCHK(hipMemsetAsync(dA, 0, (size_t)rows * d * 8, sc.st));
+  UCHK(hipMemsetAsync(dB, 0, (size_t)cols * d * 8, sc.st));
+  UCHK(hipMemsetAsync(dPart, 0, ((size_t)npart + n_ls + 1) * 8, sc.st));
+  hipEvent_t e0 = next_event(&sc.h), e1 = next_event(&sc.h);
+  if (!e0 || !e1) return fail(nullptr, GPX_E_HIP, "hipEventCreate failed");
+  auto once = [&] {
+    launch_cross_dtheta(kernel, dW, ldw, rows, rows, cols, cols, dA, dB, d, n_ls, 1.0, nullptr, 1.0, dPart, dPart + npart, sc.st);
   };
   once();
   UCHK(hipEventRecord(e0, sc.st));

@@ -13,9 +13,14 @@ on a shared 33-step grid with ``Z`` = the grid and ``jitter=0``: mean to 2.5e-13
 ``jitter`` goes on the diagonal of ``Kuu`` only.  It is a (tiny) change of the MODEL, not of the noise: on that grid
 ``jitter=1e-6`` already moves the variance by 9e-4 relative.  The default is ``1e-8 * variance``.
 
-Not part of this class (out of scope of the first version): the gradient of the bound and an ``optimize``, float32 /
-mixed precision, shards and device groups, derivative observations, path ids, basis functions, and update / remove / loo
-on a sparse fit.  There is no CPU fallback.
+The hyperparameters are learnt on the bound itself: ``elbo_gradient()`` is its analytic gradient by the log lengthscales,
+log variance and log noise on the GPU (one more streamed pass over the observations, which ``fit`` therefore keeps
+references to), and ``optimize`` runs L-BFGS-B on it with ``Z`` fixed.  Learning them on a subsample with the dense ``GP``
+optimises another objective: the bound has a trace term the marginal likelihood lacks.
+
+Not part of this class: the gradient with respect to the inducing locations ``Z``, float32 / mixed precision, shards and
+device groups, derivative observations, path ids, basis functions, and update / remove / loo on a sparse fit.  There is no
+CPU fallback.
 """
 from __future__ import annotations
 
@@ -47,7 +52,8 @@ def choose_inducing(X, m, random_state=0):
 
 
 class SparseGP:
-    """``SparseGP(kernel, lengthscale, variance, noise, jitter=None, device=None, chunk=None)``: fit, predict, ``elbo``.
+    """``SparseGP(kernel, lengthscale, variance, noise, jitter=None, device=None, chunk=None)``: fit, predict, ``elbo``,
+    ``elbo_gradient``, ``optimize``.
 
     kernel : "rbf" | "matern52" | "matern32" | "matern12"
     lengthscale : scalar (isotropic) or (d,) array (ARD)
@@ -67,6 +73,7 @@ class SparseGP:
         self.variance, self.noise = float(variance), float(noise)
         if not self.variance > 0 or not self.noise > 0:
             raise ValueError("need variance > 0 and noise > 0")
+        self._jitter_default = jitter is None   # optimize() re-derives the default from the variance it learns
         self.jitter = 1e-8 * self.variance if jitter is None else float(jitter)
         if self.jitter < 0:
             raise ValueError("need jitter >= 0")
@@ -86,6 +93,7 @@ class SparseGP:
             raise _abi.GpxError(rc, self._lib.gpx_last_error(None).decode())
         self._h = h
         self._fitted = False
+        self._obs = None
         self.info_ = 0
         self.inducing_ = None
 
@@ -185,7 +193,7 @@ class SparseGP:
         zin = self._like(Z, dev)
         info = C.c_int64(0)
         ls = self.lengthscale
-        self._fitted = False
+        self._fitted, self._obs = False, None
         self._check(self._lib.gpx_sparse_fit(self._h, px, py, pw, N, d, k, self._ptr(zin), Z.shape[0], _abi.dptr(ls), ls.size,
                                              self.variance, self.noise, self.jitter, self.chunk, kind, C.byref(info)))
         self.info_ = int(info.value)
@@ -195,6 +203,7 @@ class SparseGP:
                                         "identical inducing points need jitter > 0")
         self.inducing_ = self._like(Z, dev)
         self._d, self._k, self._N = d, k, N
+        self._obs = (px, py, pw, kind, (keepx, keepy, keepw))   # references, not copies: elbo_gradient() streams them again
         self._fitted = True
         return self
 
@@ -235,6 +244,93 @@ class SparseGP:
         out = np.empty(self._k, dtype=np.float64)
         self._check(self._lib.gpx_sparse_elbo(self._h, _abi.dptr(out)))
         return out
+
+    def elbo_gradient(self):
+        """``(elbo().sum(), grad)``: the bound summed over the target columns and its gradient by the LOG parameters,
+        ``grad`` (n_ls + 2,) float64 NumPy ordered as ``GP.lml_gradient``'s: the lengthscales, ``variance``, ``noise``.
+        ``Z`` and ``jitter`` are constants.  Analytic, on the GPU: an O(m^3) stage and one more streamed pass over the
+        observations ``fit`` was given — ``fit`` keeps references to them, not copies, so they must not have been
+        changed in place since.  The fit is left as it is: ``predict`` afterwards returns the same bits."""
+        if not self._fitted:
+            raise RuntimeError("elbo_gradient() before a successful fit()")
+        px, py, pw, kind, _ = self._obs
+        elbo = np.empty(self._k, dtype=np.float64)
+        grad = np.empty(self.lengthscale.size + 2, dtype=np.float64)
+        self._check(self._lib.gpx_sparse_elbo_grad(self._h, px, py, pw, self._N, kind, _abi.dptr(elbo), _abi.dptr(grad)))
+        return float(elbo.sum()), grad
+
+    def optimize(self, X, y, inducing, params=("lengthscale", "variance", "noise"), bounds=(1e-4, 1e4), maxiter=40,
+                 jac="analytic", noise_weights=None, random_state=0):
+        """Learn the hyperparameters by maximising the bound ``elbo().sum()`` with L-BFGS-B in log space (the shape of
+        ``GP.optimize``).  ``params`` chooses what moves ("lengthscale" moves every ARD entry).  An int ``inducing`` is
+        resolved to ``Z`` once, as :meth:`fit` does, and ``Z`` then stays fixed through the search.  ``jac="analytic"``:
+        every evaluation is one ``fit`` and one ``elbo_gradient`` on the GPU; ``jac="3-point"``: central differences of
+        the bound, 2 p extra fits per gradient.  A trial point whose factorisation fails counts as very bad, it does
+        not raise.  A ``jitter`` left at None in the constructor is re-derived as ``1e-8 * variance`` at every point; one
+        that was given stays.  Leaves the model fitted at the best point found, with ``lengthscale``, ``variance`` and
+        ``noise`` updated, and returns scipy's result with ``.fun == -elbo().sum()`` there."""
+        from scipy.optimize import minimize
+        known = ("lengthscale", "variance", "noise")
+        names = [p for p in known if p in params]
+        if not names or len(names) != len(tuple(params)):
+            raise ValueError("params must be a non-empty subset of " + " / ".join(known))
+        if jac not in ("analytic", "3-point"):
+            raise ValueError('jac must be "analytic" or "3-point"')
+        if isinstance(inducing, (int, np.integer)):
+            Xh = X.detach().cpu().numpy() if _is_torch(X) else np.asarray(X, dtype=np.float64)
+            inducing = choose_inducing(Xh, int(inducing), random_state)
+        n_ls = self.lengthscale.size
+        cols = []
+        for p in names:
+            cols.extend(range(n_ls) if p == "lengthscale" else [n_ls + ("variance", "noise").index(p)])
+        analytic = jac == "analytic"
+
+        def pack():
+            v = []
+            for p in names:
+                v.extend(np.log(self.lengthscale) if p == "lengthscale" else [np.log(max(getattr(self, p), bounds[0]))])
+            return np.asarray(v, dtype=np.float64)
+
+        def unpack(v):
+            i = 0
+            for p in names:
+                if p == "lengthscale":
+                    self.lengthscale = np.exp(v[i:i + n_ls])
+                    i += n_ls
+                else:
+                    setattr(self, p, float(np.exp(v[i])))
+                    i += 1
+            if self._jitter_default:
+                self.jitter = 1e-8 * self.variance
+
+        best = {"f": np.inf, "v": pack()}
+
+        def objective(v):
+            unpack(v)
+            g = np.zeros(len(cols))
+            try:
+                self.fit(X, y, inducing, noise_weights=noise_weights)
+                if analytic:
+                    f, full = self.elbo_gradient()
+                    f, g = -f, -full[cols]
+                else:
+                    f = -float(self.elbo().sum())
+            except np.linalg.LinAlgError:
+                f = 1e300
+            if not np.isfinite(f) or not np.all(np.isfinite(g)):
+                f, g = 1e300, np.zeros(len(cols))
+            if f < best["f"]:
+                best["f"], best["v"] = f, np.array(v, copy=True)
+            return (f, g) if analytic else f
+
+        v0 = pack()
+        lo, hi = np.log(bounds[0]), np.log(bounds[1])
+        res = minimize(objective, v0, method="L-BFGS-B", jac=True if analytic else "3-point", bounds=[(lo, hi)] * v0.size,
+                       options={"maxiter": int(maxiter)} if analytic else {"maxiter": int(maxiter), "eps": 1e-4})
+        unpack(best["v"])
+        self.fit(X, y, inducing, noise_weights=noise_weights)
+        res.x, res.fun = best["v"], -float(self.elbo().sum())
+        return res
 
     @property
     def chunk_(self):

@@ -599,9 +599,26 @@ int gpx_pathwise_info(gpx_handle* h, int64_t* S, int64_t* F, int64_t* n_normals)
  * A handle holds a dense fit or a sparse fit, never both: either fit call replaces the other state, every other dense entry
  * point refuses a sparse-fitted handle with GPX_E_ARG (gpx_last_error names gpx_sparse_*), and the sparse entry points refuse
  * a dense-fitted handle the same way; the existing fit stays valid.  Not available on a sparse fit: the gradient of the
- * bound, update / remove / loo, derivative observations, path ids, basis functions.
+ * bound with respect to Z, update / remove / loo, derivative observations, path ids, basis functions.
  * Timings: kbuild (Kuu and the chunks' cross-kernel rows), chol (both factorisations), solve (whitening and contraction),
- * logdet, fit_total; kstar, trsm, mean, var, d2h, predict_total. */
+ * logdet, fit_total; kstar, trsm, mean, var, d2h, predict_total.
+ *
+ * gpx_sparse_elbo_grad: grad (n_ls + 2) = the gradient of F = sum_c ELBO_c by the LOG parameters, ordered as gpx_lml_grad's
+ * (lengthscale[0..n_ls), sf2, sn2); elbo (k; may be NULL) = gpx_sparse_elbo's values.  Z and jitter are constants.  With
+ *   ch = LB^-T c,   H = k (I - B^-1) - ch ch^T,   Guu = 1/2 L^-T [k (2 I - B^-1 - B) - ch ch^T] L^-1,
+ *   t_n = L^-T (H a_n + ch yt_n^T) / s_n   (a_n: column n of A; row n of T = dF / dKuf^T):
+ *   dF/dlog l_c = sum T . dKfu/dlog l_c + sum Guu . dKuu/dlog l_c          (dk/dlog l_c = kd ((x_c - z_c) / l_c)^2)
+ *   dF/dlog sf2 = sum T . Kfu + sum Guu . sf2 k(Z,Z) - 1/2 k sf2 sum_n 1 / s_n^2
+ *   dF/dlog sn2 = 1/2 k (m - tr B^-1) - 1/2 k N + 1/2 |yt|^2 - |c|^2 + 1/2 (|c|^2 - |ch|^2) + 1/2 k sf2 sum_n 1 / s_n^2
+ *                 - 1/2 k tr(A A^T)
+ * The fit does not keep the observations: the caller passes the X, y, w (and N) of the gpx_sparse_fit the handle holds, in
+ * one memory kind; N != the fit's is GPX_E_ARG, and other data of the same N is the caller's error (the result is then the
+ * gradient of nothing).  The observations stream once more in the fit's chunks; the cost is O(m^3) + one more pass of the
+ * fit's build and whitening + 2 N m^2 flops of one product, the memory five m x m temporaries and one more chunk buffer
+ * (scratch: gpx_release_scratch frees them), checked before anything is allocated (GPX_E_NOMEM).  Refusals as the other
+ * gpx_sparse_* calls.  A call that fails writes neither output; the fit stays valid either way, and a later
+ * gpx_sparse_predict returns the bits it returned before.  Two calls agree bit for bit.  Timings: grad_trtri (the O(m^3)
+ * stage), grad_trace (the streamed pass), grad_total. */
 int gpx_sparse_fit(gpx_handle* h, const void* X, const void* y, const void* w /* (N) or NULL */, int64_t N, int32_t d, int32_t k,
                    const void* Z, int64_t m, const double* lengthscale, int32_t n_ls, double sf2, double sn2, double jitter,
                    int64_t chunk /* 0: library's choice */, int32_t mem_kind, int64_t* info);
@@ -611,6 +628,8 @@ int gpx_sparse_predict_cov(gpx_handle* h, const void* Xs, int64_t M, void* mean 
                            int32_t mem_kind);
 int gpx_sparse_elbo(gpx_handle* h, double* elbo /* (k) */);
 int gpx_sparse_info(gpx_handle* h, int64_t* N, int64_t* m, int64_t* k, int64_t* chunk);
+int gpx_sparse_elbo_grad(gpx_handle* h, const void* X, const void* y, const void* w /* (N) or NULL */, int64_t N,
+                         int32_t mem_kind, double* elbo /* (k) | NULL */, double* grad /* n_ls + 2 */);
 int gpx_logdet(gpx_handle* h, double* out);
 /* Frees what only the NEXT predict / gradient call would use (the V^T batch, the L^-T buffer of
  * gpx_lml_grad, per-tile partials, compact block buffers, the buffers of the joint-posterior calls); the fit itself (factor, alpha, block
@@ -784,6 +803,17 @@ int gpx_syrk_tn(double* C, int64_t n, const double* X, int64_t rows, int32_t acc
  * route 0: the TN kernel as the fit launches it; 1: a transpose of X, then the NT tile engine (128-tiles, lower); 2: that NT
  * launch alone.  n a multiple of 128 (<= 16384), rows a multiple of 64.  tools/sparse_bench.py. */
 int gpx_debug_syrk_tn_bench(int64_t n, int64_t rows, int32_t route, int32_t iters, double* ms_per_call);
+/* The derivative contraction of gpx_sparse_elbo_grad alone (its kernel's unit entry; host buffers, as gpx_kernel_dl_matrix):
+ * out[t] = sum_{i < na, j < nb} W[i][j] (dK / dlog theta_t)(A_i, B_j) for theta = (lengthscale[0..n_ls), sf2), K = sf2 k(A, B);
+ * W (na,nb) row-major, out n_ls + 1 entries.  Two calls agree bit for bit; a coincident pair contributes its finite value. */
+int gpx_cross_dtheta_contract(int32_t kernel, const double* A, int64_t na, const double* B, int64_t nb, int32_t d,
+                              const double* W /* (na, nb) */, const double* lengthscale, int32_t n_ls, double sf2,
+                              double* out /* n_ls + 1 */);
+/* That kernel and its reduction alone on zero-filled resident operands (W at the leading dimension of a fit with m = cols),
+ * `iters` repeats after a warm-up; *ms_per_call = the mean time.  rows (<= 2^22) and cols (<= 65536) multiples of 64.
+ * tools/sparse_grad_bench.py. */
+int gpx_debug_cross_dtheta_bench(int32_t kernel, int64_t rows, int64_t cols, int32_t d, int32_t n_ls, int32_t iters,
+                                 double* ms_per_call);
 /* fp64 MFMA layout probe: D (16,16) = A (16,4) B (4,16) through one
  * v_mfma_f64_16x16x4_f64. */
 int gpx_mfma_probe(const double* A, const double* B, double* D);
