@@ -132,7 +132,13 @@ const char* gpx_last_error(gpx_handle* h); /* h may be NULL: last error of gpx_c
  * precision study; GPX_MIXED: fp32 factorisation + fp64 refinement, k <= 8).  ABI v5: every dtype also on
  * a shard / device group (the row-block shard runs in the handle's element type; the mixed mode's fp64
  * refinement is replicated work on every rank, its fp32 solves local on a replicated factor and collective
- * on a factor that is only held distributed).  lengthscale: n_ls = 1 or d. */
+ * on a factor that is only held distributed).  lengthscale: n_ls = 1 or d.
+ * *info (written when the call returns 0; never negative): 0 = fitted.  p > 0 = K is not positive definite, LAPACK's potrf
+ * convention: p is the 1-based index of the first failing pivot, i.e. the leading minor of order p is the first that is
+ * not positive definite; rows [0, p - 1) of the factor are valid (the factor of the leading minor of order p - 1), nothing
+ * else is, and the handle holds no fit.  A non-finite input row counts as failing: a NaN in row r of X makes pivot r NaN
+ * and *info = r + 1 (with a Strassen level of the two-level schedule on and r right of its split c: c < *info <= r + 1,
+ * DESIGN.md §3.2 item 6). */
 int gpx_fit(gpx_handle* h, const void* X, const void* y, int64_t N, int32_t d, int32_t k,
             const double* lengthscale, int32_t n_ls, double sf2, double sn2, double jitter,
             int32_t mem_kind, int64_t* info);
@@ -788,7 +794,9 @@ int gpx_pathwise_eval_raw(int32_t kernel, int32_t dtype, const double* Xq, int64
                           const double* W /* (C,2F) */, const double* V /* (C,N) */, int64_t C, double* out /* (C,M) */);
 /* in-place lower Cholesky of A (n,n), lda = n; n multiple of 64.  The strictly upper
  * triangle is never read and is scratch on return (diagonal tiles are updated whole).
- * block = panel width (0 = default). */
+ * block = panel width (0 = default).  *info = p > 0: the first failing pivot, 1-based (LAPACK: the leading minor of
+ * order p is the first that is not positive definite; a NaN pivot counts as failing); rows [0, p - 1) of the factor are
+ * valid.  Never negative. */
 int gpx_potrf(double* A, int64_t n, int32_t block, int64_t* info);
 /* X (m,nb) <- X L^-T, L (nb,nb) lower; m, nb multiples of 64. */
 int gpx_trsm(double* X, int64_t m, const double* L, int64_t nb);
